@@ -17,8 +17,16 @@ torch.distributed.run with N ranks (one per GPU, RCCL); it refuses to run when
 fewer than N devices are visible, and a torchrun launch whose WORLD_SIZE differs
 from --gpus is an error, so `n_gpus` in the output is always the rank count that ran.
 
-After the timed region the last batch's first and last CPI are compared with the
-fp64 NumPy oracle (checker only, never timed); a violation exits non-zero.
+A plain run sets up, warms up, times the --steps steps and prints the line.
+`--dump-outputs DIR` also writes what the last timed step computed as DIR/*.npy
+(float32 / float64; the maps of a fixed sample of the batch's CPIs, the metrics
+of all of them and, with --chain full, the filter flags and detections).
+
+`--full` adds everything beyond the headline: after the timed region the last
+batch's first and last CPI are compared with the fp64 NumPy oracle (checker only,
+never timed; a violation exits non-zero), the long timed region, the per-kernel
+roofline pass and, on one GPU, the CPU baseline, the host-buffer figures and the
+legs of the other BASELINE configurations and of the replay.
 """
 import argparse
 import json
@@ -121,6 +129,50 @@ def synth_batch(torch, n_cpi, n, seed, fs, device):
     yc = 0.8 * xc + a * xd * ph + torch.view_as_complex(noise)
     q = lambda v: torch.view_as_complex(torch.clamp(torch.round(torch.view_as_real(v)), -32768, 32767).contiguous())
     return q(xc).contiguous(), q(yc).contiguous()
+
+
+# ----------------------------------------------------------------------------- --dump-outputs
+DUMP_BYTES = 64_000_000  # all files of one dump together
+DUMP_MAP_BYTES = 40_000_000  # of which the sampled maps
+
+
+def dump_outputs(np, torch, out_dir, amb, out, met, ok=None, hits=None, cnt=None, cap=0):
+    """What one step handed its caller, as float32 / float64 .npy files in ``out_dir``:
+    map.npy         (k, nD, nC, 2) float32, real and imaginary part of the maps of the CPIs in map_cpis.npy
+                    (k evenly spaced CPIs of the batch, first and last included, as many as fit the budget)
+    map_cpis.npy    (k,) the CPI indices of map.npy
+    metrics.npy     (B, 2) float64, noisePower and maxPower of every CPI
+    --chain full also:
+    filter_ok.npy   (B,) the clutter filter's ok flag of every CPI
+    detections.npy  (K, 4) float64, (cpi, delay, doppler, snr) of every detection of the CPIs in map_cpis.npy"""
+    import blah2_amd
+    os.makedirs(out_dir, exist_ok=True)
+    B, nD, nC = out.shape
+    per_cpi = nD * nC * 8
+    k = min(B, max(1, DUMP_MAP_BYTES // per_cpi))
+    if k * per_cpi > DUMP_MAP_BYTES:
+        raise SystemExit(f"bench.py --dump-outputs: one map is {per_cpi / 1e6:.0f} MB, over the {DUMP_MAP_BYTES / 1e6:.0f} MB budget")
+    cpis = np.unique(np.linspace(0, B - 1, k).round().astype(np.int64))
+    files = {"map": torch.view_as_real(out[torch.as_tensor(cpis, device=out.device)]).cpu().numpy().astype(np.float32),
+             "map_cpis": cpis.astype(np.float64),
+             "metrics": met.cpu().numpy().astype(np.float64)}
+    if ok is not None:
+        files["filter_ok"] = ok.cpu().numpy().astype(np.float64)
+        counts = cnt.cpu().numpy()
+        rows = []
+        for c in cpis:
+            n_ = int(counts[c])
+            if n_ > cap:
+                raise RuntimeError(f"bench.py: {n_} detections in CPI {c}, capacity {cap}")
+            rec = hits[c, :max(n_, 1)].cpu().numpy().view(blah2_amd.HIT_DTYPE).reshape(-1)
+            d_ = blah2_amd.hits_to_detection(amb, rec, n_, cap)
+            rows.append(np.stack([np.full(n_, float(c)), d_.get_delay(), d_.get_doppler(), d_.get_snr()], axis=1))
+        files["detections"] = np.concatenate(rows).astype(np.float64) if rows else np.zeros((0, 4))
+    total = sum(arr.nbytes for arr in files.values())
+    if total > DUMP_BYTES:
+        raise SystemExit(f"bench.py --dump-outputs: {total / 1e6:.0f} MB of outputs, over the {DUMP_BYTES / 1e6:.0f} MB budget")
+    for name, arr in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
 
 
 # ----------------------------------------------------------------------------- CPU baseline
@@ -277,9 +329,10 @@ def parity_check(np, O, G, cfg, fmt, chain, cfar, n_doppler, x_h, y_h, got_map, 
 # ----------------------------------------------------------------------------- one measurement
 def measure(a, env):
     """One bench line's worth of measurement for the configuration in ``a``: data, handles, the timed region (barrier +
-    synchronize on both sides), a second region with every kernel bracketed by HIP events, the parity gate.  Returns
-    (result dict on rank 0 else None, parity dict or None).  Frees what it allocated, also when it raises: the default run
-    calls it once for the headline and once per secondary BASELINE configuration (``config_legs``)."""
+    synchronize on both sides); with --full also a second region with every kernel bracketed by HIP events, the parity gate.  Returns
+    (result dict on rank 0 else None, parity dict or None).  A plain run (no --full) stops after the timed region (and the
+    dump of --dump-outputs).  Frees what it allocated, also when it raises: a --full run calls it once for the headline
+    and once per secondary BASELINE configuration (``config_legs``)."""
     handles = []
     try:
         return _measure(a, env, handles)
@@ -442,8 +495,40 @@ def _measure(a, env, handles):
         elapsed, ranks_seen = float(t[0].item()), int(round(float(t[1].item())))
         assert ranks_seen == world
 
-    # the same region again, long enough (>= --long-s) that clock ramps and box-to-box jitter average out: `headline_long`
     last = a.warmup + a.steps - 1
+    if a.dump_outputs and rank == 0:  # what the last timed step left, before anything else runs on its buffers
+        q_ = last % NS
+        dump_outputs(np, torch, a.dump_outputs, ambs[q_], outs[q_], mets[q_],
+                     *((okflags[q_], hitss[q_], hitcnts[q_], CAP) if wh is not None else ()))
+
+    res = None
+    if rank == 0:
+        total_cpis = world * B * a.steps
+        res = {
+            "metric": "CPIs/s", "value": total_cpis / elapsed, "unit": "CPIs/s",
+            "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+            "ms_per_step": elapsed / a.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": f"{cfg_desc} -> {nD} Doppler x {nC} delay bins, synthetic {a.fmt} IQ resident in HBM"
+                       + ("" if a.chain == "amb" else f" + clutter filter ({dmax - dmin} taps) + {a.cfar} CA-CFAR"),
+                       "chain": a.chain,
+                       "batch_cpis_per_step": B, "fmt": a.fmt, "n_samples": n, "fs": fs,
+                       "n_doppler_bins": nD, "n_delay_bins": nC, "n_corr": amb.get_n_corr(),
+                       "fft_len": amb.dims.fft_len, "n_seg": amb.dims.n_seg, "seg_len": amb.dims.seg_len,
+                       "doppler_kernel": amb.last_doppler_kernel(),
+                       "prewarm_s": a.prewarm_s, "prewarm_steps": n_pre,
+                       "range_kernel": {1: "e16", 2: "e8", 3: "wave", 5: "wave1k", 6: "ps", 7: "fir+e16"}.get(amb.info(blah2_amd._lib.INFO_LAST_RANGE_KERNEL)),
+                       "fir": ("fused into the range kernel (range_fir_kernel)" if fused_fir else "two-stage (clutter_fir_kernel)") if wh is not None else None,
+                       "ring_batches": ring, "streams_per_gpu": NS, "sharding": f"{world} independent CPI streams, one per GPU",
+                       "ranks_seen_by_rccl": ranks_seen if dist is not None else None},
+            "cells_per_s": total_cpis * cells / elapsed,
+            "us_per_cpi": elapsed / (B * a.steps) * 1e6,
+            "per_gpu_cpis_per_s": total_cpis / elapsed / world,
+        }
+    if not a.full:  # a plain run: the headline and nothing else
+        return res, None
+
+    # the same region again, long enough (>= --long-s) that clock ramps and box-to-box jitter average out: `headline_long`
     long_res = None
     if a.long_s > 0:
         n_long = int(min(20000, max(a.steps, math.ceil(a.long_s / (elapsed / a.steps)))))
@@ -633,29 +718,8 @@ def _measure(a, env, handles):
             parity["filter_ok"] = all(c_.get("filter_ok") is True for c_ in checks)
             parity["detections"] = [c_.get("detections") for c_ in checks]
 
-    res = None
     if rank == 0:
-        total_cpis = world * B * a.steps
-        res = {
-            "metric": "CPIs/s", "value": total_cpis / elapsed, "unit": "CPIs/s",
-            "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-            "ms_per_step": elapsed / a.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"{cfg_desc} -> {nD} Doppler x {nC} delay bins, synthetic {a.fmt} IQ resident in HBM"
-                       + ("" if a.chain == "amb" else f" + clutter filter ({dmax - dmin} taps) + {a.cfar} CA-CFAR"),
-                       "chain": a.chain,
-                       "batch_cpis_per_step": B, "fmt": a.fmt, "n_samples": n, "fs": fs,
-                       "n_doppler_bins": nD, "n_delay_bins": nC, "n_corr": amb.get_n_corr(),
-                       "fft_len": amb.dims.fft_len, "n_seg": amb.dims.n_seg, "seg_len": amb.dims.seg_len,
-                       "doppler_kernel": amb.last_doppler_kernel(),
-                       "prewarm_s": a.prewarm_s, "prewarm_steps": n_pre,
-                       "range_kernel": {1: "e16", 2: "e8", 3: "wave", 5: "wave1k", 6: "ps", 7: "fir+e16"}.get(amb.info(blah2_amd._lib.INFO_LAST_RANGE_KERNEL)),
-                       "fir": ("fused into the range kernel (range_fir_kernel)" if fused_fir else "two-stage (clutter_fir_kernel)") if wh is not None else None,
-                       "ring_batches": ring, "streams_per_gpu": NS, "sharding": f"{world} independent CPI streams, one per GPU",
-                       "ranks_seen_by_rccl": ranks_seen if dist is not None else None},
-            "cells_per_s": total_cpis * cells / elapsed,
-            "us_per_cpi": elapsed / (B * a.steps) * 1e6,
-            "per_gpu_cpis_per_s": total_cpis / elapsed / world,
+        res.update({
             "parity": parity,
             "headline_long": long_res,
             "roofline": {"bound": "hbm", "kernel": {1: "range_kernel", 2: "range8_kernel", 3: "rangew_kernel", 5: "rangew1k_kernel", 6: "rangeps_kernel", 7: "range_fir_kernel"}.get(
@@ -680,7 +744,7 @@ def _measure(a, env, handles):
                          "kernels": kernels,
                          "kernel_us_per_step": {k: v[0] / max(v[1], 1) * 1e3 for k, v in kt.items() if v[1]},
                          "chain_us_per_step": chain_s * 1e6},
-        }
+        })
     return res, parity
 
 
@@ -892,7 +956,7 @@ def _leg_args(a, extra):
         name = k[2:].replace("-", "_")
         setattr(la, name, int(v) if name in ("batch", "streams") else v)
     la.target_s, la.warmup, la.prewarm_s, la.parity_cpis, la.long_s = 0.3, 3, 0.3, "last", 0.0
-    la.no_parity = a.no_parity
+    la.no_parity, la.full, la.dump_outputs = a.no_parity, True, None
     return la
 
 
@@ -903,6 +967,11 @@ def main(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: oracle parity, --long-s region, per-kernel roofline pass, and on one GPU "
+                         "the CPU baseline, host-buffer figures and the legs of the other configurations and of the replay")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/*.npy (see dump_outputs)")
     ap.add_argument("--batch", type=int, default=0,
                     help="CPIs per step (per GPU); default 256 for the 2 MS/s configs (8 GB of fp32 IQ per step: a pulse is the scheduling unit of the range kernel, and 256 x 513 pulses are 42.75 rounds of its "
                          "3072 resident waves -- measured on one box: 98.8 k / 107.7 k / 110.3 k CPIs/s at 32 / 128 / 256); "
@@ -911,8 +980,8 @@ def main(argv=None):
                          "measured: cfg3 93.9 / 88.8 / 84.7 us/CPI at 8 / 16 / 32, cfg5 142.8 / 138.4 / 138.8 at 4 / 8 / 16")
     ap.add_argument("--config", default="cfg2", choices=sorted(CONFIGS))
     ap.add_argument("--fmt", default="c32", choices=["c32", "i16", "f16"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="skip the oracle comparison after the timed region")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the host-buffer figures")
+    ap.add_argument("--no-parity", action="store_true", help="--full: skip the oracle comparison after the timed region")
     ap.add_argument("--chain", default="amb", choices=["amb", "full"],
                     help="amb: range+Doppler+metrics (BASELINE headline); full: clutter filter + amb + CFAR (configs[2])")
     ap.add_argument("--cfar", default="2d", choices=["1d", "2d"])
@@ -937,16 +1006,18 @@ def main(argv=None):
                     help="independent CPI streams per GPU (engine handles on their own HIP streams); successive "
                          "steps alternate between them so one batch's Doppler stage overlaps the next batch's range stage")
     ap.add_argument("--no-configs", action="store_true",
-                    help="headline only: skip the short legs for the other single-GPU BASELINE configurations (`configs` in the JSON line)")
+                    help="--full: skip the short legs for the other single-GPU BASELINE configurations (`configs` in the JSON line)")
     ap.add_argument("--long-s", type=float, default=0.5,
-                    help="after the K timed steps, the same region again for at least this long (`headline_long` in the line); 0 = skip")
+                    help="--full: after the K timed steps, the same region again for at least this long (`headline_long` in the line); 0 = skip")
     ap.add_argument("--no-replay", action="store_true",
-                    help="skip the PCIe-inclusive replay legs (`replay` in the JSON line: BASELINE configs[3] at N = 1)")
+                    help="--full: skip the PCIe-inclusive replay legs (`replay` in the JSON line: BASELINE configs[3] at N = 1)")
     ap.add_argument("--target-s", type=float, default=0.0,
                     help="pick --steps so that the timed region lasts about this long (the legs of `configs` use it)")
     ap.add_argument("--parity-cpis", default="both", choices=["both", "last"],
                     help="CPIs of the last timed batch compared with the oracle: first and last, or the last only")
     a = ap.parse_args(argv)
+    if a.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
 
     import torch
     action, detail = plan_launch(a.gpus, os.environ, torch.cuda.device_count() if torch.cuda.is_available() else 0)
@@ -974,7 +1045,7 @@ def main(argv=None):
     env = types.SimpleNamespace(torch=torch, np=np, b2=blah2_amd, rank=rank, world=world, local=local, dev=dev, dist=dist,
                                 failed_legs=[])
     res, parity = measure(a, env)
-    if rank == 0:
+    if rank == 0 and a.full:
         cfg = CONFIGS[a.config][0]
         if world == 1 and not a.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(cfg)
@@ -984,6 +1055,7 @@ def main(argv=None):
             res["configs"] = config_legs(a, env)  # every other single-GPU BASELINE configuration, same process, same box
             if not a.no_replay and not env.failed_legs:
                 res["replay"] = replay_legs(a, env)  # BASELINE configs[3] at N = 1 (PCIe-inclusive; never `value`)
+    if rank == 0:
         print(json.dumps(res), flush=True)
     if dist is not None:
         dist.barrier()  # rank 0 has been checking parity: every rank leaves the group together

@@ -4,6 +4,6 @@ P='import sys,json; j=json.loads(sys.stdin.read().strip().split("\n")[-1]); B=j[
 for rep in 1 2; do
 for lib in "" $(ls tools/ab/*.so 2>/dev/null); do
   t=tree; if [ -n "$lib" ]; then t=$(basename $lib .so); export BLAH2HIP_LIBRARY=$PWD/$lib; else unset BLAH2HIP_LIBRARY; fi
-  python bench.py --no-cpu-baseline "$@" 2>&1 | python -c "$P" $t
+  python bench.py --full --no-cpu-baseline "$@" 2>&1 | python -c "$P" $t
 done
 done

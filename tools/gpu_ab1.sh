@@ -7,7 +7,7 @@ for rep in 1 2; do
 for lib in "" $(ls tools/ab/*.so 2>/dev/null); do
   t=tree; [ -n "$lib" ] && t=$(basename $lib .so)
   if [ -n "$lib" ]; then export BLAH2HIP_LIBRARY=$REPO/$lib; else unset BLAH2HIP_LIBRARY; fi
-  python bench.py --no-cpu-baseline "$@" > $OUT/ab1_$t.log 2> $OUT/ab1_$t.err
+  python bench.py --full --no-cpu-baseline "$@" > $OUT/ab1_$t.log 2> $OUT/ab1_$t.err
   python - <<PY
 import json
 try:

@@ -9,6 +9,6 @@ for rep in 1 2; do
 for lib in "" $@; do
   name=${lib:-product}
   if [ -z "$lib" ]; then unset BLAH2HIP_LIBRARY; else export BLAH2HIP_LIBRARY=$PWD/tools/ab/$lib; fi
-  timeout 400 python bench.py --config cfg3 --chain full --batch 32 --steps 8 --warmup 2 --no-cpu-baseline 2>&1 | show "cfg3 full b32 $name"
+  timeout 400 python bench.py --full --config cfg3 --chain full --batch 32 --steps 8 --warmup 2 --no-cpu-baseline 2>&1 | show "cfg3 full b32 $name"
 done
 done

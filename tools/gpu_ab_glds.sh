@@ -8,7 +8,7 @@ BLAH2HIP_LIBRARY=$V python -m pytest tests/test_timed_kernels_gpu.py tests/test_
 for rep in 1 2 3; do
   for lib in default glds; do
     if [ $lib = glds ]; then export BLAH2HIP_LIBRARY=$V; else unset BLAH2HIP_LIBRARY; fi
-    python bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-configs --no-parity --long-s 0 2>/dev/null | python -c "
+    python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --no-configs --no-parity --long-s 0 2>/dev/null | python -c "
 import json,sys
 r=json.loads(sys.stdin.read().strip().splitlines()[-1]); rl=r['roofline']
 print('$lib', 'us/CPI %.3f' % r['us_per_cpi'], 'range us/launch %.1f' % rl['avg_launch_us'], 'frac %.4f' % rl['frac'], 'kernel', rl['kernel'])"

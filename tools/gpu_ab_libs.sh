@@ -10,15 +10,15 @@ for lib in "" $@; do
   name=${lib:-product}
   export BLAH2HIP_LIBRARY=${lib:+$PWD/tools/ab/$lib}
   [ -z "$lib" ] && unset BLAH2HIP_LIBRARY
-  timeout 300 python bench.py --steps 30 --warmup 5 --no-cpu-baseline 2>&1 | show "headline $name"
+  timeout 300 python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline 2>&1 | show "headline $name"
 done
 done
 for lib in "" $@; do
   name=${lib:-product}
   export BLAH2HIP_LIBRARY=${lib:+$PWD/tools/ab/$lib}
   [ -z "$lib" ] && unset BLAH2HIP_LIBRARY
-  timeout 300 python bench.py --chain full --steps 12 --no-cpu-baseline 2>&1 | show "cfg2 full $name"
-  timeout 300 python bench.py --config cfg3 --steps 12 --warmup 3 --no-cpu-baseline 2>&1 | show "cfg3 $name"
-  timeout 300 python bench.py --config cfg5 --fmt f16 --steps 8 --warmup 2 --no-cpu-baseline 2>&1 | show "cfg5 $name"
-  timeout 400 python bench.py --config cfg3 --chain full --batch 32 --steps 8 --warmup 2 --no-cpu-baseline 2>&1 | show "cfg3 full b32 $name"
+  timeout 300 python bench.py --full --chain full --steps 12 --no-cpu-baseline 2>&1 | show "cfg2 full $name"
+  timeout 300 python bench.py --full --config cfg3 --steps 12 --warmup 3 --no-cpu-baseline 2>&1 | show "cfg3 $name"
+  timeout 300 python bench.py --full --config cfg5 --fmt f16 --steps 8 --warmup 2 --no-cpu-baseline 2>&1 | show "cfg5 $name"
+  timeout 400 python bench.py --full --config cfg3 --chain full --batch 32 --steps 8 --warmup 2 --no-cpu-baseline 2>&1 | show "cfg3 full b32 $name"
 done

@@ -11,5 +11,5 @@ except Exception as e:
     print(sys.argv[2], "ERR", open(sys.argv[1]).read()[-400:])
 PY
 }
-for B in 4 8 16; do python bench.py --config cfg5 --fmt f16 --batch $B --steps 8 --warmup 2 --no-cpu-baseline > $OUT/bs_cfg5_$B.log 2>&1; show $OUT/bs_cfg5_$B.log "cfg5 f16 batch $B"; done
-for B in 8 16 32; do python bench.py --config cfg3 --batch $B --steps 8 --warmup 2 --no-cpu-baseline > $OUT/bs_cfg3_$B.log 2>&1; show $OUT/bs_cfg3_$B.log "cfg3 batch $B"; done
+for B in 4 8 16; do python bench.py --full --config cfg5 --fmt f16 --batch $B --steps 8 --warmup 2 --no-cpu-baseline > $OUT/bs_cfg5_$B.log 2>&1; show $OUT/bs_cfg5_$B.log "cfg5 f16 batch $B"; done
+for B in 8 16 32; do python bench.py --full --config cfg3 --batch $B --steps 8 --warmup 2 --no-cpu-baseline > $OUT/bs_cfg3_$B.log 2>&1; show $OUT/bs_cfg3_$B.log "cfg3 batch $B"; done

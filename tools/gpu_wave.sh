@@ -5,7 +5,7 @@ REPO=$(pwd); OUT=$REPO/gpurun_out; mkdir -p $OUT
 if [ "${SKIPTEST:-0}" = 0 ]; then python -m pytest tests/test_timed_kernels_gpu.py -m gpu -q -k "one_wave" > $OUT/pytest_wave.log 2>&1; echo "pytest rc=$?" >> $OUT/pytest_wave.log; tail -n 3 $OUT/pytest_wave.log; fi
 run() { # tag, env lib, extra args
   if [ -n "$2" ]; then export BLAH2HIP_LIBRARY=$2; else unset BLAH2HIP_LIBRARY; fi
-  python bench.py --steps 10 --warmup 3 --no-cpu-baseline ${@:3} > $OUT/bw_$1.log 2> $OUT/bw_$1.err
+  python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline ${@:3} > $OUT/bw_$1.log 2> $OUT/bw_$1.err
   python - <<PY
 import json
 try:

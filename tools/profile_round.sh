@@ -18,7 +18,7 @@ prune() { # dir: keep what tools/summarize_prof.py reads (the stats table; the c
 }
 profile() { # tag, json description, bench args...
   local tag=$1; local desc=$2; shift 2
-  local B="python $REPO/bench.py $* --no-cpu-baseline --no-parity --no-configs --long-s 0"
+  local B="python $REPO/bench.py --full $* --no-cpu-baseline --no-parity --no-configs --long-s 0"
   mkdir -p $OUT/prof/$tag
   echo "$desc" > $OUT/prof/$tag/bench_config.json
   timeout 400 rocprofv3 --kernel-trace --stats -d $OUT/prof/$tag/trace -o bench --output-format csv -- $B > $OUT/prof/$tag/trace.log 2>&1
@@ -40,26 +40,26 @@ timeout 200 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/cal/write -o cal -
 prune $OUT/cal
 cd $REPO
 rm -f $OUT/bench_r6*.log
-python bench.py > $OUT/bench_r6.log 2>&1                      # the default line: headline + configs[] legs + cpu_baseline + e2e_host
-python bench.py --fmt i16 --no-cpu-baseline --no-configs --no-replay > $OUT/bench_r6_i16.log 2>&1
-python bench.py --chain full --steps 20 --no-cpu-baseline --no-configs --no-replay > $OUT/bench_r6_full.log 2>&1
-python bench.py --config cfg3 --steps 20 --warmup 3 --no-cpu-baseline --no-configs --no-replay > $OUT/bench_r6_cfg3.log 2>&1
-python bench.py --config cfg3 --chain full --cfar 2d --batch 32 --streams 2 --steps 20 --warmup 3 --no-cpu-baseline --no-configs --no-replay > $OUT/bench_r6_cfg3_full.log 2>&1
-python bench.py --config cfg3 --chain full --cfar 2d --batch 32 --streams 2 --fir two-stage --steps 20 --warmup 3 --no-cpu-baseline --no-configs --no-replay > $OUT/bench_r6_cfg3_full_twostage.log 2>&1
-python bench.py --config cfg5 --fmt f16 --steps 10 --warmup 2 --no-cpu-baseline --no-configs --no-replay > $OUT/bench_r6_cfg5.log 2>&1
-python bench.py --batch 1 --steps 2000 --warmup 50 --no-cpu-baseline --no-configs --no-replay > $OUT/bench_r6_b1.log 2>&1
-python bench.py --chain full --cfar 1d --batch 1 --steps 500 --warmup 20 --no-cpu-baseline --no-configs --no-replay > $OUT/bench_r6_full_b1.log 2>&1
-python bench.py --config small --steps 40 --warmup 3 --no-cpu-baseline --no-configs --no-replay > $OUT/bench_r6_small.log 2>&1
-python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_r6_torchrun.log 2>&1
+python bench.py --full > $OUT/bench_r6.log 2>&1                      # the default line: headline + configs[] legs + cpu_baseline + e2e_host
+python bench.py --full --fmt i16 --no-cpu-baseline --no-configs --no-replay > $OUT/bench_r6_i16.log 2>&1
+python bench.py --full --chain full --steps 20 --no-cpu-baseline --no-configs --no-replay > $OUT/bench_r6_full.log 2>&1
+python bench.py --full --config cfg3 --steps 20 --warmup 3 --no-cpu-baseline --no-configs --no-replay > $OUT/bench_r6_cfg3.log 2>&1
+python bench.py --full --config cfg3 --chain full --cfar 2d --batch 32 --streams 2 --steps 20 --warmup 3 --no-cpu-baseline --no-configs --no-replay > $OUT/bench_r6_cfg3_full.log 2>&1
+python bench.py --full --config cfg3 --chain full --cfar 2d --batch 32 --streams 2 --fir two-stage --steps 20 --warmup 3 --no-cpu-baseline --no-configs --no-replay > $OUT/bench_r6_cfg3_full_twostage.log 2>&1
+python bench.py --full --config cfg5 --fmt f16 --steps 10 --warmup 2 --no-cpu-baseline --no-configs --no-replay > $OUT/bench_r6_cfg5.log 2>&1
+python bench.py --full --batch 1 --steps 2000 --warmup 50 --no-cpu-baseline --no-configs --no-replay > $OUT/bench_r6_b1.log 2>&1
+python bench.py --full --chain full --cfar 1d --batch 1 --steps 500 --warmup 20 --no-cpu-baseline --no-configs --no-replay > $OUT/bench_r6_full_b1.log 2>&1
+python bench.py --full --config small --steps 40 --warmup 3 --no-cpu-baseline --no-configs --no-replay > $OUT/bench_r6_small.log 2>&1
+python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_r6_torchrun.log 2>&1
 # the Toeplitz solve on its own: HIP-event time per launch by taps / batch / form, and rocprofv3's kernel durations of the same
 python tools/gpu_solve.py --json $OUT/solve_timing.json > $OUT/solve_timing.log 2>&1
 mkdir -p $OUT/prof/solve
 (cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/prof/solve/trace -o bench --output-format csv -- python $REPO/tools/gpu_solve.py --quick > $OUT/prof/solve/trace.log 2>&1)
 # the lone-CPI chain (small-launch kernels) under the profiler
 mkdir -p $OUT/prof/b1
-(cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/prof/b1/trace -o bench --output-format csv -- python $REPO/bench.py --batch 1 --steps 500 --warmup 20 --no-cpu-baseline --no-parity --no-configs > $OUT/prof/b1/trace.log 2>&1)
+(cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/prof/b1/trace -o bench --output-format csv -- python $REPO/bench.py --full --batch 1 --steps 500 --warmup 20 --no-cpu-baseline --no-parity --no-configs > $OUT/prof/b1/trace.log 2>&1)
 mkdir -p $OUT/prof/b1full
-(cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/prof/b1full/trace -o bench --output-format csv -- python $REPO/bench.py --chain full --cfar 1d --batch 1 --steps 500 --warmup 20 --no-cpu-baseline --no-parity --no-configs --no-replay --long-s 0 > $OUT/prof/b1full/trace.log 2>&1)
+(cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/prof/b1full/trace -o bench --output-format csv -- python $REPO/bench.py --full --chain full --cfar 1d --batch 1 --steps 500 --warmup 20 --no-cpu-baseline --no-parity --no-configs --no-replay --long-s 0 > $OUT/prof/b1full/trace.log 2>&1)
 prune $OUT/prof/solve; prune $OUT/prof/b1; prune $OUT/prof/b1full
 # the fused FIR + range kernel beside the two kernels it replaces (configs[2], 16 CPIs per launch)
 bash $REPO/tools/prof_fused_ab.sh 16 10 > $OUT/fused_fir_ab.txt 2>&1
