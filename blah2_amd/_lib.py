@@ -38,7 +38,7 @@ RANGE_E16, RANGE_E8, RANGE_WAVE, RANGE_WAVE1K, RANGE_PS, RANGE_FIR = 1, 2, 3, 5,
 INFO_LAST_DOPPLER_KERNEL, INFO_LAST_RANGE_KERNEL, INFO_DOPPLER_FFT_LEN, INFO_RANGE_GRID, INFO_NUM_CU = 1, 2, 3, 4, 5
 INFO_DOPPLER_GRID, INFO_DOPPLER_TILES = 6, 7
 INFO_LEAK_LAGS, INFO_LEAK_MAX_E12 = 8, 9
-INFO_HOT_COLUMNS = 10
+INFO_HOT_COLUMNS, INFO_HOT_COLUMNS_MISSED = 10, 11
 
 
 class Blah2HipError(RuntimeError):

@@ -83,7 +83,7 @@ struct blah2hip_amb_s {
   cf *d_tw = nullptr;
   cf *d_dopW = nullptr;
   double2 *d_dopW64 = nullptr;   // hot_columns_kernel: exp(-2 pi i k / nD) in fp64
-  uint32_t *d_hotCount = nullptr; // [max_batch] columns the last call's hot_columns_kernel rewrote
+  uint32_t *d_hotCount = nullptr; // [2][max_batch]: columns the last call's hot_columns_kernel rewrote, columns it left out
   cf *d_R = nullptr;
   cf *d_map = nullptr;
   double *d_partSum = nullptr;
@@ -136,6 +136,7 @@ struct blah2hip_amb_s {
   int hotMode = 1;                  // BLAH2HIP_OPT_HOT_COLUMNS: 0 off, 1 auto (CPIs long enough for a peak HOT_RATIO above the mean level), 2 always
   bool lastHot = false;             // the last process call launched hot_columns_kernel
   hipStream_t lastHotStream = nullptr; // ... on this stream (BLAH2HIP_INFO_HOT_COLUMNS waits for that one only)
+  uint32_t lastHotCpis = 0;         // ... over this many CPIs
   int lastLeakLags = 0;             // BLAH2HIP_INFO_LEAK_LAGS: lags corrected by the last process call (0 = not applied)
   double lastLeakMax = 0.0;         // BLAH2HIP_INFO_LEAK_MAX_E12: the largest |g| of the calibration the last call ran under
 };
@@ -757,14 +758,52 @@ __global__ __launch_bounds__(64) void leak_fix_kernel(cf *map, size_t cells, siz
 // the only one beyond north_star's 1e-4).  The reference computes in fp64 and has no such floor.  So the few columns whose
 // peak can stand more than HOT_RATIO above the map's mean level are transformed again in fp64, straight from the fp32
 // range map (direct DFT, nD^2 complex fp64 MACs a column -- 1e6 at nD = 1025, spread over nD/32 workgroups), and written
-// over the fp32 result.  Which columns: those whose mean power over four pulses of the range map (less the first pulse's
-// value: the Doppler kernels remove the column's zero-Doppler content exactly before they transform it), taken as a coherent tone
-// (x nD), would reach HOT_RATIO x the mean level of the Map::set_metrics partials -- noise columns sit sqrt(nD)/0.75 below
-// that test, so a launch with nothing hot costs one read of 4 x nDelay cells per workgroup.  At most HOT_MAX columns a CPI
-// (the strongest; ties to the lower lag), every workgroup of the CPI deriving the same list.  The Map::set_metrics partials
-// were taken before: rewriting 1e-7 of a peak moves noisePower by < 1e-8 dB.
-constexpr int HOT_ROWS = 32, HOT_MAX = 16, HOT_CAND = 256, HOT_SAMPLES = 4, HOT_ND_MAX = 4096;
+// over the fp32 result.  Which columns: those whose amplitude estimate from the range map, times nD / HOT_BOUND, reaches
+// HOT_RATIO x the mean level of the Map::set_metrics partials.  The estimate is the larger of two sample standard deviations
+// of the column (the variance sum|r|^2/n - |mean r|^2 does not see the zero-Doppler content, which the Doppler kernels take
+// out exactly before they transform -- the direct path's column is no reason to transform it again): over the S contiguous
+// pulses 0 .. S-1, and over the S pulses floor((2s+1) nD / (2S)), S = HOT_SET_SMALL up to nD = HOT_SET_SMALL_ND, else
+// HOT_SET_LARGE.  For a tone k bins off zero Doppler each set is blind where its phases line up: the block for
+// |k| << nD / S, the spaced set near multiples of S; S^2 >= 2 nD keeps the two blind ranges apart.  HOT_BOUND is the worst
+// ratio of the estimate to the tone's amplitude (its on-bin peak / nD; for |k| < 1, its largest off-zero-Doppler cell / nD),
+// swept over k on a 1/16-bin grid at nD = 101 ... 4096 by tests/test_hot_columns_model.py, which reads these constants: 0.976
+// at nD <= 2049, 0.827 at nD = 4096 (k = 47.5).  Noise columns (sigma per pulse: mean level 0.75 sigma sqrt(nD), estimate
+// ~sigma) sit a factor 0.75 HOT_BOUND HOT_RATIO / sqrt(nD) below the test: 2.3 at nD = 4096, 6.6 at nD = 513.  A launch
+// with nothing hot costs one read of (2S + 1) x nDelay cells per workgroup -- which is why a large batch runs ONE workgroup
+// per CPI (HotArgs::groups).  At most HOT_MAX columns a CPI (the strongest; ties to the lower lag), every workgroup of the
+// CPI deriving the same list; a column past HOT_MAX, or past the HOT_CAND / 4 candidates of its wave's quarter of the lags,
+// keeps its fp32 values and is counted in `missed`.  The Map::set_metrics partials were taken before: rewriting 1e-7 of a
+// peak moves noisePower by < 1e-8 dB.
+constexpr int HOT_ROWS = 32, HOT_MAX = 16, HOT_CAND = 256, HOT_ND_MAX = 4096;
+constexpr int HOT_SET_SMALL = 32, HOT_SET_LARGE = 48, HOT_SET_SMALL_ND = 1025; // pulses in each set of the estimate
+constexpr double HOT_BOUND = 0.8;   // estimate / tone amplitude >= 0.8 at every Doppler (worst measured 0.827, nD = 4096)
 constexpr double HOT_RATIO = 250.0; // 1.2e-7 x 250 = 3e-5 of a mean-level cell: a third of the 1e-4 gate, as LEAK_REACH
+
+// the larger of the two sample variances of column Rj (pulse stride 16 cells), S pulses a set, every load in flight together
+template <int S>
+__device__ __forceinline__ float hot_estimate(const cf *__restrict__ Rj, int nD)
+{
+  // (differences to pulse 0: the variance is the same, and a column's zero-Doppler content -- the direct path's, 1e3 x the
+  // tone that is looked for -- does not cancel in fp32)
+  const cf r0 = Rj[0];
+  cf b[S], q[S];
+#pragma unroll
+  for (int i = 0; i < S; i++) {
+    b[i] = Rj[(size_t)(i < nD ? i : 0) * 16]; // block: pulses 0 .. min(S, nD)-1 (beyond nD pulse 0 again, which adds zeros)
+    q[i] = Rj[(size_t)(((int64_t)(2 * i + 1) * nD) / (2 * S)) * 16];
+  }
+  float bx = 0.f, by = 0.f, bp = 0.f, qx = 0.f, qy = 0.f, qp = 0.f;
+#pragma unroll
+  for (int i = 0; i < S; i++) {
+    const float dx = b[i].x - r0.x, dy = b[i].y - r0.y, ex = q[i].x - r0.x, ey = q[i].y - r0.y;
+    bx += dx; by += dy; bp = fmaf(dx, dx, fmaf(dy, dy, bp));
+    qx += ex; qy += ey; qp = fmaf(ex, ex, fmaf(ey, ey, qp));
+  }
+  const float nb = (float)min(S, nD);
+  const float vb = bp / nb - (bx * bx + by * by) / (nb * nb);
+  const float vq = qp * (1.f / S) - (qx * qx + qy * qy) * (1.f / ((float)S * S));
+  return fmaxf(fmaxf(vb, vq), 0.f);
+}
 
 struct HotArgs {
   const cf *R;             // tiled range map (rmap_index)
@@ -773,10 +812,12 @@ struct HotArgs {
   const double *partSum;   // [nCpi][nParts] (nParts > 0) ...
   const double *metrics;   // ... or the finished [nCpi][2] (nParts == 0: doppler_sub1k_kernel)
   uint32_t *count;         // [nCpi]: columns rewritten
+  uint32_t *missed;        // [nCpi]: columns that passed the test and were not rewritten (HOT_MAX, HOT_CAND / 4 a wave)
   int32_t nParts, partStride, nD, nDelay, nTiles;
-  int32_t groups;          // 32-row groups a workgroup walks: 1 on small launches (latency), 4 in batches (the candidate scan,
-                           // which every workgroup repeats, is most of a launch that finds nothing)
-  float ratioDb;           // 10 log10(HOT_RATIO)
+  int32_t groups;          // 32-row groups a workgroup walks: 1 on small launches (latency), 4 in batches, all of them (one
+                           // workgroup a CPI) in large batches (the candidate scan, which every workgroup repeats, is most of
+                           // a launch that finds nothing)
+  float ratioDb;           // 10 log10(HOT_RATIO x HOT_BOUND)
 };
 
 __global__ __launch_bounds__(256) void hot_columns_kernel(HotArgs a)
@@ -785,7 +826,7 @@ __global__ __launch_bounds__(256) void hot_columns_kernel(HotArgs a)
   __shared__ double sred[4];
   __shared__ int candLag[HOT_CAND];
   __shared__ float candDb[HOT_CAND];
-  __shared__ int waveCnt[4], hot[HOT_MAX], nHot;
+  __shared__ int waveCnt[4], waveAll[4], hot[HOT_MAX], nHot;
   __shared__ double2 red[8][HOT_ROWS];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int cpi = blockIdx.y, nD = a.nD, nDelay = a.nDelay;
@@ -815,16 +856,9 @@ __global__ __launch_bounds__(256) void hot_columns_kernel(HotArgs a)
     const int j = j0 + lane;
     float db = -1e30f;
     if (j < nDelay) {
-      // (less the first pulse's value, as the Doppler kernels transform the column: what stands at zero Doppler -- the direct
-      // path's column -- is exact there already and is no reason to transform it again)
-      const cf r0 = a.R[rmap_index(nD, a.nTiles, cpi, 0, j)];
-      float pw = 0.f;
-#pragma unroll
-      for (int s = 0; s < HOT_SAMPLES; s++) {
-        const cf r = a.R[rmap_index(nD, a.nTiles, cpi, (int)(((int64_t)(2 * s + 1) * nD) / (2 * HOT_SAMPLES)), j)];
-        pw += (r.x - r0.x) * (r.x - r0.x) + (r.y - r0.y) * (r.y - r0.y);
-      }
-      db = 5.f * log10f(pw * (1.f / HOT_SAMPLES)); // 10 log10 of the amplitude
+      const cf *Rj = a.R + rmap_index(nD, a.nTiles, cpi, 0, j);
+      const float v = nD <= HOT_SET_SMALL_ND ? hot_estimate<HOT_SET_SMALL>(Rj, nD) : hot_estimate<HOT_SET_LARGE>(Rj, nD);
+      db = 5.f * log10f(v); // 10 log10 of the amplitude estimate
     }
     const uint64_t m = __ballot(db > thr);
     if (db > thr) {
@@ -833,7 +867,7 @@ __global__ __launch_bounds__(256) void hot_columns_kernel(HotArgs a)
     }
     mine += __popcll(m);
   }
-  if (lane == 0) waveCnt[wave] = min(mine, HOT_CAND / 4);
+  if (lane == 0) { waveCnt[wave] = min(mine, HOT_CAND / 4); waveAll[wave] = mine; }
   __syncthreads();
   if (t == 0) { // the HOT_MAX strongest, ties to the lower lag
     int n = 0;
@@ -850,7 +884,10 @@ __global__ __launch_bounds__(256) void hot_columns_kernel(HotArgs a)
       hot[n] = candLag[best];
     }
     nHot = n;
-    if (blockIdx.x == 0) a.count[cpi] = (uint32_t)n;
+    if (blockIdx.x == 0) {
+      a.count[cpi] = (uint32_t)n;
+      a.missed[cpi] = (uint32_t)((waveAll[0] + waveAll[1]) + (waveAll[2] + waveAll[3]) - n);
+    }
   }
   __syncthreads();
   const int nh = nHot;
@@ -1153,8 +1190,8 @@ int blah2hip_amb_create_ex(int32_t delay_min, int32_t delay_max, int32_t doppler
     }
     HIPCHK(hipMalloc(&h->d_dopW64, nD * sizeof(double2)));
     HIPCHK(hipMemcpy(h->d_dopW64, dw64.data(), nD * sizeof(double2), hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc(&h->d_hotCount, max_batch * sizeof(uint32_t)));
-    HIPCHK(hipMemset(h->d_hotCount, 0, max_batch * sizeof(uint32_t)));
+    HIPCHK(hipMalloc(&h->d_hotCount, 2 * max_batch * sizeof(uint32_t)));
+    HIPCHK(hipMemset(h->d_hotCount, 0, 2 * max_batch * sizeof(uint32_t)));
   }
   HIPCHK(hipMemcpy(h->d_doppler, h->dopplerAxis.data(), nD * sizeof(double), hipMemcpyHostToDevice));
   if (h->dopR3) {
@@ -1326,6 +1363,17 @@ int blah2hip_amb_get_info(blah2hip_amb_t h, int key, int64_t *value)
     HIPCHK(hipMemcpyAsync(&n, h->d_hotCount, sizeof(n), hipMemcpyDeviceToHost, h->lastHotStream));
     HIPCHK(hipStreamSynchronize(h->lastHotStream));
     *value = n;
+    return BLAH2HIP_OK;
+  }
+  case BLAH2HIP_INFO_HOT_COLUMNS_MISSED: { // the most of any CPI of the last call; waits for the device
+    *value = 0;
+    if (!h->lastHot) return BLAH2HIP_OK;
+    std::vector<uint32_t> n(h->lastHotCpis);
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipMemcpyAsync(n.data(), h->d_hotCount + h->dims.max_batch, n.size() * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                          h->lastHotStream));
+    HIPCHK(hipStreamSynchronize(h->lastHotStream));
+    for (uint32_t v : n) *value = std::max<int64_t>(*value, v);
     return BLAH2HIP_OK;
   }
   default: return fail(BLAH2HIP_ERR_INVALID, "unknown info key");
@@ -1606,16 +1654,17 @@ int blah2hip_amb_process_dev(blah2hip_amb_t h, int fmt, const void *d_x, const v
       (h->hotMode == 2 || 1.34 * std::sqrt((double)h->dims.n_used) >= HOT_RATIO)) { // |peak| <= sqrt(N) sx sy, mean level ~ 0.75 sqrt(N) sx sy
     HotArgs ha;
     ha.R = h->d_R; ha.map = map; ha.W = h->d_dopW64;
-    ha.partSum = h->d_partSum; ha.metrics = met; ha.count = h->d_hotCount;
+    ha.partSum = h->d_partSum; ha.metrics = met; ha.count = h->d_hotCount; ha.missed = h->d_hotCount + h->dims.max_batch;
     ha.nParts = nPartsUsed; ha.partStride = nPartsUsed; ha.nD = (int32_t)nD; ha.nDelay = (int32_t)nDelay; ha.nTiles = h->nTiles;
-    ha.ratioDb = (float)(10.0 * std::log10(HOT_RATIO));
-    ha.groups = n_cpi >= 4 ? 4 : 1;
+    ha.ratioDb = (float)(10.0 * std::log10(HOT_RATIO * HOT_BOUND));
+    ha.groups = (int)n_cpi >= h->numCU / 4 ? ((int)nD + HOT_ROWS - 1) / HOT_ROWS : (n_cpi >= 4 ? 4 : 1);
     const size_t lds = 2 * (size_t)nD * sizeof(double2);
     LDSCFG(hot_columns_kernel, (size_t)2 * HOT_ND_MAX * sizeof(double2));
     hipLaunchKernelGGL(hot_columns_kernel, dim3((nD + HOT_ROWS * ha.groups - 1) / (HOT_ROWS * ha.groups), n_cpi), dim3(256), lds, st, ha);
     HIPCHK(hipGetLastError());
     h->lastHot = true;
     h->lastHotStream = st;
+    h->lastHotCpis = (uint32_t)n_cpi;
   }
   if (leak) { // inside the Doppler bracket: one 64-thread workgroup per CPI on a few dozen cells of the zero-Doppler row
     leak_fix_kernel<<<dim3(n_cpi), dim3(64), 0, st>>>(map, (size_t)nD * nDelay, (size_t)leak_row0(h) * nDelay, leak_col0(h),

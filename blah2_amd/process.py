@@ -258,6 +258,11 @@ class Ambiguity:
         """Columns of the last call's first CPI that were transformed again in fp64 (waits for the device)."""
         return self.info(_lib.INFO_HOT_COLUMNS)
 
+    def hot_columns_missed(self):
+        """The most columns of any CPI of the last call that qualified for the fp64 transform and kept their fp32 values (beyond
+        the 16 a CPI, or beyond 64 candidates in one quarter of the lags); waits for the device."""
+        return self.info(_lib.INFO_HOT_COLUMNS_MISSED)
+
     def set_leak_compensation(self, mode):
         """BLAH2HIP_OPT_LEAK_COMPENSATION: "off", "auto" (default) or "always" (include/blah2hip.h)."""
         mode = {"off": _lib.LEAK_OFF, "auto": _lib.LEAK_AUTO, "always": _lib.LEAK_ALWAYS}.get(mode, mode)

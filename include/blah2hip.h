@@ -152,8 +152,12 @@ int blah2hip_amb_get_axes(blah2hip_amb_t h, int32_t *delay, double *doppler);
 #define BLAH2HIP_OPT_HOT_COLUMNS 8    /* fp64 Doppler transform of the delay columns that hold a peak more than 250x (24 dB) above the map's
                                        * mean level (csrc/capi.hip, "hot columns"): the fp32 transform leaves up to 1.2e-7 of a column's peak
                                        * in that column's other rows, which behind the clutter filter (the floor 8x down, a target 1400x above
-                                       * it at 10 MS/s) is 1.7e-4 of a mean-level cell.  At most 16 columns a CPI, found from four pulses of
-                                       * the range map.  1 (default): CPIs of >= 35 000 samples (a shorter one cannot hold such a peak);
+                                       * it at 10 MS/s) is 1.7e-4 of a mean-level cell.  At most 16 columns a CPI
+                                       * (BLAH2HIP_INFO_HOT_COLUMNS_MISSED counts the rest), found from the range map: the
+                                       * larger of two sample standard deviations of the column, over S contiguous pulses and
+                                       * over S evenly spaced ones (S = 32 up to nD = 1025, else 48), reads at least 0.8 of a
+                                       * tone's amplitude at every Doppler (nD <= 4096), and the test is lowered by that factor.
+                                       * 1 (default): CPIs of >= 35 000 samples (a shorter one cannot hold such a peak);
                                        * 2: every call; 0: never.  No reference counterpart (the reference computes in fp64). */
 #define BLAH2HIP_CFAR2D_AUTO 0
 #define BLAH2HIP_CFAR2D_TILE 1
@@ -190,6 +194,9 @@ int blah2hip_amb_set_option(blah2hip_amb_t h, int option, int64_t value);
 #define BLAH2HIP_INFO_LEAK_MAX_E12 9         /* 1e12 x the largest |g| measured for the kernel pair the last call ran (0 = not measurable: no
                                               * zero-Doppler row / lag-0 column, rotated reference channel, chunked lag window) */
 #define BLAH2HIP_INFO_HOT_COLUMNS 10          /* columns of the last call's first CPI rewritten in fp64 (BLAH2HIP_OPT_HOT_COLUMNS); waits for that call's stream */
+#define BLAH2HIP_INFO_HOT_COLUMNS_MISSED 11   /* the most columns of any CPI of the last call that passed the hot-column test and were NOT
+                                               * rewritten -- beyond the 16 a CPI, or beyond 64 candidates in one quarter of the lags:
+                                               * they keep the fp32 floor; waits for that call's stream */
 #define BLAH2HIP_INFO_DOPPLER_TILES 7       /* tiles (units of work the persistent workgroups walk) of the last Doppler launch; 0 for the
                                              * non-persistent kernels */
 int blah2hip_amb_get_info(blah2hip_amb_t h, int key, int64_t *value);
