@@ -122,6 +122,7 @@ SYMBOLS = {
     "blah2hip_ctx_d2h": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
     "blah2hip_ctx_d2d": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
     "blah2hip_stream_read_dev": (C.c_int, [_vp, C.c_size_t, _vp, _vp]),
+    "blah2hip_deblock_c32_dev": (C.c_int, [_vp, _u32, C.c_uint64, _u32, _u32, _vp, _vp, C.c_uint64, _vp]),
     "blah2hip_clutter_estimate_dev_fmt": (C.c_int, [_vp, C.c_int, _vp, _vp, _u32, C.c_uint64, _vp, _vp]),
     "blah2hip_clutter_taps_dev": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_u32), C.POINTER(_i32)]),
     "blah2hip_amb_set_fir": (C.c_int, [_vp, _vp, _u32, _i32]),

@@ -624,6 +624,12 @@ class SpectrumAnalyser:
         check(self._L.blah2hip_spectrum_process_dev(self._h, fmt, d_x, n_cpi, cpi_stride, d_out, stream))
 
 
+def deblock_c32_dev(d_raw, block, first, n_samples, n_cpi, d_x, d_y, cpi_stride, stream=0):
+    """Enqueue on ``stream``: the x and y planes [n_cpi][cpi_stride] complex64 of a USRP capture's channel-blocked fc32
+    bytes at d_raw (blocks of ``block`` samples, x block then y block); CPI i sample j is sample first + i*n_samples + j."""
+    check(_lib.load().blah2hip_deblock_c32_dev(d_raw, block, first, n_samples, n_cpi, d_x, d_y, cpi_stride, stream))
+
+
 def next_hamming(v: int) -> int:
     """src/process/meta/HammingNumber.cpp:38-48."""
     return int(_lib.load().blah2hip_next_hamming(v))

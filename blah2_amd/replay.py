@@ -1,4 +1,4 @@
-"""Offline replay of .rspduo captures, CPI-sharded across GPUs.
+"""Offline replay of blah2 captures (.rspduo and USRP), CPI-sharded across GPUs.
 
 The reference replays a capture by pushing int16 I1 Q1 I2 Q2 samples into the
 two IqData FIFOs (src/capture/rspduo/RspDuo.cpp:150-179) and the processing
@@ -8,6 +8,16 @@ products are emitted as soon as it is done, in order (blah2.cpp:299-321).
 Ambiguity, WienerHopf, CfarDetector1D and Map::set_metrics carry no state from
 one CPI to the next, so the capture shards over the ranks with NO data-path
 collective.
+
+A USRP capture (``YYYYmmdd-HHMMSS.usrp.iq``, Usrp.cpp:96-104) holds fc32 values
+in channel blocks: B complex<float> of the reference channel, then B of the
+surveillance channel, and so on, with B = UHD's get_max_num_samps, which the
+file does not record (:class:`UsrpFile` is told it).  A CPI starts and ends
+mid-block, but a batch of consecutive CPIs is still one contiguous byte range
+of whole block pairs; the device chain uploads that range as it is and one
+kernel (blah2hip_deblock_c32_dev) writes the two complex-fp32 planes the rest
+of the chain reads.  The reference itself cannot replay such a file
+(``Usrp::replay`` is empty, Usrp.cpp:108-111).
 
 The unit of work is a BATCH of `batch` consecutive CPIs (one contiguous read,
 one launch of the device chain).  Batch b belongs to rank b mod world; a ROUND
@@ -25,11 +35,13 @@ results of batch k-1 while the kernels of batch k run on the compute stream;
 HIP events order the three.
 At 16 MB of int16 per 1 s CPI the GPU needs 9 us for what PCIe needs 290 us to
 deliver: a replay is bound by the host link, and the pipeline's job is to keep
-that link busy (tools/replay_bench.py measures both).
+that link busy (tools/replay_bench.py measures both).  A USRP CPI is twice the
+bytes (fc32), so the same link carries half the CPIs per second.
 
 `processor` is a :class:`GpuChain`, or -- for the CPU tests of the sharding,
-which has no GPU dependency -- any callable ``(int16 array [B, nSamples, 4])
--> list of B result dicts``.
+which has no GPU dependency -- any callable that takes what the capture's
+``batch()`` returns (int16 [B, nSamples, 4] for .rspduo, complex64 [B, 2,
+nSamples] (x, y) for USRP) and returns a list of B result dicts.
 """
 from __future__ import annotations
 
@@ -45,31 +57,23 @@ from typing import Callable, Iterator, List, Optional, Tuple
 import numpy as np
 
 BYTES_PER_SAMPLE = 8  # int16 I1 Q1 I2 Q2
+FC32_BYTES = 8  # one complex<float> of a USRP capture
 PAGE = 4096
 _MADV_POPULATE_READ = 22  # Linux 5.14+
 _LIBC = C.CDLL(None, use_errno=True)
 _LIBC.madvise.argtypes = [C.c_void_p, C.c_size_t, C.c_int]
 
 
-class RspduoFile:
-    """A .rspduo capture, indexed by CPI (memory-mapped for random access; :meth:`read_into` for streaming)."""
+class _RawCapture:
+    """What the readers share: a file memory-mapped in ``_mm`` whose batches of consecutive CPIs are contiguous byte ranges
+    (:meth:`extent`), read out by :meth:`read_into` or exposed in place by :meth:`window`."""
 
-    def __init__(self, path: str, n_samples: int):
-        self.path = path
-        self.n_samples = int(n_samples)
-        size = os.path.getsize(path)
-        self.n_cpis = size // (self.n_samples * BYTES_PER_SAMPLE)
-        self._mm = np.memmap(path, dtype="<i2", mode="r") if size else np.zeros(0, dtype="<i2")
-        self._fd = None
+    layout = ""
 
-    def cpi(self, k: int) -> np.ndarray:
-        if not 0 <= k < self.n_cpis:
-            raise IndexError(k)
-        a = self._mm[k * self.n_samples * 4:(k + 1) * self.n_samples * 4]
-        return np.asarray(a).reshape(self.n_samples, 4)
-
-    def batch(self, ks) -> np.ndarray:
-        return np.stack([self.cpi(k) for k in ks]) if len(ks) else np.zeros((0, self.n_samples, 4), dtype=np.int16)
+    def extent(self, k0: int, count: int) -> Tuple[int, int, int]:
+        """(file offset, bytes, first) of CPIs k0 .. k0+count-1: the contiguous byte range a batch is read as, and the index
+        of CPI k0's first sample inside that range, counted in samples of one channel."""
+        raise NotImplementedError
 
     def read_into(self, k0: int, count: int, dst: np.ndarray, pool: Optional[ThreadPoolExecutor] = None, parts: int = 8,
                   how: str = "memmove"):
@@ -78,8 +82,7 @@ class RspduoFile:
         kernel fill the page tables of its piece (madvise MADV_POPULATE_READ: 47 GB/s per thread, against a fault per 64 KB)
         and copies it with memmove (non-temporal stores for large sizes): 12.5 GB/s per thread on the MI355X host;
         ``how="pread"``: the kernel's copy_to_user, 9.5 GB/s per thread.  PCIe takes 57."""
-        nbytes = count * self.n_samples * BYTES_PER_SAMPLE
-        off0 = k0 * self.n_samples * BYTES_PER_SAMPLE
+        off0, nbytes, _ = self.extent(k0, count)
         if how == "pread":
             if self._fd is None:
                 self._fd = os.open(self.path, os.O_RDONLY)
@@ -115,15 +118,113 @@ class RspduoFile:
     def window(self, k0: int, count: int) -> Tuple[int, int]:
         """(address, bytes) of CPIs k0 .. k0+count-1 inside the read-only shared mapping of the file: the page cache's own
         pages, which the zero-copy read path registers with the device and uploads from (``GpuChain(read_mode="mapped")``)."""
-        nbytes = count * self.n_samples * BYTES_PER_SAMPLE
-        off0 = k0 * self.n_samples * BYTES_PER_SAMPLE
+        off0, nbytes, _ = self.extent(k0, count)
         return self._mm.ctypes.data + off0, nbytes
 
     def close(self):
         if self._fd is not None:
             os.close(self._fd)
             self._fd = None
-        self._mm = np.zeros(0, dtype="<i2")  # the mapping goes with its last reference (anything registered of it must be released first)
+        self._mm = np.zeros(0, dtype=self._mm.dtype)  # the mapping goes with its last reference (anything registered of it must be released first)
+
+
+class RspduoFile(_RawCapture):
+    """A .rspduo capture, indexed by CPI (memory-mapped for random access; :meth:`read_into` for streaming)."""
+
+    layout = "rspduo"
+
+    def __init__(self, path: str, n_samples: int):
+        self.path = path
+        self.n_samples = int(n_samples)
+        size = os.path.getsize(path)
+        self.n_cpis = size // (self.n_samples * BYTES_PER_SAMPLE)
+        self._mm = np.memmap(path, dtype="<i2", mode="r") if size else np.zeros(0, dtype="<i2")
+        self._fd = None
+
+    def cpi(self, k: int) -> np.ndarray:
+        if not 0 <= k < self.n_cpis:
+            raise IndexError(k)
+        a = self._mm[k * self.n_samples * 4:(k + 1) * self.n_samples * 4]
+        return np.asarray(a).reshape(self.n_samples, 4)
+
+    def batch(self, ks) -> np.ndarray:
+        return np.stack([self.cpi(k) for k in ks]) if len(ks) else np.zeros((0, self.n_samples, 4), dtype=np.int16)
+
+    def extent(self, k0: int, count: int) -> Tuple[int, int, int]:
+        """CPI k is file bytes [k*nSamples*8, (k+1)*nSamples*8): whole records, ``first`` is 0."""
+        return k0 * self.n_samples * BYTES_PER_SAMPLE, count * self.n_samples * BYTES_PER_SAMPLE, 0
+
+
+def usrp_deblock(raw: np.ndarray, block: int, first: int, n_samples: int, n_cpi: int) -> np.ndarray:
+    """complex64 [n_cpi, 2, n_samples]: (x, y) of CPI i, sample j = sample first + i*n_samples + j of each channel of
+    ``raw``, the complex64 values of a USRP capture's byte range (blocks of ``block`` x samples, then ``block`` y
+    samples: sample s of channel c is value (s // block) * 2*block + c*block + s % block).  The NumPy statement of
+    blah2hip_deblock_c32_dev: an exact copy."""
+    B = int(block)
+    s = int(first) + np.arange(int(n_cpi) * int(n_samples), dtype=np.int64)
+    at = (s // B) * (2 * B) + s % B
+    out = np.empty((int(n_cpi), 2, int(n_samples)), dtype=np.complex64)
+    out[:, 0] = raw[at].reshape(n_cpi, n_samples)
+    out[:, 1] = raw[at + B].reshape(n_cpi, n_samples)
+    return out
+
+
+class UsrpFile(_RawCapture):
+    """A USRP capture (Usrp.cpp:96-104: per recv(), ``block`` complex<float> of the reference channel x, then ``block`` of
+    the surveillance channel y), indexed by CPI.  ``block`` is UHD's get_max_num_samps for the device and transport the
+    capture was recorded with; the file does not record it.  Every block is taken as full: the writer pads a short
+    recv() with stale values that the file cannot tell apart.  A trailing partial block pair belongs to no CPI.
+
+    :meth:`cpi` and :meth:`batch` return complex64 [2, n] and [len, 2, n] (x, y); :meth:`read_into` and :meth:`window`
+    give a batch's raw bytes (whole block pairs, :meth:`extent`), which the device chain de-blocks itself."""
+
+    layout = "usrp"
+
+    def __init__(self, path: str, n_samples: int, block: int):
+        self.path = path
+        self.n_samples = int(n_samples)
+        self.block = int(block)
+        if self.n_samples <= 0 or self.block <= 0:
+            raise ValueError(f"UsrpFile: n_samples ({n_samples}) and block ({block}) must be positive")
+        size = os.path.getsize(path)
+        pairs = size // (2 * self.block * FC32_BYTES)
+        self.n_cpis = pairs * self.block // self.n_samples
+        self._mm = np.memmap(path, dtype=np.uint8, mode="r") if size else np.zeros(0, dtype=np.uint8)
+        self._fd = None
+
+    def extent(self, k0: int, count: int) -> Tuple[int, int, int]:
+        """Whole block pairs floor(k0*n / B) .. floor(((k0+count)*n - 1) / B); ``first`` = k0*n mod B."""
+        if k0 < 0 or count < 0 or k0 + count > self.n_cpis:
+            raise IndexError((k0, count))
+        n, B = self.n_samples, self.block
+        p0 = k0 * n // B
+        p1 = ((k0 + count) * n - 1) // B + 1 if count else p0
+        return p0 * 2 * B * FC32_BYTES, (p1 - p0) * 2 * B * FC32_BYTES, k0 * n - p0 * B
+
+    def batch(self, ks) -> np.ndarray:
+        ks = list(ks)
+        if not ks:
+            return np.zeros((0, 2, self.n_samples), dtype=np.complex64)
+        if ks == list(range(ks[0], ks[0] + len(ks))):  # consecutive (every batch replay() asks for): one pass
+            off, nb, first = self.extent(ks[0], len(ks))
+            return usrp_deblock(self._mm[off:off + nb].view("<c8"), self.block, first, self.n_samples, len(ks))
+        return np.stack([self.cpi(k) for k in ks])
+
+    def cpi(self, k: int) -> np.ndarray:
+        if not 0 <= k < self.n_cpis:
+            raise IndexError(k)
+        return self.batch([k])[0]
+
+
+def open_capture(path: str, n_samples: int, layout: str = "rspduo", usrp_block: Optional[int] = None) -> _RawCapture:
+    """The reader for a capture of ``layout`` ("rspduo" or "usrp", the latter with its block length)."""
+    if layout == "rspduo":
+        return RspduoFile(path, n_samples)
+    if layout == "usrp":
+        if usrp_block is None:
+            raise ValueError("a USRP capture needs its block length (UHD's get_max_num_samps)")
+        return UsrpFile(path, n_samples, usrp_block)
+    raise ValueError(f"capture layout {layout!r}: 'rspduo' or 'usrp'")
 
 
 class LoopedCapture(RspduoFile):
@@ -187,7 +288,7 @@ def shard_batches(n_cpis: int, batch: int, rank: int, world: int) -> List[Tuple[
     return [(b * batch, min(batch, n_cpis - b * batch)) for b in range(rank, n_batches, world)]
 
 
-def _iter_local(capture: RspduoFile, processor, mine) -> Iterator[List[dict]]:
+def _iter_local(capture: _RawCapture, processor, mine) -> Iterator[List[dict]]:
     """Results of this rank's batches, one list per batch, in order."""
     if hasattr(processor, "run_batches"):  # the pipelined device chain
         yield from processor.run_batches(capture, mine)
@@ -226,7 +327,7 @@ def _gather_bytes(dist, group, payload: bytes, rank: int, world: int) -> Optiona
     return [bytes(p[:int(sz.item())].numpy().tobytes()) for p, sz in zip(parts, sizes)]
 
 
-def replay(capture: RspduoFile, processor, batch: int = 1, dist=None, limit: Optional[int] = None,
+def replay(capture: _RawCapture, processor, batch: int = 1, dist=None, limit: Optional[int] = None,
            emit: Optional[Callable[[dict], None]] = None, serialise: Optional[Callable[[dict], dict]] = None,
            stats: Optional[dict] = None) -> Optional[List[dict]]:
     """Processes every CPI of ``capture`` exactly once across the ranks of ``dist`` (a torch.distributed module with an
@@ -362,10 +463,22 @@ class GpuChain:
     Batch k+1's read and upload and batch k-1's download overlap batch k's kernels.
 
     A CPI whose clutter filter fails (normal equations not positive definite) is SKIPPED like the reference does
-    (``if (!filter->process(x, y)) continue;`` blah2.cpp:270-273): its result is ``{"skipped": True}``."""
+    (``if (!filter->process(x, y)) continue;`` blah2.cpp:270-273): its result is ``{"skipped": True}``.
+
+    ``layout`` is the capture layout the chain replays: "rspduo" (int16 I1 Q1 I2 Q2, read by the kernels as it is) or
+    "usrp" with its block length ``usrp_block`` (:class:`UsrpFile`).  A USRP batch is uploaded as its raw bytes; on the
+    compute stream blah2hip_deblock_c32_dev writes them into one pair of complex-fp32 planes [batch, n] (shared by the
+    slots, like the filtered channel) and the FMT_C32 chain runs on those."""
 
     def __init__(self, cfg: dict, device: int = 0, batch: int = 1, want_map: bool = False, depth: int = 3,
-                 reader_threads: int = 4, hit_copy: int = 4096, read_mode: str = "memmove", numa: bool = True):
+                 reader_threads: int = 4, hit_copy: int = 4096, read_mode: str = "memmove", numa: bool = True,
+                 layout: str = "rspduo", usrp_block: Optional[int] = None):
+        if layout not in ("rspduo", "usrp"):
+            raise ValueError(f"layout {layout!r}: 'rspduo' or 'usrp'")
+        if layout == "usrp" and (usrp_block is None or int(usrp_block) <= 0):
+            raise ValueError("a USRP chain needs the capture's block length (usrp_block > 0)")
+        self.layout = layout
+        self.usrp_block = int(usrp_block) if layout == "usrp" else None
         import torch
 
         import blah2_amd
@@ -423,7 +536,7 @@ class GpuChain:
             self.wh = blah2_amd.WienerHopf(clu_c["delayMin"], clu_c["delayMax"], n, device=device, max_batch=B)
             # the filter's FIR inside the range kernel where one 4096-point transform covers the geometry (range_fir_kernel):
             # the filtered channel never crosses HBM.  clutter: {fused: false} keeps the two-stage chain.
-            self.fused_fir = bool(clu_c.get("fused", True)) and self.amb.fir_fusable(self.wh, blah2_amd.FMT_I16) is None
+            self.fused_fir = bool(clu_c.get("fused", True)) and self.amb.fir_fusable(self.wh, self._fmt_in()) is None
             if self.fused_fir:
                 self.amb.set_fir(self.wh)
         self.cfar = self.centroid = self.interp = None
@@ -461,6 +574,10 @@ class GpuChain:
             self.read_mode = "memmove"
         # the filtered surveillance channel (one buffer: the compute stream is in order)
         self.yf = torch.empty((B, n), dtype=torch.complex64, device=dev) if self.wh is not None and not self.fused_fir else None
+        # USRP: a batch's raw bytes are whole block pairs, at most B*n*16 + 32*block of them (a CPI run that starts and ends
+        # mid-block); the de-blocked x and y planes are one pair for all slots, like yf
+        self.raw_bytes = -(-(B * n * 2 * FC32_BYTES + 4 * self.usrp_block * FC32_BYTES) // 16) * 16 if self.layout == "usrp" else None
+        self.planes = torch.empty((2, B, n), dtype=torch.complex64, device=dev) if self.layout == "usrp" else None
         self.busy_ms, self.batches_done = 0.0, 0  # kernels' time on the compute stream / batches collected, since construction
         self.slots = []
         for _ in range(self.depth):
@@ -468,7 +585,9 @@ class GpuChain:
                 "h_iq": None,  # pinned staging batch of the pread path, allocated when that path first runs
                 "h_ends": torch.empty(2 * PAGE, dtype=torch.uint8).pin_memory(),  # the ragged ends of a mapped batch
                 "registered": [],
-                "d_iq": torch.empty((B, n, 4), dtype=torch.int16, device=dev),
+                "d_iq": torch.empty((B, n, 4), dtype=torch.int16, device=dev) if self.layout == "rspduo" else
+                        torch.empty(self.raw_bytes, dtype=torch.uint8, device=dev),
+                "first": 0,  # the batch's first sample inside its raw bytes (UsrpFile.extent)
                 "d_met": torch.zeros((B, 2), dtype=torch.float64, device=dev),
                 "d_ok": torch.ones(B, dtype=torch.int32, device=dev),
                 "d_hits": torch.zeros((B, self.cap, 2), dtype=torch.float64, device=dev),  # blah2hip_hit_t records, 16 bytes
@@ -486,9 +605,28 @@ class GpuChain:
             }
             self.slots.append(s)
 
+    def _fmt_in(self):
+        """The format the filter and the range kernel read: the .rspduo words, or the de-blocked USRP planes."""
+        return self.b2.FMT_I16 if self.layout == "rspduo" else self.b2.FMT_C32
+
+    def _host_batch(self):
+        """The pinned staging batch of the copying read paths."""
+        with self._on_node():
+            if self.layout == "rspduo":
+                return self.torch.empty((self.batch, self.n, 4), dtype=self.torch.int16).pin_memory()
+            return self.torch.empty(self.raw_bytes, dtype=self.torch.uint8).pin_memory()
+
+    def _check_capture(self, capture):
+        layout = getattr(capture, "layout", "rspduo")
+        if layout != self.layout:
+            raise ValueError(f"a {self.layout} chain was handed a {layout} capture")
+        if layout == "usrp" and capture.block != self.usrp_block:
+            raise ValueError(f"USRP capture of block {capture.block} handed to a chain built for block {self.usrp_block}")
+
     # -- the three stages of one batch -------------------------------------------------
-    def _read(self, capture: RspduoFile, slot: dict, k0: int, cnt: int):
+    def _read(self, capture: _RawCapture, slot: dict, k0: int, cnt: int):
         slot["mapped"] = None
+        _, slot["nbytes"], slot["first"] = capture.extent(k0, cnt)
         if self.read_mode == "mapped":
             addr, nbytes = capture.window(k0, cnt)
             head, pieces, tail = page_split(addr, nbytes, self.reader_threads)
@@ -514,8 +652,7 @@ class GpuChain:
             print(f"[blah2_amd.replay] hipHostRegister of the mapped capture failed ({hip.hipGetErrorString(max(rcs)).decode()}): "
                   "copying into a pinned buffer instead", file=sys.stderr)
         if slot["h_iq"] is None:
-            with self._on_node():
-                slot["h_iq"] = self.torch.empty((self.batch, self.n, 4), dtype=self.torch.int16).pin_memory()
+            slot["h_iq"] = self._host_batch()
         capture.read_into(k0, cnt, slot["h_iq"].numpy(), self.pool, self.reader_threads, how=self.read_mode)
 
     def _release(self, slot: dict):
@@ -536,22 +673,30 @@ class GpuChain:
                         rc = hip.hipMemcpyAsync(dst + o, src, ln, 1, st)  # hipMemcpyHostToDevice
                         if rc:
                             raise RuntimeError(f"hipMemcpyAsync from the mapped capture: {hip.hipGetErrorString(rc).decode()}")
-            else:
+            elif self.layout == "rspduo":
                 slot["d_iq"][:cnt].copy_(slot["h_iq"][:cnt], non_blocking=True)
+            else:
+                nb = slot["nbytes"]
+                slot["d_iq"][:nb].copy_(slot["h_iq"][:nb], non_blocking=True)
             slot["uploaded"].record(self.copy)
         with torch.cuda.stream(self.compute):
             self.compute.wait_event(slot["uploaded"])
             slot["started"].record(self.compute)
             st = self.compute.cuda_stream
             iq = slot["d_iq"].data_ptr()
+            if self.layout == "rspduo":  # the kernels read the .rspduo words
+                fmt, fmt_yf, x, y = b2.FMT_I16, b2.FMT_I16X_C32Y, iq, None
+            else:  # USRP: the batch's block pairs into the x and y planes first
+                fmt, fmt_yf, x, y = b2.FMT_C32, b2.FMT_C32, self.planes[0].data_ptr(), self.planes[1].data_ptr()
+                b2.deblock_c32_dev(iq, self.usrp_block, slot["first"], n, cnt, x, y, n, st)
             if self.wh is None:
-                amb.process_dev(b2.FMT_I16, iq, 0, cnt, n, slot["d_map"].data_ptr(), slot["d_met"].data_ptr(), st)
+                amb.process_dev(fmt, x, y, cnt, n, slot["d_map"].data_ptr(), slot["d_met"].data_ptr(), st)
             elif self.fused_fir:
-                self.wh.estimate_dev_fmt(b2.FMT_I16, iq, None, cnt, n, slot["d_ok"].data_ptr(), st)
-                amb.process_dev(b2.FMT_I16, iq, None, cnt, n, slot["d_map"].data_ptr(), slot["d_met"].data_ptr(), st)
+                self.wh.estimate_dev_fmt(fmt, x, y, cnt, n, slot["d_ok"].data_ptr(), st)
+                amb.process_dev(fmt, x, y, cnt, n, slot["d_map"].data_ptr(), slot["d_met"].data_ptr(), st)
             else:
-                self.wh.process_dev_fmt(b2.FMT_I16, iq, None, cnt, n, self.yf.data_ptr(), n, slot["d_ok"].data_ptr(), st)
-                amb.process_dev(b2.FMT_I16X_C32Y, iq, self.yf.data_ptr(), cnt, n, slot["d_map"].data_ptr(),
+                self.wh.process_dev_fmt(fmt, x, y, cnt, n, self.yf.data_ptr(), n, slot["d_ok"].data_ptr(), st)
+                amb.process_dev(fmt_yf, x, self.yf.data_ptr(), cnt, n, slot["d_map"].data_ptr(),
                                 slot["d_met"].data_ptr(), st)
             if self.cfar is not None:
                 self.cfar.process_dev(amb, cnt, slot["d_hits"].data_ptr(), self.cap, slot["d_cnt"].data_ptr(),
@@ -601,13 +746,14 @@ class GpuChain:
             res.append(r)
         return res
 
-    def run_batches(self, capture: RspduoFile, batches) -> Iterator[List[dict]]:
+    def run_batches(self, capture: _RawCapture, batches) -> Iterator[List[dict]]:
         """The pipeline over this rank's batches: yields each batch's results in order.  Up to ``depth`` batches are in
         flight; batch i's slot is reused by batch i + depth.  A slot has two halves with different lifetimes: its INPUT
         (the pinned batch, or the registered pages) is free as soon as the upload has completed, its RESULT buffers when the
         batch has been collected -- so the read of the next batch is started (on a background thread that drives the reader
         threads) the moment the previous read has ended, before this thread enqueues, synchronises, converts and yields:
-        the reader threads never wait for Python."""
+        the reader threads never wait for Python.  A capture of another layout than the chain's is a ValueError."""
+        self._check_capture(capture)
         batches = list(batches)
         D, n = self.depth, len(batches)
         reads = {}
@@ -640,12 +786,14 @@ class GpuChain:
             self.release_all()
 
     def __call__(self, iq: np.ndarray) -> List[dict]:
-        """One batch, synchronously, from a host array [B, nSamples, 4] (tests; a caller that has the samples in memory)."""
+        """One batch, synchronously, from a host array [B, nSamples, 4] (tests; a caller that has the samples in memory).
+        .rspduo chains only."""
+        if self.layout != "rspduo":
+            raise ValueError("GpuChain(...)(iq) takes .rspduo int16 samples; a USRP chain replays a UsrpFile")
         cnt = iq.shape[0]
         slot = self.slots[0]
         if slot["h_iq"] is None:
-            with self._on_node():
-                slot["h_iq"] = self.torch.empty((self.batch, self.n, 4), dtype=self.torch.int16).pin_memory()
+            slot["h_iq"] = self._host_batch()
         slot["h_iq"][:cnt].copy_(self.torch.from_numpy(np.ascontiguousarray(iq)))
         slot["mapped"] = None
         self._submit(slot, cnt)
@@ -693,14 +841,26 @@ def send_frame(sock, doc: str):
         sock.sendall(raw[i:i + MTU])
 
 
+def config_layout(y: dict) -> str:
+    """The capture layout a blah2 config.yml records with: "usrp" for capture.device.type Usrp, else "rspduo" (the
+    RspDuo's, and the default of a config that names no device; blah2's other drivers save no captures)."""
+    dev = ((y or {}).get("capture") or {}).get("device") or {}
+    return "usrp" if str(dev.get("type", "")).lower() == "usrp" else "rspduo"
+
+
 def main(argv=None):
     import argparse
     import socket
 
     import yaml
-    ap = argparse.ArgumentParser(description="CPI-sharded replay of a .rspduo capture on MI355X")
+    ap = argparse.ArgumentParser(description="CPI-sharded replay of a blah2 capture (.rspduo or USRP) on MI355X")
     ap.add_argument("capture")
     ap.add_argument("-c", "--config", required=True, help="blah2 config.yml")
+    ap.add_argument("--format", choices=("rspduo", "usrp"), default=None,
+                    help="capture layout (default: from the config's capture.device.type, Usrp or RspDuo)")
+    ap.add_argument("--usrp-block", type=int, default=None, metavar="B",
+                    help="USRP captures: samples per channel block, the get_max_num_samps UHD reported when the capture "
+                         "was recorded (the file does not hold it)")
     ap.add_argument("--batch", type=int, default=4)
     ap.add_argument("--limit", type=int, default=None)
     ap.add_argument("--json", action="store_true",
@@ -711,6 +871,12 @@ def main(argv=None):
                          "framed like Socket::sendData, instead of printing them")
     a = ap.parse_args(argv)
     y = yaml.safe_load(open(a.config))
+    layout = a.format or config_layout(y)
+    if layout == "usrp" and a.usrp_block is None:
+        ap.error("a USRP capture needs --usrp-block B (UHD's get_max_num_samps for the device and transport it was "
+                 "recorded with)")
+    if a.usrp_block is not None and (layout != "usrp" or a.usrp_block <= 0):
+        ap.error("--usrp-block takes a positive block length, for USRP captures only")
     fs = int(y["capture"]["fs"])
     n = int(fs * float(y["process"]["data"]["cpi"]))  # blah2.cpp:142-144
     cfg = dict(y["process"], fs=fs, n_samples=n)
@@ -723,7 +889,8 @@ def main(argv=None):
         dist_.init_process_group("nccl" if torch.cuda.device_count() >= int(os.environ["WORLD_SIZE"]) else "gloo")
         dist = dist_
     import torch
-    proc = gpu_processor(cfg, local % max(1, torch.cuda.device_count()), a.batch, want_map=a.json)
+    proc = gpu_processor(cfg, local % max(1, torch.cuda.device_count()), a.batch, want_map=a.json, layout=layout,
+                         usrp_block=a.usrp_block)
     rank0 = dist is None or dist.get_rank() == 0
     socks = {}
     if rank0 and a.json and a.connect:
@@ -752,7 +919,7 @@ def main(argv=None):
                 sys.stdout.write(doc + "\n")
         sys.stdout.flush()
 
-    replay(RspduoFile(a.capture, n), proc, a.batch, dist, a.limit, emit=emit, serialise=serialise)
+    replay(open_capture(a.capture, n, layout, a.usrp_block), proc, a.batch, dist, a.limit, emit=emit, serialise=serialise)
     for s in socks.values():
         s.close()
     proc.close()

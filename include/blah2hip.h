@@ -443,6 +443,20 @@ int blah2hip_ctx_d2d(blah2hip_ctx_t c, void *dst, const void *src, size_t bytes)
  * (16-byte aligned) and does nothing else -- the streaming-read rate of the memory system, which bench.py reports
  * beside the copy rate as the ceiling for the range kernel's loads.  d_sink: 4 device bytes, never written, or NULL. */
 int blah2hip_stream_read_dev(const void *d_src, size_t bytes, void *d_sink, void *stream);
+/* ---- USRP captures --------------------------------------------------------
+ * blah2's USRP driver records a two-channel fc32 stream (Usrp.cpp:96-104): per recv() it writes samps_per_buff =
+ * B complex<float> of the reference channel x, then B of the surveillance channel y, so sample s of channel c
+ * (0 = x, 1 = y) is complex value (s / B) * 2B + c * B + s % B of the file.  B (UHD's get_max_num_samps) is not in
+ * the file.  The writer writes all B values even when recv() returned fewer, so such a block ends in stale values;
+ * nothing in the file marks it and every block is taken as full.
+ * x plane [n_cpi][cpi_stride] and y plane: CPI i sample j = sample (first + i*n_samples + j) of the channel-blocked
+ * fc32 buffer d_raw (blocks of `block` complex values, x block then y block).  Enqueue-only on `stream`.
+ * Bit-exact copy into BLAH2HIP_FMT_C32 planes; writes n_samples elements per row and nothing beyond.  16-byte accesses
+ * when block, first, n_samples and cpi_stride are even and the three pointers 16-byte aligned, 8-byte ones otherwise.
+ * BLAH2HIP_ERR_INVALID, with nothing enqueued: NULL pointer, block == 0, n_samples == 0, cpi_stride < n_samples with
+ * n_cpi > 1.  n_cpi == 0 enqueues nothing. */
+int blah2hip_deblock_c32_dev(const void *d_raw, uint32_t block, uint64_t first, uint32_t n_samples, uint32_t n_cpi,
+                             void *d_x, void *d_y, uint64_t cpi_stride, void *stream);
 /* device pointers of a handle's internal results of the last blah2hip_amb_process_dev with NULL outputs:
  * map [max_batch][n_doppler][n_delay] complex fp32 and metrics [max_batch][2] doubles */
 int blah2hip_amb_result_ptrs(blah2hip_amb_t h, const void **d_map, const double **d_metrics);
