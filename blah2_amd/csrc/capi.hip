@@ -542,6 +542,7 @@ bool doppler_kernel_applicable(const blah2hip_amb_s *h, int which)
   case BLAH2HIP_DOP_TILE16WG:
   case BLAH2HIP_DOP_SUB4:
   case BLAH2HIP_DOP_TILE16: return h->dopR3 == 4;
+  case BLAH2HIP_DOP_PFA513: return h->dopR3 == 4 && nD == DOPP_ND;
   case BLAH2HIP_DOP_TILEM: return (h->dopR3 == 8 && nD <= DopM<8>::MAX_ND) || (h->dopR3 == 16 && nD <= DopM<16>::MAX_ND);
   case BLAH2HIP_DOP_TILEW: return h->dopR3 == 8 && nD <= DOPW_MAX_ND;
   case BLAH2HIP_DOP_TILEW2: return h->dopR3 == 16 && nD <= DOPW2_MAX_ND;
@@ -562,6 +563,10 @@ int pick_doppler(const blah2hip_amb_s *h, uint32_t n_cpi)
   const bool fills = (int)n_cpi * tiles >= h->numCU / 2;
   // nD <= 513: whole 16-column tiles (128-byte row pieces, one persistent workgroup per CU) once a launch has
   // a tile per CU (cfg 2 x 128: 1.49 vs 1.59 us/CPI); 8-column half tiles, two workgroups per CU, below
+  // nD = 513 (BASELINE configs[1]): the prime-factor transform in place of the chirp-z one once a launch has a whole tile
+  // for each of its two workgroups per CU
+  if (h->dopR3 == 4 && (int)n_cpi * ((nDelay + 15) / 16) >= 2 * h->numCU && doppler_kernel_applicable(h, BLAH2HIP_DOP_PFA513))
+    return BLAH2HIP_DOP_PFA513;
   if (h->dopR3 == 4 && (int)n_cpi * ((nDelay + 15) / 16) >= h->numCU) return BLAH2HIP_DOP_TILE16;
   if (fills && h->dopR3 == 4) return BLAH2HIP_DOP_TILE8;
   if (h->dopR3 == 4) return BLAH2HIP_DOP_SUB4; // a lone CPI: every CU gets a 4-column piece
@@ -1565,6 +1570,17 @@ int blah2hip_amb_process_dev(blah2hip_amb_t h, int fmt, const void *d_x, const v
       LDSCFG(doppler_tile_kernel<8>, lds);
       hipLaunchKernelGGL(doppler_tile_kernel<8>, dim3(wgs), dim3(512), lds, st, da, (int)n_cpi);
     }
+    nPartsUsed = grid;
+    break;
+  }
+  case BLAH2HIP_DOP_PFA513: {
+    // persistent: two workgroups per CU (LDS: the sixteen 513-value column regions)
+    const int grid = (int)((nDelay + DOPP_NCOL - 1) / DOPP_NCOL);
+    const size_t lds = (size_t)DOPP_LDS_ELEMS * sizeof(cf);
+    const int wgs = (int)std::min<int64_t>((int64_t)grid * n_cpi, h->dopGridForce ? h->dopGridForce : 2 * h->numCU);
+    dopGrid = wgs; dopTiles = grid * (int)n_cpi;
+    LDSCFG(doppler_pfa513_kernel, lds);
+    hipLaunchKernelGGL(doppler_pfa513_kernel, dim3(wgs), dim3(DOPP_NT), lds, st, da, (int)n_cpi);
     nPartsUsed = grid;
     break;
   }

@@ -23,6 +23,7 @@
 #include "fft_wave.hpp"
 #include "fft_wave2.hpp"
 #include "fft_wave1k.hpp"
+#include "fft_pfa513.hpp"
 #include "bufload.hpp"
 #include "trace.hpp"
 
@@ -1617,6 +1618,118 @@ template <int NCOL> __global__ __launch_bounds__(64 * NCOL, 4) void doppler_tile
 #endif
 }
 #undef D1_T
+
+// doppler_tile1k_kernel<16> at nD = 513 on the prime-factor transform of fft_pfa513.hpp (27 x 19, no chirp, no zero
+// padding, no kernel-spectrum product).  Same walk, tile, DC removal, rotation and metrics order; what changes is the
+// column phase.  A column needs 27 lanes (step 1) and 19 lanes (step 2), so a wave takes TWO columns, one per 32-lane
+// half: 8 waves per 16-column tile.  No tables, so the LDS is the sixteen column regions alone (513 values each, which
+// are also the exchange regions: 64.1 KB) and TWO workgroups fit per CU -- four waves per SIMD, 128 registers, the same
+// occupancy as the 1024-thread chirp-z kernel at one workgroup per CU.  Each thread carries 17 of the tile's 8208
+// cells (the next tile's, in flight during the transforms).
+constexpr int DOPP_ND = 513, DOPP_NCOL = 16, DOPP_NT = 512, DOPP_NR = (DOPP_ND * DOPP_NCOL + DOPP_NT - 1) / DOPP_NT;
+constexpr int DOPP_LDS_ELEMS = DOPP_NCOL * DOPP_ND;
+__global__ __launch_bounds__(DOPP_NT, 4) void doppler_pfa513_kernel(DopplerArgs a, int nCpi)
+{
+  using K = Pfa513;
+  constexpr int ND = DOPP_ND, NCOL = DOPP_NCOL, NT = DOPP_NT, NR = DOPP_NR, RS = NT / NCOL; // RS: rows per pass
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  __shared__ double wsum[NT / 64];
+  __shared__ float wmax[NT / 64];
+  cf *lds = reinterpret_cast<cf *>(smem);
+  const int tid = threadIdx.x;
+  const int w = tid >> 6, l = tid & 31;          // wave; lane within the half wave
+  cf *region = lds + (2 * w + ((tid >> 5) & 1)) * ND; // this half wave's column
+  const int tilesPerCpi = (a.nDelay + NCOL - 1) / NCOL;
+  const int nTilesAll = tilesPerCpi * nCpi;
+  constexpr int cells = ND * NCOL;
+  // step-2 lane l: output k1 goes to row (out_index(k1, l) - (nD/2 + 1)) mod nD = (190 k1 + ob) mod nD
+  const int ob0 = (324 * l + ND - (ND / 2 + 1)) % ND;
+
+  cf nt[NR];
+  auto tile_load = [&](int it) {
+    const int cpi = it / tilesPerCpi, sub = it - cpi * tilesPerCpi;
+    const cf *Rt = a.R + rmap_index(ND, a.nTiles, cpi, 0, sub * NCOL);
+    const int tl = relaunder(tid);
+#pragma unroll
+    for (int j = 0; j < NR; j++) {
+      const int idx = tl + NT * j; // the 16-column tile is contiguous: cell = row * 16 + column
+      nt[j] = Rt[idx < cells ? idx : 0];
+    }
+  };
+  int it = blockIdx.x;
+  if (it < nTilesAll) tile_load(it);
+  for (; it < nTilesAll; it += gridDim.x) {
+    const int cpi = it / tilesPerCpi, sub = it - cpi * tilesPerCpi;
+    const int col0 = sub * NCOL;
+    // phase 1: the tile, transposed into the per-column regions
+    {
+      const int tl = relaunder(tid);
+      cf *dst = lds + (tl & (NCOL - 1)) * ND + (tl >> 4); // idx + 512 j: same column, row + 32 j
+#pragma unroll
+      for (int j = 0; j < NR; j++)
+        if (tl + NT * j < cells) dst[RS * j] = nt[j];
+    }
+    __syncthreads();
+
+    // phase 2: next tile's loads, then this half wave's column through the two steps (region = exchange region)
+    if (it + (int)gridDim.x < nTilesAll) tile_load(it + gridDim.x);
+    const cf r0 = region[0];
+    cf v[27];
+    // (lane-derived addresses are recomputed per tile: kept live across the walk, the 46 of them spill)
+    if (l < K::N1) {
+      const int l1 = relaunder(l);
+      K::load1(l1, region, r0, v);
+      K::dft19_store(v, region + l1);
+    }
+    __builtin_amdgcn_wave_barrier();
+    if (l < K::N2) {
+      K::load2(relaunder(l), region, v);
+      K::dft27(v);
+      if (l == 0) v[0] = cmake(v[0].x + (float)ND * r0.x, v[0].y + (float)ND * r0.y);
+      // phase 3: rotate rows by nD/2 + 1 and park the column back in its region
+      const unsigned ob = (unsigned)relaunder(ob0);
+#pragma unroll
+      for (int k1 = 0; k1 < K::N1; k1++) {
+        const unsigned o = ob + (unsigned)((190 * k1) % ND);
+        region[o < (unsigned)ND ? o : o - ND] = v[k1];
+      }
+    }
+    __syncthreads();
+
+    // phase 4: coalesced row-segment stores + Map::set_metrics partials
+    double lsum = 0.0;
+    float lmax = 0.f;
+    cf *mapb = a.map + (size_t)cpi * ND * a.nDelay + col0;
+    const int ncol = min(NCOL, a.nDelay - col0);
+    {
+      const int tl = relaunder(tid);
+      const int c = tl & (NCOL - 1), o0 = tl >> 4;
+      const cf *src = lds + c * ND + o0;
+      cf *dstg = mapb + (size_t)o0 * a.nDelay + c;
+      const size_t gstep = (size_t)RS * a.nDelay;
+#pragma unroll
+      for (int j = 0; j < NR; j++) {
+        const bool ok = tl + NT * j < cells && c < ncol;
+        const cf d = src[min(RS * j, ND - 1 - o0)];
+        if (ok) dstg[gstep * j] = d;
+        const float db = db_of(d);
+        lsum += ok ? (double)db : 0.0;
+        lmax = ok ? fmaxf(lmax, db) : lmax;
+      }
+    }
+    wave_sum_max(lsum, lmax);
+    if ((tid & 63) == 0) { const int wl = relaunder(tid) >> 6; wsum[wl] = lsum; wmax[wl] = lmax; }
+    __syncthreads(); // also: every thread has taken its rows out of the regions
+    if (tid == 0) {
+      double sacc = 0.0;
+      float m = 0.f; // Map.cpp:193: the running max starts at 0
+      for (int i = 0; i < NT / 64; i++) { sacc += wsum[i]; m = fmaxf(m, wmax[i]); }
+      const size_t part = (size_t)cpi * tilesPerCpi + sub;
+      a.partSum[part] = sacc;
+      a.partMax[part] = m;
+    }
+  }
+}
 
 // The reduction of metrics_kernel (below) by the 256 threads of a workgroup: the same order of operations, so that the
 // fused finish and the separate launch give the same bits.
