@@ -70,6 +70,33 @@ struct ChanF16 {
   }
 };
 
+// int8 (I, Q) pairs, 2 bytes per sample (HackRF / KrakenSDR planes, range_core.hpp InI8).  The first channel whose
+// windows start and end at any EVEN byte, not at a dword: a pulse starts at i*nCorr samples, a y window at
+// s*segLen + delayMin samples.  One buffer_load_ushort per sample (2-byte aligned, upper register half zero, so the
+// raw type stays a dword and whole-register reuse of overlapping windows carries over).  Probed on gfx950 with
+// tools/membench/bufprobe16.hip (2-byte accesses through a raw descriptor, base 2- and 4-byte aligned):
+// the range check is 2-byte granular -- the last sample (offset = num_records - 2, num_records ending mid-dword) is
+// returned, offset = num_records and beyond read 0; every negative offset reads 0, a negative voffset also whatever
+// soffset adds; the upper half of the register comes back zero; a base that is only 2-byte aligned changes nothing.
+// ONE case differs from the dword loads: with a NEGATIVE voffset and the rest in the immediate, the lane whose sum is
+// exactly 0 -- the pulse's first sample -- came back 0 in a full wave (voffset -512, offset:512; its neighbours at -2
+// and +2 were right, and so was a lone lane at -1000 + 1000).  With the whole offset in the VGPR and no immediate every
+// window probed (first sample -299, -43, -10, 1; both ends out of range) is exact.  So this channel's loads put
+// voffset + immediate + soffset into ONE register (a v_add per load) and the range check IS the zero padding here too;
+// no select on the sample index (mask_seg_x / mask_seg_y) was needed.
+struct ChanI8 {
+  static constexpr int STRIDE = 2;
+  using raw = uint32_t;
+  template <int IMM> static __device__ __forceinline__ void ld(raw &r, b2_v4i d, int voff, int soff)
+  {
+    // the whole offset in a VGPR (see above): the destination register holds it until the load replaces it
+    asm volatile("v_add_u32 %0, %4, %1\n\tv_add_u32 %0, %3, %0\n\tbuffer_load_ushort %0, %0, %2, 0 offen"
+                 : "=&v"(r) : "v"(voff), "s"(d), "s"(soff), "n"(IMM) : "memory");
+  }
+  // sign-extend each byte, then v_cvt_f32_i32: every int8 value is exact in fp32
+  static __device__ __forceinline__ cf cvt(raw r) { return cmake((float)(int8_t)(r & 0xffu), (float)(int8_t)((r >> 8) & 0xffu)); }
+};
+
 // the two channels of an input format: X = reference, Y = surveillance
 template <class In> struct BufLoad;
 template <> struct BufLoad<InC32> {
@@ -95,6 +122,19 @@ template <> struct BufLoad<InI16C32> {
   using Y = ChanC32;
   static __device__ __forceinline__ const void *xp(const InI16C32 &in, int64_t i) { return in.iq + 4 * i; }
   static __device__ __forceinline__ const void *yp(const InI16C32 &in, int64_t i) { return in.y + i; }
+};
+
+template <> struct BufLoad<InI8> {
+  using X = ChanI8;
+  using Y = ChanI8;
+  static __device__ __forceinline__ const void *xp(const InI8 &in, int64_t i) { return in.x + 2 * i; }
+  static __device__ __forceinline__ const void *yp(const InI8 &in, int64_t i) { return in.y + 2 * i; }
+};
+template <> struct BufLoad<InI8C32> {
+  using X = ChanI8;
+  using Y = ChanC32;
+  static __device__ __forceinline__ const void *xp(const InI8C32 &in, int64_t i) { return in.x + 2 * i; }
+  static __device__ __forceinline__ const void *yp(const InI8C32 &in, int64_t i) { return in.y + i; }
 };
 
 // wait until at most N of the loads issued so far are outstanding; r[0..E) are
@@ -154,6 +194,16 @@ template <> struct RawBuiltin<ChanF16> {
   using raw = unsigned;
   static __device__ __forceinline__ raw ld(__amdgpu_buffer_rsrc_t d, int voff, int soff) { return __builtin_amdgcn_raw_buffer_load_b32(d, voff, soff, 0); }
   static __device__ __forceinline__ cf cvt(raw r) { return ChanF16::cvt(r); }
+};
+template <> struct RawBuiltin<ChanI8> {
+  using raw = unsigned;
+  static __device__ __forceinline__ raw ld(__amdgpu_buffer_rsrc_t d, int voff, int soff)
+  {
+    int off = voff; // opaque: a constant part of a possibly negative voffset must not move to the immediate (see ChanI8);
+    asm volatile("" : "+v"(off)); // soffset is only ever used with voffset >= 0 (x windows)
+    return __builtin_amdgcn_raw_buffer_load_b16(d, off, soff, 0); // zero-extended: buffer_load_ushort
+  }
+  static __device__ __forceinline__ cf cvt(raw r) { return ChanI8::cvt(r); }
 };
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc_b(const void *base, int bytes)
 {

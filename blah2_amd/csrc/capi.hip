@@ -1058,6 +1058,7 @@ const char *fir_unfusable(const blah2hip_amb_s *h, int fmt, int nBins, int firDm
   const int L = 2048;
   const int nDelay = (int)h->dims.n_delay_bins;
   if (h->dims.fft_len != 4096) return "fused FIR: the handle's transform length must be 4096 (BLAH2HIP_OPT_FFT_LEN)";
+  if (fmt == BLAH2HIP_FMT_I8 || fmt == BLAH2HIP_FMT_I8X_C32Y) return "fused FIR: fp32 planes or int16 words, not BLAH2HIP_FMT_I8 (run the two-stage filter)";
   if (fmt != BLAH2HIP_FMT_C32 && fmt != BLAH2HIP_FMT_I16) return "fused FIR: fp32 planes or int16 words";
   if (h->chunks.size() != 1 || h->dopplerMin + h->dopplerMax != 0) return "fused FIR: one lag chunk, symmetric Doppler limits";
   if (nBins < 1 || nBins > L + 1 || nDelay > L + 1) return "fused FIR: at most 2049 taps and 2049 delay bins";
@@ -1391,7 +1392,8 @@ int blah2hip_amb_process_dev(blah2hip_amb_t h, int fmt, const void *d_x, const v
 {
   if (!h) return fail(BLAH2HIP_ERR_INVALID, "NULL handle");
   if (n_cpi == 0 || n_cpi > h->dims.max_batch) return fail(BLAH2HIP_ERR_INVALID, "n_cpi outside [1, max_batch]");
-  if (fmt != BLAH2HIP_FMT_C32 && fmt != BLAH2HIP_FMT_I16 && fmt != BLAH2HIP_FMT_F16 && fmt != BLAH2HIP_FMT_I16X_C32Y)
+  if (fmt != BLAH2HIP_FMT_C32 && fmt != BLAH2HIP_FMT_I16 && fmt != BLAH2HIP_FMT_F16 && fmt != BLAH2HIP_FMT_I16X_C32Y &&
+      fmt != BLAH2HIP_FMT_I8 && fmt != BLAH2HIP_FMT_I8X_C32Y)
     return fail(BLAH2HIP_ERR_INVALID, "unknown sample format");
   if (!d_x || (fmt != BLAH2HIP_FMT_I16 && !d_y)) return fail(BLAH2HIP_ERR_INVALID, "NULL input pointer");
 #ifndef B2_EXPERIMENT_ALIASED_CPIS // tools/gpu_cfg3_bytes.py: a timing experiment's build lets every CPI of a batch sit at the same addresses
@@ -1459,6 +1461,14 @@ int blah2hip_amb_process_dev(blah2hip_amb_t h, int fmt, const void *d_x, const v
       InI16C32 in{(const int16_t *)d_x, (const cf *)d_y};
       hipLaunchKernelGGL(rotate_kernel<InI16C32>, grid, dim3(256), 0, st, in, xo, yo,
                          (int64_t)cpi_stride, (int64_t)plane, nrot, m2, h->fs);
+    } else if (fmt == BLAH2HIP_FMT_I8) {
+      InI8 in{(const int8_t *)d_x, (const int8_t *)d_y};
+      hipLaunchKernelGGL(rotate_kernel<InI8>, grid, dim3(256), 0, st, in, xo, yo,
+                         (int64_t)cpi_stride, (int64_t)plane, nrot, m2, h->fs);
+    } else if (fmt == BLAH2HIP_FMT_I8X_C32Y) {
+      InI8C32 in{(const int8_t *)d_x, (const cf *)d_y};
+      hipLaunchKernelGGL(rotate_kernel<InI8C32>, grid, dim3(256), 0, st, in, xo, yo,
+                         (int64_t)cpi_stride, (int64_t)plane, nrot, m2, h->fs);
     } else {
       InI16 in{(const int16_t *)d_x};
       hipLaunchKernelGGL(rotate_kernel<InI16>, grid, dim3(256), 0, st, in, xo, yo,
@@ -1511,6 +1521,12 @@ int blah2hip_amb_process_dev(blah2hip_amb_t h, int fmt, const void *d_x, const v
         rc = launch_range(h, ra, in, st);
       } else if (fmt == BLAH2HIP_FMT_I16X_C32Y) {
         InI16C32 in{(const int16_t *)d_x, (const cf *)d_y};
+        rc = launch_range(h, ra, in, st);
+      } else if (fmt == BLAH2HIP_FMT_I8) {
+        InI8 in{(const int8_t *)d_x, (const int8_t *)d_y};
+        rc = launch_range(h, ra, in, st);
+      } else if (fmt == BLAH2HIP_FMT_I8X_C32Y) {
+        InI8C32 in{(const int8_t *)d_x, (const cf *)d_y};
         rc = launch_range(h, ra, in, st);
       } else {
         InI16 in{(const int16_t *)d_x};
@@ -1783,6 +1799,22 @@ int blah2hip_amb_process_i16(blah2hip_amb_t h, const int16_t *iq, uint32_t n, fl
   if ((rc = ensure_staging(h, bytes))) return rc;
   HIPCHK(hipMemcpyAsync(h->d_in, iq, bytes, hipMemcpyHostToDevice, h->stream));
   if ((rc = blah2hip_amb_process_dev(h, BLAH2HIP_FMT_I16, h->d_in, nullptr, 1, n, nullptr, nullptr, h->stream))) return rc;
+  return host_tail(h, map_out, metrics);
+}
+
+int blah2hip_amb_process_i8(blah2hip_amb_t h, const int8_t *x, const int8_t *y, uint32_t n, float *map_out,
+                            double *metrics)
+{
+  if (!h || !x || !y) return fail(BLAH2HIP_ERR_INVALID, "NULL argument");
+  if (n < h->dims.n_used) return fail(BLAH2HIP_ERR_UNDERFLOW, "Attempting to pop from an empty deque");
+  HIPCHK(hipSetDevice(h->device));
+  const size_t bytes = (size_t)n * 2; // the planes travel as they are: no widening on the host
+  int rc;
+  if ((rc = ensure_staging(h, 2 * bytes))) return rc;
+  char *dx = (char *)h->d_in, *dy = dx + bytes;
+  HIPCHK(hipMemcpyAsync(dx, x, bytes, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(dy, y, bytes, hipMemcpyHostToDevice, h->stream));
+  if ((rc = blah2hip_amb_process_dev(h, BLAH2HIP_FMT_I8, dx, dy, 1, n, nullptr, nullptr, h->stream))) return rc;
   return host_tail(h, map_out, metrics);
 }
 

@@ -104,6 +104,14 @@ struct I16Chan {
     return cmake((float)(int16_t)(w & 0xffffu), (float)(int16_t)(w >> 16));
   }
 };
+struct I8Chan { // a plane of int8 (I, Q) pairs (range_core.hpp InI8)
+  const int8_t *p;
+  __device__ __forceinline__ cf operator[](uint32_t i) const
+  {
+    const uint32_t w = *reinterpret_cast<const uint16_t *>(p + 2 * (size_t)i); // (I, Q) as one 2-byte load
+    return cmake((float)(int8_t)(w & 0xffu), (float)(int8_t)(w >> 8));
+  }
+};
 template <class In> struct ChanOf;
 template <> struct ChanOf<InC32> {
   using type = const cf *;
@@ -114,6 +122,11 @@ template <> struct ChanOf<InI16> {
   using type = I16Chan;
   static __device__ __forceinline__ type x(const void *px, const void *, int64_t i) { return I16Chan{(const int16_t *)px + 4 * i}; }
   static __device__ __forceinline__ type y(const void *px, const void *, int64_t i) { return I16Chan{(const int16_t *)px + 4 * i + 2}; }
+};
+template <> struct ChanOf<InI8> {
+  using type = I8Chan;
+  static __device__ __forceinline__ type x(const void *px, const void *, int64_t i) { return I8Chan{(const int8_t *)px + 2 * i}; }
+  static __device__ __forceinline__ type y(const void *, const void *py, int64_t i) { return I8Chan{(const int8_t *)py + 2 * i}; }
 };
 
 // one channel of a CPI as the raw-buffer channel type of bufload.hpp (sample stride, raw word, conversion)
@@ -130,6 +143,12 @@ template <> struct BufChanOf<InI16> {
   static __device__ __forceinline__ const void *x(const void *px, const void *, int64_t i) { return (const int16_t *)px + 4 * i; }
   static __device__ __forceinline__ const void *y(const void *px, const void *, int64_t i) { return (const int16_t *)px + 4 * i + 2; }
 };
+template <> struct BufChanOf<InI8> {
+  using X = ChanI8;
+  using Y = ChanI8;
+  static __device__ __forceinline__ const void *x(const void *px, const void *, int64_t i) { return (const int8_t *)px + 2 * i; }
+  static __device__ __forceinline__ const void *y(const void *, const void *py, int64_t i) { return (const int8_t *)py + 2 * i; }
+};
 // Does the window [src0, src0 + F) of the shifted reference channel map to ONE contiguous run of x, and where does it
 // start?  xs_index is i - sub from `thresh` on (then mod N): contiguous unless the window starts before `thresh` (or
 // before sample 0) or runs over the end of the CPI, which only the first and last windows of a CPI do.  *cnt = the samples
@@ -143,7 +162,7 @@ __device__ __forceinline__ bool xs_window_plain(int src0, int F, const XsMap &m,
 }
 
 struct CorrArgs {
-  const void *x, *y; // InC32: the two planes; InI16: x = the interleaved buffer, y unused
+  const void *x, *y; // InC32, InI8: the two planes; InI16: x = the interleaved buffer, y unused
   int64_t cpiStride;
   uint32_t N;
   XsMap xs;
@@ -1549,8 +1568,9 @@ int blah2hip_clutter_process_dev_fmt(blah2hip_clutter_t h, int fmt, const void *
                                      uint64_t cpi_stride, void *d_y_out, uint64_t out_stride, int32_t *d_ok, void *stream)
 {
   if (!h || !d_x || !d_y_out) CFAIL(BLAH2HIP_ERR_INVALID, "NULL argument");
-  if (fmt != BLAH2HIP_FMT_C32 && fmt != BLAH2HIP_FMT_I16) CFAIL(BLAH2HIP_ERR_INVALID, "clutter filter input: BLAH2HIP_FMT_C32 or BLAH2HIP_FMT_I16");
-  if (fmt == BLAH2HIP_FMT_C32 && !d_y) CFAIL(BLAH2HIP_ERR_INVALID, "NULL argument");
+  if (fmt != BLAH2HIP_FMT_C32 && fmt != BLAH2HIP_FMT_I16 && fmt != BLAH2HIP_FMT_I8)
+    CFAIL(BLAH2HIP_ERR_INVALID, "clutter filter input: BLAH2HIP_FMT_C32, BLAH2HIP_FMT_I16 or BLAH2HIP_FMT_I8");
+  if (fmt != BLAH2HIP_FMT_I16 && !d_y) CFAIL(BLAH2HIP_ERR_INVALID, "NULL argument");
   if (n_cpi == 0 || n_cpi > h->maxBatch) CFAIL(BLAH2HIP_ERR_INVALID, "n_cpi outside [1, max_batch]");
 #ifndef B2_EXPERIMENT_ALIASED_CPIS // tools/gpu_cfg3_bytes.py
   if (n_cpi > 1 && (cpi_stride < h->N || out_stride < h->N)) CFAIL(BLAH2HIP_ERR_INVALID, "cpi_stride / out_stride < nSamples");
@@ -1563,6 +1583,7 @@ int blah2hip_clutter_process_dev_fmt(blah2hip_clutter_t h, int fmt, const void *
   const int64_t cs = (int64_t)cpi_stride, os = (int64_t)out_stride;
   cf *yo = (cf *)d_y_out;
   if (h->subCorr) {
+    if (fmt == BLAH2HIP_FMT_I8) CFAIL(BLAH2HIP_ERR_UNSUPPORTED, "a long filter (more than 4081 taps) takes fp32 planes only, not BLAH2HIP_FMT_I8");
     if (fmt != BLAH2HIP_FMT_C32) CFAIL(BLAH2HIP_ERR_UNSUPPORTED, "a long filter (more than 4081 taps) takes fp32 planes only");
     return long_process(h, (const cf *)d_x, (const cf *)d_y, n_cpi, cs, yo, os, ok, st);
   }
@@ -1571,6 +1592,13 @@ int blah2hip_clutter_process_dev_fmt(blah2hip_clutter_t h, int fmt, const void *
     case 4: return launch_clutter<4, InI16>(h, d_x, nullptr, n_cpi, cs, yo, os, ok, st);
     case 8: return launch_clutter<8, InI16>(h, d_x, nullptr, n_cpi, cs, yo, os, ok, st);
     default: return launch_clutter<16, InI16>(h, d_x, nullptr, n_cpi, cs, yo, os, ok, st);
+    }
+  }
+  if (fmt == BLAH2HIP_FMT_I8) {
+    switch (h->r3) {
+    case 4: return launch_clutter<4, InI8>(h, d_x, d_y, n_cpi, cs, yo, os, ok, st);
+    case 8: return launch_clutter<8, InI8>(h, d_x, d_y, n_cpi, cs, yo, os, ok, st);
+    default: return launch_clutter<16, InI8>(h, d_x, d_y, n_cpi, cs, yo, os, ok, st);
     }
   }
   switch (h->r3) {
@@ -1584,8 +1612,9 @@ int blah2hip_clutter_estimate_dev_fmt(blah2hip_clutter_t h, int fmt, const void 
                                       uint64_t cpi_stride, int32_t *d_ok, void *stream)
 {
   if (!h || !d_x) CFAIL(BLAH2HIP_ERR_INVALID, "NULL argument");
-  if (fmt != BLAH2HIP_FMT_C32 && fmt != BLAH2HIP_FMT_I16) CFAIL(BLAH2HIP_ERR_INVALID, "clutter filter input: BLAH2HIP_FMT_C32 or BLAH2HIP_FMT_I16");
-  if (fmt == BLAH2HIP_FMT_C32 && !d_y) CFAIL(BLAH2HIP_ERR_INVALID, "NULL argument");
+  if (fmt != BLAH2HIP_FMT_C32 && fmt != BLAH2HIP_FMT_I16 && fmt != BLAH2HIP_FMT_I8)
+    CFAIL(BLAH2HIP_ERR_INVALID, "clutter filter input: BLAH2HIP_FMT_C32, BLAH2HIP_FMT_I16 or BLAH2HIP_FMT_I8");
+  if (fmt != BLAH2HIP_FMT_I16 && !d_y) CFAIL(BLAH2HIP_ERR_INVALID, "NULL argument");
   if (n_cpi == 0 || n_cpi > h->maxBatch) CFAIL(BLAH2HIP_ERR_INVALID, "n_cpi outside [1, max_batch]");
   if (n_cpi > 1 && cpi_stride < h->N) CFAIL(BLAH2HIP_ERR_INVALID, "cpi_stride < nSamples");
   CHIP(hipSetDevice(h->device));
@@ -1593,6 +1622,7 @@ int blah2hip_clutter_estimate_dev_fmt(blah2hip_clutter_t h, int fmt, const void 
   int32_t *ok = d_ok ? d_ok : h->d_ok;
   const int64_t cs = (int64_t)cpi_stride;
   if (h->subCorr) {
+    if (fmt == BLAH2HIP_FMT_I8) CFAIL(BLAH2HIP_ERR_UNSUPPORTED, "a long filter (more than 4081 taps) takes fp32 planes only, not BLAH2HIP_FMT_I8");
     if (fmt != BLAH2HIP_FMT_C32) CFAIL(BLAH2HIP_ERR_UNSUPPORTED, "a long filter (more than 4081 taps) takes fp32 planes only");
     return long_process(h, (const cf *)d_x, (const cf *)d_y, n_cpi, cs, nullptr, 0, ok, st);
   }
@@ -1601,6 +1631,13 @@ int blah2hip_clutter_estimate_dev_fmt(blah2hip_clutter_t h, int fmt, const void 
     case 4: return launch_clutter<4, InI16>(h, d_x, nullptr, n_cpi, cs, nullptr, 0, ok, st);
     case 8: return launch_clutter<8, InI16>(h, d_x, nullptr, n_cpi, cs, nullptr, 0, ok, st);
     default: return launch_clutter<16, InI16>(h, d_x, nullptr, n_cpi, cs, nullptr, 0, ok, st);
+    }
+  }
+  if (fmt == BLAH2HIP_FMT_I8) {
+    switch (h->r3) {
+    case 4: return launch_clutter<4, InI8>(h, d_x, d_y, n_cpi, cs, nullptr, 0, ok, st);
+    case 8: return launch_clutter<8, InI8>(h, d_x, d_y, n_cpi, cs, nullptr, 0, ok, st);
+    default: return launch_clutter<16, InI8>(h, d_x, d_y, n_cpi, cs, nullptr, 0, ok, st);
     }
   }
   switch (h->r3) {

@@ -73,6 +73,26 @@ struct InI16C32 {
   B2_HD cf ly(int64_t i) const { return y[i]; }
 };
 
+// 8-bit receivers: two planes of int8 (I, Q) pairs, 2 bytes per sample -- what the HackRF and KrakenSDR callbacks read
+// (src/capture/hackrf/HackRf.cpp:119-127, kraken/Kraken.cpp:100-108: the bytes taken as SIGNED, I then Q,
+// one stream per device).  x = reference, y = surveillance.
+struct InI8 {
+  const int8_t *x;
+  const int8_t *y;
+  B2_HD cf lx(int64_t i) const { return cmake((float)x[2 * i], (float)x[2 * i + 1]); }
+  B2_HD cf ly(int64_t i) const { return cmake((float)y[2 * i], (float)y[2 * i + 1]); }
+  B2_HD InI8 at(int64_t i) const { return InI8{x + 2 * i, y + 2 * i}; }
+};
+
+// Reference channel from the int8 plane, surveillance channel from a complex fp32 plane: the ambiguity stage behind
+// the clutter filter of an 8-bit replay (the role InI16C32 has for the .rspduo words).
+struct InI8C32 {
+  const int8_t *x;
+  const cf *y;
+  B2_HD cf lx(int64_t i) const { return cmake((float)x[2 * i], (float)x[2 * i + 1]); }
+  B2_HD cf ly(int64_t i) const { return y[i]; }
+};
+
 // load_seg_* / mask_seg_* below DEFINE the segment windows (clamped index, then a
 // select).  The GPU kernels fetch the same windows with raw buffer loads whose
 // range check does the zero padding (bufload.hpp); these portable forms are what

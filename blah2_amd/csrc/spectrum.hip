@@ -422,6 +422,11 @@ int blah2hip_spectrum_process_dev(blah2hip_spectrum_t h, int fmt, const void *d_
     hipLaunchKernelGGL(spectrum_fold_kernel<InF16>, g1, dim3(64 * FOLD_WAVES), 0, st, a, in);
     break;
   }
+  case BLAH2HIP_FMT_I8: {
+    InI8 in{(const int8_t *)d_x, (const int8_t *)d_x};
+    hipLaunchKernelGGL(spectrum_fold_kernel<InI8>, g1, dim3(64 * FOLD_WAVES), 0, st, a, in);
+    break;
+  }
   default: SFAIL(BLAH2HIP_ERR_INVALID, "unknown sample format");
   }
   SHIP(hipGetLastError());

@@ -183,8 +183,27 @@ class Ambiguity:
         self._gen += 1
         return self._result(out, met)
 
+    def process_i8(self, x, y):
+        """Same, on the 8-bit receivers' samples: two int8 arrays [n, 2] = I, Q (FMT_I8), uploaded as they are."""
+        x = np.ascontiguousarray(x, dtype=np.int8).reshape(-1, 2)
+        y = np.ascontiguousarray(y, dtype=np.int8).reshape(-1, 2)
+        if x.shape != y.shape:
+            raise ValueError("x and y must hold the same number of samples")
+        nD, nC = self.dims.n_doppler_bins, self.dims.n_delay_bins
+        out = np.empty((nD, nC), dtype=np.complex64)
+        met = np.zeros(2, dtype=np.float64)
+        rc = self._L.blah2hip_amb_process_i8(self._h, _ptr(x), _ptr(y), x.shape[0], _ptr(out), _ptr(met))
+        if rc == _lib.ERR_UNDERFLOW:
+            raise RuntimeError("Attempting to pop from an empty deque")
+        check(rc)
+        self._n_samples = self.dims.n_used
+        self._gen += 1
+        return self._result(out, met)
+
     def process_dev(self, fmt, d_x, d_y, n_cpi, cpi_stride, d_map=None, d_metrics=None, stream=0):
-        """Enqueue the device-resident chain on ``stream`` (raw pointers/ints)."""
+        """Enqueue the device-resident chain on ``stream`` (raw pointers/ints).  ``fmt``: FMT_C32, FMT_F16 or FMT_I8 (two
+        planes), FMT_I16 (d_x = the .rspduo words, d_y unused), FMT_I16X_C32Y or FMT_I8X_C32Y (d_x as for FMT_I16 / FMT_I8,
+        d_y a complex64 plane: behind the two-stage clutter filter)."""
         fir = getattr(self, "_fir", None)
         if fir is not None:
             if fir._h is None:
@@ -239,7 +258,8 @@ class Ambiguity:
         self._fir = wiener_hopf
 
     def fir_fusable(self, wiener_hopf, fmt):
-        """None if ``set_fir(wiener_hopf)`` is covered for samples in format ``fmt`` (FMT_C32 / FMT_I16), else the reason."""
+        """None if ``set_fir(wiener_hopf)`` is covered for samples in format ``fmt`` (FMT_C32 / FMT_I16), else the reason
+        (always one for FMT_I8: the fused kernel has no int8 form, an 8-bit chain runs the two-stage filter)."""
         _, nb, dm = wiener_hopf.taps_dev()
         rc = self._L.blah2hip_amb_fir_fusable(self._h, int(fmt), nb, dm)
         if rc == _lib.OK:
@@ -479,14 +499,15 @@ class WienerHopf:
         check(self._L.blah2hip_clutter_process_dev(self._h, d_x, d_y, n_cpi, cpi_stride, d_y_out, d_ok, stream))
 
     def process_dev_fmt(self, fmt, d_x, d_y, n_cpi, cpi_stride, d_y_out, out_stride, d_ok=None, stream=0):
-        """Enqueue on ``stream`` with the input in format ``fmt`` (FMT_C32 planes, or FMT_I16: d_x = the interleaved
-        .rspduo buffer); the filtered channel is written as a complex64 plane with ``out_stride`` samples per CPI."""
+        """Enqueue on ``stream`` with the input in format ``fmt`` (FMT_C32 planes, FMT_I8 planes of int8 pairs, or FMT_I16:
+        d_x = the interleaved .rspduo buffer); the filtered channel is written as a complex64 plane with ``out_stride`` samples per CPI."""
         check(self._L.blah2hip_clutter_process_dev_fmt(self._h, fmt, d_x, d_y, n_cpi, cpi_stride, d_y_out, out_stride,
                                                        d_ok, stream))
 
     def estimate_dev_fmt(self, fmt, d_x, d_y, n_cpi, cpi_stride, d_ok=None, stream=0):
         """The filter's correlations, reduction and Toeplitz solve only: the taps stay in the handle (``taps_dev``) for an
-        Ambiguity handle that runs the FIR fused into its range kernel (``Ambiguity.set_fir``)."""
+        Ambiguity handle that runs the FIR fused into its range kernel (``Ambiguity.set_fir``).  ``fmt``: FMT_C32, FMT_I16
+        or FMT_I8, as for ``process_dev_fmt``."""
         check(self._L.blah2hip_clutter_estimate_dev_fmt(self._h, fmt, d_x, d_y, n_cpi, cpi_stride, d_ok, stream))
 
     def taps_dev(self):
@@ -620,7 +641,8 @@ class SpectrumAnalyser:
         return out, np.empty(0, dtype=np.float64)
 
     def process_dev(self, fmt, d_x, n_cpi, cpi_stride, d_out, stream=0):
-        """Enqueue on ``stream``; d_out is [n_cpi][nSpectrum] complex128 in HBM."""
+        """Enqueue on ``stream``; d_x in format ``fmt`` (FMT_C32, FMT_I16, FMT_F16 or FMT_I8: the reference plane); d_out
+        is [n_cpi][nSpectrum] complex128 in HBM."""
         check(self._L.blah2hip_spectrum_process_dev(self._h, fmt, d_x, n_cpi, cpi_stride, d_out, stream))
 
 

@@ -1,4 +1,4 @@
-"""Offline replay of blah2 captures (.rspduo and USRP), CPI-sharded across GPUs.
+"""Offline replay of blah2 captures (.rspduo, USRP and 8-bit pairs), CPI-sharded across GPUs.
 
 The reference replays a capture by pushing int16 I1 Q1 I2 Q2 samples into the
 two IqData FIFOs (src/capture/rspduo/RspDuo.cpp:150-179) and the processing
@@ -18,6 +18,15 @@ of whole block pairs; the device chain uploads that range as it is and one
 kernel (blah2hip_deblock_c32_dev) writes the two complex-fp32 planes the rest
 of the chain reads.  The reference itself cannot replay such a file
 (``Usrp::replay`` is empty, Usrp.cpp:108-111).
+
+The 8-bit receivers (HackRF, KrakenSDR / RTL-SDR) deliver one stream of int8
+I, Q pairs per device (HackRf.cpp:116-133, Kraken.cpp:97-112); a recording of
+such a pair is two files, one per channel (what ``hackrf_transfer -r`` writes
+per board).  :class:`Cs8Pair` reads them, and the device chain uploads the
+bytes as they lie on disk -- 2 bytes per sample and channel -- for the kernels
+to read directly (BLAH2HIP_FMT_I8): no conversion on the host or the device.
+The reference has no file writer or replay for these devices (``replay`` is
+empty, HackRf.cpp:135-138, Kraken.cpp:114-117).
 
 The unit of work is a BATCH of `batch` consecutive CPIs (one contiguous read,
 one launch of the device chain).  Batch b belongs to rank b mod world; a ROUND
@@ -41,7 +50,8 @@ bytes (fc32), so the same link carries half the CPIs per second.
 `processor` is a :class:`GpuChain`, or -- for the CPU tests of the sharding,
 which has no GPU dependency -- any callable that takes what the capture's
 ``batch()`` returns (int16 [B, nSamples, 4] for .rspduo, complex64 [B, 2,
-nSamples] (x, y) for USRP) and returns a list of B result dicts.
+nSamples] (x, y) for USRP, int8 [B, 2, nSamples, 2] (x, y; I, Q) for an 8-bit
+pair) and returns a list of B result dicts.
 """
 from __future__ import annotations
 
@@ -58,6 +68,7 @@ import numpy as np
 
 BYTES_PER_SAMPLE = 8  # int16 I1 Q1 I2 Q2
 FC32_BYTES = 8  # one complex<float> of a USRP capture
+CS8_BYTES = 2  # one int8 I, Q pair of an 8-bit capture
 PAGE = 4096
 _MADV_POPULATE_READ = 22  # Linux 5.14+
 _LIBC = C.CDLL(None, use_errno=True)
@@ -120,6 +131,11 @@ class _RawCapture:
         pages, which the zero-copy read path registers with the device and uploads from (``GpuChain(read_mode="mapped")``)."""
         off0, nbytes, _ = self.extent(k0, count)
         return self._mm.ctypes.data + off0, nbytes
+
+    def windows(self, k0: int, count: int) -> List[Tuple[int, int]]:
+        """The same as a list of (address, bytes) runs that land back to back in the batch's device buffer: one run for a
+        capture that is one file."""
+        return [self.window(k0, count)]
 
     def close(self):
         if self._fd is not None:
@@ -216,15 +232,110 @@ class UsrpFile(_RawCapture):
         return self.batch([k])[0]
 
 
-def open_capture(path: str, n_samples: int, layout: str = "rspduo", usrp_block: Optional[int] = None) -> _RawCapture:
-    """The reader for a capture of ``layout`` ("rspduo" or "usrp", the latter with its block length)."""
+class _Cs8Channel(_RawCapture):
+    """One file of int8 I, Q pairs: CPI k is bytes [(skip + k*n)*2, (skip + (k+1)*n)*2)."""
+
+    layout = "cs8"
+
+    def __init__(self, path: str, n_samples: int, skip: int):
+        self.path, self.n_samples, self.skip = path, int(n_samples), int(skip)
+        size = os.path.getsize(path)
+        self.pairs = size // CS8_BYTES  # an odd byte count: the dangling byte belongs to no sample
+        self.n_cpis = max(0, self.pairs - self.skip) // self.n_samples
+        self._mm = np.memmap(path, dtype=np.int8, mode="r") if size else np.zeros(0, dtype=np.int8)
+        self._fd = None
+
+    def extent(self, k0: int, count: int) -> Tuple[int, int, int]:
+        return (self.skip + k0 * self.n_samples) * CS8_BYTES, count * self.n_samples * CS8_BYTES, 0
+
+
+class Cs8Pair(_RawCapture):
+    """An 8-bit capture: two files of int8 I, Q pairs, ``path_x`` the reference channel and ``path_y`` the surveillance
+    channel -- the bytes the HackRF and KrakenSDR callbacks read (HackRf.cpp:119-127, Kraken.cpp:100-108: signed, I then
+    Q), one stream per device, as ``hackrf_transfer -r`` or a signed-byte RTL-SDR dump writes them.  ``n_cpis`` is what
+    BOTH files hold in whole CPIs: two boards never stop on the same sample, the tail of the longer file is ignored, and
+    so is the dangling byte of an odd byte count.  Aligning the two streams is the capture's business, as in the
+    reference, which starts the boards one after the other (HackRf.cpp:107-114); ``skip_x`` / ``skip_y`` drop that many
+    leading samples of a channel for a user who knows the lag.
+
+    :meth:`cpi` and :meth:`batch` return int8 [2, n, 2] and [len, 2, n, 2] (x, y; I, Q).  :meth:`read_into` puts a
+    batch's x bytes, then its y bytes, back to back into the destination: the layout the device chain uploads and
+    BLAH2HIP_FMT_I8 reads (x plane at byte 0, y plane at byte count * n * 2)."""
+
+    layout = "cs8"
+
+    def __init__(self, path_x: str, path_y: str, n_samples: int, skip_x: int = 0, skip_y: int = 0):
+        self.n_samples = int(n_samples)
+        if self.n_samples <= 0:
+            raise ValueError(f"Cs8Pair: n_samples ({n_samples}) must be positive")
+        if int(skip_x) < 0 or int(skip_y) < 0:
+            raise ValueError("Cs8Pair: skip_x and skip_y are sample counts >= 0")
+        self.path, self.path_y = path_x, path_y
+        self._x = _Cs8Channel(path_x, self.n_samples, skip_x)
+        self._y = _Cs8Channel(path_y, self.n_samples, skip_y)
+        self.n_cpis = min(self._x.n_cpis, self._y.n_cpis)
+
+    def _check(self, k0: int, count: int):
+        if k0 < 0 or count < 0 or k0 + count > self.n_cpis:
+            raise IndexError((k0, count))
+
+    def extent(self, k0: int, count: int) -> Tuple[int, int, int]:
+        """(0, bytes, 0): a batch is two byte ranges, one per file; ``bytes`` is their sum, the x half first."""
+        self._check(k0, count)
+        return 0, 2 * count * self.n_samples * CS8_BYTES, 0
+
+    def read_into(self, k0, count, dst, pool=None, parts=8, how="memmove"):
+        self._check(k0, count)
+        half = count * self.n_samples * CS8_BYTES
+        flat = np.frombuffer(memoryview(dst).cast("B"), dtype=np.uint8)
+        if flat.nbytes < 2 * half:
+            raise ValueError("destination smaller than the CPIs asked for")
+        self._x.read_into(k0, count, flat[:half], pool, parts, how)
+        self._y.read_into(k0, count, flat[half:2 * half], pool, parts, how)
+
+    def window(self, k0: int, count: int):
+        raise NotImplementedError("an 8-bit pair is two mappings: windows()")
+
+    def windows(self, k0: int, count: int) -> List[Tuple[int, int]]:
+        self._check(k0, count)
+        return [self._x.window(k0, count), self._y.window(k0, count)]
+
+    def batch(self, ks) -> np.ndarray:
+        n = self.n_samples
+        out = np.empty((len(ks), 2, n, 2), dtype=np.int8)
+        for i, k in enumerate(ks):
+            if not 0 <= k < self.n_cpis:
+                raise IndexError(k)
+            for c, ch in enumerate((self._x, self._y)):
+                a = (ch.skip + k * n) * CS8_BYTES
+                out[i, c] = np.asarray(ch._mm[a:a + n * CS8_BYTES]).reshape(n, 2)
+        return out
+
+    def cpi(self, k: int) -> np.ndarray:
+        return self.batch([k])[0]
+
+    def close(self):
+        self._x.close()
+        self._y.close()
+
+
+def open_capture(path: str, n_samples: int, layout: str = "rspduo", usrp_block: Optional[int] = None,
+                 path_y: Optional[str] = None, skip_x: int = 0, skip_y: int = 0) -> _RawCapture:
+    """The reader for a capture of ``layout``: "rspduo", "usrp" (with its block length) or "cs8" (``path`` the reference
+    channel's file, ``path_y`` the surveillance channel's)."""
+    if layout == "cs8":
+        if path_y is None:
+            raise ValueError("an 8-bit capture is two files: path_y names the surveillance channel's")
+        return Cs8Pair(path, path_y, n_samples, skip_x, skip_y)
+    if path_y is not None:
+        raise ValueError(f"path_y belongs to an 8-bit ('cs8') capture, not to layout {layout!r}")
     if layout == "rspduo":
         return RspduoFile(path, n_samples)
     if layout == "usrp":
         if usrp_block is None:
             raise ValueError("a USRP capture needs its block length (UHD's get_max_num_samps)")
         return UsrpFile(path, n_samples, usrp_block)
-    raise ValueError(f"capture layout {layout!r}: 'rspduo' or 'usrp'")
+    raise ValueError(f"capture layout {layout!r}: 'rspduo', 'usrp' or 'cs8'")
 
 
 class LoopedCapture(RspduoFile):
@@ -468,13 +579,16 @@ class GpuChain:
     ``layout`` is the capture layout the chain replays: "rspduo" (int16 I1 Q1 I2 Q2, read by the kernels as it is) or
     "usrp" with its block length ``usrp_block`` (:class:`UsrpFile`).  A USRP batch is uploaded as its raw bytes; on the
     compute stream blah2hip_deblock_c32_dev writes them into one pair of complex-fp32 planes [batch, n] (shared by the
-    slots, like the filtered channel) and the FMT_C32 chain runs on those."""
+    slots, like the filtered channel) and the FMT_C32 chain runs on those.  "cs8" replays a :class:`Cs8Pair`: a slot holds
+    the batch's x bytes, then its y bytes, in one upload, and the kernels read the int8 pairs as they are (FMT_I8 into the
+    filter and the range kernel, FMT_I8X_C32Y into the range kernel behind the filter): no conversion kernel, no fp32
+    planes.  The filter of a cs8 chain is always the two-stage one (the fused kernel has no int8 form)."""
 
     def __init__(self, cfg: dict, device: int = 0, batch: int = 1, want_map: bool = False, depth: int = 3,
                  reader_threads: int = 4, hit_copy: int = 4096, read_mode: str = "memmove", numa: bool = True,
                  layout: str = "rspduo", usrp_block: Optional[int] = None):
-        if layout not in ("rspduo", "usrp"):
-            raise ValueError(f"layout {layout!r}: 'rspduo' or 'usrp'")
+        if layout not in ("rspduo", "usrp", "cs8"):
+            raise ValueError(f"layout {layout!r}: 'rspduo', 'usrp' or 'cs8'")
         if layout == "usrp" and (usrp_block is None or int(usrp_block) <= 0):
             raise ValueError("a USRP chain needs the capture's block length (usrp_block > 0)")
         self.layout = layout
@@ -576,14 +690,15 @@ class GpuChain:
         self.yf = torch.empty((B, n), dtype=torch.complex64, device=dev) if self.wh is not None and not self.fused_fir else None
         # USRP: a batch's raw bytes are whole block pairs, at most B*n*16 + 32*block of them (a CPI run that starts and ends
         # mid-block); the de-blocked x and y planes are one pair for all slots, like yf
-        self.raw_bytes = -(-(B * n * 2 * FC32_BYTES + 4 * self.usrp_block * FC32_BYTES) // 16) * 16 if self.layout == "usrp" else None
+        self.raw_bytes = (-(-(B * n * 2 * FC32_BYTES + 4 * self.usrp_block * FC32_BYTES) // 16) * 16 if self.layout == "usrp" else
+                          2 * B * n * CS8_BYTES if self.layout == "cs8" else None)  # cs8: the x bytes, then the y bytes
         self.planes = torch.empty((2, B, n), dtype=torch.complex64, device=dev) if self.layout == "usrp" else None
         self.busy_ms, self.batches_done = 0.0, 0  # kernels' time on the compute stream / batches collected, since construction
         self.slots = []
         for _ in range(self.depth):
             s = {
                 "h_iq": None,  # pinned staging batch of the pread path, allocated when that path first runs
-                "h_ends": torch.empty(2 * PAGE, dtype=torch.uint8).pin_memory(),  # the ragged ends of a mapped batch
+                "h_ends": torch.empty(4 * PAGE, dtype=torch.uint8).pin_memory(),  # the ragged ends of a mapped batch's (one or two) runs
                 "registered": [],
                 "d_iq": torch.empty((B, n, 4), dtype=torch.int16, device=dev) if self.layout == "rspduo" else
                         torch.empty(self.raw_bytes, dtype=torch.uint8, device=dev),
@@ -606,8 +721,8 @@ class GpuChain:
             self.slots.append(s)
 
     def _fmt_in(self):
-        """The format the filter and the range kernel read: the .rspduo words, or the de-blocked USRP planes."""
-        return self.b2.FMT_I16 if self.layout == "rspduo" else self.b2.FMT_C32
+        """The format the filter and the range kernel read: the .rspduo words, the int8 planes, or the de-blocked USRP planes."""
+        return {"rspduo": self.b2.FMT_I16, "cs8": self.b2.FMT_I8}.get(self.layout, self.b2.FMT_C32)
 
     def _host_batch(self):
         """The pinned staging batch of the copying read paths."""
@@ -628,26 +743,32 @@ class GpuChain:
         slot["mapped"] = None
         _, slot["nbytes"], slot["first"] = capture.extent(k0, cnt)
         if self.read_mode == "mapped":
-            addr, nbytes = capture.window(k0, cnt)
-            head, pieces, tail = page_split(addr, nbytes, self.reader_threads)
             hip, dev = self._hip, self.dev.index
+            # one run of the file per mapping (two for an 8-bit pair), landing back to back in the device buffer
+            runs, at = [], 0
+            for addr, nbytes in capture.windows(k0, cnt):
+                runs.append((addr, at) + page_split(addr, nbytes, self.reader_threads))
+                at += nbytes
+            todo = [addr + o for addr, _, _, pieces, _ in runs for o, _ in pieces]
+            lens = [ln for _, _, _, pieces, _ in runs for _, ln in pieces]
 
             def register(pc):
                 hip.hipSetDevice(dev)  # the pool's threads start on device 0
-                return hip.hipHostRegister(addr + pc[0], pc[1], 0)
+                return hip.hipHostRegister(pc[0], pc[1], 0)
 
-            rcs = list(self.pool.map(register, pieces))
-            done = [pc for pc, rc in zip(pieces, rcs) if rc == 0]
-            if len(done) == len(pieces):
+            rcs = list(self.pool.map(register, zip(todo, lens)))
+            done = [a for a, rc in zip(todo, rcs) if rc == 0]
+            if len(done) == len(todo):
                 ends = slot["h_ends"].numpy()
-                for (o, ln), at in ((head, 0), (tail, PAGE)):  # under a page each: a copy
-                    if ln:
-                        C.memmove(ends.ctypes.data + at, addr + o, ln)
-                slot["registered"] = [addr + o for o, _ in pieces]
-                slot["mapped"] = (addr, head, pieces, tail)
+                for r, (addr, _, head, _, tail) in enumerate(runs):
+                    for (o, ln), e in ((head, 2 * r), (tail, 2 * r + 1)):  # under a page each: a copy
+                        if ln:
+                            C.memmove(ends.ctypes.data + e * PAGE, addr + o, ln)
+                slot["registered"] = todo
+                slot["mapped"] = runs
                 return
-            for o, _ in done:
-                hip.hipHostUnregister(addr + o)
+            for a in done:
+                hip.hipHostUnregister(a)
             self.read_mode = "memmove"  # this runtime / this file system does not register file mappings
             print(f"[blah2_amd.replay] hipHostRegister of the mapped capture failed ({hip.hipGetErrorString(max(rcs)).decode()}): "
                   "copying into a pinned buffer instead", file=sys.stderr)
@@ -665,14 +786,16 @@ class GpuChain:
         torch, b2, n, amb = self.torch, self.b2, self.n, self.amb
         with torch.cuda.stream(self.copy):
             if slot["mapped"] is not None:
-                addr, head, pieces, tail = slot["mapped"]
-                dst, st, hip = slot["d_iq"].data_ptr(), self.copy.cuda_stream, self._hip
+                st, hip = self.copy.cuda_stream, self._hip
                 ends = slot["h_ends"].data_ptr()
-                for src, (o, ln) in [(addr + o, (o, ln)) for o, ln in pieces] + [(ends, head), (ends + PAGE, tail)]:
-                    if ln:
-                        rc = hip.hipMemcpyAsync(dst + o, src, ln, 1, st)  # hipMemcpyHostToDevice
-                        if rc:
-                            raise RuntimeError(f"hipMemcpyAsync from the mapped capture: {hip.hipGetErrorString(rc).decode()}")
+                for r, (addr, at, head, pieces, tail) in enumerate(slot["mapped"]):
+                    dst = slot["d_iq"].data_ptr() + at
+                    for src, (o, ln) in ([(addr + o, (o, ln)) for o, ln in pieces] +
+                                         [(ends + 2 * r * PAGE, head), (ends + (2 * r + 1) * PAGE, tail)]):
+                        if ln:
+                            rc = hip.hipMemcpyAsync(dst + o, src, ln, 1, st)  # hipMemcpyHostToDevice
+                            if rc:
+                                raise RuntimeError(f"hipMemcpyAsync from the mapped capture: {hip.hipGetErrorString(rc).decode()}")
             elif self.layout == "rspduo":
                 slot["d_iq"][:cnt].copy_(slot["h_iq"][:cnt], non_blocking=True)
             else:
@@ -686,6 +809,8 @@ class GpuChain:
             iq = slot["d_iq"].data_ptr()
             if self.layout == "rspduo":  # the kernels read the .rspduo words
                 fmt, fmt_yf, x, y = b2.FMT_I16, b2.FMT_I16X_C32Y, iq, None
+            elif self.layout == "cs8":  # ... or the int8 pairs: the y plane follows the batch's x bytes
+                fmt, fmt_yf, x, y = b2.FMT_I8, b2.FMT_I8X_C32Y, iq, iq + slot["nbytes"] // 2
             else:  # USRP: the batch's block pairs into the x and y planes first
                 fmt, fmt_yf, x, y = b2.FMT_C32, b2.FMT_C32, self.planes[0].data_ptr(), self.planes[1].data_ptr()
                 b2.deblock_c32_dev(iq, self.usrp_block, slot["first"], n, cnt, x, y, n, st)
@@ -789,7 +914,7 @@ class GpuChain:
         """One batch, synchronously, from a host array [B, nSamples, 4] (tests; a caller that has the samples in memory).
         .rspduo chains only."""
         if self.layout != "rspduo":
-            raise ValueError("GpuChain(...)(iq) takes .rspduo int16 samples; a USRP chain replays a UsrpFile")
+            raise ValueError("GpuChain(...)(iq) takes .rspduo int16 samples; a USRP or cs8 chain replays its capture reader")
         cnt = iq.shape[0]
         slot = self.slots[0]
         if slot["h_iq"] is None:
@@ -842,10 +967,16 @@ def send_frame(sock, doc: str):
 
 
 def config_layout(y: dict) -> str:
-    """The capture layout a blah2 config.yml records with: "usrp" for capture.device.type Usrp, else "rspduo" (the
-    RspDuo's, and the default of a config that names no device; blah2's other drivers save no captures)."""
+    """The capture layout that goes with a blah2 config.yml: "usrp" for capture.device.type Usrp, "cs8" for the 8-bit
+    receivers HackRF and Kraken (the spellings src/capture/Capture.cpp compares against, case-insensitive here; their
+    drivers save nothing themselves: the layout is that of the bytes their callbacks read), else "rspduo" (the RspDuo's,
+    and the default of a config that names no device)."""
     dev = ((y or {}).get("capture") or {}).get("device") or {}
-    return "usrp" if str(dev.get("type", "")).lower() == "usrp" else "rspduo"
+    kind = str(dev.get("type", "")).lower()
+    return "usrp" if kind == "usrp" else "cs8" if kind in ("hackrf", "kraken") else "rspduo"
+
+
+capture_layout = config_layout
 
 
 def main(argv=None):
@@ -853,11 +984,16 @@ def main(argv=None):
     import socket
 
     import yaml
-    ap = argparse.ArgumentParser(description="CPI-sharded replay of a blah2 capture (.rspduo or USRP) on MI355X")
-    ap.add_argument("capture")
+    ap = argparse.ArgumentParser(description="CPI-sharded replay of a blah2 capture (.rspduo, USRP or an 8-bit pair) on MI355X")
+    ap.add_argument("capture", help="the capture; for --format cs8 the reference channel's file")
     ap.add_argument("-c", "--config", required=True, help="blah2 config.yml")
-    ap.add_argument("--format", choices=("rspduo", "usrp"), default=None,
-                    help="capture layout (default: from the config's capture.device.type, Usrp or RspDuo)")
+    ap.add_argument("--format", choices=("rspduo", "usrp", "cs8"), default=None,
+                    help="capture layout (default: from the config's capture.device.type: Usrp, HackRF / Kraken (cs8) or RspDuo)")
+    ap.add_argument("--capture-y", default=None, metavar="FILE",
+                    help="cs8 captures: the surveillance channel's file of int8 I Q pairs (the positional capture is the "
+                         "reference channel's)")
+    ap.add_argument("--skip-x", type=int, default=0, metavar="S", help="cs8 captures: leading samples of the reference file to drop")
+    ap.add_argument("--skip-y", type=int, default=0, metavar="S", help="cs8 captures: leading samples of the surveillance file to drop")
     ap.add_argument("--usrp-block", type=int, default=None, metavar="B",
                     help="USRP captures: samples per channel block, the get_max_num_samps UHD reported when the capture "
                          "was recorded (the file does not hold it)")
@@ -877,6 +1013,12 @@ def main(argv=None):
                  "recorded with)")
     if a.usrp_block is not None and (layout != "usrp" or a.usrp_block <= 0):
         ap.error("--usrp-block takes a positive block length, for USRP captures only")
+    if layout == "cs8" and a.capture_y is None:
+        ap.error("an 8-bit (cs8) capture is two files: --capture-y FILE names the surveillance channel's")
+    if layout != "cs8" and (a.capture_y is not None or a.skip_x or a.skip_y):
+        ap.error("--capture-y, --skip-x and --skip-y belong to 8-bit (cs8) captures only")
+    if a.skip_x < 0 or a.skip_y < 0:
+        ap.error("--skip-x and --skip-y are sample counts >= 0")
     fs = int(y["capture"]["fs"])
     n = int(fs * float(y["process"]["data"]["cpi"]))  # blah2.cpp:142-144
     cfg = dict(y["process"], fs=fs, n_samples=n)
@@ -919,7 +1061,8 @@ def main(argv=None):
                 sys.stdout.write(doc + "\n")
         sys.stdout.flush()
 
-    replay(open_capture(a.capture, n, layout, a.usrp_block), proc, a.batch, dist, a.limit, emit=emit, serialise=serialise)
+    replay(open_capture(a.capture, n, layout, a.usrp_block, a.capture_y, a.skip_x, a.skip_y), proc, a.batch, dist, a.limit,
+           emit=emit, serialise=serialise)
     for s in socks.values():
         s.close()
     proc.close()

@@ -62,6 +62,15 @@ extern "C" {
 #define BLAH2HIP_FMT_I16X_C32Y 3 /* reference channel from the .rspduo buffer (tuner 1 of I1 Q1 I2 Q2), surveillance channel from a
                                   * complex fp32 plane: the ambiguity stage behind blah2hip_clutter_process_dev_fmt(FMT_I16), which
                                   * leaves x untouched and writes the filtered y as fp32 (WienerHopf.cpp:156-160) */
+#define BLAH2HIP_FMT_I8 4 /* two planes of int8 (I, Q) pairs, 2 bytes per sample: d_x = reference, d_y = surveillance; CPI c at
+                           * c * cpi_stride samples.  The sample format of the 8-bit receivers: the HackRF and the KrakenSDR /
+                           * RTL-SDR callbacks (HackRf.cpp:119-127, Kraken.cpp:100-108) read each device's stream as int8_t, I
+                           * then Q.  The bytes are taken as SIGNED, as both callbacks take them; RTL-SDR bytes are unsigned
+                           * (offset binary) on the wire and the reference reinterprets them, so this format does too.  A
+                           * plane needs 2-byte alignment only. */
+#define BLAH2HIP_FMT_I8X_C32Y 5 /* reference channel from the int8 plane d_x, surveillance channel from a complex fp32 plane d_y:
+                                 * the ambiguity stage behind blah2hip_clutter_process_dev_fmt(FMT_I8), the role FMT_I16X_C32Y has
+                                 * for the .rspduo words (WienerHopf.cpp:156-160: x untouched, filtered y written as fp32) */
 
 typedef struct blah2hip_amb_s *blah2hip_amb_t;
 typedef struct blah2hip_clutter_s *blah2hip_clutter_t;
@@ -212,10 +221,14 @@ int blah2hip_amb_process_c32(blah2hip_amb_t h, const float *x, const float *y, u
                              float *map_out, double *metrics);
 int blah2hip_amb_process_i16(blah2hip_amb_t h, const int16_t *iq, uint32_t n, float *map_out,
                              double *metrics);
+/* x, y: host planes of n int8 (I, Q) pairs each (BLAH2HIP_FMT_I8), uploaded as they are: one CPI */
+int blah2hip_amb_process_i8(blah2hip_amb_t h, const int8_t *x, const int8_t *y, uint32_t n, float *map_out,
+                            double *metrics);
 
 /* Device-resident chain: range kernel -> Doppler kernel (+ fused metrics).
- * d_x/d_y: device pointers (fmt C32: two planes; fmt I16: d_x = interleaved
- * buffer, d_y ignored).  CPI c starts at sample c*cpi_stride.  d_map:
+ * d_x/d_y: device pointers (fmt C32, F16, I8: two planes; fmt I16: d_x = interleaved
+ * buffer, d_y ignored; fmt I16X_C32Y, I8X_C32Y: d_x as for I16 / I8, d_y an fp32 plane).
+ * CPI c starts at sample c*cpi_stride.  d_map:
  * [n_cpi][n_doppler][n_delay] complex fp32; d_metrics: [n_cpi][2] doubles.
  * Either output may be NULL (then the handle's internal buffer is used and
  * can be read with blah2hip_amb_read_last). */
@@ -324,7 +337,8 @@ int blah2hip_clutter_process_dev(blah2hip_clutter_t h, const void *d_x, const vo
                                  void *stream);
 /* The same with the INPUT in format fmt: BLAH2HIP_FMT_C32 (d_x, d_y planes) or BLAH2HIP_FMT_I16 (d_x = the interleaved
  * .rspduo buffer I1 Q1 I2 Q2, d_y ignored: the correlation and FIR kernels read the int16 words directly,
- * RspDuo.cpp:512-526).  The filtered surveillance channel is always written as a complex fp32 plane, CPI c at
+ * RspDuo.cpp:512-526) or BLAH2HIP_FMT_I8 (d_x, d_y planes of int8 pairs, read directly).  A long filter (more than 4081 taps)
+ * takes fp32 planes only: BLAH2HIP_ERR_UNSUPPORTED for FMT_I16 and FMT_I8.  The filtered surveillance channel is always written as a complex fp32 plane, CPI c at
  * d_y_out + c * out_stride samples (for FMT_C32 it may alias d_y with out_stride = cpi_stride).  Enqueues only. */
 int blah2hip_clutter_process_dev_fmt(blah2hip_clutter_t h, int fmt, const void *d_x, const void *d_y, uint32_t n_cpi,
                                      uint64_t cpi_stride, void *d_y_out, uint64_t out_stride, int32_t *d_ok, void *stream);
@@ -399,7 +413,7 @@ int blah2hip_spectrum_get_dims(blah2hip_spectrum_t h, uint32_t *decimation, uint
 int blah2hip_spectrum_process_c64(blah2hip_spectrum_t h, const double *x, uint32_t n, double *spectrum_out);
 int blah2hip_spectrum_process_c32(blah2hip_spectrum_t h, const float *x, uint32_t n, double *spectrum_out);
 /* dev: d_x in format fmt (C32: complex fp32 plane; I16: the interleaved .rspduo
- * buffer, tuner 1 is used; F16: half pairs), d_out [n_cpi][nSpectrum] complex fp64.
+ * buffer, tuner 1 is used; F16: half pairs; I8: the reference plane of int8 pairs), d_out [n_cpi][nSpectrum] complex fp64.
  * Enqueues only. */
 int blah2hip_spectrum_process_dev(blah2hip_spectrum_t h, int fmt, const void *d_x, uint32_t n_cpi,
                                   uint64_t cpi_stride, double *d_out, void *stream);
@@ -411,7 +425,8 @@ int blah2hip_spectrum_process_dev(blah2hip_spectrum_t h, int fmt, const void *d_
  * kernel (csrc/kernels.hpp range_fir_kernel).  The result is the two-stage result (same linear operations; fp32 rounding in a
  * different order).  Supported where one 4096-point transform covers it -- the handle's transform length is 4096
  * (BLAH2HIP_OPT_FFT_LEN), n_bins <= 2049, at most 2049 delay bins in one chunk, the filter's first lag equal to the map's and
- * <= 0, symmetric Doppler limits, pulses of at least 2048 - delayMin samples, fp32 or int16 samples -- else
+ * <= 0, symmetric Doppler limits, pulses of at least 2048 - delayMin samples, fp32 or int16 samples (not FMT_F16, and not
+ * FMT_I8: the fused kernel has no int8 instantiation, an 8-bit chain runs the two-stage filter) -- else
  * BLAH2HIP_ERR_UNSUPPORTED at the process call.  d_w = NULL switches back to the plain range kernels.  The ambiguity handle keeps
  * the POINTER: the filter handle must outlive its use, and a process call may not ask for more CPIs than the filter handle's max_batch. */
 int blah2hip_clutter_estimate_dev_fmt(blah2hip_clutter_t h, int fmt, const void *d_x, const void *d_y, uint32_t n_cpi,
