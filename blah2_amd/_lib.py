@@ -24,6 +24,7 @@ CLUTTER_KERNEL_NAMES = {CK_CORR: "clutter_corr", CK_REDUCE: "clutter_reduce", CK
 OPT_DOPPLER_KERNEL, OPT_RANGE_GRID, OPT_RANGE_KERNEL, OPT_DOPPLER_GRID, OPT_FFT_LEN, OPT_CFAR2D_KERNEL = 1, 2, 3, 4, 5, 6
 OPT_LEAK_COMPENSATION = 7
 OPT_HOT_COLUMNS = 8
+OPT_CFAR2D_SEG_ROWS, OPT_CFAR2D_GRID = 9, 10
 LEAK_OFF, LEAK_AUTO, LEAK_ALWAYS = 0, 1, 2
 CFAR2D_AUTO, CFAR2D_TILE, CFAR2D_SAT, CFAR2D_STREAM = 0, 1, 2, 3
 CLUTTER_OPT_SOLVE_K, CLUTTER_OPT_FFT_LEN, CLUTTER_OPT_CORR, CLUTTER_OPT_SOLVE_FORM, CLUTTER_OPT_SOLVE_E, CLUTTER_OPT_FIR_CARRY = 1, 2, 3, 4, 5, 6
@@ -41,6 +42,7 @@ INFO_LAST_DOPPLER_KERNEL, INFO_LAST_RANGE_KERNEL, INFO_DOPPLER_FFT_LEN, INFO_RAN
 INFO_DOPPLER_GRID, INFO_DOPPLER_TILES = 6, 7
 INFO_LEAK_LAGS, INFO_LEAK_MAX_E12 = 8, 9
 INFO_HOT_COLUMNS, INFO_HOT_COLUMNS_MISSED = 10, 11
+INFO_CFAR2D_SEG_ROWS, INFO_CFAR2D_GRID = 12, 13
 
 
 class Blah2HipError(RuntimeError):

@@ -110,6 +110,9 @@ struct blah2hip_amb_s {
   int fftLenForce = 0;              // BLAH2HIP_OPT_FFT_LEN (0 = planner)
   int cfar2dForce = 0;              // BLAH2HIP_OPT_CFAR2D_KERNEL
   int dopGridForce = 0;             // BLAH2HIP_OPT_DOPPLER_GRID (0 = residency of the persistent kernel)
+  int cfar2dSegRows = 0;            // BLAH2HIP_OPT_CFAR2D_SEG_ROWS (0 = cost model of cfar2d_stream_launch)
+  int cfar2dGridForce = 0;          // BLAH2HIP_OPT_CFAR2D_GRID (0 = one workgroup per CU)
+  int cfar2dSegRowsLast = 0, cfar2dGridLast = 0; // BLAH2HIP_INFO_CFAR2D_SEG_ROWS / _GRID
   int dopGridLast = 0, dopTilesLast = 0; // BLAH2HIP_INFO_DOPPLER_GRID / _TILES
   struct AlphaTable { double pfa; size_t n; double *d; bool pinned; }; // pinned: handed out by *_prepare, never evicted
   std::vector<AlphaTable> alphaTables; // CFAR threshold factors, one per (pfa, size) seen
@@ -660,7 +663,7 @@ bool cfar2d_use_stream(const blah2hip_amb_s *h, int ngd, int ntd, int ngf, int n
 }
 
 // rows per segment: the fewest rounds of (segment + its 2 hR halo rows) over the wave slots of the chip
-void cfar2d_stream_launch(const blah2hip_amb_s *h, const Cfar2dArgs &a, uint32_t n_cpi, hipStream_t st)
+void cfar2d_stream_launch(blah2hip_amb_s *h, const Cfar2dArgs &a, uint32_t n_cpi, hipStream_t st)
 {
   Cfar2dStreamArgs ta;
   ta.d = a;
@@ -675,6 +678,12 @@ void cfar2d_stream_launch(const blah2hip_amb_s *h, const Cfar2dArgs &a, uint32_t
     const int64_t cost = ((tasks + slots - 1) / slots) * (std::min(R, (int)a.nD) + 2 * hR + 16); // 16: start-up of a wave, in rows
     if (cost < best) { best = cost; ta.rowsPerSeg = std::min(R, (int)a.nD); ta.segs = (int32_t)segs; }
   }
+  if (h->cfar2dSegRows > 0) { // BLAH2HIP_OPT_CFAR2D_SEG_ROWS
+    ta.rowsPerSeg = std::min(h->cfar2dSegRows, (int)a.nD);
+    ta.segs = (a.nD + ta.rowsPerSeg - 1) / ta.rowsPerSeg;
+  }
+  h->cfar2dSegRowsLast = ta.rowsPerSeg;
+  h->cfar2dGridLast = 0;
   ta.nTasks = ta.nCpi * ta.segs * ta.strips;
   cfar2d_dead_rows(h, a.minDoppler, &ta.deadLo, &ta.deadHi);
   const int grid = (((ta.nTasks + 3) / 4) + 7) & ~7;
@@ -1296,6 +1305,14 @@ int blah2hip_amb_set_option(blah2hip_amb_t h, int option, int64_t value)
     if (value < 0 || value > (1 << 20)) return fail(BLAH2HIP_ERR_INVALID, "Doppler grid outside [0, 2^20]");
     h->dopGridForce = (int)value;
     return BLAH2HIP_OK;
+  case BLAH2HIP_OPT_CFAR2D_SEG_ROWS:
+    if (value < 0 || value > 65535) return fail(BLAH2HIP_ERR_INVALID, "2-D detector rows per segment outside [0, 65535]");
+    h->cfar2dSegRows = (int)value;
+    return BLAH2HIP_OK;
+  case BLAH2HIP_OPT_CFAR2D_GRID:
+    if (value < 0 || value > (1 << 20)) return fail(BLAH2HIP_ERR_INVALID, "2-D detector grid outside [0, 2^20]");
+    h->cfar2dGridForce = (int)value;
+    return BLAH2HIP_OK;
   case BLAH2HIP_OPT_FFT_LEN: {
     if (value != 0 && value != 1024 && value != 2048 && value != 4096)
       return fail(BLAH2HIP_ERR_INVALID, "range transform length: 0 (planner), 1024, 2048 or 4096");
@@ -1358,6 +1375,8 @@ int blah2hip_amb_get_info(blah2hip_amb_t h, int key, int64_t *value)
   case BLAH2HIP_INFO_NUM_CU: *value = h->numCU; return BLAH2HIP_OK;
   case BLAH2HIP_INFO_DOPPLER_GRID: *value = h->dopGridLast; return BLAH2HIP_OK;
   case BLAH2HIP_INFO_DOPPLER_TILES: *value = h->dopTilesLast; return BLAH2HIP_OK;
+  case BLAH2HIP_INFO_CFAR2D_SEG_ROWS: *value = h->cfar2dSegRowsLast; return BLAH2HIP_OK;
+  case BLAH2HIP_INFO_CFAR2D_GRID: *value = h->cfar2dGridLast; return BLAH2HIP_OK;
   case BLAH2HIP_INFO_LEAK_LAGS: *value = h->lastLeakLags; return BLAH2HIP_OK;
   case BLAH2HIP_INFO_LEAK_MAX_E12: *value = (int64_t)std::llround(h->lastLeakMax * 1e12); return BLAH2HIP_OK;
   case BLAH2HIP_INFO_HOT_COLUMNS: { // of the last call's first CPI; waits for the device
@@ -2041,7 +2060,10 @@ int blah2hip_cfar2d_dev(blah2hip_amb_t h, const void *d_map, const double *d_met
     ta.alphaLds = (tableN <= 2048 && c2t_lds_bytes(hC, (int)tableN) <= 160 * 1024) ? (int32_t)tableN : 0;
     const size_t lds = c2t_lds_bytes(hC, ta.alphaLds);
     const int64_t nAll = (int64_t)ta.tilesX * ta.tilesY * n_cpi;
-    const int grid = (int)std::max<int64_t>(8, (std::min<int64_t>(nAll, h->numCU) + 7) & ~7); // one persistent workgroup per CU (LDS)
+    const int64_t wgCap = h->cfar2dGridForce > 0 ? h->cfar2dGridForce : h->numCU; // BLAH2HIP_OPT_CFAR2D_GRID
+    const int grid = (int)std::max<int64_t>(8, (std::min<int64_t>(nAll, wgCap) + 7) & ~7); // one persistent workgroup per CU (LDS)
+    h->cfar2dGridLast = grid;
+    h->cfar2dSegRowsLast = 0;
     if ((rc = tic(h, BLAH2HIP_K_CFAR, st))) return rc;
     auto launch = [&](auto kern) -> int {
       LDSCFG(kern, lds);
@@ -2056,6 +2078,7 @@ int blah2hip_cfar2d_dev(blah2hip_amb_t h, const void *d_map, const double *d_met
     if ((rc = toc(h, BLAH2HIP_K_CFAR, st))) return rc;
     return BLAH2HIP_OK;
   }
+  h->cfar2dGridLast = h->cfar2dSegRowsLast = 0;
   if ((rc = tic(h, BLAH2HIP_K_SAT_ROWS, st))) return rc;
   hipLaunchKernelGGL(sat_rows_kernel, dim3(nD, n_cpi), dim3(256), 0, st, a);
   if ((rc = toc(h, BLAH2HIP_K_SAT_ROWS, st))) return rc;

@@ -245,6 +245,16 @@ class Ambiguity:
             which = {"auto": _lib.CFAR2D_AUTO, "tile": _lib.CFAR2D_TILE, "sat": _lib.CFAR2D_SAT, "stream": _lib.CFAR2D_STREAM}[which]
         check(self._L.blah2hip_amb_set_option(self._h, _lib.OPT_CFAR2D_KERNEL, int(which)))
 
+    def set_cfar2d_seg_rows(self, n):
+        """Doppler rows per segment of the 2-D stream kernel (0 = its cost model); ``info(INFO_CFAR2D_SEG_ROWS)`` reports
+        what the last launch used."""
+        check(self._L.blah2hip_amb_set_option(self._h, _lib.OPT_CFAR2D_SEG_ROWS, int(n)))
+
+    def set_cfar2d_grid(self, n):
+        """Workgroup cap of the persistent 2-D tile kernel (0 = one per CU); ``info(INFO_CFAR2D_GRID)`` reports the grid of
+        the last launch."""
+        check(self._L.blah2hip_amb_set_option(self._h, _lib.OPT_CFAR2D_GRID, int(n)))
+
     def set_fir(self, wiener_hopf):
         """Run the clutter filter's FIR fused into the range kernel with the taps of ``wiener_hopf`` (a WienerHopf whose
         ``estimate_dev_fmt`` precedes each ``process_dev`` on the same stream); None: back to the plain range kernels."""

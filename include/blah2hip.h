@@ -168,6 +168,11 @@ int blah2hip_amb_get_axes(blah2hip_amb_t h, int32_t *delay, double *doppler);
                                        * tone's amplitude at every Doppler (nD <= 4096), and the test is lowered by that factor.
                                        * 1 (default): CPIs of >= 35 000 samples (a shorter one cannot hold such a peak);
                                        * 2: every call; 0: never.  No reference counterpart (the reference computes in fp64). */
+#define BLAH2HIP_OPT_CFAR2D_SEG_ROWS 9 /* Doppler rows per segment of the 2-D stream kernel (a wave walks one segment of one strip of columns);
+                                       * 0 = the launch's cost model (8 ... 1024 rows, or the whole map); larger values are clipped to the
+                                       * map.  For tests: the seams between segments fall on other rows than a small fixture would give them */
+#define BLAH2HIP_OPT_CFAR2D_GRID 10   /* workgroup cap of the PERSISTENT 2-D tile kernel, rounded up to a multiple of 8; 0 = one per CU (or
+                                       * per tile).  A small cap makes every workgroup walk many tiles on a small fixture (tests) */
 #define BLAH2HIP_CFAR2D_AUTO 0
 #define BLAH2HIP_CFAR2D_TILE 1
 #define BLAH2HIP_CFAR2D_SAT 2
@@ -207,6 +212,8 @@ int blah2hip_amb_set_option(blah2hip_amb_t h, int option, int64_t value);
 #define BLAH2HIP_INFO_HOT_COLUMNS_MISSED 11   /* the most columns of any CPI of the last call that passed the hot-column test and were NOT
                                                * rewritten -- beyond the 16 a CPI, or beyond 64 candidates in one quarter of the lags:
                                                * they keep the fp32 floor; waits for that call's stream */
+#define BLAH2HIP_INFO_CFAR2D_SEG_ROWS 12     /* rows per segment of the last 2-D detector launch if it was the stream kernel, else 0 */
+#define BLAH2HIP_INFO_CFAR2D_GRID 13         /* workgroups of the last 2-D detector launch if it was the tile kernel, else 0 */
 #define BLAH2HIP_INFO_DOPPLER_TILES 7       /* tiles (units of work the persistent workgroups walk) of the last Doppler launch; 0 for the
                                              * non-persistent kernels */
 int blah2hip_amb_get_info(blah2hip_amb_t h, int key, int64_t *value);
@@ -278,7 +285,13 @@ int blah2hip_cfar1d_map(const float *map, uint32_t n_doppler, uint32_t n_delay, 
  * rectangle (2(ngd+ntd)+1) x (2(ngf+ntf)+1) minus the guard box, in-bounds cells
  * only, delay column 0 never trains, |z|^2 statistic, alpha = N(pfa^(-1/N)-1);
  * with n_guard_doppler = n_train_doppler = 0 it is exactly blah2hip_cfar1d_*.
- * Same output conventions as the 1-D entry points. */
+ * Same output conventions as the 1-D entry points.
+ * Cells that are not finite: |z|^2 is formed in fp64, and a NaN or +Inf cell makes the window sums that hold it NaN
+ * or +Inf.  The one-pass kernels (stream, tile) sum every window on its own, so exactly the cells whose training
+ * window holds such a cell are lost (nothing exceeds a NaN or +Inf threshold), and a +Inf cell itself is reported when
+ * its own window is finite.  The summed-area table carries the value into every prefix below and right of the cell:
+ * there the table kernels may lose detections (all of them, in the worst case), but they never report a cell the
+ * one-pass kernels would not. */
 int blah2hip_cfar2d_dev(blah2hip_amb_t h, const void *d_map, const double *d_metrics, uint32_t n_cpi,
                         double pfa, int32_t n_guard_delay, int32_t n_train_delay,
                         int32_t n_guard_doppler, int32_t n_train_doppler, int32_t min_delay,

@@ -316,6 +316,60 @@ def cfar2d(m, delay_axis, doppler_axis, noise_power, pfa, ng_d, nt_d, ng_f, nt_f
     return res
 
 
+def cfar2d_window_sums(sq, ng_d, nt_d, ng_f, nt_f):
+    """Sum of the training cells of every cell's window as a sum of shifted copies of ``sq`` (|z|^2, [nD, nC]), one
+    per training offset, in the brute-force loops' order (Doppler offset outer, delay offset inner; an offset that
+    leaves the map adds an exact 0): bitwise what :func:`cfar2d_bruteforce` accumulates.  Column 0 never trains."""
+    nD, nC = sq.shape
+    hR, hC = ng_f + nt_f, ng_d + nt_d
+    pad = np.zeros((nD + 2 * hR, nC + 2 * hC))
+    pad[hR:hR + nD, hC:hC + nC] = sq
+    pad[:, hC] = 0.0
+    tot = np.zeros((nD, nC))
+    with np.errstate(invalid="ignore"):
+        for di in range(-min(hR, nD - 1), min(hR, nD - 1) + 1):
+            for dj in range(-min(hC, nC - 1), min(hC, nC - 1) + 1):
+                if abs(di) <= ng_f and abs(dj) <= ng_d:
+                    continue
+                tot += pad[hR + di:hR + di + nD, hC + dj:hC + dj + nC]
+    return tot
+
+
+def cfar2d_additive(m, delay_axis, doppler_axis, noise_power, pfa, ng_d, nt_d, ng_f, nt_f, min_delay, min_doppler,
+                    return_margin=False):
+    """:func:`cfar2d_bruteforce` vectorised over the cells, window sums by :func:`cfar2d_window_sums`.  No summed-area
+    differences, so a window of small cells beside a cell 1e38 times larger keeps its sum (:func:`cfar2d` loses it),
+    and a NaN / Inf cell only reaches the windows that hold it.  |z|^2 is re^2 + im^2 (the kernels' form; ``abs(z*z)``
+    turns an infinite cell into NaN).  Same result tuple as :func:`cfar2d`."""
+    m = np.asarray(m, dtype=np.complex128)
+    nD, nC = m.shape
+    sq = m.real * m.real + m.imag * m.imag
+    hR, hC = ng_f + nt_f, ng_d + nt_d
+    tot = cfar2d_window_sums(sq, ng_d, nt_d, ng_f, nt_f)
+    i = np.arange(nD)
+    j = np.arange(nC)
+    R0, R1 = np.clip(i - hR, 0, nD), np.clip(i + hR + 1, 0, nD)
+    G0, G1 = np.clip(i - ng_f, 0, nD), np.clip(i + ng_f + 1, 0, nD)
+    C0, C1 = np.clip(j - hC, 0, nC), np.clip(j + hC + 1, 0, nC)
+    H0, H1 = np.clip(j - ng_d, 0, nC), np.clip(j + ng_d + 1, 0, nC)
+    cols = lambda a, b: np.maximum(b, 1) - np.maximum(a, 1)  # columns >= 1 in [a, b)
+    n = np.outer(R1 - R0, cols(C0, C1)) - np.outer(G1 - G0, cols(H0, H1))
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        alpha = n * (np.power(pfa, -1.0 / n) - 1)
+        thr = alpha * (tot / n)
+        hit = (sq > thr) & (n > 0)
+    hit &= (np.asarray(delay_axis) >= min_delay)[None, :]
+    hit &= (np.abs(np.asarray(doppler_axis)) >= min_doppler)[:, None]
+    ii, jj = np.nonzero(hit)
+    with np.errstate(divide="ignore"):
+        snr = 10.0 * np.log10(np.abs(m[ii, jj])) - noise_power
+    res = ((jj + delay_axis[0]).astype(np.float64), np.asarray(doppler_axis)[ii].astype(np.float64), snr)
+    if return_margin:
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return res + (sq / thr,)
+    return res
+
+
 # --------------------------------------------------------------------------
 def spectrum_dims(n, bandwidth):
     """``SpectrumAnalyser::SpectrumAnalyser`` (src/process/spectrum/SpectrumAnalyser.cpp:9-24):

@@ -2,8 +2,10 @@
 right before it checks anything.  Fast forms against their definitional forms, and
 the derived sizes against the invariants the reference's constructor guarantees."""
 import numpy as np
+import pytest
 from hypothesis import given, settings, strategies as st
 
+import cfar_crafted as X
 from oracle import blah2_oracle as O
 from oracle import ref_lib as R
 
@@ -86,6 +88,55 @@ def test_cfar_fast_forms_equal_their_definitions(seed, n_guard, n_train, min_del
     assert all(np.array_equal(u, v) for u, v in zip(c[:2], e[:2]))
     if ng_f == 0 and nt_f == 0:  # the 2-D extension collapses to CfarDetector1D.cpp:23-100
         assert all(np.array_equal(u, v) for u, v in zip(a[:2], e[:2]))
+
+
+ADDITIVE_MAPS = {
+    # name: (nD, nC, Doppler axis, map flavour)
+    "small": (9, 21, np.arange(-4.0, 5.0), "floor"),
+    "one-column": (7, 1, np.arange(-3.0, 4.0), "floor"),
+    "fewer-rows-than-the-halo": (3, 30, np.arange(-1.0, 2.0), "floor"),
+    "one-sided-axis": (12, 17, 11.5 + np.arange(-6.0, 6.0), "floor"),
+    "dynamic-range": (10, 24, np.arange(-5.0, 5.0), "range"),
+}
+
+
+@pytest.mark.parametrize("window", X.WINDOWS, ids=lambda w: "w" + "_".join(map(str, w)))
+@pytest.mark.parametrize("name", sorted(ADDITIVE_MAPS))
+def test_cfar2d_additive_equals_the_bruteforce_definition(name, window):
+    """The vectorised additive form (what the crafted detector tests compare against) returns the hit list of the
+    four-loop definition: every stream-kernel window, two tile-only windows and a summed-area-only one, on a map of
+    one column, one with fewer rows than the halo, a one-sided Doppler axis and cells from 1e-20 to 1e18."""
+    nD, nC, doppler, kind = ADDITIVE_MAPS[name]
+    rng = np.random.default_rng([nD, nC, *window])
+    m = np.sqrt(rng.exponential(1.0, (nD, nC))) * np.exp(2j * np.pi * rng.uniform(0, 1, (nD, nC)))
+    m[rng.integers(0, nD, 6), rng.integers(0, nC, 6)] *= 40.0
+    if kind == "range":
+        m *= 10.0 ** (-20.0 + 38.0 * np.arange(nD * nC).reshape(nD, nC) / (nD * nC - 1)) / np.abs(m).max()
+    m = m.astype(np.complex64).astype(np.complex128)
+    delay = np.arange(-2, nC - 2)
+    for min_delay, min_doppler in ((-128, 0.0), (0, 2.0)):
+        a = O.cfar2d_bruteforce(m, delay, doppler, 1.5, 0.05, *window, min_delay, min_doppler)
+        b = O.cfar2d_additive(m, delay, doppler, 1.5, 0.05, *window, min_delay, min_doppler, return_margin=True)
+        assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+        assert np.allclose(a[2], b[2], rtol=0, atol=1e-12)
+        assert b[3].shape == (nD, nC)
+        if nC > 1 and min_delay == -128:
+            assert len(a[0]) > 0
+
+
+@pytest.mark.parametrize("group", sorted(X.groups()))
+def test_crafted_detector_inputs_keep_clear_of_the_threshold(group):
+    """The conditions test_cfar_crafted_gpu.py rests on, for every input it runs: the oracle puts no tested cell within
+    1e-9 of its threshold (so the additive kernels are compared by plain set equality), and at most 1 % of the hits lie
+    inside the summed-area kernels' per-cell band."""
+    n_hits = 0
+    for case in X.groups()[group]:
+        e = X.expected(case)
+        assert e.in_band == 0, (case.name, e.in_band)
+        if case.kind != "nonfinite" and "sat" in case.kernels():
+            assert e.sat_share <= 0.01, (case.name, e.sat_share)
+        n_hits += sum(len(h) for h in e.hits)
+    assert n_hits > 0
 
 
 @FAST
