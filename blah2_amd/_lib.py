@@ -43,6 +43,7 @@ INFO_DOPPLER_GRID, INFO_DOPPLER_TILES = 6, 7
 INFO_LEAK_LAGS, INFO_LEAK_MAX_E12 = 8, 9
 INFO_HOT_COLUMNS, INFO_HOT_COLUMNS_MISSED = 10, 11
 INFO_CFAR2D_SEG_ROWS, INFO_CFAR2D_GRID = 12, 13
+INFO_DETECT_GRID, INFO_DETECT_TILED = 14, 15
 
 
 class Blah2HipError(RuntimeError):
@@ -60,6 +61,10 @@ class AmbDims(C.Structure):
 
 class Hit(C.Structure):
     _fields_ = [("row", C.c_int32), ("col", C.c_int32), ("snr", C.c_double)]
+
+
+class Det(C.Structure):
+    _fields_ = [("row", C.c_int32), ("col", C.c_int32), ("delay", C.c_double), ("doppler", C.c_double), ("snr", C.c_double)]
 
 
 # every symbol include/blah2hip.h declares: name -> (restype, argtypes)
@@ -95,6 +100,8 @@ SYMBOLS = {
     "blah2hip_centroid": (C.c_int, [_vp, _vp, _vp, _u32, C.c_uint16, C.c_uint16, _dbl, _vp, _vp, _vp, C.POINTER(_u32)]),
     "blah2hip_interpolate": (C.c_int, [_vp, _vp, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _dbl, C.c_int, C.c_int,
                                        _vp, _vp, _vp, C.POINTER(_u32)]),
+    "blah2hip_detect_dev": (C.c_int, [_vp, _vp, _vp, _u32, _vp, _u32, _vp, C.c_uint16, C.c_uint16, _dbl, C.c_int, C.c_int, C.c_int,
+                                      _vp, _u32, _vp, _vp]),
     "blah2hip_clutter_create": (C.c_int, [_i32, _i32, _u32, C.c_int, _u32, C.POINTER(_vp)]),
     "blah2hip_clutter_destroy": (C.c_int, [_vp]),
     "blah2hip_clutter_process_c64": (C.c_int, [_vp, _vp, _vp, _u32, _vp, C.POINTER(C.c_int)]),

@@ -3,6 +3,7 @@
 // libamdhip64 and nothing else.
 #include "kernels.hpp"
 #include "cfar_kernels.hpp"
+#include "detect_kernels.hpp"
 #include "timing.hpp"
 
 #include <algorithm>
@@ -121,6 +122,8 @@ struct blah2hip_amb_s {
   cf *d_bf = nullptr;               // chirp-kernel spectrum / M in register layout
   cf *d_bfn = nullptr;              // the same in natural order (M = 2048 only: doppler_tilew_kernel)
   double *d_sat = nullptr;          // 2-D CFAR summed-area table [max_batch][nD+1][nDelay+1]
+  uint32_t *d_detWords = nullptr;   // detect_finish_kernel, tiled form: [2][max_batch] records appended, tickets taken; zero between launches
+  int detGridLast = 0, detTiledLast = 0; // BLAH2HIP_INFO_DETECT_GRID / _TILED
 
   KernelTimer<BLAH2HIP_K_COUNT> timer;
 
@@ -1192,6 +1195,8 @@ int blah2hip_amb_create_ex(int32_t delay_min, int32_t delay_max, int32_t doppler
   HIPCHK(hipMalloc(&h->d_partMax, (size_t)h->nParts * max_batch * sizeof(float)));
   HIPCHK(hipMalloc(&h->d_tickets, max_batch * sizeof(uint32_t)));
   HIPCHK(hipMemset(h->d_tickets, 0, max_batch * sizeof(uint32_t)));
+  HIPCHK(hipMalloc(&h->d_detWords, 2 * max_batch * sizeof(uint32_t)));
+  HIPCHK(hipMemset(h->d_detWords, 0, 2 * max_batch * sizeof(uint32_t)));
   HIPCHK(hipMalloc(&h->d_metrics, 2 * max_batch * sizeof(double)));
   HIPCHK(hipMalloc(&h->d_doppler, nD * sizeof(double)));
   HIPCHK(hipMalloc(&h->d_count, max_batch * sizeof(uint32_t)));
@@ -1243,7 +1248,8 @@ int blah2hip_amb_destroy(blah2hip_amb_t h)
                   (void *)h->d_partSum, (void *)h->d_partMax, (void *)h->d_tickets, (void *)h->d_metrics,
                   (void *)h->d_doppler, h->d_in, (void *)h->d_rot,
                   (void *)h->d_hits, (void *)h->d_count, (void *)h->d_sat, (void *)h->d_dtw, (void *)h->d_chirp,
-                  (void *)h->d_bf, (void *)h->d_bfn, (void *)h->d_H, (void *)h->d_dopW64, (void *)h->d_hotCount, (void *)h->d_firK0})
+                  (void *)h->d_bf, (void *)h->d_bfn, (void *)h->d_H, (void *)h->d_dopW64, (void *)h->d_hotCount, (void *)h->d_firK0,
+                  (void *)h->d_detWords})
     if (p) (void)hipFree(p);
   for (auto &t : h->alphaTables)
     if (t.d) (void)hipFree(t.d);
@@ -1377,6 +1383,8 @@ int blah2hip_amb_get_info(blah2hip_amb_t h, int key, int64_t *value)
   case BLAH2HIP_INFO_DOPPLER_TILES: *value = h->dopTilesLast; return BLAH2HIP_OK;
   case BLAH2HIP_INFO_CFAR2D_SEG_ROWS: *value = h->cfar2dSegRowsLast; return BLAH2HIP_OK;
   case BLAH2HIP_INFO_CFAR2D_GRID: *value = h->cfar2dGridLast; return BLAH2HIP_OK;
+  case BLAH2HIP_INFO_DETECT_GRID: *value = h->detGridLast; return BLAH2HIP_OK;
+  case BLAH2HIP_INFO_DETECT_TILED: *value = h->detTiledLast; return BLAH2HIP_OK;
   case BLAH2HIP_INFO_LEAK_LAGS: *value = h->lastLeakLags; return BLAH2HIP_OK;
   case BLAH2HIP_INFO_LEAK_MAX_E12: *value = (int64_t)std::llround(h->lastLeakMax * 1e12); return BLAH2HIP_OK;
   case BLAH2HIP_INFO_HOT_COLUMNS: { // of the last call's first CPI; waits for the device
@@ -2250,6 +2258,54 @@ int blah2hip_interpolate(const double *delay, const double *doppler, const doubl
     kept++;
   }
   *count_out = kept;
+  return BLAH2HIP_OK;
+}
+
+// ------------------------------------------- centroid / interpolate, device --
+// Centroid::process and Interpolate::process on device-resident hit lists and maps (blah2.cpp:285-287 without the host):
+// one launch of detect_finish_kernel, nothing in front of it.
+int blah2hip_detect_dev(blah2hip_amb_t h, const void *d_map, const double *d_metrics, uint32_t n_cpi,
+                        const blah2hip_hit_t *d_hits, uint32_t cap, const uint32_t *d_count,
+                        uint16_t n_centroid_delay, uint16_t n_centroid_doppler, double resolution_doppler,
+                        int do_centroid, int do_delay, int do_doppler,
+                        blah2hip_det_t *d_out, uint32_t cap_out, uint32_t *d_count_out, void *stream)
+{
+  if (!h || !d_hits || !d_count || !d_out || !d_count_out) return fail(BLAH2HIP_ERR_INVALID, "NULL argument");
+  if (n_cpi == 0 || n_cpi > h->dims.max_batch) return fail(BLAH2HIP_ERR_INVALID, "n_cpi outside [1, max_batch]");
+  if (cap == 0) return fail(BLAH2HIP_ERR_INVALID, "cap is 0");
+  HIPCHK(hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  DetectArgs a;
+  a.map = d_map ? (const cf *)d_map : h->d_map;
+  a.metrics = d_metrics ? d_metrics : h->d_metrics;
+  a.doppler = h->d_doppler;
+  a.hits = d_hits;
+  a.count = d_count;
+  a.out = d_out;
+  a.countOut = d_count_out;
+  a.appended = h->d_detWords;
+  a.tickets = h->d_detWords + h->dims.max_batch;
+  a.nD = (int32_t)h->dims.n_doppler_bins;
+  a.nDelay = (int32_t)h->dims.n_delay_bins;
+  a.delayMin = h->delayAxis[0];
+  a.nCentroidDelay = (int32_t)n_centroid_delay;
+  a.boxDoppler = n_centroid_doppler * resolution_doppler; // the expression of blah2hip_centroid (Centroid.cpp:38-39)
+  a.cap = cap;
+  a.capOut = cap_out;
+  a.doCentroid = do_centroid != 0; a.doDelay = do_delay != 0; a.doDoppler = do_doppler != 0;
+  // A list that fits one LDS tile: one workgroup per CPI, counter in LDS.  Longer lists: blocks of DET_BLOCK hits over G
+  // workgroups per CPI, enough of them to fill the device with a lone CPI at its cap and no more than eight a CPI once
+  // the batch alone fills it (a workgroup without a block of its CPI's list leaves after one load).
+  const uint32_t blocks = (cap + DET_BLOCK - 1) / DET_BLOCK;
+  const bool tiled = cap > (uint32_t)DET_TILE;
+  const uint32_t G = tiled ? std::min(blocks, std::max(8u, (uint32_t)(4 * h->numCU) / n_cpi)) : 1u;
+  if (tiled)
+    hipLaunchKernelGGL(detect_finish_kernel<true>, dim3(G, n_cpi), dim3(DET_BLOCK), 0, st, a);
+  else
+    hipLaunchKernelGGL(detect_finish_kernel<false>, dim3(1, n_cpi), dim3(DET_BLOCK), 0, st, a);
+  HIPCHK(hipGetLastError());
+  h->detGridLast = (int)G;
+  h->detTiledLast = tiled ? 1 : 0;
   return BLAH2HIP_OK;
 }
 

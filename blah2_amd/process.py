@@ -457,6 +457,41 @@ class Interpolate:
         return Detection(od[:k.value], of[:k.value], os_[:k.value])
 
 
+DET_DTYPE = np.dtype([("row", np.int32), ("col", np.int32), ("delay", np.float64), ("doppler", np.float64), ("snr", np.float64)])
+
+
+class DetectionFinisher:
+    """:class:`Centroid`, then :class:`Interpolate`, on device-resident hit lists and maps (blah2.cpp:285-287 without the
+    host; blah2hip_detect_dev): what the batched chains run behind ``process_dev`` of a detector.  ``doCentroid=False``
+    skips the first step; ``doDelay = doDoppler = False`` leaves the list as Centroid returns it."""
+
+    def __init__(self, nDelay, nDoppler, resolutionDoppler, doDelay=True, doDoppler=True, doCentroid=True):
+        for name, v in (("nDelay", nDelay), ("nDoppler", nDoppler)):
+            if not 0 <= int(v) <= 0xFFFF:  # uint16_t in the reference
+                raise ValueError(f"{name} outside uint16 range")
+        self.nDelay, self.nDoppler, self.resolutionDoppler = int(nDelay), int(nDoppler), float(resolutionDoppler)
+        self.doDelay, self.doDoppler, self.doCentroid = bool(doDelay), bool(doDoppler), bool(doCentroid)
+
+    def process_dev(self, amb, n_cpi, d_hits, cap, d_count, d_out, cap_out, d_count_out, d_map=None, d_metrics=None, stream=0):
+        """Enqueue one kernel for n_cpi hit lists (d_hits [n_cpi][cap], d_count [n_cpi], as a detector's ``process_dev``
+        wrote them) and their maps (None = the engine's internal buffers): final records (:data:`DET_DTYPE`) into d_out
+        [n_cpi][cap_out], their number into d_count_out [n_cpi] (it may exceed cap_out; then cap_out were stored)."""
+        check(amb._L.blah2hip_detect_dev(amb._h, d_map, d_metrics, n_cpi, d_hits, cap, d_count, self.nDelay, self.nDoppler,
+                                         self.resolutionDoppler, int(self.doCentroid), int(self.doDelay), int(self.doDoppler),
+                                         d_out, cap_out, d_count_out, stream))
+
+
+def dets_to_detection(recs, count, cap_out):
+    """One CPI's final records (``blah2hip_det_t``, :data:`DET_DTYPE`; arbitrary order) -> :class:`Detection` in the
+    reference's emission order: Centroid and Interpolate keep the detector's row-major order (Centroid.cpp:34-69,
+    Interpolate.cpp:35-87), so the records are sorted by the hit they came from."""
+    if count > cap_out:
+        raise Blah2HipError(_lib.ERR_CAPACITY, f"{count} detections, capacity {cap_out}")
+    d = np.asarray(recs[:count])
+    d = d[np.lexsort((d["col"], d["row"]))]
+    return Detection(d["delay"], d["doppler"], d["snr"])
+
+
 class WienerHopf:
     """src/process/clutter/WienerHopf.h:68-78: least-squares clutter canceller.
 

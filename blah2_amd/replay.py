@@ -564,13 +564,19 @@ def _hip_runtime(torch):
 class GpuChain:
     """blah2.cpp:268-287 on the HIP engine for batches of CPIs, device resident from the int16 upload to the hit lists:
     clutter filter (optional; reads the .rspduo words directly) -> ambiguity -> metrics -> CFAR (blah2hip_cfar1d_dev),
-    then Centroid and Interpolate (host arithmetic on a handful of detections) when ``nCentroid`` is configured.  ``cfg``
-    carries the keys of the reference's config.yml ``process`` section plus ``fs`` and ``n_samples``.
+    then Centroid and Interpolate when ``nCentroid`` is configured.  ``cfg`` carries the keys of the reference's config.yml
+    ``process`` section plus ``fs`` and ``n_samples``.
+
+    ``detect`` says where Centroid and Interpolate run.  "device" (the default when ``nCentroid`` is configured): one more
+    kernel on the compute stream (blah2hip_detect_dev) on the hit lists and maps where they lie; the copy stream brings
+    back the final records (32 bytes each) and their counts, the map stays on the device unless ``want_map`` asks for it,
+    and collecting a batch makes no call into the library.  "host": the hit lists and every CPI's map come back and the
+    host functions (blah2hip_centroid, blah2hip_interpolate) run per CPI.
 
     A ring of ``depth`` slots, each with a pinned host batch, its device copy, device result buffers and their pinned
     host copies.  For batch k: reader threads fill the slot's host buffer; the COPY stream uploads it; the COMPUTE stream
     (after the upload's event) runs the chain into the slot's result buffers; the copy stream (after the compute event)
-    brings {metrics, ok flags, hit counts, the first ``hit_copy`` hit records per CPI, and the map when wanted} back.
+    brings {metrics, ok flags, hit counts, the first ``hit_copy`` hit (or final) records per CPI, and the map when wanted} back.
     Batch k+1's read and upload and batch k-1's download overlap batch k's kernels.
 
     A CPI whose clutter filter fails (normal equations not positive definite) is SKIPPED like the reference does
@@ -586,7 +592,10 @@ class GpuChain:
 
     def __init__(self, cfg: dict, device: int = 0, batch: int = 1, want_map: bool = False, depth: int = 3,
                  reader_threads: int = 4, hit_copy: int = 4096, read_mode: str = "memmove", numa: bool = True,
-                 layout: str = "rspduo", usrp_block: Optional[int] = None):
+                 layout: str = "rspduo", usrp_block: Optional[int] = None, detect: Optional[str] = None):
+        if detect not in (None, "device", "host"):
+            raise ValueError(f"detect {detect!r}: 'device' or 'host'")
+        self._detect_arg = detect
         if layout not in ("rspduo", "usrp", "cs8"):
             raise ValueError(f"layout {layout!r}: 'rspduo', 'usrp' or 'cs8'")
         if layout == "usrp" and (usrp_block is None or int(usrp_block) <= 0):
@@ -660,7 +669,13 @@ class GpuChain:
             if "nCentroid" in det_c:  # blah2.cpp:176-181
                 self.centroid = blah2_amd.Centroid(det_c["nCentroid"], det_c["nCentroid"], 1 / (n / self.fs))
                 self.interp = blah2_amd.Interpolate(True, True)
-        self.need_map = self.want_map or self.interp is not None
+        # where Centroid and Interpolate run (None: not configured)
+        self.detect = (self._detect_arg or "device") if self.centroid is not None else None
+        self.finisher = None
+        if self.detect == "device":
+            self.finisher = blah2_amd.DetectionFinisher(self.centroid.nDelay, self.centroid.nDoppler, self.centroid.resolutionDoppler,
+                                                        self.interp.doDelay, self.interp.doDoppler)
+        self.need_map = self.want_map or self.detect == "host"
         dev = self.dev = torch.device("cuda", device)
         self.cap = int(det_c.get("capacity", min(nD * nC, 1 << 16)))
         self.hit_copy = min(self.cap, int(hit_copy))
@@ -695,6 +710,7 @@ class GpuChain:
         self.planes = torch.empty((2, B, n), dtype=torch.complex64, device=dev) if self.layout == "usrp" else None
         self.busy_ms, self.batches_done = 0.0, 0  # kernels' time on the compute stream / batches collected, since construction
         self.slots = []
+        on_dev = self.finisher is not None
         for _ in range(self.depth):
             s = {
                 "h_iq": None,  # pinned staging batch of the pread path, allocated when that path first runs
@@ -710,7 +726,12 @@ class GpuChain:
                 "d_map": torch.zeros((B, nD, nC), dtype=torch.complex64, device=dev),
                 "h_met": torch.zeros((B, 2), dtype=torch.float64).pin_memory(),
                 "h_ok": torch.ones(B, dtype=torch.int32).pin_memory(),
-                "h_hits": torch.zeros((B, self.hit_copy, 2), dtype=torch.float64).pin_memory(),
+                "h_hits": None if on_dev else torch.zeros((B, self.hit_copy, 2), dtype=torch.float64).pin_memory(),
+                # detect="device": blah2hip_det_t records, 32 bytes, as many as the hit list may hold (Centroid only drops)
+                "d_dets": torch.zeros((B, self.cap, 4), dtype=torch.float64, device=dev) if on_dev else None,
+                "d_dcnt": torch.zeros(B, dtype=torch.int32, device=dev) if on_dev else None,
+                "h_dets": torch.zeros((B, self.hit_copy, 4), dtype=torch.float64).pin_memory() if on_dev else None,
+                "h_dcnt": torch.zeros(B, dtype=torch.int32).pin_memory() if on_dev else None,
                 "h_cnt": torch.zeros(B, dtype=torch.int32).pin_memory(),
                 "h_map": torch.zeros((B, nD, nC), dtype=torch.complex64).pin_memory() if self.need_map else None,
                 "uploaded": torch.cuda.Event(), "downloaded": torch.cuda.Event(),
@@ -826,6 +847,10 @@ class GpuChain:
             if self.cfar is not None:
                 self.cfar.process_dev(amb, cnt, slot["d_hits"].data_ptr(), self.cap, slot["d_cnt"].data_ptr(),
                                       slot["d_map"].data_ptr(), slot["d_met"].data_ptr(), st)
+                if self.finisher is not None:
+                    self.finisher.process_dev(amb, cnt, slot["d_hits"].data_ptr(), self.cap, slot["d_cnt"].data_ptr(),
+                                              slot["d_dets"].data_ptr(), self.cap, slot["d_dcnt"].data_ptr(),
+                                              slot["d_map"].data_ptr(), slot["d_met"].data_ptr(), st)
             slot["computed"].record(self.compute)
         with torch.cuda.stream(self.copy):
             self.copy.wait_event(slot["computed"])
@@ -833,8 +858,12 @@ class GpuChain:
             if self.wh is not None:
                 slot["h_ok"][:cnt].copy_(slot["d_ok"][:cnt], non_blocking=True)
             if self.cfar is not None:
-                slot["h_cnt"][:cnt].copy_(slot["d_cnt"][:cnt], non_blocking=True)
-                slot["h_hits"][:cnt].copy_(slot["d_hits"][:cnt, :self.hit_copy], non_blocking=True)
+                slot["h_cnt"][:cnt].copy_(slot["d_cnt"][:cnt], non_blocking=True)  # (device path: for the capacity check)
+                if self.finisher is not None:
+                    slot["h_dcnt"][:cnt].copy_(slot["d_dcnt"][:cnt], non_blocking=True)
+                    slot["h_dets"][:cnt].copy_(slot["d_dets"][:cnt, :self.hit_copy], non_blocking=True)
+                else:
+                    slot["h_hits"][:cnt].copy_(slot["d_hits"][:cnt, :self.hit_copy], non_blocking=True)
             if self.need_map:
                 slot["h_map"][:cnt].copy_(slot["d_map"][:cnt], non_blocking=True)
             slot["downloaded"].record(self.copy)
@@ -856,6 +885,18 @@ class GpuChain:
                 k = int(slot["h_cnt"][b])
                 if k > self.cap:
                     raise b2.Blah2HipError(b2._lib.ERR_CAPACITY, f"{k} detections in one CPI, capacity {self.cap}")
+                if self.finisher is not None:  # the final records, made on the device: sorted into emission order, no library call
+                    kd = int(slot["h_dcnt"][b])
+                    if kd > self.hit_copy:  # rare: beyond what the pipelined copy carries
+                        recs = slot["d_dets"][b, :kd].cpu().numpy()
+                    else:
+                        recs = slot["h_dets"][b, :max(kd, 1)].numpy()
+                    det = b2.dets_to_detection(recs.view(b2.DET_DTYPE).reshape(-1), kd, self.cap)
+                    r.update(delay=det.delay.tolist(), doppler=det.doppler.tolist(), snr=det.snr.tolist())
+                    if self.want_map:
+                        r["map"] = slot["h_map"][b].numpy().copy()
+                    res.append(r)
+                    continue
                 if k > self.hit_copy:  # rare: more hits than the pipelined copy carries -- fetch this CPI's records now
                     recs = slot["d_hits"][b, :k].cpu().numpy()
                 else:
@@ -1002,6 +1043,10 @@ def main(argv=None):
     ap.add_argument("--json", action="store_true",
                     help="emit, per CPI in file order, the map and detection documents blah2.cpp sends (one per line on "
                          "stdout, or as TCP frames with --connect)")
+    ap.add_argument("--detect", choices=("device", "host"), default=None,
+                    help="where Centroid and Interpolate run when detection.nCentroid is configured: in one kernel on the "
+                         "hit lists and maps where they lie (device, the default), or on the host, which then downloads "
+                         "every CPI's map")
     ap.add_argument("--connect", action="store_true",
                     help="with --json: send the documents to network.ip:ports.map / ports.detection of the config, "
                          "framed like Socket::sendData, instead of printing them")
@@ -1032,7 +1077,7 @@ def main(argv=None):
         dist = dist_
     import torch
     proc = gpu_processor(cfg, local % max(1, torch.cuda.device_count()), a.batch, want_map=a.json, layout=layout,
-                         usrp_block=a.usrp_block)
+                         usrp_block=a.usrp_block, detect=a.detect)
     rank0 = dist is None or dist.get_rank() == 0
     socks = {}
     if rank0 and a.json and a.connect:

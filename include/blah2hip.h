@@ -102,6 +102,16 @@ typedef struct blah2hip_hit {
   double snr;  /* 10*log10|z| - noisePower (CfarDetector1D.cpp:48) */
 } blah2hip_hit_t;
 
+/* One final detection as blah2hip_detect_dev writes it: the hit it came from and
+ * Detection's triplet after Centroid and Interpolate. */
+typedef struct blah2hip_det {
+  int32_t row;    /* Doppler bin index of the hit */
+  int32_t col;    /* delay bin index of the hit   */
+  double delay;   /* bins (Interpolate.cpp:61)    */
+  double doppler; /* Hz   (Interpolate.cpp:81)    */
+  double snr;     /* dB   (Interpolate.cpp:86)    */
+} blah2hip_det_t;
+
 const char *blah2hip_last_error(void);
 const char *blah2hip_version(void);
 int blah2hip_device_count(int *count);
@@ -216,6 +226,9 @@ int blah2hip_amb_set_option(blah2hip_amb_t h, int option, int64_t value);
 #define BLAH2HIP_INFO_CFAR2D_GRID 13         /* workgroups of the last 2-D detector launch if it was the tile kernel, else 0 */
 #define BLAH2HIP_INFO_DOPPLER_TILES 7       /* tiles (units of work the persistent workgroups walk) of the last Doppler launch; 0 for the
                                              * non-persistent kernels */
+#define BLAH2HIP_INFO_DETECT_GRID 14         /* workgroups per CPI of the last blah2hip_detect_dev launch */
+#define BLAH2HIP_INFO_DETECT_TILED 15        /* 1: that launch spread a CPI's hits over several workgroups (cap beyond one LDS tile of 1024
+                                              * hits), 0: one workgroup per CPI */
 int blah2hip_amb_get_info(blah2hip_amb_t h, int key, int64_t *value);
 
 /* Ambiguity::process + Map::set_metrics on host buffers (blah2.cpp:278-279).
@@ -325,6 +338,26 @@ int blah2hip_interpolate(const double *delay, const double *doppler, const doubl
                          const float *map, uint32_t n_doppler, uint32_t n_delay, const int32_t *delay_axis,
                          const double *doppler_axis, double noise_power, int do_delay, int do_doppler,
                          double *delay_out, double *doppler_out, double *snr_out, uint32_t *count_out);
+
+/* ---- Centroid + Interpolate on the device (blah2.cpp:285-287) -------------
+ * Centroid::process (Centroid.cpp:19-73), then Interpolate::process (Interpolate.cpp:20-91) on its survivors, for
+ * n_cpi device-resident hit lists as blah2hip_cfar1d_dev / blah2hip_cfar2d_dev leave them (d_hits [n_cpi][cap],
+ * d_count [n_cpi]; a count beyond cap: the first cap records are the list, d_count is not written) and the maps they
+ * came from (d_map / d_metrics as for the detectors, NULL = the handle's internal buffers).  The same arithmetic as
+ * blah2hip_centroid and blah2hip_interpolate on the handle's own axes: delay = col + delay[0], doppler = doppler[row];
+ * the uint16_t delay limits, the strict inequalities, the Doppler estimate stored into the delay variable (:80) and
+ * max(max(.,.),.) of :86 included.  do_centroid = 0 skips the first step, do_delay / do_doppler are
+ * Interpolate's two flags (both 0: the list after Centroid).  A record whose row or col lies outside the map is ignored.
+ * d_out: [n_cpi][cap_out] records in arbitrary order; d_count_out [n_cpi]: the number of final detections, also when it
+ * exceeds cap_out (then only cap_out were stored).  Enqueues ONE kernel on `stream` and nothing else: neither output
+ * needs to be zeroed.  Calls on one handle must be ordered on the device (one stream, or events): the multi-workgroup form
+ * counts through words the handle owns.  n_cpi outside [1, max_batch], cap == 0 or a NULL list / count / output:
+ * BLAH2HIP_ERR_INVALID. */
+int blah2hip_detect_dev(blah2hip_amb_t h, const void *d_map, const double *d_metrics, uint32_t n_cpi,
+                        const blah2hip_hit_t *d_hits, uint32_t cap, const uint32_t *d_count,
+                        uint16_t n_centroid_delay, uint16_t n_centroid_doppler, double resolution_doppler,
+                        int do_centroid, int do_delay, int do_doppler,
+                        blah2hip_det_t *d_out, uint32_t cap_out, uint32_t *d_count_out, void *stream);
 
 /* ---- WienerHopf clutter filter (WienerHopf.h:68-78) ---------------------
  * nBins = delay_max - delay_min taps (WienerHopf.cpp:12).  Up to 4081 taps run on one on-chip transform (fp32 planes or the int16
