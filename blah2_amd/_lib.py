@@ -25,6 +25,9 @@ OPT_DOPPLER_KERNEL, OPT_RANGE_GRID, OPT_RANGE_KERNEL, OPT_DOPPLER_GRID, OPT_FFT_
 OPT_LEAK_COMPENSATION = 7
 OPT_HOT_COLUMNS = 8
 OPT_CFAR2D_SEG_ROWS, OPT_CFAR2D_GRID = 9, 10
+OPT_MULTI_SURV_RANGE = 11
+MULTI_AUTO, MULTI_SHARED, MULTI_PER_CHANNEL = 0, 1, 2
+MAX_SURV = 8
 LEAK_OFF, LEAK_AUTO, LEAK_ALWAYS = 0, 1, 2
 CFAR2D_AUTO, CFAR2D_TILE, CFAR2D_SAT, CFAR2D_STREAM = 0, 1, 2, 3
 CLUTTER_OPT_SOLVE_K, CLUTTER_OPT_FFT_LEN, CLUTTER_OPT_CORR, CLUTTER_OPT_SOLVE_FORM, CLUTTER_OPT_SOLVE_E, CLUTTER_OPT_FIR_CARRY = 1, 2, 3, 4, 5, 6
@@ -38,6 +41,7 @@ DOPPLER_KERNEL_NAMES = {DOP_AUTO: "auto", DOP_TILE8: "tile8", DOP_TILE16: "tile1
                         DOP_COLUMN: "column", DOP_DIRECT: "direct", DOP_TILEW: "tilew", DOP_TILEW2: "tilew2", DOP_TILE16WG: "tile16wg", DOP_SUB4: "sub4", DOP_TILE8K: "tile8k", DOP_TILEW4: "tilew4",
                         DOP_PFA513: "pfa513"}
 RANGE_E16, RANGE_E8, RANGE_WAVE, RANGE_WAVE1K, RANGE_PS, RANGE_FIR = 1, 2, 3, 5, 6, 7
+RANGE_SHARED = 8
 INFO_LAST_DOPPLER_KERNEL, INFO_LAST_RANGE_KERNEL, INFO_DOPPLER_FFT_LEN, INFO_RANGE_GRID, INFO_NUM_CU = 1, 2, 3, 4, 5
 INFO_DOPPLER_GRID, INFO_DOPPLER_TILES = 6, 7
 INFO_LEAK_LAGS, INFO_LEAK_MAX_E12 = 8, 9
@@ -86,6 +90,8 @@ SYMBOLS = {
     "blah2hip_amb_process_i16": (C.c_int, [_vp, _vp, _u32, _vp, _vp]),
     "blah2hip_amb_process_i8": (C.c_int, [_vp, _vp, _vp, _u32, _vp, _vp]),
     "blah2hip_amb_process_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _u32, C.c_uint64, _vp, _vp, _vp]),
+    "blah2hip_amb_process_multi_dev": (C.c_int, [_vp, C.c_int, _vp, C.POINTER(_vp), _u32, _u32, C.c_uint64, _vp, _vp, _vp]),
+    "blah2hip_amb_process_multi_c32": (C.c_int, [_vp, _vp, C.POINTER(_vp), _u32, _u32, _vp, _vp]),
     "blah2hip_amb_read_last": (C.c_int, [_vp, _u32, _vp, _vp]),
     "blah2hip_amb_db_dev": (C.c_int, [_vp, _vp, _vp, _u32, _vp, _vp]),
     "blah2hip_cfar1d_dev": (C.c_int, [_vp, _vp, _vp, _u32, _dbl, _i32, _i32, _i32, _dbl, _vp, _u32, _vp, _vp]),

@@ -109,6 +109,7 @@ struct blah2hip_amb_s {
   int lastRange = 0;                // BLAH2HIP_INFO_LAST_RANGE_KERNEL
   int rangeKernel = 0;              // BLAH2HIP_OPT_RANGE_KERNEL (0 = by transform length)
   int fftLenForce = 0;              // BLAH2HIP_OPT_FFT_LEN (0 = planner)
+  int multiMode = BLAH2HIP_MULTI_AUTO; // BLAH2HIP_OPT_MULTI_SURV_RANGE
   int cfar2dForce = 0;              // BLAH2HIP_OPT_CFAR2D_KERNEL
   int dopGridForce = 0;             // BLAH2HIP_OPT_DOPPLER_GRID (0 = residency of the persistent kernel)
   int cfar2dSegRows = 0;            // BLAH2HIP_OPT_CFAR2D_SEG_ROWS (0 = cost model of cfar2d_stream_launch)
@@ -450,6 +451,27 @@ template <class In> int launch_rangew1k_t(blah2hip_amb_s *h, const RangeArgs &a,
   hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * RANGEW1K_WAVES), lds, st, a, in);
   HIPCHK(hipGetLastError());
   h->lastRange = BLAH2HIP_RANGE_WAVE1K;
+  return BLAH2HIP_OK;
+}
+
+// Two surveillance channels against one reference channel on rangew1k_shared_kernel: in0.x == in1.x, a.out is the block of
+// the pair's first channel, the second channel's block starts nCpi CPIs further
+template <class In> int launch_rangew1k_shared_t(blah2hip_amb_s *h, const RangeArgs &a, int nCpi, In in0, In in1, hipStream_t st)
+{
+  const size_t lds = (size_t)(Wave1kFft::TW_ELEMS + RANGEWS_WAVES * Wave1kFft::X_ELEMS) * sizeof(cf);
+  const bool shortx = a.plan.segLen <= 9 * 64;
+  const bool out7 = a.plan.nDelay <= 7 * 64;
+  const bool reuse = a.plan.segLen == 9 * 64 && a.plan.nDelay <= 7 * 64 + 1; // as in launch_rangew1k_t
+  auto kern = reuse ? (out7 ? rangew1k_shared_kernel<In, true, true, true> : rangew1k_shared_kernel<In, true, false, true>)
+              : shortx ? (out7 ? rangew1k_shared_kernel<In, true, true> : rangew1k_shared_kernel<In, true, false>)
+                       : (out7 ? rangew1k_shared_kernel<In, false, true> : rangew1k_shared_kernel<In, false, false>);
+  LDSCFG(kern, lds);
+  RangeSharedArgs sa;
+  sa.r = a;
+  sa.nCpi = nCpi;
+  const int grid = std::min<int>((a.nPulses + RANGEWS_WAVES - 1) / RANGEWS_WAVES, range_grid_cap(h, lds, RANGEWS_WAVES, 8)); // two waves per SIMD
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * RANGEWS_WAVES), lds, st, sa, in0, in1);
+  HIPCHK(hipGetLastError());
   return BLAH2HIP_OK;
 }
 
@@ -1349,6 +1371,11 @@ int blah2hip_amb_set_option(blah2hip_amb_t h, int option, int64_t value)
     if (value < 0 || value > 2) return fail(BLAH2HIP_ERR_INVALID, "hot columns: 0 (off), 1 (auto) or 2 (always)");
     h->hotMode = (int)value;
     return BLAH2HIP_OK;
+  case BLAH2HIP_OPT_MULTI_SURV_RANGE:
+    if (value != BLAH2HIP_MULTI_AUTO && value != BLAH2HIP_MULTI_SHARED && value != BLAH2HIP_MULTI_PER_CHANNEL)
+      return fail(BLAH2HIP_ERR_INVALID, "multi-channel range path: BLAH2HIP_MULTI_AUTO, _SHARED or _PER_CHANNEL");
+    h->multiMode = (int)value;
+    return BLAH2HIP_OK;
   default: return fail(BLAH2HIP_ERR_INVALID, "unknown option");
   }
 }
@@ -1413,38 +1440,12 @@ int blah2hip_amb_get_info(blah2hip_amb_t h, int key, int64_t *value)
   }
 }
 
-int blah2hip_amb_process_dev(blah2hip_amb_t h, int fmt, const void *d_x, const void *d_y,
-                             uint32_t n_cpi, uint64_t cpi_stride, void *d_map, double *d_metrics,
-                             void *stream)
+// The fixed-pattern leak of the kernel pair (rid, did) (calibrated at the pair's first launch): *leak = the calibration to
+// apply, or nullptr
+static int amb_leak_lookup(blah2hip_amb_s *h, int rid, int did, bool fused, hipStream_t st, const blah2hip_amb_s::LeakCal **leak)
 {
-  if (!h) return fail(BLAH2HIP_ERR_INVALID, "NULL handle");
-  if (n_cpi == 0 || n_cpi > h->dims.max_batch) return fail(BLAH2HIP_ERR_INVALID, "n_cpi outside [1, max_batch]");
-  if (fmt != BLAH2HIP_FMT_C32 && fmt != BLAH2HIP_FMT_I16 && fmt != BLAH2HIP_FMT_F16 && fmt != BLAH2HIP_FMT_I16X_C32Y &&
-      fmt != BLAH2HIP_FMT_I8 && fmt != BLAH2HIP_FMT_I8X_C32Y)
-    return fail(BLAH2HIP_ERR_INVALID, "unknown sample format");
-  if (!d_x || (fmt != BLAH2HIP_FMT_I16 && !d_y)) return fail(BLAH2HIP_ERR_INVALID, "NULL input pointer");
-#ifndef B2_EXPERIMENT_ALIASED_CPIS // tools/gpu_cfg3_bytes.py: a timing experiment's build lets every CPI of a batch sit at the same addresses
-  if (n_cpi > 1 && cpi_stride < h->dims.n_used) return fail(BLAH2HIP_ERR_INVALID, "cpi_stride < samples used per CPI");
-#endif
-  HIPCHK(hipSetDevice(h->device));
-  hipStream_t st = (hipStream_t)stream;
-  const uint32_t nD = h->dims.n_doppler_bins, nDelay = h->dims.n_delay_bins;
-  cf *map = d_map ? (cf *)d_map : h->d_map;
-  double *met = d_metrics ? d_metrics : h->d_metrics;
-
-  // FIR fused into the range kernel: what one 4096-point transform covers (include/blah2hip.h)
-  const bool fused = h->firW != nullptr && !h->inLeakCal;
-  if (fused) {
-    const char *why = fir_unfusable(h, fmt, h->firBins, h->firDmin);
-    if (why) return fail(BLAH2HIP_ERR_UNSUPPORTED, why);
-    if (n_cpi > 1 && cpi_stride < h->dims.n_samples) return fail(BLAH2HIP_ERR_INVALID, "fused FIR: cpi_stride < nSamples");
-    if (!h->d_H) HIPCHK(hipMalloc(&h->d_H, (size_t)h->dims.max_batch * 16 * 256 * sizeof(cf)));
-    if (!h->d_firK0) HIPCHK(hipMalloc(&h->d_firK0, (size_t)h->dims.max_batch * sizeof(int32_t)));
-  }
-  // the fixed-pattern leak of the kernel pair this launch will run (calibrated at the pair's first launch)
-  const blah2hip_amb_s::LeakCal *leak = nullptr;
+  *leak = nullptr;
   if (h->leakMode != 0 && !h->inLeakCal && !fused) { // (behind the filter the lag-0 column holds no peak to leak)
-    const int rid = predict_range(h, (int)(n_cpi * nD)), did = pick_doppler(h, n_cpi);
     auto it = h->leak.find(rid * 64 + did);
     if (it == h->leak.end()) {
       blah2hip_amb_s::LeakCal cal;
@@ -1453,14 +1454,22 @@ int blah2hip_amb_process_dev(blah2hip_amb_t h, int fmt, const void *d_x, const v
       it = h->leak.emplace(rid * 64 + did, cal).first;
     }
     h->lastLeakMax = it->second.maxAbs;
-    if (it->second.nLags > 0 && (it->second.active || h->leakMode == 2)) leak = &it->second;
+    if (it->second.nLags > 0 && (it->second.active || h->leakMode == 2)) *leak = &it->second;
   }
-  if (!h->inLeakCal) h->lastLeakLags = leak ? leak->nLags : 0;
+  if (!h->inLeakCal) h->lastLeakLags = *leak ? (*leak)->nLags : 0;
+  return BLAH2HIP_OK;
+}
 
+// The range stage of n_cpi CPIs of one (reference, surveillance) pair into `out`, a block of n_cpi CPIs of the tiled range
+// map: the rotate pass for asymmetric Doppler limits, the lag chunks, launch_range (or the fused-FIR kernel).
+static int amb_range_stage(blah2hip_amb_s *h, int fmt, const void *d_x, const void *d_y, uint32_t n_cpi, uint64_t cpi_stride,
+                           cf *out, bool fused, hipStream_t st)
+{
+  const uint32_t nD = h->dims.n_doppler_bins;
   RangeArgs ra;
   ra.plan = h->plan;
   ra.tw = h->d_tw;
-  ra.out = h->d_R;
+  ra.out = out;
   ra.cpiStride = (int64_t)cpi_stride;
   ra.nPulses = (int32_t)(n_cpi * nD);
 
@@ -1520,7 +1529,7 @@ int blah2hip_amb_process_dev(blah2hip_amb_t h, int fmt, const void *d_x, const v
     RangeFirArgs fa;
     fa.plan = h->plan;
     fa.plan.delayMin = h->chunks[0].lag0; fa.plan.nDelay = h->chunks[0].count; fa.plan.colOff = h->chunks[0].col0;
-    fa.tw = h->d_tw; fa.out = h->d_R; fa.cpiStride = (int64_t)cpi_stride; fa.nPulses = (int32_t)(n_cpi * nD);
+    fa.tw = h->d_tw; fa.out = out; fa.cpiStride = (int64_t)cpi_stride; fa.nPulses = (int32_t)(n_cpi * nD);
     fa.H = h->d_H; fa.N = h->dims.n_samples; fa.w = h->firW; fa.nBins = h->firBins; fa.k0 = h->d_firK0;
     const size_t ldsf = lds + 240 * sizeof(cf); // + the stage-3 twiddle table
     const int grid = std::min<int>(fa.nPulses, range_grid_cap(h, ldsf, 4, 8));
@@ -1563,7 +1572,14 @@ int blah2hip_amb_process_dev(blah2hip_amb_t h, int fmt, const void *d_x, const v
     }
     if ((rc = toc(h, BLAH2HIP_K_RANGE, st))) return rc;
   }
+  return BLAH2HIP_OK;
+}
 
+// Everything behind the range map, over n_cpi CPIs of h->d_R: Doppler kernel, hot columns, leak fix, Map::set_metrics.
+static int amb_tail_stage(blah2hip_amb_s *h, uint32_t n_cpi, cf *map, double *met, const blah2hip_amb_s::LeakCal *leak, hipStream_t st)
+{
+  const uint32_t nD = h->dims.n_doppler_bins, nDelay = h->dims.n_delay_bins;
+  int rc;
   DopplerArgs da;
   da.R = h->d_R;
   da.map = map;
@@ -1742,6 +1758,147 @@ int blah2hip_amb_process_dev(blah2hip_amb_t h, int fmt, const void *d_x, const v
   return BLAH2HIP_OK;
 }
 
+int blah2hip_amb_process_dev(blah2hip_amb_t h, int fmt, const void *d_x, const void *d_y,
+                             uint32_t n_cpi, uint64_t cpi_stride, void *d_map, double *d_metrics,
+                             void *stream)
+{
+  if (!h) return fail(BLAH2HIP_ERR_INVALID, "NULL handle");
+  if (n_cpi == 0 || n_cpi > h->dims.max_batch) return fail(BLAH2HIP_ERR_INVALID, "n_cpi outside [1, max_batch]");
+  if (fmt != BLAH2HIP_FMT_C32 && fmt != BLAH2HIP_FMT_I16 && fmt != BLAH2HIP_FMT_F16 && fmt != BLAH2HIP_FMT_I16X_C32Y &&
+      fmt != BLAH2HIP_FMT_I8 && fmt != BLAH2HIP_FMT_I8X_C32Y)
+    return fail(BLAH2HIP_ERR_INVALID, "unknown sample format");
+  if (!d_x || (fmt != BLAH2HIP_FMT_I16 && !d_y)) return fail(BLAH2HIP_ERR_INVALID, "NULL input pointer");
+#ifndef B2_EXPERIMENT_ALIASED_CPIS // tools/gpu_cfg3_bytes.py: a timing experiment's build lets every CPI of a batch sit at the same addresses
+  if (n_cpi > 1 && cpi_stride < h->dims.n_used) return fail(BLAH2HIP_ERR_INVALID, "cpi_stride < samples used per CPI");
+#endif
+  HIPCHK(hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  const uint32_t nD = h->dims.n_doppler_bins;
+  cf *map = d_map ? (cf *)d_map : h->d_map;
+  double *met = d_metrics ? d_metrics : h->d_metrics;
+
+  // FIR fused into the range kernel: what one 4096-point transform covers (include/blah2hip.h)
+  const bool fused = h->firW != nullptr && !h->inLeakCal;
+  if (fused) {
+    const char *why = fir_unfusable(h, fmt, h->firBins, h->firDmin);
+    if (why) return fail(BLAH2HIP_ERR_UNSUPPORTED, why);
+    if (n_cpi > 1 && cpi_stride < h->dims.n_samples) return fail(BLAH2HIP_ERR_INVALID, "fused FIR: cpi_stride < nSamples");
+    if (!h->d_H) HIPCHK(hipMalloc(&h->d_H, (size_t)h->dims.max_batch * 16 * 256 * sizeof(cf)));
+    if (!h->d_firK0) HIPCHK(hipMalloc(&h->d_firK0, (size_t)h->dims.max_batch * sizeof(int32_t)));
+  }
+  // the fixed-pattern leak of the kernel pair this launch will run
+  const blah2hip_amb_s::LeakCal *leak = nullptr;
+  int rc;
+  if ((rc = amb_leak_lookup(h, predict_range(h, (int)(n_cpi * nD)), pick_doppler(h, n_cpi), fused, st, &leak))) return rc;
+  if ((rc = amb_range_stage(h, fmt, d_x, d_y, n_cpi, cpi_stride, h->d_R, fused, st))) return rc;
+  return amb_tail_stage(h, n_cpi, map, met, leak, st);
+}
+
+// (format, channel count) cases for which the shared-reference kernel measured faster than the per-channel path
+// (tools/gpu_multi_surv_ab.py, profiles/r08_multi_surv_ab.json): what BLAH2HIP_MULTI_AUTO may pick
+static bool multi_shared_wins(int fmt, uint32_t n_surv)
+{
+  // measured: K = 2 and K = 4, FMT_C32 and FMT_I8.  FMT_I8 at K = 2 was a tie by the rule (its ratio inside the run's same-mode
+  // spread) and stays on the per-channel path, like every channel count that was not measured
+  if (fmt == BLAH2HIP_FMT_C32) return n_surv == 2 || n_surv == 4;
+  if (fmt == BLAH2HIP_FMT_I8) return n_surv == 4;
+  return false;
+}
+
+// nullptr if rangew1k_shared_kernel covers this call, else the reason
+static const char *multi_unshareable(const blah2hip_amb_s *h, int fmt)
+{
+  if (h->r3 != 4) return "shared-reference range kernel: the handle's transform length must be 1024";
+  if (h->dopplerMin + h->dopplerMax != 0) return "shared-reference range kernel: asymmetric Doppler limits run the rotate pass per channel";
+  if (fmt != BLAH2HIP_FMT_C32 && fmt != BLAH2HIP_FMT_I8) return "shared-reference range kernel: built for BLAH2HIP_FMT_C32 and BLAH2HIP_FMT_I8";
+  if (h->rangeKernel != 0 && h->rangeKernel != BLAH2HIP_RANGE_WAVE1K) return "shared-reference range kernel: BLAH2HIP_OPT_RANGE_KERNEL forces another kernel";
+  return nullptr;
+}
+
+int blah2hip_amb_process_multi_dev(blah2hip_amb_t h, int fmt, const void *d_x, const void *const *d_y, uint32_t n_surv,
+                                   uint32_t n_cpi, uint64_t cpi_stride, void *d_map, double *d_metrics, void *stream)
+{
+  if (!h) return fail(BLAH2HIP_ERR_INVALID, "NULL handle");
+  if (fmt == BLAH2HIP_FMT_I16)
+    return fail(BLAH2HIP_ERR_UNSUPPORTED, "BLAH2HIP_FMT_I16: the .rspduo words hold one surveillance channel only");
+  if (fmt != BLAH2HIP_FMT_C32 && fmt != BLAH2HIP_FMT_F16 && fmt != BLAH2HIP_FMT_I16X_C32Y && fmt != BLAH2HIP_FMT_I8 &&
+      fmt != BLAH2HIP_FMT_I8X_C32Y)
+    return fail(BLAH2HIP_ERR_INVALID, "unknown sample format");
+  if (n_surv == 0) return fail(BLAH2HIP_ERR_INVALID, "n_surv is 0: no surveillance channel");
+  if (n_surv > BLAH2HIP_MAX_SURV) return fail(BLAH2HIP_ERR_INVALID, "n_surv above BLAH2HIP_MAX_SURV (8)");
+  if (n_cpi == 0) return fail(BLAH2HIP_ERR_INVALID, "n_cpi is 0");
+  if ((uint64_t)n_surv * n_cpi > h->dims.max_batch) return fail(BLAH2HIP_ERR_INVALID, "n_surv * n_cpi above max_batch");
+  if (!d_x || !d_y) return fail(BLAH2HIP_ERR_INVALID, "NULL input pointer");
+  for (uint32_t k = 0; k < n_surv; k++)
+    if (!d_y[k]) return fail(BLAH2HIP_ERR_INVALID, "NULL surveillance plane " + std::to_string(k));
+  if (n_cpi > 1 && cpi_stride < h->dims.n_used) return fail(BLAH2HIP_ERR_INVALID, "cpi_stride < samples used per CPI");
+  if (h->firW != nullptr)
+    return fail(BLAH2HIP_ERR_UNSUPPORTED, "fused FIR set (blah2hip_amb_set_fir): several surveillance channels run the two-stage filter per channel");
+  HIPCHK(hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  const uint32_t nD = h->dims.n_doppler_bins, nTot = n_surv * n_cpi;
+  cf *map = d_map ? (cf *)d_map : h->d_map;
+  double *met = d_metrics ? d_metrics : h->d_metrics;
+
+  // which range path: pairs of channels on the shared-reference kernel, or every channel on the two-channel stage
+  bool shared = false;
+  if (n_surv >= 2 && h->multiMode != BLAH2HIP_MULTI_PER_CHANNEL) {
+    const char *why = multi_unshareable(h, fmt);
+    if (h->multiMode == BLAH2HIP_MULTI_SHARED) {
+      if (why) return fail(BLAH2HIP_ERR_UNSUPPORTED, why);
+      shared = true;
+    } else {
+      shared = !why && use_wave1k_range(h, (int)(n_cpi * nD)) && multi_shared_wins(fmt, n_surv);
+    }
+  }
+  // per channel the shared kernel's arithmetic is rangew1k_kernel's: its leak calibration is that kernel's
+  const int rid = shared ? BLAH2HIP_RANGE_WAVE1K : predict_range(h, (int)(n_cpi * nD));
+  const blah2hip_amb_s::LeakCal *leak = nullptr;
+  int rc;
+  if ((rc = amb_leak_lookup(h, rid, pick_doppler(h, nTot), false, st, &leak))) return rc;
+
+  // a channel's n_cpi CPIs are one contiguous block of the tiled range map [cpi][lag / 16][pulse][16]
+  const size_t block = (size_t)n_cpi * h->nTiles * nD * 16;
+  if (!shared) {
+    for (uint32_t k = 0; k < n_surv; k++)
+      if ((rc = amb_range_stage(h, fmt, d_x, d_y[k], n_cpi, cpi_stride, h->d_R + k * block, false, st))) return rc;
+  } else {
+    RangeArgs ra;
+    ra.plan = h->plan;
+    ra.tw = h->d_tw;
+    ra.cpiStride = (int64_t)cpi_stride;
+    ra.nPulses = (int32_t)(n_cpi * nD);
+    if ((rc = tic(h, BLAH2HIP_K_RANGE, st))) return rc;
+    for (const auto &ck : h->chunks) {
+      ra.plan.delayMin = ck.lag0; ra.plan.nDelay = ck.count; ra.plan.colOff = ck.col0;
+      for (uint32_t k = 0; k < n_surv; k += 2) {
+        ra.out = h->d_R + k * block;
+        if (fmt == BLAH2HIP_FMT_C32) {
+          InC32 in0{(const cf *)d_x, (const cf *)d_y[k]};
+          if (k + 1 < n_surv) {
+            InC32 in1{(const cf *)d_x, (const cf *)d_y[k + 1]};
+            rc = launch_rangew1k_shared_t(h, ra, (int)n_cpi, in0, in1, st);
+          } else {
+            rc = launch_rangew1k_t(h, ra, in0, st); // the odd last channel
+          }
+        } else {
+          InI8 in0{(const int8_t *)d_x, (const int8_t *)d_y[k]};
+          if (k + 1 < n_surv) {
+            InI8 in1{(const int8_t *)d_x, (const int8_t *)d_y[k + 1]};
+            rc = launch_rangew1k_shared_t(h, ra, (int)n_cpi, in0, in1, st);
+          } else {
+            rc = launch_rangew1k_t(h, ra, in0, st);
+          }
+        }
+        if (rc) return rc;
+      }
+    }
+    h->lastRange = BLAH2HIP_RANGE_SHARED;
+    if ((rc = toc(h, BLAH2HIP_K_RANGE, st))) return rc;
+  }
+  return amb_tail_stage(h, nTot, map, met, leak, st);
+}
+
 int blah2hip_amb_read_last(blah2hip_amb_t h, uint32_t cpi, float *map_out, double *metrics)
 {
   if (!h) return fail(BLAH2HIP_ERR_INVALID, "NULL handle");
@@ -1783,6 +1940,34 @@ int blah2hip_amb_process_c32(blah2hip_amb_t h, const float *x, const float *y, u
   HIPCHK(hipMemcpyAsync(dy, y, bytes, hipMemcpyHostToDevice, h->stream));
   if ((rc = blah2hip_amb_process_dev(h, BLAH2HIP_FMT_C32, dx, dy, 1, n, nullptr, nullptr, h->stream))) return rc;
   return host_tail(h, map_out, metrics);
+}
+
+int blah2hip_amb_process_multi_c32(blah2hip_amb_t h, const float *x, const float *const *y, uint32_t n_surv, uint32_t n,
+                                   float *map_out, double *metrics)
+{
+  if (!h || !x || !y) return fail(BLAH2HIP_ERR_INVALID, "NULL argument");
+  if (n_surv == 0 || n_surv > BLAH2HIP_MAX_SURV) return fail(BLAH2HIP_ERR_INVALID, "n_surv outside [1, BLAH2HIP_MAX_SURV]");
+  for (uint32_t k = 0; k < n_surv; k++)
+    if (!y[k]) return fail(BLAH2HIP_ERR_INVALID, "NULL surveillance plane " + std::to_string(k));
+  if (n < h->dims.n_used) return fail(BLAH2HIP_ERR_UNDERFLOW, "Attempting to pop from an empty deque");
+  HIPCHK(hipSetDevice(h->device));
+  const size_t bytes = (size_t)n * sizeof(cf);
+  int rc;
+  if ((rc = ensure_staging(h, (1 + (size_t)n_surv) * bytes))) return rc;
+  char *dx = (char *)h->d_in;
+  const void *dy[BLAH2HIP_MAX_SURV];
+  HIPCHK(hipMemcpyAsync(dx, x, bytes, hipMemcpyHostToDevice, h->stream));
+  for (uint32_t k = 0; k < n_surv; k++) {
+    dy[k] = dx + (1 + (size_t)k) * bytes;
+    HIPCHK(hipMemcpyAsync((void *)dy[k], y[k], bytes, hipMemcpyHostToDevice, h->stream));
+  }
+  if ((rc = blah2hip_amb_process_multi_dev(h, BLAH2HIP_FMT_C32, dx, dy, n_surv, 1, n, nullptr, nullptr, h->stream))) return rc;
+  // channel-major: [n_surv][n_doppler][n_delay] cells, [n_surv][2] metrics
+  const size_t cells = (size_t)h->dims.n_doppler_bins * h->dims.n_delay_bins;
+  if (map_out) HIPCHK(hipMemcpyAsync(map_out, h->d_map, n_surv * cells * sizeof(cf), hipMemcpyDeviceToHost, h->stream));
+  if (metrics) HIPCHK(hipMemcpyAsync(metrics, h->d_metrics, n_surv * 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return BLAH2HIP_OK;
 }
 
 int blah2hip_amb_process_c64(blah2hip_amb_t h, const double *x, const double *y, uint32_t n,

@@ -850,6 +850,130 @@ __global__ __launch_bounds__(64 * RANGEW1K_WAVES, RANGEW1K_WAVES_PER_SIMD) void 
   }
 }
 
+// --------------------------------------------------------------------------
+// Shared-reference range kernel (blah2hip_amb_process_multi_dev): rangew1k_kernel for TWO surveillance channels against one
+// reference channel.  Per segment the x' window is read and transformed ONCE, its spectrum stays in 32 registers, and each
+// channel's y' window goes through the steps of rangew1k_kernel in the same order (window -> s1_nd -> finish -> acc_k +=
+// Y conj(X)); per pulse each channel has its own inverse and store, channel k of CPI c into virtual CPI k * nCpi + c of
+// a.out.  Three forward transforms a segment instead of four.
+//
+// Registers.  X spectrum 32 + two accumulators 64 + the Y transform in flight 32 + the next x' (18; 9 for int8) + BOTH
+// channels' next y' windows, requested a segment ahead like rangew1k_kernel's one (2 x 32 for fp32 planes, 2 x 16 for int8):
+// above the 168 of three waves per SIMD for either format, so the kernel is built for TWO waves per SIMD (<= 256) and the
+// loads a segment ahead carry what the third wave did.  A tile of four channels (accumulators alone 128) does not fit
+// without giving the prefetch up; K > 2 runs as passes over pairs, an odd last channel on rangew1k_kernel itself.
+#ifndef RANGEWS_WAVES
+#define RANGEWS_WAVES 8
+#endif
+struct RangeSharedArgs {
+  RangeArgs r;   // r.out: block of the pair's first channel; r.nPulses = nCpi * nDoppler
+  int32_t nCpi;  // CPIs per channel: the second channel's block starts nCpi CPIs further
+};
+
+// one channel's share of a segment: yv = FFT(y'), acc += yv conj(X), then the next window's request into ry
+template <class In, bool REUSE>
+__device__ __forceinline__ void ws_channel(const In &in, const RangePlan &p, int64_t nbase, int ns, int t, bool more,
+                                           typename RawBuiltin<typename BufLoad<In>::Y>::raw *ry, const cf *v, cf *acc,
+                                           const Wave1kFft::Tw &w, cf *X)
+{
+  using W = Wave1kFft;
+  using RY = RawBuiltin<typename BufLoad<In>::Y>;
+  cf yin[16], yv[16];
+#pragma unroll
+  for (int k = 0; k < 16; k++) yin[k] = RY::cvt(ry[k]);
+  W::s1_nd<-1>(yv, yin, w);
+  W::finish<-1>(t, yv, w, X); // yv = Y spectrum
+#pragma unroll
+  for (int e = 0; e < 16; e++) acc[e] = cmacc(acc[e], yv[e], v[e]);
+  __builtin_amdgcn_sched_barrier(0);
+  if constexpr (REUSE) {
+    if (ns != 0) {
+#pragma unroll
+      for (int k = 0; k < 7; k++) ry[k] = ry[9 + k];
+      w1k_issue_y<In, 7>(in, p, nbase, ns, t, more, ry);
+    } else {
+      w1k_issue_y<In>(in, p, nbase, ns, t, more, ry);
+    }
+  } else {
+    w1k_issue_y<In>(in, p, nbase, ns, t, more, ry);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+}
+
+// in0.x == in1.x: the reference channel; in0.y, in1.y: the two surveillance planes.  SHORTX / OUT7 / REUSE as above.
+template <class In, bool SHORTX, bool OUT7, bool REUSE = false>
+__global__ __launch_bounds__(64 * RANGEWS_WAVES, 2) void rangew1k_shared_kernel(RangeSharedArgs sa, In in0, In in1)
+{
+  static_assert(!REUSE || SHORTX, "");
+  using W = Wave1kFft;
+  using RX = RawBuiltin<typename BufLoad<In>::X>;
+  using RY = RawBuiltin<typename BufLoad<In>::Y>;
+  constexpr int NX = SHORTX ? 9 : 16;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  cf *table = reinterpret_cast<cf *>(smem);
+  const int t = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  cf *X = table + W::TW_ELEMS + wave * W::X_ELEMS;
+  const RangeArgs &a = sa.r;
+  W::fill_table(threadIdx.x, 64 * RANGEWS_WAVES, a.tw, table);
+  __syncthreads(); // the only barrier: waves without a pulse leave after it
+  W::Tw w;
+  W::load_twiddles(t, a.tw, table, w);
+  const RangePlan p = a.plan;
+  const int stride = gridDim.x * RANGEWS_WAVES;
+  int pulse = blockIdx.x * RANGEWS_WAVES + wave;
+  if (pulse >= a.nPulses) return;
+  int cpi = pulse / p.nDoppler;
+  int i = pulse - cpi * p.nDoppler;
+  int64_t base = (int64_t)cpi * a.cpiStride + (int64_t)i * p.nCorr;
+  int s = 0;
+  typename RX::raw rx[NX];
+  typename RY::raw ry0[16], ry1[16];
+  cf acc0[16], acc1[16];
+#pragma unroll
+  for (int e = 0; e < 16; e++) acc0[e] = acc1[e] = cmake(0.f, 0.f);
+  w1k_issue_x<In, NX>(in0, p, base, 0, t, true, rx);
+  w1k_issue_y<In>(in0, p, base, 0, t, true, ry0);
+  w1k_issue_y<In>(in1, p, base, 0, t, true, ry1);
+  for (;;) {
+    // the segment after this one (wave-uniform)
+    int ns = s + 1, npulse = pulse, ncpi = cpi, ni = i;
+    int64_t nbase = base;
+    if (ns == p.nSeg) {
+      ns = 0;
+      npulse = pulse + stride;
+      ncpi = npulse / p.nDoppler;
+      ni = npulse - ncpi * p.nDoppler;
+      nbase = (int64_t)ncpi * a.cpiStride + (int64_t)ni * p.nCorr;
+    }
+    const bool more = npulse < a.nPulses;
+    cf v[16];
+#pragma unroll
+    for (int k = 0; k < NX; k++) v[k] = RX::cvt(rx[k]);
+    W::s1<-1, NX>(v, w);
+    __builtin_amdgcn_sched_barrier(0);
+    w1k_issue_x<In, NX>(in0, p, nbase, ns, t, more, rx);
+    __builtin_amdgcn_sched_barrier(0);
+    W::finish<-1>(t, v, w, X); // v = X spectrum, kept for both channels
+    ws_channel<In, REUSE>(in0, p, nbase, ns, t, more, ry0, v, acc0, w, X);
+    ws_channel<In, REUSE>(in1, p, nbase, ns, t, more, ry1, v, acc1, w, X);
+    if (ns == 0) { // the pulse is complete
+      W::template transform<+1, 16, OUT7>(t, acc0, w, X);
+      store_lags_w<OUT7 ? 7 : 16>(a.out, p, cpi, i, t, acc0);
+      W::template transform<+1, 16, OUT7>(t, acc1, w, X);
+      store_lags_w<OUT7 ? 7 : 16>(a.out, p, sa.nCpi + cpi, i, t, acc1);
+      if (!more) break;
+#pragma unroll
+      for (int e = 0; e < 16; e++) acc0[e] = acc1[e] = cmake(0.f, 0.f);
+      pulse = npulse;
+      cpi = ncpi;
+      i = ni;
+    }
+    s = ns;
+    base = nbase;
+  }
+}
+
 #ifdef B2_RANGEW1K_GLDS
 // EXPERIMENT (round 6; built only with -DB2_RANGEW1K_GLDS, tools/build_variant.sh): rangew1k_kernel
 // with a segment's x' and y' windows landing in the wave's exchange region by LDS-DMA (`buffer_load_dwordx4 ... lds`)

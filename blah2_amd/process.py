@@ -214,6 +214,39 @@ class Ambiguity:
                                                d_metrics, stream))
         self._gen += 1
 
+    def process_multi_dev(self, fmt, d_x, d_ys, n_cpi, cpi_stride, d_map=None, d_metrics=None, stream=0):
+        """One reference plane against ``len(d_ys)`` surveillance planes (blah2hip_amb_process_multi_dev; raw pointers/ints).
+        ``fmt``: FMT_C32, FMT_F16, FMT_I8, FMT_I16X_C32Y or FMT_I8X_C32Y.  Output channel-major: channel k of CPI c is
+        virtual CPI ``k * n_cpi + c`` of the map / metrics buffers, of ``read_last`` and of the detectors' ``process_dev``
+        (called with ``n_cpi * len(d_ys)``)."""
+        planes = (C.c_void_p * max(1, len(d_ys)))(*[int(p) if p else None for p in d_ys])
+        check(self._L.blah2hip_amb_process_multi_dev(self._h, fmt, d_x, planes, len(d_ys), n_cpi, cpi_stride, d_map,
+                                                     d_metrics, stream))
+        self._gen += 1
+
+    def process_multi(self, x, ys):
+        """Host arrays, one CPI: complex64 reference ``x`` against the complex64 surveillance channels ``ys``
+        (blah2hip_amb_process_multi_c32); one :class:`Map` per channel."""
+        x = np.ascontiguousarray(x, dtype=np.complex64)
+        ys = [np.ascontiguousarray(y, dtype=np.complex64) for y in ys]
+        nD, nC = self.dims.n_doppler_bins, self.dims.n_delay_bins
+        out = np.empty((len(ys), nD, nC), dtype=np.complex64)
+        met = np.zeros((len(ys), 2), dtype=np.float64)
+        planes = (C.c_void_p * max(1, len(ys)))(*[y.ctypes.data for y in ys])
+        n = min([x.shape[0]] + [y.shape[0] for y in ys])
+        rc = self._L.blah2hip_amb_process_multi_c32(self._h, _ptr(x), planes, len(ys), n, _ptr(out), _ptr(met))
+        if rc == _lib.ERR_UNDERFLOW:
+            raise RuntimeError("Attempting to pop from an empty deque")
+        check(rc)
+        self._n_samples = self.dims.n_used
+        self._gen += 1
+        return [self._result(out[k], met[k], k) for k in range(len(ys))]
+
+    def set_multi_surv_range(self, mode):
+        """BLAH2HIP_OPT_MULTI_SURV_RANGE: "auto", "shared" (the shared-reference range kernel) or "per_channel"."""
+        mode = {"auto": _lib.MULTI_AUTO, "shared": _lib.MULTI_SHARED, "per_channel": _lib.MULTI_PER_CHANNEL}.get(mode, mode)
+        check(self._L.blah2hip_amb_set_option(self._h, _lib.OPT_MULTI_SURV_RANGE, int(mode)))
+
     def read_last(self, cpi=0):
         nD, nC = self.dims.n_doppler_bins, self.dims.n_delay_bins
         out = np.empty((nD, nC), dtype=np.complex64)

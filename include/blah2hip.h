@@ -183,6 +183,15 @@ int blah2hip_amb_get_axes(blah2hip_amb_t h, int32_t *delay, double *doppler);
                                        * map.  For tests: the seams between segments fall on other rows than a small fixture would give them */
 #define BLAH2HIP_OPT_CFAR2D_GRID 10   /* workgroup cap of the PERSISTENT 2-D tile kernel, rounded up to a multiple of 8; 0 = one per CU (or
                                        * per tile).  A small cap makes every workgroup walk many tiles on a small fixture (tests) */
+#define BLAH2HIP_OPT_MULTI_SURV_RANGE 11 /* range path of blah2hip_amb_process_multi_dev: BLAH2HIP_MULTI_AUTO (the shared-reference kernel
+                                       * where BLAH2HIP_RANGE_WAVE1K would have run and only for the (format, channel count) cases it
+                                       * measured faster in), _SHARED (BLAH2HIP_ERR_UNSUPPORTED at the call where
+                                       * the kernel does not cover it: F != 1024, asymmetric Doppler limits, a format other than
+                                       * FMT_C32 / FMT_I8, another range kernel forced; a lone channel has nothing to share and runs
+                                       * the per-channel path) or _PER_CHANNEL (the two-channel range stage once per channel) */
+#define BLAH2HIP_MULTI_AUTO 0
+#define BLAH2HIP_MULTI_SHARED 1
+#define BLAH2HIP_MULTI_PER_CHANNEL 2
 #define BLAH2HIP_CFAR2D_AUTO 0
 #define BLAH2HIP_CFAR2D_TILE 1
 #define BLAH2HIP_CFAR2D_SAT 2
@@ -207,6 +216,8 @@ int blah2hip_amb_get_axes(blah2hip_amb_t h, int32_t *delay, double *doppler);
 #define BLAH2HIP_RANGE_WAVE1K 5 /* one wave per pulse, 16 points per lane, four waves per SIMD (F = 1024) */
 #define BLAH2HIP_RANGE_FIR 7      /* INFO_LAST_RANGE_KERNEL only: range_fir_kernel (blah2hip_amb_set_fir) */
 #define BLAH2HIP_RANGE_PS 6     /* small launches (a lone CPI) at F = 1024: one workgroup of four waves per pulse, its segments dealt round-robin to the waves */
+#define BLAH2HIP_RANGE_SHARED 8  /* INFO_LAST_RANGE_KERNEL only: rangew1k_shared_kernel, _WAVE1K for pairs of surveillance channels against
+                                  * one reference channel whose transform they share (blah2hip_amb_process_multi_dev, F = 1024) */
 /* BLAH2HIP_ERR_UNSUPPORTED when the kernel does not cover the handle's Doppler length */
 int blah2hip_amb_set_option(blah2hip_amb_t h, int option, int64_t value);
 #define BLAH2HIP_INFO_LAST_DOPPLER_KERNEL 1 /* BLAH2HIP_DOP_* the last process call launched (0 = none yet) */
@@ -255,6 +266,25 @@ int blah2hip_amb_process_i8(blah2hip_amb_t h, const int8_t *x, const int8_t *y, 
 int blah2hip_amb_process_dev(blah2hip_amb_t h, int fmt, const void *d_x, const void *d_y,
                              uint32_t n_cpi, uint64_t cpi_stride, void *d_map, double *d_metrics,
                              void *stream);
+/* One reference channel against n_surv surveillance channels on the same clock (a KrakenSDR: one reference antenna, up to four
+ * surveillance antennas).  d_y: HOST array of n_surv device planes, read at the call; every plane has the layout and cpi_stride
+ * d_y has above for the same fmt.  fmt: the formats whose surveillance channel is a plane of its own -- FMT_C32, FMT_F16, FMT_I8,
+ * FMT_I16X_C32Y, FMT_I8X_C32Y (the two mixed ones are what a clutter filter per channel leaves behind); FMT_I16 is
+ * BLAH2HIP_ERR_UNSUPPORTED.  Output, channel-major: d_map [n_surv][n_cpi][n_doppler][n_delay], d_metrics [n_surv][n_cpi][2]
+ * (NULL: the handle's buffers, same order).  Channel k of CPI c is thus VIRTUAL CPI k * n_cpi + c for blah2hip_amb_read_last,
+ * blah2hip_cfar1d_dev, blah2hip_cfar2d_dev, blah2hip_detect_dev, blah2hip_amb_db_dev and BLAH2HIP_INFO_HOT_COLUMNS*, which are called
+ * with n_cpi * n_surv CPIs.  The reference channel is read and transformed once per pair of channels where the shared-reference
+ * range kernel runs (BLAH2HIP_OPT_MULTI_SURV_RANGE); everything behind the range map is one launch sequence over the virtual CPIs.
+ * n_surv = 1 is blah2hip_amb_process_dev bit for bit.  BLAH2HIP_ERR_INVALID: n_surv == 0 or > BLAH2HIP_MAX_SURV, a NULL plane,
+ * n_surv * n_cpi > max_batch; BLAH2HIP_ERR_UNSUPPORTED: a fused FIR set on the handle (blah2hip_amb_set_fir) -- several channels
+ * run the two-stage filter per channel. */
+#define BLAH2HIP_MAX_SURV 8
+int blah2hip_amb_process_multi_dev(blah2hip_amb_t h, int fmt, const void *d_x, const void *const *d_y, uint32_t n_surv,
+                                   uint32_t n_cpi, uint64_t cpi_stride, void *d_map, double *d_metrics, void *stream);
+/* host planes of n complex fp32 samples each, uploaded, one CPI; map_out [n_surv][n_doppler][n_delay] (may be NULL),
+ * metrics [n_surv][2] */
+int blah2hip_amb_process_multi_c32(blah2hip_amb_t h, const float *x, const float *const *y, uint32_t n_surv, uint32_t n,
+                                   float *map_out, double *metrics);
 /* copies CPI `cpi` of the handle's internal map/metrics to the host (synchronises) */
 int blah2hip_amb_read_last(blah2hip_amb_t h, uint32_t cpi, float *map_out, double *metrics);
 /* The values Map::to_json prints (Map.cpp:148-155): d_db[cpi][doppler][delay] =
