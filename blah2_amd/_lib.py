@@ -114,6 +114,7 @@ SYMBOLS = {
     "blah2hip_clutter_process_c32": (C.c_int, [_vp, _vp, _vp, _u32, _vp, C.POINTER(C.c_int)]),
     "blah2hip_clutter_process_dev": (C.c_int, [_vp, _vp, _vp, _u32, C.c_uint64, _vp, _vp, _vp]),
     "blah2hip_clutter_process_dev_fmt": (C.c_int, [_vp, C.c_int, _vp, _vp, _u32, C.c_uint64, _vp, C.c_uint64, _vp, _vp]),
+    "blah2hip_clutter_process_multi_dev_fmt": (C.c_int, [_vp, C.c_int, _vp, C.POINTER(_vp), _u32, _u32, C.c_uint64, C.POINTER(_vp), C.c_uint64, _vp, _vp]),
     "blah2hip_clutter_set_option": (C.c_int, [_vp, C.c_int, C.c_int64]),
     "blah2hip_clutter_solve": (C.c_int, [_vp, _vp, _u32, _vp, _vp]),
     "blah2hip_clutter_solve_dev": (C.c_int, [_vp, _vp, _u32, _vp, _vp, _vp]),

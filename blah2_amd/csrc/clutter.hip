@@ -420,6 +420,277 @@ template <int R3, class In> __global__ __launch_bounds__(16 * R3, 2) void clutte
   finish(accB, 1);
 }
 
+// ---- several surveillance channels against ONE reference (blah2hip_clutter_process_multi_dev_fmt) --------------------
+// r = xs against xs belongs to the reference alone, and so does the spectrum every b_k is formed against.  The two kernels
+// below are clutter_corr_kernel and clutter_corr_half_kernel with the channel as a compile-time tile:
+//   WITH_R, NB = 1: the parent's work on (x, y_0) -- r and b_0 -- written into the wider partial layout;
+//   !WITH_R, NB = 1 | 2: the channels behind the first, one or two per pass: the reference's spectrum once more (one
+//     transform per segment), then one window transform and accB_c += Y_c conj(.) per channel.  No xs window transform and
+//     no r accumulation: their registers hold the second channel, so no instantiation needs more than its parent.
+// Per channel the segment walk, the job count and the order of the accumulation are the parent's: r and every b_k are
+// the bits of the per-channel call.  Transforms per segment for K channels: windowed 3 + (K - 1) + ceil((K - 1) / 2)
+// against 3K, half-window 2 + (K - 1) + ceil((K - 1) / 2) against 2K.
+constexpr int CORR_TILE = 2;
+struct CorrMultiArgs {
+  const void *x;            // the reference plane
+  const void *y[CORR_TILE]; // this pass's surveillance planes
+  int64_t cpiStride;
+  uint32_t N;
+  XsMap xs;
+  int32_t nBins, segLen, nSeg, per, nJobs; // windowed: segLen, nSeg as CorrArgs; half-window: nSeg, per as CorrHalfArgs
+  const cf *tw;
+  cf *partial;        // [nCpi][rows][nJobs][nBins]: row 0 = r, row 1 + k = b_k
+  float scale;
+  int32_t rows, row0; // row0: the row of y[0]'s b
+};
+
+template <int R3, class In, bool WITH_R, int NB>
+__global__ __launch_bounds__(16 * R3, R3 == 16 ? 1 : 2) void clutter_corr_multi_kernel(CorrMultiArgs a)
+{
+  static_assert(NB >= 1 && NB <= CORR_TILE && (!WITH_R || NB == 1), "r rides with the first channel alone");
+  using W = WgFft<R3>;
+  constexpr int T = W::T;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  cf *P = reinterpret_cast<cf *>(smem);
+  cf *Q = P + W::A_ELEMS;
+  const int t = threadIdx.x;
+  const int cpi = blockIdx.y;
+  const typename ChanOf<In>::type X = ChanOf<In>::x(a.x, nullptr, (int64_t)cpi * a.cpiStride);
+  cf tw1[15], tw3[16];
+  W::load_twiddles(t, a.tw, tw1, tw3);
+
+  cf accR[16], accB[NB][16];
+#pragma unroll
+  for (int e = 0; e < 16; e++) {
+    accR[e] = cmake(0.f, 0.f);
+#pragma unroll
+    for (int c = 0; c < NB; c++) accB[c][e] = cmake(0.f, 0.f);
+  }
+  const SegWalk sw = seg_walk(a.nSeg);
+  for (int r = sw.first; r < sw.count; r += sw.step) {
+    const int g = sw.base + r;
+    const uint32_t n0 = (uint32_t)g * (uint32_t)a.segLen;
+    cf v[16], wv[16], yw[NB][16];
+    uint32_t j0;
+    int xcnt;
+    const bool whole = (uint64_t)n0 + 16 * T <= a.N;
+    const bool plain = whole && xs_window_plain((int)n0, 16 * T, a.xs, &j0, &xcnt);
+    auto load_y = [&](int c) { // c is a constant after unrolling
+      if (plain) {
+        using CY = typename BufChanOf<In>::Y;
+        const __amdgpu_buffer_rsrc_t yd = make_rsrc_b(BufChanOf<In>::y(a.x, a.y[c], (int64_t)cpi * a.cpiStride + n0), 16 * T * CY::STRIDE);
+#pragma unroll
+        for (int k = 0; k < 16; k++) yw[c][k] = RawBuiltin<CY>::cvt(RawBuiltin<CY>::ld(yd, (t + T * k) * CY::STRIDE, 0));
+      } else {
+        const typename ChanOf<In>::type Y = ChanOf<In>::y(a.x, a.y[c], (int64_t)cpi * a.cpiStride);
+#pragma unroll
+        for (int k = 0; k < 16; k++) yw[c][k] = Y[wrapN(n0 + (uint32_t)(t + T * k), a.N)];
+      }
+    };
+    if (plain) {
+      using CX = typename BufChanOf<In>::X;
+      const __amdgpu_buffer_rsrc_t xd = make_rsrc_b(BufChanOf<In>::x(a.x, nullptr, (int64_t)cpi * a.cpiStride + j0), 16 * T * CX::STRIDE);
+#pragma unroll
+      for (int k = 0; k < 16; k++) wv[k] = RawBuiltin<CX>::cvt(RawBuiltin<CX>::ld(xd, (t + T * k) * CX::STRIDE, 0));
+    } else {
+#pragma unroll
+      for (int k = 0; k < 16; k++) wv[k] = X[xs_index(wrapN(n0 + (uint32_t)(t + T * k), a.N), a.xs)];
+    }
+    // the y windows with the xs window, as the parent requests them (at F = 4096 with r: inside the second transform)
+    if (!WITH_R || R3 < 16) load_y(0);
+#pragma unroll
+    for (int k = 0; k < 16; k++) {
+      const int m = t + T * k;
+      v[k] = (m < a.segLen && n0 + (uint32_t)m < a.N) ? wv[k] : cmake(0.f, 0.f);
+    }
+    W::fwd_s1(t, v, tw1, P);
+    __syncthreads();
+    W::fwd_s2(t, v, P, Q);
+    __syncthreads();
+    W::fwd_s3(t, v, tw3, Q); // v = X' spectrum
+    if (WITH_R) {
+      W::fwd_s1(t, wv, tw1, P);
+      __syncthreads();
+      W::fwd_s2(t, wv, P, Q);
+      if (R3 == 16) load_y(0);
+      __syncthreads();
+      W::fwd_s3(t, wv, tw3, Q);
+#pragma unroll
+      for (int e = 0; e < 16; e++) accR[e] = cmacc(accR[e], wv[e], v[e]);
+    }
+#pragma unroll
+    for (int c = 0; c < NB; c++) {
+      W::fwd_s1(t, yw[c], tw1, P);
+      __syncthreads();
+      W::fwd_s2(t, yw[c], P, Q);
+      if (c + 1 < NB) load_y(c + 1); // the next channel's window behind this transform's last exchange write: five register sets, as the parent
+      __syncthreads();
+      W::fwd_s3(t, yw[c], tw3, Q);
+#pragma unroll
+      for (int e = 0; e < 16; e++) accB[c][e] = cmacc(accB[c][e], yw[c][e], v[e]);
+    }
+    __syncthreads();
+  }
+  auto finish = [&](cf *acc, int row) {
+    W::inv_s1(t, acc, tw3, P);
+    __syncthreads();
+    W::inv_s2(t, acc, P, Q);
+    __syncthreads();
+    W::inv_s3(t, acc, tw1, Q);
+    cf *dst = a.partial + (((size_t)cpi * a.rows + row) * a.nJobs + blockIdx.x) * a.nBins;
+#pragma unroll
+    for (int c = 0; c < 16; c++) {
+      const int k = t + T * c;
+      if (k < a.nBins) dst[k] = cmake(acc[c].x * a.scale, acc[c].y * a.scale);
+    }
+    __syncthreads();
+  };
+  if (WITH_R) finish(accR, 0);
+  finish(accB[0], a.row0);
+  if (NB > 1) finish(accB[NB - 1], a.row0 + 1);
+}
+
+// The half-window form.  z = X_g + (-1)^m X_{g-1} takes the previous segment's registers as soon as it is formed, and the
+// channels' transforms follow one after the other against it: five register sets at NB = 2, the parent's count.
+// (F = 4096 with two channels: built for ONE workgroup per SIMD set, like clutter_corr_kernel<16> -- at the 256-register cap
+// of two the allocator put 1 value of the segment loop and 62 of the wrap-around product into scratch.)
+template <int R3, class In, bool WITH_R, int NB>
+__global__ __launch_bounds__(16 * R3, (R3 == 16 && NB == 2) ? 1 : 2) void clutter_corr_half_multi_kernel(CorrMultiArgs a)
+{
+  static_assert(NB >= 1 && NB <= CORR_TILE && (!WITH_R || NB == 1), "r rides with the first channel alone");
+  using W = WgFft<R3>;
+  constexpr int T = W::T, L = W::F / 2;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  cf *P = reinterpret_cast<cf *>(smem);
+  cf *Q = P + W::A_ELEMS;
+  const int t = threadIdx.x;
+  const int cpi = blockIdx.y;
+  const typename ChanOf<In>::type X = ChanOf<In>::x(a.x, nullptr, (int64_t)cpi * a.cpiStride);
+  cf tw1[15], tw3[16];
+  W::load_twiddles(t, a.tw, tw1, tw3);
+  const float sgn = ((t >> 4) & 1) ? -1.f : 1.f;
+
+  auto fwd = [&](cf *v) {
+    W::fwd_s1(t, v, tw1, P);
+    __syncthreads();
+    W::fwd_s2(t, v, P, Q);
+    __syncthreads();
+    W::fwd_s3(t, v, tw3, Q);
+    __syncthreads();
+  };
+  using CX = typename BufChanOf<In>::X;
+  using CY = typename BufChanOf<In>::Y;
+  auto load_xs = [&](uint32_t n0, uint32_t len, cf *v) {
+    uint32_t j0;
+    int cnt;
+    if (xs_window_plain((int)n0, (int)len, a.xs, &j0, &cnt) && cnt == (int)len) {
+      const __amdgpu_buffer_rsrc_t d = make_rsrc_b(BufChanOf<In>::x(a.x, nullptr, (int64_t)cpi * a.cpiStride + j0), (int)len * CX::STRIDE);
+#pragma unroll
+      for (int k = 0; k < 8; k++) v[k] = RawBuiltin<CX>::cvt(RawBuiltin<CX>::ld(d, (t + T * k) * CX::STRIDE, 0));
+    } else {
+#pragma unroll
+      for (int k = 0; k < 8; k++) {
+        const uint32_t m = (uint32_t)(t + T * k);
+        const bool inr = m < len;
+        const cf s = X[xs_index(inr ? n0 + m : 0u, a.xs)];
+        v[k] = inr ? s : cmake(0.f, 0.f);
+      }
+    }
+#pragma unroll
+    for (int k = 8; k < 16; k++) v[k] = cmake(0.f, 0.f);
+  };
+  auto load_y = [&](int c, uint32_t n0, uint32_t len, cf *v) {
+    const __amdgpu_buffer_rsrc_t d = make_rsrc_b(BufChanOf<In>::y(a.x, a.y[c], (int64_t)cpi * a.cpiStride + n0), (int)len * CY::STRIDE);
+#pragma unroll
+    for (int k = 0; k < 8; k++) v[k] = RawBuiltin<CY>::cvt(RawBuiltin<CY>::ld(d, (t + T * k) * CY::STRIDE, 0));
+#pragma unroll
+    for (int k = 8; k < 16; k++) v[k] = cmake(0.f, 0.f);
+  };
+  auto seg_len = [&](int g) { return min((uint32_t)L, a.N - (uint32_t)g * (uint32_t)L); };
+
+  cf accR[16], accB[NB][16], prevX[16];
+#pragma unroll
+  for (int e = 0; e < 16; e++) {
+    accR[e] = cmake(0.f, 0.f);
+    prevX[e] = cmake(0.f, 0.f);
+#pragma unroll
+    for (int c = 0; c < NB; c++) accB[c][e] = cmake(0.f, 0.f);
+  }
+  const int g0 = blockIdx.x * a.per, g1 = min(g0 + a.per, a.nSeg);
+  if (g0 > 0 && g0 < g1) {
+    load_xs((uint32_t)(g0 - 1) * (uint32_t)L, (uint32_t)L, prevX);
+    fwd(prevX);
+  }
+  for (int g = g0; g < g1; g++) {
+    const uint32_t n0 = (uint32_t)g * (uint32_t)L, len = seg_len(g);
+    cf v[16], yv[16];
+    load_xs(n0, len, v);
+    if (WITH_R) load_y(0, n0, len, yv); // with the xs segment, as the parent requests it
+    fwd(v);
+#pragma unroll
+    for (int e = 0; e < 16; e++) {
+      const cf z = cmake(v[e].x + sgn * prevX[e].x, v[e].y + sgn * prevX[e].y); // X_g + (-1)^m X_{g-1}
+      if (WITH_R) accR[e] = cmacc(accR[e], v[e], z);
+      prevX[e] = z;
+    }
+#pragma unroll
+    for (int c = 0; c < NB; c++) {
+      if (!WITH_R || c > 0) load_y(c, n0, len, yv);
+      fwd(yv);
+#pragma unroll
+      for (int e = 0; e < 16; e++) accB[c][e] = cmacc(accB[c][e], yv[e], prevX[e]);
+    }
+#pragma unroll
+    for (int e = 0; e < 16; e++) prevX[e] = v[e];
+  }
+  if (blockIdx.x == (unsigned)a.nJobs - 1 && a.nBins > 1) { // the wrap-around pairs
+    const uint32_t tau = (uint32_t)a.nBins - 1;
+    cf v[16], yv[16];
+    load_xs(a.N - tau, tau, prevX); // tail of xs
+    fwd(prevX);
+#pragma unroll
+    for (int j = 0; j < W::NP; j++)
+#pragma unroll
+      for (int sidx = 0; sidx < R3; sidx++) {
+        const int e = j * R3 + sidx;
+        const int p16 = t + T * j;
+        const int m = (p16 >> 4) + 16 * (p16 & 15) + 256 * sidx;
+        const cf ph = a.tw[((uint32_t)m * tau) & (W::F - 1)];
+        prevX[e] = cmulc(prevX[e], ph); // conj(phase) * X_tail
+      }
+    if (WITH_R) {
+      load_xs(0u, tau, v); // head of xs
+      fwd(v);
+#pragma unroll
+      for (int e = 0; e < 16; e++) accR[e] = cmacc(accR[e], v[e], prevX[e]);
+    }
+#pragma unroll
+    for (int c = 0; c < NB; c++) {
+      load_y(c, 0u, tau, yv); // head of y
+      fwd(yv);
+#pragma unroll
+      for (int e = 0; e < 16; e++) accB[c][e] = cmacc(accB[c][e], yv[e], prevX[e]);
+    }
+  }
+  auto finish = [&](cf *acc, int row) {
+    W::inv_s1(t, acc, tw3, P);
+    __syncthreads();
+    W::inv_s2(t, acc, P, Q);
+    __syncthreads();
+    W::inv_s3(t, acc, tw1, Q);
+    cf *dst = a.partial + (((size_t)cpi * a.rows + row) * a.nJobs + blockIdx.x) * a.nBins;
+#pragma unroll
+    for (int c = 0; c < 16; c++) {
+      const int k = t + T * c;
+      if (k < a.nBins) dst[k] = cmake(acc[c].x * a.scale, acc[c].y * a.scale);
+    }
+    __syncthreads();
+  };
+  if (WITH_R) finish(accR, 0);
+  finish(accB[0], a.row0);
+  if (NB > 1) finish(accB[NB - 1], a.row0 + 1);
+}
+
 // ---- reduction of the partials (fp64), then the Toeplitz solve -----------------
 struct SolveArgs {
   const cf *partial; // [nCpi][2][nJobs][nBins]
@@ -618,6 +889,135 @@ __global__ __launch_bounds__(1024) void clutter_solve_kernel(SolveArgs a)
   if (t == 0) a.ok[cpi] = ok ? 1 : 0;
 }
 
+// clutter_solve_kernel for several right-hand sides on ONE matrix (blah2hip_clutter_process_multi_dev_fmt): the columns
+// (U, v), ef, D and 1 / s_{m+1} belong to toeplitz(r) and are formed once per order; a channel adds one Acc, one d and one
+// dt = d / s_{m+1}.  Per channel the arithmetic is clutter_solve_kernel's in its order, so the taps are its bits.  A
+// workgroup carries a tile of NS channels (blockIdx.y = the tile; NS = 8, 4, 2 at 1, 2, 4 indices per thread: 32 registers
+// of Acc); channels of the tile beyond nSurv run on zeros and are not written.  LDS: cur / nxt as there, and the scalars
+// with NS values of d.
+template <int NS> struct SolveScalM {
+  dcx ef;
+  double rs, pad;
+  dcx d[NS];
+};
+struct SolveMultiArgs {
+  const dcx *rb; // [nCpi][rows][nBins]: r, then b_0 .. b_{nSurv-1}
+  cf *w;         // [nSurv][nCpi][nBins]
+  int32_t *ok;   // [nSurv][nCpi]
+  int32_t nBins, rows, nSurv, nCpi;
+};
+
+template <int K, int NS>
+__global__ __launch_bounds__(1024) void clutter_solve_multi_kernel(SolveMultiArgs a)
+{
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int n = a.nBins;
+  dcx *cur = reinterpret_cast<dcx *>(smem);
+  dcx *nxt = cur + (n + 1);
+  SolveScalM<NS> *scal = reinterpret_cast<SolveScalM<NS> *>(nxt + (n + 1)); // [parity]
+  const int cpi = blockIdx.x, k0 = blockIdx.y * NS;
+  const int ns = min(NS, a.nSurv - k0);
+  const int t = threadIdx.x, NT = blockDim.x;
+  const dcx *rg = a.rb + (size_t)cpi * a.rows * n;
+  const dcx *bg = rg + (size_t)(1 + k0) * n; // b of channel k0 + c: bg + c n
+  const double r0 = rg[0].x;
+  bool ok = (r0 > 0.0) && isfinite(r0);
+  const double inv0 = ok ? 1.0 / r0 : 0.0;
+  dcx x0[NS];
+#pragma unroll
+  for (int c = 0; c < NS; c++) {
+    x0[c] = {0.0, 0.0};
+    if (c < ns) x0[c] = {bg[(size_t)c * n].x * inv0, bg[(size_t)c * n].y * inv0}; // x_1[0] = b[0] / r[0]
+  }
+  dcx U[K], Acc[NS][K];
+#pragma unroll
+  for (int k = 0; k < K; k++) {
+    const int j = t + NT * k;
+    U[k] = {0.0, 0.0};
+#pragma unroll
+    for (int c = 0; c < NS; c++) Acc[c][k] = {0.0, 0.0};
+    if (j < n) {
+      const dcx rj = rg[j];
+      if (j == 0) {
+        U[k] = {inv0, 0.0};
+#pragma unroll
+        for (int c = 0; c < NS; c++) Acc[c][k] = x0[c];
+      } else {
+        U[k] = {rj.x * inv0, rj.y * inv0};
+#pragma unroll
+        for (int c = 0; c < NS; c++)
+          if (c < ns) {
+            const dcx g = dsub_mul(bg[(size_t)c * n + j], rj, x0[c]); // g_1[j] = b[j] - r[j] x_1[0]
+            Acc[c][k] = {-g.x, -g.y};
+          }
+      }
+      cur[j] = U[k];
+      if (j == 1) {
+        SolveScalM<NS> s;
+        s.ef = U[k]; s.rs = 1.0; s.pad = 0.0;
+#pragma unroll
+        for (int c = 0; c < NS; c++) { s.d[c] = {-Acc[c][k].x, -Acc[c][k].y}; Acc[c][k] = {0.0, 0.0}; }
+        scal[1] = s;
+        U[k] = {0.0, 0.0};
+      }
+    }
+  }
+  if (t == 0) { cur[n] = {0.0, 0.0}; nxt[n] = {0.0, 0.0}; }
+  __syncthreads();
+  for (int m = 1; m < n && ok; m++) {
+    const SolveScalM<NS> q = scal[m & 1];
+    dcx v[K];
+#pragma unroll
+    for (int k = 0; k < K; k++) {
+      const int j = t + NT * k;
+      const int src = (j > m) ? j - 1 : (j == 0 ? n : m - j);
+      const dcx s = cur[min(src, n)];
+      v[k] = {s.x, (j > m) ? s.y : -s.y};
+    }
+    const double D = __builtin_fma(-q.ef.y, q.ef.y, __builtin_fma(-q.ef.x, q.ef.x, 1.0));
+    if (!(D > 0.0) || !isfinite(D)) { ok = false; break; }
+    const double rsn = q.rs * fast_rcp(D);
+    dcx dt[NS];
+#pragma unroll
+    for (int c = 0; c < NS; c++) dt[c] = {q.d[c].x * rsn, q.d[c].y * rsn};
+    const dcx efc = {q.ef.x, -q.ef.y};
+#pragma unroll
+    for (int k = 0; k < K; k++) {
+      const int j = t + NT * k;
+      if (j < n) {
+        const dcx un = dsub_mul(U[k], q.ef, v[k]);
+        const dcx vn = dsub_mul(v[k], efc, U[k]);
+        const bool hi = j > m;
+        nxt[j] = {hi ? vn.x : un.x, hi ? vn.y : un.y};
+        const bool owner = (j == m + 1);
+        SolveScalM<NS> s;
+        s.ef = {un.x * rsn, un.y * rsn}; s.rs = rsn; s.pad = 0.0;
+#pragma unroll
+        for (int c = 0; c < NS; c++) {
+          const dcx an = dadd_mul(Acc[c][k], dt[c], vn);
+          s.d[c] = {-an.x, -an.y};
+          Acc[c][k] = {owner ? 0.0 : an.x, owner ? 0.0 : an.y};
+        }
+        if (owner) scal[(m + 1) & 1] = s;
+        U[k] = {owner ? 0.0 : un.x, owner ? 0.0 : un.y};
+      }
+    }
+    __syncthreads();
+    dcx *tmp = cur; cur = nxt; nxt = tmp;
+  }
+#pragma unroll
+  for (int c = 0; c < NS; c++)
+    if (c < ns) {
+      cf *wc = a.w + ((size_t)(k0 + c) * a.nCpi + cpi) * n;
+#pragma unroll
+      for (int k = 0; k < K; k++) {
+        const int j = t + NT * k;
+        if (j < n) wc[j] = ok ? cmake((float)Acc[c][k].x, (float)Acc[c][k].y) : cmake(0.f, 0.f);
+      }
+      if (t == 0) a.ok[(size_t)(k0 + c) * a.nCpi + cpi] = ok ? 1 : 0;
+    }
+}
+
 // The same recursion for ANY n (the long filters, blah2hip_clutter_create): every vector in global memory -- per CPI cur / nxt
 // (n + 1 entries each, shared between the threads: written and read through L2, sc1, with the workgroup barrier between), U and
 // Acc (n each, touched by their owner only) -- and a loop over the indices a thread owns instead of register arrays.  A few
@@ -713,7 +1113,9 @@ struct FirArgs {
   int32_t carry;     // segLen = F/2: the upper half of a block's x window is the lower half of the next block's (see the kernel)
 };
 
-template <int R3, class In> __global__ __launch_bounds__(16 * R3, 2) void clutter_fir_kernel(FirArgs a)
+// SKIP_BAD (blah2hip_clutter_process_multi_dev_fmt): a CPI whose matrix is not positive definite is left unwritten
+// instead of passed through -- the workgroup leaves before it reads a sample
+template <int R3, class In, bool SKIP_BAD = false> __global__ __launch_bounds__(16 * R3, 2) void clutter_fir_kernel(FirArgs a)
 {
   using W = WgFft<R3>;
   constexpr int T = W::T;
@@ -726,6 +1128,7 @@ template <int R3, class In> __global__ __launch_bounds__(16 * R3, 2) void clutte
   const typename ChanOf<In>::type Y = ChanOf<In>::y(a.x, a.y, (int64_t)cpi * a.cpiStride);
   cf *O = a.yout + (int64_t)cpi * a.outStride;
   const bool ok = a.ok[cpi] != 0;
+  if (SKIP_BAD && !ok) return; // uniform: one flag per CPI
   cf tw1[15], tw3[16];
   W::load_twiddles(t, a.tw, tw1, tw3);
 
@@ -960,11 +1363,31 @@ struct blah2hip_clutter_s {
   int nChunks = 0;
   cf *d_long = nullptr;      // [3][maxBatch][N]: private copies of x and y (the output is built in the y copy) + one work plane
   dcx *d_solveWs = nullptr;  // [maxBatch][4 nBins + 2]: clutter_solve_big_kernel's vectors
+  // several surveillance channels on one reference (blah2hip_clutter_process_multi_dev_fmt): built by the first such call
+  // for the channels it asks for, kept apart from d_w / d_rb (an ambiguity handle may hold d_w, blah2hip_amb_set_fir)
+  uint32_t multiK = 0;         // channels the buffers below hold
+  cf *d_partialM = nullptr;    // [n_cpi][rows][nJobs][nBins], rows = 1 + K rounded up to even: r, b_0 .. b_{K-1}
+  dcx *d_rbM = nullptr;        // [n_cpi][rows][nBins]
+  cf *d_wM = nullptr;          // [K][n_cpi][nBins]: virtual CPI k n_cpi + c
+  int32_t *d_okM = nullptr;    // [K][n_cpi]
+  uint32_t lastSurv = 0, lastNCpi = 0; // the last call was a multi call: its channels and CPIs per channel (0: a single call)
 };
 
 namespace {
 
 hipError_t solve_la_capacity(blah2hip_clutter_s *h);
+
+// the multi-channel buffers (multi_alloc builds them); the caller has synchronised the device
+hipError_t multi_free(blah2hip_clutter_s *h)
+{
+  for (void **p : {(void **)&h->d_partialM, (void **)&h->d_rbM, (void **)&h->d_wM, (void **)&h->d_okM}) {
+    if (*p) { hipError_t e = hipFree(*p); if (e != hipSuccess) return e; }
+    *p = nullptr;
+  }
+  h->multiK = 0;
+  if (h->lastSurv) { h->lastSurv = 0; h->lastOk = nullptr; }
+  return hipSuccess;
+}
 
 // Mailboxes of the look-ahead Toeplitz solve (solve_la.hpp): sized for the largest launch each plan can be chosen for
 // (create, and again when BLAH2HIP_CLUTTER_OPT_SOLVE_E changes).  Zeroed once: tags are launch epochs >= 1.
@@ -1072,6 +1495,7 @@ int clutter_plan(blah2hip_clutter_s *h)
   h->d_tw = nullptr;
   if (h->d_partial) CHIP(hipFree(h->d_partial));
   h->d_partial = nullptr;
+  CHIP(multi_free(h)); // sized by this plan's job count: the next multi call builds them again
   CHIP(hipMalloc(&h->d_tw, h->F * sizeof(cf)));
   CHIP(hipMemcpy(h->d_tw, tw.data(), h->F * sizeof(cf), hipMemcpyHostToDevice));
   CHIP(hipMalloc(&h->d_partial, (size_t)h->maxBatch * 2 * h->nJobs * nBins * sizeof(cf)));
@@ -1143,6 +1567,16 @@ __global__ void solve_epoch_kernel(uint32_t *epoch)
   *epoch = e ? e : 1u;
 }
 
+// workgroups per CPI of the correlation and FIR kernels at a batch of nCpi (see launch_clutter)
+void clutter_grids(const blah2hip_clutter_s *h, uint32_t nCpi, int *nJobs, int *firGrid)
+{
+  const int slots = 4 * h->numCU; // residency of these kernels: 4 workgroups per CU (LDS)
+  // (multiples of 8: the segment walk is XCD-aware, see seg_walk)
+  auto up8 = [](int v) { return std::max(8, (v + 7) & ~7); };
+  *nJobs = std::min(h->nJobs, up8((2 * slots + (int)nCpi - 1) / (int)nCpi));
+  *firGrid = std::min(h->firGrid, up8((2 * slots + (int)nCpi - 1) / (int)nCpi));
+}
+
 template <int R3, class In> int launch_clutter(blah2hip_clutter_s *h, const void *px, const void *py, uint32_t nCpi,
                                                int64_t stride, cf *yout, int64_t outStride, int32_t *ok, hipStream_t st)
 {
@@ -1160,11 +1594,8 @@ template <int R3, class In> int launch_clutter(blah2hip_clutter_s *h, const void
   // inverse transforms and a partial write, a FIR workgroup starts with the transform of
   // the taps -- per-workgroup costs that a long walk over segments amortises.  Two
   // resident generations' worth keeps the tail short.
-  const int slots = 4 * h->numCU; // residency of these kernels: 4 workgroups per CU (LDS)
-  // (multiples of 8: the segment walk is XCD-aware, see seg_walk)
-  auto up8 = [](int v) { return std::max(8, (v + 7) & ~7); };
-  const int nJobs = std::min(h->nJobs, up8((2 * slots + (int)nCpi - 1) / (int)nCpi));
-  const int firGrid = std::min(h->firGrid, up8((2 * slots + (int)nCpi - 1) / (int)nCpi));
+  int nJobs, firGrid;
+  clutter_grids(h, nCpi, &nJobs, &firGrid);
   if (h->stages & 1) {
   CHIP(h->timer.tic(BLAH2HIP_CK_CORR, st));
   if (h->corrHalf) {
@@ -1205,9 +1636,156 @@ template <int R3, class In> int launch_clutter(blah2hip_clutter_s *h, const void
     CHIP(hipGetLastError());
     CHIP(h->timer.toc(BLAH2HIP_CK_FIR, st));
   }
+  h->lastSurv = 0;
   h->lastOk = ok;
   h->lastStream = st;
   return BLAH2HIP_OK;
+}
+
+// ---- several surveillance channels against one reference ----------------------------------------------------------------
+// Buffers for K channels (the first multi call, or one that asks for more channels than the handle has seen): blocking.
+int multi_alloc(blah2hip_clutter_s *h, uint32_t K)
+{
+  if (K <= h->multiK) return BLAH2HIP_OK;
+  CHIP(hipDeviceSynchronize()); // smaller buffers may still be in use by enqueued work
+  CHIP(multi_free(h));
+  const size_t rows = (K + 2) & ~1u, n = (size_t)h->nBins;
+  if (!h->subCorr) {
+    size_t jobs = 0; // the largest n_cpi x (workgroups per CPI) a launch can have
+    for (uint32_t c = 1; c <= h->maxBatch; c++) {
+      int nJobs, firGrid;
+      clutter_grids(h, c, &nJobs, &firGrid);
+      jobs = std::max(jobs, (size_t)c * nJobs);
+    }
+    CHIP(hipMalloc(&h->d_partialM, jobs * rows * n * sizeof(cf)));
+    CHIP(hipMemset(h->d_partialM, 0, jobs * rows * n * sizeof(cf))); // (the padding row of an even K is summed like the others)
+  }
+  CHIP(hipMalloc(&h->d_rbM, (size_t)h->maxBatch * rows * n * sizeof(dcx)));
+  CHIP(hipMemset(h->d_rbM, 0, (size_t)h->maxBatch * rows * n * sizeof(dcx)));
+  CHIP(hipMalloc(&h->d_wM, (size_t)K * h->maxBatch * n * sizeof(cf)));
+  CHIP(hipMalloc(&h->d_okM, (size_t)K * h->maxBatch * sizeof(int32_t)));
+  h->multiK = K;
+  return BLAH2HIP_OK;
+}
+
+template <int KI, int NS> int launch_solve_multi_ns(const SolveMultiArgs &ma, int nt, size_t ldsVec, hipStream_t st)
+{
+  const size_t sl = ldsVec + 2 * sizeof(SolveScalM<NS>);
+  CHIP(blah2hip_ensure_lds_((const void *)clutter_solve_multi_kernel<KI, NS>, 160 * 1024 - 2048));
+  hipLaunchKernelGGL((clutter_solve_multi_kernel<KI, NS>), dim3(ma.nCpi, (ma.nSurv + NS - 1) / NS), dim3(nt), sl, st, ma);
+  return BLAH2HIP_OK;
+}
+// the smallest tile that holds the channels, up to the register budget of KI indices per thread
+int launch_solve_multi(blah2hip_clutter_s *h, const SolveMultiArgs &ma, hipStream_t st)
+{
+  const size_t ldsVec = ((size_t)2 * (h->nBins + 1)) * sizeof(dcx);
+  const int kper = h->solveK ? h->solveK : (h->nBins > 2048 ? 4 : (h->nBins > 1024 ? 2 : 1));
+  const int nt = std::min(1024, 64 * ((h->nBins + 64 * kper - 1) / (64 * kper)));
+  const int K = ma.nSurv;
+  if (K == 1) {
+    if (kper == 1) return launch_solve_multi_ns<1, 1>(ma, nt, ldsVec, st);
+    if (kper == 2) return launch_solve_multi_ns<2, 1>(ma, nt, ldsVec, st);
+    return launch_solve_multi_ns<4, 1>(ma, nt, ldsVec, st);
+  }
+  if (kper == 4) return launch_solve_multi_ns<4, 2>(ma, nt, ldsVec, st);
+  if (kper == 2) return K <= 2 ? launch_solve_multi_ns<2, 2>(ma, nt, ldsVec, st) : launch_solve_multi_ns<2, 4>(ma, nt, ldsVec, st);
+  if (K <= 2) return launch_solve_multi_ns<1, 2>(ma, nt, ldsVec, st);
+  if (K <= 4) return launch_solve_multi_ns<1, 4>(ma, nt, ldsVec, st);
+  return launch_solve_multi_ns<1, 8>(ma, nt, ldsVec, st);
+}
+
+// launch_clutter for K channels: correlations (the reference's part once per pass), one reduction over 1 + K rows per CPI,
+// one recursion per CPI with K right-hand sides, then the FIR kernel per channel.  Everything sized by nCpi as launch_clutter
+// sizes it.  ok: [K][nCpi].
+template <int R3, class In> int launch_clutter_multi(blah2hip_clutter_s *h, const void *px, const void *const *pys, uint32_t K,
+                                                     uint32_t nCpi, int64_t stride, void *const *youts, int64_t outStride,
+                                                     int32_t *ok, hipStream_t st)
+{
+  using W = WgFft<R3>;
+  const size_t lds = (size_t)(W::A_ELEMS + W::B_ELEMS) * sizeof(cf);
+  XsMap xs;
+  xs.N = h->N;
+  xs.thresh = h->delayMin > 0 ? (uint32_t)h->delayMin : 0u;
+  xs.sub = (uint32_t)h->delayMin;
+  xs.wrapC = (uint32_t)(((1ull << 32) - (uint64_t)(h->delayMin > 0 ? h->delayMin : 0)) % h->N);
+  int nJobs, firGrid;
+  clutter_grids(h, nCpi, &nJobs, &firGrid);
+  const int rows = (int)((K + 2) & ~1u);
+
+  CorrMultiArgs ca;
+  ca.x = px; ca.cpiStride = stride; ca.N = h->N; ca.xs = xs; ca.nBins = h->nBins; ca.nJobs = nJobs;
+  ca.tw = h->d_tw; ca.partial = h->d_partialM; ca.scale = 1.0f / (float)h->F; ca.rows = rows;
+  if (h->corrHalf) {
+    ca.segLen = 0; ca.nSeg = (int)((h->N + (uint32_t)(h->F / 2) - 1) / (uint32_t)(h->F / 2)); ca.per = (ca.nSeg + nJobs - 1) / nJobs;
+    CHIP(blah2hip_ensure_lds_((const void *)clutter_corr_half_multi_kernel<R3, In, true, 1>, (int)lds));
+    CHIP(blah2hip_ensure_lds_((const void *)clutter_corr_half_multi_kernel<R3, In, false, 1>, (int)lds));
+    CHIP(blah2hip_ensure_lds_((const void *)clutter_corr_half_multi_kernel<R3, In, false, 2>, (int)lds));
+  } else {
+    ca.segLen = h->segLen; ca.nSeg = h->nSeg; ca.per = 0;
+    CHIP(blah2hip_ensure_lds_((const void *)clutter_corr_multi_kernel<R3, In, true, 1>, (int)lds));
+    CHIP(blah2hip_ensure_lds_((const void *)clutter_corr_multi_kernel<R3, In, false, 1>, (int)lds));
+    CHIP(blah2hip_ensure_lds_((const void *)clutter_corr_multi_kernel<R3, In, false, 2>, (int)lds));
+  }
+  const dim3 cg(nJobs, nCpi), cb(W::T);
+  CHIP(h->timer.tic(BLAH2HIP_CK_CORR, st));
+  for (uint32_t k = 0; k < K;) { // r and b_0, then the other channels in pairs
+    const uint32_t nb = k == 0 ? 1u : std::min<uint32_t>(CORR_TILE, K - k);
+    ca.y[0] = pys[k]; ca.y[1] = pys[k + nb - 1]; ca.row0 = 1 + (int)k;
+    if (h->corrHalf) {
+      if (k == 0) hipLaunchKernelGGL((clutter_corr_half_multi_kernel<R3, In, true, 1>), cg, cb, lds, st, ca);
+      else if (nb == 1) hipLaunchKernelGGL((clutter_corr_half_multi_kernel<R3, In, false, 1>), cg, cb, lds, st, ca);
+      else hipLaunchKernelGGL((clutter_corr_half_multi_kernel<R3, In, false, 2>), cg, cb, lds, st, ca);
+    } else {
+      if (k == 0) hipLaunchKernelGGL((clutter_corr_multi_kernel<R3, In, true, 1>), cg, cb, lds, st, ca);
+      else if (nb == 1) hipLaunchKernelGGL((clutter_corr_multi_kernel<R3, In, false, 1>), cg, cb, lds, st, ca);
+      else hipLaunchKernelGGL((clutter_corr_multi_kernel<R3, In, false, 2>), cg, cb, lds, st, ca);
+    }
+    k += nb;
+  }
+  CHIP(hipGetLastError());
+  CHIP(h->timer.toc(BLAH2HIP_CK_CORR, st));
+
+  // clutter_reduce_kernel sums pairs of rows: [nCpi][rows] is [nCpi rows / 2][2]
+  SolveArgs ra;
+  ra.partial = h->d_partialM; ra.rb = h->d_rbM; ra.w = nullptr; ra.ok = nullptr; ra.nBins = h->nBins; ra.nJobs = nJobs;
+  ra.epoch = nullptr; // the look-ahead solve's mailboxes are not used here
+  CHIP(h->timer.tic(BLAH2HIP_CK_REDUCE, st));
+  hipLaunchKernelGGL(clutter_reduce_kernel, dim3((h->nBins + 15) / 16, 2, nCpi * (uint32_t)(rows / 2)), dim3(16 * RED_SLICES), 0, st, ra);
+  CHIP(hipGetLastError());
+  CHIP(h->timer.toc(BLAH2HIP_CK_REDUCE, st));
+
+  SolveMultiArgs ma;
+  ma.rb = h->d_rbM; ma.w = h->d_wM; ma.ok = ok; ma.nBins = h->nBins; ma.rows = rows; ma.nSurv = (int)K; ma.nCpi = (int)nCpi;
+  CHIP(h->timer.tic(BLAH2HIP_CK_SOLVE, st));
+  { const int rc_ = launch_solve_multi(h, ma, st); if (rc_) return rc_; }
+  CHIP(hipGetLastError());
+  CHIP(h->timer.toc(BLAH2HIP_CK_SOLVE, st));
+  h->lastForm = BLAH2HIP_CLUTTER_SOLVE_STEPWISE; h->lastE = 0; h->lastG = 1;
+
+  if (youts) { // the taps only otherwise (as blah2hip_clutter_estimate_dev_fmt)
+    CHIP(blah2hip_ensure_lds_((const void *)clutter_fir_kernel<R3, In, true>, (int)lds));
+    FirArgs fa;
+    fa.x = px; fa.cpiStride = stride; fa.outStride = outStride; fa.N = h->N; fa.xs = xs;
+    fa.nBins = h->nBins; fa.segLen = h->segLen; fa.nSeg = h->nSeg; fa.tw = h->d_tw;
+    fa.scale = 1.0f / (float)h->F;
+    fa.carry = h->firCarry ? 1 : 0;
+    CHIP(h->timer.tic(BLAH2HIP_CK_FIR, st));
+    for (uint32_t k = 0; k < K; k++) {
+      fa.y = pys[k]; fa.yout = (cf *)youts[k]; fa.w = h->d_wM + (size_t)k * nCpi * h->nBins; fa.ok = ok + (size_t)k * nCpi;
+      hipLaunchKernelGGL((clutter_fir_kernel<R3, In, true>), dim3(firGrid, nCpi), dim3(W::T), lds, st, fa);
+    }
+    CHIP(hipGetLastError());
+    CHIP(h->timer.toc(BLAH2HIP_CK_FIR, st));
+  }
+  return BLAH2HIP_OK;
+}
+
+// a long filter's result into the caller's plane, CPI by CPI where ok (the multi entry point leaves the others unwritten)
+__global__ __launch_bounds__(256) void long_out_kernel(const cf *src, cf *dst, uint32_t N, int64_t dstStride, const int32_t *ok)
+{
+  const uint32_t m = blockIdx.x * 256u + threadIdx.x;
+  if (m >= N || !ok[blockIdx.y]) return;
+  dst[(int64_t)blockIdx.y * dstStride + m] = src[(size_t)blockIdx.y * N + m];
 }
 
 // ---- LONG filters: more taps than one transform holds --------------------------------------------------------------
@@ -1264,7 +1842,7 @@ __global__ __launch_bounds__(256) void long_taps_kernel(const cf *w, cf *wsub, i
 }
 
 int long_process(blah2hip_clutter_s *h, const cf *d_x, const cf *d_y, uint32_t nCpi, int64_t stride, cf *yout, int64_t outStride,
-                 int32_t *ok, hipStream_t st)
+                 int32_t *ok, hipStream_t st, bool skipBad = false)
 {
   const uint32_t N = h->N, dmin = (uint32_t)h->delayMin;
   const int n = h->nBins, C = LONG_C;
@@ -1308,9 +1886,15 @@ int long_process(blah2hip_clutter_s *h, const cf *d_x, const cf *d_y, uint32_t n
       const int rc = launch_clutter<16, InC32>(sf, wp, yp, nCpi, (int64_t)N, yp, (int64_t)N, ok, st); // in place: y -= w_c * xs_c
       if (rc) return rc;
     }
-    CHIP(hipMemcpy2DAsync(yout, (size_t)outStride * sizeof(cf), yp, (size_t)N * sizeof(cf), (size_t)N * sizeof(cf), nCpi, hipMemcpyDeviceToDevice, st));
+    if (skipBad) {
+      long_out_kernel<<<pg, 256, 0, st>>>(yp, yout, N, outStride, ok);
+      CHIP(hipGetLastError());
+    } else {
+      CHIP(hipMemcpy2DAsync(yout, (size_t)outStride * sizeof(cf), yp, (size_t)N * sizeof(cf), (size_t)N * sizeof(cf), nCpi, hipMemcpyDeviceToDevice, st));
+    }
     CHIP(h->timer.toc(BLAH2HIP_CK_FIR, st));
   }
+  h->lastSurv = 0;
   h->lastOk = ok;
   h->lastStream = st;
   return BLAH2HIP_OK;
@@ -1388,7 +1972,8 @@ int blah2hip_clutter_destroy(blah2hip_clutter_t h)
   if (h->subCorr) (void)blah2hip_clutter_destroy(h->subCorr);
   if (h->subFir) (void)blah2hip_clutter_destroy(h->subFir);
   for (void *p : {(void *)h->d_tw, (void *)h->d_partial, (void *)h->d_rb, (void *)h->d_w, (void *)h->d_ok,
-                  (void *)h->d_stage, (void *)h->d_mail, (void *)h->d_epoch, (void *)h->d_long, (void *)h->d_solveWs})
+                  (void *)h->d_stage, (void *)h->d_mail, (void *)h->d_epoch, (void *)h->d_long, (void *)h->d_solveWs,
+                  (void *)h->d_partialM, (void *)h->d_rbM, (void *)h->d_wM, (void *)h->d_okM})
     if (p) (void)hipFree(p);
   h->timer.destroy();
   if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -1430,6 +2015,23 @@ int blah2hip_clutter_get_info(blah2hip_clutter_t h, int what, int64_t *value)
 int blah2hip_clutter_read_last(blah2hip_clutter_t h, uint32_t cpi, float *w, double *rb, int *ok)
 {
   if (!h) CFAIL(BLAH2HIP_ERR_INVALID, "NULL handle");
+  if (h->lastSurv) { // behind a multi call: virtual CPI k n_cpi + c
+    if (cpi >= h->lastSurv * h->lastNCpi) CFAIL(BLAH2HIP_ERR_INVALID, "cpi index out of range (virtual CPIs of the last multi call)");
+    CHIP(hipSetDevice(h->device));
+    CHIP(hipDeviceSynchronize());
+    const size_t n = (size_t)h->nBins, k = cpi / h->lastNCpi, c = cpi % h->lastNCpi, rows = (h->lastSurv + 2) & ~1u;
+    if (w) CHIP(hipMemcpy(w, h->d_wM + (size_t)cpi * n, n * sizeof(cf), hipMemcpyDeviceToHost));
+    if (rb) {
+      CHIP(hipMemcpy(rb, h->d_rbM + c * rows * n, n * sizeof(dcx), hipMemcpyDeviceToHost));
+      CHIP(hipMemcpy(rb + 2 * n, h->d_rbM + (c * rows + 1 + k) * n, n * sizeof(dcx), hipMemcpyDeviceToHost));
+    }
+    if (ok) {
+      int32_t v = 0;
+      CHIP(hipMemcpy(&v, h->lastOk + cpi, sizeof(int32_t), hipMemcpyDeviceToHost));
+      *ok = v;
+    }
+    return BLAH2HIP_OK;
+  }
   if (cpi >= h->maxBatch) CFAIL(BLAH2HIP_ERR_INVALID, "cpi index out of range");
   CHIP(hipSetDevice(h->device));
   CHIP(hipDeviceSynchronize());
@@ -1519,6 +2121,7 @@ int blah2hip_clutter_solve(blah2hip_clutter_t h, const double *rb, uint32_t n_cp
   SolveArgs sa;
   sa.partial = nullptr; sa.rb = h->d_rb; sa.w = h->d_w; sa.ok = h->d_ok; sa.nBins = h->nBins; sa.nJobs = 0; sa.epoch = h->d_epoch;
   { const int rc_ = launch_solve(h, sa, n_cpi, h->stream); if (rc_) return rc_; }
+  h->lastSurv = 0;
   h->lastOk = h->d_ok;
   h->lastStream = h->stream;
   CHIP(hipMemcpyAsync(w, h->d_w, (size_t)n_cpi * n * sizeof(cf), hipMemcpyDeviceToHost, h->stream));
@@ -1536,6 +2139,7 @@ int blah2hip_clutter_solve_dev(blah2hip_clutter_t h, const double *d_rb, uint32_
   hipLaunchKernelGGL(solve_epoch_kernel, dim3(1), dim3(1), 0, st, h->d_epoch);
   SolveArgs sa;
   sa.partial = nullptr; sa.rb = (dcx *)d_rb; sa.w = (cf *)d_w; sa.ok = d_ok; sa.nBins = h->nBins; sa.nJobs = 0; sa.epoch = h->d_epoch;
+  h->lastSurv = 0;
   h->lastOk = d_ok;
   h->lastStream = (hipStream_t)stream;
   return launch_solve(h, sa, n_cpi, st);
@@ -1647,10 +2251,65 @@ int blah2hip_clutter_estimate_dev_fmt(blah2hip_clutter_t h, int fmt, const void 
   }
 }
 
+int blah2hip_clutter_process_multi_dev_fmt(blah2hip_clutter_t h, int fmt, const void *d_x, const void *const *d_y, uint32_t n_surv,
+                                           uint32_t n_cpi, uint64_t cpi_stride, void *const *d_y_out, uint64_t out_stride,
+                                           int32_t *d_ok, void *stream)
+{
+  if (!h || !d_x || !d_y) CFAIL(BLAH2HIP_ERR_INVALID, "NULL argument");
+  if (fmt == BLAH2HIP_FMT_I16)
+    CFAIL(BLAH2HIP_ERR_UNSUPPORTED, "BLAH2HIP_FMT_I16 carries one surveillance channel in the reference's words: several channels need planes of their own");
+  if (fmt != BLAH2HIP_FMT_C32 && fmt != BLAH2HIP_FMT_I8)
+    CFAIL(BLAH2HIP_ERR_INVALID, "clutter filter input of several channels: BLAH2HIP_FMT_C32 or BLAH2HIP_FMT_I8");
+  if (n_surv == 0) CFAIL(BLAH2HIP_ERR_INVALID, "n_surv is 0");
+  if (n_surv > BLAH2HIP_MAX_SURV) CFAIL(BLAH2HIP_ERR_INVALID, "n_surv exceeds BLAH2HIP_MAX_SURV");
+  for (uint32_t k = 0; k < n_surv; k++) {
+    if (!d_y[k]) CFAIL(BLAH2HIP_ERR_INVALID, ("NULL surveillance plane " + std::to_string(k)).c_str());
+    if (d_y_out && !d_y_out[k]) CFAIL(BLAH2HIP_ERR_INVALID, ("NULL output plane " + std::to_string(k)).c_str());
+  }
+  if (n_cpi == 0 || n_cpi > h->maxBatch) CFAIL(BLAH2HIP_ERR_INVALID, "n_cpi outside [1, max_batch]");
+  if (n_cpi > 1 && (cpi_stride < h->N || (d_y_out && out_stride < h->N))) CFAIL(BLAH2HIP_ERR_INVALID, "cpi_stride / out_stride < nSamples");
+  CHIP(hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  { const int rc_ = multi_alloc(h, n_surv); if (rc_) return rc_; }
+  int32_t *ok = d_ok ? d_ok : h->d_okM;
+  const int64_t cs = (int64_t)cpi_stride, os = (int64_t)out_stride;
+  int rc = BLAH2HIP_OK;
+  if (h->subCorr) { // a long filter: the per-channel path, channel by channel; nothing is shared
+    if (fmt != BLAH2HIP_FMT_C32) CFAIL(BLAH2HIP_ERR_UNSUPPORTED, "a long filter (more than 4081 taps) takes fp32 planes only, not BLAH2HIP_FMT_I8");
+    const size_t n = (size_t)h->nBins, rows = (n_surv + 2) & ~1u;
+    for (uint32_t k = 0; k < n_surv && !rc; k++) {
+      rc = long_process(h, (const cf *)d_x, (const cf *)d_y[k], n_cpi, cs, d_y_out ? (cf *)d_y_out[k] : nullptr, os, ok + (size_t)k * n_cpi, st, true);
+      if (rc) break;
+      // taps and correlations into the virtual-CPI layout
+      CHIP(hipMemcpyAsync(h->d_wM + (size_t)k * n_cpi * n, h->d_w, (size_t)n_cpi * n * sizeof(cf), hipMemcpyDeviceToDevice, st));
+      if (k == 0)
+        CHIP(hipMemcpy2DAsync(h->d_rbM, rows * n * sizeof(dcx), h->d_rb, 2 * n * sizeof(dcx), n * sizeof(dcx), n_cpi, hipMemcpyDeviceToDevice, st));
+      CHIP(hipMemcpy2DAsync(h->d_rbM + (1 + k) * n, rows * n * sizeof(dcx), h->d_rb + n, 2 * n * sizeof(dcx), n * sizeof(dcx), n_cpi, hipMemcpyDeviceToDevice, st));
+    }
+  } else if (fmt == BLAH2HIP_FMT_I8) {
+    switch (h->r3) {
+    case 4: rc = launch_clutter_multi<4, InI8>(h, d_x, d_y, n_surv, n_cpi, cs, d_y_out, os, ok, st); break;
+    case 8: rc = launch_clutter_multi<8, InI8>(h, d_x, d_y, n_surv, n_cpi, cs, d_y_out, os, ok, st); break;
+    default: rc = launch_clutter_multi<16, InI8>(h, d_x, d_y, n_surv, n_cpi, cs, d_y_out, os, ok, st); break;
+    }
+  } else {
+    switch (h->r3) {
+    case 4: rc = launch_clutter_multi<4, InC32>(h, d_x, d_y, n_surv, n_cpi, cs, d_y_out, os, ok, st); break;
+    case 8: rc = launch_clutter_multi<8, InC32>(h, d_x, d_y, n_surv, n_cpi, cs, d_y_out, os, ok, st); break;
+    default: rc = launch_clutter_multi<16, InC32>(h, d_x, d_y, n_surv, n_cpi, cs, d_y_out, os, ok, st); break;
+    }
+  }
+  if (rc) return rc;
+  h->lastSurv = n_surv; h->lastNCpi = n_cpi;
+  h->lastOk = ok;
+  h->lastStream = st;
+  return BLAH2HIP_OK;
+}
+
 int blah2hip_clutter_taps_dev(blah2hip_clutter_t h, const float **d_w, uint32_t *n_bins, int32_t *delay_min)
 {
   if (!h) CFAIL(BLAH2HIP_ERR_INVALID, "NULL handle");
-  if (d_w) *d_w = reinterpret_cast<const float *>(h->d_w);
+  if (d_w) *d_w = reinterpret_cast<const float *>(h->lastSurv ? h->d_wM : h->d_w);
   if (n_bins) *n_bins = (uint32_t)h->nBins;
   if (delay_min) *delay_min = h->delayMin;
   return BLAH2HIP_OK;

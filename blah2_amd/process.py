@@ -588,6 +588,21 @@ class WienerHopf:
         or FMT_I8, as for ``process_dev_fmt``."""
         check(self._L.blah2hip_clutter_estimate_dev_fmt(self._h, fmt, d_x, d_y, n_cpi, cpi_stride, d_ok, stream))
 
+    def process_multi_dev(self, fmt, d_x, d_ys, n_cpi, cpi_stride, d_youts, out_stride, d_ok=None, stream=0):
+        """One reference plane, ``len(d_ys)`` surveillance planes (blah2hip_clutter_process_multi_dev_fmt; raw pointers/ints):
+        r, the reference's spectra and the Toeplitz recursion once per CPI, b_k, the taps and the FIR per channel.  ``fmt``:
+        FMT_C32 or FMT_I8; ``d_youts``: one complex64 plane per channel, or None to estimate only; ``d_ok``: int32
+        [len(d_ys)][n_cpi].  Channel k of CPI c is virtual CPI ``k * n_cpi + c`` of ``d_ok``, ``read_last`` and ``taps_dev``."""
+        K = len(d_ys)
+        planes = (C.c_void_p * max(1, K))(*[int(p) if p else None for p in d_ys])
+        outs = None
+        if d_youts is not None:
+            if len(d_youts) != K:
+                raise ValueError(f"{K} surveillance planes, {len(d_youts)} output planes")
+            outs = (C.c_void_p * max(1, K))(*[int(p) if p else None for p in d_youts])
+        check(self._L.blah2hip_clutter_process_multi_dev_fmt(self._h, fmt, d_x, planes, K, n_cpi, cpi_stride, outs, out_stride,
+                                                             d_ok, stream))
+
     def taps_dev(self):
         """(device pointer of the taps [max_batch][nBins] complex64, nBins, the filter's first lag)."""
         p, nb, dm = C.c_void_p(), C.c_uint32(), C.c_int32()

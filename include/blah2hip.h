@@ -418,6 +418,32 @@ int blah2hip_clutter_process_dev(blah2hip_clutter_t h, const void *d_x, const vo
  * d_y_out + c * out_stride samples (for FMT_C32 it may alias d_y with out_stride = cpi_stride).  Enqueues only. */
 int blah2hip_clutter_process_dev_fmt(blah2hip_clutter_t h, int fmt, const void *d_x, const void *d_y, uint32_t n_cpi,
                                      uint64_t cpi_stride, void *d_y_out, uint64_t out_stride, int32_t *d_ok, void *stream);
+/* Several surveillance channels on the same clock against ONE reference (a KrakenSDR; the filter in front of
+ * blah2hip_amb_process_multi_dev).  d_y, d_y_out: HOST arrays of n_surv device planes, read at the call; every plane has the
+ * layout and stride blah2hip_clutter_process_dev_fmt takes for the same fmt, d_y_out[k] is a complex fp32 plane (FMT_C32: it may
+ * alias d_y[k]).  d_y_out = NULL: estimate only, as blah2hip_clutter_estimate_dev_fmt (the taps stay in the handle).
+ * What belongs to the reference alone is computed once per CPI instead of once per channel: its autocorrelation r and the
+ * spectra every b_k is formed against (shared-reference forms of both correlation kernels; one reduction over 1 + n_surv rows),
+ * and the Levinson/Schur recursion on toeplitz(r) (one recursion with n_surv right-hand sides).  The FIR kernel runs once per
+ * channel.  r, b_k, the taps and the filtered planes are the BITS of n_surv blah2hip_clutter_process_dev_fmt calls on a handle set
+ * to BLAH2HIP_CLUTTER_SOLVE_STEPWISE: the look-ahead solve has no form with several right-hand sides, this entry point always
+ * runs the one-workgroup recursion and BLAH2HIP_CLUTTER_INFO_SOLVE_FORM reports _STEPWISE (K per-channel calls keep the
+ * look-ahead solve).
+ * d_ok: [n_surv][n_cpi] int32, channel-major (NULL: the handle's): the matrix is shared, so the n_surv flags of a CPI are equal;
+ * channel k of CPI c is VIRTUAL CPI k * n_cpi + c, as for the maps of blah2hip_amb_process_multi_dev.  Where ok = 0 the taps are
+ * zero and NO channel's output is written for that CPI (the single-channel dev calls pass y through there).
+ * After this call blah2hip_clutter_read_last and blah2hip_clutter_taps_dev count virtual CPIs: read_last(k * n_cpi + c) returns
+ * w_k, r and b_k of CPI c, taps_dev points at [n_surv][n_cpi][n_bins] (a buffer of its own: the pointer differs from the one a
+ * single-channel call leaves, which stays valid).  set_timing / get_timing: the BLAH2HIP_CK_* slots, one bracket per stage.
+ * fmt: BLAH2HIP_FMT_C32 or BLAH2HIP_FMT_I8; BLAH2HIP_FMT_I16 (one surveillance channel inside the reference's words) is
+ * BLAH2HIP_ERR_UNSUPPORTED.  BLAH2HIP_ERR_INVALID: n_surv == 0 or > BLAH2HIP_MAX_SURV, a NULL plane, n_cpi == 0 or > max_batch
+ * (max_batch counts CPIs per channel here).  A long filter (more than 4081 taps) runs the per-channel path inside the call,
+ * channel after channel: the same result, nothing shared, FMT_C32 only.
+ * Enqueues only -- except the first call (and a call with more channels than any before, or the first after a re-planning
+ * blah2hip_clutter_set_option), which builds the handle's buffers for n_surv channels: blocking, like the other lazily built state. */
+int blah2hip_clutter_process_multi_dev_fmt(blah2hip_clutter_t h, int fmt, const void *d_x, const void *const *d_y, uint32_t n_surv,
+                                           uint32_t n_cpi, uint64_t cpi_stride, void *const *d_y_out, uint64_t out_stride,
+                                           int32_t *d_ok, void *stream);
 /* Execution plan of the filter.  SOLVE_K: indices of the Toeplitz recursion per thread (0 = by
  * size: 1 up to 1024 taps, 2 up to 2048, 4 above; the workgroup has ceil(nBins / K) threads rounded up to a wave). */
 #define BLAH2HIP_CLUTTER_OPT_SOLVE_K 1
