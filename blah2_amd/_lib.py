@@ -15,9 +15,9 @@ LIB_PATH = os.path.join(PKG, "libblah2hip.so")
 OK = 0
 ERR_INVALID, ERR_HIP, ERR_UNSUPPORTED, ERR_UNDERFLOW, ERR_NO_DEVICE, ERR_CAPACITY = -1, -2, -3, -4, -5, -6
 FMT_C32, FMT_I16, FMT_F16, FMT_I16X_C32Y, FMT_I8, FMT_I8X_C32Y = 0, 1, 2, 3, 4, 5
-K_RANGE, K_DOPPLER, K_METRICS, K_CFAR, K_SAT_ROWS, K_SAT_COLS, K_ROTATE, K_COUNT = 0, 1, 2, 3, 4, 5, 6, 8
+K_RANGE, K_DOPPLER, K_METRICS, K_CFAR, K_SAT_ROWS, K_SAT_COLS, K_ROTATE, K_BEAM, K_COUNT = 0, 1, 2, 3, 4, 5, 6, 7, 8
 KERNEL_NAMES = {K_RANGE: "range", K_DOPPLER: "doppler", K_METRICS: "metrics", K_CFAR: "cfar",
-                K_SAT_ROWS: "sat_rows", K_SAT_COLS: "sat_cols", K_ROTATE: "rotate"}
+                K_SAT_ROWS: "sat_rows", K_SAT_COLS: "sat_cols", K_ROTATE: "rotate", K_BEAM: "beam"}
 CK_CORR, CK_REDUCE, CK_SOLVE, CK_FIR, CK_COUNT = 0, 1, 2, 3, 4
 CLUTTER_KERNEL_NAMES = {CK_CORR: "clutter_corr", CK_REDUCE: "clutter_reduce", CK_SOLVE: "clutter_solve",
                         CK_FIR: "clutter_fir"}
@@ -28,6 +28,7 @@ OPT_CFAR2D_SEG_ROWS, OPT_CFAR2D_GRID = 9, 10
 OPT_MULTI_SURV_RANGE = 11
 MULTI_AUTO, MULTI_SHARED, MULTI_PER_CHANNEL = 0, 1, 2
 MAX_SURV = 8
+MAX_BEAMS = 8
 LEAK_OFF, LEAK_AUTO, LEAK_ALWAYS = 0, 1, 2
 CFAR2D_AUTO, CFAR2D_TILE, CFAR2D_SAT, CFAR2D_STREAM = 0, 1, 2, 3
 CLUTTER_OPT_SOLVE_K, CLUTTER_OPT_FFT_LEN, CLUTTER_OPT_CORR, CLUTTER_OPT_SOLVE_FORM, CLUTTER_OPT_SOLVE_E, CLUTTER_OPT_FIR_CARRY = 1, 2, 3, 4, 5, 6
@@ -94,6 +95,8 @@ SYMBOLS = {
     "blah2hip_amb_process_multi_c32": (C.c_int, [_vp, _vp, C.POINTER(_vp), _u32, _u32, _vp, _vp]),
     "blah2hip_amb_read_last": (C.c_int, [_vp, _u32, _vp, _vp]),
     "blah2hip_amb_db_dev": (C.c_int, [_vp, _vp, _vp, _u32, _vp, _vp]),
+    "blah2hip_amb_beamform_dev": (C.c_int, [_vp, _vp, _u32, _u32, _vp, _u32, _vp, _vp, _vp]),
+    "blah2hip_amb_snapshot_dev": (C.c_int, [_vp, _vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _vp]),
     "blah2hip_cfar1d_dev": (C.c_int, [_vp, _vp, _vp, _u32, _dbl, _i32, _i32, _i32, _dbl, _vp, _u32, _vp, _vp]),
     "blah2hip_cfar1d_prepare": (C.c_int, [_vp, _dbl, _i32]),
     "blah2hip_cfar2d_prepare": (C.c_int, [_vp, _dbl, _i32, _i32, _i32, _i32]),

@@ -4,6 +4,7 @@
 #include "kernels.hpp"
 #include "cfar_kernels.hpp"
 #include "detect_kernels.hpp"
+#include "beam_kernels.hpp"
 #include "timing.hpp"
 
 #include <algorithm>
@@ -1922,6 +1923,91 @@ int blah2hip_amb_db_dev(blah2hip_amb_t h, const void *d_map, const double *d_met
   const double *met = d_metrics ? d_metrics : h->d_metrics;
   const int gx = (int)std::min<uint32_t>((cells + 255) / 256, 4u * (uint32_t)h->numCU);
   hipLaunchKernelGGL(db_map_kernel, dim3(gx, n_cpi), dim3(256), 0, (hipStream_t)stream, map, met, d_db, cells);
+  HIPCHK(hipGetLastError());
+  return BLAH2HIP_OK;
+}
+
+// ------------------------------------------------ beams in the map domain --
+static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
+{
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a0 < b0 + nb && b0 < a0 + na;
+}
+
+int blah2hip_amb_beamform_dev(blah2hip_amb_t h, const void *d_map, uint32_t n_surv, uint32_t n_cpi, const float *w,
+                              uint32_t n_beams, void *d_beam_map, double *d_beam_metrics, void *stream)
+{
+  if (!h) return fail(BLAH2HIP_ERR_INVALID, "NULL handle");
+  if (n_surv == 0 || n_surv > BLAH2HIP_MAX_SURV) return fail(BLAH2HIP_ERR_INVALID, "n_surv outside [1, BLAH2HIP_MAX_SURV]");
+  if (n_beams == 0 || n_beams > BLAH2HIP_MAX_BEAMS) return fail(BLAH2HIP_ERR_INVALID, "n_beams outside [1, BLAH2HIP_MAX_BEAMS]");
+  if (n_cpi == 0) return fail(BLAH2HIP_ERR_INVALID, "n_cpi is 0");
+  if ((uint64_t)n_surv * n_cpi > h->dims.max_batch) return fail(BLAH2HIP_ERR_INVALID, "n_surv * n_cpi above max_batch");
+  if ((uint64_t)n_beams * n_cpi > h->dims.max_batch) return fail(BLAH2HIP_ERR_INVALID, "n_beams * n_cpi above max_batch");
+  if (!w || !d_beam_map || !d_beam_metrics) return fail(BLAH2HIP_ERR_INVALID, "NULL weights or output");
+  const size_t cells = (size_t)h->dims.n_doppler_bins * h->dims.n_delay_bins;
+  const cf *in = d_map ? (const cf *)d_map : h->d_map;
+  const size_t inBytes = (size_t)n_surv * n_cpi * cells * sizeof(cf);
+  if (ranges_overlap(in, inBytes, d_beam_map, (size_t)n_beams * n_cpi * cells * sizeof(cf)) ||
+      ranges_overlap(in, inBytes, d_beam_metrics, (size_t)n_beams * n_cpi * 2 * sizeof(double)))
+    return fail(BLAH2HIP_ERR_INVALID, "beamform: an output overlaps the input maps");
+  HIPCHK(hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+
+  BeamArgs a;
+  a.in = in;
+  a.out = (cf *)d_beam_map;
+  a.partSum = h->d_partSum;
+  a.partMax = h->d_partMax;
+  a.cells = (uint32_t)cells;
+  a.nCpi = n_cpi;
+  a.nBeams = n_beams;
+  memset(a.w, 0, sizeof(a.w));
+  for (uint32_t b = 0; b < n_beams; b++)
+    for (uint32_t k = 0; k < n_surv; k++) a.w[b][k] = cmake(w[2 * (b * n_surv + k)], w[2 * (b * n_surv + k) + 1]);
+  // 16-byte accesses where CPI c starts at the same offset modulo 16 bytes in every channel's and every beam's block: the
+  // blocks are n_cpi * cells cells apart, so an odd product (odd cell count, odd n_cpi) with more than one block does not
+  const bool oddBlock = ((size_t)n_cpi * cells) & 1;
+  const bool wide = !(((uintptr_t)in ^ (uintptr_t)d_beam_map) & 15) && !((uintptr_t)in & 7) &&
+                    !(oddBlock && (n_surv > 1 || n_beams > 1));
+  // workgroups per CPI: eight a CU over the launch, each with at least one pass of 256 units, and no more than the
+  // handle has partials for (nParts per CPI of max_batch >= n_beams * n_cpi)
+  const size_t units = wide ? (cells + 1) / 2 : cells;
+  const uint32_t gMax = (uint32_t)std::min<size_t>((size_t)h->nParts, (units + 255) / 256);
+  const uint32_t G = std::max(1u, std::min(gMax, (8u * (uint32_t)h->numCU + n_cpi - 1) / n_cpi));
+  int rc;
+  if ((rc = tic(h, BLAH2HIP_K_BEAM, st))) return rc;
+  if (wide) launch_beamform<2>(n_surv, dim3(G, n_cpi), st, a);
+  else launch_beamform<1>(n_surv, dim3(G, n_cpi), st, a);
+  HIPCHK(hipGetLastError());
+  if ((rc = toc(h, BLAH2HIP_K_BEAM, st))) return rc;
+  if ((rc = tic(h, BLAH2HIP_K_METRICS, st))) return rc;
+  hipLaunchKernelGGL(metrics_kernel, dim3(n_beams * n_cpi), dim3(256), 0, st, h->d_partSum, h->d_partMax, (int)G,
+                     (double)cells, d_beam_metrics);
+  HIPCHK(hipGetLastError());
+  return toc(h, BLAH2HIP_K_METRICS, st);
+}
+
+int blah2hip_amb_snapshot_dev(blah2hip_amb_t h, const void *d_map, uint32_t n_surv, uint32_t n_cpi,
+                              const blah2hip_det_t *d_dets, uint32_t cap, const uint32_t *d_count, uint32_t n_lists,
+                              float *d_snap, void *stream)
+{
+  if (!h || !d_dets || !d_count || !d_snap) return fail(BLAH2HIP_ERR_INVALID, "NULL argument");
+  if (n_surv == 0 || n_surv > BLAH2HIP_MAX_SURV) return fail(BLAH2HIP_ERR_INVALID, "n_surv outside [1, BLAH2HIP_MAX_SURV]");
+  if (n_cpi == 0 || (uint64_t)n_surv * n_cpi > h->dims.max_batch) return fail(BLAH2HIP_ERR_INVALID, "n_cpi is 0 or n_surv * n_cpi above max_batch");
+  if (cap == 0) return fail(BLAH2HIP_ERR_INVALID, "cap is 0");
+  if (n_lists == 0 || n_lists % n_cpi != 0) return fail(BLAH2HIP_ERR_INVALID, "n_lists is 0 or not a multiple of n_cpi");
+  HIPCHK(hipSetDevice(h->device));
+  SnapArgs a;
+  a.map = d_map ? (const cf *)d_map : h->d_map;
+  a.dets = d_dets;
+  a.count = d_count;
+  a.snap = (cf *)d_snap;
+  a.nSurv = n_surv; a.nCpi = n_cpi; a.cap = cap; a.nLists = n_lists;
+  a.nD = (int32_t)h->dims.n_doppler_bins;
+  a.nDelay = (int32_t)h->dims.n_delay_bins;
+  const size_t blocks = ((size_t)n_lists * cap + 255) / 256;
+  hipLaunchKernelGGL(snapshot_kernel, dim3((uint32_t)std::min<size_t>(blocks, 8u * (size_t)h->numCU)), dim3(256), 0,
+                     (hipStream_t)stream, a);
   HIPCHK(hipGetLastError());
   return BLAH2HIP_OK;
 }

@@ -22,6 +22,16 @@ def _ptr(a):
     return C.c_void_p(a.ctypes.data) if a is not None else None
 
 
+def ula_weights(n_surv, spacing_wavelengths, angles_deg):
+    """Beam weights of a uniform line array of ``n_surv`` elements ``spacing_wavelengths`` apart, one row per angle
+    (degrees off broadside): the conjugate steering vectors over the element count,
+    ``w[b][k] = exp(-2j pi k d sin(theta_b)) / n_surv``, complex128 ``[n_beams, n_surv]`` -- the ``w`` of
+    :meth:`Ambiguity.beamform_dev`.  Pure NumPy."""
+    theta = np.deg2rad(np.atleast_1d(np.asarray(angles_deg, dtype=np.float64)))
+    k = np.arange(int(n_surv), dtype=np.float64)
+    return np.exp(-2j * np.pi * float(spacing_wavelengths) * np.sin(theta)[:, None] * k[None, :]) / int(n_surv)
+
+
 class Map:
     """src/data/Map.h: rows = Doppler, cols = delay.  ``data`` is complex64."""
 
@@ -241,6 +251,56 @@ class Ambiguity:
         self._n_samples = self.dims.n_used
         self._gen += 1
         return [self._result(out[k], met[k], k) for k in range(len(ys))]
+
+    def beamform_dev(self, d_map, n_surv, n_cpi, w, d_beam_map, d_beam_metrics, stream=0):
+        """Beams over the channel maps of ``process_multi_dev`` (blah2hip_amb_beamform_dev; raw pointers/ints): ``w`` is a
+        complex array ``[n_beams, n_surv]`` (host), ``d_map`` the ``[n_surv][n_cpi]`` maps (None: the handle's own).  Beam b of
+        CPI c is virtual CPI ``b * n_cpi + c`` of ``d_beam_map`` / ``d_beam_metrics`` for the detectors' ``process_dev``
+        (called with ``n_beams * n_cpi``)."""
+        w = np.ascontiguousarray(w, dtype=np.complex64)
+        if w.ndim != 2 or w.shape[1] != n_surv:
+            raise ValueError("w must be [n_beams, n_surv]")
+        check(self._L.blah2hip_amb_beamform_dev(self._h, d_map, n_surv, n_cpi, _ptr(w), w.shape[0], d_beam_map,
+                                                d_beam_metrics, stream))
+
+    def snapshot_dev(self, d_map, n_surv, n_cpi, d_dets, cap, d_count, n_lists, d_snap, stream=0):
+        """The ``n_surv`` channel cells under every record of ``n_lists`` detection lists (blah2hip_amb_snapshot_dev; raw
+        pointers/ints): ``d_snap`` is complex64 ``[n_lists][cap][n_surv]``, list l reads the channel maps of CPI
+        ``l % n_cpi``."""
+        check(self._L.blah2hip_amb_snapshot_dev(self._h, d_map, n_surv, n_cpi, d_dets, cap, d_count, n_lists, d_snap, stream))
+
+    def beamform(self, maps, w):
+        """Host arrays, one CPI: the channel maps ``maps`` (:class:`Map` or complex64 ``[n_doppler, n_delay]`` arrays, one per
+        channel) combined with ``w`` (complex ``[n_beams, n_surv]``); uploads, runs ``beamform_dev`` and returns one
+        :class:`Map` per beam with its metrics."""
+        data = np.stack([np.ascontiguousarray(getattr(m, "data", m), dtype=np.complex64) for m in maps])
+        w = np.ascontiguousarray(w, dtype=np.complex64)
+        nD, nC = self.dims.n_doppler_bins, self.dims.n_delay_bins
+        if data.shape[1:] != (nD, nC):
+            raise ValueError(f"maps must be [{nD}, {nC}]")
+        out = np.empty((w.shape[0], nD, nC), dtype=np.complex64)
+        met = np.zeros((w.shape[0], 2), dtype=np.float64)
+        L, ctx = self._L, C.c_void_p()
+        check(L.blah2hip_ctx_create(self.device, C.byref(ctx)))
+        bufs = []
+        try:
+            for nbytes in (data.nbytes, out.nbytes, met.nbytes):
+                p = C.c_void_p()
+                check(L.blah2hip_ctx_malloc(ctx, nbytes, C.byref(p)))
+                bufs.append(p)
+            d_in, d_out, d_met = bufs
+            check(L.blah2hip_ctx_h2d(ctx, d_in, _ptr(data), data.nbytes))
+            self.beamform_dev(d_in, data.shape[0], 1, w, d_out, d_met, L.blah2hip_ctx_stream(ctx))
+            check(L.blah2hip_ctx_d2h(ctx, _ptr(out), d_out, out.nbytes))
+            check(L.blah2hip_ctx_d2h(ctx, _ptr(met), d_met, met.nbytes))
+            check(L.blah2hip_ctx_sync(ctx))
+        finally:
+            for p in bufs:
+                L.blah2hip_ctx_free(ctx, p)
+            L.blah2hip_ctx_destroy(ctx)
+        # (a beam map is not the engine's device copy: no owner, so a detector uploads it)
+        return [Map(None, out[b], self.delay.copy(), self.doppler.copy(), float(met[b, 0]), float(met[b, 1]), b)
+                for b in range(w.shape[0])]
 
     def set_multi_surv_range(self, mode):
         """BLAH2HIP_OPT_MULTI_SURV_RANGE: "auto", "shared" (the shared-reference range kernel) or "per_channel"."""

@@ -293,6 +293,40 @@ int blah2hip_amb_read_last(blah2hip_amb_t h, uint32_t cpi, float *map_out, doubl
 int blah2hip_amb_db_dev(blah2hip_amb_t h, const void *d_map, const double *d_metrics, uint32_t n_cpi,
                         float *d_db, void *stream);
 
+/* ---- the surveillance channels as ONE array (no reference counterpart) -----
+ * Beams in the map domain.  The cross-ambiguity map is linear in the surveillance channel: the beam
+ * y_b = sum_k w[b][k] y_k has the map M_b = sum_k w[b][k] M_k, so every beam costs one pass over the K maps that
+ * blah2hip_amb_process_multi_dev left in HBM, not a range + Doppler chain.
+ * d_map: [n_surv][n_cpi][n_doppler][n_delay] complex fp32 as that call writes it (NULL = the handle's internal map).
+ * w: HOST array [n_beams][n_surv] of (re, im) fp32 pairs, read at the call and carried in the launch arguments: no upload,
+ * no allocation, no synchronisation; the call enqueues only and can be captured in a graph.
+ * Output, beam-major: d_beam_map [n_beams][n_cpi][n_doppler][n_delay], d_beam_metrics [n_beams][n_cpi][2] (Map::set_metrics of
+ * every beam map, on the cells as written).  Beam b of CPI c is thus VIRTUAL CPI b * n_cpi + c for blah2hip_cfar1d_dev,
+ * blah2hip_cfar2d_dev, blah2hip_detect_dev and blah2hip_amb_db_dev, which are called with n_beams * n_cpi CPIs and these two
+ * buffers.  Under noise a beam map is a complex Gaussian field like a channel map, so the detectors' pfa holds per beam map.
+ * Every cell is accumulated in fp32 in the order k = 0 .. n_surv - 1; a weight of exactly 1 or 0 passes cells through bit for
+ * bit.  One kernel reads the K maps once and writes the n_beams maps once, (n_surv + n_beams) * cells * 8 bytes per CPI; the
+ * metrics are finished by metrics_kernel in index order (no floating-point atomics: two calls give the same bits).  The
+ * per-workgroup partials live in the handle's buffers, so calls on one handle must be ordered on the device.
+ * BLAH2HIP_ERR_INVALID, with nothing enqueued: n_surv outside [1, BLAH2HIP_MAX_SURV], n_beams outside
+ * [1, BLAH2HIP_MAX_BEAMS], n_cpi == 0, n_surv * n_cpi or n_beams * n_cpi above max_batch, a NULL w or output, an output
+ * that overlaps the input maps (the handle's internal map when d_map is NULL). */
+#define BLAH2HIP_MAX_BEAMS 8
+int blah2hip_amb_beamform_dev(blah2hip_amb_t h, const void *d_map, uint32_t n_surv, uint32_t n_cpi,
+                              const float *w, uint32_t n_beams,
+                              void *d_beam_map, double *d_beam_metrics, void *stream);
+/* The array snapshot under every detection: d_snap[l][i][k] = cell (row_i, col_i) of CHANNEL map k of CPI l mod n_cpi, complex
+ * fp32, shape [n_lists][cap][n_surv] (re, im) -- what phase differences, a Bartlett or MUSIC bearing or a monopulse ratio are
+ * computed from without downloading K maps.  d_dets [n_lists][cap] and d_count [n_lists] as blah2hip_detect_dev leaves them
+ * (a count beyond cap: cap records).  List l belongs to CPI l mod n_cpi: the lists of n_beams * n_cpi beam maps and of
+ * n_surv * n_cpi channel maps (virtual CPIs) both fit.  d_map as above (NULL = the handle's internal map).  Slots beyond a
+ * list's count and records whose row or col lies outside the map are left unwritten.  Enqueues ONE kernel.
+ * BLAH2HIP_ERR_INVALID: a NULL list / count / output, cap == 0, n_cpi == 0, n_lists == 0 or not a multiple of n_cpi, n_surv
+ * outside [1, BLAH2HIP_MAX_SURV], n_surv * n_cpi above max_batch. */
+int blah2hip_amb_snapshot_dev(blah2hip_amb_t h, const void *d_map, uint32_t n_surv, uint32_t n_cpi,
+                              const blah2hip_det_t *d_dets, uint32_t cap, const uint32_t *d_count, uint32_t n_lists,
+                              float *d_snap, void *stream);
+
 /* ---- CfarDetector1D (CfarDetector1D.h:46-55) ---------------------------- */
 /* dev: d_map/d_metrics as written by blah2hip_amb_process_dev (NULL = the
  * handle's internal buffers).  d_hits: [n_cpi][cap]; d_count: [n_cpi], zeroed
@@ -587,6 +621,7 @@ int blah2hip_amb_result_ptrs(blah2hip_amb_t h, const void **d_map, const double 
 #define BLAH2HIP_K_SAT_ROWS 4 /* 2-D CFAR through the summed-area table (large windows): row prefix sums */
 #define BLAH2HIP_K_SAT_COLS 5 /* ... column prefix sums */
 #define BLAH2HIP_K_ROTATE 6   /* Doppler-centre shift (asymmetric limits only) */
+#define BLAH2HIP_K_BEAM 7     /* beamform_kernel (blah2hip_amb_beamform_dev; its metrics_kernel counts under _METRICS) */
 #define BLAH2HIP_K_COUNT 8
 /* enable != 0: every dev call brackets each kernel with hipEvents */
 int blah2hip_amb_set_timing(blah2hip_amb_t h, int enable);
