@@ -15,9 +15,9 @@ LIB_PATH = os.path.join(PKG, "libblah2hip.so")
 OK = 0
 ERR_INVALID, ERR_HIP, ERR_UNSUPPORTED, ERR_UNDERFLOW, ERR_NO_DEVICE, ERR_CAPACITY = -1, -2, -3, -4, -5, -6
 FMT_C32, FMT_I16, FMT_F16, FMT_I16X_C32Y, FMT_I8, FMT_I8X_C32Y = 0, 1, 2, 3, 4, 5
-K_RANGE, K_DOPPLER, K_METRICS, K_CFAR, K_SAT_ROWS, K_SAT_COLS, K_ROTATE, K_BEAM, K_COUNT = 0, 1, 2, 3, 4, 5, 6, 7, 8
+K_RANGE, K_DOPPLER, K_METRICS, K_CFAR, K_SAT_ROWS, K_SAT_COLS, K_ROTATE, K_BEAM, K_COV, K_COUNT = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
 KERNEL_NAMES = {K_RANGE: "range", K_DOPPLER: "doppler", K_METRICS: "metrics", K_CFAR: "cfar",
-                K_SAT_ROWS: "sat_rows", K_SAT_COLS: "sat_cols", K_ROTATE: "rotate", K_BEAM: "beam"}
+                K_SAT_ROWS: "sat_rows", K_SAT_COLS: "sat_cols", K_ROTATE: "rotate", K_BEAM: "beam", K_COV: "cov"}
 CK_CORR, CK_REDUCE, CK_SOLVE, CK_FIR, CK_COUNT = 0, 1, 2, 3, 4
 CLUTTER_KERNEL_NAMES = {CK_CORR: "clutter_corr", CK_REDUCE: "clutter_reduce", CK_SOLVE: "clutter_solve",
                         CK_FIR: "clutter_fir"}
@@ -96,6 +96,9 @@ SYMBOLS = {
     "blah2hip_amb_read_last": (C.c_int, [_vp, _u32, _vp, _vp]),
     "blah2hip_amb_db_dev": (C.c_int, [_vp, _vp, _vp, _u32, _vp, _vp]),
     "blah2hip_amb_beamform_dev": (C.c_int, [_vp, _vp, _u32, _u32, _vp, _u32, _vp, _vp, _vp]),
+    "blah2hip_amb_beamform_wdev": (C.c_int, [_vp, _vp, _u32, _u32, _vp, _u32, _vp, _vp, _vp]),
+    "blah2hip_amb_covariance_dev": (C.c_int, [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _vp]),
+    "blah2hip_amb_mvdr_weights_dev": (C.c_int, [_vp, _vp, _u32, _u32, _vp, _u32, _dbl, _vp, _vp, _vp]),
     "blah2hip_amb_snapshot_dev": (C.c_int, [_vp, _vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _vp]),
     "blah2hip_cfar1d_dev": (C.c_int, [_vp, _vp, _vp, _u32, _dbl, _i32, _i32, _i32, _dbl, _vp, _u32, _vp, _vp]),
     "blah2hip_cfar1d_prepare": (C.c_int, [_vp, _dbl, _i32]),

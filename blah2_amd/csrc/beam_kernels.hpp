@@ -4,6 +4,9 @@
 //   beamform_kernel    M_b = sum_k w[b][k] M_k for every beam b in ONE pass over the K channel maps, with the
 //                      per-workgroup partials of Map::set_metrics (Map.cpp:187-206) of every beam map
 //   snapshot_kernel    the K channel cells under every detection of a list (what a bearing is computed from)
+//   array_cov_kernel   the K x K array covariance of the channel maps over a training rectangle, per CPI, in fp64
+//   cov_fold_kernel    ... its per-workgroup partials folded in index order into the Hermitian matrix
+//   mvdr_weights_kernel  minimum-variance (Capon) weights from that covariance: an fp64 Cholesky solve per CPI and beam
 //
 // The cross-ambiguity map is linear in the surveillance channel, so the map of the beam y_b = sum_k w[b][k] y_k is the
 // same combination of the channel maps blah2hip_amb_process_multi_dev left in HBM: a further beam costs one more map
@@ -33,10 +36,13 @@ template <> struct BeamVec<2> { typedef float type __attribute__((ext_vector_typ
 // V adjacent cells from cell i of the CPI on: the K loads first (all in flight together), then beam after beam.  The
 // beam loop is unrolled to its limit behind a wave-uniform test so that weights and partials are statically indexed.
 // Per component the sum is a chain of fused multiply-adds in the order k = 0 .. K-1: 2K roundings, each at most 2^-24
-// of sum_k |w_k| |M_k|; a weight of exactly 1 or 0 passes a cell through bit for bit.
-template <int K, int V>
-__device__ __forceinline__ void beam_cells(const BeamArgs &a, const cf *in, cf *out, size_t chStride, size_t i,
-                                           double (&lsum)[BLAH2HIP_MAX_BEAMS], float (&lmax)[BLAH2HIP_MAX_BEAMS])
+// of sum_k |w_k| |M_k|; a weight of exactly 1 or 0 passes a cell through bit for bit.  The weights w[b][k] are the launch
+// arguments' (W = BLAH2HIP_MAX_SURV) or the CPI's own, read from the device up front (W = K): the operations and their
+// order are the same, so equal weights give equal bits.
+template <int K, int V, int W>
+__device__ __forceinline__ void beam_cells(const BeamArgs &a, const cf (&wts)[BLAH2HIP_MAX_BEAMS][W], const cf *in, cf *out,
+                                           size_t chStride, size_t i, double (&lsum)[BLAH2HIP_MAX_BEAMS],
+                                           float (&lmax)[BLAH2HIP_MAX_BEAMS])
 {
   typedef typename BeamVec<V>::type vec;
   vec m[K];
@@ -51,7 +57,7 @@ __device__ __forceinline__ void beam_cells(const BeamArgs &a, const cf *in, cf *
         float re = 0.f, im = 0.f;
 #pragma unroll
         for (int k = 0; k < K; k++) {
-          const cf w = a.w[b][k];
+          const cf w = wts[b][k];
           const float mx = m[k][2 * v], my = m[k][2 * v + 1];
           re = fmaf(-w.y, my, k ? fmaf(w.x, mx, re) : w.x * mx);
           im = fmaf(w.y, mx, k ? fmaf(w.x, my, im) : w.x * my);
@@ -71,8 +77,8 @@ __device__ __forceinline__ void beam_cells(const BeamArgs &a, const cf *in, cf *
 // every channel's and every beam's copy of a CPI to start at the same offset modulo 16 bytes (the host checks it): a CPI
 // that starts 8 bytes off -- every odd one of a map with an odd cell count -- then has a one-cell head, and whatever is
 // left behind the last pair is a one-cell tail; both go through 8-byte accesses in workgroup 0.  V = 1 otherwise.
-template <int K, int V>
-__global__ __launch_bounds__(256) void beamform_kernel(BeamArgs a)
+template <int K, int V, int W>
+__device__ __forceinline__ void beam_run(const BeamArgs &a, const cf (&wts)[BLAH2HIP_MAX_BEAMS][W])
 {
   const uint32_t cpi = blockIdx.y;
   const size_t cells = a.cells;
@@ -87,10 +93,10 @@ __global__ __launch_bounds__(256) void beamform_kernel(BeamArgs a)
   const size_t head = V == 2 ? (size_t)(((uintptr_t)in >> 3) & 1) : 0;
   const size_t nUnits = (cells - head) / V;
   for (size_t u = (size_t)blockIdx.x * 256 + threadIdx.x; u < nUnits; u += (size_t)gridDim.x * 256)
-    beam_cells<K, V>(a, in, out, chStride, head + u * V, lsum, lmax);
+    beam_cells<K, V>(a, wts, in, out, chStride, head + u * V, lsum, lmax);
   if (V == 2 && blockIdx.x == 0) {
     const size_t nLeft = head + ((cells - head) & 1);
-    if (threadIdx.x < nLeft) beam_cells<K, 1>(a, in, out, chStride, (threadIdx.x == 0 && head) ? 0 : cells - 1, lsum, lmax);
+    if (threadIdx.x < nLeft) beam_cells<K, 1>(a, wts, in, out, chStride, (threadIdx.x == 0 && head) ? 0 : cells - 1, lsum, lmax);
   }
 
   // one (sum, max) partial per workgroup and beam; metrics_kernel folds them in index order
@@ -104,19 +110,42 @@ __global__ __launch_bounds__(256) void beamform_kernel(BeamArgs a)
   }
 }
 
-// beamform_kernel<K, V> for the call's channel count, 16-byte (V = 2) or 8-byte (V = 1) accesses
-template <int V> inline void launch_beamform(uint32_t K, dim3 grid, hipStream_t st, const BeamArgs &a)
+// one set of weights for every CPI, in the launch arguments (blah2hip_amb_beamform_dev)
+template <int K, int V>
+__global__ __launch_bounds__(256) void beamform_kernel(BeamArgs a)
 {
-  switch (K) {
-  case 1: hipLaunchKernelGGL((beamform_kernel<1, V>), grid, dim3(256), 0, st, a); break;
-  case 2: hipLaunchKernelGGL((beamform_kernel<2, V>), grid, dim3(256), 0, st, a); break;
-  case 3: hipLaunchKernelGGL((beamform_kernel<3, V>), grid, dim3(256), 0, st, a); break;
-  case 4: hipLaunchKernelGGL((beamform_kernel<4, V>), grid, dim3(256), 0, st, a); break;
-  case 5: hipLaunchKernelGGL((beamform_kernel<5, V>), grid, dim3(256), 0, st, a); break;
-  case 6: hipLaunchKernelGGL((beamform_kernel<6, V>), grid, dim3(256), 0, st, a); break;
-  case 7: hipLaunchKernelGGL((beamform_kernel<7, V>), grid, dim3(256), 0, st, a); break;
-  default: hipLaunchKernelGGL((beamform_kernel<8, V>), grid, dim3(256), 0, st, a); break;
+  beam_run<K, V>(a, a.w);
+}
+
+// the CPI's own weights wdev[cpi][b][k] on the device (blah2hip_amb_beamform_wdev; a.w is unused): blockIdx.y is the CPI, so
+// they are uniform over the workgroup and read once, before the first cell
+template <int K, int V>
+__global__ __launch_bounds__(256) void beamform_wdev_kernel(BeamArgs a, const cf *wdev)
+{
+  cf wts[BLAH2HIP_MAX_BEAMS][K];
+  const cf *wd = wdev + (size_t)blockIdx.y * a.nBeams * K;
+#pragma unroll
+  for (int b = 0; b < BLAH2HIP_MAX_BEAMS; b++) {
+#pragma unroll
+    for (int k = 0; k < K; k++) wts[b][k] = b < (int)a.nBeams ? wd[b * K + k] : cmake(0.f, 0.f);
   }
+  beam_run<K, V>(a, wts);
+}
+
+// beamform_kernel<K, V> (or beamform_wdev_kernel<K, V>) for the call's channel count, 16-byte (V = 2) or 8-byte (V = 1)
+// accesses
+template <int V, bool WDEV> inline void launch_beamform(uint32_t K, dim3 grid, hipStream_t st, const BeamArgs &a, const cf *wdev)
+{
+#define BLAH2_BEAM_CASE(k)                                                                    \
+  case k:                                                                                     \
+    if (WDEV) hipLaunchKernelGGL((beamform_wdev_kernel<k, V>), grid, dim3(256), 0, st, a, wdev); \
+    else hipLaunchKernelGGL((beamform_kernel<k, V>), grid, dim3(256), 0, st, a);              \
+    break;
+  switch (K) {
+    BLAH2_BEAM_CASE(1) BLAH2_BEAM_CASE(2) BLAH2_BEAM_CASE(3) BLAH2_BEAM_CASE(4)
+    BLAH2_BEAM_CASE(5) BLAH2_BEAM_CASE(6) BLAH2_BEAM_CASE(7) BLAH2_BEAM_CASE(8)
+  }
+#undef BLAH2_BEAM_CASE
 }
 
 struct SnapArgs {
@@ -141,6 +170,219 @@ __global__ __launch_bounds__(256) void snapshot_kernel(SnapArgs a)
     if (row < 0 || row >= a.nD || col < 0 || col >= a.nDelay) continue;
     const cf *z = a.map + (l % a.nCpi) * cells + (size_t)row * a.nDelay + col;
     for (uint32_t k = 0; k < a.nSurv; k++) a.snap[t * a.nSurv + k] = z[(size_t)k * a.nCpi * cells];
+  }
+}
+
+// ---- adaptive beams: array covariance and minimum-variance weights -----------------------------------------------------
+struct CovArgs {
+  const cf *in;    // [K][nCpi][nD][nDelay]
+  double *part;    // [nCpi][gridDim.x][K * K] per-workgroup partials, packed as below
+  size_t chStride; // nCpi * nD * nDelay
+  uint32_t cells, nDelay;
+  uint32_t row0, col0, nRows, width; // the training rectangle
+};
+
+// R[c][i][j] = sum over the rectangle of M_i conj(M_j), per CPI c.  grid (G, nCpi), 256 threads.  A thread walks the
+// rectangle's cells t = r * width + q with a stride of gridDim.x * 256 (row and column are carried along, no division in
+// the loop), loads the K channel cells first (8-byte loads, all in flight together) and then updates the upper triangle:
+// K real sums for the diagonal and K (K - 1) / 2 complex ones above it, K * K fp64 accumulators (128 VGPRs at K = 8).
+// A product of two fp32 values is exact in fp64, so every accumulator update is one fp64 fused multiply-add: no fp32
+// rounding at all, every addition fp64 -- inside the arithmetic contract of blah2hip_amb_covariance_dev, whose bound
+// allows fp32 products.  The K * K sums are packed into one K x K array of doubles: [i][j] with i <= j holds
+// Re R[i][j], [j][i] with i < j holds Im R[i][j].  The workgroup's partial is the lanes' sums folded by a butterfly, then
+// the four waves' in order; cov_fold_kernel adds the partials in index order.  No floating-point atomics.
+template <int K>
+__global__ __launch_bounds__(256) void array_cov_kernel(CovArgs a)
+{
+  __shared__ double wpart[4][K * K];
+  const uint32_t cpi = blockIdx.y;
+  const cf *in = a.in + (size_t)cpi * a.cells + (size_t)a.row0 * a.nDelay + a.col0;
+  double acc[K * K];
+#pragma unroll
+  for (int e = 0; e < K * K; e++) acc[e] = 0.0;
+
+  const uint64_t n = (uint64_t)a.nRows * a.width;
+  const uint64_t stride = (uint64_t)gridDim.x * 256;
+  const uint32_t dr = (uint32_t)(stride / a.width), dq = (uint32_t)(stride % a.width);
+  uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  uint32_t r = (uint32_t)(t / a.width), q = (uint32_t)(t % a.width);
+  for (; t < n; t += stride) {
+    const cf *p = in + (size_t)r * a.nDelay + q;
+    cf m[K];
+#pragma unroll
+    for (int k = 0; k < K; k++) m[k] = p[k * a.chStride];
+    double x[K], y[K];
+#pragma unroll
+    for (int k = 0; k < K; k++) { x[k] = (double)m[k].x; y[k] = (double)m[k].y; }
+#pragma unroll
+    for (int i = 0; i < K; i++) {
+      acc[i * K + i] = fma(y[i], y[i], fma(x[i], x[i], acc[i * K + i]));
+#pragma unroll
+      for (int j = i + 1; j < K; j++) {
+        acc[i * K + j] = fma(y[i], y[j], fma(x[i], x[j], acc[i * K + j]));  // Re M_i conj(M_j)
+        acc[j * K + i] = fma(-x[i], y[j], fma(y[i], x[j], acc[j * K + i])); // Im M_i conj(M_j)
+      }
+    }
+    r += dr;
+    q += dq;
+    if (q >= a.width) { q -= a.width; r++; }
+  }
+
+#pragma unroll
+  for (int e = 0; e < K * K; e++) {
+    double v = acc[e];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    if ((threadIdx.x & 63) == 0) wpart[threadIdx.x >> 6][e] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < K * K) {
+    const int e = threadIdx.x;
+    a.part[((size_t)cpi * gridDim.x + blockIdx.x) * (K * K) + e] = ((wpart[0][e] + wpart[1][e]) + wpart[2][e]) + wpart[3][e];
+  }
+}
+
+inline void launch_array_cov(uint32_t K, dim3 grid, hipStream_t st, const CovArgs &a)
+{
+  switch (K) {
+  case 1: hipLaunchKernelGGL((array_cov_kernel<1>), grid, dim3(256), 0, st, a); break;
+  case 2: hipLaunchKernelGGL((array_cov_kernel<2>), grid, dim3(256), 0, st, a); break;
+  case 3: hipLaunchKernelGGL((array_cov_kernel<3>), grid, dim3(256), 0, st, a); break;
+  case 4: hipLaunchKernelGGL((array_cov_kernel<4>), grid, dim3(256), 0, st, a); break;
+  case 5: hipLaunchKernelGGL((array_cov_kernel<5>), grid, dim3(256), 0, st, a); break;
+  case 6: hipLaunchKernelGGL((array_cov_kernel<6>), grid, dim3(256), 0, st, a); break;
+  case 7: hipLaunchKernelGGL((array_cov_kernel<7>), grid, dim3(256), 0, st, a); break;
+  case 8: hipLaunchKernelGGL((array_cov_kernel<8>), grid, dim3(256), 0, st, a); break;
+  }
+}
+
+// grid (nCpi), 64 threads: thread e < K * K adds entry e of the CPI's nParts partials in index order, then the packed sums
+// become cov[c][i][j] (re, im): both triangles, R[j][i] the exact conjugate of R[i][j], the diagonal's imaginary part 0.
+__global__ __launch_bounds__(64) void cov_fold_kernel(const double *part, uint32_t nParts, uint32_t K, double *cov)
+{
+  __shared__ double s[BLAH2HIP_MAX_SURV * BLAH2HIP_MAX_SURV];
+  const uint32_t cpi = blockIdx.x, e = threadIdx.x, KK = K * K;
+  if (e < KK) {
+    double v = 0.0;
+    for (uint32_t g = 0; g < nParts; g++) v += part[((size_t)cpi * nParts + g) * KK + e];
+    s[e] = v;
+  }
+  __syncthreads();
+  if (e < KK) {
+    const uint32_t i = e / K, j = e % K;
+    double *o = cov + 2 * ((size_t)cpi * KK + e);
+    if (i == j) { o[0] = s[e]; o[1] = 0.0; }
+    else if (i < j) { o[0] = s[i * K + j]; o[1] = s[j * K + i]; }
+    else { o[0] = s[j * K + i]; o[1] = -s[i * K + j]; }
+  }
+}
+
+struct MvdrArgs {
+  const double *cov; // [nCpi][K][K] (re, im)
+  cf *w;             // [nCpi][nBeams][K]
+  int32_t *ok;       // [nCpi] or nullptr
+  double loading;
+  uint32_t nBeams;
+  cf steer[BLAH2HIP_MAX_BEAMS][BLAH2HIP_MAX_SURV]; // in the launch arguments
+};
+
+// grid (nCpi), 64 threads: thread b < nBeams computes beam b of its CPI, everything in fp64 registers (K is a template
+// parameter, every loop unrolled).  R_l = R + loading (tr R / K) I from the lower triangle of cov; Cholesky R_l = L L^H;
+// L y = a, L^H x = y; h = x / (a^H x) with a^H x = y^H y; w = conj(h) rounded to fp32.  A pivot that is not finite or
+// not positive (an all-zero CPI, a NaN anywhere in the triangle reaches a pivot) fails the CPI: ok = 0 and the
+// conventional conj(a) / (a^H a).  Every thread of a CPI factorises the same matrix the same way (K <= 8: cheaper than
+// sharing the factor), so they agree on ok.
+template <int K>
+__global__ __launch_bounds__(64) void mvdr_weights_kernel(MvdrArgs a)
+{
+  const uint32_t cpi = blockIdx.x, b = threadIdx.x;
+  if (b >= a.nBeams) return;
+  const double *R = a.cov + 2 * (size_t)cpi * K * K;
+  double lr[K][K], li[K][K]; // lower triangle: R_l, overwritten by L
+  double tr = 0.0;
+#pragma unroll
+  for (int i = 0; i < K; i++) {
+#pragma unroll
+    for (int j = 0; j <= i; j++) { lr[i][j] = R[2 * (i * K + j)]; li[i][j] = R[2 * (i * K + j) + 1]; }
+    tr += lr[i][i];
+  }
+  const double delta = a.loading * (tr / K);
+  bool good = true;
+#pragma unroll
+  for (int j = 0; j < K; j++) {
+    double d = lr[j][j] + delta;
+#pragma unroll
+    for (int p = 0; p < j; p++) d -= lr[j][p] * lr[j][p] + li[j][p] * li[j][p];
+    if (!(d > 0.0) || !(d < __builtin_huge_val())) good = false;
+    const double piv = sqrt(d), inv = 1.0 / piv;
+    lr[j][j] = piv;
+#pragma unroll
+    for (int i = j + 1; i < K; i++) {
+      double sr = lr[i][j], si = li[i][j];
+#pragma unroll
+      for (int p = 0; p < j; p++) { // - L[i][p] conj(L[j][p])
+        sr -= lr[i][p] * lr[j][p] + li[i][p] * li[j][p];
+        si -= li[i][p] * lr[j][p] - lr[i][p] * li[j][p];
+      }
+      lr[i][j] = sr * inv;
+      li[i][j] = si * inv;
+    }
+  }
+  double ar[K], ai[K];
+#pragma unroll
+  for (int k = 0; k < K; k++) { ar[k] = (double)a.steer[b][k].x; ai[k] = (double)a.steer[b][k].y; }
+  double hr[K], hi[K];
+  if (good) {
+    double yr[K], yi[K], den = 0.0;
+#pragma unroll
+    for (int i = 0; i < K; i++) { // L y = a
+      double sr = ar[i], si = ai[i];
+#pragma unroll
+      for (int p = 0; p < i; p++) {
+        sr -= lr[i][p] * yr[p] - li[i][p] * yi[p];
+        si -= lr[i][p] * yi[p] + li[i][p] * yr[p];
+      }
+      yr[i] = sr / lr[i][i];
+      yi[i] = si / lr[i][i];
+      den += yr[i] * yr[i] + yi[i] * yi[i];
+    }
+#pragma unroll
+    for (int i = K - 1; i >= 0; i--) { // L^H x = y
+      double sr = yr[i], si = yi[i];
+#pragma unroll
+      for (int p = i + 1; p < K; p++) { // - conj(L[p][i]) x[p]
+        sr -= lr[p][i] * hr[p] + li[p][i] * hi[p];
+        si -= lr[p][i] * hi[p] - li[p][i] * hr[p];
+      }
+      hr[i] = sr / lr[i][i];
+      hi[i] = si / lr[i][i];
+    }
+#pragma unroll
+    for (int k = 0; k < K; k++) { hr[k] /= den; hi[k] /= den; }
+  } else {
+    double den = 0.0;
+#pragma unroll
+    for (int k = 0; k < K; k++) den += ar[k] * ar[k] + ai[k] * ai[k];
+#pragma unroll
+    for (int k = 0; k < K; k++) { hr[k] = ar[k] / den; hi[k] = ai[k] / den; }
+  }
+  cf *w = a.w + ((size_t)cpi * a.nBeams + b) * K;
+#pragma unroll
+  for (int k = 0; k < K; k++) w[k] = cmake((float)hr[k], (float)-hi[k]);
+  if (b == 0 && a.ok) a.ok[cpi] = good ? 1 : 0;
+}
+
+inline void launch_mvdr_weights(uint32_t K, uint32_t nCpi, hipStream_t st, const MvdrArgs &a)
+{
+  switch (K) {
+  case 1: hipLaunchKernelGGL((mvdr_weights_kernel<1>), dim3(nCpi), dim3(64), 0, st, a); break;
+  case 2: hipLaunchKernelGGL((mvdr_weights_kernel<2>), dim3(nCpi), dim3(64), 0, st, a); break;
+  case 3: hipLaunchKernelGGL((mvdr_weights_kernel<3>), dim3(nCpi), dim3(64), 0, st, a); break;
+  case 4: hipLaunchKernelGGL((mvdr_weights_kernel<4>), dim3(nCpi), dim3(64), 0, st, a); break;
+  case 5: hipLaunchKernelGGL((mvdr_weights_kernel<5>), dim3(nCpi), dim3(64), 0, st, a); break;
+  case 6: hipLaunchKernelGGL((mvdr_weights_kernel<6>), dim3(nCpi), dim3(64), 0, st, a); break;
+  case 7: hipLaunchKernelGGL((mvdr_weights_kernel<7>), dim3(nCpi), dim3(64), 0, st, a); break;
+  case 8: hipLaunchKernelGGL((mvdr_weights_kernel<8>), dim3(nCpi), dim3(64), 0, st, a); break;
   }
 }
 

@@ -1934,8 +1934,9 @@ static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
   return a0 < b0 + nb && b0 < a0 + na;
 }
 
-int blah2hip_amb_beamform_dev(blah2hip_amb_t h, const void *d_map, uint32_t n_surv, uint32_t n_cpi, const float *w,
-                              uint32_t n_beams, void *d_beam_map, double *d_beam_metrics, void *stream)
+// blah2hip_amb_beamform_dev (w: the host's one set of weights) and blah2hip_amb_beamform_wdev (d_w: a set per CPI on the device)
+static int beamform_enqueue(blah2hip_amb_t h, const void *d_map, uint32_t n_surv, uint32_t n_cpi, const float *w, const float *d_w,
+                            uint32_t n_beams, void *d_beam_map, double *d_beam_metrics, void *stream)
 {
   if (!h) return fail(BLAH2HIP_ERR_INVALID, "NULL handle");
   if (n_surv == 0 || n_surv > BLAH2HIP_MAX_SURV) return fail(BLAH2HIP_ERR_INVALID, "n_surv outside [1, BLAH2HIP_MAX_SURV]");
@@ -1943,7 +1944,7 @@ int blah2hip_amb_beamform_dev(blah2hip_amb_t h, const void *d_map, uint32_t n_su
   if (n_cpi == 0) return fail(BLAH2HIP_ERR_INVALID, "n_cpi is 0");
   if ((uint64_t)n_surv * n_cpi > h->dims.max_batch) return fail(BLAH2HIP_ERR_INVALID, "n_surv * n_cpi above max_batch");
   if ((uint64_t)n_beams * n_cpi > h->dims.max_batch) return fail(BLAH2HIP_ERR_INVALID, "n_beams * n_cpi above max_batch");
-  if (!w || !d_beam_map || !d_beam_metrics) return fail(BLAH2HIP_ERR_INVALID, "NULL weights or output");
+  if ((!w && !d_w) || !d_beam_map || !d_beam_metrics) return fail(BLAH2HIP_ERR_INVALID, "NULL weights or output");
   const size_t cells = (size_t)h->dims.n_doppler_bins * h->dims.n_delay_bins;
   const cf *in = d_map ? (const cf *)d_map : h->d_map;
   const size_t inBytes = (size_t)n_surv * n_cpi * cells * sizeof(cf);
@@ -1962,8 +1963,9 @@ int blah2hip_amb_beamform_dev(blah2hip_amb_t h, const void *d_map, uint32_t n_su
   a.nCpi = n_cpi;
   a.nBeams = n_beams;
   memset(a.w, 0, sizeof(a.w));
-  for (uint32_t b = 0; b < n_beams; b++)
-    for (uint32_t k = 0; k < n_surv; k++) a.w[b][k] = cmake(w[2 * (b * n_surv + k)], w[2 * (b * n_surv + k) + 1]);
+  if (!d_w)
+    for (uint32_t b = 0; b < n_beams; b++)
+      for (uint32_t k = 0; k < n_surv; k++) a.w[b][k] = cmake(w[2 * (b * n_surv + k)], w[2 * (b * n_surv + k) + 1]);
   // 16-byte accesses where CPI c starts at the same offset modulo 16 bytes in every channel's and every beam's block: the
   // blocks are n_cpi * cells cells apart, so an odd product (odd cell count, odd n_cpi) with more than one block does not
   const bool oddBlock = ((size_t)n_cpi * cells) & 1;
@@ -1976,8 +1978,13 @@ int blah2hip_amb_beamform_dev(blah2hip_amb_t h, const void *d_map, uint32_t n_su
   const uint32_t G = std::max(1u, std::min(gMax, (8u * (uint32_t)h->numCU + n_cpi - 1) / n_cpi));
   int rc;
   if ((rc = tic(h, BLAH2HIP_K_BEAM, st))) return rc;
-  if (wide) launch_beamform<2>(n_surv, dim3(G, n_cpi), st, a);
-  else launch_beamform<1>(n_surv, dim3(G, n_cpi), st, a);
+  if (d_w) {
+    if (wide) launch_beamform<2, true>(n_surv, dim3(G, n_cpi), st, a, (const cf *)d_w);
+    else launch_beamform<1, true>(n_surv, dim3(G, n_cpi), st, a, (const cf *)d_w);
+  } else {
+    if (wide) launch_beamform<2, false>(n_surv, dim3(G, n_cpi), st, a, nullptr);
+    else launch_beamform<1, false>(n_surv, dim3(G, n_cpi), st, a, nullptr);
+  }
   HIPCHK(hipGetLastError());
   if ((rc = toc(h, BLAH2HIP_K_BEAM, st))) return rc;
   if ((rc = tic(h, BLAH2HIP_K_METRICS, st))) return rc;
@@ -1985,6 +1992,90 @@ int blah2hip_amb_beamform_dev(blah2hip_amb_t h, const void *d_map, uint32_t n_su
                      (double)cells, d_beam_metrics);
   HIPCHK(hipGetLastError());
   return toc(h, BLAH2HIP_K_METRICS, st);
+}
+
+int blah2hip_amb_beamform_dev(blah2hip_amb_t h, const void *d_map, uint32_t n_surv, uint32_t n_cpi, const float *w,
+                              uint32_t n_beams, void *d_beam_map, double *d_beam_metrics, void *stream)
+{
+  return beamform_enqueue(h, d_map, n_surv, n_cpi, w, nullptr, n_beams, d_beam_map, d_beam_metrics, stream);
+}
+
+int blah2hip_amb_beamform_wdev(blah2hip_amb_t h, const void *d_map, uint32_t n_surv, uint32_t n_cpi, const float *d_w,
+                               uint32_t n_beams, void *d_beam_map, double *d_beam_metrics, void *stream)
+{
+  return beamform_enqueue(h, d_map, n_surv, n_cpi, nullptr, d_w, n_beams, d_beam_map, d_beam_metrics, stream);
+}
+
+// ------------------------------------------------------- adaptive beams --
+int blah2hip_amb_covariance_dev(blah2hip_amb_t h, const void *d_map, uint32_t n_surv, uint32_t n_cpi, uint32_t row0, uint32_t row1,
+                                uint32_t col0, uint32_t col1, double *d_cov, void *stream)
+{
+  if (!h || !d_cov) return fail(BLAH2HIP_ERR_INVALID, "NULL handle or output");
+  if (n_surv == 0 || n_surv > BLAH2HIP_MAX_SURV) return fail(BLAH2HIP_ERR_INVALID, "n_surv outside [1, BLAH2HIP_MAX_SURV]");
+  if (n_cpi == 0) return fail(BLAH2HIP_ERR_INVALID, "n_cpi is 0");
+  if ((uint64_t)n_surv * n_cpi > h->dims.max_batch) return fail(BLAH2HIP_ERR_INVALID, "n_surv * n_cpi above max_batch");
+  const uint32_t nD = h->dims.n_doppler_bins, nDelay = h->dims.n_delay_bins;
+  if (row0 >= row1 || row1 > nD || col0 >= col1 || col1 > nDelay)
+    return fail(BLAH2HIP_ERR_INVALID, "covariance: the training rectangle is empty or leaves the map");
+  const size_t cells = (size_t)nD * nDelay;
+  const cf *in = d_map ? (const cf *)d_map : h->d_map;
+  const size_t KK = (size_t)n_surv * n_surv;
+  if (ranges_overlap(in, (size_t)n_surv * n_cpi * cells * sizeof(cf), d_cov, (size_t)n_cpi * KK * 2 * sizeof(double)))
+    return fail(BLAH2HIP_ERR_INVALID, "covariance: the output overlaps the input maps");
+  HIPCHK(hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+
+  CovArgs a;
+  a.in = in;
+  a.part = h->d_partSum;
+  a.chStride = (size_t)n_cpi * cells;
+  a.cells = (uint32_t)cells;
+  a.nDelay = nDelay;
+  a.row0 = row0; a.col0 = col0; a.nRows = row1 - row0; a.width = col1 - col0;
+  // workgroups per CPI: eight a CU over the launch, each with at least one pass of 256 cells, and no more than the
+  // handle's partials hold: n_cpi * G * K^2 doubles in max_batch * nParts (n_surv * n_cpi <= max_batch and nParts >= 128,
+  // so there is room for 16 at the least)
+  const size_t n = (size_t)a.nRows * a.width;
+  const size_t gCap = ((size_t)h->dims.max_batch * h->nParts) / ((size_t)n_cpi * KK);
+  if (gCap == 0) return fail(BLAH2HIP_ERR_INVALID, "covariance: the handle's partials are too small");
+  const uint32_t gMax = (uint32_t)std::min<size_t>(gCap, (n + 255) / 256);
+  const uint32_t G = std::max(1u, std::min(gMax, (8u * (uint32_t)h->numCU + n_cpi - 1) / n_cpi));
+  int rc;
+  if ((rc = tic(h, BLAH2HIP_K_COV, st))) return rc;
+  launch_array_cov(n_surv, dim3(G, n_cpi), st, a);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(cov_fold_kernel, dim3(n_cpi), dim3(64), 0, st, h->d_partSum, G, n_surv, d_cov);
+  HIPCHK(hipGetLastError());
+  return toc(h, BLAH2HIP_K_COV, st);
+}
+
+int blah2hip_amb_mvdr_weights_dev(blah2hip_amb_t h, const double *d_cov, uint32_t n_surv, uint32_t n_cpi, const float *steer,
+                                  uint32_t n_beams, double loading, float *d_w, int32_t *d_ok, void *stream)
+{
+  if (!h || !d_cov || !steer || !d_w) return fail(BLAH2HIP_ERR_INVALID, "NULL argument");
+  if (n_surv == 0 || n_surv > BLAH2HIP_MAX_SURV) return fail(BLAH2HIP_ERR_INVALID, "n_surv outside [1, BLAH2HIP_MAX_SURV]");
+  if (n_beams == 0 || n_beams > BLAH2HIP_MAX_BEAMS) return fail(BLAH2HIP_ERR_INVALID, "n_beams outside [1, BLAH2HIP_MAX_BEAMS]");
+  if (n_cpi == 0) return fail(BLAH2HIP_ERR_INVALID, "n_cpi is 0");
+  if (!(loading >= 0.0) || !std::isfinite(loading)) return fail(BLAH2HIP_ERR_INVALID, "mvdr: loading is negative or not finite");
+  MvdrArgs a;
+  memset(a.steer, 0, sizeof(a.steer));
+  for (uint32_t b = 0; b < n_beams; b++) {
+    bool any = false;
+    for (uint32_t k = 0; k < n_surv; k++) {
+      a.steer[b][k] = cmake(steer[2 * (b * n_surv + k)], steer[2 * (b * n_surv + k) + 1]);
+      any = any || a.steer[b][k].x != 0.f || a.steer[b][k].y != 0.f;
+    }
+    if (!any) return fail(BLAH2HIP_ERR_INVALID, "mvdr: a steering vector is all zero");
+  }
+  HIPCHK(hipSetDevice(h->device));
+  a.cov = d_cov;
+  a.w = (cf *)d_w;
+  a.ok = d_ok;
+  a.loading = loading;
+  a.nBeams = n_beams;
+  launch_mvdr_weights(n_surv, n_cpi, (hipStream_t)stream, a);
+  HIPCHK(hipGetLastError());
+  return BLAH2HIP_OK;
 }
 
 int blah2hip_amb_snapshot_dev(blah2hip_amb_t h, const void *d_map, uint32_t n_surv, uint32_t n_cpi,

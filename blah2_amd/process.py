@@ -32,6 +32,74 @@ def ula_weights(n_surv, spacing_wavelengths, angles_deg):
     return np.exp(-2j * np.pi * float(spacing_wavelengths) * np.sin(theta)[:, None] * k[None, :]) / int(n_surv)
 
 
+def ula_steering(n_surv, spacing_wavelengths, angles_deg):
+    """Steering vectors of the same array, one row per angle: ``a[b][k] = exp(+2j pi k d sin(theta_b))``, complex128
+    ``[n_beams, n_surv]`` -- ``conj(ula_weights) * n_surv``, the ``steer`` of :meth:`Ambiguity.mvdr_weights_dev`.  Pure NumPy."""
+    theta = np.deg2rad(np.atleast_1d(np.asarray(angles_deg, dtype=np.float64)))
+    k = np.arange(int(n_surv), dtype=np.float64)
+    return np.exp(2j * np.pi * float(spacing_wavelengths) * np.sin(theta)[:, None] * k[None, :])
+
+
+def mvdr_weights(R, steer, loading):
+    """blah2hip_amb_mvdr_weights_dev restated in fp64 NumPy.  ``R``: Hermitian ``[..., K, K]`` (the lower triangle is read),
+    ``steer``: ``[n_beams, K]``.  With ``R_l = R + loading (tr R / K) I``: ``h_b = R_l^-1 a_b / (a_b^H R_l^-1 a_b)`` through
+    a Cholesky factorisation, and ``w[..., b, :] = conj(h_b)`` -- the weights of ``beamform_dev`` (``M_b = sum_k w[b][k]
+    M_k``), distortionless: ``w[b] @ a_b = 1``.  Where a pivot is not finite or not positive (a zero matrix, a NaN) ``ok`` is
+    0 and the weights are the conventional ``conj(a_b) / (a_b^H a_b)``.  Returns ``(w [..., n_beams, K] complex128,
+    ok [...] int32)``."""
+    R = np.asarray(R, dtype=np.complex128)
+    a = np.atleast_2d(np.asarray(steer, dtype=np.complex128))
+    K = R.shape[-1]
+    if R.ndim < 2 or R.shape[-2] != K or a.shape[1] != K:
+        raise ValueError("R must be [..., K, K] and steer [n_beams, K]")
+    if not (np.isfinite(loading) and loading >= 0):
+        raise ValueError("loading must be finite and not negative")
+    if (np.abs(a).sum(axis=1) == 0).any():
+        raise ValueError("a steering vector is all zero")
+    batch = R.shape[:-2]
+    Rf = R.reshape((-1, K, K))
+    n = Rf.shape[0]
+    tr = np.zeros(n)
+    for i in range(K):
+        tr = tr + Rf[:, i, i].real
+    delta = float(loading) * (tr / K)
+    L = np.zeros((n, K, K), dtype=np.complex128)
+    good = np.ones(n, dtype=bool)
+    with np.errstate(all="ignore"):
+        for j in range(K):
+            d = Rf[:, j, j].real + delta
+            for p in range(j):
+                d = d - (L[:, j, p].real ** 2 + L[:, j, p].imag ** 2)
+            good &= (d > 0) & np.isfinite(d)
+            piv = np.sqrt(d)
+            L[:, j, j] = piv
+            for i in range(j + 1, K):
+                v = Rf[:, i, j].copy()
+                for p in range(j):
+                    v = v - L[:, i, p] * np.conj(L[:, j, p])
+                L[:, i, j] = v / piv
+        w = np.empty((n, a.shape[0], K), dtype=np.complex128)
+        for b in range(a.shape[0]):
+            y = np.zeros((n, K), dtype=np.complex128)
+            den = np.zeros(n)
+            for i in range(K):  # L y = a
+                v = np.full(n, a[b, i])
+                for p in range(i):
+                    v = v - L[:, i, p] * y[:, p]
+                y[:, i] = v / L[:, i, i].real
+                den = den + y[:, i].real ** 2 + y[:, i].imag ** 2
+            x = np.zeros((n, K), dtype=np.complex128)
+            for i in range(K - 1, -1, -1):  # L^H x = y
+                v = y[:, i].copy()
+                for p in range(i + 1, K):
+                    v = v - np.conj(L[:, p, i]) * x[:, p]
+                x[:, i] = v / L[:, i, i].real
+            w[:, b, :] = np.conj(x / den[:, None])
+    conventional = np.conj(a) / (np.abs(a) ** 2).sum(axis=1)[:, None]
+    w[~good] = conventional
+    return w.reshape(batch + (a.shape[0], K)), good.astype(np.int32).reshape(batch)
+
+
 class Map:
     """src/data/Map.h: rows = Doppler, cols = delay.  ``data`` is complex64."""
 
@@ -262,6 +330,38 @@ class Ambiguity:
             raise ValueError("w must be [n_beams, n_surv]")
         check(self._L.blah2hip_amb_beamform_dev(self._h, d_map, n_surv, n_cpi, _ptr(w), w.shape[0], d_beam_map,
                                                 d_beam_metrics, stream))
+
+    def beamform_wdev(self, d_map, n_surv, n_cpi, d_w, n_beams, d_beam_map, d_beam_metrics, stream=0):
+        """``beamform_dev`` with a set of weights per CPI on the device (blah2hip_amb_beamform_wdev; raw pointers/ints):
+        ``d_w`` is complex64 ``[n_cpi][n_beams][n_surv]``, as ``mvdr_weights_dev`` writes it."""
+        check(self._L.blah2hip_amb_beamform_wdev(self._h, d_map, n_surv, n_cpi, d_w, n_beams, d_beam_map, d_beam_metrics, stream))
+
+    def covariance_dev(self, d_map, n_surv, n_cpi, d_cov, region=None, stream=0):
+        """The array covariance of the channel maps per CPI (blah2hip_amb_covariance_dev; raw pointers/ints): ``d_cov`` is
+        complex128 ``[n_cpi][n_surv][n_surv]``, ``R[c][i][j] = sum M_i conj(M_j)`` over the cells of ``region`` =
+        ``(row0, row1, col0, col1)`` (None: the whole map)."""
+        row0, row1, col0, col1 = region if region is not None else (0, self.dims.n_doppler_bins, 0, self.dims.n_delay_bins)
+        check(self._L.blah2hip_amb_covariance_dev(self._h, d_map, n_surv, n_cpi, row0, row1, col0, col1, d_cov, stream))
+
+    def mvdr_weights_dev(self, d_cov, n_surv, n_cpi, steer, loading, d_w, d_ok=None, stream=0):
+        """Minimum-variance weights per CPI and beam from ``d_cov`` (blah2hip_amb_mvdr_weights_dev; raw pointers/ints):
+        ``steer`` is a complex array ``[n_beams, n_surv]`` (host, e.g. :func:`ula_steering`), ``d_w`` complex64
+        ``[n_cpi][n_beams][n_surv]``, ``d_ok`` int32 ``[n_cpi]`` or None.  :func:`mvdr_weights` is the same in NumPy."""
+        steer = np.ascontiguousarray(steer, dtype=np.complex64)
+        if steer.ndim != 2 or steer.shape[1] != n_surv:
+            raise ValueError("steer must be [n_beams, n_surv]")
+        check(self._L.blah2hip_amb_mvdr_weights_dev(self._h, d_cov, n_surv, n_cpi, _ptr(steer), steer.shape[0], float(loading),
+                                                    d_w, d_ok, stream))
+
+    def adaptive_beamform_dev(self, d_map, n_surv, n_cpi, steer, loading, d_cov, d_w, d_ok, d_beam_map, d_beam_metrics,
+                              region=None, stream=0):
+        """Adaptive beams, enqueued in order on ``stream``: ``covariance_dev`` over ``region``, ``mvdr_weights_dev`` towards
+        ``steer`` (``[n_beams, n_surv]``, host) and ``beamform_wdev`` with the weights it left in ``d_w``.  Beam b of CPI c is
+        virtual CPI ``b * n_cpi + c`` of ``d_beam_map`` / ``d_beam_metrics``, as for ``beamform_dev``."""
+        steer = np.ascontiguousarray(steer, dtype=np.complex64)
+        self.covariance_dev(d_map, n_surv, n_cpi, d_cov, region, stream)
+        self.mvdr_weights_dev(d_cov, n_surv, n_cpi, steer, loading, d_w, d_ok, stream)
+        self.beamform_wdev(d_map, n_surv, n_cpi, d_w, steer.shape[0], d_beam_map, d_beam_metrics, stream)
 
     def snapshot_dev(self, d_map, n_surv, n_cpi, d_dets, cap, d_count, n_lists, d_snap, stream=0):
         """The ``n_surv`` channel cells under every record of ``n_lists`` detection lists (blah2hip_amb_snapshot_dev; raw

@@ -315,6 +315,52 @@ int blah2hip_amb_db_dev(blah2hip_amb_t h, const void *d_map, const double *d_met
 int blah2hip_amb_beamform_dev(blah2hip_amb_t h, const void *d_map, uint32_t n_surv, uint32_t n_cpi,
                               const float *w, uint32_t n_beams,
                               void *d_beam_map, double *d_beam_metrics, void *stream);
+/* The same beams with weights that differ from CPI to CPI and live on the device: d_w is a DEVICE array
+ * [n_cpi][n_beams][n_surv] of (re, im) fp32 pairs, as blah2hip_amb_mvdr_weights_dev writes it; beam b of CPI c is
+ * M_b(c) = sum_k d_w[c][b][k] M_k(c).  Everything else is blah2hip_amb_beamform_dev: outputs, virtual-CPI order, metrics,
+ * alignment handling, error cases (a NULL d_w for a NULL w) and the BLAH2HIP_K_BEAM / _METRICS slots.  The kernel is a second
+ * instantiation of beamform_kernel that reads its CPI's weights once before the first cell; per cell the operations and
+ * their order are the same, so weights equal to a beamform_dev call's give that call's bits, maps and metrics.  d_w is read
+ * when the kernel runs: whatever writes it must be ordered before this call on the device.  Enqueues only. */
+int blah2hip_amb_beamform_wdev(blah2hip_amb_t h, const void *d_map, uint32_t n_surv, uint32_t n_cpi,
+                               const float *d_w, uint32_t n_beams,
+                               void *d_beam_map, double *d_beam_metrics, void *stream);
+/* ---- adaptive beams: array covariance -> minimum-variance (MVDR / Capon) weights -> blah2hip_amb_beamform_wdev ----
+ * The array covariance of the channel maps over a training rectangle of cells, per CPI:
+ *   d_cov[c][i][j] = sum over row0 <= r < row1, col0 <= q < col1 of M_i(c; r, q) conj(M_j(c; r, q))
+ * as (re, im) doubles, shape [n_cpi][n_surv][n_surv]; the whole map is 0, n_doppler, 0, n_delay.  d_map as for
+ * blah2hip_amb_beamform_dev (NULL = the handle's internal map).  Both triangles are written, d_cov[c][j][i] is the exact
+ * conjugate of d_cov[c][i][j] and the diagonal's imaginary part is exactly 0.
+ * Arithmetic: the product of two fp32 values is exact in fp64, and every accumulation -- in the thread, the workgroup and
+ * the final fold -- is fp64 (fused multiply-adds in the thread), so the error is that of an fp64 sum of n terms; the
+ * contract callers may rely on is the weaker |error| <= 4 * 2^-24 * sum |M_i| |M_j| (fp32 products allowed).  No
+ * floating-point atomics: array_cov_kernel leaves one partial per workgroup and cov_fold_kernel adds them in index order, so
+ * two calls give the same bits.  The partials live in the handle's metrics partials (max_batch * nParts doubles; the
+ * workgroups per CPI are bounded so that n_cpi * G * n_surv^2 fits), which blah2hip_amb_beamform_dev and the process calls use
+ * too: calls on one handle must be ordered on the device.  No allocation, upload or synchronisation: the call enqueues only
+ * (two kernels, both under BLAH2HIP_K_COV) and can be captured in a graph.
+ * BLAH2HIP_ERR_INVALID, with nothing enqueued: NULL handle or output, n_surv outside [1, BLAH2HIP_MAX_SURV], n_cpi == 0,
+ * n_surv * n_cpi above max_batch, an empty or out-of-range rectangle (row0 >= row1, row1 > n_doppler, col0 >= col1,
+ * col1 > n_delay), d_cov overlapping the input maps. */
+int blah2hip_amb_covariance_dev(blah2hip_amb_t h, const void *d_map, uint32_t n_surv, uint32_t n_cpi,
+                                uint32_t row0, uint32_t row1, uint32_t col0, uint32_t col1,
+                                double *d_cov, void *stream);
+/* Minimum-variance distortionless-response weights per CPI c and beam b from d_cov [n_cpi][n_surv][n_surv] (as above; the
+ * lower triangle is read) and the steering vectors a_b -- steer: HOST array [n_beams][n_surv] of (re, im) fp32 pairs, read at
+ * the call and carried in the launch arguments like w of blah2hip_amb_beamform_dev:
+ *   R_l = R[c] + loading * (tr R[c] / n_surv) * I,   h_b = R_l^-1 a_b / (a_b^H R_l^-1 a_b),   d_w[c][b][k] = conj(h_b[k])
+ * complex fp32, shape [n_cpi][n_beams][n_surv]: the d_w of blah2hip_amb_beamform_wdev (M_b = sum_k w[b][k] M_k).  The beam is
+ * distortionless, sum_k d_w[c][b][k] a_b[k] = 1, and R = I gives conj(a_b) / n_surv for unit-modulus a_b.  The solve is an
+ * fp64 Cholesky factorisation with forward and back substitution (mvdr_weights_kernel, one workgroup per CPI, one thread per
+ * beam); only the result is rounded to fp32.
+ * d_ok[c] (int32, may be NULL): 1 where the factorisation succeeded, 0 where a pivot was not finite or not positive (an
+ * all-zero CPI, a NaN in the maps); a failed CPI's weights are the conventional conj(a_b) / (a_b^H a_b), so whatever follows
+ * still runs, and the other CPIs of the batch are unaffected.  Enqueues ONE kernel; no allocation or synchronisation.
+ * BLAH2HIP_ERR_INVALID, with nothing enqueued: a NULL handle, d_cov, steer or d_w, n_surv outside [1, BLAH2HIP_MAX_SURV],
+ * n_beams outside [1, BLAH2HIP_MAX_BEAMS], n_cpi == 0, loading negative or not finite, a steering vector that is all zero. */
+int blah2hip_amb_mvdr_weights_dev(blah2hip_amb_t h, const double *d_cov, uint32_t n_surv, uint32_t n_cpi,
+                                  const float *steer, uint32_t n_beams, double loading,
+                                  float *d_w, int32_t *d_ok, void *stream);
 /* The array snapshot under every detection: d_snap[l][i][k] = cell (row_i, col_i) of CHANNEL map k of CPI l mod n_cpi, complex
  * fp32, shape [n_lists][cap][n_surv] (re, im) -- what phase differences, a Bartlett or MUSIC bearing or a monopulse ratio are
  * computed from without downloading K maps.  d_dets [n_lists][cap] and d_count [n_lists] as blah2hip_detect_dev leaves them
@@ -622,7 +668,8 @@ int blah2hip_amb_result_ptrs(blah2hip_amb_t h, const void **d_map, const double 
 #define BLAH2HIP_K_SAT_COLS 5 /* ... column prefix sums */
 #define BLAH2HIP_K_ROTATE 6   /* Doppler-centre shift (asymmetric limits only) */
 #define BLAH2HIP_K_BEAM 7     /* beamform_kernel (blah2hip_amb_beamform_dev; its metrics_kernel counts under _METRICS) */
-#define BLAH2HIP_K_COUNT 8
+#define BLAH2HIP_K_COV 8      /* array_cov_kernel + cov_fold_kernel (blah2hip_amb_covariance_dev) */
+#define BLAH2HIP_K_COUNT 9
 /* enable != 0: every dev call brackets each kernel with hipEvents */
 int blah2hip_amb_set_timing(blah2hip_amb_t h, int enable);
 /* synchronises the recorded events; ms_total[k] = summed duration of kernel k
