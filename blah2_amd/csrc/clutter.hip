@@ -68,6 +68,10 @@ __device__ __forceinline__ uint32_t xs_index(uint32_t i, const XsMap &m)
 }
 // n < 2N -> n mod N
 __device__ __forceinline__ uint32_t wrapN(uint32_t n, uint32_t N) { return n >= N ? n - N : n; }
+// Sample n0 + m of a circular window of F samples, for any n0 + m < N + F.  A lag below nBins <= N pairs a sample below N
+// with one below N + nBins - 1 <= 2N - 1, so what lies at 2N - 1 and beyond (only a CPI shorter than the transform has it)
+// reaches no lag that is kept: it is clamped to an index inside the CPI, not reduced
+__device__ __forceinline__ uint32_t wrapWin(uint32_t n, uint32_t N) { return wrapN(min(n, 2u * N - 1u), N); }
 
 // XCD-aware walk over the segments of a CPI.  Neighbouring segments read overlapping windows (F samples
 // for segLen = F - nBins + 1 new ones: 2x at nBins = F/2), and workgroups are dispatched round-robin
@@ -216,7 +220,7 @@ template <int R3, class In> __global__ __launch_bounds__(16 * R3, R3 == 16 ? 1 :
         for (int k = 0; k < 16; k++) yw[k] = RawBuiltin<CY>::cvt(RawBuiltin<CY>::ld(yd, (t + T * k) * CY::STRIDE, 0));
       } else {
 #pragma unroll
-        for (int k = 0; k < 16; k++) yw[k] = Y[wrapN(n0 + (uint32_t)(t + T * k), a.N)]; // y window (mode b)
+        for (int k = 0; k < 16; k++) yw[k] = Y[wrapWin(n0 + (uint32_t)(t + T * k), a.N)]; // y window (mode b)
       }
     };
     if (plain) {
@@ -226,7 +230,7 @@ template <int R3, class In> __global__ __launch_bounds__(16 * R3, R3 == 16 ? 1 :
       for (int k = 0; k < 16; k++) wv[k] = RawBuiltin<CX>::cvt(RawBuiltin<CX>::ld(xd, (t + T * k) * CX::STRIDE, 0));
     } else {
 #pragma unroll
-      for (int k = 0; k < 16; k++) wv[k] = X[xs_index(wrapN(n0 + (uint32_t)(t + T * k), a.N), a.xs)]; // xs window (mode r): circular index, n0 + m < N + F
+      for (int k = 0; k < 16; k++) wv[k] = X[xs_index(wrapWin(n0 + (uint32_t)(t + T * k), a.N), a.xs)]; // xs window (mode r): circular index, n0 + m < N + F
     }
     if (R3 < 16) load_y();
 #pragma unroll
@@ -484,7 +488,7 @@ __global__ __launch_bounds__(16 * R3, R3 == 16 ? 1 : 2) void clutter_corr_multi_
       } else {
         const typename ChanOf<In>::type Y = ChanOf<In>::y(a.x, a.y[c], (int64_t)cpi * a.cpiStride);
 #pragma unroll
-        for (int k = 0; k < 16; k++) yw[c][k] = Y[wrapN(n0 + (uint32_t)(t + T * k), a.N)];
+        for (int k = 0; k < 16; k++) yw[c][k] = Y[wrapWin(n0 + (uint32_t)(t + T * k), a.N)];
       }
     };
     if (plain) {
@@ -494,7 +498,7 @@ __global__ __launch_bounds__(16 * R3, R3 == 16 ? 1 : 2) void clutter_corr_multi_
       for (int k = 0; k < 16; k++) wv[k] = RawBuiltin<CX>::cvt(RawBuiltin<CX>::ld(xd, (t + T * k) * CX::STRIDE, 0));
     } else {
 #pragma unroll
-      for (int k = 0; k < 16; k++) wv[k] = X[xs_index(wrapN(n0 + (uint32_t)(t + T * k), a.N), a.xs)];
+      for (int k = 0; k < 16; k++) wv[k] = X[xs_index(wrapWin(n0 + (uint32_t)(t + T * k), a.N), a.xs)];
     }
     // the y windows with the xs window, as the parent requests them (at F = 4096 with r: inside the second transform)
     if (!WITH_R || R3 < 16) load_y(0);
@@ -1926,6 +1930,7 @@ int blah2hip_clutter_create(int32_t delay_min, int32_t delay_max, uint32_t n_sam
   const bool isLong = nBins > 4096 - 15;
   // (more taps than samples: the reference reads its nSamples correlation lags out of bounds, WienerHopf.cpp:76-108)
   if (isLong && (uint32_t)nBins > n_samples) CFAIL(BLAH2HIP_ERR_UNSUPPORTED, "a long filter (more than 4081 taps) needs nBins <= nSamples");
+  if ((uint32_t)nBins > n_samples) CFAIL(BLAH2HIP_ERR_INVALID, "more taps than samples: the clutter filter needs delayMax - delayMin <= nSamples");
   auto *h = new blah2hip_clutter_s;
   // everything that can fail runs inside `build`; a partially built handle is torn down by destroy()
   auto build = [&]() -> int {
@@ -1997,6 +2002,13 @@ int blah2hip_clutter_get_info(blah2hip_clutter_t h, int what, int64_t *value)
   case BLAH2HIP_CLUTTER_INFO_SOLVE_FORM: *value = h->lastForm; return BLAH2HIP_OK;
   case BLAH2HIP_CLUTTER_INFO_SOLVE_E: *value = h->lastE; return BLAH2HIP_OK;
   case BLAH2HIP_CLUTTER_INFO_SOLVE_G: *value = h->lastG; return BLAH2HIP_OK;
+  case BLAH2HIP_CLUTTER_INFO_CORR_FORM: { // the long form's correlations are its first child's
+    const blah2hip_clutter_s *p = h->subCorr ? h->subCorr : h;
+    *value = p->corrHalf ? BLAH2HIP_CLUTTER_CORR_HALF : BLAH2HIP_CLUTTER_CORR_WINDOW;
+    return BLAH2HIP_OK;
+  }
+  case BLAH2HIP_CLUTTER_INFO_FIR_CARRY: *value = (h->subFir ? h->subFir : h)->firCarry ? 1 : 0; return BLAH2HIP_OK;
+  case BLAH2HIP_CLUTTER_INFO_CHUNKS: *value = h->nChunks; return BLAH2HIP_OK;
   case BLAH2HIP_CLUTTER_INFO_SOLVE_FAULT:
   case BLAH2HIP_CLUTTER_INFO_SOLVE_RETRIES: {
     // the stream the handle's last call ran on, not the device (a poll in a pipeline must not stall other streams and

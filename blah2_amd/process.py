@@ -836,6 +836,19 @@ class WienerHopf:
             out[name] = int(v.value)
         return out
 
+    def plan_info(self):
+        """The plan the next call runs: {'corr' ('half' / 'window'), 'carry' (the FIR kernel carries the window overlap in
+        registers), 'chunks' (chunks of 2048 taps of a long filter, else 0)}."""
+        out = {}
+        for name, what in (("corr", _lib.CLUTTER_INFO_CORR_FORM), ("carry", _lib.CLUTTER_INFO_FIR_CARRY),
+                           ("chunks", _lib.CLUTTER_INFO_CHUNKS)):
+            v = C.c_int64(0)
+            check(self._L.blah2hip_clutter_get_info(self._h, what, C.byref(v)))
+            out[name] = int(v.value)
+        out["corr"] = "half" if out["corr"] == _lib.CLUTTER_CORR_HALF else "window"
+        out["carry"] = bool(out["carry"])
+        return out
+
     def read_last(self, cpi=0):
         """(ok, w, r, b) of CPI ``cpi`` of the last call: the nBins filter taps (complex64) and the fp64
         correlations r, b of the normal equations A w = b, A[i][j] = r[i-j] (diagnostics)."""

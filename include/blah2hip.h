@@ -564,6 +564,12 @@ int blah2hip_clutter_set_option(blah2hip_clutter_t h, int option, int64_t value)
 #define BLAH2HIP_CLUTTER_INFO_SOLVE_G 3
 #define BLAH2HIP_CLUTTER_INFO_SOLVE_FAULT 4
 #define BLAH2HIP_CLUTTER_INFO_SOLVE_RETRIES 5
+/* The plan the next process call runs (it follows BLAH2HIP_CLUTTER_OPT_FFT_LEN / _CORR / _FIR_CARRY): CORR_FORM =
+ * BLAH2HIP_CLUTTER_CORR_HALF or _WINDOW, FIR_CARRY = 1 where the FIR kernel carries the window overlap in registers,
+ * CHUNKS = chunks of 2048 taps of a long filter (more than 4081 taps), 0 for every other. */
+#define BLAH2HIP_CLUTTER_INFO_CORR_FORM 6
+#define BLAH2HIP_CLUTTER_INFO_FIR_CARRY 7
+#define BLAH2HIP_CLUTTER_INFO_CHUNKS 8
 int blah2hip_clutter_get_info(blah2hip_clutter_t h, int what, int64_t *value);
 /* The filter's Toeplitz solve on its own: n_cpi systems toeplitz(r) w = b given as rb = [n_cpi][2][nBins] complex fp64 (r then b,
  * interleaved re, im; the layout blah2hip_clutter_read_last returns), taps to w ([n_cpi][nBins] complex fp32), ok[c] = 0
