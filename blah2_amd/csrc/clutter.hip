@@ -1854,9 +1854,12 @@ int long_process(blah2hip_clutter_s *h, const cf *d_x, const cf *d_y, uint32_t n
   cf *xp = h->d_long, *yp = xp + plane, *wp = yp + plane;
   const dim3 pg((N + 255) / 256, nCpi), gg((C + 255) / 256, nCpi);
   blah2hip_clutter_s *sc = h->subCorr, *sf = h->subFir;
-  // private copies with the children's stride (the caller's may differ from N); the output is built in the copy of y
-  CHIP(hipMemcpy2DAsync(xp, (size_t)N * sizeof(cf), d_x, (size_t)stride * sizeof(cf), (size_t)N * sizeof(cf), nCpi, hipMemcpyDeviceToDevice, st));
-  CHIP(hipMemcpy2DAsync(yp, (size_t)N * sizeof(cf), d_y, (size_t)stride * sizeof(cf), (size_t)N * sizeof(cf), nCpi, hipMemcpyDeviceToDevice, st));
+  // private copies with the children's stride (the caller's may differ from N); the output is built in the copy of y.
+  // A lone CPI has no second row: the entry points take any stride with it (0 included), and a pitch below the row width
+  // is refused by the runtime, so the pitches are N there.
+  const size_t inPitch = (nCpi == 1 ? (size_t)N : (size_t)stride) * sizeof(cf), outPitch = (nCpi == 1 ? (size_t)N : (size_t)outStride) * sizeof(cf);
+  CHIP(hipMemcpy2DAsync(xp, (size_t)N * sizeof(cf), d_x, inPitch, (size_t)N * sizeof(cf), nCpi, hipMemcpyDeviceToDevice, st));
+  CHIP(hipMemcpy2DAsync(yp, (size_t)N * sizeof(cf), d_y, inPitch, (size_t)N * sizeof(cf), nCpi, hipMemcpyDeviceToDevice, st));
   sc->stages = 1;
   for (int c = 0; c < h->nChunks; c++) {
     const cf *yin = yp;
@@ -1894,7 +1897,7 @@ int long_process(blah2hip_clutter_s *h, const cf *d_x, const cf *d_y, uint32_t n
       long_out_kernel<<<pg, 256, 0, st>>>(yp, yout, N, outStride, ok);
       CHIP(hipGetLastError());
     } else {
-      CHIP(hipMemcpy2DAsync(yout, (size_t)outStride * sizeof(cf), yp, (size_t)N * sizeof(cf), (size_t)N * sizeof(cf), nCpi, hipMemcpyDeviceToDevice, st));
+      CHIP(hipMemcpy2DAsync(yout, outPitch, yp, (size_t)N * sizeof(cf), (size_t)N * sizeof(cf), nCpi, hipMemcpyDeviceToDevice, st));
     }
     CHIP(h->timer.toc(BLAH2HIP_CK_FIR, st));
   }

@@ -24,7 +24,13 @@ def corr_lags(y, xs, C):
     return np.array([np.sum(y * np.conj(np.roll(xs, k))) for k in range(C)]) / 1.0
 
 
-@pytest.mark.parametrize("dmin,nbins,n,C", [(-3, 50, 211, 16), (0, 37, 150, 16), (2, 45, 187, 8), (-7, 64, 256, 32)])
+@pytest.mark.parametrize("dmin,nbins,n,C", [(-3, 50, 211, 16), (0, 37, 150, 16), (2, 45, 187, 8), (-7, 64, 256, 32),
+                                            # the chunk edges (on the device: tests/test_clutter_long_edges_gpu.py)
+                                            (0, 64, 64, 16),     # whole chunks only, and as many taps as samples
+                                            (-3, 48, 100, 16),   # whole chunks only
+                                            (1, 33, 70, 16),     # a last chunk of ONE tap, positive first lag
+                                            (-5, 32, 32, 16),    # as many taps as samples: the last chunk's offset comes close to N
+                                            (2, 49, 49, 16)])    # ... with a one-tap last chunk and a positive first lag
 def test_chunked_correlations_and_fir(dmin, nbins, n, C):
     rng = np.random.default_rng(nbins)
     x = rng.standard_normal(n) + 1j * rng.standard_normal(n)
