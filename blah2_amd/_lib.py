@@ -15,9 +15,10 @@ LIB_PATH = os.path.join(PKG, "libblah2hip.so")
 OK = 0
 ERR_INVALID, ERR_HIP, ERR_UNSUPPORTED, ERR_UNDERFLOW, ERR_NO_DEVICE, ERR_CAPACITY = -1, -2, -3, -4, -5, -6
 FMT_C32, FMT_I16, FMT_F16, FMT_I16X_C32Y, FMT_I8, FMT_I8X_C32Y = 0, 1, 2, 3, 4, 5
-K_RANGE, K_DOPPLER, K_METRICS, K_CFAR, K_SAT_ROWS, K_SAT_COLS, K_ROTATE, K_BEAM, K_COV, K_COUNT = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
+K_RANGE, K_DOPPLER, K_METRICS, K_CFAR, K_SAT_ROWS, K_SAT_COLS, K_ROTATE, K_BEAM, K_COV, K_BEARING, K_COUNT = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
 KERNEL_NAMES = {K_RANGE: "range", K_DOPPLER: "doppler", K_METRICS: "metrics", K_CFAR: "cfar",
-                K_SAT_ROWS: "sat_rows", K_SAT_COLS: "sat_cols", K_ROTATE: "rotate", K_BEAM: "beam", K_COV: "cov"}
+                K_SAT_ROWS: "sat_rows", K_SAT_COLS: "sat_cols", K_ROTATE: "rotate", K_BEAM: "beam", K_COV: "cov",
+                K_BEARING: "bearing"}
 CK_CORR, CK_REDUCE, CK_SOLVE, CK_FIR, CK_COUNT = 0, 1, 2, 3, 4
 CLUTTER_KERNEL_NAMES = {CK_CORR: "clutter_corr", CK_REDUCE: "clutter_reduce", CK_SOLVE: "clutter_solve",
                         CK_FIR: "clutter_fir"}
@@ -29,6 +30,8 @@ OPT_MULTI_SURV_RANGE = 11
 MULTI_AUTO, MULTI_SHARED, MULTI_PER_CHANNEL = 0, 1, 2
 MAX_SURV = 8
 MAX_BEAMS = 8
+MAX_BEARING_GRID = 384
+BEARING_WRAP = 1
 LEAK_OFF, LEAK_AUTO, LEAK_ALWAYS = 0, 1, 2
 CFAR2D_AUTO, CFAR2D_TILE, CFAR2D_SAT, CFAR2D_STREAM = 0, 1, 2, 3
 CLUTTER_OPT_SOLVE_K, CLUTTER_OPT_FFT_LEN, CLUTTER_OPT_CORR, CLUTTER_OPT_SOLVE_FORM, CLUTTER_OPT_SOLVE_E, CLUTTER_OPT_FIR_CARRY = 1, 2, 3, 4, 5, 6
@@ -50,6 +53,7 @@ INFO_LEAK_LAGS, INFO_LEAK_MAX_E12 = 8, 9
 INFO_HOT_COLUMNS, INFO_HOT_COLUMNS_MISSED = 10, 11
 INFO_CFAR2D_SEG_ROWS, INFO_CFAR2D_GRID = 12, 13
 INFO_DETECT_GRID, INFO_DETECT_TILED = 14, 15
+INFO_BEARING_GRID = 16
 
 
 class Blah2HipError(RuntimeError):
@@ -71,6 +75,10 @@ class Hit(C.Structure):
 
 class Det(C.Structure):
     _fields_ = [("row", C.c_int32), ("col", C.c_int32), ("delay", C.c_double), ("doppler", C.c_double), ("snr", C.c_double)]
+
+
+class Bearing(C.Structure):
+    _fields_ = [("index", C.c_int32), ("adaptive", C.c_int32), ("offset", C.c_double), ("power", C.c_double), ("coherence", C.c_double)]
 
 
 # every symbol include/blah2hip.h declares: name -> (restype, argtypes)
@@ -101,6 +109,7 @@ SYMBOLS = {
     "blah2hip_amb_covariance_dev": (C.c_int, [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _vp]),
     "blah2hip_amb_mvdr_weights_dev": (C.c_int, [_vp, _vp, _u32, _u32, _vp, _u32, _dbl, _vp, _vp, _vp]),
     "blah2hip_amb_snapshot_dev": (C.c_int, [_vp, _vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _vp]),
+    "blah2hip_amb_bearing_dev": (C.c_int, [_vp, _vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _dbl, _vp, _u32, _u32, _vp, _vp]),
     "blah2hip_cfar1d_dev": (C.c_int, [_vp, _vp, _vp, _u32, _dbl, _i32, _i32, _i32, _dbl, _vp, _u32, _vp, _vp]),
     "blah2hip_cfar1d_prepare": (C.c_int, [_vp, _dbl, _i32]),
     "blah2hip_cfar2d_prepare": (C.c_int, [_vp, _dbl, _i32, _i32, _i32, _i32]),

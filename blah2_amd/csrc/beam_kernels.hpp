@@ -7,6 +7,8 @@
 //   array_cov_kernel   the K x K array covariance of the channel maps over a training rectangle, per CPI, in fp64
 //   cov_fold_kernel    ... its per-workgroup partials folded in index order into the Hermitian matrix
 //   mvdr_weights_kernel  minimum-variance (Capon) weights from that covariance: an fp64 Cholesky solve per CPI and beam
+//   bearing_kernel     the bearing of every detection: its snapshot scanned over a steering table, whitened by that
+//                      covariance's Cholesky factor (the adaptive matched filter) or not (Bartlett), in fp64
 //
 // The cross-ambiguity map is linear in the surveillance channel, so the map of the beam y_b = sum_k w[b][k] y_k is the
 // same combination of the channel maps blah2hip_amb_process_multi_dev left in HBM: a further beam costs one more map
@@ -157,6 +159,18 @@ struct SnapArgs {
   int32_t nD, nDelay;
 };
 
+// The cell under record i of list l in channel map 0 of the list's CPI l mod nCpi -- channel k lies k * nCpi * cells
+// further on -- or nullptr where the slot lies behind the list's count or the record's row or column outside the map.
+__device__ __forceinline__ const cf *snap_cell(const cf *map, const blah2hip_det_t *dets, const uint32_t *count, uint32_t cap,
+                                               uint32_t nCpi, int32_t nD, int32_t nDelay, uint32_t l, uint32_t i)
+{
+  if (i >= count[l]) return nullptr;
+  const blah2hip_det_t *d = dets + (size_t)l * cap + i;
+  const int32_t row = d->row, col = d->col;
+  if (row < 0 || row >= nD || col < 0 || col >= nDelay) return nullptr;
+  return map + (l % nCpi) * ((size_t)nD * nDelay) + (size_t)row * nDelay + col;
+}
+
 // One thread per record slot (list l, index i).  Slots behind the list's count and records outside the map are left
 // unwritten.
 __global__ __launch_bounds__(256) void snapshot_kernel(SnapArgs a)
@@ -164,11 +178,8 @@ __global__ __launch_bounds__(256) void snapshot_kernel(SnapArgs a)
   const size_t total = (size_t)a.nLists * a.cap;
   const size_t cells = (size_t)a.nD * a.nDelay;
   for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (size_t)gridDim.x * 256) {
-    const uint32_t l = (uint32_t)(t / a.cap), i = (uint32_t)(t % a.cap);
-    if (i >= a.count[l]) continue;
-    const int32_t row = a.dets[t].row, col = a.dets[t].col;
-    if (row < 0 || row >= a.nD || col < 0 || col >= a.nDelay) continue;
-    const cf *z = a.map + (l % a.nCpi) * cells + (size_t)row * a.nDelay + col;
+    const cf *z = snap_cell(a.map, a.dets, a.count, a.cap, a.nCpi, a.nD, a.nDelay, (uint32_t)(t / a.cap), (uint32_t)(t % a.cap));
+    if (!z) continue;
     for (uint32_t k = 0; k < a.nSurv; k++) a.snap[t * a.nSurv + k] = z[(size_t)k * a.nCpi * cells];
   }
 }
@@ -286,6 +297,67 @@ struct MvdrArgs {
   cf steer[BLAH2HIP_MAX_BEAMS][BLAH2HIP_MAX_SURV]; // in the launch arguments
 };
 
+// R_l = R + loading (tr R / K) I from the lower triangle of R ([K][K] (re, im)) and its Cholesky factor R_l = L L^H, left
+// in the lower triangle of lr / li (the diagonal is real), everything in fp64 registers (K is a template parameter, every
+// loop unrolled).  False where a pivot is not finite or not positive (an all-zero matrix; a NaN anywhere in the triangle
+// reaches a pivot).  The statements are mvdr_weights_kernel's own, which keeps them inline: moved into a function they compile
+// to other fused multiply-adds, and that kernel's bits are a contract.
+template <int K>
+__device__ __forceinline__ bool cholesky_loaded(const double *R, double loading, double (&lr)[K][K], double (&li)[K][K])
+{
+  double tr = 0.0;
+#pragma unroll
+  for (int i = 0; i < K; i++) {
+#pragma unroll
+    for (int j = 0; j <= i; j++) { lr[i][j] = R[2 * (i * K + j)]; li[i][j] = R[2 * (i * K + j) + 1]; }
+    tr += lr[i][i];
+  }
+  const double delta = loading * (tr / K);
+  bool good = true;
+#pragma unroll
+  for (int j = 0; j < K; j++) {
+    double d = lr[j][j] + delta;
+#pragma unroll
+    for (int p = 0; p < j; p++) d -= lr[j][p] * lr[j][p] + li[j][p] * li[j][p];
+    if (!(d > 0.0) || !(d < __builtin_huge_val())) good = false;
+    const double piv = sqrt(d), inv = 1.0 / piv;
+    lr[j][j] = piv;
+#pragma unroll
+    for (int i = j + 1; i < K; i++) {
+      double sr = lr[i][j], si = li[i][j];
+#pragma unroll
+      for (int p = 0; p < j; p++) { // - L[i][p] conj(L[j][p])
+        sr -= lr[i][p] * lr[j][p] + li[i][p] * li[j][p];
+        si -= li[i][p] * lr[j][p] - lr[i][p] * li[j][p];
+      }
+      lr[i][j] = sr * inv;
+      li[i][j] = si * inv;
+    }
+  }
+  return good;
+}
+
+// L y = a by forward substitution; returns y^H y, summed in the order i = 0 .. K-1
+template <int K>
+__device__ __forceinline__ double forward_solve(const double (&lr)[K][K], const double (&li)[K][K], const double (&ar)[K],
+                                                const double (&ai)[K], double (&yr)[K], double (&yi)[K])
+{
+  double den = 0.0;
+#pragma unroll
+  for (int i = 0; i < K; i++) {
+    double sr = ar[i], si = ai[i];
+#pragma unroll
+    for (int p = 0; p < i; p++) {
+      sr -= lr[i][p] * yr[p] - li[i][p] * yi[p];
+      si -= lr[i][p] * yi[p] + li[i][p] * yr[p];
+    }
+    yr[i] = sr / lr[i][i];
+    yi[i] = si / lr[i][i];
+    den += yr[i] * yr[i] + yi[i] * yi[i];
+  }
+  return den;
+}
+
 // grid (nCpi), 64 threads: thread b < nBeams computes beam b of its CPI, everything in fp64 registers (K is a template
 // parameter, every loop unrolled).  R_l = R + loading (tr R / K) I from the lower triangle of cov; Cholesky R_l = L L^H;
 // L y = a, L^H x = y; h = x / (a^H x) with a^H x = y^H y; w = conj(h) rounded to fp32.  A pivot that is not finite or
@@ -383,6 +455,148 @@ inline void launch_mvdr_weights(uint32_t K, uint32_t nCpi, hipStream_t st, const
   case 6: hipLaunchKernelGGL((mvdr_weights_kernel<6>), dim3(nCpi), dim3(64), 0, st, a); break;
   case 7: hipLaunchKernelGGL((mvdr_weights_kernel<7>), dim3(nCpi), dim3(64), 0, st, a); break;
   case 8: hipLaunchKernelGGL((mvdr_weights_kernel<8>), dim3(nCpi), dim3(64), 0, st, a); break;
+  }
+}
+
+// ---- a bearing per detection ----------------------------------------------------------------------------------------------
+struct BearingArgs {
+  const cf *map;              // [K][nCpi][nD][nDelay]
+  const blah2hip_det_t *dets; // [nLists][cap]
+  const uint32_t *count;      // [nLists]; more than cap: the first cap records are the list
+  const double *cov;          // [nCpi][K][K] (re, im), or nullptr: the Bartlett scan
+  const cf *steer;            // [nGrid][K]
+  blah2hip_bearing_t *out;    // [nLists][cap]
+  double loading;
+  uint32_t nCpi, cap, nGrid, wrap;
+  int32_t nD, nDelay;
+};
+
+constexpr uint32_t BEARING_CHUNK = 16; // records a workgroup scans per table it builds: four per wave
+
+// P(g) = |u_g^H t|^2 from the normalised table: 4 K fused multiply-adds in the order k = 0 .. K-1, then the squares
+template <int K>
+__device__ __forceinline__ double bearing_power(const double (&ur)[K][BLAH2HIP_MAX_BEARING_GRID],
+                                                const double (&ui)[K][BLAH2HIP_MAX_BEARING_GRID], uint32_t g,
+                                                const double (&tr)[K], const double (&ti)[K])
+{
+  double pr = 0.0, pi = 0.0;
+#pragma unroll
+  for (int k = 0; k < K; k++) { // conj(u) t
+    const double x = ur[k][g], y = ui[k][g];
+    pr = fma(y, ti[k], fma(x, tr[k], pr));
+    pi = fma(-y, tr[k], fma(x, ti[k], pi));
+  }
+  return pr * pr + pi * pi;
+}
+
+// grid (X, nLists), 256 threads.  List l belongs to CPI l mod nCpi.  A workgroup whose first record lies behind the list's
+// count returns at once; the others
+//   1. factorise the CPI's R_l = L L^H, every thread the same matrix in its own registers as in mvdr_weights_kernel (cov
+//      == nullptr or a failed pivot: L = I, adaptive = 0 -- the SAME code then runs on the identity, so an identity
+//      covariance, a failed one and no covariance give the same bits),
+//   2. whiten and normalise the steering table, thread per grid point: v_g = L^-1 a_g, u_g = v_g / sqrt(v_g^H v_g) (0 where
+//      v_g^H v_g is 0), into LDS as ur / ui [k][g] -- lanes of consecutive g read consecutive 8-byte words, no bank
+//      conflict; 2 * K * 384 doubles, 48 KB at K = 8,
+//   3. walk chunks of BEARING_CHUNK records with a stride of gridDim.x, one wave per record: the K cells through
+//      snap_cell, t = L^-1 s in every lane, P(g) = |u_g^H t|^2 for g = lane, lane + 64, ...; the lane keeps its first
+//      largest P, a butterfly folds the 64 (P, g) pairs with the lower index on equal P; the two neighbours' powers come
+//      from the same table through the same function, so they carry the scan's bits; lane 0 writes the record.
+// Everything is fp64 (the fp32 cells and steering entries convert exactly).  No atomics: a record is a function of its
+// inputs alone.
+template <int K>
+__global__ __launch_bounds__(256) void bearing_kernel(BearingArgs a)
+{
+  __shared__ double ur[K][BLAH2HIP_MAX_BEARING_GRID], ui[K][BLAH2HIP_MAX_BEARING_GRID];
+  const uint32_t l = blockIdx.y;
+  const uint32_t n = min(a.count[l], a.cap);
+  if ((uint64_t)blockIdx.x * BEARING_CHUNK >= n) return; // uniform over the workgroup, before any barrier
+
+  double lr[K][K], li[K][K];
+  bool adaptive = false;
+  if (a.cov) adaptive = cholesky_loaded<K>(a.cov + 2 * (size_t)(l % a.nCpi) * K * K, a.loading, lr, li);
+  if (!adaptive) {
+#pragma unroll
+    for (int i = 0; i < K; i++) {
+#pragma unroll
+      for (int j = 0; j <= i; j++) { lr[i][j] = i == j ? 1.0 : 0.0; li[i][j] = 0.0; }
+    }
+  }
+
+  for (uint32_t g = threadIdx.x; g < a.nGrid; g += 256) {
+    double ar[K], ai[K], vr[K], vi[K];
+#pragma unroll
+    for (int k = 0; k < K; k++) { const cf s = a.steer[(size_t)g * K + k]; ar[k] = (double)s.x; ai[k] = (double)s.y; }
+    const double vv = forward_solve<K>(lr, li, ar, ai, vr, vi);
+    const double rs = vv > 0.0 ? 1.0 / sqrt(vv) : 0.0;
+#pragma unroll
+    for (int k = 0; k < K; k++) { ur[k][g] = vr[k] * rs; ui[k][g] = vi[k] * rs; }
+  }
+  __syncthreads();
+
+  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const size_t chStride = (size_t)a.nCpi * a.nD * a.nDelay;
+  for (uint64_t first = (uint64_t)blockIdx.x * BEARING_CHUNK; first < n; first += (uint64_t)gridDim.x * BEARING_CHUNK) {
+    const uint32_t end = (uint32_t)min((uint64_t)n, first + BEARING_CHUNK);
+    for (uint32_t i = (uint32_t)first + wave; i < end; i += 4) { // uniform over the wave
+      const cf *z = snap_cell(a.map, a.dets, a.count, a.cap, a.nCpi, a.nD, a.nDelay, l, i);
+      if (!z) continue;
+      double sr[K], si[K];
+      bool zero = true, finite = true;
+#pragma unroll
+      for (int k = 0; k < K; k++) {
+        const cf c = z[(size_t)k * chStride];
+        sr[k] = (double)c.x;
+        si[k] = (double)c.y;
+        zero = zero && c.x == 0.f && c.y == 0.f;
+        finite = finite && fabsf(c.x) < __builtin_huge_valf() && fabsf(c.y) < __builtin_huge_valf();
+      }
+      blah2hip_bearing_t rec = {-1, 0, 0.0, 0.0, 0.0};
+      if (!zero && finite) {
+        double tr[K], ti[K];
+        const double tt = forward_solve<K>(lr, li, sr, si, tr, ti);
+        double best = -1.0; // every P is >= 0; a NaN (a steering entry that is not finite) never wins
+        uint32_t bg = 0xFFFFFFFFu;
+        for (uint32_t g = lane; g < a.nGrid; g += 64) {
+          const double p = bearing_power<K>(ur, ui, g, tr, ti);
+          if (p > best) { best = p; bg = g; }
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+          const double op = __shfl_xor(best, off);
+          const uint32_t og = (uint32_t)__shfl_xor((int)bg, off);
+          if (op > best || (op == best && og < bg)) { best = op; bg = og; }
+        }
+        if (bg < a.nGrid) {
+          double offset = 0.0;
+          const bool inner = bg > 0 && bg + 1 < a.nGrid;
+          if (inner || a.wrap) {
+            const double pm = bearing_power<K>(ur, ui, bg > 0 ? bg - 1 : a.nGrid - 1, tr, ti);
+            const double pp = bearing_power<K>(ur, ui, bg + 1 < a.nGrid ? bg + 1 : 0, tr, ti);
+            const double den = (pm - 2.0 * best) + pp;
+            if (den < 0.0) offset = 0.5 * (pm - pp) / den;
+          }
+          rec.index = (int32_t)bg;
+          rec.adaptive = adaptive ? 1 : 0;
+          rec.offset = offset;
+          rec.power = best;
+          rec.coherence = tt > 0.0 ? best / tt : 0.0;
+        }
+      }
+      if (lane == 0) a.out[(size_t)l * a.cap + i] = rec;
+    }
+  }
+}
+
+inline void launch_bearing(uint32_t K, dim3 grid, hipStream_t st, const BearingArgs &a)
+{
+  switch (K) {
+  case 2: hipLaunchKernelGGL((bearing_kernel<2>), grid, dim3(256), 0, st, a); break;
+  case 3: hipLaunchKernelGGL((bearing_kernel<3>), grid, dim3(256), 0, st, a); break;
+  case 4: hipLaunchKernelGGL((bearing_kernel<4>), grid, dim3(256), 0, st, a); break;
+  case 5: hipLaunchKernelGGL((bearing_kernel<5>), grid, dim3(256), 0, st, a); break;
+  case 6: hipLaunchKernelGGL((bearing_kernel<6>), grid, dim3(256), 0, st, a); break;
+  case 7: hipLaunchKernelGGL((bearing_kernel<7>), grid, dim3(256), 0, st, a); break;
+  case 8: hipLaunchKernelGGL((bearing_kernel<8>), grid, dim3(256), 0, st, a); break;
   }
 }
 

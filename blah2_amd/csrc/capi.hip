@@ -126,6 +126,7 @@ struct blah2hip_amb_s {
   double *d_sat = nullptr;          // 2-D CFAR summed-area table [max_batch][nD+1][nDelay+1]
   uint32_t *d_detWords = nullptr;   // detect_finish_kernel, tiled form: [2][max_batch] records appended, tickets taken; zero between launches
   int detGridLast = 0, detTiledLast = 0; // BLAH2HIP_INFO_DETECT_GRID / _TILED
+  int bearingGridLast = 0;          // BLAH2HIP_INFO_BEARING_GRID
 
   KernelTimer<BLAH2HIP_K_COUNT> timer;
 
@@ -1413,6 +1414,7 @@ int blah2hip_amb_get_info(blah2hip_amb_t h, int key, int64_t *value)
   case BLAH2HIP_INFO_CFAR2D_GRID: *value = h->cfar2dGridLast; return BLAH2HIP_OK;
   case BLAH2HIP_INFO_DETECT_GRID: *value = h->detGridLast; return BLAH2HIP_OK;
   case BLAH2HIP_INFO_DETECT_TILED: *value = h->detTiledLast; return BLAH2HIP_OK;
+  case BLAH2HIP_INFO_BEARING_GRID: *value = h->bearingGridLast; return BLAH2HIP_OK;
   case BLAH2HIP_INFO_LEAK_LAGS: *value = h->lastLeakLags; return BLAH2HIP_OK;
   case BLAH2HIP_INFO_LEAK_MAX_E12: *value = (int64_t)std::llround(h->lastLeakMax * 1e12); return BLAH2HIP_OK;
   case BLAH2HIP_INFO_HOT_COLUMNS: { // of the last call's first CPI; waits for the device
@@ -2101,6 +2103,45 @@ int blah2hip_amb_snapshot_dev(blah2hip_amb_t h, const void *d_map, uint32_t n_su
                      (hipStream_t)stream, a);
   HIPCHK(hipGetLastError());
   return BLAH2HIP_OK;
+}
+
+int blah2hip_amb_bearing_dev(blah2hip_amb_t h, const void *d_map, uint32_t n_surv, uint32_t n_cpi,
+                             const blah2hip_det_t *d_dets, uint32_t cap, const uint32_t *d_count, uint32_t n_lists,
+                             const double *d_cov, double loading, const float *d_steer, uint32_t n_grid, uint32_t flags,
+                             blah2hip_bearing_t *d_out, void *stream)
+{
+  if (!h || !d_dets || !d_count || !d_steer || !d_out) return fail(BLAH2HIP_ERR_INVALID, "NULL argument");
+  if (n_surv < 2 || n_surv > BLAH2HIP_MAX_SURV) return fail(BLAH2HIP_ERR_INVALID, "n_surv outside [2, BLAH2HIP_MAX_SURV]");
+  if (n_cpi == 0 || (uint64_t)n_surv * n_cpi > h->dims.max_batch) return fail(BLAH2HIP_ERR_INVALID, "n_cpi is 0 or n_surv * n_cpi above max_batch");
+  if (cap == 0) return fail(BLAH2HIP_ERR_INVALID, "cap is 0");
+  if (n_lists == 0 || n_lists % n_cpi != 0 || n_lists > 65535)
+    return fail(BLAH2HIP_ERR_INVALID, "n_lists is 0, not a multiple of n_cpi or above 65535");
+  if (n_grid < 3 || n_grid > BLAH2HIP_MAX_BEARING_GRID) return fail(BLAH2HIP_ERR_INVALID, "n_grid outside [3, BLAH2HIP_MAX_BEARING_GRID]");
+  if (flags & ~BLAH2HIP_BEARING_WRAP) return fail(BLAH2HIP_ERR_INVALID, "bearing: unknown flag bits");
+  if (d_cov && (!(loading >= 0.0) || !std::isfinite(loading))) return fail(BLAH2HIP_ERR_INVALID, "bearing: loading is negative or not finite");
+  HIPCHK(hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  BearingArgs a;
+  a.map = d_map ? (const cf *)d_map : h->d_map;
+  a.dets = d_dets;
+  a.count = d_count;
+  a.cov = d_cov;
+  a.steer = (const cf *)d_steer;
+  a.out = d_out;
+  a.loading = d_cov ? loading : 0.0;
+  a.nCpi = n_cpi; a.cap = cap; a.nGrid = n_grid;
+  a.wrap = flags & BLAH2HIP_BEARING_WRAP;
+  a.nD = (int32_t)h->dims.n_doppler_bins;
+  a.nDelay = (int32_t)h->dims.n_delay_bins;
+  // workgroups per list: the count lives on the device, so one per BEARING_CHUNK slots of cap (those behind the count return
+  // before they build the table), and no more than eight a CU over the launch: a workgroup strides over the chunks
+  const uint32_t X = std::max(1u, std::min(cap / BEARING_CHUNK + (cap % BEARING_CHUNK ? 1u : 0u), 8u * (uint32_t)h->numCU / n_lists));
+  int rc;
+  if ((rc = tic(h, BLAH2HIP_K_BEARING, st))) return rc;
+  launch_bearing(n_surv, dim3(X, n_lists), st, a);
+  HIPCHK(hipGetLastError());
+  h->bearingGridLast = (int)X;
+  return toc(h, BLAH2HIP_K_BEARING, st);
 }
 
 int blah2hip_amb_process_c32(blah2hip_amb_t h, const float *x, const float *y, uint32_t n,

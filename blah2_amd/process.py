@@ -40,6 +40,44 @@ def ula_steering(n_surv, spacing_wavelengths, angles_deg):
     return np.exp(2j * np.pi * float(spacing_wavelengths) * np.sin(theta)[:, None] * k[None, :])
 
 
+def _cholesky_loaded(Rf, loading):
+    """``R_l = R + loading (tr R / K) I = L L^H`` for a stack ``Rf [n, K, K]`` (the lower triangle is read), written out
+    column by column in the order of mvdr_weights_kernel.  Returns ``(L [n, K, K], good [n] bool)``; ``good`` is False where a
+    pivot is not finite or not positive."""
+    n, K = Rf.shape[0], Rf.shape[-1]
+    tr = np.zeros(n)
+    for i in range(K):
+        tr = tr + Rf[:, i, i].real
+    delta = float(loading) * (tr / K)
+    L = np.zeros((n, K, K), dtype=np.complex128)
+    good = np.ones(n, dtype=bool)
+    for j in range(K):
+        d = Rf[:, j, j].real + delta
+        for p in range(j):
+            d = d - (L[:, j, p].real ** 2 + L[:, j, p].imag ** 2)
+        good &= (d > 0) & np.isfinite(d)
+        piv = np.sqrt(d)
+        L[:, j, j] = piv
+        for i in range(j + 1, K):
+            v = Rf[:, i, j].copy()
+            for p in range(j):
+                v = v - L[:, i, p] * np.conj(L[:, j, p])
+            L[:, i, j] = v / piv
+    return L, good
+
+
+def _forward_solve(L, a):
+    """``L y = a`` by forward substitution, ``L [K, K]`` lower triangular with a real diagonal, ``a [..., K]``."""
+    K = L.shape[-1]
+    y = np.zeros(a.shape, dtype=np.complex128)
+    for i in range(K):
+        v = a[..., i].copy()
+        for p in range(i):
+            v = v - L[i, p] * y[..., p]
+        y[..., i] = v / L[i, i].real
+    return y
+
+
 def mvdr_weights(R, steer, loading):
     """blah2hip_amb_mvdr_weights_dev restated in fp64 NumPy.  ``R``: Hermitian ``[..., K, K]`` (the lower triangle is read),
     ``steer``: ``[n_beams, K]``.  With ``R_l = R + loading (tr R / K) I``: ``h_b = R_l^-1 a_b / (a_b^H R_l^-1 a_b)`` through
@@ -59,25 +97,8 @@ def mvdr_weights(R, steer, loading):
     batch = R.shape[:-2]
     Rf = R.reshape((-1, K, K))
     n = Rf.shape[0]
-    tr = np.zeros(n)
-    for i in range(K):
-        tr = tr + Rf[:, i, i].real
-    delta = float(loading) * (tr / K)
-    L = np.zeros((n, K, K), dtype=np.complex128)
-    good = np.ones(n, dtype=bool)
     with np.errstate(all="ignore"):
-        for j in range(K):
-            d = Rf[:, j, j].real + delta
-            for p in range(j):
-                d = d - (L[:, j, p].real ** 2 + L[:, j, p].imag ** 2)
-            good &= (d > 0) & np.isfinite(d)
-            piv = np.sqrt(d)
-            L[:, j, j] = piv
-            for i in range(j + 1, K):
-                v = Rf[:, i, j].copy()
-                for p in range(j):
-                    v = v - L[:, i, p] * np.conj(L[:, j, p])
-                L[:, i, j] = v / piv
+        L, good = _cholesky_loaded(Rf, loading)
         w = np.empty((n, a.shape[0], K), dtype=np.complex128)
         for b in range(a.shape[0]):
             y = np.zeros((n, K), dtype=np.complex128)
@@ -98,6 +119,94 @@ def mvdr_weights(R, steer, loading):
     conventional = np.conj(a) / (np.abs(a) ** 2).sum(axis=1)[:, None]
     w[~good] = conventional
     return w.reshape(batch + (a.shape[0], K)), good.astype(np.int32).reshape(batch)
+
+
+def uca_steering(n_surv, radius_wavelengths, angles_deg):
+    """Steering vectors of a uniform circular array of ``n_surv`` elements on a circle of ``radius_wavelengths``, element k at
+    the azimuth ``2 pi k / n_surv``, one row per angle (degrees of azimuth): ``a[g][k] = exp(2j pi r cos(theta_g - 2 pi k /
+    n_surv))``, complex128 ``[n_grid, n_surv]`` -- a ``steer`` table for :func:`bearing` and :meth:`Ambiguity.bearing_dev`
+    (rounded to complex64 and uploaded).  Pure NumPy."""
+    theta = np.deg2rad(np.atleast_1d(np.asarray(angles_deg, dtype=np.float64)))
+    phi = 2.0 * np.pi * np.arange(int(n_surv), dtype=np.float64) / int(n_surv)
+    return np.exp(2j * np.pi * float(radius_wavelengths) * np.cos(theta[:, None] - phi[None, :]))
+
+
+def bearing_powers(snap, steer, R=None, loading=0.0):
+    """The scan behind :func:`bearing`: ``(P [n, G], t^H t [n], usable [n] bool, adaptive bool)`` for snapshots ``[n, K]`` of
+    one CPI; rows of snapshots that are all zero or not finite are scanned as zeros and flagged not usable."""
+    s = np.ascontiguousarray(np.atleast_2d(np.asarray(snap, dtype=np.complex128)))
+    a = np.atleast_2d(np.asarray(steer, dtype=np.complex128))
+    n, K = s.shape
+    G = a.shape[0]
+    if a.shape[1] != K or G < 3:
+        raise ValueError("steer must be [G >= 3, K] for snapshots [n, K]")
+    L, adaptive = np.eye(K, dtype=np.complex128), False
+    with np.errstate(all="ignore"):
+        if R is not None:
+            if not (np.isfinite(loading) and loading >= 0):
+                raise ValueError("loading must be finite and not negative")
+            R = np.asarray(R, dtype=np.complex128)
+            if R.shape != (K, K):
+                raise ValueError("R must be [K, K]")
+            Lc, good = _cholesky_loaded(R[None], loading)
+            if good[0]:
+                L, adaptive = Lc[0], True
+        v = _forward_solve(L, a)
+        vv = np.zeros(G)
+        for k in range(K):
+            vv = vv + (v[:, k].real ** 2 + v[:, k].imag ** 2)
+        usable = np.isfinite(s.view(np.float64)).all(axis=1) & (s != 0).any(axis=1)
+        t = _forward_solve(L, np.where(usable[:, None], s, 0))
+        tt = np.zeros(n)
+        for k in range(K):
+            tt = tt + (t[:, k].real ** 2 + t[:, k].imag ** 2)
+        num = np.abs(t @ np.conj(v).T) ** 2
+        P = np.where(vv > 0, num / np.where(vv > 0, vv, 1.0), 0.0)
+    return P, tt, usable, adaptive
+
+
+def bearing(snap, steer, R=None, loading=0.0, wrap=False):
+    """blah2hip_amb_bearing_dev restated in fp64 NumPy for the detections of ONE CPI.  ``snap``: ``[n, K]`` (or ``[K]``) array
+    snapshots, ``steer``: the table ``[G, K]``, ``R``: the CPI's Hermitian ``[K, K]`` covariance (the lower triangle is read) or
+    None.  With ``R_l = R + loading (tr R / K) I = L L^H`` (the Cholesky factor and substitution order of
+    :func:`mvdr_weights`; ``L = I`` without ``R`` or where the factorisation fails), ``v_g = L^-1 a_g`` and ``t = L^-1 s``:
+    ``P(g) = |v_g^H t|^2 / (v_g^H v_g)`` (0 where the denominator is 0), ``index`` the first largest ``P``, ``offset`` the
+    vertex of the parabola through the linear powers at ``index - 1, index, index + 1`` (0 where it does not open downwards,
+    and at an end of the grid unless ``wrap`` closes it), ``power = P(index)``, ``coherence = power / (t^H t)``.  A snapshot
+    that is all zero or not finite has index -1 and zeros elsewhere.  Returns ``(index int32, offset, power, coherence,
+    adaptive int32)``, arrays ``[n]`` (scalars for a ``[K]`` snapshot)."""
+    single = np.ndim(snap) == 1
+    P, tt, ok, good = bearing_powers(snap, steer, R, loading)
+    n, G = P.shape
+    with np.errstate(all="ignore"):
+        idx = np.argmax(P, axis=1)                            # the first of equal maxima
+        rows = np.arange(n)
+        p0 = P[rows, idx]
+        pm, pp = P[rows, (idx - 1) % G], P[rows, (idx + 1) % G]
+        den = (pm - 2.0 * p0) + pp
+        inner = (idx > 0) & (idx < G - 1)
+        use = (inner | bool(wrap)) & (den < 0)
+        offset = np.where(use, 0.5 * (pm - pp) / np.where(use, den, 1.0), 0.0)
+        coherence = np.where(tt > 0, p0 / np.where(tt > 0, tt, 1.0), 0.0)
+    index = np.where(ok, idx, -1).astype(np.int32)
+    offset, power, coherence = (np.where(ok, x, 0.0) for x in (offset, p0, coherence))
+    adaptive = np.where(ok, 1 if good else 0, 0).astype(np.int32)
+    if single:
+        return int(index[0]), float(offset[0]), float(power[0]), float(coherence[0]), int(adaptive[0])
+    return index, offset, power, coherence, adaptive
+
+
+def bearing_degrees(index, offset, angles_deg, wrap=False):
+    """``index + offset`` of :func:`bearing` / ``bearing_dev`` as an angle on the uniformly spaced grid ``angles_deg``:
+    ``angles_deg[0] + (index + offset) * step``, modulo 360 when ``wrap`` is set; NaN where index is -1."""
+    ang = np.asarray(angles_deg, dtype=np.float64)
+    step = ang[1] - ang[0]
+    index = np.asarray(index)
+    deg = ang[0] + (index.astype(np.float64) + np.asarray(offset, dtype=np.float64)) * step
+    if wrap:
+        deg = np.mod(deg, 360.0)
+    deg = np.where(index < 0, np.nan, deg)
+    return deg if deg.ndim else float(deg)
 
 
 class Map:
@@ -368,6 +477,16 @@ class Ambiguity:
         pointers/ints): ``d_snap`` is complex64 ``[n_lists][cap][n_surv]``, list l reads the channel maps of CPI
         ``l % n_cpi``."""
         check(self._L.blah2hip_amb_snapshot_dev(self._h, d_map, n_surv, n_cpi, d_dets, cap, d_count, n_lists, d_snap, stream))
+
+    def bearing_dev(self, d_map, n_surv, n_cpi, d_dets, cap, d_count, n_lists, d_steer, n_grid, d_out, d_cov=None, loading=0.0,
+                    wrap=False, stream=0):
+        """A bearing per record of ``n_lists`` detection lists (blah2hip_amb_bearing_dev; raw pointers/ints): the snapshot
+        under each record scanned over the DEVICE table ``d_steer`` (complex64 ``[n_grid][n_surv]``), whitened by the CPI's
+        covariance ``d_cov`` (complex128 ``[n_cpi][n_surv][n_surv]``, as ``covariance_dev`` writes it) with diagonal
+        ``loading`` -- or the Bartlett scan where ``d_cov`` is None.  ``d_out`` is ``[n_lists][cap]`` of
+        :data:`BEARING_DTYPE`; list l reads CPI ``l % n_cpi``.  :func:`bearing` is the same in NumPy."""
+        check(self._L.blah2hip_amb_bearing_dev(self._h, d_map, n_surv, n_cpi, d_dets, cap, d_count, n_lists, d_cov, float(loading),
+                                               d_steer, n_grid, _lib.BEARING_WRAP if wrap else 0, d_out, stream))
 
     def beamform(self, maps, w):
         """Host arrays, one CPI: the channel maps ``maps`` (:class:`Map` or complex64 ``[n_doppler, n_delay]`` arrays, one per
@@ -651,6 +770,10 @@ class Interpolate:
 
 
 DET_DTYPE = np.dtype([("row", np.int32), ("col", np.int32), ("delay", np.float64), ("doppler", np.float64), ("snr", np.float64)])
+
+
+BEARING_DTYPE = np.dtype([("index", np.int32), ("adaptive", np.int32), ("offset", np.float64), ("power", np.float64),
+                          ("coherence", np.float64)])
 
 
 class DetectionFinisher:

@@ -240,6 +240,7 @@ int blah2hip_amb_set_option(blah2hip_amb_t h, int option, int64_t value);
 #define BLAH2HIP_INFO_DETECT_GRID 14         /* workgroups per CPI of the last blah2hip_detect_dev launch */
 #define BLAH2HIP_INFO_DETECT_TILED 15        /* 1: that launch spread a CPI's hits over several workgroups (cap beyond one LDS tile of 1024
                                               * hits), 0: one workgroup per CPI */
+#define BLAH2HIP_INFO_BEARING_GRID 16         /* workgroups per list of the last blah2hip_amb_bearing_dev launch */
 int blah2hip_amb_get_info(blah2hip_amb_t h, int key, int64_t *value);
 
 /* Ambiguity::process + Map::set_metrics on host buffers (blah2.cpp:278-279).
@@ -372,6 +373,51 @@ int blah2hip_amb_mvdr_weights_dev(blah2hip_amb_t h, const double *d_cov, uint32_
 int blah2hip_amb_snapshot_dev(blah2hip_amb_t h, const void *d_map, uint32_t n_surv, uint32_t n_cpi,
                               const blah2hip_det_t *d_dets, uint32_t cap, const uint32_t *d_count, uint32_t n_lists,
                               float *d_snap, void *stream);
+/* The bearing of every detection: the angle scan of its array snapshot s (the n_surv channel cells under the record, gathered
+ * from d_map as blah2hip_amb_snapshot_dev gathers them; no snapshot buffer in between) over a steering table a_g,
+ * g = 0 .. n_grid - 1 -- d_steer, a DEVICE array [n_grid][n_surv] of (re, im) fp32 pairs: any array geometry, the call knows
+ * no angles.  With d_cov [n_cpi][n_surv][n_surv] as blah2hip_amb_covariance_dev writes it (the lower triangle is read) it is
+ * the adaptive matched filter's scan, which reads the target's bearing in a cell that also holds an interferer the
+ * covariance has seen; with d_cov NULL it is the conventional (Bartlett) scan:
+ *   R_l = R[c] + loading * (tr R[c] / n_surv) * I = L L^H   (Cholesky, formed as blah2hip_amb_mvdr_weights_dev forms it;
+ *                                                            d_cov NULL: L = I)
+ *   v_g = L^-1 a_g,  t = L^-1 s,  P(g) = |v_g^H t|^2 / (v_g^H v_g)   (0 where v_g^H v_g is 0)
+ *   index     = argmax P, the LOWEST g on an exact tie
+ *   offset    = (P- - P+) / (2 (P- - 2 P0 + P+)) on the linear powers at index - 1, index, index + 1: a fraction of a grid step
+ *               to add to index; 0 where the denominator is not negative
+ *   power     = P(index),   coherence = P(index) / (t^H t), in [0, 1]: 1 for a noise-free plane wave on the grid
+ * Ends of the grid: with BLAH2HIP_BEARING_WRAP the grid is a closed circle (360 degrees of a circular array) and the
+ * neighbours of index 0 and n_grid - 1 wrap; without it a peak at an end has offset 0.  A snapshot that is all zero or not
+ * finite gives index -1 and zeros in the other fields.  A CPI whose factorisation meets a pivot that is not finite or not
+ * positive (an all-zero CPI, a NaN in the maps) falls back to L = I and marks its records adaptive = 0; the other CPIs of
+ * the batch are unaffected, bit for bit -- the rule of blah2hip_amb_mvdr_weights_dev.  An identity covariance with loading 0
+ * gives the bits of the d_cov = NULL call in every field but adaptive.
+ * d_dets [n_lists][cap], d_count [n_lists], the rule that list l belongs to CPI l mod n_cpi (maps and covariance) and d_map are
+ * those of blah2hip_amb_snapshot_dev; d_out is [n_lists][cap].  Slots beyond a list's count (a count beyond cap: cap
+ * records) and records whose row or col lies outside the map are left unwritten.
+ * Arithmetic: everything is fp64 -- the fp32 cells and steering entries convert exactly, the table is whitened and
+ * normalised in fp64 (bearing_kernel: once per workgroup into LDS, then one wave per detection, lanes over g) and nothing
+ * is rounded to fp32.  No atomics: two calls give the same bits.  Enqueues ONE kernel (BLAH2HIP_K_BEARING); no allocation,
+ * upload or synchronisation, and the call can be captured in a graph.  d_cov, d_steer, the lists and the maps are read when
+ * the kernel runs: whatever writes them must be ordered before this call on the device.
+ * BLAH2HIP_ERR_INVALID, with nothing enqueued: a NULL handle, list, count, steering table or output, cap == 0, n_cpi == 0,
+ * n_lists == 0, not a multiple of n_cpi or above 65535, n_surv outside [2, BLAH2HIP_MAX_SURV], n_surv * n_cpi above
+ * max_batch, n_grid outside [3, BLAH2HIP_MAX_BEARING_GRID], unknown flag bits, loading negative or not finite when d_cov is
+ * not NULL. */
+#define BLAH2HIP_MAX_BEARING_GRID 384     /* 360 degrees in 1 degree steps fits */
+#define BLAH2HIP_BEARING_WRAP 1u
+typedef struct blah2hip_bearing {
+  int32_t index;      /* grid index of the peak, -1: no estimate */
+  int32_t adaptive;   /* 1: the CPI's covariance was used, 0: Bartlett (d_cov NULL or a failed factorisation) */
+  double offset;      /* fraction of a grid step, added to index */
+  double power;
+  double coherence;
+} blah2hip_bearing_t;
+int blah2hip_amb_bearing_dev(blah2hip_amb_t h, const void *d_map, uint32_t n_surv, uint32_t n_cpi,
+                             const blah2hip_det_t *d_dets, uint32_t cap, const uint32_t *d_count, uint32_t n_lists,
+                             const double *d_cov, double loading,
+                             const float *d_steer, uint32_t n_grid, uint32_t flags,
+                             blah2hip_bearing_t *d_out, void *stream);
 
 /* ---- CfarDetector1D (CfarDetector1D.h:46-55) ---------------------------- */
 /* dev: d_map/d_metrics as written by blah2hip_amb_process_dev (NULL = the
@@ -675,7 +721,8 @@ int blah2hip_amb_result_ptrs(blah2hip_amb_t h, const void **d_map, const double 
 #define BLAH2HIP_K_ROTATE 6   /* Doppler-centre shift (asymmetric limits only) */
 #define BLAH2HIP_K_BEAM 7     /* beamform_kernel (blah2hip_amb_beamform_dev; its metrics_kernel counts under _METRICS) */
 #define BLAH2HIP_K_COV 8      /* array_cov_kernel + cov_fold_kernel (blah2hip_amb_covariance_dev) */
-#define BLAH2HIP_K_COUNT 9
+#define BLAH2HIP_K_BEARING 9  /* bearing_kernel (blah2hip_amb_bearing_dev) */
+#define BLAH2HIP_K_COUNT 10
 /* enable != 0: every dev call brackets each kernel with hipEvents */
 int blah2hip_amb_set_timing(blah2hip_amb_t h, int enable);
 /* synchronises the recorded events; ms_total[k] = summed duration of kernel k
