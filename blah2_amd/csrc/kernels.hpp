@@ -25,6 +25,7 @@
 #include "fft_wave1k.hpp"
 #include "fft_pfa513.hpp"
 #include "bufload.hpp"
+#include "doppler_walk.hpp"
 #include "trace.hpp"
 
 namespace blah2 {
@@ -1456,9 +1457,11 @@ __global__ __launch_bounds__(64 * NCOL) void doppler_tile_kernel(DopplerArgs a, 
       nt[j] = Rt[idx < cells ? row * 16 + c : 0];
     }
   };
-  int it = blockIdx.x;
-  if (it < nTilesAll) tile_load(it);
-  for (; it < nTilesAll; it += gridDim.x) {
+  // the walk (doppler_walk.hpp): `it` is this iteration's tile, `nx` the next one's (-1: none)
+  int it = doppler_walk_tile(blockIdx.x, gridDim.x, 0, nTilesAll);
+  if (it >= 0) tile_load(it);
+  for (int wk = 1, nx; it >= 0; it = nx, wk++) {
+    nx = doppler_walk_tile(blockIdx.x, gridDim.x, wk, nTilesAll);
     const int cpi = it / tilesPerCpi, sub = it - cpi * tilesPerCpi;
     const int col0 = sub * NCOL;
     // phase 1: the tile, transposed into the per-column regions
@@ -1491,7 +1494,7 @@ __global__ __launch_bounds__(64 * NCOL) void doppler_tile_kernel(DopplerArgs a, 
     }
 #pragma unroll
     for (int k = NR; k < 16; k++) v[k] = cmake(0.f, 0.f);
-    if (it + (int)gridDim.x < nTilesAll) tile_load(it + gridDim.x);
+    if (nx >= 0) tile_load(nx);
     __builtin_amdgcn_wave_barrier();
     W::fwd_s1(t, v, tw1, region);
     __builtin_amdgcn_wave_barrier();
@@ -1637,10 +1640,12 @@ template <int NCOL> __global__ __launch_bounds__(64 * NCOL, 4) void doppler_tile
       nt[j] = Rt[idx < cells ? (NCOL == 16 ? idx : (idx >> SH) * 16 + (idx & (NCOL - 1))) : 0];
     }
   };
-  int it = blockIdx.x;
-  if (it < nTilesAll) tile_load(it, 0, PRE);
+  // the walk (doppler_walk.hpp): `it` is this iteration's tile, `nx` the next one's (-1: none)
+  int it = doppler_walk_tile(blockIdx.x, gridDim.x, 0, nTilesAll);
+  if (it >= 0) tile_load(it, 0, PRE);
   __syncthreads(); // tables
-  for (; it < nTilesAll; it += gridDim.x) {
+  for (int wk = 1, nx; it >= 0; it = nx, wk++) {
+    nx = doppler_walk_tile(blockIdx.x, gridDim.x, wk, nTilesAll);
     const int cpi = it / tilesPerCpi, sub = it - cpi * tilesPerCpi;
     const int col0 = sub * NCOL;
     // phase 1: the tile, transposed into the per-column regions
@@ -1662,7 +1667,7 @@ template <int NCOL> __global__ __launch_bounds__(64 * NCOL, 4) void doppler_tile
 #pragma unroll
     for (int k = 0; k < NR; k++) // rows beyond nD: a valid cell times 0 (NCOL = 8 recomputes the clamped row: nine registers it needs elsewhere)
       v[k] = cmul(csub(region[NCOL == 16 ? ridx[k] : min(t + T * k, nD - 1)], r0), ch[k]);
-    if (it + (int)gridDim.x < nTilesAll) tile_load(it + gridDim.x, 0, PRE);
+    if (nx >= 0) tile_load(nx, 0, PRE);
     __builtin_amdgcn_wave_barrier();
     D1_T(2)
     K::transform<-1, 9>(t, v, tw, region);
@@ -1754,6 +1759,12 @@ constexpr int DOPP_ND = 513, DOPP_NCOL = 16, DOPP_NT = 512, DOPP_NR = (DOPP_ND *
 constexpr int DOPP_LDS_ELEMS = DOPP_NCOL * DOPP_ND;
 __global__ __launch_bounds__(DOPP_NT, 4) void doppler_pfa513_kernel(DopplerArgs a, int nCpi)
 {
+#ifdef DOPW_TRACE
+  uint64_t tr[8] = {0, 0, 0, 0, 0, 0, 0, 0}, t0_ = __builtin_amdgcn_s_memtime();
+#define DP_T(k) { const uint64_t now_ = __builtin_amdgcn_s_memtime(); tr[k] += now_ - t0_; t0_ = now_; }
+#else
+#define DP_T(k)
+#endif
   using K = Pfa513;
   constexpr int ND = DOPP_ND, NCOL = DOPP_NCOL, NT = DOPP_NT, NR = DOPP_NR, RS = NT / NCOL; // RS: rows per pass
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1780,9 +1791,11 @@ __global__ __launch_bounds__(DOPP_NT, 4) void doppler_pfa513_kernel(DopplerArgs 
       nt[j] = Rt[idx < cells ? idx : 0];
     }
   };
-  int it = blockIdx.x;
-  if (it < nTilesAll) tile_load(it);
-  for (; it < nTilesAll; it += gridDim.x) {
+  // the walk (doppler_walk.hpp): `it` is this iteration's tile, `nx` the next one's (-1: none)
+  int it = doppler_walk_tile(blockIdx.x, gridDim.x, 0, nTilesAll);
+  if (it >= 0) tile_load(it);
+  for (int wk = 1, nx; it >= 0; it = nx, wk++) {
+    nx = doppler_walk_tile(blockIdx.x, gridDim.x, wk, nTilesAll);
     const int cpi = it / tilesPerCpi, sub = it - cpi * tilesPerCpi;
     const int col0 = sub * NCOL;
     // phase 1: the tile, transposed into the per-column regions
@@ -1793,10 +1806,12 @@ __global__ __launch_bounds__(DOPP_NT, 4) void doppler_pfa513_kernel(DopplerArgs 
       for (int j = 0; j < NR; j++)
         if (tl + NT * j < cells) dst[RS * j] = nt[j];
     }
+    DP_T(0)
     __syncthreads();
+    DP_T(1)
 
     // phase 2: next tile's loads, then this half wave's column through the two steps (region = exchange region)
-    if (it + (int)gridDim.x < nTilesAll) tile_load(it + gridDim.x);
+    if (nx >= 0) tile_load(nx);
     const cf r0 = region[0];
     cf v[27];
     // (lane-derived addresses are recomputed per tile: kept live across the walk, the 46 of them spill)
@@ -1806,10 +1821,12 @@ __global__ __launch_bounds__(DOPP_NT, 4) void doppler_pfa513_kernel(DopplerArgs 
       K::dft19_store(v, region + l1);
     }
     __builtin_amdgcn_wave_barrier();
+    DP_T(2)
     if (l < K::N2) {
       K::load2(relaunder(l), region, v);
       K::dft27(v);
       if (l == 0) v[0] = cmake(v[0].x + (float)ND * r0.x, v[0].y + (float)ND * r0.y);
+      DP_T(3)
       // phase 3: rotate rows by nD/2 + 1 and park the column back in its region
       const unsigned ob = (unsigned)relaunder(ob0);
 #pragma unroll
@@ -1818,7 +1835,9 @@ __global__ __launch_bounds__(DOPP_NT, 4) void doppler_pfa513_kernel(DopplerArgs 
         region[o < (unsigned)ND ? o : o - ND] = v[k1];
       }
     }
+    DP_T(4)
     __syncthreads();
+    DP_T(1)
 
     // phase 4: coalesced row-segment stores + Map::set_metrics partials
     double lsum = 0.0;
@@ -1843,6 +1862,7 @@ __global__ __launch_bounds__(DOPP_NT, 4) void doppler_pfa513_kernel(DopplerArgs 
     }
     wave_sum_max(lsum, lmax);
     if ((tid & 63) == 0) { const int wl = relaunder(tid) >> 6; wsum[wl] = lsum; wmax[wl] = lmax; }
+    DP_T(5)
     __syncthreads(); // also: every thread has taken its rows out of the regions
     if (tid == 0) {
       double sacc = 0.0;
@@ -1852,8 +1872,13 @@ __global__ __launch_bounds__(DOPP_NT, 4) void doppler_pfa513_kernel(DopplerArgs 
       a.partSum[part] = sacc;
       a.partMax[part] = m;
     }
+    DP_T(1)
   }
+#ifdef DOPW_TRACE // buckets: fill, barriers, next tile's requests + step 1 (19-point), step 2 (27-point), park, stores + metrics
+  if ((tid & 63) == 0) trace_finish("dopp", tr, blockIdx.x == 0);
+#endif
 }
+#undef DP_T
 
 // The reduction of metrics_kernel (below) by the 256 threads of a workgroup: the same order of operations, so that the
 // fused finish and the separate launch give the same bits.
