@@ -271,6 +271,26 @@ class Detection:
         return int(self.delay.size)
 
 
+class _FirTaps:
+    """Given taps for ``Ambiguity.set_fir``: a complex64 device tensor [CPIs][nBins] (anything with torch's ``data_ptr``,
+    ``shape``, ``dtype``, ``is_contiguous``) in the place of a WienerHopf handle.  Holds the tensor: the ambiguity handle
+    reads its memory on every call."""
+
+    _h = True  # never closed
+
+    def __init__(self, taps, delay_min):
+        if len(taps.shape) != 2 or taps.shape[0] < 1 or taps.shape[1] < 1:
+            raise ValueError("set_fir: taps of shape [CPIs][nBins]")
+        if "complex64" not in str(taps.dtype) or not taps.is_contiguous() or not getattr(taps, "is_cuda", False):
+            raise ValueError("set_fir: a contiguous complex64 tensor on the device")
+        self.taps = taps
+        self.max_batch, self.n_bins = int(taps.shape[0]), int(taps.shape[1])
+        self.delay_min = int(delay_min)
+
+    def taps_dev(self):
+        return self.taps.data_ptr(), self.n_bins, self.delay_min
+
+
 class Ambiguity:
     """src/process/ambiguity/Ambiguity.h:34-58."""
 
@@ -567,22 +587,31 @@ class Ambiguity:
         the last launch."""
         check(self._L.blah2hip_amb_set_option(self._h, _lib.OPT_CFAR2D_GRID, int(n)))
 
-    def set_fir(self, wiener_hopf):
+    def set_fir(self, wiener_hopf, delay_min=None):
         """Run the clutter filter's FIR fused into the range kernel with the taps of ``wiener_hopf`` (a WienerHopf whose
-        ``estimate_dev_fmt`` precedes each ``process_dev`` on the same stream); None: back to the plain range kernels."""
+        ``estimate_dev_fmt`` precedes each ``process_dev`` on the same stream); None: back to the plain range kernels.
+        With ``delay_min`` given, ``wiener_hopf`` is instead a contiguous complex64 device tensor [CPIs][nBins] of taps, tap k
+        of a row at lag ``delay_min + k``: given taps, no estimate (a row per CPI of the calls that follow)."""
         if wiener_hopf is None:
             check(self._L.blah2hip_amb_set_fir(self._h, None, 0, 0))
         else:
+            if delay_min is not None:
+                wiener_hopf = _FirTaps(wiener_hopf, delay_min)
             p, nb, dm = wiener_hopf.taps_dev()
             check(self._L.blah2hip_amb_set_fir(self._h, p, nb, dm))
         # the ambiguity handle reads the filter handle's device array on every call: keep it alive, and remember how many
         # CPIs' taps it holds
         self._fir = wiener_hopf
 
-    def fir_fusable(self, wiener_hopf, fmt):
+    def fir_fusable(self, wiener_hopf, fmt, delay_min=None):
         """None if ``set_fir(wiener_hopf)`` is covered for samples in format ``fmt`` (FMT_C32 / FMT_I16), else the reason
-        (always one for FMT_I8: the fused kernel has no int8 form, an 8-bit chain runs the two-stage filter)."""
-        _, nb, dm = wiener_hopf.taps_dev()
+        (always one for FMT_I8: the fused kernel has no int8 form, an 8-bit chain runs the two-stage filter).  With
+        ``delay_min`` given, ``wiener_hopf`` is the number of taps (or a tensor of taps as for ``set_fir``)."""
+        if delay_min is None:
+            _, nb, dm = wiener_hopf.taps_dev()
+        else:
+            nb = int(wiener_hopf) if isinstance(wiener_hopf, (int, np.integer)) else _FirTaps(wiener_hopf, delay_min).n_bins
+            dm = int(delay_min)
         rc = self._L.blah2hip_amb_fir_fusable(self._h, int(fmt), nb, dm)
         if rc == _lib.OK:
             return None
