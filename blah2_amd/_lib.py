@@ -27,6 +27,8 @@ OPT_LEAK_COMPENSATION = 7
 OPT_HOT_COLUMNS = 8
 OPT_CFAR2D_SEG_ROWS, OPT_CFAR2D_GRID = 9, 10
 OPT_MULTI_SURV_RANGE = 11
+OPT_RANGE_WALK = 12
+WALK_AUTO, WALK_STATIC, WALK_TICKET = 0, 1, 2
 MULTI_AUTO, MULTI_SHARED, MULTI_PER_CHANNEL = 0, 1, 2
 MAX_SURV = 8
 MAX_BEAMS = 8

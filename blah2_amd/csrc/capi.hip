@@ -79,6 +79,8 @@ struct blah2hip_amb_s {
   int numCU = 256;
   int rangeGridForce = 0;           // BLAH2HIP_OPT_RANGE_GRID (0 = the launched kernel's residency)
   int rangeGridLast = 0;            // BLAH2HIP_INFO_RANGE_GRID: workgroup cap of the last launch
+  int rangeWalk = 0;                // BLAH2HIP_OPT_RANGE_WALK (0 = the engine's choice)
+  uint32_t *d_rangeWalk = nullptr;  // rangew1k_kernel's ticket heads and exit counter (range_walk.hpp), zero between launches
   void *h_pin = nullptr;            // pinned host staging of the c64 entry point
   size_t h_pin_bytes = 0;
 
@@ -408,6 +410,9 @@ template <class In> int launch_rangew_t(blah2hip_amb_s *h, const RangeArgs &a, I
 // (radix 8-8-8-4 twiddles + the lane butterflies) and the kernel follows that count, not its occupancy.
 // F = 4096 on the two-wave kernel
 
+#ifndef RANGEW1K_WALK_DEFAULT
+#define RANGEW1K_WALK_DEFAULT BLAH2HIP_WALK_TICKET
+#endif
 // F = 1024 on the one-wave kernel with 16 points per lane (four waves per SIMD)
 bool use_wave1k_range(const blah2hip_amb_s *h, int nPulses)
 {
@@ -445,12 +450,24 @@ template <class In> int launch_rangew1k_t(blah2hip_amb_s *h, const RangeArgs &a,
   const bool shortx = a.plan.segLen <= 9 * 64;
   const bool out7 = a.plan.nDelay <= 7 * 64;
   const bool reuse = a.plan.segLen == 9 * 64 && a.plan.nDelay <= 7 * 64 + 1; // whole-register overlap of consecutive y' windows
-  auto kern = reuse ? (out7 ? rangew1k_kernel<In, true, true, true> : rangew1k_kernel<In, true, false, true>)
+  const int grid = std::min<int>((a.nPulses + RANGEW1K_WAVES - 1) / RANGEW1K_WAVES, range_grid_cap(h, lds, RANGEW1K_WAVES, 4 * RANGEW1K_WAVES_PER_SIMD));
+  // the pulse walk (BLAH2HIP_OPT_RANGE_WALK).  The engine's choice: tickets wherever a wave walks more than one pulse
+  // (measured at 43 pulses per wave: the static walk's last wave leaves eight pulse times behind its median wave, DESIGN.md
+  // section 7 item 11); a launch with at most a pulse per wave has nothing to balance and keeps the static form, which
+  // starts without waiting for a counter
+  const int walk = h->rangeWalk ? h->rangeWalk
+                   : a.nPulses > grid * RANGEW1K_WAVES ? RANGEW1K_WALK_DEFAULT : BLAH2HIP_WALK_STATIC;
+  const bool ticket = walk == BLAH2HIP_WALK_TICKET;
+  auto kern = ticket ? (reuse ? (out7 ? rangew1k_kernel<In, true, true, true, true> : rangew1k_kernel<In, true, false, true, true>)
+                        : shortx ? (out7 ? rangew1k_kernel<In, true, true, false, true> : rangew1k_kernel<In, true, false, false, true>)
+                                 : (out7 ? rangew1k_kernel<In, false, true, false, true> : rangew1k_kernel<In, false, false, false, true>))
+              : reuse ? (out7 ? rangew1k_kernel<In, true, true, true> : rangew1k_kernel<In, true, false, true>)
               : shortx ? (out7 ? rangew1k_kernel<In, true, true> : rangew1k_kernel<In, true, false>)
                        : (out7 ? rangew1k_kernel<In, false, true> : rangew1k_kernel<In, false, false>);
   LDSCFG(kern, lds);
-  const int grid = std::min<int>((a.nPulses + RANGEW1K_WAVES - 1) / RANGEW1K_WAVES, range_grid_cap(h, lds, RANGEW1K_WAVES, 4 * RANGEW1K_WAVES_PER_SIMD));
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * RANGEW1K_WAVES), lds, st, a, in);
+  RangeArgs aw = a;
+  aw.walk = h->d_rangeWalk;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * RANGEW1K_WAVES), lds, st, aw, in);
   HIPCHK(hipGetLastError());
   h->lastRange = BLAH2HIP_RANGE_WAVE1K;
   return BLAH2HIP_OK;
@@ -1219,6 +1236,8 @@ int blah2hip_amb_create_ex(int32_t delay_min, int32_t delay_max, int32_t doppler
   HIPCHK(hipMalloc(&h->d_partMax, (size_t)h->nParts * max_batch * sizeof(float)));
   HIPCHK(hipMalloc(&h->d_tickets, max_batch * sizeof(uint32_t)));
   HIPCHK(hipMemset(h->d_tickets, 0, max_batch * sizeof(uint32_t)));
+  HIPCHK(hipMalloc(&h->d_rangeWalk, RWALK_WORDS * sizeof(uint32_t)));
+  HIPCHK(hipMemset(h->d_rangeWalk, 0, RWALK_WORDS * sizeof(uint32_t)));
   HIPCHK(hipMalloc(&h->d_detWords, 2 * max_batch * sizeof(uint32_t)));
   HIPCHK(hipMemset(h->d_detWords, 0, 2 * max_batch * sizeof(uint32_t)));
   HIPCHK(hipMalloc(&h->d_metrics, 2 * max_batch * sizeof(double)));
@@ -1268,12 +1287,15 @@ int blah2hip_amb_destroy(blah2hip_amb_t h)
   // teardown: nothing useful can be done with a failure here
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
+#ifdef RANGEW_TRACE
+  trace_rw_dump();
+#endif
   for (void *p : {(void *)h->d_tw, (void *)h->d_dopW, (void *)h->d_R, (void *)h->d_map,
                   (void *)h->d_partSum, (void *)h->d_partMax, (void *)h->d_tickets, (void *)h->d_metrics,
                   (void *)h->d_doppler, h->d_in, (void *)h->d_rot,
                   (void *)h->d_hits, (void *)h->d_count, (void *)h->d_sat, (void *)h->d_dtw, (void *)h->d_chirp,
                   (void *)h->d_bf, (void *)h->d_bfn, (void *)h->d_H, (void *)h->d_dopW64, (void *)h->d_hotCount, (void *)h->d_firK0,
-                  (void *)h->d_detWords})
+                  (void *)h->d_detWords, (void *)h->d_rangeWalk})
     if (p) (void)hipFree(p);
   for (auto &t : h->alphaTables)
     if (t.d) (void)hipFree(t.d);
@@ -1312,6 +1334,11 @@ int blah2hip_amb_set_option(blah2hip_amb_t h, int option, int64_t value)
   case BLAH2HIP_OPT_RANGE_GRID:
     if (value < 0 || value > (1 << 20)) return fail(BLAH2HIP_ERR_INVALID, "range grid outside [0, 2^20]");
     h->rangeGridForce = (int)value;
+    return BLAH2HIP_OK;
+  case BLAH2HIP_OPT_RANGE_WALK:
+    if (value != 0 && value != BLAH2HIP_WALK_STATIC && value != BLAH2HIP_WALK_TICKET)
+      return fail(BLAH2HIP_ERR_INVALID, "range walk: 0 (the engine's choice), BLAH2HIP_WALK_STATIC or _TICKET");
+    h->rangeWalk = (int)value;
     return BLAH2HIP_OK;
   case BLAH2HIP_OPT_RANGE_KERNEL:
     if (value != 0 && value != BLAH2HIP_RANGE_WAVE && value != BLAH2HIP_RANGE_E16 && value != BLAH2HIP_RANGE_WAVE1K &&

@@ -27,6 +27,7 @@
 #include "bufload.hpp"
 #include "doppler_walk.hpp"
 #include "trace.hpp"
+#include "range_walk.hpp"
 
 namespace blah2 {
 
@@ -52,6 +53,7 @@ struct RangeArgs {
   cf *out;             // tiled range map, see rmap_index()
   int64_t cpiStride;   // samples between consecutive CPIs of the batch
   int32_t nPulses;     // nCpi * nDoppler
+  uint32_t *walk = nullptr; // rangew1k_kernel's ticketed walk: RWALK_WORDS counters (range_walk.hpp), zero between launches
 };
 
 // segment s of the pulse at sample index pulseBase: v[k] = x'[t + T*k], yv[k] = y'[t + T*k]
@@ -733,7 +735,41 @@ __device__ __forceinline__ void w1k_issue_y(const In &in, const RangePlan &p, in
 // overlap (nDelay - 1 of every segLen + nDelay - 1 samples) is otherwise read again, and at this kernel's streaming
 // rate an XCD's L2 has turned over between two segments of a wave: the re-read comes from HBM (PMC: 1.08-1.14 x the
 // algorithmic bytes at F = 2048, more at F = 1024 with its shorter segments).
-template <class In, bool SHORTX, bool OUT7, bool REUSE = false>
+//
+// TICKET: the waves take their pulses from the eight heads of a.walk (range_walk.hpp) instead of walking b*12 + w + k*G*12.
+// The ticket for the next pulse is requested one segment before the pulse's first windows are (in front of the x' request
+// of the last-but-one segment), so it has long returned when the last segment starts and the prefetch of the next pulse's
+// windows never waits for it; no earlier, so that no wave holds a pulse it will not start for most of a pulse time.  With
+// one segment per pulse that is one pulse ahead.  Every wave counts itself out on a.walk's exit word when it leaves, with
+// or without a pulse, and the last one zeroes the nine words for the next launch on the stream: no memset launch and no
+// host-side count, so a captured graph replays.  A pulse's result does not depend on which wave computes it.
+static_assert(RWALK_BLOCK == RANGEW1K_WAVES, "range_walk.hpp deals blocks of one workgroup's waves");
+// one ticket of head x: one lane asks, the wave reads the answer with range_walk_ticket_value().  The word index goes
+// through an opaque VGPR: on a wave-uniform address the compiler rewrites the atomic for a whole wave (one lane adds the number
+// of active lanes) and reads the result back AT ONCE, with an s_waitcnt vmcnt(0) behind the request -- the wait the early
+// request exists to avoid.  This way the wait sits at the first use, counted with the loads issued in between.
+__device__ __forceinline__ unsigned range_walk_request(uint32_t *walk, int head, int t)
+{
+  unsigned tk = 0;
+  if (t == 0) {
+    int word = range_walk_head_word(head);
+    asm volatile("" : "+v"(word));
+    tk = __hip_atomic_fetch_add(walk + word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  return tk;
+}
+__device__ __forceinline__ uint32_t range_walk_ticket_value(unsigned tk) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)tk); }
+// a wave leaves: the last of the launch's `waves` resets the counters (plain stores; the kernel boundary publishes them)
+__device__ __forceinline__ void range_walk_leave(uint32_t *walk, unsigned waves, int t)
+{
+  if (t != 0) return;
+  if (__hip_atomic_fetch_add(walk + RWALK_EXIT_WORD, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u == waves) {
+#pragma unroll
+    for (int x = 0; x <= RWALK_HEADS; x++) walk[x * RWALK_LINE_WORDS] = 0u;
+  }
+}
+
+template <class In, bool SHORTX, bool OUT7, bool REUSE = false, bool TICKET = false>
 __global__ __launch_bounds__(64 * RANGEW1K_WAVES, RANGEW1K_WAVES_PER_SIMD) void rangew1k_kernel(RangeArgs a, In in)
 {
   static_assert(!REUSE || SHORTX, "");
@@ -752,8 +788,30 @@ __global__ __launch_bounds__(64 * RANGEW1K_WAVES, RANGEW1K_WAVES_PER_SIMD) void 
   W::load_twiddles(t, a.tw, table, w);
   const RangePlan p = a.plan;
   const int stride = gridDim.x * RANGEW1K_WAVES;
+#ifdef RANGEW_TRACE
+  const unsigned long long trStart = wall_clock64();
+  unsigned trPulses = 0;
+#define RW_LEAVE() { if (t == 0) trace_rw_leave(blockIdx.x * RANGEW1K_WAVES + wave, stride, trStart, trPulses); }
+#else
+#define RW_LEAVE()
+#endif
   int pulse = blockIdx.x * RANGEW1K_WAVES + wave;
-  if (pulse >= a.nPulses) return;
+  int head = blockIdx.x & (RWALK_HEADS - 1); // TICKET: the head this wave pulls from
+  unsigned tk = 0;                           // TICKET: lane 0 holds the ticket requested for the next pulse
+  const auto pull = [&](int x) { return range_walk_ticket_value(range_walk_request(a.walk, x, t)); };
+  if constexpr (TICKET) {
+    pulse = range_walk_next(head, a.nPulses, pull);
+    if (pulse < 0) {
+      RW_LEAVE()
+      range_walk_leave(a.walk, stride, t);
+      return;
+    }
+  } else {
+    if (pulse >= a.nPulses) {
+      RW_LEAVE()
+      return;
+    }
+  }
   int cpi = pulse / p.nDoppler;
   int i = pulse - cpi * p.nDoppler;
   int64_t base = (int64_t)cpi * a.cpiStride + (int64_t)i * p.nCorr;
@@ -763,6 +821,8 @@ __global__ __launch_bounds__(64 * RANGEW1K_WAVES, RANGEW1K_WAVES_PER_SIMD) void 
   cf acc[16];
 #pragma unroll
   for (int e = 0; e < 16; e++) acc[e] = cmake(0.f, 0.f);
+  if constexpr (TICKET)
+    if (p.nSeg == 1) tk = range_walk_request(a.walk, head, t); // the first iteration is a pulse's last segment already
   w1k_issue_x<In, NX>(in, p, base, 0, t, true, rx);
   w1k_issue_y<In>(in, p, base, 0, t, true, ry);
 #ifdef RANGEW_TRACE // buckets: 0 loop bookkeeping, 1 wait x, 2 issue x + X transform, 3 wait y, 4 Y transform + product + issue y, 5 inverse + stores
@@ -774,7 +834,12 @@ __global__ __launch_bounds__(64 * RANGEW1K_WAVES, RANGEW1K_WAVES_PER_SIMD) void 
     int64_t nbase = base;
     if (ns == p.nSeg) {
       ns = 0;
-      npulse = pulse + stride;
+      if constexpr (TICKET) {
+        npulse = range_walk_next(head, a.nPulses, pull, true, range_walk_ticket_value(tk));
+        if (npulse < 0) npulse = a.nPulses; // no pulse left: the requests below read nothing
+      } else {
+        npulse = pulse + stride;
+      }
       ncpi = npulse / p.nDoppler;
       ni = npulse - ncpi * p.nDoppler;
       nbase = (int64_t)ncpi * a.cpiStride + (int64_t)ni * p.nCorr;
@@ -792,6 +857,8 @@ __global__ __launch_bounds__(64 * RANGEW1K_WAVES, RANGEW1K_WAVES_PER_SIMD) void 
     // them -- requested before, the compiler has to copy the 18 registers out of the loads' way
     W::s1<-1, NX>(v, w);
     __builtin_amdgcn_sched_barrier(0);
+    if constexpr (TICKET)
+      if (ns == p.nSeg - 1 && more) tk = range_walk_request(a.walk, head, t); // the next iteration is a pulse's last segment
     w1k_issue_x<In, NX>(in, p, nbase, ns, t, more, rx);
     __builtin_amdgcn_sched_barrier(0);
     W::finish<-1>(t, v, w, X); // v = X spectrum
@@ -816,6 +883,12 @@ __global__ __launch_bounds__(64 * RANGEW1K_WAVES, RANGEW1K_WAVES_PER_SIMD) void 
       if (ns != 0) {
 #pragma unroll
         for (int k = 0; k < 7; k++) ry[k] = ry[9 + k];
+        // the carried registers move HERE, in front of the requests.  Left to the compiler the copies sit at the end of
+        // the loop body: registers 9..15 are then still occupied when the loads are issued, the loads land in spare
+        // registers, and the copy out of those waits for every one of them -- an s_waitcnt vmcnt(0) at the end of every
+        // segment, nothing in flight during the x transform
+#pragma unroll
+        for (int k = 0; k < 7; k++) asm volatile("" : "+v"(ry[k]));
         w1k_issue_y<In, 7>(in, p, nbase, ns, t, more, ry);
       } else {
         w1k_issue_y<In>(in, p, nbase, ns, t, more, ry);
@@ -833,8 +906,10 @@ __global__ __launch_bounds__(64 * RANGEW1K_WAVES, RANGEW1K_WAVES_PER_SIMD) void 
       store_lags_w<OUT7 ? 7 : 16>(a.out, p, cpi, i, t, acc);
 #ifdef RANGEW_TRACE
       RW_T(5)
+      trPulses++;
       if (!more) {
         if (t == 0) trace_finish("rangew1k", tr, blockIdx.x == 0 && threadIdx.x == 0);
+        RW_LEAVE()
         break;
       }
 #else
@@ -849,6 +924,8 @@ __global__ __launch_bounds__(64 * RANGEW1K_WAVES, RANGEW1K_WAVES_PER_SIMD) void 
     s = ns;
     base = nbase;
   }
+  if constexpr (TICKET) range_walk_leave(a.walk, stride, t);
+#undef RW_LEAVE
 }
 
 // --------------------------------------------------------------------------

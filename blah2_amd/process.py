@@ -567,6 +567,13 @@ class Ambiguity:
     def set_range_grid(self, n):
         check(self._L.blah2hip_amb_set_option(self._h, _lib.OPT_RANGE_GRID, int(n)))
 
+    def set_range_walk(self, which):
+        """Pulse walk of the one-wave 1024-point range kernel: ``_lib.WALK_AUTO`` (the engine's choice), ``_STATIC``
+        or ``_TICKET`` (or 'auto' / 'static' / 'ticket').  The results are the same bits."""
+        if isinstance(which, str):
+            which = {"auto": _lib.WALK_AUTO, "static": _lib.WALK_STATIC, "ticket": _lib.WALK_TICKET}[which]
+        check(self._L.blah2hip_amb_set_option(self._h, _lib.OPT_RANGE_WALK, int(which)))
+
     def set_doppler_grid(self, n):
         """Workgroup cap of the persistent Doppler tile kernels (0 = their residency)."""
         check(self._L.blah2hip_amb_set_option(self._h, _lib.OPT_DOPPLER_GRID, int(n)))

@@ -146,6 +146,12 @@ int blah2hip_amb_get_axes(blah2hip_amb_t h, int32_t *delay, double *doppler);
 /* Execution plan, per handle.  Options take effect on the next process call. */
 #define BLAH2HIP_OPT_DOPPLER_KERNEL 1 /* BLAH2HIP_DOP_*; AUTO picks by launch size */
 #define BLAH2HIP_OPT_RANGE_GRID 2     /* workgroups of the range kernel; 0 = the launched kernel's residency */
+#define BLAH2HIP_OPT_RANGE_WALK (BLAH2HIP_OPT_MULTI_SURV_RANGE + 1) /* = 12: how the waves of the _WAVE1K range kernel get their pulses: 0 = the engine's choice,
+                                       * BLAH2HIP_WALK_STATIC (wave w of workgroup b of G: pulses b*12 + w + k*G*12) or _TICKET (each
+                                       * wave takes its next pulse from one of eight counters when it needs one; the same bits).  Other
+                                       * range kernels walk statically whatever this says */
+#define BLAH2HIP_WALK_STATIC 1
+#define BLAH2HIP_WALK_TICKET 2
 #define BLAH2HIP_OPT_RANGE_KERNEL 3   /* 0 = by transform length and launch size (4096: E16; 2048: WAVE once a launch has a pulse per wave
                                        * slot of the chip -- 8 x CUs -- else E16, e.g. a single CPI; 1024: WAVE1K from 12 x CUs pulses,
                                        * else E8); BLAH2HIP_RANGE_E16 / _WAVE (F = 2048) / _WAVE2 (F = 4096, measured 5 % slower than

@@ -8,6 +8,6 @@ cd "$(dirname "$0")/.."
 name=$1; shift
 mkdir -p tools/ab
 hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -Wno-unused-value -fno-slp-vectorize "$@" \
-  -I include -I blah2_amd/csrc blah2_amd/csrc/capi.hip blah2_amd/csrc/clutter.hip blah2_amd/csrc/spectrum.hip \
+  -I include -I blah2_amd/csrc blah2_amd/csrc/*.hip \
   -o tools/ab/libblah2hip_${name}.so
 echo "tools/ab/libblah2hip_${name}.so"
