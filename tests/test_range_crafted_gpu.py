@@ -16,8 +16,8 @@ asserted.  Finding (MI355X): every kernel holds 1e-5 on every CPI whose populate
 CPI whose ONLY populated pulse is pulse 0 misses it from nD = 512 on, in every kernel alike, in the zero-Doppler row first:
 the kernels subtract the first pulse's value r0 from a column before the transform and add nD r0 back to bin 0 (DESIGN.md
 section 3), which turns this column into nD - 1 rows of -r0 whose fp32 sum, nD times the size of the result, cancels down
-to it -- err / peak = 4.2e-5 at 513, 8.5e-5 at 1025, 1.7e-4 at 2049 for the transforms (0.8e-7 nD), up to 5.2e-4 for the
-direct kernel's sequential sum.  That is the fp32 floor of the form on an input it was not chosen for, not a wrong row:
+to it -- err / peak = 4.2e-5 at 513, 8.5e-5 at 1025, 1.7e-4 at 2049 for the transforms (0.8e-7 nD), about half that for
+the direct kernel's blocked sum (5.2e-4 at 2049 while it was one running sum).  That is the fp32 floor of the form on an input it was not chosen for, not a wrong row:
 FIRST_PULSE_MEASURED records the figure of every (nD, kernel) and that one CPI is held to twice it; all other CPIs, and
 nD = 65 throughout, stay at 1e-5.
 
@@ -265,12 +265,12 @@ def doppler_case(nD):
 # docstring), where it exceeds PEAK_TOL; that CPI's bound is twice the figure (case-to-case spread)
 FIRST_PULSE_MEASURED = {
     (512, "tile8"): 4.234e-05, (512, "tile8k"): 4.234e-05, (512, "tile16"): 4.234e-05, (512, "tile16wg"): 4.234e-05,
-    (512, "sub4"): 4.234e-05, (512, "column"): 4.234e-05, (512, "direct"): 3.022e-05,
+    (512, "sub4"): 4.234e-05, (512, "column"): 4.234e-05, (512, "direct"): 2.263e-05,
     (513, "tile8"): 4.225e-05, (513, "tile8k"): 2.991e-05, (513, "tile16"): 2.991e-05, (513, "tile16wg"): 4.225e-05,
-    (513, "sub4"): 2.991e-05, (513, "column"): 4.225e-05, (513, "direct"): 4.267e-05, (513, "pfa513"): 4.234e-05,
-    (1025, "tilew"): 5.854e-05, (1025, "tilem"): 8.472e-05, (1025, "column"): 8.472e-05, (1025, "direct"): 1.629e-04,
+    (513, "sub4"): 2.991e-05, (513, "column"): 4.225e-05, (513, "direct"): 2.726e-05, (513, "pfa513"): 4.234e-05,
+    (1025, "tilew"): 5.854e-05, (1025, "tilem"): 8.472e-05, (1025, "column"): 8.472e-05, (1025, "direct"): 4.491e-05,
     (2049, "tilem"): 1.693e-04, (2049, "tilew2"): 1.693e-04, (2049, "tilew4"): 1.697e-04, (2049, "column"): 1.693e-04,
-    (2049, "direct"): 5.228e-04,
+    (2049, "direct"): 8.505e-05,
 }
 
 
