@@ -110,6 +110,9 @@ SYMBOLS = {
     "blah2hip_amb_beamform_wdev": (C.c_int, [_vp, _vp, _u32, _u32, _vp, _u32, _vp, _vp, _vp]),
     "blah2hip_amb_covariance_dev": (C.c_int, [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _vp]),
     "blah2hip_amb_mvdr_weights_dev": (C.c_int, [_vp, _vp, _u32, _u32, _vp, _u32, _dbl, _vp, _vp, _vp]),
+    "blah2hip_amb_sample_covariance_dev": (C.c_int, [_vp, C.c_int, C.POINTER(_vp), _u32, _u32, C.c_uint64, _u32, _u32, _vp, _vp]),
+    "blah2hip_amb_beam_samples_dev": (C.c_int, [_vp, C.c_int, C.POINTER(_vp), _u32, _u32, C.c_uint64, _vp, _u32, C.POINTER(_vp), C.c_uint64, _vp]),
+    "blah2hip_amb_beam_samples_wdev": (C.c_int, [_vp, C.c_int, C.POINTER(_vp), _u32, _u32, C.c_uint64, _vp, _u32, C.POINTER(_vp), C.c_uint64, _vp]),
     "blah2hip_amb_snapshot_dev": (C.c_int, [_vp, _vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _vp]),
     "blah2hip_amb_bearing_dev": (C.c_int, [_vp, _vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _dbl, _vp, _u32, _u32, _vp, _vp]),
     "blah2hip_cfar1d_dev": (C.c_int, [_vp, _vp, _vp, _u32, _dbl, _i32, _i32, _i32, _dbl, _vp, _u32, _vp, _vp]),

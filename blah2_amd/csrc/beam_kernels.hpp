@@ -9,6 +9,12 @@
 //   mvdr_weights_kernel  minimum-variance (Capon) weights from that covariance: an fp64 Cholesky solve per CPI and beam
 //   bearing_kernel     the bearing of every detection: its snapshot scanned over a steering table, whitened by that
 //                      covariance's Cholesky factor (the adaptive matched filter) or not (Bartlett), in fp64
+// ... and in front of the whole chain, on the K sample planes themselves:
+//   sample_cov_kernel  the K x K array covariance of the channels' SAMPLES over a window of the CPI, per CPI, in fp64
+//                      (complex fp32 planes, or int8 (I, Q) planes: exact); cov_fold_kernel finishes it
+//   beam_samples_kernel / beam_samples_wdev_kernel
+//                      y_b = sum_k w[b][k] y_k for every beam b in ONE pass over the K sample planes: each beam plane is
+//                      then one surveillance channel to the clutter filter and the range + Doppler chain
 //
 // The cross-ambiguity map is linear in the surveillance channel, so the map of the beam y_b = sum_k w[b][k] y_k is the
 // same combination of the channel maps blah2hip_amb_process_multi_dev left in HBM: a further beam costs one more map
@@ -598,6 +604,261 @@ inline void launch_bearing(uint32_t K, dim3 grid, hipStream_t st, const BearingA
   case 7: hipLaunchKernelGGL((bearing_kernel<7>), grid, dim3(256), 0, st, a); break;
   case 8: hipLaunchKernelGGL((bearing_kernel<8>), grid, dim3(256), 0, st, a); break;
   }
+}
+
+// ---- the array in the sample domain: covariance and beam planes of the K channels' samples ------------------------------
+// A channel is a plane of complex fp32 samples or of int8 (I, Q) pairs (BLAH2HIP_FMT_I8: 2 bytes per sample, 2-byte
+// aligned).  COVW: the samples of sample_cov_kernel's wide access (16 and 8 bytes).
+struct SampC32 { static constexpr int BYTES = 8, COVW = 2; };
+struct SampI8 { static constexpr int BYTES = 2, COVW = 4; };
+
+// V adjacent samples of a plane in one access, from an address aligned to V * BYTES; get<v>: sample v as fp32 (every int8
+// value converts exactly)
+template <class Ch, int V> struct SampRaw;
+template <> struct SampRaw<SampC32, 1> {
+  typedef float type __attribute__((ext_vector_type(2)));
+  template <int v> static __device__ __forceinline__ cf get(const type &r) { return cmake(r[0], r[1]); }
+};
+template <> struct SampRaw<SampC32, 2> {
+  typedef float type __attribute__((ext_vector_type(4)));
+  template <int v> static __device__ __forceinline__ cf get(const type &r) { return cmake(r[2 * v], r[2 * v + 1]); }
+};
+__device__ __forceinline__ cf samp_i8(uint32_t w) { return cmake((float)(int8_t)(w & 0xffu), (float)(int8_t)((w >> 8) & 0xffu)); }
+template <> struct SampRaw<SampI8, 1> {
+  typedef uint16_t type;
+  template <int v> static __device__ __forceinline__ cf get(const type &r) { return samp_i8(r); }
+};
+template <> struct SampRaw<SampI8, 2> {
+  typedef uint32_t type;
+  template <int v> static __device__ __forceinline__ cf get(const type &r) { return samp_i8(r >> (16 * v)); }
+};
+template <> struct SampRaw<SampI8, 4> {
+  typedef uint32_t type __attribute__((ext_vector_type(2)));
+  template <int v> static __device__ __forceinline__ cf get(const type &r) { return samp_i8(r[v >> 1] >> (16 * (v & 1))); }
+};
+
+// samples in front of the first address aligned to V * BYTES, at most n
+template <class Ch, int V> __device__ __forceinline__ uint32_t samp_head(const char *p, uint32_t n)
+{
+  if (V == 1) return 0;
+  const uint32_t at = (uint32_t)(((uintptr_t)p / Ch::BYTES) & (V - 1));
+  return min(n, (V - at) & (V - 1));
+}
+
+struct SampCovArgs {
+  const void *y[BLAH2HIP_MAX_SURV]; // the K planes
+  double *part;                     // [nCpi][gridDim.x][K * K] per-workgroup partials, packed as array_cov_kernel's
+  uint64_t cpiStride;               // samples from CPI to CPI
+  uint32_t s0, n;                   // the training window: n samples from sample s0 of the CPI
+};
+
+// sample v of each of K accesses into the K * K packed sums: array_cov_kernel's update, one fp64 fused multiply-add per
+// product (fp32 x fp32 and int8 x int8 are both exact in fp64)
+template <int K, class Raw, int v>
+__device__ __forceinline__ void cov_update(const typename Raw::type (&m)[K], double (&acc)[K * K])
+{
+  double x[K], y[K];
+#pragma unroll
+  for (int k = 0; k < K; k++) { const cf s = Raw::template get<v>(m[k]); x[k] = (double)s.x; y[k] = (double)s.y; }
+#pragma unroll
+  for (int i = 0; i < K; i++) {
+    acc[i * K + i] = fma(y[i], y[i], fma(x[i], x[i], acc[i * K + i]));
+#pragma unroll
+    for (int j = i + 1; j < K; j++) {
+      acc[i * K + j] = fma(y[i], y[j], fma(x[i], x[j], acc[i * K + j]));  // Re y_i conj(y_j)
+      acc[j * K + i] = fma(-x[i], y[j], fma(y[i], x[j], acc[j * K + i])); // Im y_i conj(y_j)
+    }
+  }
+}
+
+// V adjacent samples from sample i of the window on: the K loads first (all in flight together), then sample after sample
+template <int K, class Ch, int V>
+__device__ __forceinline__ void cov_samples(const char *const (&p)[K], size_t i, double (&acc)[K * K])
+{
+  typedef SampRaw<Ch, V> Raw;
+  typename Raw::type m[K];
+#pragma unroll
+  for (int k = 0; k < K; k++) m[k] = *reinterpret_cast<const typename Raw::type *>(p[k] + i * Ch::BYTES);
+  // sample after sample, the scheduler kept from converting them all ahead: at K = 8 the K * K sums fill half the registers
+  cov_update<K, Raw, 0>(m, acc);
+  if (V > 1) {
+    __builtin_amdgcn_sched_barrier(0);
+    cov_update<K, Raw, (V > 1 ? 1 : 0)>(m, acc);
+  }
+  if (V > 2) {
+    __builtin_amdgcn_sched_barrier(0);
+    cov_update<K, Raw, (V > 2 ? 2 : 0)>(m, acc);
+    __builtin_amdgcn_sched_barrier(0);
+    cov_update<K, Raw, (V > 2 ? 3 : 0)>(m, acc);
+  }
+}
+
+// R[c][i][j] = sum over s0 <= n < s0 + a.n of y_i[c * cpiStride + n] conj(y_j[c * cpiStride + n]), per CPI c: array_cov_kernel
+// over a window of samples instead of a rectangle of cells.  grid (G, nCpi), 256 threads; the same K * K packed fp64 sums,
+// the same fold (butterfly over the lanes, the four waves in order, one partial per workgroup, cov_fold_kernel adds them
+// in index order).  No floating-point atomics.  fp32 planes: array_cov_kernel's arithmetic and contract.  int8 planes:
+// every product is an integer of at most 2^14 and every sum one below 2^53 (2^32 samples would be needed to get there), so
+// every fused multiply-add and every addition of the folds is exact: the result is the integer sum, whatever the grid.
+// V = 1: one sample per access.  V = Ch::COVW: accesses of V samples (16 bytes of fp32 pairs, 8 bytes of int8 pairs) from
+// the first aligned sample of the window on; the host picks it where every channel's window of a CPI starts at the same
+// offset modulo the access (it may differ from CPI to CPI).  The at most V - 1 samples in front and behind go through
+// single-sample accesses in workgroup 0.
+template <int K, class Ch, int V>
+__global__ __launch_bounds__(256) void sample_cov_kernel(SampCovArgs a)
+{
+  __shared__ double wpart[4][K * K];
+  const uint32_t cpi = blockIdx.y;
+  const char *p[K];
+#pragma unroll
+  for (int k = 0; k < K; k++) p[k] = (const char *)a.y[k] + ((size_t)cpi * a.cpiStride + a.s0) * Ch::BYTES;
+  double acc[K * K];
+#pragma unroll
+  for (int e = 0; e < K * K; e++) acc[e] = 0.0;
+
+  const uint32_t head = samp_head<Ch, V>(p[0], a.n);
+  const uint32_t nUnits = (a.n - head) / V;
+  for (uint64_t u = blockIdx.x * 256 + threadIdx.x; u < nUnits; u += gridDim.x * 256)
+    cov_samples<K, Ch, V>(p, head + (size_t)u * V, acc);
+  if (V > 1 && blockIdx.x == 0) {
+    const uint32_t done = head + nUnits * V; // the tail starts here
+    if (threadIdx.x < head + (a.n - done)) cov_samples<K, Ch, 1>(p, threadIdx.x < head ? threadIdx.x : done + (threadIdx.x - head), acc);
+  }
+
+#pragma unroll
+  for (int e = 0; e < K * K; e++) {
+    double v = acc[e];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    if ((threadIdx.x & 63) == 0) wpart[threadIdx.x >> 6][e] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < K * K) {
+    const int e = threadIdx.x;
+    a.part[((size_t)cpi * gridDim.x + blockIdx.x) * (K * K) + e] = ((wpart[0][e] + wpart[1][e]) + wpart[2][e]) + wpart[3][e];
+  }
+}
+
+template <class Ch, int V> inline void launch_sample_cov(uint32_t K, dim3 grid, hipStream_t st, const SampCovArgs &a)
+{
+  switch (K) {
+  case 1: hipLaunchKernelGGL((sample_cov_kernel<1, Ch, V>), grid, dim3(256), 0, st, a); break;
+  case 2: hipLaunchKernelGGL((sample_cov_kernel<2, Ch, V>), grid, dim3(256), 0, st, a); break;
+  case 3: hipLaunchKernelGGL((sample_cov_kernel<3, Ch, V>), grid, dim3(256), 0, st, a); break;
+  case 4: hipLaunchKernelGGL((sample_cov_kernel<4, Ch, V>), grid, dim3(256), 0, st, a); break;
+  case 5: hipLaunchKernelGGL((sample_cov_kernel<5, Ch, V>), grid, dim3(256), 0, st, a); break;
+  case 6: hipLaunchKernelGGL((sample_cov_kernel<6, Ch, V>), grid, dim3(256), 0, st, a); break;
+  case 7: hipLaunchKernelGGL((sample_cov_kernel<7, Ch, V>), grid, dim3(256), 0, st, a); break;
+  case 8: hipLaunchKernelGGL((sample_cov_kernel<8, Ch, V>), grid, dim3(256), 0, st, a); break;
+  }
+}
+
+struct BeamSampArgs {
+  const void *y[BLAH2HIP_MAX_SURV]; // the K input planes
+  cf *out[BLAH2HIP_MAX_BEAMS];      // the beam planes
+  uint64_t cpiStride, beamStride;   // samples from CPI to CPI, in and out
+  uint32_t nSamples, nBeams;
+  cf w[BLAH2HIP_MAX_BEAMS][BLAH2HIP_MAX_SURV]; // in the launch arguments: wave-uniform, read by scalar loads
+};
+
+// V adjacent samples from sample i of the CPI on: the K loads first (all in flight together), then beam after beam, the
+// beam loop unrolled to its limit behind a wave-uniform test as in beam_cells.  Per component the sum is beam_cells' chain
+// of fused multiply-adds in the order k = 0 .. K-1, written out again here so that beamform_kernel's code, whose bits are a
+// contract, is not touched: 2K roundings, a weight of exactly 1 or 0 passes a sample (int8: its exact conversion) through.
+template <int K, class Ch, int V, int W>
+__device__ __forceinline__ void beam_samples(const BeamSampArgs &a, const cf (&wts)[BLAH2HIP_MAX_BEAMS][W], const char *const (&p)[K],
+                                             size_t outOff, size_t i)
+{
+  typedef SampRaw<Ch, V> Raw;
+  typedef typename BeamVec<V>::type vec;
+  typename Raw::type m[K];
+#pragma unroll
+  for (int k = 0; k < K; k++) m[k] = *reinterpret_cast<const typename Raw::type *>(p[k] + i * Ch::BYTES);
+  cf s[K][V];
+#pragma unroll
+  for (int k = 0; k < K; k++) {
+    s[k][0] = Raw::template get<0>(m[k]);
+    if (V == 2) s[k][V - 1] = Raw::template get<V - 1>(m[k]);
+  }
+#pragma unroll
+  for (int b = 0; b < BLAH2HIP_MAX_BEAMS; b++) {
+    if (b < (int)a.nBeams) {
+      vec r;
+#pragma unroll
+      for (int v = 0; v < V; v++) {
+        float re = 0.f, im = 0.f;
+#pragma unroll
+        for (int k = 0; k < K; k++) {
+          const cf w = wts[b][k];
+          const float mx = s[k][v].x, my = s[k][v].y;
+          re = fmaf(-w.y, my, k ? fmaf(w.x, mx, re) : w.x * mx);
+          im = fmaf(w.y, mx, k ? fmaf(w.x, my, im) : w.x * my);
+        }
+        r[2 * v] = re;
+        r[2 * v + 1] = im;
+      }
+      *reinterpret_cast<vec *>(a.out[b] + outOff + i) = r;
+    }
+  }
+}
+
+// grid (G, nCpi), 256 threads.  A workgroup strides over its CPI in units of V samples.  V = 2 (16-byte stores; 16-byte
+// loads of fp32 pairs, 4-byte loads of int8 pairs) needs every input plane's and every beam plane's copy of a CPI to start at
+// the same parity of sample with respect to its access (the host checks it CPI by CPI): a CPI that starts one sample off then has
+// a one-sample head, and whatever is left behind the last pair is a one-sample tail; both go through single-sample accesses
+// in workgroup 0.  V = 1 otherwise.  Samples from nSamples on -- the gap up to beamStride -- are not written.
+template <int K, class Ch, int V, int W>
+__device__ __forceinline__ void beam_samples_run(const BeamSampArgs &a, const cf (&wts)[BLAH2HIP_MAX_BEAMS][W])
+{
+  const uint32_t cpi = blockIdx.y;
+  const char *p[K];
+#pragma unroll
+  for (int k = 0; k < K; k++) p[k] = (const char *)a.y[k] + (size_t)cpi * a.cpiStride * Ch::BYTES;
+  const size_t outOff = (size_t)cpi * a.beamStride;
+  const uint32_t head = samp_head<Ch, V>(p[0], a.nSamples);
+  const uint32_t nUnits = (a.nSamples - head) / V;
+  for (uint64_t u = blockIdx.x * 256 + threadIdx.x; u < nUnits; u += gridDim.x * 256)
+    beam_samples<K, Ch, V>(a, wts, p, outOff, head + (size_t)u * V);
+  if (V == 2 && blockIdx.x == 0) {
+    const uint32_t done = head + nUnits * V;
+    if (threadIdx.x < head + (a.nSamples - done))
+      beam_samples<K, Ch, 1>(a, wts, p, outOff, threadIdx.x < head ? threadIdx.x : done + (threadIdx.x - head));
+  }
+}
+
+// one set of weights for every CPI, in the launch arguments (blah2hip_amb_beam_samples_dev)
+template <int K, class Ch, int V>
+__global__ __launch_bounds__(256) void beam_samples_kernel(BeamSampArgs a)
+{
+  beam_samples_run<K, Ch, V>(a, a.w);
+}
+
+// the CPI's own weights wdev[cpi][b][k] on the device (blah2hip_amb_beam_samples_wdev; a.w is unused), read once before the
+// first sample as in beamform_wdev_kernel: the operations and their order are the same, so equal weights give equal bits
+template <int K, class Ch, int V>
+__global__ __launch_bounds__(256) void beam_samples_wdev_kernel(BeamSampArgs a, const cf *wdev)
+{
+  cf wts[BLAH2HIP_MAX_BEAMS][K];
+  const cf *wd = wdev + (size_t)blockIdx.y * a.nBeams * K;
+#pragma unroll
+  for (int b = 0; b < BLAH2HIP_MAX_BEAMS; b++) {
+#pragma unroll
+    for (int k = 0; k < K; k++) wts[b][k] = b < (int)a.nBeams ? wd[b * K + k] : cmake(0.f, 0.f);
+  }
+  beam_samples_run<K, Ch, V>(a, wts);
+}
+
+template <class Ch, int V, bool WDEV> inline void launch_beam_samples(uint32_t K, dim3 grid, hipStream_t st, const BeamSampArgs &a, const cf *wdev)
+{
+#define BLAH2_BEAM_SAMPLES_CASE(k)                                                                        \
+  case k:                                                                                                 \
+    if (WDEV) hipLaunchKernelGGL((beam_samples_wdev_kernel<k, Ch, V>), grid, dim3(256), 0, st, a, wdev); \
+    else hipLaunchKernelGGL((beam_samples_kernel<k, Ch, V>), grid, dim3(256), 0, st, a);                \
+    break;
+  switch (K) {
+    BLAH2_BEAM_SAMPLES_CASE(1) BLAH2_BEAM_SAMPLES_CASE(2) BLAH2_BEAM_SAMPLES_CASE(3) BLAH2_BEAM_SAMPLES_CASE(4)
+    BLAH2_BEAM_SAMPLES_CASE(5) BLAH2_BEAM_SAMPLES_CASE(6) BLAH2_BEAM_SAMPLES_CASE(7) BLAH2_BEAM_SAMPLES_CASE(8)
+  }
+#undef BLAH2_BEAM_SAMPLES_CASE
 }
 
 } // namespace blah2

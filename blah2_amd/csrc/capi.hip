@@ -2107,6 +2107,160 @@ int blah2hip_amb_mvdr_weights_dev(blah2hip_amb_t h, const double *d_cov, uint32_
   return BLAH2HIP_OK;
 }
 
+// ------------------------------------------- the array in the sample domain --
+// what the sample-domain calls share: format, counts, planes and their alignment, stride.  bytes: one sample of a plane.
+static int sample_planes_check(blah2hip_amb_t h, int fmt, const void *const *d_y, uint32_t n_surv, uint32_t n_cpi, uint64_t cpi_stride,
+                               size_t *bytes)
+{
+  if (!h) return fail(BLAH2HIP_ERR_INVALID, "NULL handle");
+  if (fmt != BLAH2HIP_FMT_C32 && fmt != BLAH2HIP_FMT_I8)
+    return fail(BLAH2HIP_ERR_UNSUPPORTED, "sample-domain beams: BLAH2HIP_FMT_C32 or BLAH2HIP_FMT_I8 planes");
+  if (n_surv == 0 || n_surv > BLAH2HIP_MAX_SURV) return fail(BLAH2HIP_ERR_INVALID, "n_surv outside [1, BLAH2HIP_MAX_SURV]");
+  if (n_cpi == 0) return fail(BLAH2HIP_ERR_INVALID, "n_cpi is 0");
+  if (!d_y) return fail(BLAH2HIP_ERR_INVALID, "NULL plane array");
+  *bytes = fmt == BLAH2HIP_FMT_I8 ? 2 : 8;
+  for (uint32_t k = 0; k < n_surv; k++) {
+    if (!d_y[k]) return fail(BLAH2HIP_ERR_INVALID, "NULL plane");
+    if ((uintptr_t)d_y[k] & (*bytes - 1))
+      return fail(BLAH2HIP_ERR_INVALID, "a plane is not aligned to its sample (int8 pairs: 2 bytes, fp32 pairs: 8 bytes)");
+  }
+  if (n_cpi > 1 && cpi_stride < h->dims.n_samples) return fail(BLAH2HIP_ERR_INVALID, "cpi_stride < n_samples");
+  return BLAH2HIP_OK;
+}
+
+// true where, CPI by CPI, sample `first` of every plane sits at the same offset modulo an access of V samples: the
+// number of single samples in front of the first aligned access is then one number per CPI (it may differ between CPIs)
+static bool sample_planes_agree(const void *const *planes, uint32_t n_planes, size_t bytes, uint64_t stride, uint32_t n_cpi,
+                                uint32_t first, uint32_t V, const void *const *more = nullptr, uint32_t n_more = 0, size_t more_bytes = 0,
+                                uint64_t more_stride = 0)
+{
+  for (uint32_t c = 0; c < n_cpi; c++) {
+    const uint64_t at0 = ((uintptr_t)planes[0] / bytes + c * stride + first) % V;
+    for (uint32_t k = 1; k < n_planes; k++)
+      if (((uintptr_t)planes[k] / bytes + c * stride + first) % V != at0) return false;
+    for (uint32_t b = 0; b < n_more; b++)
+      if (((uintptr_t)more[b] / more_bytes + c * more_stride + first) % V != at0) return false;
+  }
+  return true;
+}
+
+int blah2hip_amb_sample_covariance_dev(blah2hip_amb_t h, int fmt, const void *const *d_y, uint32_t n_surv, uint32_t n_cpi,
+                                       uint64_t cpi_stride, uint32_t s0, uint32_t s1, double *d_cov, void *stream)
+{
+  size_t bytes = 0;
+  int rc;
+  if ((rc = sample_planes_check(h, fmt, d_y, n_surv, n_cpi, cpi_stride, &bytes))) return rc;
+  if (!d_cov) return fail(BLAH2HIP_ERR_INVALID, "NULL output");
+  if ((uint64_t)n_surv * n_cpi > h->dims.max_batch) return fail(BLAH2HIP_ERR_INVALID, "n_surv * n_cpi above max_batch");
+  const uint32_t nS = h->dims.n_samples;
+  if (s0 >= s1 || s1 > nS) return fail(BLAH2HIP_ERR_INVALID, "sample covariance: the window is empty or leaves the CPI");
+  const size_t KK = (size_t)n_surv * n_surv;
+  const size_t planeBytes = ((size_t)(n_cpi - 1) * cpi_stride + nS) * bytes;
+  for (uint32_t k = 0; k < n_surv; k++)
+    if (ranges_overlap(d_y[k], planeBytes, d_cov, (size_t)n_cpi * KK * 2 * sizeof(double)))
+      return fail(BLAH2HIP_ERR_INVALID, "sample covariance: the output overlaps an input plane");
+  HIPCHK(hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+
+  SampCovArgs a;
+  memset(a.y, 0, sizeof(a.y));
+  for (uint32_t k = 0; k < n_surv; k++) a.y[k] = d_y[k];
+  a.part = h->d_partSum;
+  a.cpiStride = cpi_stride;
+  a.s0 = s0;
+  a.n = s1 - s0;
+  const uint32_t V = fmt == BLAH2HIP_FMT_I8 ? SampI8::COVW : SampC32::COVW;
+  const bool wide = sample_planes_agree(d_y, n_surv, bytes, cpi_stride, n_cpi, s0, V);
+  // workgroups per CPI: blah2hip_amb_covariance_dev's rule, over accesses instead of cells
+  const size_t units = wide ? (a.n + V - 1) / V : a.n;
+  const size_t gCap = ((size_t)h->dims.max_batch * h->nParts) / ((size_t)n_cpi * KK);
+  if (gCap == 0) return fail(BLAH2HIP_ERR_INVALID, "sample covariance: the handle's partials are too small");
+  const uint32_t gMax = (uint32_t)std::min<size_t>(gCap, (units + 255) / 256);
+  const uint32_t G = std::max(1u, std::min(gMax, (8u * (uint32_t)h->numCU + n_cpi - 1) / n_cpi));
+  if ((rc = tic(h, BLAH2HIP_K_COV, st))) return rc;
+  const dim3 grid(G, n_cpi);
+  if (fmt == BLAH2HIP_FMT_I8) {
+    if (wide) launch_sample_cov<SampI8, SampI8::COVW>(n_surv, grid, st, a);
+    else launch_sample_cov<SampI8, 1>(n_surv, grid, st, a);
+  } else {
+    if (wide) launch_sample_cov<SampC32, SampC32::COVW>(n_surv, grid, st, a);
+    else launch_sample_cov<SampC32, 1>(n_surv, grid, st, a);
+  }
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(cov_fold_kernel, dim3(n_cpi), dim3(64), 0, st, h->d_partSum, G, n_surv, d_cov);
+  HIPCHK(hipGetLastError());
+  return toc(h, BLAH2HIP_K_COV, st);
+}
+
+// blah2hip_amb_beam_samples_dev (w: the host's one set of weights) and blah2hip_amb_beam_samples_wdev (d_w: a set per CPI on the device)
+static int beam_samples_enqueue(blah2hip_amb_t h, int fmt, const void *const *d_y, uint32_t n_surv, uint32_t n_cpi, uint64_t cpi_stride,
+                                const float *w, const float *d_w, uint32_t n_beams, void *const *d_beam, uint64_t beam_stride,
+                                void *stream)
+{
+  size_t bytes = 0;
+  int rc;
+  if ((rc = sample_planes_check(h, fmt, d_y, n_surv, n_cpi, cpi_stride, &bytes))) return rc;
+  if (n_beams == 0 || n_beams > BLAH2HIP_MAX_BEAMS) return fail(BLAH2HIP_ERR_INVALID, "n_beams outside [1, BLAH2HIP_MAX_BEAMS]");
+  if ((!w && !d_w) || !d_beam) return fail(BLAH2HIP_ERR_INVALID, "NULL weights or output");
+  const uint32_t nS = h->dims.n_samples;
+  if (n_cpi > 1 && beam_stride < nS) return fail(BLAH2HIP_ERR_INVALID, "beam_stride < n_samples");
+  const size_t inBytes = ((size_t)(n_cpi - 1) * cpi_stride + nS) * bytes;
+  const size_t outBytes = ((size_t)(n_cpi - 1) * beam_stride + nS) * sizeof(cf);
+  for (uint32_t b = 0; b < n_beams; b++) {
+    if (!d_beam[b]) return fail(BLAH2HIP_ERR_INVALID, "NULL beam plane");
+    if ((uintptr_t)d_beam[b] & 7) return fail(BLAH2HIP_ERR_INVALID, "a beam plane is not 8-byte aligned");
+    for (uint32_t k = 0; k < n_surv; k++)
+      if (ranges_overlap(d_y[k], inBytes, d_beam[b], outBytes)) return fail(BLAH2HIP_ERR_INVALID, "beam samples: a beam plane overlaps an input plane");
+    for (uint32_t o = 0; o < b; o++)
+      if (ranges_overlap(d_beam[o], outBytes, d_beam[b], outBytes)) return fail(BLAH2HIP_ERR_INVALID, "beam samples: two beam planes overlap");
+  }
+  HIPCHK(hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+
+  BeamSampArgs a;
+  memset(a.y, 0, sizeof(a.y));
+  memset(a.out, 0, sizeof(a.out));
+  for (uint32_t k = 0; k < n_surv; k++) a.y[k] = d_y[k];
+  for (uint32_t b = 0; b < n_beams; b++) a.out[b] = (cf *)d_beam[b];
+  a.cpiStride = cpi_stride;
+  a.beamStride = beam_stride;
+  a.nSamples = nS;
+  a.nBeams = n_beams;
+  memset(a.w, 0, sizeof(a.w));
+  if (!d_w)
+    for (uint32_t b = 0; b < n_beams; b++)
+      for (uint32_t k = 0; k < n_surv; k++) a.w[b][k] = cmake(w[2 * (b * n_surv + k)], w[2 * (b * n_surv + k) + 1]);
+  // pairs of samples where every input plane's and every beam plane's copy of a CPI starts at the same parity of sample
+  const bool wide = sample_planes_agree(d_y, n_surv, bytes, cpi_stride, n_cpi, 0, 2, (const void *const *)d_beam, n_beams, sizeof(cf), beam_stride);
+  // workgroups per CPI: eight a CU over the launch, each with at least one pass of 256 accesses
+  const size_t units = wide ? ((size_t)nS + 1) / 2 : nS;
+  const uint32_t G = (uint32_t)std::max<size_t>(1, std::min<size_t>((units + 255) / 256, (8u * (size_t)h->numCU + n_cpi - 1) / n_cpi));
+  if ((rc = tic(h, BLAH2HIP_K_BEAM, st))) return rc;
+  const dim3 grid(G, n_cpi);
+  const cf *wd = (const cf *)d_w;
+  if (fmt == BLAH2HIP_FMT_I8) {
+    if (d_w) { if (wide) launch_beam_samples<SampI8, 2, true>(n_surv, grid, st, a, wd); else launch_beam_samples<SampI8, 1, true>(n_surv, grid, st, a, wd); }
+    else { if (wide) launch_beam_samples<SampI8, 2, false>(n_surv, grid, st, a, wd); else launch_beam_samples<SampI8, 1, false>(n_surv, grid, st, a, wd); }
+  } else {
+    if (d_w) { if (wide) launch_beam_samples<SampC32, 2, true>(n_surv, grid, st, a, wd); else launch_beam_samples<SampC32, 1, true>(n_surv, grid, st, a, wd); }
+    else { if (wide) launch_beam_samples<SampC32, 2, false>(n_surv, grid, st, a, wd); else launch_beam_samples<SampC32, 1, false>(n_surv, grid, st, a, wd); }
+  }
+  HIPCHK(hipGetLastError());
+  return toc(h, BLAH2HIP_K_BEAM, st);
+}
+
+int blah2hip_amb_beam_samples_dev(blah2hip_amb_t h, int fmt, const void *const *d_y, uint32_t n_surv, uint32_t n_cpi, uint64_t cpi_stride,
+                                  const float *w, uint32_t n_beams, void *const *d_beam, uint64_t beam_stride, void *stream)
+{
+  return beam_samples_enqueue(h, fmt, d_y, n_surv, n_cpi, cpi_stride, w, nullptr, n_beams, d_beam, beam_stride, stream);
+}
+
+int blah2hip_amb_beam_samples_wdev(blah2hip_amb_t h, int fmt, const void *const *d_y, uint32_t n_surv, uint32_t n_cpi, uint64_t cpi_stride,
+                                   const float *d_w, uint32_t n_beams, void *const *d_beam, uint64_t beam_stride, void *stream)
+{
+  return beam_samples_enqueue(h, fmt, d_y, n_surv, n_cpi, cpi_stride, nullptr, d_w, n_beams, d_beam, beam_stride, stream);
+}
+
 int blah2hip_amb_snapshot_dev(blah2hip_amb_t h, const void *d_map, uint32_t n_surv, uint32_t n_cpi,
                               const blah2hip_det_t *d_dets, uint32_t cap, const uint32_t *d_count, uint32_t n_lists,
                               float *d_snap, void *stream)

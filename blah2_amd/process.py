@@ -121,6 +121,25 @@ def mvdr_weights(R, steer, loading):
     return w.reshape(batch + (a.shape[0], K)), good.astype(np.int32).reshape(batch)
 
 
+def sample_covariance(ys, s0=0, s1=None):
+    """blah2hip_amb_sample_covariance_dev restated in fp64 NumPy.  ``ys``: the channels' samples ``[K, ..., n]`` (complex, or
+    anything that converts to complex128 exactly); ``R[..., i, j] = sum over s0 <= n < s1 of y_i[n] conj(y_j[n])``,
+    complex128 ``[..., K, K]`` (``s1`` None: to the end).  Integer-valued samples (int8 planes) give the exact integer sums."""
+    y = np.asarray(ys).astype(np.complex128)[..., s0:s1]
+    return np.einsum("i...n,j...n->...ij", y, np.conj(y))
+
+
+def beam_samples(ys, w):
+    """blah2hip_amb_beam_samples_dev restated in fp64 NumPy: ``ys [K, ..., n]``, ``w [n_beams, K]`` (one set) or
+    ``[n_cpi, n_beams, K]`` with ``ys [K, n_cpi, n]`` (a set per CPI, as ``mvdr_weights`` returns it);
+    ``y_b = sum_k w[b][k] y_k``, complex128 ``[n_beams, ..., n]``."""
+    y = np.asarray(ys).astype(np.complex128)
+    w = np.asarray(w, dtype=np.complex128)
+    if w.ndim == 3:
+        return np.einsum("cbk,kcn->bcn", w, y)
+    return np.einsum("bk,k...n->b...n", w, y)
+
+
 def uca_steering(n_surv, radius_wavelengths, angles_deg):
     """Steering vectors of a uniform circular array of ``n_surv`` elements on a circle of ``radius_wavelengths``, element k at
     the azimuth ``2 pi k / n_surv``, one row per angle (degrees of azimuth): ``a[g][k] = exp(2j pi r cos(theta_g - 2 pi k /
@@ -491,6 +510,48 @@ class Ambiguity:
         self.covariance_dev(d_map, n_surv, n_cpi, d_cov, region, stream)
         self.mvdr_weights_dev(d_cov, n_surv, n_cpi, steer, loading, d_w, d_ok, stream)
         self.beamform_wdev(d_map, n_surv, n_cpi, d_w, steer.shape[0], d_beam_map, d_beam_metrics, stream)
+
+    @staticmethod
+    def _planes(ptrs):
+        return (C.c_void_p * max(1, len(ptrs)))(*[int(p) if p else None for p in ptrs])
+
+    def sample_covariance_dev(self, fmt, d_ys, n_cpi, cpi_stride, d_cov, window=None, stream=0):
+        """The array covariance of the channels' SAMPLES per CPI (blah2hip_amb_sample_covariance_dev; raw pointers/ints):
+        ``d_ys`` the ``n_surv`` planes (FMT_C32 or FMT_I8), ``d_cov`` complex128 ``[n_cpi][n_surv][n_surv]`` as
+        ``covariance_dev`` writes it, over the samples ``window`` = ``(s0, s1)`` of every CPI (None: all of it).
+        :func:`sample_covariance` is the same in NumPy."""
+        s0, s1 = window if window is not None else (0, self.dims.n_samples)
+        check(self._L.blah2hip_amb_sample_covariance_dev(self._h, fmt, self._planes(d_ys), len(d_ys), n_cpi, cpi_stride, s0, s1,
+                                                         d_cov, stream))
+
+    def beam_samples_dev(self, fmt, d_ys, n_cpi, cpi_stride, w, d_beams, beam_stride, stream=0):
+        """Beam planes from the channels' samples (blah2hip_amb_beam_samples_dev; raw pointers/ints): ``w`` is a complex array
+        ``[n_beams, n_surv]`` (host), ``d_beams`` the ``n_beams`` complex64 output planes, CPI c at ``c * beam_stride``
+        samples -- each one a ``d_y`` for ``process_dev`` (FMT_C32, FMT_I8X_C32Y, FMT_I16X_C32Y) and for the clutter filter.
+        :func:`beam_samples` is the same in NumPy."""
+        w = np.ascontiguousarray(w, dtype=np.complex64)
+        if w.ndim != 2 or w.shape[1] != len(d_ys) or w.shape[0] != len(d_beams):
+            raise ValueError("w must be [n_beams, n_surv]")
+        check(self._L.blah2hip_amb_beam_samples_dev(self._h, fmt, self._planes(d_ys), len(d_ys), n_cpi, cpi_stride, _ptr(w),
+                                                    len(d_beams), self._planes(d_beams), beam_stride, stream))
+
+    def beam_samples_wdev(self, fmt, d_ys, n_cpi, cpi_stride, d_w, d_beams, beam_stride, stream=0):
+        """``beam_samples_dev`` with a set of weights per CPI on the device (blah2hip_amb_beam_samples_wdev; raw
+        pointers/ints): ``d_w`` is complex64 ``[n_cpi][n_beams][n_surv]``, as ``mvdr_weights_dev`` writes it."""
+        check(self._L.blah2hip_amb_beam_samples_wdev(self._h, fmt, self._planes(d_ys), len(d_ys), n_cpi, cpi_stride, d_w,
+                                                     len(d_beams), self._planes(d_beams), beam_stride, stream))
+
+    def adaptive_beam_samples_dev(self, fmt, d_ys, n_cpi, cpi_stride, steer, loading, d_cov, d_w, d_ok, d_beams, beam_stride,
+                                  window=None, stream=0):
+        """Adaptive beam planes, enqueued in order on ``stream``: ``sample_covariance_dev`` over ``window``,
+        ``mvdr_weights_dev`` towards ``steer`` (``[n_beams, n_surv]``, host) and ``beam_samples_wdev`` with the weights it left
+        in ``d_w`` -- ``adaptive_beamform_dev`` in front of the range and Doppler stages instead of behind them."""
+        steer = np.ascontiguousarray(steer, dtype=np.complex64)
+        if steer.ndim != 2 or steer.shape[0] != len(d_beams):
+            raise ValueError("steer must be [n_beams, n_surv] with one row per beam plane")
+        self.sample_covariance_dev(fmt, d_ys, n_cpi, cpi_stride, d_cov, window, stream)
+        self.mvdr_weights_dev(d_cov, len(d_ys), n_cpi, steer, loading, d_w, d_ok, stream)
+        self.beam_samples_wdev(fmt, d_ys, n_cpi, cpi_stride, d_w, d_beams, beam_stride, stream)
 
     def snapshot_dev(self, d_map, n_surv, n_cpi, d_dets, cap, d_count, n_lists, d_snap, stream=0):
         """The ``n_surv`` channel cells under every record of ``n_lists`` detection lists (blah2hip_amb_snapshot_dev; raw

@@ -368,6 +368,60 @@ int blah2hip_amb_covariance_dev(blah2hip_amb_t h, const void *d_map, uint32_t n_
 int blah2hip_amb_mvdr_weights_dev(blah2hip_amb_t h, const double *d_cov, uint32_t n_surv, uint32_t n_cpi,
                                   const float *steer, uint32_t n_beams, double loading,
                                   float *d_w, int32_t *d_ok, void *stream);
+/* ---- the array in the SAMPLE domain: covariance and beam planes in front of the whole chain ----
+ * The beam y_b[n] = sum_k w[b][k] y_k[n] is linear in the channels like the clutter filter and the map, so a beam plane formed
+ * from the samples is an ordinary surveillance channel: ONE clutter filter, range pass and Doppler pass per beam instead of one
+ * per channel, and a covariance estimated where the direct path and the clutter dominate (a target lies far under the noise
+ * per sample, so nothing has to be kept out of the training window).
+ * d_y: HOST array of n_surv device planes as in blah2hip_amb_process_multi_dev, CPI c at c * cpi_stride samples, the handle's
+ * n_samples samples per CPI.  fmt: BLAH2HIP_FMT_C32 (planes of complex fp32, 8-byte aligned) or BLAH2HIP_FMT_I8 (planes of int8
+ * (I, Q) pairs, 2-byte aligned); any other format: BLAH2HIP_ERR_UNSUPPORTED.
+ *
+ * The sample covariance over the window [s0, s1) of every CPI (0, n_samples: all of it):
+ *   d_cov[c][i][j] = sum over s0 <= n < s1 of y_i[c * cpi_stride + n] conj(y_j[c * cpi_stride + n])
+ * in the layout and with the properties of blah2hip_amb_covariance_dev's output -- (re, im) doubles [n_cpi][n_surv][n_surv], both
+ * triangles, exact conjugates, the diagonal's imaginary part exactly 0 -- so it feeds blah2hip_amb_mvdr_weights_dev and
+ * blah2hip_amb_bearing_dev unchanged.  Arithmetic, FMT_C32: that call's (fp64 fused multiply-adds on the exactly converted
+ * values, every addition fp64); the contract is |error| <= 4 * 2^-24 * sum |y_i| |y_j| per entry.  FMT_I8: the result is
+ * EXACT -- every product and every partial sum is an integer below 2^53 -- and so the same whatever the grid.  No
+ * floating-point atomics; sample_cov_kernel leaves one partial per workgroup in the handle's metrics partials (the workgroups
+ * per CPI are bounded as for blah2hip_amb_covariance_dev; calls on one handle must be ordered on the device) and
+ * cov_fold_kernel adds them in index order: two calls give the same bits.  Accesses of several samples (16 bytes of fp32 pairs,
+ * 8 bytes of int8 pairs) are used where, CPI by CPI, every plane's window starts at the same offset modulo the access;
+ * any other bases and strides go one sample per access.  Enqueues only (two kernels, both under BLAH2HIP_K_COV): no
+ * allocation, upload or synchronisation, capturable in a graph.
+ * BLAH2HIP_ERR_INVALID, with nothing enqueued: a NULL handle, plane array, plane or output, n_surv outside
+ * [1, BLAH2HIP_MAX_SURV], n_cpi == 0, n_surv * n_cpi above max_batch, s0 >= s1 or s1 > n_samples, cpi_stride < n_samples with
+ * n_cpi > 1, an int8 plane at an odd address (an fp32 plane off 8 bytes), d_cov overlapping an input plane. */
+int blah2hip_amb_sample_covariance_dev(blah2hip_amb_t h, int fmt, const void *const *d_y, uint32_t n_surv,
+                                       uint32_t n_cpi, uint64_t cpi_stride, uint32_t s0, uint32_t s1,
+                                       double *d_cov, void *stream);
+/* Beam planes: d_beam[b][c * beam_stride + n] = sum_k w[b][k] y_k[c * cpi_stride + n], n < n_samples, complex fp32.  w: HOST
+ * array [n_beams][n_surv] of (re, im) fp32 pairs, read at the call and carried in the launch arguments, as in
+ * blah2hip_amb_beamform_dev.  d_beam: HOST array of n_beams device planes (8-byte aligned).  Samples n >= n_samples of an output
+ * CPI -- the gap up to beam_stride -- are not written.  Each beam plane is a valid d_y for blah2hip_clutter_process_dev_fmt
+ * (FMT_C32), for blah2hip_amb_process_dev with FMT_C32, FMT_I8X_C32Y or FMT_I16X_C32Y and for blah2hip_amb_process_multi_dev.
+ * One kernel (beam_samples_kernel, BLAH2HIP_K_BEAM) reads the n_surv planes once and writes the n_beams planes once.  Per
+ * sample and beam the sum is the fp32 fused-multiply-add chain of blah2hip_amb_beamform_dev in the order k = 0 .. n_surv - 1:
+ * |error| <= 4 (n_surv + 1) * 2^-24 * sum_k |w_k| |y_k|; a weight of exactly 1 or 0 passes an fp32 sample through bit for bit and
+ * an int8 sample as its exact conversion.  16-byte stores (pairs of samples) where, CPI by CPI, every input and every beam
+ * plane starts at the same parity of sample; single samples otherwise.  Enqueues only: no allocation, upload or
+ * synchronisation, capturable in a graph.
+ * BLAH2HIP_ERR_INVALID, with nothing enqueued: a NULL handle, plane array, plane, w or output, n_surv outside
+ * [1, BLAH2HIP_MAX_SURV], n_beams outside [1, BLAH2HIP_MAX_BEAMS], n_cpi == 0, cpi_stride or beam_stride < n_samples with
+ * n_cpi > 1, an int8 plane at an odd address (an fp32 plane, in or out, off 8 bytes), a beam plane that overlaps an input plane
+ * or another beam plane. */
+int blah2hip_amb_beam_samples_dev(blah2hip_amb_t h, int fmt, const void *const *d_y, uint32_t n_surv,
+                                  uint32_t n_cpi, uint64_t cpi_stride, const float *w, uint32_t n_beams,
+                                  void *const *d_beam, uint64_t beam_stride, void *stream);
+/* The same with weights that differ from CPI to CPI and live on the device: d_w is a DEVICE array [n_cpi][n_beams][n_surv] of
+ * (re, im) fp32 pairs, as blah2hip_amb_mvdr_weights_dev writes it.  beam_samples_wdev_kernel reads its CPI's weights once
+ * before the first sample; per sample the operations and their order are the same, so weights equal to a
+ * blah2hip_amb_beam_samples_dev call's give that call's bits.  d_w is read when the kernel runs: whatever writes it must be
+ * ordered before this call on the device.  Everything else, error cases included (a NULL d_w for a NULL w), as above. */
+int blah2hip_amb_beam_samples_wdev(blah2hip_amb_t h, int fmt, const void *const *d_y, uint32_t n_surv,
+                                   uint32_t n_cpi, uint64_t cpi_stride, const float *d_w, uint32_t n_beams,
+                                   void *const *d_beam, uint64_t beam_stride, void *stream);
 /* The array snapshot under every detection: d_snap[l][i][k] = cell (row_i, col_i) of CHANNEL map k of CPI l mod n_cpi, complex
  * fp32, shape [n_lists][cap][n_surv] (re, im) -- what phase differences, a Bartlett or MUSIC bearing or a monopulse ratio are
  * computed from without downloading K maps.  d_dets [n_lists][cap] and d_count [n_lists] as blah2hip_detect_dev leaves them
@@ -725,8 +779,8 @@ int blah2hip_amb_result_ptrs(blah2hip_amb_t h, const void **d_map, const double 
 #define BLAH2HIP_K_SAT_ROWS 4 /* 2-D CFAR through the summed-area table (large windows): row prefix sums */
 #define BLAH2HIP_K_SAT_COLS 5 /* ... column prefix sums */
 #define BLAH2HIP_K_ROTATE 6   /* Doppler-centre shift (asymmetric limits only) */
-#define BLAH2HIP_K_BEAM 7     /* beamform_kernel (blah2hip_amb_beamform_dev; its metrics_kernel counts under _METRICS) */
-#define BLAH2HIP_K_COV 8      /* array_cov_kernel + cov_fold_kernel (blah2hip_amb_covariance_dev) */
+#define BLAH2HIP_K_BEAM 7     /* beamform_kernel (blah2hip_amb_beamform_dev; its metrics_kernel counts under _METRICS), beam_samples_kernel */
+#define BLAH2HIP_K_COV 8      /* array_cov_kernel or sample_cov_kernel + cov_fold_kernel (blah2hip_amb_covariance_dev, _sample_covariance_dev) */
 #define BLAH2HIP_K_BEARING 9  /* bearing_kernel (blah2hip_amb_bearing_dev) */
 #define BLAH2HIP_K_COUNT 10
 /* enable != 0: every dev call brackets each kernel with hipEvents */
