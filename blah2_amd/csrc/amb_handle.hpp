@@ -1,0 +1,170 @@
+// Internal to the library: what the units behind include/blah2hip.h share.  The ambiguity handle, whose fields every
+// unit reads directly (no accessors), the error and launch-check helpers, and the few engine functions (capi.hip)
+// that another unit calls.  Host code only: capi.hip, array.hip, detect.hip and context.hip all include it.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include "blah2hip.h"
+#include "range_core.hpp"
+#include "timing.hpp"
+
+#include <algorithm>
+#include <map>
+#include <string>
+#include <vector>
+
+// context.hip: the thread's error string (blah2hip_last_error) and the once-per-(device, kernel) LDS attribute
+extern "C" void blah2hip_set_error_(const char *msg);
+extern "C" hipError_t blah2hip_ensure_lds_(const void *kern, int bytes);
+
+struct blah2hip_amb_s {
+  typedef blah2::cf cf;
+  // ---- geometry and plan: written by create and blah2hip_amb_set_option (capi.hip), read by every unit
+  int device = 0;
+  blah2hip_amb_dims_t dims{};
+  int32_t delayMin = 0, delayMax = 0, dopplerMin = 0, dopplerMax = 0;
+  uint32_t fs = 0;
+  int r3 = 8;
+  blah2::RangePlan plan{};          // segmentation (of the longest chunk) + the first chunk's lag window
+  struct LagChunk { int32_t lag0, count, col0; }; // linear lags lag0 .. lag0 + count - 1 -> map columns col0 ..
+  std::vector<LagChunk> chunks;     // the delay axis as runs of consecutive LINEAR lags (one chunk in the usual case)
+  int32_t maxChunk = 0;
+  std::vector<int32_t> delayAxis;
+  std::vector<double> dopplerAxis;
+  hipStream_t stream = nullptr;
+  int numCU = 256;
+  int dopTilesX = 0, dopTilesY = 0; // direct-DFT fallback grid
+  int dopR3 = 0;                    // 0 = direct fallback, else Bluestein on WgFft<dopR3>
+  int dopGridX = 0;
+  int nParts = 0;                   // metrics partials per CPI
+  int nTiles = 0;                   // 16-column tiles of the range map
+
+  // ---- execution plan: per handle, fixed at create or through blah2hip_amb_set_option (capi.hip); detect.hip reads cfar2d*
+  int rangeGridForce = 0;           // BLAH2HIP_OPT_RANGE_GRID (0 = the launched kernel's residency)
+  int rangeWalk = 0;                // BLAH2HIP_OPT_RANGE_WALK (0 = the engine's choice)
+  int dopForce = BLAH2HIP_DOP_AUTO; // BLAH2HIP_OPT_DOPPLER_KERNEL
+  int rangeKernel = 0;              // BLAH2HIP_OPT_RANGE_KERNEL (0 = by transform length)
+  int fftLenForce = 0;              // BLAH2HIP_OPT_FFT_LEN (0 = planner)
+  int multiMode = BLAH2HIP_MULTI_AUTO; // BLAH2HIP_OPT_MULTI_SURV_RANGE
+  int cfar2dForce = 0;              // BLAH2HIP_OPT_CFAR2D_KERNEL
+  int dopGridForce = 0;             // BLAH2HIP_OPT_DOPPLER_GRID (0 = residency of the persistent kernel)
+  int cfar2dSegRows = 0;            // BLAH2HIP_OPT_CFAR2D_SEG_ROWS (0 = cost model of cfar2d_stream_launch)
+  int cfar2dGridForce = 0;          // BLAH2HIP_OPT_CFAR2D_GRID (0 = one workgroup per CU)
+  int leakMode = 1;                 // BLAH2HIP_OPT_LEAK_COMPENSATION: 0 off, 1 auto (applied where it can reach 3e-5 of the mean level), 2 always
+  int hotMode = 1;                  // BLAH2HIP_OPT_HOT_COLUMNS: 0 off, 1 auto (CPIs long enough for a peak HOT_RATIO above the mean level), 2 always
+
+  // ---- device buffers allocated by create (capi.hip) and freed by destroy, which frees every buffer of the handle
+  cf *d_tw = nullptr;
+  cf *d_dopW = nullptr;
+  double2 *d_dopW64 = nullptr;   // hot_columns_kernel: exp(-2 pi i k / nD) in fp64
+  uint32_t *d_hotCount = nullptr; // [2][max_batch]: columns the last call's hot_columns_kernel rewrote, columns it left out
+  cf *d_R = nullptr;
+  cf *d_map = nullptr;
+  double *d_partSum = nullptr;   // (array.hip's kernels leave their per-workgroup partials here too)
+  float *d_partMax = nullptr;
+  uint32_t *d_tickets = nullptr; // arrival counters of the fused Map::set_metrics finish (doppler_sub1k_kernel), zero between launches
+  uint32_t *d_rangeWalk = nullptr;  // rangew1k_kernel's ticket heads and exit counter (range_walk.hpp), zero between launches
+  double *d_metrics = nullptr;
+  double *d_doppler = nullptr;
+  uint32_t *d_count = nullptr;
+  uint32_t *d_detWords = nullptr;   // detect_finish_kernel, tiled form: [2][max_batch] records appended, tickets taken; zero between launches
+  cf *d_dtw = nullptr;              // exp(-2 pi i k/M)
+  cf *d_chirp = nullptr;            // exp(-i pi n^2/nD)
+  cf *d_bf = nullptr;               // chirp-kernel spectrum / M in register layout
+  cf *d_bfn = nullptr;              // the same in natural order (M = 2048 only: doppler_tilew_kernel)
+
+  // ---- written by capi.hip while it runs: lazily allocated staging, what the last launch ran, FIR, leak, hot columns
+  void *h_pin = nullptr;            // pinned host staging of the c64 entry point
+  size_t h_pin_bytes = 0;
+  void *d_in = nullptr; // staging for the host entry points
+  size_t d_in_bytes = 0;
+  cf *d_rot = nullptr; // rotated reference / converted planes for asymmetric Doppler limits
+  int rangeGridLast = 0;            // BLAH2HIP_INFO_RANGE_GRID: workgroup cap of the last launch
+  int lastDoppler = 0;              // BLAH2HIP_INFO_LAST_DOPPLER_KERNEL
+  int lastRange = 0;                // BLAH2HIP_INFO_LAST_RANGE_KERNEL
+  int dopGridLast = 0, dopTilesLast = 0; // BLAH2HIP_INFO_DOPPLER_GRID / _TILES
+
+  // the clutter filter's FIR fused into the range correlation (blah2hip_amb_set_fir): the filter handle's taps
+  const cf *firW = nullptr; // [max_batch][firBins]; nullptr: the plain range kernels
+  int firBins = 0, firDmin = 0;
+  cf *d_H = nullptr;        // [max_batch][16][256]: the taps' spectrum in the transform's register layout (taps_spectrum_kernel)
+  int32_t *d_firK0 = nullptr; // [max_batch]: the largest tap's index (left out of d_H, applied in the time domain)
+
+  // Fixed-pattern leak compensation (see leak_calibrate): per (range kernel, Doppler kernel) the lags of the zero-Doppler row
+  // into which the fp32 transform chain leaks a fixed fraction g of the lag-0 cell, measured once on a synthetic CPI
+  struct LeakCal { int nLags = 0; double maxAbs = 0.0; bool active = false; int32_t *d_lag = nullptr; cf *d_g = nullptr; };
+  std::map<int, LeakCal> leak;      // key = range kernel id * 64 + Doppler kernel id
+  bool inLeakCal = false;
+  bool lastHot = false;             // the last process call launched hot_columns_kernel
+  hipStream_t lastHotStream = nullptr; // ... on this stream (BLAH2HIP_INFO_HOT_COLUMNS waits for that one only)
+  uint32_t lastHotCpis = 0;         // ... over this many CPIs
+  int lastLeakLags = 0;             // BLAH2HIP_INFO_LEAK_LAGS: lags corrected by the last process call (0 = not applied)
+  double lastLeakMax = 0.0;         // BLAH2HIP_INFO_LEAK_MAX_E12: the largest |g| of the calibration the last call ran under
+
+  // ---- written by detect.hip; bearingGridLast by array.hip
+  struct AlphaTable { double pfa; size_t n; double *d; bool pinned; }; // pinned: handed out by *_prepare, never evicted
+  std::vector<AlphaTable> alphaTables; // CFAR threshold factors, one per (pfa, size) seen
+  double *d_sat = nullptr;          // 2-D CFAR summed-area table [max_batch][nD+1][nDelay+1], allocated at its first use
+  blah2hip_hit_t *d_hits = nullptr; // the *_process calls' hit list, grown to the map's cell count
+  uint32_t hitCap = 0;
+  int cfar2dSegRowsLast = 0, cfar2dGridLast = 0; // BLAH2HIP_INFO_CFAR2D_SEG_ROWS / _GRID
+  int detGridLast = 0, detTiledLast = 0; // BLAH2HIP_INFO_DETECT_GRID / _TILED
+  int bearingGridLast = 0;          // BLAH2HIP_INFO_BEARING_GRID
+
+  // ---- every unit brackets its launches (tic / toc below)
+  blah2::KernelTimer<BLAH2HIP_K_COUNT> timer;
+
+};
+
+namespace blah2 {
+
+static inline int fail(int code, const std::string &msg)
+{
+  blah2hip_set_error_(msg.c_str());
+  return code;
+}
+
+#define HIPCHK(expr)                                                                         \
+  do {                                                                                       \
+    hipError_t e_ = (expr);                                                                  \
+    if (e_ != hipSuccess)                                                                    \
+      return fail(BLAH2HIP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));      \
+  } while (0)
+
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (device, kernel): the
+// attribute belongs to the function object of the CURRENT device, and a process
+// may hold handles on several devices.
+#define LDSCFG(kern, bytes)                                                                   \
+  do {                                                                                       \
+    hipError_t e_ = blah2hip_ensure_lds_((const void *)(kern), (int)(bytes));                 \
+    if (e_ != hipSuccess)                                                                    \
+      return fail(BLAH2HIP_ERR_HIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(e_)); \
+  } while (0)
+
+static inline int tic(blah2hip_amb_s *h, int k, hipStream_t st)
+{
+  HIPCHK(h->timer.tic(k, st));
+  return BLAH2HIP_OK;
+}
+
+static inline int toc(blah2hip_amb_s *h, int k, hipStream_t st)
+{
+  HIPCHK(h->timer.toc(k, st));
+  return BLAH2HIP_OK;
+}
+
+// Workgroups per CPI of a launch that strides over `units` accesses a CPI: eight a CU over the launch of n_cpi CPIs, each
+// with at least one pass of 256 units, and no more than `cap` (what the handle has partials for, where the kernel
+// leaves one per workgroup)
+static inline uint32_t groups_per_cpi(const blah2hip_amb_s *h, size_t units, uint32_t n_cpi, size_t cap = SIZE_MAX)
+{
+  const size_t passes = (units + 255) / 256, spread = (8 * (size_t)h->numCU + n_cpi - 1) / n_cpi;
+  return (uint32_t)std::max<size_t>(1, std::min({cap, passes, spread}));
+}
+
+// capi.hip: Map::set_metrics of n_maps maps of `cells` cells from the n_parts partials a map in h->d_partSum / d_partMax
+// (metrics_kernel, inside its BLAH2HIP_K_METRICS bracket).  Not exported from the library.
+__attribute__((visibility("hidden"))) int amb_metrics_enqueue(blah2hip_amb_s *h, uint32_t n_maps, int n_parts, double cells, double *d_metrics, hipStream_t st);
+
+} // namespace blah2

@@ -1,5 +1,6 @@
 // A receiver array behind the Doppler stage (gfx950 / MI355X only).  No reference counterpart: blah2 has one
 // surveillance channel.
+// Included by array.hip alone: this header defines kernels, so a second unit must not include it.
 //
 //   beamform_kernel    M_b = sum_k w[b][k] M_k for every beam b in ONE pass over the K channel maps, with the
 //                      per-workgroup partials of Map::set_metrics (Map.cpp:187-206) of every beam map
@@ -24,9 +25,27 @@
 #include <hip/hip_runtime.h>
 
 #include "blah2hip.h"
-#include "kernels.hpp"
+#include "metrics_core.hpp"
+
+#include <type_traits>
 
 namespace blah2 {
+
+// f(std::integral_constant<int, K>()) for the call's channel count K = 1 .. BLAH2HIP_MAX_SURV: how every launcher below
+// picks the kernel that is instantiated for K channels (inlined: a launcher is the switch, not a call of it)
+template <class F> __attribute__((always_inline)) inline void with_channel_count(uint32_t K, F f)
+{
+  switch (K) {
+  case 1: f(std::integral_constant<int, 1>()); break;
+  case 2: f(std::integral_constant<int, 2>()); break;
+  case 3: f(std::integral_constant<int, 3>()); break;
+  case 4: f(std::integral_constant<int, 4>()); break;
+  case 5: f(std::integral_constant<int, 5>()); break;
+  case 6: f(std::integral_constant<int, 6>()); break;
+  case 7: f(std::integral_constant<int, 7>()); break;
+  case 8: f(std::integral_constant<int, 8>()); break;
+  }
+}
 
 struct BeamArgs {
   const cf *in;    // [K][nCpi][cells]
@@ -144,16 +163,10 @@ __global__ __launch_bounds__(256) void beamform_wdev_kernel(BeamArgs a, const cf
 // accesses
 template <int V, bool WDEV> inline void launch_beamform(uint32_t K, dim3 grid, hipStream_t st, const BeamArgs &a, const cf *wdev)
 {
-#define BLAH2_BEAM_CASE(k)                                                                    \
-  case k:                                                                                     \
-    if (WDEV) hipLaunchKernelGGL((beamform_wdev_kernel<k, V>), grid, dim3(256), 0, st, a, wdev); \
-    else hipLaunchKernelGGL((beamform_kernel<k, V>), grid, dim3(256), 0, st, a);              \
-    break;
-  switch (K) {
-    BLAH2_BEAM_CASE(1) BLAH2_BEAM_CASE(2) BLAH2_BEAM_CASE(3) BLAH2_BEAM_CASE(4)
-    BLAH2_BEAM_CASE(5) BLAH2_BEAM_CASE(6) BLAH2_BEAM_CASE(7) BLAH2_BEAM_CASE(8)
-  }
-#undef BLAH2_BEAM_CASE
+  with_channel_count(K, [&](auto k) {
+    if (WDEV) hipLaunchKernelGGL((beamform_wdev_kernel<decltype(k)::value, V>), grid, dim3(256), 0, st, a, wdev);
+    else hipLaunchKernelGGL((beamform_kernel<decltype(k)::value, V>), grid, dim3(256), 0, st, a);
+  });
 }
 
 struct SnapArgs {
@@ -261,16 +274,7 @@ __global__ __launch_bounds__(256) void array_cov_kernel(CovArgs a)
 
 inline void launch_array_cov(uint32_t K, dim3 grid, hipStream_t st, const CovArgs &a)
 {
-  switch (K) {
-  case 1: hipLaunchKernelGGL((array_cov_kernel<1>), grid, dim3(256), 0, st, a); break;
-  case 2: hipLaunchKernelGGL((array_cov_kernel<2>), grid, dim3(256), 0, st, a); break;
-  case 3: hipLaunchKernelGGL((array_cov_kernel<3>), grid, dim3(256), 0, st, a); break;
-  case 4: hipLaunchKernelGGL((array_cov_kernel<4>), grid, dim3(256), 0, st, a); break;
-  case 5: hipLaunchKernelGGL((array_cov_kernel<5>), grid, dim3(256), 0, st, a); break;
-  case 6: hipLaunchKernelGGL((array_cov_kernel<6>), grid, dim3(256), 0, st, a); break;
-  case 7: hipLaunchKernelGGL((array_cov_kernel<7>), grid, dim3(256), 0, st, a); break;
-  case 8: hipLaunchKernelGGL((array_cov_kernel<8>), grid, dim3(256), 0, st, a); break;
-  }
+  with_channel_count(K, [&](auto k) { hipLaunchKernelGGL((array_cov_kernel<decltype(k)::value>), grid, dim3(256), 0, st, a); });
 }
 
 // grid (nCpi), 64 threads: thread e < K * K adds entry e of the CPI's nParts partials in index order, then the packed sums
@@ -452,16 +456,7 @@ __global__ __launch_bounds__(64) void mvdr_weights_kernel(MvdrArgs a)
 
 inline void launch_mvdr_weights(uint32_t K, uint32_t nCpi, hipStream_t st, const MvdrArgs &a)
 {
-  switch (K) {
-  case 1: hipLaunchKernelGGL((mvdr_weights_kernel<1>), dim3(nCpi), dim3(64), 0, st, a); break;
-  case 2: hipLaunchKernelGGL((mvdr_weights_kernel<2>), dim3(nCpi), dim3(64), 0, st, a); break;
-  case 3: hipLaunchKernelGGL((mvdr_weights_kernel<3>), dim3(nCpi), dim3(64), 0, st, a); break;
-  case 4: hipLaunchKernelGGL((mvdr_weights_kernel<4>), dim3(nCpi), dim3(64), 0, st, a); break;
-  case 5: hipLaunchKernelGGL((mvdr_weights_kernel<5>), dim3(nCpi), dim3(64), 0, st, a); break;
-  case 6: hipLaunchKernelGGL((mvdr_weights_kernel<6>), dim3(nCpi), dim3(64), 0, st, a); break;
-  case 7: hipLaunchKernelGGL((mvdr_weights_kernel<7>), dim3(nCpi), dim3(64), 0, st, a); break;
-  case 8: hipLaunchKernelGGL((mvdr_weights_kernel<8>), dim3(nCpi), dim3(64), 0, st, a); break;
-  }
+  with_channel_count(K, [&](auto k) { hipLaunchKernelGGL((mvdr_weights_kernel<decltype(k)::value>), dim3(nCpi), dim3(64), 0, st, a); });
 }
 
 // ---- a bearing per detection ----------------------------------------------------------------------------------------------
@@ -595,15 +590,9 @@ __global__ __launch_bounds__(256) void bearing_kernel(BearingArgs a)
 
 inline void launch_bearing(uint32_t K, dim3 grid, hipStream_t st, const BearingArgs &a)
 {
-  switch (K) {
-  case 2: hipLaunchKernelGGL((bearing_kernel<2>), grid, dim3(256), 0, st, a); break;
-  case 3: hipLaunchKernelGGL((bearing_kernel<3>), grid, dim3(256), 0, st, a); break;
-  case 4: hipLaunchKernelGGL((bearing_kernel<4>), grid, dim3(256), 0, st, a); break;
-  case 5: hipLaunchKernelGGL((bearing_kernel<5>), grid, dim3(256), 0, st, a); break;
-  case 6: hipLaunchKernelGGL((bearing_kernel<6>), grid, dim3(256), 0, st, a); break;
-  case 7: hipLaunchKernelGGL((bearing_kernel<7>), grid, dim3(256), 0, st, a); break;
-  case 8: hipLaunchKernelGGL((bearing_kernel<8>), grid, dim3(256), 0, st, a); break;
-  }
+  with_channel_count(K, [&](auto k) { // (a bearing needs two channels)
+    if constexpr (decltype(k)::value >= 2) hipLaunchKernelGGL((bearing_kernel<decltype(k)::value>), grid, dim3(256), 0, st, a);
+  });
 }
 
 // ---- the array in the sample domain: covariance and beam planes of the K channels' samples ------------------------------
@@ -740,16 +729,7 @@ __global__ __launch_bounds__(256) void sample_cov_kernel(SampCovArgs a)
 
 template <class Ch, int V> inline void launch_sample_cov(uint32_t K, dim3 grid, hipStream_t st, const SampCovArgs &a)
 {
-  switch (K) {
-  case 1: hipLaunchKernelGGL((sample_cov_kernel<1, Ch, V>), grid, dim3(256), 0, st, a); break;
-  case 2: hipLaunchKernelGGL((sample_cov_kernel<2, Ch, V>), grid, dim3(256), 0, st, a); break;
-  case 3: hipLaunchKernelGGL((sample_cov_kernel<3, Ch, V>), grid, dim3(256), 0, st, a); break;
-  case 4: hipLaunchKernelGGL((sample_cov_kernel<4, Ch, V>), grid, dim3(256), 0, st, a); break;
-  case 5: hipLaunchKernelGGL((sample_cov_kernel<5, Ch, V>), grid, dim3(256), 0, st, a); break;
-  case 6: hipLaunchKernelGGL((sample_cov_kernel<6, Ch, V>), grid, dim3(256), 0, st, a); break;
-  case 7: hipLaunchKernelGGL((sample_cov_kernel<7, Ch, V>), grid, dim3(256), 0, st, a); break;
-  case 8: hipLaunchKernelGGL((sample_cov_kernel<8, Ch, V>), grid, dim3(256), 0, st, a); break;
-  }
+  with_channel_count(K, [&](auto k) { hipLaunchKernelGGL((sample_cov_kernel<decltype(k)::value, Ch, V>), grid, dim3(256), 0, st, a); });
 }
 
 struct BeamSampArgs {
@@ -849,16 +829,10 @@ __global__ __launch_bounds__(256) void beam_samples_wdev_kernel(BeamSampArgs a, 
 
 template <class Ch, int V, bool WDEV> inline void launch_beam_samples(uint32_t K, dim3 grid, hipStream_t st, const BeamSampArgs &a, const cf *wdev)
 {
-#define BLAH2_BEAM_SAMPLES_CASE(k)                                                                        \
-  case k:                                                                                                 \
-    if (WDEV) hipLaunchKernelGGL((beam_samples_wdev_kernel<k, Ch, V>), grid, dim3(256), 0, st, a, wdev); \
-    else hipLaunchKernelGGL((beam_samples_kernel<k, Ch, V>), grid, dim3(256), 0, st, a);                \
-    break;
-  switch (K) {
-    BLAH2_BEAM_SAMPLES_CASE(1) BLAH2_BEAM_SAMPLES_CASE(2) BLAH2_BEAM_SAMPLES_CASE(3) BLAH2_BEAM_SAMPLES_CASE(4)
-    BLAH2_BEAM_SAMPLES_CASE(5) BLAH2_BEAM_SAMPLES_CASE(6) BLAH2_BEAM_SAMPLES_CASE(7) BLAH2_BEAM_SAMPLES_CASE(8)
-  }
-#undef BLAH2_BEAM_SAMPLES_CASE
+  with_channel_count(K, [&](auto k) {
+    if (WDEV) hipLaunchKernelGGL((beam_samples_wdev_kernel<decltype(k)::value, Ch, V>), grid, dim3(256), 0, st, a, wdev);
+    else hipLaunchKernelGGL((beam_samples_kernel<decltype(k)::value, Ch, V>), grid, dim3(256), 0, st, a);
+  });
 }
 
 } // namespace blah2

@@ -1,55 +1,21 @@
-// C-ABI implementation of include/blah2hip.h: handle management, execution
-// planning, table generation and kernel launches.  gfx950 only; links against
-// libamdhip64 and nothing else.
+// C-ABI implementation of include/blah2hip.h, the engine: handle creation and teardown, options and info, execution
+// planning, table generation, the range and Doppler launchers, leak compensation and hot columns.  The array calls live
+// in array.hip, the detectors in detect.hip, the device context and the error string in context.hip; amb_handle.hpp holds
+// what they share.  gfx950 only; links against libamdhip64 and nothing else.
+#include "amb_handle.hpp"
 #include "kernels.hpp"
-#include "cfar_kernels.hpp"
-#include "detect_kernels.hpp"
-#include "beam_kernels.hpp"
-#include "timing.hpp"
 
 #include <algorithm>
 #include <cmath>
 #include <complex>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <deque>
-#include <map>
-#include <mutex>
-#include <set>
 #include <string>
 #include <vector>
 
 using namespace blah2;
 
 namespace {
-
-thread_local std::string g_err;
-
-int fail(int code, const std::string &msg)
-{
-  g_err = msg;
-  return code;
-}
-
-#define HIPCHK(expr)                                                                         \
-  do {                                                                                       \
-    hipError_t e_ = (expr);                                                                  \
-    if (e_ != hipSuccess)                                                                    \
-      return fail(BLAH2HIP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));      \
-  } while (0)
-
-extern "C" hipError_t blah2hip_ensure_lds_(const void *kern, int bytes);
-
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (device, kernel): the
-// attribute belongs to the function object of the CURRENT device, and a process
-// may hold handles on several devices.
-#define LDSCFG(kern, bytes)                                                                   \
-  do {                                                                                       \
-    hipError_t e_ = blah2hip_ensure_lds_((const void *)(kern), (int)(bytes));                 \
-    if (e_ != hipSuccess)                                                                    \
-      return fail(BLAH2HIP_ERR_HIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(e_)); \
-  } while (0)
 
 // exp(-2*pi*i*k/n) from the exactly reduced angle, fp64 -> fp32
 cf root_of_unity(int64_t k, int64_t n)
@@ -60,99 +26,6 @@ cf root_of_unity(int64_t k, int64_t n)
   // octant folding keeps the argument of sin/cos small; fp64 is ample for an fp32 result
   return cmake((float)std::cos(a), (float)std::sin(a));
 }
-
-} // namespace
-
-struct blah2hip_amb_s {
-  int device = 0;
-  blah2hip_amb_dims_t dims{};
-  int32_t delayMin = 0, delayMax = 0, dopplerMin = 0, dopplerMax = 0;
-  uint32_t fs = 0;
-  int r3 = 8;
-  RangePlan plan{};                 // segmentation (of the longest chunk) + the first chunk's lag window
-  struct LagChunk { int32_t lag0, count, col0; }; // linear lags lag0 .. lag0 + count - 1 -> map columns col0 ..
-  std::vector<LagChunk> chunks;     // the delay axis as runs of consecutive LINEAR lags (one chunk in the usual case)
-  int32_t maxChunk = 0;
-  std::vector<int32_t> delayAxis;
-  std::vector<double> dopplerAxis;
-  hipStream_t stream = nullptr;
-  int numCU = 256;
-  int rangeGridForce = 0;           // BLAH2HIP_OPT_RANGE_GRID (0 = the launched kernel's residency)
-  int rangeGridLast = 0;            // BLAH2HIP_INFO_RANGE_GRID: workgroup cap of the last launch
-  int rangeWalk = 0;                // BLAH2HIP_OPT_RANGE_WALK (0 = the engine's choice)
-  uint32_t *d_rangeWalk = nullptr;  // rangew1k_kernel's ticket heads and exit counter (range_walk.hpp), zero between launches
-  void *h_pin = nullptr;            // pinned host staging of the c64 entry point
-  size_t h_pin_bytes = 0;
-
-  cf *d_tw = nullptr;
-  cf *d_dopW = nullptr;
-  double2 *d_dopW64 = nullptr;   // hot_columns_kernel: exp(-2 pi i k / nD) in fp64
-  uint32_t *d_hotCount = nullptr; // [2][max_batch]: columns the last call's hot_columns_kernel rewrote, columns it left out
-  cf *d_R = nullptr;
-  cf *d_map = nullptr;
-  double *d_partSum = nullptr;
-  uint32_t *d_tickets = nullptr; // arrival counters of the fused Map::set_metrics finish (doppler_sub1k_kernel), zero between launches
-  float *d_partMax = nullptr;
-  double *d_metrics = nullptr;
-  double *d_doppler = nullptr;
-  void *d_in = nullptr; // staging for the host entry points
-  size_t d_in_bytes = 0;
-  cf *d_rot = nullptr; // rotated reference / converted planes for asymmetric Doppler limits
-  blah2hip_hit_t *d_hits = nullptr;
-  uint32_t *d_count = nullptr;
-  uint32_t hitCap = 0;
-  int dopTilesX = 0, dopTilesY = 0; // direct-DFT fallback grid
-  int dopR3 = 0;                    // 0 = direct fallback, else Bluestein on WgFft<dopR3>
-  int dopGridX = 0;
-  int nParts = 0;                   // metrics partials per CPI
-  int nTiles = 0;                   // 16-column tiles of the range map
-  // execution plan: per handle, fixed at create or through blah2hip_amb_set_option
-  int dopForce = BLAH2HIP_DOP_AUTO; // BLAH2HIP_OPT_DOPPLER_KERNEL
-  int lastDoppler = 0;              // BLAH2HIP_INFO_LAST_DOPPLER_KERNEL
-  int lastRange = 0;                // BLAH2HIP_INFO_LAST_RANGE_KERNEL
-  int rangeKernel = 0;              // BLAH2HIP_OPT_RANGE_KERNEL (0 = by transform length)
-  int fftLenForce = 0;              // BLAH2HIP_OPT_FFT_LEN (0 = planner)
-  int multiMode = BLAH2HIP_MULTI_AUTO; // BLAH2HIP_OPT_MULTI_SURV_RANGE
-  int cfar2dForce = 0;              // BLAH2HIP_OPT_CFAR2D_KERNEL
-  int dopGridForce = 0;             // BLAH2HIP_OPT_DOPPLER_GRID (0 = residency of the persistent kernel)
-  int cfar2dSegRows = 0;            // BLAH2HIP_OPT_CFAR2D_SEG_ROWS (0 = cost model of cfar2d_stream_launch)
-  int cfar2dGridForce = 0;          // BLAH2HIP_OPT_CFAR2D_GRID (0 = one workgroup per CU)
-  int cfar2dSegRowsLast = 0, cfar2dGridLast = 0; // BLAH2HIP_INFO_CFAR2D_SEG_ROWS / _GRID
-  int dopGridLast = 0, dopTilesLast = 0; // BLAH2HIP_INFO_DOPPLER_GRID / _TILES
-  struct AlphaTable { double pfa; size_t n; double *d; bool pinned; }; // pinned: handed out by *_prepare, never evicted
-  std::vector<AlphaTable> alphaTables; // CFAR threshold factors, one per (pfa, size) seen
-  cf *d_dtw = nullptr;              // exp(-2 pi i k/M)
-  cf *d_chirp = nullptr;            // exp(-i pi n^2/nD)
-  cf *d_bf = nullptr;               // chirp-kernel spectrum / M in register layout
-  cf *d_bfn = nullptr;              // the same in natural order (M = 2048 only: doppler_tilew_kernel)
-  double *d_sat = nullptr;          // 2-D CFAR summed-area table [max_batch][nD+1][nDelay+1]
-  uint32_t *d_detWords = nullptr;   // detect_finish_kernel, tiled form: [2][max_batch] records appended, tickets taken; zero between launches
-  int detGridLast = 0, detTiledLast = 0; // BLAH2HIP_INFO_DETECT_GRID / _TILED
-  int bearingGridLast = 0;          // BLAH2HIP_INFO_BEARING_GRID
-
-  KernelTimer<BLAH2HIP_K_COUNT> timer;
-
-  // the clutter filter's FIR fused into the range correlation (blah2hip_amb_set_fir): the filter handle's taps
-  const cf *firW = nullptr; // [max_batch][firBins]; nullptr: the plain range kernels
-  int firBins = 0, firDmin = 0;
-  cf *d_H = nullptr;        // [max_batch][16][256]: the taps' spectrum in the transform's register layout (taps_spectrum_kernel)
-  int32_t *d_firK0 = nullptr; // [max_batch]: the largest tap's index (left out of d_H, applied in the time domain)
-
-  // Fixed-pattern leak compensation (see leak_calibrate): per (range kernel, Doppler kernel) the lags of the zero-Doppler row
-  // into which the fp32 transform chain leaks a fixed fraction g of the lag-0 cell, measured once on a synthetic CPI
-  struct LeakCal { int nLags = 0; double maxAbs = 0.0; bool active = false; int32_t *d_lag = nullptr; cf *d_g = nullptr; };
-  std::map<int, LeakCal> leak;      // key = range kernel id * 64 + Doppler kernel id
-  int leakMode = 1;                 // BLAH2HIP_OPT_LEAK_COMPENSATION: 0 off, 1 auto (applied where it can reach 3e-5 of the mean level), 2 always
-  bool inLeakCal = false;
-  int hotMode = 1;                  // BLAH2HIP_OPT_HOT_COLUMNS: 0 off, 1 auto (CPIs long enough for a peak HOT_RATIO above the mean level), 2 always
-  bool lastHot = false;             // the last process call launched hot_columns_kernel
-  hipStream_t lastHotStream = nullptr; // ... on this stream (BLAH2HIP_INFO_HOT_COLUMNS waits for that one only)
-  uint32_t lastHotCpis = 0;         // ... over this many CPIs
-  int lastLeakLags = 0;             // BLAH2HIP_INFO_LEAK_LAGS: lags corrected by the last process call (0 = not applied)
-  double lastLeakMax = 0.0;         // BLAH2HIP_INFO_LEAK_MAX_E12: the largest |g| of the calibration the last call ran under
-};
-
-namespace {
 
 // ---------------------------------------------------------------- planning --
 // Ambiguity::Ambiguity, Ambiguity.cpp:11-82 (same fp64 expressions, same
@@ -545,18 +418,6 @@ int upload_range_table(blah2hip_amb_s *h)
   return BLAH2HIP_OK;
 }
 
-int tic(blah2hip_amb_s *h, int k, hipStream_t st)
-{
-  HIPCHK(h->timer.tic(k, st));
-  return BLAH2HIP_OK;
-}
-
-int toc(blah2hip_amb_s *h, int k, hipStream_t st)
-{
-  HIPCHK(h->timer.toc(k, st));
-  return BLAH2HIP_OK;
-}
-
 int ensure_staging(blah2hip_amb_s *h, size_t bytes)
 {
   if (h->d_in_bytes >= bytes) return BLAH2HIP_OK;
@@ -621,123 +482,6 @@ int pick_doppler(const blah2hip_amb_s *h, uint32_t n_cpi)
   if (fills && doppler_kernel_applicable(h, BLAH2HIP_DOP_TILEW2)) return BLAH2HIP_DOP_TILEW2;
   if (fills && doppler_kernel_applicable(h, BLAH2HIP_DOP_TILEM)) return BLAH2HIP_DOP_TILEM;
   return BLAH2HIP_DOP_COLUMN;
-}
-
-// CFAR threshold factors alpha[n] = n*(pfa^(-1/n) - 1), n = 1..maxN, evaluated with the
-// same libm pow the reference calls (CfarDetector1D.cpp:76).  A small per-handle cache keyed by
-// (pfa, maxN), least recently used first out (a caller that adapts pfa per CPI does not grow device
-// memory): a hit only hands out the pointer; a miss allocates and uploads (blocking), which is
-// refused while `st` is being captured into a graph -- *_prepare is the call for that.  A table *_prepare has handed out
-// lives as long as the handle (`pin`): a graph captured afterwards has its address baked in, and no synchronisation
-// at eviction time protects a later replay.  Only unpinned tables are evicted.
-constexpr size_t ALPHA_TABLES_MAX = 8;
-int alpha_table(blah2hip_amb_s *h, double pfa, size_t maxN, const double **out, hipStream_t st = nullptr, bool pin = false)
-{
-  auto &T = h->alphaTables;
-  for (size_t i = 0; i < T.size(); i++)
-    if (T[i].pfa == pfa && T[i].n >= maxN) {
-      blah2hip_amb_s::AlphaTable t = T[i];
-      t.pinned = t.pinned || pin;
-      T.erase(T.begin() + (long)i);
-      T.push_back(t); // most recently used last
-      *out = t.d;
-      return BLAH2HIP_OK;
-    }
-  if (st) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-      return fail(BLAH2HIP_ERR_INVALID, "threshold table of this (pfa, window) is not resident: call blah2hip_cfar1d_prepare / "
-                                        "blah2hip_cfar2d_prepare before capturing the stream");
-  }
-  std::vector<double> alpha(maxN + 1);
-  alpha[0] = std::nan("");
-  for (size_t n = 1; n <= maxN; n++) alpha[n] = (double)n * (pow(pfa, -1.0 / (double)n) - 1);
-  size_t unpinned = 0;
-  for (const auto &e : T) unpinned += e.pinned ? 0 : 1;
-  if (unpinned >= ALPHA_TABLES_MAX) {
-    HIPCHK(hipDeviceSynchronize()); // the oldest unpinned table may still be read by enqueued work
-    for (size_t i = 0; i < T.size(); i++)
-      if (!T[i].pinned) {
-        (void)hipFree(T[i].d);
-        T.erase(T.begin() + (long)i);
-        break;
-      }
-  }
-  blah2hip_amb_s::AlphaTable t{pfa, maxN, nullptr, pin};
-  HIPCHK(hipMalloc(&t.d, (maxN + 1) * sizeof(double)));
-  hipError_t e = hipMemcpy(t.d, alpha.data(), (maxN + 1) * sizeof(double), hipMemcpyHostToDevice);
-  if (e != hipSuccess) { (void)hipFree(t.d); return fail(BLAH2HIP_ERR_HIP, std::string("alpha table upload: ") + hipGetErrorString(e)); }
-  T.push_back(t);
-  *out = t.d;
-  return BLAH2HIP_OK;
-}
-
-// the one-pass tile kernel covers windows whose halo fits its LDS budget; larger ones take the summed-area table
-bool cfar2d_use_tile(const blah2hip_amb_s *h, int ngd, int ntd, int ngf, int ntf)
-{
-  if (h->cfar2dForce == BLAH2HIP_CFAR2D_SAT) return false;
-  return ngf + ntf <= C2T_MAX_HR && ngd + ntd <= C2T_MAX_HC;
-}
-
-// the stream kernel exists for the window shapes of C2S_SHAPES (cfar_kernels.hpp)
-bool cfar2d_stream_shape(int ngd, int ntd, int ngf, int ntf)
-{
-#define B2_X(TD, GD, TF, GF) if (ntd == TD && ngd == GD && ntf == TF && ngf == GF) return true;
-  C2S_SHAPES(B2_X)
-#undef B2_X
-  return false;
-}
-// The rows the detector skips (|doppler| < minDoppler, CfarDetector1D.cpp:40) as ONE interval [lo, hi) of the handle's Doppler axis
-// (monotonic: Ambiguity.cpp:60-66), which the stream kernel tests with scalar compares; false if they are not one interval.
-bool cfar2d_dead_rows(const blah2hip_amb_s *h, double min_doppler, int *lo, int *hi)
-{
-  const int nD = (int)h->dims.n_doppler_bins;
-  int first = nD, last = -1, count = 0;
-  for (int i = 0; i < nD; i++)
-    if (std::fabs(h->dopplerAxis[i]) < min_doppler) { first = std::min(first, i); last = i; count++; }
-  if (count == 0) { *lo = *hi = 0; return true; }
-  *lo = first; *hi = last + 1;
-  return count == last + 1 - first;
-}
-bool cfar2d_use_stream(const blah2hip_amb_s *h, int ngd, int ntd, int ngf, int ntf, double min_doppler)
-{
-  if (h->cfar2dForce == BLAH2HIP_CFAR2D_SAT || h->cfar2dForce == BLAH2HIP_CFAR2D_TILE) return false;
-  int lo, hi;
-  return cfar2d_stream_shape(ngd, ntd, ngf, ntf) && cfar2d_dead_rows(h, min_doppler, &lo, &hi);
-}
-
-// rows per segment: the fewest rounds of (segment + its 2 hR halo rows) over the wave slots of the chip
-void cfar2d_stream_launch(blah2hip_amb_s *h, const Cfar2dArgs &a, uint32_t n_cpi, hipStream_t st)
-{
-  Cfar2dStreamArgs ta;
-  ta.d = a;
-  ta.nCpi = (int32_t)n_cpi;
-  const int hC = a.ngD + a.ntD, hR = a.ngF + a.ntF;
-  ta.strips = (a.nDelay + (64 - 2 * hC) - 1) / (64 - 2 * hC);
-  const int64_t slots = (int64_t)h->numCU * 4 * 5; // about five waves per SIMD at ~ 100 VGPRs
-  int64_t best = INT64_MAX;
-  for (int R : {8, 16, 32, 64, 128, 256, 512, 1024, (int)a.nD}) { // a lone CPI: short segments, every SIMD a wave
-    if (R > a.nD) continue;
-    const int64_t segs = (a.nD + R - 1) / R, tasks = segs * ta.strips * n_cpi;
-    const int64_t cost = ((tasks + slots - 1) / slots) * (std::min(R, (int)a.nD) + 2 * hR + 16); // 16: start-up of a wave, in rows
-    if (cost < best) { best = cost; ta.rowsPerSeg = std::min(R, (int)a.nD); ta.segs = (int32_t)segs; }
-  }
-  if (h->cfar2dSegRows > 0) { // BLAH2HIP_OPT_CFAR2D_SEG_ROWS
-    ta.rowsPerSeg = std::min(h->cfar2dSegRows, (int)a.nD);
-    ta.segs = (a.nD + ta.rowsPerSeg - 1) / ta.rowsPerSeg;
-  }
-  h->cfar2dSegRowsLast = ta.rowsPerSeg;
-  h->cfar2dGridLast = 0;
-  ta.nTasks = ta.nCpi * ta.segs * ta.strips;
-  cfar2d_dead_rows(h, a.minDoppler, &ta.deadLo, &ta.deadHi);
-  const int grid = (((ta.nTasks + 3) / 4) + 7) & ~7;
-#define B2_X(TD, GD, TF, GF) \
-  if (a.ntD == TD && a.ngD == GD && a.ntF == TF && a.ngF == GF) { \
-    hipLaunchKernelGGL((cfar2d_stream_kernel<TD, GD, TF, GF>), dim3(grid), dim3(256), 0, st, ta); \
-    return; \
-  }
-  C2S_SHAPES(B2_X)
-#undef B2_X
 }
 
 // ------------------------------------------------------------ leak compensation --
@@ -1123,31 +867,20 @@ const char *fir_unfusable(const blah2hip_amb_s *h, int fmt, int nBins, int firDm
   return nullptr;
 }
 
-int ensure_sat(blah2hip_amb_s *h)
-{
-  if (h->d_sat) return BLAH2HIP_OK;
-  const size_t satElems = (size_t)(h->dims.n_doppler_bins + 1) * (h->dims.n_delay_bins + 1);
-  HIPCHK(hipMalloc(&h->d_sat, satElems * h->dims.max_batch * sizeof(double)));
-  HIPCHK(hipMemset(h->d_sat, 0, satElems * h->dims.max_batch * sizeof(double))); // zero borders
-  return BLAH2HIP_OK;
-}
-
 } // namespace
+
+int blah2::amb_metrics_enqueue(blah2hip_amb_s *h, uint32_t n_maps, int n_parts, double cells, double *d_metrics, hipStream_t st)
+{
+  int rc;
+  if ((rc = tic(h, BLAH2HIP_K_METRICS, st))) return rc;
+  hipLaunchKernelGGL(metrics_kernel, dim3(n_maps), dim3(256), 0, st, h->d_partSum, h->d_partMax, n_parts, cells, d_metrics);
+  HIPCHK(hipGetLastError());
+  return toc(h, BLAH2HIP_K_METRICS, st);
+}
 
 extern "C" {
 
-const char *blah2hip_last_error(void) { return g_err.c_str(); }
 const char *blah2hip_version(void) { return "blah2hip 0.1 (gfx950)"; }
-
-int blah2hip_device_count(int *count)
-{
-  if (!count) return fail(BLAH2HIP_ERR_INVALID, "count is NULL");
-  int n = 0;
-  hipError_t e = hipGetDeviceCount(&n);
-  if (e != hipSuccess) { *count = 0; return fail(BLAH2HIP_ERR_NO_DEVICE, hipGetErrorString(e)); }
-  *count = n;
-  return BLAH2HIP_OK;
-}
 
 // HammingNumber.cpp:38-48: first 5-smooth number strictly above v.
 uint32_t blah2hip_next_hamming(uint32_t v)
@@ -1778,13 +1511,7 @@ static int amb_tail_stage(blah2hip_amb_s *h, uint32_t n_cpi, cf *map, double *me
   }
   if ((rc = toc(h, BLAH2HIP_K_DOPPLER, st))) return rc;
 
-  if (nPartsUsed) {
-    if ((rc = tic(h, BLAH2HIP_K_METRICS, st))) return rc;
-    hipLaunchKernelGGL(metrics_kernel, dim3(n_cpi), dim3(256), 0, st, h->d_partSum, h->d_partMax,
-                       nPartsUsed, (double)nD * (double)nDelay, met);
-    HIPCHK(hipGetLastError());
-    if ((rc = toc(h, BLAH2HIP_K_METRICS, st))) return rc;
-  }
+  if (nPartsUsed) return amb_metrics_enqueue(h, n_cpi, nPartsUsed, (double)nD * (double)nDelay, met, st);
   return BLAH2HIP_OK;
 }
 
@@ -1956,375 +1683,6 @@ int blah2hip_amb_db_dev(blah2hip_amb_t h, const void *d_map, const double *d_met
   return BLAH2HIP_OK;
 }
 
-// ------------------------------------------------ beams in the map domain --
-static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-  return a0 < b0 + nb && b0 < a0 + na;
-}
-
-// blah2hip_amb_beamform_dev (w: the host's one set of weights) and blah2hip_amb_beamform_wdev (d_w: a set per CPI on the device)
-static int beamform_enqueue(blah2hip_amb_t h, const void *d_map, uint32_t n_surv, uint32_t n_cpi, const float *w, const float *d_w,
-                            uint32_t n_beams, void *d_beam_map, double *d_beam_metrics, void *stream)
-{
-  if (!h) return fail(BLAH2HIP_ERR_INVALID, "NULL handle");
-  if (n_surv == 0 || n_surv > BLAH2HIP_MAX_SURV) return fail(BLAH2HIP_ERR_INVALID, "n_surv outside [1, BLAH2HIP_MAX_SURV]");
-  if (n_beams == 0 || n_beams > BLAH2HIP_MAX_BEAMS) return fail(BLAH2HIP_ERR_INVALID, "n_beams outside [1, BLAH2HIP_MAX_BEAMS]");
-  if (n_cpi == 0) return fail(BLAH2HIP_ERR_INVALID, "n_cpi is 0");
-  if ((uint64_t)n_surv * n_cpi > h->dims.max_batch) return fail(BLAH2HIP_ERR_INVALID, "n_surv * n_cpi above max_batch");
-  if ((uint64_t)n_beams * n_cpi > h->dims.max_batch) return fail(BLAH2HIP_ERR_INVALID, "n_beams * n_cpi above max_batch");
-  if ((!w && !d_w) || !d_beam_map || !d_beam_metrics) return fail(BLAH2HIP_ERR_INVALID, "NULL weights or output");
-  const size_t cells = (size_t)h->dims.n_doppler_bins * h->dims.n_delay_bins;
-  const cf *in = d_map ? (const cf *)d_map : h->d_map;
-  const size_t inBytes = (size_t)n_surv * n_cpi * cells * sizeof(cf);
-  if (ranges_overlap(in, inBytes, d_beam_map, (size_t)n_beams * n_cpi * cells * sizeof(cf)) ||
-      ranges_overlap(in, inBytes, d_beam_metrics, (size_t)n_beams * n_cpi * 2 * sizeof(double)))
-    return fail(BLAH2HIP_ERR_INVALID, "beamform: an output overlaps the input maps");
-  HIPCHK(hipSetDevice(h->device));
-  hipStream_t st = (hipStream_t)stream;
-
-  BeamArgs a;
-  a.in = in;
-  a.out = (cf *)d_beam_map;
-  a.partSum = h->d_partSum;
-  a.partMax = h->d_partMax;
-  a.cells = (uint32_t)cells;
-  a.nCpi = n_cpi;
-  a.nBeams = n_beams;
-  memset(a.w, 0, sizeof(a.w));
-  if (!d_w)
-    for (uint32_t b = 0; b < n_beams; b++)
-      for (uint32_t k = 0; k < n_surv; k++) a.w[b][k] = cmake(w[2 * (b * n_surv + k)], w[2 * (b * n_surv + k) + 1]);
-  // 16-byte accesses where CPI c starts at the same offset modulo 16 bytes in every channel's and every beam's block: the
-  // blocks are n_cpi * cells cells apart, so an odd product (odd cell count, odd n_cpi) with more than one block does not
-  const bool oddBlock = ((size_t)n_cpi * cells) & 1;
-  const bool wide = !(((uintptr_t)in ^ (uintptr_t)d_beam_map) & 15) && !((uintptr_t)in & 7) &&
-                    !(oddBlock && (n_surv > 1 || n_beams > 1));
-  // workgroups per CPI: eight a CU over the launch, each with at least one pass of 256 units, and no more than the
-  // handle has partials for (nParts per CPI of max_batch >= n_beams * n_cpi)
-  const size_t units = wide ? (cells + 1) / 2 : cells;
-  const uint32_t gMax = (uint32_t)std::min<size_t>((size_t)h->nParts, (units + 255) / 256);
-  const uint32_t G = std::max(1u, std::min(gMax, (8u * (uint32_t)h->numCU + n_cpi - 1) / n_cpi));
-  int rc;
-  if ((rc = tic(h, BLAH2HIP_K_BEAM, st))) return rc;
-  if (d_w) {
-    if (wide) launch_beamform<2, true>(n_surv, dim3(G, n_cpi), st, a, (const cf *)d_w);
-    else launch_beamform<1, true>(n_surv, dim3(G, n_cpi), st, a, (const cf *)d_w);
-  } else {
-    if (wide) launch_beamform<2, false>(n_surv, dim3(G, n_cpi), st, a, nullptr);
-    else launch_beamform<1, false>(n_surv, dim3(G, n_cpi), st, a, nullptr);
-  }
-  HIPCHK(hipGetLastError());
-  if ((rc = toc(h, BLAH2HIP_K_BEAM, st))) return rc;
-  if ((rc = tic(h, BLAH2HIP_K_METRICS, st))) return rc;
-  hipLaunchKernelGGL(metrics_kernel, dim3(n_beams * n_cpi), dim3(256), 0, st, h->d_partSum, h->d_partMax, (int)G,
-                     (double)cells, d_beam_metrics);
-  HIPCHK(hipGetLastError());
-  return toc(h, BLAH2HIP_K_METRICS, st);
-}
-
-int blah2hip_amb_beamform_dev(blah2hip_amb_t h, const void *d_map, uint32_t n_surv, uint32_t n_cpi, const float *w,
-                              uint32_t n_beams, void *d_beam_map, double *d_beam_metrics, void *stream)
-{
-  return beamform_enqueue(h, d_map, n_surv, n_cpi, w, nullptr, n_beams, d_beam_map, d_beam_metrics, stream);
-}
-
-int blah2hip_amb_beamform_wdev(blah2hip_amb_t h, const void *d_map, uint32_t n_surv, uint32_t n_cpi, const float *d_w,
-                               uint32_t n_beams, void *d_beam_map, double *d_beam_metrics, void *stream)
-{
-  return beamform_enqueue(h, d_map, n_surv, n_cpi, nullptr, d_w, n_beams, d_beam_map, d_beam_metrics, stream);
-}
-
-// ------------------------------------------------------- adaptive beams --
-int blah2hip_amb_covariance_dev(blah2hip_amb_t h, const void *d_map, uint32_t n_surv, uint32_t n_cpi, uint32_t row0, uint32_t row1,
-                                uint32_t col0, uint32_t col1, double *d_cov, void *stream)
-{
-  if (!h || !d_cov) return fail(BLAH2HIP_ERR_INVALID, "NULL handle or output");
-  if (n_surv == 0 || n_surv > BLAH2HIP_MAX_SURV) return fail(BLAH2HIP_ERR_INVALID, "n_surv outside [1, BLAH2HIP_MAX_SURV]");
-  if (n_cpi == 0) return fail(BLAH2HIP_ERR_INVALID, "n_cpi is 0");
-  if ((uint64_t)n_surv * n_cpi > h->dims.max_batch) return fail(BLAH2HIP_ERR_INVALID, "n_surv * n_cpi above max_batch");
-  const uint32_t nD = h->dims.n_doppler_bins, nDelay = h->dims.n_delay_bins;
-  if (row0 >= row1 || row1 > nD || col0 >= col1 || col1 > nDelay)
-    return fail(BLAH2HIP_ERR_INVALID, "covariance: the training rectangle is empty or leaves the map");
-  const size_t cells = (size_t)nD * nDelay;
-  const cf *in = d_map ? (const cf *)d_map : h->d_map;
-  const size_t KK = (size_t)n_surv * n_surv;
-  if (ranges_overlap(in, (size_t)n_surv * n_cpi * cells * sizeof(cf), d_cov, (size_t)n_cpi * KK * 2 * sizeof(double)))
-    return fail(BLAH2HIP_ERR_INVALID, "covariance: the output overlaps the input maps");
-  HIPCHK(hipSetDevice(h->device));
-  hipStream_t st = (hipStream_t)stream;
-
-  CovArgs a;
-  a.in = in;
-  a.part = h->d_partSum;
-  a.chStride = (size_t)n_cpi * cells;
-  a.cells = (uint32_t)cells;
-  a.nDelay = nDelay;
-  a.row0 = row0; a.col0 = col0; a.nRows = row1 - row0; a.width = col1 - col0;
-  // workgroups per CPI: eight a CU over the launch, each with at least one pass of 256 cells, and no more than the
-  // handle's partials hold: n_cpi * G * K^2 doubles in max_batch * nParts (n_surv * n_cpi <= max_batch and nParts >= 128,
-  // so there is room for 16 at the least)
-  const size_t n = (size_t)a.nRows * a.width;
-  const size_t gCap = ((size_t)h->dims.max_batch * h->nParts) / ((size_t)n_cpi * KK);
-  if (gCap == 0) return fail(BLAH2HIP_ERR_INVALID, "covariance: the handle's partials are too small");
-  const uint32_t gMax = (uint32_t)std::min<size_t>(gCap, (n + 255) / 256);
-  const uint32_t G = std::max(1u, std::min(gMax, (8u * (uint32_t)h->numCU + n_cpi - 1) / n_cpi));
-  int rc;
-  if ((rc = tic(h, BLAH2HIP_K_COV, st))) return rc;
-  launch_array_cov(n_surv, dim3(G, n_cpi), st, a);
-  HIPCHK(hipGetLastError());
-  hipLaunchKernelGGL(cov_fold_kernel, dim3(n_cpi), dim3(64), 0, st, h->d_partSum, G, n_surv, d_cov);
-  HIPCHK(hipGetLastError());
-  return toc(h, BLAH2HIP_K_COV, st);
-}
-
-int blah2hip_amb_mvdr_weights_dev(blah2hip_amb_t h, const double *d_cov, uint32_t n_surv, uint32_t n_cpi, const float *steer,
-                                  uint32_t n_beams, double loading, float *d_w, int32_t *d_ok, void *stream)
-{
-  if (!h || !d_cov || !steer || !d_w) return fail(BLAH2HIP_ERR_INVALID, "NULL argument");
-  if (n_surv == 0 || n_surv > BLAH2HIP_MAX_SURV) return fail(BLAH2HIP_ERR_INVALID, "n_surv outside [1, BLAH2HIP_MAX_SURV]");
-  if (n_beams == 0 || n_beams > BLAH2HIP_MAX_BEAMS) return fail(BLAH2HIP_ERR_INVALID, "n_beams outside [1, BLAH2HIP_MAX_BEAMS]");
-  if (n_cpi == 0) return fail(BLAH2HIP_ERR_INVALID, "n_cpi is 0");
-  if (!(loading >= 0.0) || !std::isfinite(loading)) return fail(BLAH2HIP_ERR_INVALID, "mvdr: loading is negative or not finite");
-  MvdrArgs a;
-  memset(a.steer, 0, sizeof(a.steer));
-  for (uint32_t b = 0; b < n_beams; b++) {
-    bool any = false;
-    for (uint32_t k = 0; k < n_surv; k++) {
-      a.steer[b][k] = cmake(steer[2 * (b * n_surv + k)], steer[2 * (b * n_surv + k) + 1]);
-      any = any || a.steer[b][k].x != 0.f || a.steer[b][k].y != 0.f;
-    }
-    if (!any) return fail(BLAH2HIP_ERR_INVALID, "mvdr: a steering vector is all zero");
-  }
-  HIPCHK(hipSetDevice(h->device));
-  a.cov = d_cov;
-  a.w = (cf *)d_w;
-  a.ok = d_ok;
-  a.loading = loading;
-  a.nBeams = n_beams;
-  launch_mvdr_weights(n_surv, n_cpi, (hipStream_t)stream, a);
-  HIPCHK(hipGetLastError());
-  return BLAH2HIP_OK;
-}
-
-// ------------------------------------------- the array in the sample domain --
-// what the sample-domain calls share: format, counts, planes and their alignment, stride.  bytes: one sample of a plane.
-static int sample_planes_check(blah2hip_amb_t h, int fmt, const void *const *d_y, uint32_t n_surv, uint32_t n_cpi, uint64_t cpi_stride,
-                               size_t *bytes)
-{
-  if (!h) return fail(BLAH2HIP_ERR_INVALID, "NULL handle");
-  if (fmt != BLAH2HIP_FMT_C32 && fmt != BLAH2HIP_FMT_I8)
-    return fail(BLAH2HIP_ERR_UNSUPPORTED, "sample-domain beams: BLAH2HIP_FMT_C32 or BLAH2HIP_FMT_I8 planes");
-  if (n_surv == 0 || n_surv > BLAH2HIP_MAX_SURV) return fail(BLAH2HIP_ERR_INVALID, "n_surv outside [1, BLAH2HIP_MAX_SURV]");
-  if (n_cpi == 0) return fail(BLAH2HIP_ERR_INVALID, "n_cpi is 0");
-  if (!d_y) return fail(BLAH2HIP_ERR_INVALID, "NULL plane array");
-  *bytes = fmt == BLAH2HIP_FMT_I8 ? 2 : 8;
-  for (uint32_t k = 0; k < n_surv; k++) {
-    if (!d_y[k]) return fail(BLAH2HIP_ERR_INVALID, "NULL plane");
-    if ((uintptr_t)d_y[k] & (*bytes - 1))
-      return fail(BLAH2HIP_ERR_INVALID, "a plane is not aligned to its sample (int8 pairs: 2 bytes, fp32 pairs: 8 bytes)");
-  }
-  if (n_cpi > 1 && cpi_stride < h->dims.n_samples) return fail(BLAH2HIP_ERR_INVALID, "cpi_stride < n_samples");
-  return BLAH2HIP_OK;
-}
-
-// true where, CPI by CPI, sample `first` of every plane sits at the same offset modulo an access of V samples: the
-// number of single samples in front of the first aligned access is then one number per CPI (it may differ between CPIs)
-static bool sample_planes_agree(const void *const *planes, uint32_t n_planes, size_t bytes, uint64_t stride, uint32_t n_cpi,
-                                uint32_t first, uint32_t V, const void *const *more = nullptr, uint32_t n_more = 0, size_t more_bytes = 0,
-                                uint64_t more_stride = 0)
-{
-  for (uint32_t c = 0; c < n_cpi; c++) {
-    const uint64_t at0 = ((uintptr_t)planes[0] / bytes + c * stride + first) % V;
-    for (uint32_t k = 1; k < n_planes; k++)
-      if (((uintptr_t)planes[k] / bytes + c * stride + first) % V != at0) return false;
-    for (uint32_t b = 0; b < n_more; b++)
-      if (((uintptr_t)more[b] / more_bytes + c * more_stride + first) % V != at0) return false;
-  }
-  return true;
-}
-
-int blah2hip_amb_sample_covariance_dev(blah2hip_amb_t h, int fmt, const void *const *d_y, uint32_t n_surv, uint32_t n_cpi,
-                                       uint64_t cpi_stride, uint32_t s0, uint32_t s1, double *d_cov, void *stream)
-{
-  size_t bytes = 0;
-  int rc;
-  if ((rc = sample_planes_check(h, fmt, d_y, n_surv, n_cpi, cpi_stride, &bytes))) return rc;
-  if (!d_cov) return fail(BLAH2HIP_ERR_INVALID, "NULL output");
-  if ((uint64_t)n_surv * n_cpi > h->dims.max_batch) return fail(BLAH2HIP_ERR_INVALID, "n_surv * n_cpi above max_batch");
-  const uint32_t nS = h->dims.n_samples;
-  if (s0 >= s1 || s1 > nS) return fail(BLAH2HIP_ERR_INVALID, "sample covariance: the window is empty or leaves the CPI");
-  const size_t KK = (size_t)n_surv * n_surv;
-  const size_t planeBytes = ((size_t)(n_cpi - 1) * cpi_stride + nS) * bytes;
-  for (uint32_t k = 0; k < n_surv; k++)
-    if (ranges_overlap(d_y[k], planeBytes, d_cov, (size_t)n_cpi * KK * 2 * sizeof(double)))
-      return fail(BLAH2HIP_ERR_INVALID, "sample covariance: the output overlaps an input plane");
-  HIPCHK(hipSetDevice(h->device));
-  hipStream_t st = (hipStream_t)stream;
-
-  SampCovArgs a;
-  memset(a.y, 0, sizeof(a.y));
-  for (uint32_t k = 0; k < n_surv; k++) a.y[k] = d_y[k];
-  a.part = h->d_partSum;
-  a.cpiStride = cpi_stride;
-  a.s0 = s0;
-  a.n = s1 - s0;
-  const uint32_t V = fmt == BLAH2HIP_FMT_I8 ? SampI8::COVW : SampC32::COVW;
-  const bool wide = sample_planes_agree(d_y, n_surv, bytes, cpi_stride, n_cpi, s0, V);
-  // workgroups per CPI: blah2hip_amb_covariance_dev's rule, over accesses instead of cells
-  const size_t units = wide ? (a.n + V - 1) / V : a.n;
-  const size_t gCap = ((size_t)h->dims.max_batch * h->nParts) / ((size_t)n_cpi * KK);
-  if (gCap == 0) return fail(BLAH2HIP_ERR_INVALID, "sample covariance: the handle's partials are too small");
-  const uint32_t gMax = (uint32_t)std::min<size_t>(gCap, (units + 255) / 256);
-  const uint32_t G = std::max(1u, std::min(gMax, (8u * (uint32_t)h->numCU + n_cpi - 1) / n_cpi));
-  if ((rc = tic(h, BLAH2HIP_K_COV, st))) return rc;
-  const dim3 grid(G, n_cpi);
-  if (fmt == BLAH2HIP_FMT_I8) {
-    if (wide) launch_sample_cov<SampI8, SampI8::COVW>(n_surv, grid, st, a);
-    else launch_sample_cov<SampI8, 1>(n_surv, grid, st, a);
-  } else {
-    if (wide) launch_sample_cov<SampC32, SampC32::COVW>(n_surv, grid, st, a);
-    else launch_sample_cov<SampC32, 1>(n_surv, grid, st, a);
-  }
-  HIPCHK(hipGetLastError());
-  hipLaunchKernelGGL(cov_fold_kernel, dim3(n_cpi), dim3(64), 0, st, h->d_partSum, G, n_surv, d_cov);
-  HIPCHK(hipGetLastError());
-  return toc(h, BLAH2HIP_K_COV, st);
-}
-
-// blah2hip_amb_beam_samples_dev (w: the host's one set of weights) and blah2hip_amb_beam_samples_wdev (d_w: a set per CPI on the device)
-static int beam_samples_enqueue(blah2hip_amb_t h, int fmt, const void *const *d_y, uint32_t n_surv, uint32_t n_cpi, uint64_t cpi_stride,
-                                const float *w, const float *d_w, uint32_t n_beams, void *const *d_beam, uint64_t beam_stride,
-                                void *stream)
-{
-  size_t bytes = 0;
-  int rc;
-  if ((rc = sample_planes_check(h, fmt, d_y, n_surv, n_cpi, cpi_stride, &bytes))) return rc;
-  if (n_beams == 0 || n_beams > BLAH2HIP_MAX_BEAMS) return fail(BLAH2HIP_ERR_INVALID, "n_beams outside [1, BLAH2HIP_MAX_BEAMS]");
-  if ((!w && !d_w) || !d_beam) return fail(BLAH2HIP_ERR_INVALID, "NULL weights or output");
-  const uint32_t nS = h->dims.n_samples;
-  if (n_cpi > 1 && beam_stride < nS) return fail(BLAH2HIP_ERR_INVALID, "beam_stride < n_samples");
-  const size_t inBytes = ((size_t)(n_cpi - 1) * cpi_stride + nS) * bytes;
-  const size_t outBytes = ((size_t)(n_cpi - 1) * beam_stride + nS) * sizeof(cf);
-  for (uint32_t b = 0; b < n_beams; b++) {
-    if (!d_beam[b]) return fail(BLAH2HIP_ERR_INVALID, "NULL beam plane");
-    if ((uintptr_t)d_beam[b] & 7) return fail(BLAH2HIP_ERR_INVALID, "a beam plane is not 8-byte aligned");
-    for (uint32_t k = 0; k < n_surv; k++)
-      if (ranges_overlap(d_y[k], inBytes, d_beam[b], outBytes)) return fail(BLAH2HIP_ERR_INVALID, "beam samples: a beam plane overlaps an input plane");
-    for (uint32_t o = 0; o < b; o++)
-      if (ranges_overlap(d_beam[o], outBytes, d_beam[b], outBytes)) return fail(BLAH2HIP_ERR_INVALID, "beam samples: two beam planes overlap");
-  }
-  HIPCHK(hipSetDevice(h->device));
-  hipStream_t st = (hipStream_t)stream;
-
-  BeamSampArgs a;
-  memset(a.y, 0, sizeof(a.y));
-  memset(a.out, 0, sizeof(a.out));
-  for (uint32_t k = 0; k < n_surv; k++) a.y[k] = d_y[k];
-  for (uint32_t b = 0; b < n_beams; b++) a.out[b] = (cf *)d_beam[b];
-  a.cpiStride = cpi_stride;
-  a.beamStride = beam_stride;
-  a.nSamples = nS;
-  a.nBeams = n_beams;
-  memset(a.w, 0, sizeof(a.w));
-  if (!d_w)
-    for (uint32_t b = 0; b < n_beams; b++)
-      for (uint32_t k = 0; k < n_surv; k++) a.w[b][k] = cmake(w[2 * (b * n_surv + k)], w[2 * (b * n_surv + k) + 1]);
-  // pairs of samples where every input plane's and every beam plane's copy of a CPI starts at the same parity of sample
-  const bool wide = sample_planes_agree(d_y, n_surv, bytes, cpi_stride, n_cpi, 0, 2, (const void *const *)d_beam, n_beams, sizeof(cf), beam_stride);
-  // workgroups per CPI: eight a CU over the launch, each with at least one pass of 256 accesses
-  const size_t units = wide ? ((size_t)nS + 1) / 2 : nS;
-  const uint32_t G = (uint32_t)std::max<size_t>(1, std::min<size_t>((units + 255) / 256, (8u * (size_t)h->numCU + n_cpi - 1) / n_cpi));
-  if ((rc = tic(h, BLAH2HIP_K_BEAM, st))) return rc;
-  const dim3 grid(G, n_cpi);
-  const cf *wd = (const cf *)d_w;
-  if (fmt == BLAH2HIP_FMT_I8) {
-    if (d_w) { if (wide) launch_beam_samples<SampI8, 2, true>(n_surv, grid, st, a, wd); else launch_beam_samples<SampI8, 1, true>(n_surv, grid, st, a, wd); }
-    else { if (wide) launch_beam_samples<SampI8, 2, false>(n_surv, grid, st, a, wd); else launch_beam_samples<SampI8, 1, false>(n_surv, grid, st, a, wd); }
-  } else {
-    if (d_w) { if (wide) launch_beam_samples<SampC32, 2, true>(n_surv, grid, st, a, wd); else launch_beam_samples<SampC32, 1, true>(n_surv, grid, st, a, wd); }
-    else { if (wide) launch_beam_samples<SampC32, 2, false>(n_surv, grid, st, a, wd); else launch_beam_samples<SampC32, 1, false>(n_surv, grid, st, a, wd); }
-  }
-  HIPCHK(hipGetLastError());
-  return toc(h, BLAH2HIP_K_BEAM, st);
-}
-
-int blah2hip_amb_beam_samples_dev(blah2hip_amb_t h, int fmt, const void *const *d_y, uint32_t n_surv, uint32_t n_cpi, uint64_t cpi_stride,
-                                  const float *w, uint32_t n_beams, void *const *d_beam, uint64_t beam_stride, void *stream)
-{
-  return beam_samples_enqueue(h, fmt, d_y, n_surv, n_cpi, cpi_stride, w, nullptr, n_beams, d_beam, beam_stride, stream);
-}
-
-int blah2hip_amb_beam_samples_wdev(blah2hip_amb_t h, int fmt, const void *const *d_y, uint32_t n_surv, uint32_t n_cpi, uint64_t cpi_stride,
-                                   const float *d_w, uint32_t n_beams, void *const *d_beam, uint64_t beam_stride, void *stream)
-{
-  return beam_samples_enqueue(h, fmt, d_y, n_surv, n_cpi, cpi_stride, nullptr, d_w, n_beams, d_beam, beam_stride, stream);
-}
-
-int blah2hip_amb_snapshot_dev(blah2hip_amb_t h, const void *d_map, uint32_t n_surv, uint32_t n_cpi,
-                              const blah2hip_det_t *d_dets, uint32_t cap, const uint32_t *d_count, uint32_t n_lists,
-                              float *d_snap, void *stream)
-{
-  if (!h || !d_dets || !d_count || !d_snap) return fail(BLAH2HIP_ERR_INVALID, "NULL argument");
-  if (n_surv == 0 || n_surv > BLAH2HIP_MAX_SURV) return fail(BLAH2HIP_ERR_INVALID, "n_surv outside [1, BLAH2HIP_MAX_SURV]");
-  if (n_cpi == 0 || (uint64_t)n_surv * n_cpi > h->dims.max_batch) return fail(BLAH2HIP_ERR_INVALID, "n_cpi is 0 or n_surv * n_cpi above max_batch");
-  if (cap == 0) return fail(BLAH2HIP_ERR_INVALID, "cap is 0");
-  if (n_lists == 0 || n_lists % n_cpi != 0) return fail(BLAH2HIP_ERR_INVALID, "n_lists is 0 or not a multiple of n_cpi");
-  HIPCHK(hipSetDevice(h->device));
-  SnapArgs a;
-  a.map = d_map ? (const cf *)d_map : h->d_map;
-  a.dets = d_dets;
-  a.count = d_count;
-  a.snap = (cf *)d_snap;
-  a.nSurv = n_surv; a.nCpi = n_cpi; a.cap = cap; a.nLists = n_lists;
-  a.nD = (int32_t)h->dims.n_doppler_bins;
-  a.nDelay = (int32_t)h->dims.n_delay_bins;
-  const size_t blocks = ((size_t)n_lists * cap + 255) / 256;
-  hipLaunchKernelGGL(snapshot_kernel, dim3((uint32_t)std::min<size_t>(blocks, 8u * (size_t)h->numCU)), dim3(256), 0,
-                     (hipStream_t)stream, a);
-  HIPCHK(hipGetLastError());
-  return BLAH2HIP_OK;
-}
-
-int blah2hip_amb_bearing_dev(blah2hip_amb_t h, const void *d_map, uint32_t n_surv, uint32_t n_cpi,
-                             const blah2hip_det_t *d_dets, uint32_t cap, const uint32_t *d_count, uint32_t n_lists,
-                             const double *d_cov, double loading, const float *d_steer, uint32_t n_grid, uint32_t flags,
-                             blah2hip_bearing_t *d_out, void *stream)
-{
-  if (!h || !d_dets || !d_count || !d_steer || !d_out) return fail(BLAH2HIP_ERR_INVALID, "NULL argument");
-  if (n_surv < 2 || n_surv > BLAH2HIP_MAX_SURV) return fail(BLAH2HIP_ERR_INVALID, "n_surv outside [2, BLAH2HIP_MAX_SURV]");
-  if (n_cpi == 0 || (uint64_t)n_surv * n_cpi > h->dims.max_batch) return fail(BLAH2HIP_ERR_INVALID, "n_cpi is 0 or n_surv * n_cpi above max_batch");
-  if (cap == 0) return fail(BLAH2HIP_ERR_INVALID, "cap is 0");
-  if (n_lists == 0 || n_lists % n_cpi != 0 || n_lists > 65535)
-    return fail(BLAH2HIP_ERR_INVALID, "n_lists is 0, not a multiple of n_cpi or above 65535");
-  if (n_grid < 3 || n_grid > BLAH2HIP_MAX_BEARING_GRID) return fail(BLAH2HIP_ERR_INVALID, "n_grid outside [3, BLAH2HIP_MAX_BEARING_GRID]");
-  if (flags & ~BLAH2HIP_BEARING_WRAP) return fail(BLAH2HIP_ERR_INVALID, "bearing: unknown flag bits");
-  if (d_cov && (!(loading >= 0.0) || !std::isfinite(loading))) return fail(BLAH2HIP_ERR_INVALID, "bearing: loading is negative or not finite");
-  HIPCHK(hipSetDevice(h->device));
-  hipStream_t st = (hipStream_t)stream;
-  BearingArgs a;
-  a.map = d_map ? (const cf *)d_map : h->d_map;
-  a.dets = d_dets;
-  a.count = d_count;
-  a.cov = d_cov;
-  a.steer = (const cf *)d_steer;
-  a.out = d_out;
-  a.loading = d_cov ? loading : 0.0;
-  a.nCpi = n_cpi; a.cap = cap; a.nGrid = n_grid;
-  a.wrap = flags & BLAH2HIP_BEARING_WRAP;
-  a.nD = (int32_t)h->dims.n_doppler_bins;
-  a.nDelay = (int32_t)h->dims.n_delay_bins;
-  // workgroups per list: the count lives on the device, so one per BEARING_CHUNK slots of cap (those behind the count return
-  // before they build the table), and no more than eight a CU over the launch: a workgroup strides over the chunks
-  const uint32_t X = std::max(1u, std::min(cap / BEARING_CHUNK + (cap % BEARING_CHUNK ? 1u : 0u), 8u * (uint32_t)h->numCU / n_lists));
-  int rc;
-  if ((rc = tic(h, BLAH2HIP_K_BEARING, st))) return rc;
-  launch_bearing(n_surv, dim3(X, n_lists), st, a);
-  HIPCHK(hipGetLastError());
-  h->bearingGridLast = (int)X;
-  return toc(h, BLAH2HIP_K_BEARING, st);
-}
-
 int blah2hip_amb_process_c32(blah2hip_amb_t h, const float *x, const float *y, uint32_t n,
                              float *map_out, double *metrics)
 {
@@ -2429,322 +1787,6 @@ int blah2hip_amb_process_i8(blah2hip_amb_t h, const int8_t *x, const int8_t *y, 
   return host_tail(h, map_out, metrics);
 }
 
-// ------------------------------------------------------------------- CFAR --
-int blah2hip_cfar1d_dev(blah2hip_amb_t h, const void *d_map, const double *d_metrics,
-                        uint32_t n_cpi, double pfa, int32_t n_guard, int32_t n_train,
-                        int32_t min_delay, double min_doppler, blah2hip_hit_t *d_hits, uint32_t cap,
-                        uint32_t *d_count, void *stream)
-{
-  if (!h || !d_hits || !d_count) return fail(BLAH2HIP_ERR_INVALID, "NULL argument");
-  if (n_cpi == 0 || n_cpi > h->dims.max_batch) return fail(BLAH2HIP_ERR_INVALID, "n_cpi outside [1, max_batch]");
-  // CfarDetector1D's ctor parameters are int8_t (CfarDetector1D.h:46)
-  if (n_guard < 0 || n_guard > 127 || n_train < 0 || n_train > 127 || min_delay < -128 || min_delay > 127)
-    return fail(BLAH2HIP_ERR_INVALID, "nGuard/nTrain/minDelay outside int8 range");
-  HIPCHK(hipSetDevice(h->device));
-  hipStream_t st = (hipStream_t)stream;
-  const double *d_alpha = nullptr;
-  int rc;
-  if ((rc = alpha_table(h, pfa, (size_t)(2 * n_train), &d_alpha, st))) return rc;
-  HIPCHK(hipMemsetAsync(d_count, 0, n_cpi * sizeof(uint32_t), st));
-  CfarArgs a;
-  a.map = d_map ? (const cf *)d_map : h->d_map;
-  a.metrics = d_metrics ? d_metrics : h->d_metrics;
-  a.doppler = h->d_doppler;
-  a.alpha = d_alpha;
-  a.hits = d_hits;
-  a.count = d_count;
-  a.nD = (int32_t)h->dims.n_doppler_bins;
-  a.nDelay = (int32_t)h->dims.n_delay_bins;
-  a.delayMin = h->delayMin;
-  a.delayAxis = nullptr; // the engine's own axis: delayMin + j
-  a.nGuard = n_guard; a.nTrain = n_train; a.minDelay = min_delay;
-  a.minDoppler = min_doppler;
-  a.cap = cap;
-  if ((rc = tic(h, BLAH2HIP_K_CFAR, st))) return rc;
-  {
-    // the row as fp64 |z|^2 in LDS while it fits (150 KB: 19 200 delay bins), straight from L2 beyond
-    const size_t rowBytes = (size_t)a.nDelay * sizeof(double);
-    if (rowBytes <= 150 * 1024) {
-      if (rowBytes > 48 * 1024) LDSCFG(cfar1d_kernel<true>, 150 * 1024); // the attribute is set once per (device, kernel): its largest use
-      hipLaunchKernelGGL(cfar1d_kernel<true>, dim3(a.nD, n_cpi), dim3(256), rowBytes, st, a);
-    } else {
-      hipLaunchKernelGGL(cfar1d_kernel<false>, dim3(a.nD, n_cpi), dim3(256), 0, st, a);
-    }
-  }
-  HIPCHK(hipGetLastError());
-  if ((rc = toc(h, BLAH2HIP_K_CFAR, st))) return rc;
-  return BLAH2HIP_OK;
-}
-
-int blah2hip_cfar1d_process(blah2hip_amb_t h, uint32_t cpi, double pfa, int32_t n_guard,
-                            int32_t n_train, int32_t min_delay, double min_doppler, double *delay,
-                            double *doppler, double *snr, uint32_t cap, uint32_t *count)
-{
-  if (!h || !count) return fail(BLAH2HIP_ERR_INVALID, "NULL argument");
-  if (cpi >= h->dims.max_batch) return fail(BLAH2HIP_ERR_INVALID, "cpi index out of range");
-  HIPCHK(hipSetDevice(h->device));
-  const size_t cells = (size_t)h->dims.n_doppler_bins * h->dims.n_delay_bins;
-  // worst case every cell fires; size the device list for that once
-  if (h->hitCap < cells) {
-    if (h->d_hits) HIPCHK(hipFree(h->d_hits));
-    h->d_hits = nullptr;
-    HIPCHK(hipMalloc(&h->d_hits, cells * sizeof(blah2hip_hit_t)));
-    h->hitCap = (uint32_t)cells;
-  }
-  // run on a one-CPI view of the internal buffers
-  const cf *m = h->d_map + cells * cpi;
-  const double *met = h->d_metrics + 2 * cpi;
-  int rc = blah2hip_cfar1d_dev(h, m, met, 1, pfa, n_guard, n_train, min_delay, min_doppler, h->d_hits,
-                               h->hitCap, h->d_count, h->stream);
-  if (rc) return rc;
-  uint32_t n = 0;
-  HIPCHK(hipMemcpyAsync(&n, h->d_count, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  n = std::min(n, h->hitCap);
-  std::vector<blah2hip_hit_t> hits(n);
-  if (n) HIPCHK(hipMemcpy(hits.data(), h->d_hits, n * sizeof(blah2hip_hit_t), hipMemcpyDeviceToHost));
-  // the reference emits row by row, then by delay (CfarDetector1D.cpp:36-92)
-  std::sort(hits.begin(), hits.end(), [](const blah2hip_hit_t &a, const blah2hip_hit_t &b) {
-    return a.row != b.row ? a.row < b.row : a.col < b.col;
-  });
-  *count = n;
-  if (n > cap) return fail(BLAH2HIP_ERR_CAPACITY, "detection capacity too small");
-  for (uint32_t i = 0; i < n; i++) {
-    if (delay) delay[i] = (double)(hits[i].col + h->delayAxis[0]); // :88  j + x->delay[0]
-    if (doppler) doppler[i] = h->dopplerAxis[hits[i].row];         // :89
-    if (snr) snr[i] = hits[i].snr;                                 // :90
-  }
-  return BLAH2HIP_OK;
-}
-
-// CfarDetector1D::process on a map that lives on the HOST (any Map<complex<double>>, not only one
-// the engine produced): uploads it, runs cfar1d_kernel, frees.  noise_power is Map::noisePower.
-int blah2hip_cfar1d_map(const float *map, uint32_t n_doppler, uint32_t n_delay, const int32_t *delay_axis,
-                        const double *doppler_axis, double noise_power, double pfa, int32_t n_guard,
-                        int32_t n_train, int32_t min_delay, double min_doppler, int device, double *delay,
-                        double *doppler, double *snr, uint32_t cap, uint32_t *count)
-{
-  if (!map || !delay_axis || !doppler_axis || !count) return fail(BLAH2HIP_ERR_INVALID, "NULL argument");
-  if (n_doppler == 0 || n_delay == 0) return fail(BLAH2HIP_ERR_INVALID, "empty map");
-  if (n_guard < 0 || n_guard > 127 || n_train < 0 || n_train > 127 || min_delay < -128 || min_delay > 127)
-    return fail(BLAH2HIP_ERR_INVALID, "nGuard/nTrain/minDelay outside int8 range");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(BLAH2HIP_ERR_NO_DEVICE, "no HIP device visible (the HIP path is the only path)");
-  if (device < 0 || device >= ndev) return fail(BLAH2HIP_ERR_INVALID, "device index out of range");
-  HIPCHK(hipSetDevice(device));
-  const size_t cells = (size_t)n_doppler * n_delay;
-  std::vector<double> alpha(2 * n_train + 1);
-  alpha[0] = std::nan("");
-  for (int n = 1; n <= 2 * n_train; n++) alpha[n] = n * (pow(pfa, -1.0 / n) - 1);
-  const double met[2] = {noise_power, 0.0};
-  char *pool = nullptr; // one allocation: map | hits | doppler | alpha | metrics | delay axis | count
-  const size_t oMap = 0, oHits = oMap + cells * sizeof(cf), oDop = oHits + cells * sizeof(blah2hip_hit_t),
-               oAlpha = oDop + n_doppler * sizeof(double), oMet = oAlpha + alpha.size() * sizeof(double),
-               oAxis = oMet + 2 * sizeof(double), oCnt = oAxis + n_delay * sizeof(int32_t), total = oCnt + sizeof(uint32_t);
-  HIPCHK(hipMalloc(&pool, total));
-  std::vector<blah2hip_hit_t> hits;
-  uint32_t n = 0;
-  auto run = [&]() -> int {
-    HIPCHK(hipMemcpy(pool + oMap, map, cells * sizeof(cf), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(pool + oDop, doppler_axis, n_doppler * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(pool + oAlpha, alpha.data(), alpha.size() * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(pool + oMet, met, sizeof met, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(pool + oAxis, delay_axis, n_delay * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(pool + oCnt, 0, sizeof(uint32_t)));
-    CfarArgs a;
-    a.map = (const cf *)(pool + oMap);
-    a.metrics = (const double *)(pool + oMet);
-    a.doppler = (const double *)(pool + oDop);
-    a.alpha = (const double *)(pool + oAlpha);
-    a.hits = (blah2hip_hit_t *)(pool + oHits);
-    a.count = (uint32_t *)(pool + oCnt);
-    a.nD = (int32_t)n_doppler; a.nDelay = (int32_t)n_delay; a.delayMin = delay_axis[0];
-    a.delayAxis = (const int32_t *)(pool + oAxis); // x->delay[j] of a caller-built map need not be delay[0] + j (CfarDetector1D.cpp:53)
-    a.nGuard = n_guard; a.nTrain = n_train; a.minDelay = min_delay; a.minDoppler = min_doppler;
-    a.cap = (uint32_t)cells;
-    const size_t rowBytes = (size_t)a.nDelay * sizeof(double);
-    if (rowBytes <= 150 * 1024) {
-      if (rowBytes > 48 * 1024) HIPCHK(blah2hip_ensure_lds_((const void *)cfar1d_kernel<true>, 150 * 1024));
-      hipLaunchKernelGGL(cfar1d_kernel<true>, dim3(a.nD, 1), dim3(256), rowBytes, 0, a);
-    } else {
-      hipLaunchKernelGGL(cfar1d_kernel<false>, dim3(a.nD, 1), dim3(256), 0, 0, a);
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(&n, pool + oCnt, sizeof(uint32_t), hipMemcpyDeviceToHost)); // synchronises with the null stream
-    hits.resize(n);
-    if (n) HIPCHK(hipMemcpy(hits.data(), pool + oHits, n * sizeof(blah2hip_hit_t), hipMemcpyDeviceToHost));
-    return BLAH2HIP_OK;
-  };
-  const int rc = run();
-  (void)hipFree(pool);
-  if (rc) return rc;
-  std::sort(hits.begin(), hits.end(), [](const blah2hip_hit_t &a, const blah2hip_hit_t &b) {
-    return a.row != b.row ? a.row < b.row : a.col < b.col;
-  });
-  *count = n;
-  if (n > cap) return fail(BLAH2HIP_ERR_CAPACITY, "detection capacity too small");
-  for (uint32_t i = 0; i < n; i++) {
-    if (delay) delay[i] = (double)(hits[i].col + delay_axis[0]); // CfarDetector1D.cpp:88
-    if (doppler) doppler[i] = doppler_axis[hits[i].row];         // :89
-    if (snr) snr[i] = hits[i].snr;                               // :90
-  }
-  return BLAH2HIP_OK;
-}
-
-// ---------------------------------------------------------------- 2-D CFAR --
-int blah2hip_cfar2d_dev(blah2hip_amb_t h, const void *d_map, const double *d_metrics, uint32_t n_cpi,
-                        double pfa, int32_t ngd, int32_t ntd, int32_t ngf, int32_t ntf, int32_t min_delay,
-                        double min_doppler, blah2hip_hit_t *d_hits, uint32_t cap, uint32_t *d_count,
-                        void *stream)
-{
-  if (!h || !d_hits || !d_count) return fail(BLAH2HIP_ERR_INVALID, "NULL argument");
-  if (n_cpi == 0 || n_cpi > h->dims.max_batch) return fail(BLAH2HIP_ERR_INVALID, "n_cpi outside [1, max_batch]");
-  for (int32_t v : {ngd, ntd, ngf, ntf})
-    if (v < 0 || v > 127) return fail(BLAH2HIP_ERR_INVALID, "guard/train sizes outside [0, 127]");
-  if (min_delay < -128 || min_delay > 127) return fail(BLAH2HIP_ERR_INVALID, "minDelay outside int8 range");
-  HIPCHK(hipSetDevice(h->device));
-  hipStream_t st = (hipStream_t)stream;
-  const int nD = (int)h->dims.n_doppler_bins, nC = (int)h->dims.n_delay_bins;
-  int rc;
-  if (h->cfar2dForce == BLAH2HIP_CFAR2D_TILE && !cfar2d_use_tile(h, ngd, ntd, ngf, ntf))
-    return fail(BLAH2HIP_ERR_UNSUPPORTED, "2-D window beyond the tile kernel's halo (nGf + nTf <= 24, nGd + nTd <= 40)");
-  if (h->cfar2dForce == BLAH2HIP_CFAR2D_STREAM && !cfar2d_stream_shape(ngd, ntd, ngf, ntf))
-    return fail(BLAH2HIP_ERR_UNSUPPORTED, "the stream kernel is not instantiated for this 2-D window (C2S_SHAPES in cfar_kernels.hpp)");
-  {
-    int lo, hi; // the handle's Doppler axis is monotonic (Ambiguity.cpp:60-66), so this cannot fail today; a forced kernel never runs another one
-    if (h->cfar2dForce == BLAH2HIP_CFAR2D_STREAM && !cfar2d_dead_rows(h, min_doppler, &lo, &hi))
-      return fail(BLAH2HIP_ERR_UNSUPPORTED, "the stream kernel needs the rows below minDoppler to be one interval of the Doppler axis");
-  }
-  if (!cfar2d_use_stream(h, ngd, ntd, ngf, ntf, min_doppler) && !cfar2d_use_tile(h, ngd, ntd, ngf, ntf) && (rc = ensure_sat(h))) return rc; // no-op once allocated
-  const double *d_alpha = nullptr;
-  if ((rc = alpha_table(h, pfa, (size_t)(2 * (ngd + ntd) + 1) * (2 * (ngf + ntf) + 1), &d_alpha, st))) return rc;
-  HIPCHK(hipMemsetAsync(d_count, 0, n_cpi * sizeof(uint32_t), st));
-  Cfar2dArgs a;
-  a.map = d_map ? (const cf *)d_map : h->d_map;
-  a.metrics = d_metrics ? d_metrics : h->d_metrics;
-  a.doppler = h->d_doppler;
-  a.alpha = d_alpha;
-  a.sat = h->d_sat;
-  a.hits = d_hits;
-  a.count = d_count;
-  a.nD = nD; a.nDelay = nC; a.delayMin = h->delayMin;
-  a.ngD = ngd; a.ntD = ntd; a.ngF = ngf; a.ntF = ntf; a.minDelay = min_delay;
-  a.minDoppler = min_doppler;
-  a.cap = cap;
-  if (cfar2d_use_stream(h, ngd, ntd, ngf, ntf, min_doppler)) {
-    if ((rc = tic(h, BLAH2HIP_K_CFAR, st))) return rc;
-    cfar2d_stream_launch(h, a, n_cpi, st);
-    HIPCHK(hipGetLastError());
-    if ((rc = toc(h, BLAH2HIP_K_CFAR, st))) return rc;
-    return BLAH2HIP_OK;
-  }
-  if (cfar2d_use_tile(h, ngd, ntd, ngf, ntf)) {
-    Cfar2dTileArgs ta;
-    ta.d = a;
-    ta.nCpi = (int32_t)n_cpi;
-    ta.rowsOut = C2T_ROWS - 2 * (ngf + ntf);
-    ta.tilesX = (nC + C2T_COLS - 1) / C2T_COLS;
-    ta.tilesY = (nD + ta.rowsOut - 1) / ta.rowsOut;
-    const int hC = ngd + ntd;
-    // the whole threshold table in LDS when it fits beside the tile (the default 17 x 9 window: 154 entries)
-    const int64_t tableN = (int64_t)(2 * (ngd + ntd) + 1) * (2 * (ngf + ntf) + 1) + 1;
-    ta.alphaLds = (tableN <= 2048 && c2t_lds_bytes(hC, (int)tableN) <= 160 * 1024) ? (int32_t)tableN : 0;
-    const size_t lds = c2t_lds_bytes(hC, ta.alphaLds);
-    const int64_t nAll = (int64_t)ta.tilesX * ta.tilesY * n_cpi;
-    const int64_t wgCap = h->cfar2dGridForce > 0 ? h->cfar2dGridForce : h->numCU; // BLAH2HIP_OPT_CFAR2D_GRID
-    const int grid = (int)std::max<int64_t>(8, (std::min<int64_t>(nAll, wgCap) + 7) & ~7); // one persistent workgroup per CU (LDS)
-    h->cfar2dGridLast = grid;
-    h->cfar2dSegRowsLast = 0;
-    if ((rc = tic(h, BLAH2HIP_K_CFAR, st))) return rc;
-    auto launch = [&](auto kern) -> int {
-      LDSCFG(kern, lds);
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * C2T_WAVES), lds, st, ta);
-      return BLAH2HIP_OK;
-    };
-    const bool two = C2T_COLS + 2 * hC <= 128;
-    if (two) rc = ta.alphaLds ? launch(cfar2d_tile_kernel<2, true>) : launch(cfar2d_tile_kernel<2, false>);
-    else rc = ta.alphaLds ? launch(cfar2d_tile_kernel<3, true>) : launch(cfar2d_tile_kernel<3, false>);
-    if (rc) return rc;
-    HIPCHK(hipGetLastError());
-    if ((rc = toc(h, BLAH2HIP_K_CFAR, st))) return rc;
-    return BLAH2HIP_OK;
-  }
-  h->cfar2dGridLast = h->cfar2dSegRowsLast = 0;
-  if ((rc = tic(h, BLAH2HIP_K_SAT_ROWS, st))) return rc;
-  hipLaunchKernelGGL(sat_rows_kernel, dim3(nD, n_cpi), dim3(256), 0, st, a);
-  if ((rc = toc(h, BLAH2HIP_K_SAT_ROWS, st))) return rc;
-  if ((rc = tic(h, BLAH2HIP_K_SAT_COLS, st))) return rc;
-  hipLaunchKernelGGL(sat_cols_kernel, dim3((nC + 63) / 64, n_cpi), dim3(64), 0, st, a);
-  if ((rc = toc(h, BLAH2HIP_K_SAT_COLS, st))) return rc;
-  if ((rc = tic(h, BLAH2HIP_K_CFAR, st))) return rc;
-  hipLaunchKernelGGL(cfar2d_kernel, dim3((nC + 255) / 256, nD, n_cpi), dim3(256), 0, st, a);
-  HIPCHK(hipGetLastError());
-  if ((rc = toc(h, BLAH2HIP_K_CFAR, st))) return rc;
-  return BLAH2HIP_OK;
-}
-
-int blah2hip_cfar1d_prepare(blah2hip_amb_t h, double pfa, int32_t n_train)
-{
-  if (!h) return fail(BLAH2HIP_ERR_INVALID, "NULL handle");
-  if (n_train < 0 || n_train > 127) return fail(BLAH2HIP_ERR_INVALID, "nTrain outside int8 range");
-  HIPCHK(hipSetDevice(h->device));
-  const double *d = nullptr;
-  return alpha_table(h, pfa, (size_t)(2 * n_train), &d, nullptr, true);
-}
-
-int blah2hip_cfar2d_prepare(blah2hip_amb_t h, double pfa, int32_t ngd, int32_t ntd, int32_t ngf, int32_t ntf)
-{
-  if (!h) return fail(BLAH2HIP_ERR_INVALID, "NULL handle");
-  for (int32_t v : {ngd, ntd, ngf, ntf})
-    if (v < 0 || v > 127) return fail(BLAH2HIP_ERR_INVALID, "guard/train sizes outside [0, 127]");
-  HIPCHK(hipSetDevice(h->device));
-  int rc;
-  if (h->cfar2dForce == BLAH2HIP_CFAR2D_TILE && !cfar2d_use_tile(h, ngd, ntd, ngf, ntf))
-    return fail(BLAH2HIP_ERR_UNSUPPORTED, "2-D window beyond the tile kernel's halo (nGf + nTf <= 24, nGd + nTd <= 40)");
-  if (h->cfar2dForce == BLAH2HIP_CFAR2D_STREAM && !cfar2d_stream_shape(ngd, ntd, ngf, ntf))
-    return fail(BLAH2HIP_ERR_UNSUPPORTED, "the stream kernel is not instantiated for this 2-D window (C2S_SHAPES in cfar_kernels.hpp)");
-  if (!cfar2d_use_stream(h, ngd, ntd, ngf, ntf, 0.0) && !cfar2d_use_tile(h, ngd, ntd, ngf, ntf) && (rc = ensure_sat(h))) return rc;
-  const double *d = nullptr;
-  return alpha_table(h, pfa, (size_t)(2 * (ngd + ntd) + 1) * (2 * (ngf + ntf) + 1), &d, nullptr, true);
-}
-
-int blah2hip_cfar2d_process(blah2hip_amb_t h, uint32_t cpi, double pfa, int32_t ngd, int32_t ntd,
-                            int32_t ngf, int32_t ntf, int32_t min_delay, double min_doppler, double *delay,
-                            double *doppler, double *snr, uint32_t cap, uint32_t *count)
-{
-  if (!h || !count) return fail(BLAH2HIP_ERR_INVALID, "NULL argument");
-  if (cpi >= h->dims.max_batch) return fail(BLAH2HIP_ERR_INVALID, "cpi index out of range");
-  HIPCHK(hipSetDevice(h->device));
-  const size_t cells = (size_t)h->dims.n_doppler_bins * h->dims.n_delay_bins;
-  if (h->hitCap < cells) {
-    if (h->d_hits) HIPCHK(hipFree(h->d_hits));
-    h->d_hits = nullptr;
-    HIPCHK(hipMalloc(&h->d_hits, cells * sizeof(blah2hip_hit_t)));
-    h->hitCap = (uint32_t)cells;
-  }
-  int rc = blah2hip_cfar2d_dev(h, h->d_map + cells * cpi, h->d_metrics + 2 * cpi, 1, pfa, ngd, ntd, ngf, ntf,
-                               min_delay, min_doppler, h->d_hits, h->hitCap, h->d_count, h->stream);
-  if (rc) return rc;
-  uint32_t n = 0;
-  HIPCHK(hipMemcpyAsync(&n, h->d_count, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  n = std::min(n, h->hitCap);
-  std::vector<blah2hip_hit_t> hits(n);
-  if (n) HIPCHK(hipMemcpy(hits.data(), h->d_hits, n * sizeof(blah2hip_hit_t), hipMemcpyDeviceToHost));
-  std::sort(hits.begin(), hits.end(), [](const blah2hip_hit_t &a, const blah2hip_hit_t &b) {
-    return a.row != b.row ? a.row < b.row : a.col < b.col;
-  });
-  *count = n;
-  if (n > cap) return fail(BLAH2HIP_ERR_CAPACITY, "detection capacity too small");
-  for (uint32_t i = 0; i < n; i++) {
-    if (delay) delay[i] = (double)(hits[i].col + h->delayAxis[0]);
-    if (doppler) doppler[i] = h->dopplerAxis[hits[i].row];
-    if (snr) snr[i] = hits[i].snr;
-  }
-  return BLAH2HIP_OK;
-}
-
 // ----------------------------------------------------------------- timing --
 int blah2hip_amb_set_timing(blah2hip_amb_t h, int enable)
 {
@@ -2762,294 +1804,12 @@ int blah2hip_amb_get_timing(blah2hip_amb_t h, double *ms_total, uint32_t *launch
   return BLAH2HIP_OK;
 }
 
-// ------------------------------------------------- centroid / interpolate --
-// Host arithmetic on a handful of detections (O(n^2) over tens of items).
-int blah2hip_centroid(const double *delay, const double *doppler, const double *snr, uint32_t count,
-                      uint16_t n_delay, uint16_t n_doppler, double resolution_doppler,
-                      double *delay_out, double *doppler_out, double *snr_out, uint32_t *count_out)
-{
-  if (!count_out || (count && (!delay || !doppler || !snr || !delay_out || !doppler_out || !snr_out)))
-    return fail(BLAH2HIP_ERR_INVALID, "NULL argument");
-  uint32_t kept = 0;
-  for (uint32_t i = 0; i < count; i++) {
-    // Centroid.cpp:36-39: uint16_t limits -> (int)delay - n_delay wraps when negative
-    const uint16_t lo = (uint16_t)((int)delay[i] - (int)n_delay);
-    const uint16_t hi = (uint16_t)((int)delay[i] + (int)n_delay);
-    const double flo = doppler[i] - (n_doppler * resolution_doppler);
-    const double fhi = doppler[i] + (n_doppler * resolution_doppler);
-    bool keep = true;
-    for (uint32_t j = 0; j < count && keep; j++) {
-      if (j == i) continue;
-      if (delay[j] > lo && delay[j] < hi && doppler[j] > flo && doppler[j] < fhi && snr[i] < snr[j]) keep = false;
-    }
-    if (keep) {
-      delay_out[kept] = delay[i];
-      doppler_out[kept] = doppler[i];
-      snr_out[kept] = snr[i];
-      kept++;
-    }
-  }
-  *count_out = kept;
-  return BLAH2HIP_OK;
-}
-
-int blah2hip_interpolate(const double *delay, const double *doppler, const double *snr, uint32_t count,
-                         const float *map, uint32_t n_doppler, uint32_t n_delay, const int32_t *delay_axis,
-                         const double *doppler_axis, double noise_power, int do_delay, int do_doppler,
-                         double *delay_out, double *doppler_out, double *snr_out, uint32_t *count_out)
-{
-  if (!count_out || !map || !delay_axis || !doppler_axis) return fail(BLAH2HIP_ERR_INVALID, "NULL argument");
-  if (count && (!delay || !doppler || !snr || !delay_out || !doppler_out || !snr_out))
-    return fail(BLAH2HIP_ERR_INVALID, "NULL argument");
-  // 10*log10|z| - noisePower of one map cell (Interpolate.cpp:50-52)
-  auto cell = [&](int64_t row, int64_t col) -> double {
-    if (row < 0 || row >= (int64_t)n_doppler || col < 0 || col >= (int64_t)n_delay)
-      return std::nan(""); // the reference would index out of bounds here
-    const float *z = map + 2 * ((size_t)row * n_delay + (size_t)col);
-    return 10.0 * std::log10(std::hypot((double)z[0], (double)z[1])) - noise_power;
-  };
-  // Map::doppler_hz_to_bin: exact match, 0 on a miss (Map.cpp:102-113)
-  auto row_of = [&](double hz) -> int64_t {
-    for (uint32_t r = 0; r < n_doppler; r++)
-      if (doppler_axis[r] == hz) return r;
-    return 0;
-  };
-  uint32_t kept = 0;
-  for (uint32_t i = 0; i < count; i++) {
-    double intDelay = delay[i], intDoppler = doppler[i], intSnrDelay = snr[i];
-    const double intSnrDoppler = snr[i]; // never updated in the reference (:80 writes intSnrDelay)
-    const int64_t row = row_of(doppler[i]);
-    const int64_t col = (int64_t)(delay[i] - delay_axis[0]);
-    if (do_delay) {
-      if (delay[i] == delay_axis[0] || delay[i] == delay_axis[n_delay - 1]) continue; // :46-49
-      const double s0 = cell(row, col - 1), s1 = cell(row, col), s2 = cell(row, col + 1);
-      if (s1 < s0 || s1 < s2) continue; // :54-58 dropped (peak lower than a neighbour)
-      double off = (s0 - s2) / (2 * (s0 - (2 * s1) + s2));
-      intSnrDelay = s1 - (((s0 - s2) * off) / 4);
-      intDelay = delay[i] + off;
-    }
-    if (do_doppler) {
-      if (doppler[i] == doppler_axis[0] || doppler[i] == doppler_axis[n_doppler - 1]) continue; // :67-70
-      const double s0 = cell(row - 1, col), s1 = cell(row, col), s2 = cell(row + 1, col);
-      if (s1 < s0 || s1 < s2) continue;
-      double off = (s0 - s2) / (2 * (s0 - (2 * s1) + s2));
-      intSnrDelay = s1 - (((s0 - s2) * off) / 4); // sic, :80
-      intDoppler = doppler[i] + ((doppler_axis[1] - doppler_axis[0]) * off);
-    }
-    delay_out[kept] = intDelay;
-    doppler_out[kept] = intDoppler;
-    snr_out[kept] = std::max(std::max(intSnrDelay, intSnrDoppler), snr[i]); // :88
-    kept++;
-  }
-  *count_out = kept;
-  return BLAH2HIP_OK;
-}
-
-// ------------------------------------------- centroid / interpolate, device --
-// Centroid::process and Interpolate::process on device-resident hit lists and maps (blah2.cpp:285-287 without the host):
-// one launch of detect_finish_kernel, nothing in front of it.
-int blah2hip_detect_dev(blah2hip_amb_t h, const void *d_map, const double *d_metrics, uint32_t n_cpi,
-                        const blah2hip_hit_t *d_hits, uint32_t cap, const uint32_t *d_count,
-                        uint16_t n_centroid_delay, uint16_t n_centroid_doppler, double resolution_doppler,
-                        int do_centroid, int do_delay, int do_doppler,
-                        blah2hip_det_t *d_out, uint32_t cap_out, uint32_t *d_count_out, void *stream)
-{
-  if (!h || !d_hits || !d_count || !d_out || !d_count_out) return fail(BLAH2HIP_ERR_INVALID, "NULL argument");
-  if (n_cpi == 0 || n_cpi > h->dims.max_batch) return fail(BLAH2HIP_ERR_INVALID, "n_cpi outside [1, max_batch]");
-  if (cap == 0) return fail(BLAH2HIP_ERR_INVALID, "cap is 0");
-  HIPCHK(hipSetDevice(h->device));
-  hipStream_t st = (hipStream_t)stream;
-  DetectArgs a;
-  a.map = d_map ? (const cf *)d_map : h->d_map;
-  a.metrics = d_metrics ? d_metrics : h->d_metrics;
-  a.doppler = h->d_doppler;
-  a.hits = d_hits;
-  a.count = d_count;
-  a.out = d_out;
-  a.countOut = d_count_out;
-  a.appended = h->d_detWords;
-  a.tickets = h->d_detWords + h->dims.max_batch;
-  a.nD = (int32_t)h->dims.n_doppler_bins;
-  a.nDelay = (int32_t)h->dims.n_delay_bins;
-  a.delayMin = h->delayAxis[0];
-  a.nCentroidDelay = (int32_t)n_centroid_delay;
-  a.boxDoppler = n_centroid_doppler * resolution_doppler; // the expression of blah2hip_centroid (Centroid.cpp:38-39)
-  a.cap = cap;
-  a.capOut = cap_out;
-  a.doCentroid = do_centroid != 0; a.doDelay = do_delay != 0; a.doDoppler = do_doppler != 0;
-  // A list that fits one LDS tile: one workgroup per CPI, counter in LDS.  Longer lists: blocks of DET_BLOCK hits over G
-  // workgroups per CPI, enough of them to fill the device with a lone CPI at its cap and no more than eight a CPI once
-  // the batch alone fills it (a workgroup without a block of its CPI's list leaves after one load).
-  const uint32_t blocks = (cap + DET_BLOCK - 1) / DET_BLOCK;
-  const bool tiled = cap > (uint32_t)DET_TILE;
-  const uint32_t G = tiled ? std::min(blocks, std::max(8u, (uint32_t)(4 * h->numCU) / n_cpi)) : 1u;
-  if (tiled)
-    hipLaunchKernelGGL(detect_finish_kernel<true>, dim3(G, n_cpi), dim3(DET_BLOCK), 0, st, a);
-  else
-    hipLaunchKernelGGL(detect_finish_kernel<false>, dim3(1, n_cpi), dim3(DET_BLOCK), 0, st, a);
-  HIPCHK(hipGetLastError());
-  h->detGridLast = (int)G;
-  h->detTiledLast = tiled ? 1 : 0;
-  return BLAH2HIP_OK;
-}
-
-// ---------------------------------------------------------- device context --
-struct blah2hip_ctx_s {
-  int device = 0;
-  hipStream_t stream = nullptr;
-};
-
-int blah2hip_ctx_create(int device, blah2hip_ctx_t *out)
-{
-  if (!out) return fail(BLAH2HIP_ERR_INVALID, "out is NULL");
-  *out = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(BLAH2HIP_ERR_NO_DEVICE, "no HIP device visible (the HIP path is the only path)");
-  if (device < 0 || device >= ndev) return fail(BLAH2HIP_ERR_INVALID, "device index out of range");
-  HIPCHK(hipSetDevice(device));
-  auto *c = new blah2hip_ctx_s;
-  c->device = device;
-  hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-  if (e != hipSuccess) { delete c; return fail(BLAH2HIP_ERR_HIP, std::string("hipStreamCreate: ") + hipGetErrorString(e)); }
-  *out = c;
-  return BLAH2HIP_OK;
-}
-
-int blah2hip_ctx_destroy(blah2hip_ctx_t c)
-{
-  if (!c) return BLAH2HIP_OK;
-  (void)hipSetDevice(c->device);
-  if (c->stream) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); }
-  delete c;
-  return BLAH2HIP_OK;
-}
-
-void *blah2hip_ctx_stream(blah2hip_ctx_t c) { return c ? (void *)c->stream : nullptr; }
-
-int blah2hip_ctx_sync(blah2hip_ctx_t c)
-{
-  if (!c) return fail(BLAH2HIP_ERR_INVALID, "NULL context");
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return BLAH2HIP_OK;
-}
-
-int blah2hip_ctx_malloc(blah2hip_ctx_t c, size_t bytes, void **dptr)
-{
-  if (!c || !dptr) return fail(BLAH2HIP_ERR_INVALID, "NULL argument");
-  HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipMalloc(dptr, bytes));
-  return BLAH2HIP_OK;
-}
-
-int blah2hip_ctx_free(blah2hip_ctx_t c, void *dptr)
-{
-  if (!c) return fail(BLAH2HIP_ERR_INVALID, "NULL context");
-  if (dptr) { HIPCHK(hipSetDevice(c->device)); HIPCHK(hipFree(dptr)); }
-  return BLAH2HIP_OK;
-}
-
-int blah2hip_ctx_malloc_host(blah2hip_ctx_t c, size_t bytes, void **hptr)
-{
-  if (!c || !hptr) return fail(BLAH2HIP_ERR_INVALID, "NULL argument");
-  HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipHostMalloc(hptr, bytes, hipHostMallocDefault));
-  return BLAH2HIP_OK;
-}
-
-int blah2hip_ctx_free_host(blah2hip_ctx_t c, void *hptr)
-{
-  if (!c) return fail(BLAH2HIP_ERR_INVALID, "NULL context");
-  if (hptr) HIPCHK(hipHostFree(hptr));
-  return BLAH2HIP_OK;
-}
-
-int blah2hip_ctx_h2d(blah2hip_ctx_t c, void *dptr, const void *hptr, size_t bytes)
-{
-  if (!c || !dptr || !hptr) return fail(BLAH2HIP_ERR_INVALID, "NULL argument");
-  HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipMemcpyAsync(dptr, hptr, bytes, hipMemcpyHostToDevice, c->stream));
-  return BLAH2HIP_OK;
-}
-
-int blah2hip_ctx_d2d(blah2hip_ctx_t c, void *dst, const void *src, size_t bytes)
-{
-  if (!c || !dst || !src) return fail(BLAH2HIP_ERR_INVALID, "NULL argument");
-  HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, c->stream));
-  return BLAH2HIP_OK;
-}
-
-int blah2hip_ctx_d2h(blah2hip_ctx_t c, void *hptr, const void *dptr, size_t bytes)
-{
-  if (!c || !dptr || !hptr) return fail(BLAH2HIP_ERR_INVALID, "NULL argument");
-  HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipMemcpyAsync(hptr, dptr, bytes, hipMemcpyDeviceToHost, c->stream));
-  return BLAH2HIP_OK;
-}
-
-// A streaming read of `bytes` of device memory and nothing else (16-byte loads, four in flight per lane, the sum kept
-// behind a condition that never holds): what the memory system delivers to a kernel that only reads, the ceiling the
-// range kernel's loads are priced against beside the copy (bench.py `roofline.read_ceiling`).
-typedef float v4f_t __attribute__((ext_vector_type(4)));
-__global__ __launch_bounds__(256) void stream_read_kernel(const v4f_t *__restrict__ src, size_t n16, float *sink)
-{
-  // a workgroup takes contiguous 64 KB chunks (16 loads of 16 bytes per lane, all requested before the first is used:
-  // the shape tools/membench measured at 6.3 TB/s), chunk c + k * gridDim.x
-  constexpr size_t CH = 16 * 256;
-  float acc = 0.f;
-  const size_t nch = n16 / CH;
-  for (size_t c = blockIdx.x; c < nch; c += gridDim.x) {
-    const v4f_t *p = src + c * CH + threadIdx.x;
-    v4f_t v[16];
-#pragma unroll
-    for (int k = 0; k < 16; k++) v[k] = __builtin_nontemporal_load(p + 256 * k);
-#pragma unroll
-    for (int k = 0; k < 16; k++) acc += (v[k].x + v[k].y) + (v[k].z + v[k].w);
-  }
-  for (size_t i = nch * CH + (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (size_t)gridDim.x * 256) {
-    const v4f_t a = src[i];
-    acc += a.x + a.y + a.z + a.w;
-  }
-  if (acc == 1.2345678e-30f && sink) *sink = acc;
-}
-
-int blah2hip_stream_read_dev(const void *d_src, size_t bytes, void *d_sink, void *stream)
-{
-  if (!d_src || ((uintptr_t)d_src & 15)) return fail(BLAH2HIP_ERR_INVALID, "stream_read_dev: source NULL or not 16-byte aligned");
-  int dev = 0, cus = 256;
-  HIPCHK(hipGetDevice(&dev));
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  stream_read_kernel<<<dim3(cus * 6), dim3(256), 0, (hipStream_t)stream>>>((const v4f_t *)d_src, bytes / 16, (float *)d_sink);
-  HIPCHK(hipGetLastError());
-  return BLAH2HIP_OK;
-}
-
 int blah2hip_amb_result_ptrs(blah2hip_amb_t h, const void **d_map, const double **d_metrics)
 {
   if (!h) return fail(BLAH2HIP_ERR_INVALID, "NULL handle");
   if (d_map) *d_map = h->d_map;
   if (d_metrics) *d_metrics = h->d_metrics;
   return BLAH2HIP_OK;
-}
-
-// ---------------------------------------------------------------- clutter --
-// implemented in clutter.hip; it reports errors through this internal hook so
-// that blah2hip_last_error() covers both translation units
-void blah2hip_set_error_(const char *msg) { g_err = msg ? msg : ""; }
-
-hipError_t blah2hip_ensure_lds_(const void *kern, int bytes)
-{
-  static std::mutex mu;
-  static std::set<std::pair<int, const void *>> done;
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  std::lock_guard<std::mutex> lk(mu);
-  if (done.count({dev, kern})) return hipSuccess;
-  e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (e == hipSuccess) done.insert({dev, kern});
-  return e;
 }
 
 } // extern "C"

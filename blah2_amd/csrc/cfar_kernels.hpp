@@ -1,4 +1,5 @@
 // Detector kernels of the blah2 engine (gfx950 / MI355X only).
+// Included by detect.hip alone: this header defines kernels, so a second unit must not include it.
 //
 //   cfar1d_kernel                  CfarDetector1D::process            CfarDetector1D.cpp:23-100
 //   cfar2d_tile_kernel             2-D CA-CFAR (BASELINE configs[2]; extension): one read of the map

@@ -1,11 +1,12 @@
 // The end of a CPI's detection list on the device (gfx950 / MI355X only).
+// Included by detect.hip alone: this header defines kernels, so a second unit must not include it.
 //
 //   detect_finish_kernel           Centroid::process, then Interpolate::process     Centroid.cpp:19-73, Interpolate.cpp:20-91
 //
 // blah2.cpp:285-287 runs CfarDetector1D -> Centroid -> Interpolate per CPI.  The detector kernels leave a list of
 // blah2hip_hit_t per CPI on the device; this kernel turns it into the final list next to the map it came from, so neither
 // the hits nor the map cross the host link.  It restates the host functions blah2hip_centroid / blah2hip_interpolate
-// (capi.hip), which restate the reference, quirk by quirk.
+// (detect.hip), which restate the reference, quirk by quirk.
 //
 // All paths are relative to the reference's src/.
 #pragma once

@@ -1,4 +1,5 @@
 // HIP kernels of the blah2 cross-ambiguity engine (gfx950 / MI355X only).
+// Included by capi.hip alone: this header defines kernels, so a second unit must not include it.
 //
 //   range_kernel / range8_kernel   Hot loop A  Ambiguity.cpp:106-149  (segmented on-chip FFT correlation;
 //                                  16 points per thread for F = 2048 / 4096, 8 for F = 1024)
@@ -28,6 +29,7 @@
 #include "doppler_walk.hpp"
 #include "trace.hpp"
 #include "range_walk.hpp"
+#include "metrics_core.hpp"
 
 namespace blah2 {
 
@@ -1350,39 +1352,6 @@ struct DopplerArgs {
   uint32_t *tickets = nullptr; // [nCpi], zero between launches
   double *metrics = nullptr;   // [nCpi][2]
 };
-
-// 10*log10|z| = 5*log10(re^2+im^2) = 5*log10(2) * log2(re^2+im^2)
-__device__ __forceinline__ float db_of(cf z) { return 1.50514997831990597607f * log2f(z.x * z.x + z.y * z.y); }
-
-// Map::set_metrics partial of one wave: the lanes' (sum of dB values, largest dB value) folded by a butterfly over the
-// lane index, every lane ending with the wave's result.  One definition for every kernel that fuses the metrics, so
-// the order of the additions -- and with it the bits of noisePower -- is the same whichever Doppler kernel ran.
-__device__ __forceinline__ void wave_sum_max(double &lsum, float &lmax)
-{
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    lsum += __shfl_xor(lsum, off);
-    lmax = fmaxf(lmax, __shfl_xor(lmax, off));
-  }
-}
-
-// sum / max over the 256 threads of a workgroup -> one partial per workgroup
-__device__ __forceinline__ void block_metrics_partial(double lsum, float lmax, double *dst_sum, float *dst_max)
-{
-  __shared__ double wsum[4];
-  __shared__ float wmax[4];
-  wave_sum_max(lsum, lmax);
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { wsum[wave] = lsum; wmax[wave] = lmax; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double s = 0.0;
-    float m = 0.f; // Map.cpp:193: the running max starts at 0
-    for (int w = 0; w < (int)(blockDim.x >> 6); w++) { s += wsum[w]; m = fmaxf(m, wmax[w]); }
-    *dst_sum = s;
-    *dst_max = m;
-  }
-}
 
 // One column per workgroup of T = 16*R3 threads (for nD <= 513 that is a single
 // wave: its barriers cost nothing and the two exchange buffers can alias).

@@ -12,8 +12,9 @@
 #include <cstdio>
 #include <cstdlib>
 namespace blah2 {
-__device__ unsigned long long trace_buckets[16];
-__device__ unsigned int trace_launches;
+// (internal linkage: more than one unit includes this header, and the kernels of one trace macro sit in one unit)
+static __device__ unsigned long long trace_buckets[16];
+static __device__ unsigned int trace_launches;
 // one lane per wave: its buckets; the first wave of the launch also counts the launch and prints every 8th
 template <int N> __device__ __forceinline__ void trace_finish(const char *tag, const uint64_t (&tr)[N], bool first_wave_of_grid)
 {
@@ -29,9 +30,9 @@ template <int N> __device__ __forceinline__ void trace_finish(const char *tag, c
 #ifdef RANGEW_TRACE
 constexpr int RW_EXIT_RING = 8, RW_EXIT_WAVES = 4096;
 struct RwExit { unsigned long long start, exit; unsigned pulses, xcd; };
-__device__ RwExit trace_rw_exit[RW_EXIT_RING][RW_EXIT_WAVES];
-__device__ unsigned trace_rw_waves[RW_EXIT_RING]; // waves of the launch in that slot
-__device__ unsigned trace_rw_exited, trace_rw_launch;
+static __device__ RwExit trace_rw_exit[RW_EXIT_RING][RW_EXIT_WAVES];
+static __device__ unsigned trace_rw_waves[RW_EXIT_RING]; // waves of the launch in that slot
+static __device__ unsigned trace_rw_exited, trace_rw_launch;
 // one lane per wave, every wave of the launch (also those without a pulse): the last one closes the launch's slot
 __device__ __forceinline__ void trace_rw_leave(unsigned wave, unsigned waves, unsigned long long start, unsigned pulses)
 {

@@ -3,6 +3,9 @@
 (hipcc -Rpass-analysis=kernel-resource-usage; cross-compiles, no GPU needed).
 
     python tools/kernel_resources.py blah2_amd/csrc/capi.hip [filter]
+
+One unit a call: the library is several .hip files (capi.hip holds the range and Doppler kernels, array.hip the beam
+kernels, detect.hip the detectors'), so the whole library is a loop over blah2_amd/csrc/*.hip.
 """
 import os
 import re
