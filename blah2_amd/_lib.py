@@ -40,8 +40,8 @@ CLUTTER_OPT_SOLVE_K, CLUTTER_OPT_FFT_LEN, CLUTTER_OPT_CORR, CLUTTER_OPT_SOLVE_FO
 CLUTTER_OPT_SOLVE_SPIN_LIMIT = 7
 CLUTTER_SOLVE_AUTO, CLUTTER_SOLVE_STEPWISE, CLUTTER_SOLVE_LOOKAHEAD = 0, 1, 2
 CLUTTER_INFO_SOLVE_FORM, CLUTTER_INFO_SOLVE_E, CLUTTER_INFO_SOLVE_G, CLUTTER_INFO_SOLVE_FAULT, CLUTTER_INFO_SOLVE_RETRIES = 1, 2, 3, 4, 5
-CLUTTER_INFO_CORR_FORM, CLUTTER_INFO_FIR_CARRY, CLUTTER_INFO_CHUNKS = 6, 7, 8
-CLUTTER_CORR_AUTO, CLUTTER_CORR_HALF, CLUTTER_CORR_WINDOW = 0, 1, 2
+CLUTTER_INFO_CORR_FORM, CLUTTER_INFO_FIR_CARRY, CLUTTER_INFO_CHUNKS, CLUTTER_INFO_BLOCKS = 6, 7, 8, 9
+CLUTTER_CORR_AUTO, CLUTTER_CORR_HALF, CLUTTER_CORR_WINDOW, CLUTTER_CORR_DIRECT = 0, 1, 2, 3
 DOP_AUTO, DOP_TILE8, DOP_TILE16, DOP_TILEM, DOP_COLUMN, DOP_DIRECT, DOP_TILEW, DOP_TILEW2, DOP_TILE16WG, DOP_SUB4, DOP_TILE8K, DOP_TILEW4 = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11
 DOP_PFA513 = 12
 DOPPLER_KERNEL_NAMES = {DOP_AUTO: "auto", DOP_TILE8: "tile8", DOP_TILE16: "tile16", DOP_TILEM: "tilem",
@@ -130,6 +130,7 @@ SYMBOLS = {
     "blah2hip_detect_dev": (C.c_int, [_vp, _vp, _vp, _u32, _vp, _u32, _vp, C.c_uint16, C.c_uint16, _dbl, C.c_int, C.c_int, C.c_int,
                                       _vp, _u32, _vp, _vp]),
     "blah2hip_clutter_create": (C.c_int, [_i32, _i32, _u32, C.c_int, _u32, C.POINTER(_vp)]),
+    "blah2hip_clutter_create_ex": (C.c_int, [_i32, _i32, _u32, _u32, C.c_int, _u32, C.POINTER(_vp)]),
     "blah2hip_clutter_destroy": (C.c_int, [_vp]),
     "blah2hip_clutter_process_c64": (C.c_int, [_vp, _vp, _vp, _u32, _vp, C.POINTER(C.c_int)]),
     "blah2hip_clutter_process_c32": (C.c_int, [_vp, _vp, _vp, _u32, _vp, C.POINTER(C.c_int)]),

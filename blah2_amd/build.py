@@ -148,12 +148,13 @@ HOSTTEST = os.path.join(HOST, "test", "test_ambiguity")
 
 
 def build_host_test(force=False, verbose=True):
-    """C++ test programs for the drop-in classes: test_ambiguity (mirrors the reference's TestAmbiguity.cpp) and
-    test_golden (the classes against the compiled reference's values, tests/test_host_cpp_gpu.py)."""
+    """C++ test programs for the drop-in classes: test_ambiguity (mirrors the reference's TestAmbiguity.cpp),
+    test_golden (the classes against the compiled reference's values, tests/test_host_cpp_gpu.py) and test_clutter_blocks
+    (WienerHopf with taps per block against the fp64 restatement, tests/test_clutter_blocks_host_gpu.py)."""
     if not os.path.exists(HOSTLIB):
         return None
     last = None
-    for name in ("test_ambiguity", "test_golden"):
+    for name in ("test_ambiguity", "test_golden", "test_clutter_blocks"):
         src = os.path.join(HOST, "test", name + ".cpp")
         exe = os.path.join(HOST, "test", name)
         if not os.path.exists(src):

@@ -1307,6 +1307,157 @@ template <int R3, class In, bool SKIP_BAD = false> __global__ __launch_bounds__(
   }
 }
 
+// ---- the FIR with taps per BLOCK of the CPI (blah2hip_clutter_create_ex, n_blocks > 1) ------------------------------------
+// The CPI of N samples is cut into B blocks of L = N / B; block j of CPI c is virtual CPI v = c B + j with taps w_v and flag
+// ok_v of its own (estimated on the block's L samples alone).  The filter's HISTORY runs on across the block edges:
+//     y_out[n] = y[n] - sum_k w_v[k] xs[n - k]   for n in block j,   xs[i] = x[(i - delayMin) mod N] over the WHOLE CPI,
+// zero fill in front of sample 0 of the CPI only.  This is clutter_fir_kernel's overlap-save pass (whole windows, the largest
+// tap in the time domain by the same argmax rule) on another grid: a workgroup serves ONE virtual CPI -- it transforms that
+// block's taps once -- and walks the block's own segments n0 = j L + g segLen, cnt = min(segLen, L - g segLen), so that no
+// segment straddles a block edge; the windows [n0 - hist, n0 - hist + F) reach back into block j - 1 through the CPI-level
+// XsMap.  The y loads and the stores are descriptors over exactly the cnt new samples, as there.
+// (The tap preamble is written out a second time: taken out into one forceinline function for both kernels it changed the
+// register allocation of four of clutter_fir_kernel's fifteen instantiations -- 101 -> 99 SGPRs for the int16 words,
+// 254 -> 256 VGPRs for <16, InC32, true> -- and that kernel's code is the n_blocks = 1 contract.)
+// Grid: a block has few segments (ceil(L / segLen)) and a launch many virtual CPIs, so seg_walk -- eight XCDs times the
+// workgroups of ONE CPI -- would leave most workgroups without a segment.  Here the launch is flat: workgroups are dealt
+// round-robin over the 8 XCDs, so workgroup b runs on XCD b & 7; virtual CPI v is served by XCD v & 7 alone, by gx workgroups
+// in consecutive dispatch slots of that XCD, which take segments job, job + gx, ...: neighbouring windows (they overlap by
+// hist samples) meet in one L2, and only the padding of nVirt to a multiple of 8 is idle.
+struct FirBlocksArgs {
+  const void *x, *y;
+  cf *yout;
+  int64_t cpiStride, outStride;
+  XsMap xs;          // of the CPI (N samples), not of the block
+  int32_t nBins, segLen, nSeg; // nSeg = segments per BLOCK
+  int32_t L, B, nVirt, gx;     // block length, blocks per CPI, virtual CPIs of the launch, workgroups per virtual CPI
+  const cf *w;       // [nVirt][nBins]
+  const int32_t *ok; // [nVirt]
+  const cf *tw;
+  float scale;
+};
+
+template <int R3, class In> __global__ __launch_bounds__(16 * R3, 2) void clutter_fir_blocks_kernel(FirBlocksArgs a)
+{
+  using W = WgFft<R3>;
+  constexpr int T = W::T;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  cf *P = reinterpret_cast<cf *>(smem);
+  cf *Q = P + W::A_ELEMS;
+  const int t = threadIdx.x;
+  const int slot = blockIdx.x >> 3;
+  const int vc = (slot / a.gx) * 8 + (blockIdx.x & 7), job = slot % a.gx;
+  if (vc >= a.nVirt) return; // uniform: the padding of the launch
+  const int cpi = vc / a.B, blk = vc - cpi * a.B;
+  const typename ChanOf<In>::type X = ChanOf<In>::x(a.x, a.y, (int64_t)cpi * a.cpiStride);
+  cf *O = a.yout + (int64_t)cpi * a.outStride;
+  const bool ok = a.ok[vc] != 0;
+  cf tw1[15], tw3[16];
+  W::load_twiddles(t, a.tw, tw1, tw3);
+
+  // spectrum of the block's taps, all but the largest (clutter_fir_kernel)
+  const cf *wv_ = a.w + (size_t)vc * a.nBins;
+  cf ws[16];
+  float bestMag = -1.f;
+  int bestIdx = 0;
+#pragma unroll
+  for (int k = 0; k < 16; k++) {
+    const int m = t + T * k;
+    const cf wv = wv_[min(m, a.nBins - 1)];
+    const float keep = (m < a.nBins) ? a.scale : 0.f;
+    ws[k] = cmake(wv.x * keep, wv.y * keep);
+    const float mag = (m < a.nBins) ? wv.x * wv.x + wv.y * wv.y : -1.f;
+    if (mag > bestMag) { bestMag = mag; bestIdx = m; } // (ascending m: ties go to the lower index)
+  }
+  {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const float mu = __shfl_xor(bestMag, off);
+      const int iu = __shfl_xor(bestIdx, off);
+      if (mu > bestMag || (mu == bestMag && iu < bestIdx)) { bestMag = mu; bestIdx = iu; }
+    }
+    if (T > 64) {
+      float *sm = reinterpret_cast<float *>(P);
+      int *si = reinterpret_cast<int *>(P) + T / 64;
+      if ((t & 63) == 0) { sm[t >> 6] = bestMag; si[t >> 6] = bestIdx; }
+      __syncthreads();
+#pragma unroll
+      for (int u = 0; u < T / 64; u++) {
+        const float mu = sm[u];
+        const int iu = si[u];
+        if (mu > bestMag || (mu == bestMag && iu < bestIdx)) { bestMag = mu; bestIdx = iu; }
+      }
+      __syncthreads();
+    }
+  }
+  const int k0 = bestIdx;
+  const cf w0 = wv_[k0];
+#pragma unroll
+  for (int k = 0; k < 16; k++)
+    if (t + T * k == k0) ws[k] = cmake(0.f, 0.f);
+  W::fwd_s1(t, ws, tw1, P);
+  __syncthreads();
+  W::fwd_s2(t, ws, P, Q);
+  __syncthreads();
+  W::fwd_s3(t, ws, tw3, Q);
+  __syncthreads();
+
+  const int hist = a.nBins - 1;
+  const int N = (int)a.xs.N;
+  const int blk0 = blk * a.L; // first sample of the block in its CPI
+  using CX = typename BufChanOf<In>::X;
+  using CY = typename BufChanOf<In>::Y;
+  // sixteen values of the window that starts at sample src0 of the CPI's xs: zero outside [0, N)
+  auto load_window = [&](cf *dst, int src0) {
+    uint32_t j0;
+    int xcnt;
+    if (xs_window_plain(src0, 16 * T, a.xs, &j0, &xcnt)) { // the interior: one contiguous run of x, immediates only
+      const __amdgpu_buffer_rsrc_t xd = make_rsrc_b(BufChanOf<In>::x(a.x, a.y, (int64_t)cpi * a.cpiStride + j0), xcnt * CX::STRIDE);
+#pragma unroll
+      for (int k = 0; k < 16; k++) dst[k] = RawBuiltin<CX>::cvt(RawBuiltin<CX>::ld(xd, (t + T * k) * CX::STRIDE, 0));
+    } else {
+#pragma unroll
+      for (int k = 0; k < 16; k++) {
+        const int src = src0 + t + T * k;
+        const bool inr = src >= 0 && src < N;
+        const cf xv = X[xs_index(inr ? (uint32_t)src : 0u, a.xs)];
+        dst[k] = inr ? xv : cmake(0.f, 0.f);
+      }
+    }
+  };
+  for (int g = job; g < a.nSeg; g += a.gx) {
+    const int off = g * a.segLen;
+    const int n0 = blk0 + off, cnt = min(a.segLen, a.L - off); // the block's own grid: the last segment ends with the block
+    cf v[16], yv[16];
+    load_window(v, n0 - hist);
+    const __amdgpu_buffer_rsrc_t yd = make_rsrc_b(BufChanOf<In>::y(a.x, a.y, (int64_t)cpi * a.cpiStride + n0), cnt * CY::STRIDE);
+    const __amdgpu_buffer_rsrc_t od = make_rsrc_b(O + n0, cnt * 8);
+#pragma unroll
+    for (int k = 0; k < 16; k++) yv[k] = RawBuiltin<CY>::cvt(RawBuiltin<CY>::ld(yd, (t + T * k - hist) * CY::STRIDE, 0));
+    cf xdir[16];
+    if (ok) {
+      W::fwd_s1(t, v, tw1, P);
+      __syncthreads();
+      W::fwd_s2(t, v, P, Q);
+      __syncthreads();
+      W::fwd_s3(t, v, tw3, Q);
+#pragma unroll
+      for (int e = 0; e < 16; e++) v[e] = cmul(v[e], ws[e]);
+      load_window(xdir, n0 - hist - k0); // register c: xs[n - k0] of the output sample n that register c writes
+      __syncthreads();
+      W::inv_s1(t, v, tw3, P);
+      __syncthreads();
+      W::inv_s2(t, v, P, Q);
+      __syncthreads();
+      W::inv_s3(t, v, tw1, Q);
+      __syncthreads();
+    }
+#pragma unroll
+    for (int c = 0; c < 16; c++)
+      bufstore_c32(od, (t + T * c - hist) * 8, ok ? csub(csub(yv[c], cmul(w0, xdir[c])), v[c]) : yv[c]); // a block that is not PD passes through
+  }
+}
+
 
 } // namespace
 
@@ -1375,6 +1526,12 @@ struct blah2hip_clutter_s {
   cf *d_wM = nullptr;          // [K][n_cpi][nBins]: virtual CPI k n_cpi + c
   int32_t *d_okM = nullptr;    // [K][n_cpi]
   uint32_t lastSurv = 0, lastNCpi = 0; // the last call was a multi call: its channels and CPIs per channel (0: a single call)
+  // taps per BLOCK of the CPI (blah2hip_clutter_create_ex with n_blocks > 1, see launch_clutter_blocks): this handle keeps the
+  // CPI's geometry (N, delayMin: the FIR's XsMap) and the FIR's timer; `blk` is a handle for CPIs of N / nBlocks samples and a
+  // batch of maxBatch nBlocks -- the plan, the estimation kernels' buffers, taps, flags and solve state of the virtual CPIs
+  uint32_t nBlocks = 1;
+  blah2hip_clutter_s *blk = nullptr;
+  bool blockChild = false; // this handle IS such a child: its launches have n_cpi n_blocks systems (launch_solve)
 };
 
 namespace {
@@ -1403,7 +1560,7 @@ int solve_la_alloc(blah2hip_clutter_s *h)
     if (h->solveE && E != h->solveE) continue;
     const sla::Plan p4 = sla::make_plan(h->nBins, E, 4), p8 = sla::make_plan(h->nBins, E, 8);
     int64_t batch = h->maxBatch;
-    if (!h->solveE && E != 12) batch = std::min<int64_t>(batch, 8 * (h->numCU / (8 * std::min(p4.G, p8.G))));
+    if (!h->solveE && E != 12 && !(h->blockChild && p8.G == 1)) batch = std::min<int64_t>(batch, 8 * (h->numCU / (8 * std::min(p4.G, p8.G))));
     need = std::max(need, p4.stride * batch);
   }
   if (need > h->mailWords) {
@@ -1533,7 +1690,16 @@ int launch_solve(blah2hip_clutter_s *h, const SolveArgs &sa, uint32_t nCpi, hipS
   CHIP(h->timer.tic(BLAH2HIP_CK_SOLVE, st));
   if (h->solveForm != BLAH2HIP_CLUTTER_SOLVE_STEPWISE && h->d_mail) {
     // blocks of 32 orders on several workgroups per CPI (solve_la.hpp): as many CUs per CPI as the launch leaves free
-    const sla::Plan p = sla::choose_plan(h->nBins, (int)nCpi, h->numCU, h->solveE, [h](int E, int NW) { return solve_la_cap(h, E, NW); });
+    sla::Plan p = sla::choose_plan(h->nBins, (int)nCpi, h->numCU, h->solveE, [h](int E, int NW) { return solve_la_cap(h, E, NW); });
+    // A block child beyond one system per CU (n_cpi n_blocks small systems: 4096 at configs[1] with 16 blocks): the planner's
+    // fallback is its widest slices, built for a lone CPI's "nothing to wait for".  The narrowest slices that still make ONE
+    // workgroup per system wait for nothing either, and ran the 1024 ... 4096 systems of 410 taps 2.8 x faster (measured,
+    // DESIGN.md section 7 item 13).  Handles without blocks keep the planner's choice: their taps' bits are a contract.
+    if (h->blockChild && !h->solveE && p.E == 12 && (int64_t)((nCpi + 7) / 8 * 8) > h->numCU)
+      for (int E : sla::kE) {
+        const sla::Plan q = sla::make_plan(h->nBins, E, 8);
+        if (q.G == 1) { p = q; break; }
+      }
     sla::Args la;
     la.rb = sa.rb; la.w = sa.w; la.ok = ok; la.mail = h->d_mail; la.epoch = h->d_epoch; la.fault = h->d_epoch + 1;
     la.spinLimit = h->spinLimit;
@@ -1581,8 +1747,13 @@ void clutter_grids(const blah2hip_clutter_s *h, uint32_t nCpi, int *nJobs, int *
   *firGrid = std::min(h->firGrid, up8((2 * slots + (int)nCpi - 1) / (int)nCpi));
 }
 
+// groups > 1 (the block form, launch_clutter_blocks, where the caller's CPIs do not lie back to back): the nCpi CPIs are
+// `groups` runs of nCpi / groups CPIs, `stride` apart inside a run, run q starting groupStride samples behind run q - 1.
+// The correlations are then one launch per run into that run's rows of the partials; the reduction and the solve stay one
+// launch over all nCpi, and the grid per CPI is the one a single launch over nCpi has, so the results are its bits.
 template <int R3, class In> int launch_clutter(blah2hip_clutter_s *h, const void *px, const void *py, uint32_t nCpi,
-                                               int64_t stride, cf *yout, int64_t outStride, int32_t *ok, hipStream_t st)
+                                               int64_t stride, cf *yout, int64_t outStride, int32_t *ok, hipStream_t st,
+                                               uint32_t groups = 1, int64_t groupStride = 0)
 {
   using W = WgFft<R3>;
   const size_t lds = (size_t)(W::A_ELEMS + W::B_ELEMS) * sizeof(cf);
@@ -1602,20 +1773,28 @@ template <int R3, class In> int launch_clutter(blah2hip_clutter_s *h, const void
   clutter_grids(h, nCpi, &nJobs, &firGrid);
   if (h->stages & 1) {
   CHIP(h->timer.tic(BLAH2HIP_CK_CORR, st));
-  if (h->corrHalf) {
-    CHIP(blah2hip_ensure_lds_((const void *)clutter_corr_half_kernel<R3, In>, (int)lds));
-    CorrHalfArgs ha;
-    ha.x = px; ha.y = py; ha.cpiStride = stride; ha.N = h->N; ha.xs = xs;
-    ha.nBins = h->nBins; ha.nSeg = (int)((h->N + (uint32_t)(h->F / 2) - 1) / (uint32_t)(h->F / 2));
-    ha.per = (ha.nSeg + nJobs - 1) / nJobs; ha.nJobs = nJobs;
-    ha.tw = h->d_tw; ha.partial = h->d_partial; ha.scale = 1.0f / (float)h->F;
-    hipLaunchKernelGGL((clutter_corr_half_kernel<R3, In>), dim3(nJobs, nCpi), dim3(W::T), lds, st, ha);
-  } else {
-    CorrArgs ca;
-    ca.x = px; ca.y = py; ca.cpiStride = stride; ca.N = h->N; ca.xs = xs;
-    ca.nBins = h->nBins; ca.segLen = h->segLen; ca.nSeg = h->nSeg; ca.nJobs = nJobs;
-    ca.tw = h->d_tw; ca.partial = h->d_partial; ca.scale = 1.0f / (float)h->F;
-    hipLaunchKernelGGL((clutter_corr_kernel<R3, In>), dim3(nJobs, nCpi), dim3(W::T), lds, st, ca);
+  const uint32_t perRun = nCpi / groups;
+  for (uint32_t q = 0; q < groups; q++) {
+    // (bytes per sample: 8 for the fp32 planes and the int16 words, 2 for the int8 planes; py is NULL with the int16 words)
+    const int64_t qoff = (int64_t)q * groupStride * BufChanOf<In>::X::STRIDE;
+    const void *qx = (const char *)px + qoff;
+    const void *qy = py ? (const char *)py + qoff : nullptr;
+    cf *qpartial = h->d_partial + (size_t)q * perRun * 2 * nJobs * h->nBins;
+    if (h->corrHalf) {
+      CHIP(blah2hip_ensure_lds_((const void *)clutter_corr_half_kernel<R3, In>, (int)lds));
+      CorrHalfArgs ha;
+      ha.x = qx; ha.y = qy; ha.cpiStride = stride; ha.N = h->N; ha.xs = xs;
+      ha.nBins = h->nBins; ha.nSeg = (int)((h->N + (uint32_t)(h->F / 2) - 1) / (uint32_t)(h->F / 2));
+      ha.per = (ha.nSeg + nJobs - 1) / nJobs; ha.nJobs = nJobs;
+      ha.tw = h->d_tw; ha.partial = qpartial; ha.scale = 1.0f / (float)h->F;
+      hipLaunchKernelGGL((clutter_corr_half_kernel<R3, In>), dim3(nJobs, perRun), dim3(W::T), lds, st, ha);
+    } else {
+      CorrArgs ca;
+      ca.x = qx; ca.y = qy; ca.cpiStride = stride; ca.N = h->N; ca.xs = xs;
+      ca.nBins = h->nBins; ca.segLen = h->segLen; ca.nSeg = h->nSeg; ca.nJobs = nJobs;
+      ca.tw = h->d_tw; ca.partial = qpartial; ca.scale = 1.0f / (float)h->F;
+      hipLaunchKernelGGL((clutter_corr_kernel<R3, In>), dim3(nJobs, perRun), dim3(W::T), lds, st, ca);
+    }
   }
   CHIP(hipGetLastError());
   CHIP(h->timer.toc(BLAH2HIP_CK_CORR, st));
@@ -1644,6 +1823,132 @@ template <int R3, class In> int launch_clutter(blah2hip_clutter_s *h, const void
   h->lastOk = ok;
   h->lastStream = st;
   return BLAH2HIP_OK;
+}
+
+// ---- correlations of a SHORT block, lag by lag in fp64 ----------------------------------------------------------------------
+// A block of L samples with nBins taps has the matrix of a circular autocorrelation over L: at L = nBins a full circulant whose
+// eigenvalues are the reference's power spectrum -- cond(A) 4e4 ... 9e5 on white references of 2047 samples, 1e2 at L = 1.5
+// nBins, 5e1 at 2 nBins, 2e1 from 3 nBins on (fp64, CPU).  The transforms' fp32 partials carry 1e-7 of r[0]; times such a
+// condition number that moved the filtered channel by 1e-2 of itself at L = nBins (measured; the gate is 1e-4).  So a block
+// child with L < 2 nBins forms r and b directly: a thread per lag, the L products summed in order in fp64 (exact products of
+// fp32 samples, 1e-13 of the sum), written where the reduction would have put them.  L nBins products per block and row: at most
+// 2 nBins^2, nothing beside the solve there -- and not a path for long blocks (L nBins grows where the transforms' L log F
+// does not).  Deterministic: one fixed-order sum per lag.
+struct CorrDirectArgs {
+  const void *x, *y;
+  int64_t cpiStride; // of the caller's CPIs; block j of CPI c starts at c cpiStride + j L
+  XsMap xs;          // of the block (N = L)
+  int32_t nBins, B, lagTiles;
+  dcx *rb;           // [nVirt][2][nBins]: r then b
+};
+template <class In> __global__ __launch_bounds__(256) void clutter_corr_direct_kernel(CorrDirectArgs a)
+{
+  const int vc = blockIdx.x / a.lagTiles, k = (blockIdx.x - vc * a.lagTiles) * 256 + threadIdx.x, mode = blockIdx.y;
+  if (k >= a.nBins) return;
+  const int cpi = vc / a.B, blk = vc - cpi * a.B;
+  const uint32_t L = a.xs.N;
+  const int64_t base = (int64_t)cpi * a.cpiStride + (int64_t)blk * L;
+  const typename ChanOf<In>::type X = ChanOf<In>::x(a.x, a.y, base);
+  const typename ChanOf<In>::type Y = ChanOf<In>::y(a.x, a.y, base);
+  double sx = 0.0, sy = 0.0;
+  uint32_t m = (uint32_t)k; // (n + k) mod L; k < nBins <= L
+  for (uint32_t n = 0; n < L; n++) {
+    const cf u = X[xs_index(n, a.xs)];
+    const cf s = mode ? Y[m] : X[xs_index(m, a.xs)];
+    // s conj(u)
+    sx = __builtin_fma((double)s.x, (double)u.x, __builtin_fma((double)s.y, (double)u.y, sx));
+    sy = __builtin_fma((double)s.y, (double)u.x, __builtin_fma(-(double)s.x, (double)u.y, sy));
+    m = (m + 1u == L) ? 0u : m + 1u;
+  }
+  a.rb[((size_t)vc * 2 + mode) * a.nBins + k] = {sx, sy};
+}
+// the rule (a planner override of the correlation form takes the child back to the transforms)
+inline bool corr_direct(const blah2hip_clutter_s *c)
+{
+  return c->blockChild && c->corrForce == BLAH2HIP_CLUTTER_CORR_AUTO && (uint64_t)c->N < 2ull * (uint64_t)c->nBins;
+}
+
+// ---- taps per block of the CPI -------------------------------------------------------------------------------------------
+// Estimation: block j of CPI c is virtual CPI c B + j of the child handle (CPIs of L = N / B samples: shift and correlations
+// circular inside the block), through the existing correlation, reduction and solve kernels.  Virtual CPI v starts at
+// c stride + j L: where the caller's CPIs lie back to back (stride == N, or one CPI) that is ONE launch over nCpi B CPIs of
+// stride L; otherwise one correlation launch per CPI (B virtual CPIs of stride L each) into that CPI's rows of the partials,
+// and still one reduction and one solve over all of them (launch_clutter's `groups`).  Then clutter_fir_blocks_kernel.
+template <int R3, class In> int launch_clutter_blocks(blah2hip_clutter_s *h, const void *px, const void *py, uint32_t nCpi,
+                                                      int64_t stride, cf *yout, int64_t outStride, int32_t *ok, hipStream_t st)
+{
+  using W = WgFft<R3>;
+  blah2hip_clutter_s *c = h->blk;
+  const uint32_t B = h->nBlocks, L = h->N / B, V = nCpi * B;
+  const bool flat = nCpi == 1 || stride == (int64_t)h->N;
+  if (corr_direct(c)) { // short blocks: r and b lag by lag in fp64, straight into the solve's input
+    CorrDirectArgs da;
+    da.x = px; da.y = py; da.cpiStride = stride;
+    da.xs.N = L;
+    da.xs.thresh = c->delayMin > 0 ? (uint32_t)c->delayMin : 0u;
+    da.xs.sub = (uint32_t)c->delayMin;
+    da.xs.wrapC = (uint32_t)(((1ull << 32) - (uint64_t)(c->delayMin > 0 ? c->delayMin : 0)) % L);
+    da.nBins = c->nBins; da.B = (int32_t)B; da.lagTiles = (c->nBins + 255) / 256; da.rb = c->d_rb;
+    CHIP(c->timer.tic(BLAH2HIP_CK_CORR, st));
+    hipLaunchKernelGGL((clutter_corr_direct_kernel<In>), dim3(V * (uint32_t)da.lagTiles, 2), dim3(256), 0, st, da);
+    CHIP(hipGetLastError());
+    CHIP(c->timer.toc(BLAH2HIP_CK_CORR, st));
+    CHIP(c->timer.tic(BLAH2HIP_CK_REDUCE, st)); // nothing to reduce: the launch that bumps the look-ahead solve's epoch
+    hipLaunchKernelGGL(solve_epoch_kernel, dim3(1), dim3(1), 0, st, c->d_epoch);
+    CHIP(c->timer.toc(BLAH2HIP_CK_REDUCE, st));
+    SolveArgs sa;
+    sa.partial = nullptr; sa.rb = c->d_rb; sa.w = c->d_w; sa.ok = ok; sa.nBins = c->nBins; sa.nJobs = 0; sa.epoch = c->d_epoch;
+    { const int rc_ = launch_solve(c, sa, V, st); if (rc_) return rc_; }
+    c->lastSurv = 0;
+    c->lastOk = ok;
+    c->lastStream = st;
+  } else {
+    c->stages = 3;
+    const int rc_ = launch_clutter<R3, In>(c, px, py, V, (int64_t)L, nullptr, 0, ok, st, flat ? 1u : nCpi, stride);
+    if (rc_) return rc_;
+  }
+  h->lastSurv = 0;
+  h->lastOk = ok;
+  h->lastStream = st;
+  if (!yout) return BLAH2HIP_OK; // the taps only (blah2hip_clutter_estimate_dev_fmt)
+
+  const size_t lds = (size_t)(W::A_ELEMS + W::B_ELEMS) * sizeof(cf);
+  CHIP(blah2hip_ensure_lds_((const void *)clutter_fir_blocks_kernel<R3, In>, (int)lds));
+  FirBlocksArgs fa;
+  fa.x = px; fa.y = py; fa.yout = yout; fa.cpiStride = stride; fa.outStride = outStride;
+  fa.xs.N = h->N;
+  fa.xs.thresh = h->delayMin > 0 ? (uint32_t)h->delayMin : 0u;
+  fa.xs.sub = (uint32_t)h->delayMin;
+  fa.xs.wrapC = (uint32_t)(((1ull << 32) - (uint64_t)(h->delayMin > 0 ? h->delayMin : 0)) % h->N);
+  fa.nBins = c->nBins; fa.segLen = c->segLen; fa.nSeg = c->nSeg; // the child's plan: segments of a block
+  fa.L = (int32_t)L; fa.B = (int32_t)B; fa.nVirt = (int32_t)V;
+  // workgroups per virtual CPI: two resident generations over the launch (clutter_grids), at most one per segment
+  const int slots = 4 * c->numCU;
+  fa.gx = std::max(1, std::min(c->nSeg, (2 * slots + (int)V - 1) / (int)V));
+  fa.w = c->d_w; fa.ok = ok; fa.tw = c->d_tw; fa.scale = 1.0f / (float)c->F;
+  const uint32_t grid = (V + 7) / 8 * 8 * (uint32_t)fa.gx;
+  CHIP(h->timer.tic(BLAH2HIP_CK_FIR, st));
+  hipLaunchKernelGGL((clutter_fir_blocks_kernel<R3, In>), dim3(grid), dim3(W::T), lds, st, fa);
+  CHIP(hipGetLastError());
+  CHIP(h->timer.toc(BLAH2HIP_CK_FIR, st));
+  return BLAH2HIP_OK;
+}
+
+template <class In> int dispatch_blocks(blah2hip_clutter_s *h, const void *px, const void *py, uint32_t nCpi, int64_t stride,
+                                        cf *yout, int64_t outStride, int32_t *ok, hipStream_t st)
+{
+  switch (h->blk->r3) {
+  case 4: return launch_clutter_blocks<4, In>(h, px, py, nCpi, stride, yout, outStride, ok, st);
+  case 8: return launch_clutter_blocks<8, In>(h, px, py, nCpi, stride, yout, outStride, ok, st);
+  default: return launch_clutter_blocks<16, In>(h, px, py, nCpi, stride, yout, outStride, ok, st);
+  }
+}
+int process_blocks(blah2hip_clutter_s *h, int fmt, const void *px, const void *py, uint32_t nCpi, int64_t stride, cf *yout,
+                   int64_t outStride, int32_t *ok, hipStream_t st)
+{
+  if (fmt == BLAH2HIP_FMT_I16) return dispatch_blocks<InI16>(h, px, nullptr, nCpi, stride, yout, outStride, ok, st);
+  if (fmt == BLAH2HIP_FMT_I8) return dispatch_blocks<InI8>(h, px, py, nCpi, stride, yout, outStride, ok, st);
+  return dispatch_blocks<InC32>(h, px, py, nCpi, stride, yout, outStride, ok, st);
 }
 
 // ---- several surveillance channels against one reference ----------------------------------------------------------------
@@ -1972,11 +2277,50 @@ int blah2hip_clutter_create(int32_t delay_min, int32_t delay_max, uint32_t n_sam
   return BLAH2HIP_OK;
 }
 
+int blah2hip_clutter_create_ex(int32_t delay_min, int32_t delay_max, uint32_t n_samples, uint32_t n_blocks, int device,
+                               uint32_t max_batch, blah2hip_clutter_t *out)
+{
+  if (!out) CFAIL(BLAH2HIP_ERR_INVALID, "out is NULL");
+  *out = nullptr;
+  if (n_blocks == 0) CFAIL(BLAH2HIP_ERR_INVALID, "n_blocks must be positive");
+  if (n_samples % n_blocks != 0) CFAIL(BLAH2HIP_ERR_INVALID, "nSamples is not a multiple of n_blocks (equal blocks only)");
+  if (n_blocks == 1) return blah2hip_clutter_create(delay_min, delay_max, n_samples, device, max_batch, out);
+  if (delay_max <= delay_min) CFAIL(BLAH2HIP_ERR_INVALID, "clutter filter needs delayMax > delayMin");
+  if (n_samples > 0x7fffffffu - 8192u) CFAIL(BLAH2HIP_ERR_UNSUPPORTED, "nSamples >= 2^31 - 8192 (32-bit sample indices)");
+  if (max_batch == 0) max_batch = 1;
+  if ((uint64_t)max_batch * n_blocks > 0x7fffffffull) CFAIL(BLAH2HIP_ERR_INVALID, "max_batch * n_blocks exceeds 2^31 - 1");
+  const int64_t nBins = (int64_t)delay_max - delay_min;
+  const uint32_t L = n_samples / n_blocks;
+  if (nBins > 4096 - 15) CFAIL(BLAH2HIP_ERR_UNSUPPORTED, "a long filter (more than 4081 taps) has no block form");
+  // (the reference reads its correlation lags out of bounds on a block shorter than the filter, WienerHopf.cpp:76-108)
+  if ((int64_t)L < nBins) CFAIL(BLAH2HIP_ERR_UNSUPPORTED, "blocks shorter than the filter: nSamples / n_blocks < delayMax - delayMin");
+  blah2hip_clutter_t blk = nullptr;
+  // everything of the estimation: the plan for CPIs of L samples and its checks (|delayMin| < L, device, ...)
+  { const int rc_ = blah2hip_clutter_create(delay_min, delay_max, L, device, max_batch * n_blocks, &blk); if (rc_) return rc_; }
+  blk->blockChild = true;
+  { const int rc_ = solve_la_alloc(blk); if (rc_) { blah2hip_clutter_destroy(blk); return rc_; } } // mailboxes for every plan such a handle can be given
+  auto *h = new blah2hip_clutter_s;
+  h->device = device;
+  h->delayMin = delay_min; h->delayMax = delay_max;
+  h->N = n_samples; h->maxBatch = max_batch; h->nBins = (int32_t)nBins;
+  h->nBlocks = n_blocks; h->blk = blk;
+  h->numCU = blk->numCU;
+  const hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+  if (e != hipSuccess) {
+    blah2hip_set_error_((std::string("hipStreamCreateWithFlags: ") + hipGetErrorString(e)).c_str());
+    blah2hip_clutter_destroy(h);
+    return BLAH2HIP_ERR_HIP;
+  }
+  *out = h;
+  return BLAH2HIP_OK;
+}
+
 int blah2hip_clutter_destroy(blah2hip_clutter_t h)
 {
   if (!h) return BLAH2HIP_OK;
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
+  if (h->blk) (void)blah2hip_clutter_destroy(h->blk);
   if (h->subCorr) (void)blah2hip_clutter_destroy(h->subCorr);
   if (h->subFir) (void)blah2hip_clutter_destroy(h->subFir);
   for (void *p : {(void *)h->d_tw, (void *)h->d_partial, (void *)h->d_rb, (void *)h->d_w, (void *)h->d_ok,
@@ -1992,22 +2336,28 @@ int blah2hip_clutter_destroy(blah2hip_clutter_t h)
 int blah2hip_clutter_get_dims(blah2hip_clutter_t h, uint32_t *n_bins, uint32_t *fft_len, uint32_t *seg_len)
 {
   if (!h) CFAIL(BLAH2HIP_ERR_INVALID, "NULL handle");
-  if (n_bins) *n_bins = (uint32_t)h->nBins;
-  if (fft_len) *fft_len = (uint32_t)h->F;
-  if (seg_len) *seg_len = (uint32_t)h->segLen;
+  const blah2hip_clutter_s *p = h->blk ? h->blk : h; // blocks: the plan is the block's
+  if (n_bins) *n_bins = (uint32_t)p->nBins;
+  if (fft_len) *fft_len = (uint32_t)p->F;
+  if (seg_len) *seg_len = (uint32_t)p->segLen;
   return BLAH2HIP_OK;
 }
 
 int blah2hip_clutter_get_info(blah2hip_clutter_t h, int what, int64_t *value)
 {
   if (!h || !value) CFAIL(BLAH2HIP_ERR_INVALID, "NULL argument");
+  if (what == BLAH2HIP_CLUTTER_INFO_BLOCKS) { *value = h->nBlocks; return BLAH2HIP_OK; }
+  if (h->blk) { // the estimation is the child's; the block FIR reads every window whole
+    if (what == BLAH2HIP_CLUTTER_INFO_FIR_CARRY) { *value = 0; return BLAH2HIP_OK; }
+    return blah2hip_clutter_get_info(h->blk, what, value);
+  }
   switch (what) {
   case BLAH2HIP_CLUTTER_INFO_SOLVE_FORM: *value = h->lastForm; return BLAH2HIP_OK;
   case BLAH2HIP_CLUTTER_INFO_SOLVE_E: *value = h->lastE; return BLAH2HIP_OK;
   case BLAH2HIP_CLUTTER_INFO_SOLVE_G: *value = h->lastG; return BLAH2HIP_OK;
   case BLAH2HIP_CLUTTER_INFO_CORR_FORM: { // the long form's correlations are its first child's
     const blah2hip_clutter_s *p = h->subCorr ? h->subCorr : h;
-    *value = p->corrHalf ? BLAH2HIP_CLUTTER_CORR_HALF : BLAH2HIP_CLUTTER_CORR_WINDOW;
+    *value = corr_direct(p) ? BLAH2HIP_CLUTTER_CORR_DIRECT : (p->corrHalf ? BLAH2HIP_CLUTTER_CORR_HALF : BLAH2HIP_CLUTTER_CORR_WINDOW);
     return BLAH2HIP_OK;
   }
   case BLAH2HIP_CLUTTER_INFO_FIR_CARRY: *value = (h->subFir ? h->subFir : h)->firCarry ? 1 : 0; return BLAH2HIP_OK;
@@ -2030,6 +2380,7 @@ int blah2hip_clutter_get_info(blah2hip_clutter_t h, int what, int64_t *value)
 int blah2hip_clutter_read_last(blah2hip_clutter_t h, uint32_t cpi, float *w, double *rb, int *ok)
 {
   if (!h) CFAIL(BLAH2HIP_ERR_INVALID, "NULL handle");
+  if (h->blk) return blah2hip_clutter_read_last(h->blk, cpi, w, rb, ok); // virtual CPI c n_blocks + j
   if (h->lastSurv) { // behind a multi call: virtual CPI k n_cpi + c
     if (cpi >= h->lastSurv * h->lastNCpi) CFAIL(BLAH2HIP_ERR_INVALID, "cpi index out of range (virtual CPIs of the last multi call)");
     CHIP(hipSetDevice(h->device));
@@ -2064,6 +2415,7 @@ int blah2hip_clutter_read_last(blah2hip_clutter_t h, uint32_t cpi, float *w, dou
 int blah2hip_clutter_set_option(blah2hip_clutter_t h, int option, int64_t value)
 {
   if (!h) CFAIL(BLAH2HIP_ERR_INVALID, "NULL handle");
+  if (h->blk) return blah2hip_clutter_set_option(h->blk, option, value); // the plan (for CPIs of one block) and the solve are the child's
   if (h->subCorr) CFAIL(BLAH2HIP_ERR_UNSUPPORTED, "a long filter (more than 4081 taps) has one plan: no options");
   switch (option) {
   case BLAH2HIP_CLUTTER_OPT_SOLVE_K:
@@ -2128,6 +2480,7 @@ int blah2hip_clutter_set_option(blah2hip_clutter_t h, int option, int64_t value)
 int blah2hip_clutter_solve(blah2hip_clutter_t h, const double *rb, uint32_t n_cpi, float *w, int32_t *ok)
 {
   if (!h || !rb || !w || !ok) CFAIL(BLAH2HIP_ERR_INVALID, "NULL argument");
+  if (h->blk) return blah2hip_clutter_solve(h->blk, rb, n_cpi, w, ok); // n_cpi counts virtual CPIs
   if (n_cpi == 0 || n_cpi > h->maxBatch) CFAIL(BLAH2HIP_ERR_INVALID, "n_cpi outside [1, max_batch]");
   CHIP(hipSetDevice(h->device));
   const size_t n = (size_t)h->nBins;
@@ -2148,6 +2501,7 @@ int blah2hip_clutter_solve(blah2hip_clutter_t h, const double *rb, uint32_t n_cp
 int blah2hip_clutter_solve_dev(blah2hip_clutter_t h, const double *d_rb, uint32_t n_cpi, float *d_w, int32_t *d_ok, void *stream)
 {
   if (!h || !d_rb || !d_w || !d_ok) CFAIL(BLAH2HIP_ERR_INVALID, "NULL argument");
+  if (h->blk) return blah2hip_clutter_solve_dev(h->blk, d_rb, n_cpi, d_w, d_ok, stream);
   if (n_cpi == 0 || n_cpi > h->maxBatch) CFAIL(BLAH2HIP_ERR_INVALID, "n_cpi outside [1, max_batch]");
   CHIP(hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream;
@@ -2165,6 +2519,7 @@ int blah2hip_clutter_set_timing(blah2hip_clutter_t h, int enable)
   if (!h) CFAIL(BLAH2HIP_ERR_INVALID, "NULL handle");
   h->timer.enabled = enable != 0;
   if (h->subCorr) h->subCorr->timer.enabled = enable != 0; // the long form: correlations and reduction are the child's launches
+  if (h->blk) h->blk->timer.enabled = enable != 0;         // blocks: everything but the FIR
   return BLAH2HIP_OK;
 }
 
@@ -2179,6 +2534,12 @@ int blah2hip_clutter_get_timing(blah2hip_clutter_t h, double *ms_total, uint32_t
     uint32_t nl[BLAH2HIP_CK_COUNT];
     CHIP(h->subCorr->timer.collect(ms, nl));
     for (int k : {BLAH2HIP_CK_CORR, BLAH2HIP_CK_REDUCE}) { ms_total[k] += ms[k]; launches[k] += nl[k]; }
+  }
+  if (h->blk) { // blocks: correlations, reduction and solve are bracketed on the child, the FIR on this handle
+    double ms[BLAH2HIP_CK_COUNT];
+    uint32_t nl[BLAH2HIP_CK_COUNT];
+    CHIP(h->blk->timer.collect(ms, nl));
+    for (int k : {BLAH2HIP_CK_CORR, BLAH2HIP_CK_REDUCE, BLAH2HIP_CK_SOLVE}) { ms_total[k] += ms[k]; launches[k] += nl[k]; }
   }
   return BLAH2HIP_OK;
 }
@@ -2196,11 +2557,12 @@ int blah2hip_clutter_process_dev_fmt(blah2hip_clutter_t h, int fmt, const void *
 #endif
   CHIP(hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream;
-  int32_t *ok = d_ok ? d_ok : h->d_ok;
+  int32_t *ok = d_ok ? d_ok : (h->blk ? h->blk->d_ok : h->d_ok);
   // in-place operation (FMT_C32, d_y_out == d_y) is safe: every output sample is read (as y) by the one
   // thread that writes it, and x is never written
   const int64_t cs = (int64_t)cpi_stride, os = (int64_t)out_stride;
   cf *yo = (cf *)d_y_out;
+  if (h->blk) return process_blocks(h, fmt, d_x, d_y, n_cpi, cs, yo, os, ok, st); // d_ok: [n_cpi][n_blocks]
   if (h->subCorr) {
     if (fmt == BLAH2HIP_FMT_I8) CFAIL(BLAH2HIP_ERR_UNSUPPORTED, "a long filter (more than 4081 taps) takes fp32 planes only, not BLAH2HIP_FMT_I8");
     if (fmt != BLAH2HIP_FMT_C32) CFAIL(BLAH2HIP_ERR_UNSUPPORTED, "a long filter (more than 4081 taps) takes fp32 planes only");
@@ -2238,8 +2600,9 @@ int blah2hip_clutter_estimate_dev_fmt(blah2hip_clutter_t h, int fmt, const void 
   if (n_cpi > 1 && cpi_stride < h->N) CFAIL(BLAH2HIP_ERR_INVALID, "cpi_stride < nSamples");
   CHIP(hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream;
-  int32_t *ok = d_ok ? d_ok : h->d_ok;
+  int32_t *ok = d_ok ? d_ok : (h->blk ? h->blk->d_ok : h->d_ok);
   const int64_t cs = (int64_t)cpi_stride;
+  if (h->blk) return process_blocks(h, fmt, d_x, d_y, n_cpi, cs, nullptr, 0, ok, st);
   if (h->subCorr) {
     if (fmt == BLAH2HIP_FMT_I8) CFAIL(BLAH2HIP_ERR_UNSUPPORTED, "a long filter (more than 4081 taps) takes fp32 planes only, not BLAH2HIP_FMT_I8");
     if (fmt != BLAH2HIP_FMT_C32) CFAIL(BLAH2HIP_ERR_UNSUPPORTED, "a long filter (more than 4081 taps) takes fp32 planes only");
@@ -2271,6 +2634,7 @@ int blah2hip_clutter_process_multi_dev_fmt(blah2hip_clutter_t h, int fmt, const 
                                            int32_t *d_ok, void *stream)
 {
   if (!h || !d_x || !d_y) CFAIL(BLAH2HIP_ERR_INVALID, "NULL argument");
+  if (h->blk) CFAIL(BLAH2HIP_ERR_UNSUPPORTED, "taps per block (n_blocks > 1) have no form for several surveillance channels");
   if (fmt == BLAH2HIP_FMT_I16)
     CFAIL(BLAH2HIP_ERR_UNSUPPORTED, "BLAH2HIP_FMT_I16 carries one surveillance channel in the reference's words: several channels need planes of their own");
   if (fmt != BLAH2HIP_FMT_C32 && fmt != BLAH2HIP_FMT_I8)
@@ -2324,6 +2688,7 @@ int blah2hip_clutter_process_multi_dev_fmt(blah2hip_clutter_t h, int fmt, const 
 int blah2hip_clutter_taps_dev(blah2hip_clutter_t h, const float **d_w, uint32_t *n_bins, int32_t *delay_min)
 {
   if (!h) CFAIL(BLAH2HIP_ERR_INVALID, "NULL handle");
+  if (h->blk) return blah2hip_clutter_taps_dev(h->blk, d_w, n_bins, delay_min); // [n_cpi n_blocks][n_bins]
   if (d_w) *d_w = reinterpret_cast<const float *>(h->lastSurv ? h->d_wM : h->d_w);
   if (n_bins) *n_bins = (uint32_t)h->nBins;
   if (delay_min) *delay_min = h->delayMin;
@@ -2351,11 +2716,14 @@ int blah2hip_clutter_process_c32(blah2hip_clutter_t h, const float *x, const flo
   cf *dx = h->d_stage, *dy = dx + plane, *dout = dy + plane;
   CHIP(hipMemcpyAsync(dx, x, plane * sizeof(cf), hipMemcpyHostToDevice, h->stream));
   CHIP(hipMemcpyAsync(dy, y, plane * sizeof(cf), hipMemcpyHostToDevice, h->stream));
-  int rc = blah2hip_clutter_process_dev(h, dx, dy, 1, plane, dout, h->d_ok, h->stream);
+  int32_t *dok = h->blk ? h->blk->d_ok : h->d_ok;
+  int rc = blah2hip_clutter_process_dev(h, dx, dy, 1, plane, dout, dok, h->stream);
   if (rc) return rc;
-  int32_t okv = 0;
-  CHIP(hipMemcpyAsync(&okv, h->d_ok, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  std::vector<int32_t> oks(h->nBlocks, 0);
+  CHIP(hipMemcpyAsync(oks.data(), dok, oks.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
   CHIP(hipStreamSynchronize(h->stream));
+  int32_t okv = 1; // the AND over the blocks (one flag without blocks)
+  for (int32_t v : oks) okv = okv && v;
   *ok = okv;
   if (okv && y_out) CHIP(hipMemcpy(y_out, dout, plane * sizeof(cf), hipMemcpyDeviceToHost));
   return BLAH2HIP_OK;

@@ -8,14 +8,14 @@
 #include <stdexcept>
 #include <string>
 
-WienerHopf::WienerHopf(int32_t delayMin, int32_t delayMax, uint32_t _nSamples) : nSamples(_nSamples)
+WienerHopf::WienerHopf(int32_t delayMin, int32_t delayMax, uint32_t _nSamples, uint32_t _nBlocks) : nSamples(_nSamples), nBlocks(_nBlocks)
 {
-  if (blah2hip_clutter_create(delayMin, delayMax, _nSamples, Ambiguity::default_device(), 1, &engine) != BLAH2HIP_OK)
+  if (blah2hip_clutter_create_ex(delayMin, delayMax, _nSamples, _nBlocks, Ambiguity::default_device(), 1, &engine) != BLAH2HIP_OK)
     throw std::runtime_error(std::string("WienerHopf: ") + blah2hip_last_error());
   try { // a constructor that throws runs no destructor: give back what has been acquired
     DeviceContext &dc = DeviceContext::get();
-    dOk = (int32_t *)dc.alloc_device(sizeof(int32_t));
-    hOk = (int32_t *)dc.alloc_pinned(sizeof(int32_t));
+    dOk = (int32_t *)dc.alloc_device(nBlocks * sizeof(int32_t)); // one flag per block
+    hOk = (int32_t *)dc.alloc_pinned(nBlocks * sizeof(int32_t));
   } catch (...) {
     if (dOk) DeviceContext::get().free_device(dOk);
     blah2hip_clutter_destroy(engine);
@@ -43,9 +43,11 @@ bool WienerHopf::process(IqData *x, IqData *y)
   void *dyf = dc.front_buffer(y, nSamples);
   if (blah2hip_clutter_process_dev_fmt(engine, BLAH2HIP_FMT_C32, dx, dy, 1, nSamples, dyf, nSamples, dOk, dc.stream()) != BLAH2HIP_OK)
     throw std::runtime_error(std::string("WienerHopf::process: ") + blah2hip_last_error());
-  dc.d2h(hOk, dOk, sizeof(int32_t));
+  dc.d2h(hOk, dOk, nBlocks * sizeof(int32_t));
   dc.sync();
-  if (!*hOk) {
+  bool ok = true; // every block's matrix positive definite
+  for (uint32_t j = 0; j < nBlocks; j++) ok = ok && hOk[j] != 0;
+  if (!ok) {
     std::cerr << "Chol decomposition failed, skip clutter filter" << std::endl; // WienerHopf.cpp:114
     return false;
   }

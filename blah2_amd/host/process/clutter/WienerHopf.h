@@ -16,7 +16,9 @@ struct blah2hip_clutter_s;
 class WienerHopf
 {
 public:
-  WienerHopf(int32_t delayMin, int32_t delayMax, uint32_t nSamples);
+  // nBlocks > 1: taps per block of nSamples / nBlocks samples, the filter's history carried across the block edges
+  // (blah2hip_clutter_create_ex); process() returns false when any block's normal equations are not positive definite
+  WienerHopf(int32_t delayMin, int32_t delayMax, uint32_t nSamples, uint32_t nBlocks = 1);
   ~WienerHopf();
   WienerHopf(const WienerHopf &) = delete;
   WienerHopf &operator=(const WienerHopf &) = delete;
@@ -25,8 +27,8 @@ public:
 
 private:
   blah2hip_clutter_s *engine = nullptr;
-  uint32_t nSamples;
-  int32_t *dOk = nullptr, *hOk = nullptr; // device flag and its pinned host copy
+  uint32_t nSamples, nBlocks;
+  int32_t *dOk = nullptr, *hOk = nullptr; // device flags (one per block) and their pinned host copy
 };
 
 #endif

@@ -663,6 +663,8 @@ class Ambiguity:
         if wiener_hopf is None:
             check(self._L.blah2hip_amb_set_fir(self._h, None, 0, 0))
         else:
+            if delay_min is None and getattr(wiener_hopf, "blocks", 1) > 1:
+                raise ValueError(_FIR_BLOCKS_REASON)
             if delay_min is not None:
                 wiener_hopf = _FirTaps(wiener_hopf, delay_min)
             p, nb, dm = wiener_hopf.taps_dev()
@@ -676,6 +678,8 @@ class Ambiguity:
         (always one for FMT_I8: the fused kernel has no int8 form, an 8-bit chain runs the two-stage filter).  With
         ``delay_min`` given, ``wiener_hopf`` is the number of taps (or a tensor of taps as for ``set_fir``)."""
         if delay_min is None:
+            if getattr(wiener_hopf, "blocks", 1) > 1:
+                return _FIR_BLOCKS_REASON
             _, nb, dm = wiener_hopf.taps_dev()
         else:
             nb = int(wiener_hopf) if isinstance(wiener_hopf, (int, np.integer)) else _FirTaps(wiener_hopf, delay_min).n_bins
@@ -905,20 +909,30 @@ def dets_to_detection(recs, count, cap_out):
     return Detection(d["delay"], d["doppler"], d["snr"])
 
 
+# the fused kernel (range_fir_kernel) convolves a CPI with ONE tap set
+_FIR_BLOCKS_REASON = "the fused FIR takes one tap set per CPI: a clutter filter with blocks > 1 runs the two-stage chain"
+
+
 class WienerHopf:
     """src/process/clutter/WienerHopf.h:68-78: least-squares clutter canceller.
 
     ``process(x, y)`` returns ``(ok, y_filtered)``; the reference returns the
     bool and replaces the contents of the y FIFO (WienerHopf.cpp:156-160).  When
     the normal equations are not positive definite ``ok`` is False and y is
-    returned unchanged (blah2.cpp:270-273 then skips the CPI)."""
+    returned unchanged (blah2.cpp:270-273 then skips the CPI).
 
-    def __init__(self, delayMin, delayMax, nSamples, device=0, max_batch=1):
+    ``blocks`` > 1: taps per block of ``nSamples / blocks`` samples, the filter's history carried across the block edges
+    (blah2hip_clutter_create_ex).  ``process`` then returns the AND of the blocks' flags; ``d_ok``, ``read_last(v)`` and
+    ``taps_dev`` count virtual CPIs ``v = cpi * blocks + block``, and ``nBins / fft_len / seg_len`` describe the plan of one
+    block.  The range kernel's fused FIR takes one tap set per CPI: ``Ambiguity.set_fir`` refuses such a filter."""
+
+    def __init__(self, delayMin, delayMax, nSamples, device=0, max_batch=1, blocks=1):
         L = _lib.load()
         h = C.c_void_p()
-        check(L.blah2hip_clutter_create(delayMin, delayMax, nSamples, device, max_batch, C.byref(h)))
+        check(L.blah2hip_clutter_create_ex(delayMin, delayMax, nSamples, int(blocks), device, max_batch, C.byref(h)))
         self._h, self._L = h, L
         self.nSamples = nSamples
+        self.blocks = int(blocks)
         self.max_batch = max(1, int(max_batch))
         nb, fl, sl = C.c_uint32(), C.c_uint32(), C.c_uint32()
         check(L.blah2hip_clutter_get_dims(h, C.byref(nb), C.byref(fl), C.byref(sl)))
@@ -1057,7 +1071,7 @@ class WienerHopf:
         return out
 
     def plan_info(self):
-        """The plan the next call runs: {'corr' ('half' / 'window'), 'carry' (the FIR kernel carries the window overlap in
+        """The plan the next call runs: {'corr' ('half' / 'window'; 'direct': blocks shorter than two filter lengths, fp64 lag sums), 'carry' (the FIR kernel carries the window overlap in
         registers), 'chunks' (chunks of 2048 taps of a long filter, else 0)}."""
         out = {}
         for name, what in (("corr", _lib.CLUTTER_INFO_CORR_FORM), ("carry", _lib.CLUTTER_INFO_FIR_CARRY),
@@ -1065,7 +1079,7 @@ class WienerHopf:
             v = C.c_int64(0)
             check(self._L.blah2hip_clutter_get_info(self._h, what, C.byref(v)))
             out[name] = int(v.value)
-        out["corr"] = "half" if out["corr"] == _lib.CLUTTER_CORR_HALF else "window"
+        out["corr"] = {_lib.CLUTTER_CORR_HALF: "half", _lib.CLUTTER_CORR_DIRECT: "direct"}.get(out["corr"], "window")
         out["carry"] = bool(out["carry"])
         return out
 

@@ -655,10 +655,14 @@ class GpuChain:
         nD, nC = self.amb.get_n_doppler_bins(), self.amb.get_n_delay_bins()
         self.wh = None
         self.fused_fir = False
+        # clutter: {blocks: K}: taps per block of n / K samples (the filter's history runs on across the blocks); a CPI
+        # has K flags then, and is skipped when any block's matrix is not positive definite
+        self.clutter_blocks = KB = int(clu_c.get("blocks", 1)) if clu_c.get("enable", False) else 1
         if clu_c.get("enable", False):
-            self.wh = blah2_amd.WienerHopf(clu_c["delayMin"], clu_c["delayMax"], n, device=device, max_batch=B)
+            self.wh = blah2_amd.WienerHopf(clu_c["delayMin"], clu_c["delayMax"], n, device=device, max_batch=B, blocks=KB)
             # the filter's FIR inside the range kernel where one 4096-point transform covers the geometry (range_fir_kernel):
-            # the filtered channel never crosses HBM.  clutter: {fused: false} keeps the two-stage chain.
+            # the filtered channel never crosses HBM.  clutter: {fused: false} keeps the two-stage chain, and so do blocks
+            # (the fused kernel takes one tap set per CPI: fir_fusable gives that reason).
             self.fused_fir = bool(clu_c.get("fused", True)) and self.amb.fir_fusable(self.wh, self._fmt_in()) is None
             if self.fused_fir:
                 self.amb.set_fir(self.wh)
@@ -720,12 +724,12 @@ class GpuChain:
                         torch.empty(self.raw_bytes, dtype=torch.uint8, device=dev),
                 "first": 0,  # the batch's first sample inside its raw bytes (UsrpFile.extent)
                 "d_met": torch.zeros((B, 2), dtype=torch.float64, device=dev),
-                "d_ok": torch.ones(B, dtype=torch.int32, device=dev),
+                "d_ok": torch.ones(B * KB, dtype=torch.int32, device=dev),
                 "d_hits": torch.zeros((B, self.cap, 2), dtype=torch.float64, device=dev),  # blah2hip_hit_t records, 16 bytes
                 "d_cnt": torch.zeros(B, dtype=torch.int32, device=dev),
                 "d_map": torch.zeros((B, nD, nC), dtype=torch.complex64, device=dev),
                 "h_met": torch.zeros((B, 2), dtype=torch.float64).pin_memory(),
-                "h_ok": torch.ones(B, dtype=torch.int32).pin_memory(),
+                "h_ok": torch.ones(B * KB, dtype=torch.int32).pin_memory(),
                 "h_hits": None if on_dev else torch.zeros((B, self.hit_copy, 2), dtype=torch.float64).pin_memory(),
                 # detect="device": blah2hip_det_t records, 32 bytes, as many as the hit list may hold (Centroid only drops)
                 "d_dets": torch.zeros((B, self.cap, 4), dtype=torch.float64, device=dev) if on_dev else None,
@@ -856,7 +860,8 @@ class GpuChain:
             self.copy.wait_event(slot["computed"])
             slot["h_met"][:cnt].copy_(slot["d_met"][:cnt], non_blocking=True)
             if self.wh is not None:
-                slot["h_ok"][:cnt].copy_(slot["d_ok"][:cnt], non_blocking=True)
+                nok = cnt * self.clutter_blocks
+                slot["h_ok"][:nok].copy_(slot["d_ok"][:nok], non_blocking=True)
             if self.cfar is not None:
                 slot["h_cnt"][:cnt].copy_(slot["d_cnt"][:cnt], non_blocking=True)  # (device path: for the capacity check)
                 if self.finisher is not None:
@@ -874,7 +879,8 @@ class GpuChain:
         self.busy_ms += slot["started"].elapsed_time(slot["computed"])
         self.batches_done += 1
         met_h = slot["h_met"].numpy()
-        ok_h = slot["h_ok"].numpy() if self.wh is not None else np.ones(cnt, dtype=np.int32)
+        ok_h = (slot["h_ok"].numpy()[:cnt * self.clutter_blocks].reshape(cnt, self.clutter_blocks).all(axis=1)
+                if self.wh is not None else np.ones(cnt, dtype=bool))
         res = []
         for b in range(cnt):
             if not ok_h[b]:
@@ -1047,6 +1053,9 @@ def main(argv=None):
                     help="where Centroid and Interpolate run when detection.nCentroid is configured: in one kernel on the "
                          "hit lists and maps where they lie (device, the default), or on the host, which then downloads "
                          "every CPI's map")
+    ap.add_argument("--clutter-blocks", type=int, default=None, metavar="B",
+                    help="clutter filter with taps per block: cut each CPI into B equal blocks (overrides process.clutter.blocks "
+                         "of the config; 1 = one tap set per CPI); the chain then runs the two-stage filter")
     ap.add_argument("--connect", action="store_true",
                     help="with --json: send the documents to network.ip:ports.map / ports.detection of the config, "
                          "framed like Socket::sendData, instead of printing them")
@@ -1067,6 +1076,10 @@ def main(argv=None):
     fs = int(y["capture"]["fs"])
     n = int(fs * float(y["process"]["data"]["cpi"]))  # blah2.cpp:142-144
     cfg = dict(y["process"], fs=fs, n_samples=n)
+    if a.clutter_blocks is not None:
+        if a.clutter_blocks < 1:
+            ap.error("--clutter-blocks takes a block count >= 1")
+        cfg["clutter"] = dict(cfg.get("clutter") or {}, blocks=a.clutter_blocks)
     dist = None
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:

@@ -584,6 +584,27 @@ int blah2hip_detect_dev(blah2hip_amb_t h, const void *d_map, const double *d_met
  * of bounds there, WienerHopf.cpp:76-108). */
 int blah2hip_clutter_create(int32_t delay_min, int32_t delay_max, uint32_t n_samples, int device,
                             uint32_t max_batch, blah2hip_clutter_t *out);
+/* Taps per BLOCK of the CPI (the batched filter, ECA-B): the CPI is cut into n_blocks blocks of L = n_samples / n_blocks, the taps
+ * are estimated per block and the filter's history runs on across the block edges.  n_blocks = 1 is blah2hip_clutter_create (the
+ * same code path, the same bits).  With n_blocks > 1, block j of CPI c is VIRTUAL CPI v = c * n_blocks + j:
+ *   estimation:  r_v, b_v, ok_v, w_v are what the filter computes on the L samples x[jL .. (j+1)L), y[jL .. (j+1)L) taken alone
+ *                (shift by delayMin and correlations circular inside the block: a true autocorrelation Toeplitz matrix);
+ *   application: xs[i] = x[(i - delayMin) mod n_samples] over the WHOLE CPI (uint32 arithmetic, xs[m < 0] = 0), and for n in
+ *                block j  y_out[n] = y[n] - sum_k w_v[k] xs[n - k]: the history of block j > 0 is the samples of block j - 1,
+ *                only block 0 sees the zero fill;
+ *   a block with ok_v = 0 passes y through (the dev entry points), the other blocks are still filtered; the host entry points
+ *   return the AND over the blocks in *ok and do not write y_out when it is 0.
+ * The plan (transform length, correlation form, segments, grids; blah2hip_clutter_get_dims, _set_option, _get_info) is made for a
+ * CPI of L samples and a batch of max_batch * n_blocks.  d_ok ([n_cpi * n_blocks]), blah2hip_clutter_read_last,
+ * blah2hip_clutter_taps_dev ([n_cpi * n_blocks][n_bins]), blah2hip_clutter_solve(_dev) and the solve's info count virtual CPIs;
+ * blah2hip_clutter_estimate_dev_fmt leaves the per-block taps.  The FIR reads every window whole: BLAH2HIP_CLUTTER_INFO_FIR_CARRY
+ * reports 0.  d_y_out may alias d_y (FMT_C32).  The timing slots are the same four.
+ * BLAH2HIP_ERR_INVALID: n_blocks == 0, n_samples % n_blocks != 0.  BLAH2HIP_ERR_UNSUPPORTED with n_blocks > 1: L < delay_max -
+ * delay_min (the reference reads out of bounds on such a block), a long filter (more than 4081 taps), and
+ * blah2hip_clutter_process_multi_dev_fmt on such a handle.  The range kernel's fused FIR takes one tap set per CPI: a chain with
+ * blocks runs the two-stage filter. */
+int blah2hip_clutter_create_ex(int32_t delay_min, int32_t delay_max, uint32_t n_samples, uint32_t n_blocks, int device,
+                               uint32_t max_batch, blah2hip_clutter_t *out);
 int blah2hip_clutter_destroy(blah2hip_clutter_t h);
 /* host: y_out = y - w*x (WienerHopf.cpp:156-160); *ok = 0 when the normal
  * equations are not positive definite (the reference returns false and the CPI
@@ -641,6 +662,11 @@ int blah2hip_clutter_process_multi_dev_fmt(blah2hip_clutter_t h, int fmt, const 
 #define BLAH2HIP_CLUTTER_CORR_AUTO 0
 #define BLAH2HIP_CLUTTER_CORR_HALF 1
 #define BLAH2HIP_CLUTTER_CORR_WINDOW 2
+/* reported by BLAH2HIP_CLUTTER_INFO_CORR_FORM only, not an option value: a handle with blocks shorter than two filter lengths
+ * (n_samples / n_blocks < 2 * n_bins) and no forced form sums r and b lag by lag in fp64 -- such a block's matrix is close to a
+ * circulant of the reference's power spectrum, and its condition number (up to 1e6 at n_samples / n_blocks = n_bins) is more
+ * than fp32 partial correlations carry */
+#define BLAH2HIP_CLUTTER_CORR_DIRECT 3
 /* The Toeplitz solve of the normal equations (WienerHopf.cpp:85-122).  SOLVE_FORM: _LOOKAHEAD = blocks of 32 orders on
  * several workgroups per CPI (as many CUs as the launch leaves free; the default), _STEPWISE = the one-workgroup kernel,
  * one barrier per order (SOLVE_K applies to it).  SOLVE_E: indices per lane of the look-ahead form's slices
@@ -676,6 +702,8 @@ int blah2hip_clutter_set_option(blah2hip_clutter_t h, int option, int64_t value)
 #define BLAH2HIP_CLUTTER_INFO_CORR_FORM 6
 #define BLAH2HIP_CLUTTER_INFO_FIR_CARRY 7
 #define BLAH2HIP_CLUTTER_INFO_CHUNKS 8
+/* blocks per CPI (blah2hip_clutter_create_ex), 1 for every other handle */
+#define BLAH2HIP_CLUTTER_INFO_BLOCKS 9
 int blah2hip_clutter_get_info(blah2hip_clutter_t h, int what, int64_t *value);
 /* The filter's Toeplitz solve on its own: n_cpi systems toeplitz(r) w = b given as rb = [n_cpi][2][nBins] complex fp64 (r then b,
  * interleaved re, im; the layout blah2hip_clutter_read_last returns), taps to w ([n_cpi][nBins] complex fp32), ok[c] = 0
