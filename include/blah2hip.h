@@ -725,8 +725,8 @@ int blah2hip_clutter_read_last(blah2hip_clutter_t h, uint32_t cpi, float *w, dou
  * decimation = uint32(n/bandwidth), nSpectrum = n/decimation, nfft = nSpectrum*decimation
  * (SpectrumAnalyser.cpp:16-18); spectrum[k] = FFT_nfft(x)[(k*decimation + nfft/2 + 1) mod nfft]
  * (:33-54).  Output: nSpectrum complex fp64 values (re, im interleaved) per CPI.
- * Fails with ERR_INVALID when n < bandwidth (the reference divides by zero) and
- * ERR_UNSUPPORTED when nSpectrum > 4096. */
+ * Fails with ERR_INVALID when n < bandwidth (the reference divides by zero), when bandwidth <= 0 or max_batch == 0, and
+ * with ERR_UNSUPPORTED when nSpectrum > 2^26 (before anything is allocated). */
 int blah2hip_spectrum_create(uint32_t n_samples, double bandwidth, int device, uint32_t max_batch,
                              blah2hip_spectrum_t *out);
 int blah2hip_spectrum_destroy(blah2hip_spectrum_t h);
@@ -736,7 +736,10 @@ int blah2hip_spectrum_process_c64(blah2hip_spectrum_t h, const double *x, uint32
 int blah2hip_spectrum_process_c32(blah2hip_spectrum_t h, const float *x, uint32_t n, double *spectrum_out);
 /* dev: d_x in format fmt (C32: complex fp32 plane; I16: the interleaved .rspduo
  * buffer, tuner 1 is used; F16: half pairs; I8: the reference plane of int8 pairs), d_out [n_cpi][nSpectrum] complex fp64.
- * Enqueues only. */
+ * cpi_stride is in SAMPLES in every format, not in bytes or words: CPI i starts 8 (C32: one float pair), 8 (I16: the four
+ * int16 words I1 Q1 I2 Q2 of a sample), 4 (F16) or 2 (I8) bytes times i * cpi_stride behind d_x.  It must be >= nfft when
+ * n_cpi > 1 and is not used when n_cpi == 1; only the first nfft samples of a CPI are read.  1 <= n_cpi <= max_batch.
+ * Refusals (ERR_INVALID: n_cpi, cpi_stride, an fmt other than these four) launch nothing.  Enqueues only. */
 int blah2hip_spectrum_process_dev(blah2hip_spectrum_t h, int fmt, const void *d_x, uint32_t n_cpi,
                                   uint64_t cpi_stride, double *d_out, void *stream);
 
