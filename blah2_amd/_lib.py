@@ -20,6 +20,8 @@ KERNEL_NAMES = {K_RANGE: "range", K_DOPPLER: "doppler", K_METRICS: "metrics", K_
                 K_SAT_ROWS: "sat_rows", K_SAT_COLS: "sat_cols", K_ROTATE: "rotate", K_BEAM: "beam", K_COV: "cov",
                 K_BEARING: "bearing"}
 CK_CORR, CK_REDUCE, CK_SOLVE, CK_FIR, CK_COUNT = 0, 1, 2, 3, 4
+NK_NCI, NK_COUNT = 0, 1
+NCI_KERNEL_NAMES = {NK_NCI: "nci"}
 CLUTTER_KERNEL_NAMES = {CK_CORR: "clutter_corr", CK_REDUCE: "clutter_reduce", CK_SOLVE: "clutter_solve",
                         CK_FIR: "clutter_fir"}
 OPT_DOPPLER_KERNEL, OPT_RANGE_GRID, OPT_RANGE_KERNEL, OPT_DOPPLER_GRID, OPT_FFT_LEN, OPT_CFAR2D_KERNEL = 1, 2, 3, 4, 5, 6
@@ -28,6 +30,9 @@ OPT_HOT_COLUMNS = 8
 OPT_CFAR2D_SEG_ROWS, OPT_CFAR2D_GRID = 9, 10
 OPT_MULTI_SURV_RANGE = 11
 OPT_RANGE_WALK = 12
+OPT_CFAR_LOOKS = 13
+MAX_CFAR_LOOKS = 1024
+MAX_NCI_WINDOW = 16
 WALK_AUTO, WALK_STATIC, WALK_TICKET = 0, 1, 2
 MULTI_AUTO, MULTI_SHARED, MULTI_PER_CHANNEL = 0, 1, 2
 MAX_SURV = 8
@@ -115,6 +120,14 @@ SYMBOLS = {
     "blah2hip_amb_beam_samples_wdev": (C.c_int, [_vp, C.c_int, C.POINTER(_vp), _u32, _u32, C.c_uint64, _vp, _u32, C.POINTER(_vp), C.c_uint64, _vp]),
     "blah2hip_amb_snapshot_dev": (C.c_int, [_vp, _vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _vp]),
     "blah2hip_amb_bearing_dev": (C.c_int, [_vp, _vp, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _dbl, _vp, _u32, _u32, _vp, _vp]),
+    "blah2hip_nci_create": (C.c_int, [_vp, _u32, _u32, _u32, C.POINTER(_vp)]),
+    "blah2hip_nci_destroy": (C.c_int, [_vp]),
+    "blah2hip_nci_reset": (C.c_int, [_vp]),
+    "blah2hip_nci_count": (C.c_int, [_vp, _u32, C.POINTER(_u32), C.POINTER(C.c_uint64)]),
+    "blah2hip_nci_process_dev": (C.c_int, [_vp, _vp, _u32, _vp, _vp, _vp, _u32, C.POINTER(_u32), C.POINTER(C.c_uint64), _vp]),
+    "blah2hip_nci_set_timing": (C.c_int, [_vp, C.c_int]),
+    "blah2hip_nci_get_timing": (C.c_int, [_vp, _vp, _vp]),
+    "blah2hip_cfar_alpha": (C.c_int, [_dbl, _u32, _u32, _vp]),
     "blah2hip_cfar1d_dev": (C.c_int, [_vp, _vp, _vp, _u32, _dbl, _i32, _i32, _i32, _dbl, _vp, _u32, _vp, _vp]),
     "blah2hip_cfar1d_prepare": (C.c_int, [_vp, _dbl, _i32]),
     "blah2hip_cfar2d_prepare": (C.c_int, [_vp, _dbl, _i32, _i32, _i32, _i32]),

@@ -53,6 +53,7 @@ struct blah2hip_amb_s {
   int cfar2dGridForce = 0;          // BLAH2HIP_OPT_CFAR2D_GRID (0 = one workgroup per CU)
   int leakMode = 1;                 // BLAH2HIP_OPT_LEAK_COMPENSATION: 0 off, 1 auto (applied where it can reach 3e-5 of the mean level), 2 always
   int hotMode = 1;                  // BLAH2HIP_OPT_HOT_COLUMNS: 0 off, 1 auto (CPIs long enough for a peak HOT_RATIO above the mean level), 2 always
+  uint32_t cfarLooks = 1;           // BLAH2HIP_OPT_CFAR_LOOKS: looks per cell the detectors' threshold factors are made for (detect.hip)
 
   // ---- device buffers allocated by create (capi.hip) and freed by destroy, which frees every buffer of the handle
   cf *d_tw = nullptr;
@@ -103,8 +104,8 @@ struct blah2hip_amb_s {
   double lastLeakMax = 0.0;         // BLAH2HIP_INFO_LEAK_MAX_E12: the largest |g| of the calibration the last call ran under
 
   // ---- written by detect.hip; bearingGridLast by array.hip
-  struct AlphaTable { double pfa; size_t n; double *d; bool pinned; }; // pinned: handed out by *_prepare, never evicted
-  std::vector<AlphaTable> alphaTables; // CFAR threshold factors, one per (pfa, size) seen
+  struct AlphaTable { double pfa; uint32_t looks; size_t n; double *d; bool pinned; }; // pinned: handed out by *_prepare, never evicted
+  std::vector<AlphaTable> alphaTables; // CFAR threshold factors, one per (pfa, looks, size) seen
   double *d_sat = nullptr;          // 2-D CFAR summed-area table [max_batch][nD+1][nDelay+1], allocated at its first use
   blah2hip_hit_t *d_hits = nullptr; // the *_process calls' hit list, grown to the map's cell count
   uint32_t hitCap = 0;

@@ -1138,6 +1138,10 @@ int blah2hip_amb_set_option(blah2hip_amb_t h, int option, int64_t value)
       return fail(BLAH2HIP_ERR_INVALID, "multi-channel range path: BLAH2HIP_MULTI_AUTO, _SHARED or _PER_CHANNEL");
     h->multiMode = (int)value;
     return BLAH2HIP_OK;
+  case BLAH2HIP_OPT_CFAR_LOOKS:
+    if (value < 1 || value > BLAH2HIP_MAX_CFAR_LOOKS) return fail(BLAH2HIP_ERR_INVALID, "CFAR looks outside [1, BLAH2HIP_MAX_CFAR_LOOKS]");
+    h->cfarLooks = (uint32_t)value;
+    return BLAH2HIP_OK;
   default: return fail(BLAH2HIP_ERR_INVALID, "unknown option");
   }
 }

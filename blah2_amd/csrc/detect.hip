@@ -5,6 +5,7 @@
 #include "detect_kernels.hpp"
 
 #include <cmath>
+#include <thread>
 
 using namespace blah2;
 
@@ -17,12 +18,45 @@ namespace {
 // refused while `st` is being captured into a graph -- *_prepare is the call for that.  A table *_prepare has handed out
 // lives as long as the handle (`pin`): a graph captured afterwards has its address baked in, and no synchronisation
 // at eviction time protects a later replay.  Only unpinned tables are evicted.
+// The looks per cell are the handle's BLAH2HIP_OPT_CFAR_LOOKS at the time of the call and part of the key; one look is the
+// expression above, more go through blah2hip_cfar_alpha's bisection (below).
 constexpr size_t ALPHA_TABLES_MAX = 8;
+
+// Pfa(t) of a cell that is the sum of L looks against the mean of n training cells of L looks each, threshold factor
+// alpha = n t, m = n L: sum_{k < L} C(m + k - 1, k) t^k / (1 + t)^(m + k), term by term in the log domain (the first term
+// alone underflows for large m, and lgamma's absolute error at m ~ 1e5 would show in the result)
+double pfa_of_looks(double t, double m, uint32_t L)
+{
+  const double lt = std::log(t), l1 = std::log1p(t);
+  double lg = -m * l1, s = std::exp(lg);
+  for (uint32_t k = 1; k < L; k++) {
+    lg += std::log((m + (double)k - 1.0) / (double)k) + lt - l1;
+    s += std::exp(lg);
+  }
+  return s;
+}
+
+// alpha[n] for L > 1 looks: Pfa(t) = pfa by bisection in fp64 until the interval no longer splits; the upper end is returned
+double alpha_of_looks(double pfa, uint32_t n, uint32_t L)
+{
+  const double m = (double)n * (double)L;
+  double lo = 0.0, hi = 1.0;
+  while (pfa_of_looks(hi, m, L) > pfa) hi *= 2.0;
+  for (;;) {
+    const double mid = 0.5 * (lo + hi);
+    if (mid == lo || mid == hi) break;
+    if (pfa_of_looks(mid, m, L) > pfa) lo = mid;
+    else hi = mid;
+  }
+  return (double)n * hi;
+}
+
 int alpha_table(blah2hip_amb_s *h, double pfa, size_t maxN, const double **out, hipStream_t st = nullptr, bool pin = false)
 {
   auto &T = h->alphaTables;
+  const uint32_t looks = h->cfarLooks;
   for (size_t i = 0; i < T.size(); i++)
-    if (T[i].pfa == pfa && T[i].n >= maxN) {
+    if (T[i].pfa == pfa && T[i].looks == looks && T[i].n >= maxN) {
       blah2hip_amb_s::AlphaTable t = T[i];
       t.pinned = t.pinned || pin;
       T.erase(T.begin() + (long)i);
@@ -37,8 +71,8 @@ int alpha_table(blah2hip_amb_s *h, double pfa, size_t maxN, const double **out, 
                                         "blah2hip_cfar2d_prepare before capturing the stream");
   }
   std::vector<double> alpha(maxN + 1);
-  alpha[0] = std::nan("");
-  for (size_t n = 1; n <= maxN; n++) alpha[n] = (double)n * (pow(pfa, -1.0 / (double)n) - 1);
+  int rc;
+  if ((rc = blah2hip_cfar_alpha(pfa, looks, (uint32_t)maxN, alpha.data()))) return rc;
   size_t unpinned = 0;
   for (const auto &e : T) unpinned += e.pinned ? 0 : 1;
   if (unpinned >= ALPHA_TABLES_MAX) {
@@ -50,7 +84,7 @@ int alpha_table(blah2hip_amb_s *h, double pfa, size_t maxN, const double **out, 
         break;
       }
   }
-  blah2hip_amb_s::AlphaTable t{pfa, maxN, nullptr, pin};
+  blah2hip_amb_s::AlphaTable t{pfa, looks, maxN, nullptr, pin};
   HIPCHK(hipMalloc(&t.d, (maxN + 1) * sizeof(double)));
   hipError_t e = hipMemcpy(t.d, alpha.data(), (maxN + 1) * sizeof(double), hipMemcpyHostToDevice);
   if (e != hipSuccess) { (void)hipFree(t.d); return fail(BLAH2HIP_ERR_HIP, std::string("alpha table upload: ") + hipGetErrorString(e)); }
@@ -183,6 +217,36 @@ int hits_to_host(blah2hip_amb_s *h, double *delay, double *doppler, double *snr,
 extern "C" {
 
 // ------------------------------------------------------------------- CFAR --
+// Host arithmetic only.  One look: the reference's expression with the same libm pow, whatever pfa is.  More looks: a
+// bisection per n of about 55 evaluations of `looks` terms each; long tables (a 2-D window at hundreds of looks) are cut
+// into interleaved slices for up to eight threads -- every entry is computed on its own, so the slices do not change it.
+int blah2hip_cfar_alpha(double pfa, uint32_t looks, uint32_t max_n, double *alpha)
+{
+  if (!alpha) return fail(BLAH2HIP_ERR_INVALID, "NULL table");
+  if (looks == 0 || looks > BLAH2HIP_MAX_CFAR_LOOKS) return fail(BLAH2HIP_ERR_INVALID, "looks outside [1, BLAH2HIP_MAX_CFAR_LOOKS]");
+  if (looks > 1 && !(pfa > 0.0 && pfa < 1.0)) return fail(BLAH2HIP_ERR_INVALID, "pfa outside (0, 1) with more than one look");
+  alpha[0] = std::nan("");
+  if (looks == 1) {
+    for (size_t n = 1; n <= max_n; n++) alpha[n] = (double)n * (pow(pfa, -1.0 / (double)n) - 1);
+    return BLAH2HIP_OK;
+  }
+  const uint64_t terms = (uint64_t)max_n * looks;
+  const uint32_t nThreads = terms < 50000 ? 1u : std::min(8u, std::max(1u, std::thread::hardware_concurrency()));
+  auto slice = [=](uint32_t first) {
+    for (uint64_t n = 1 + first; n <= max_n; n += nThreads) alpha[n] = alpha_of_looks(pfa, (uint32_t)n, looks);
+  };
+  std::vector<std::thread> pool;
+  uint32_t started = 1;
+  try {
+    for (; started < nThreads; started++) pool.emplace_back(slice, started);
+  } catch (const std::exception &) { // no thread to be had: the slices that are left run here
+  }
+  slice(0);
+  for (uint32_t t = started; t < nThreads; t++) slice(t);
+  for (auto &t : pool) t.join();
+  return BLAH2HIP_OK;
+}
+
 int blah2hip_cfar1d_dev(blah2hip_amb_t h, const void *d_map, const double *d_metrics,
                         uint32_t n_cpi, double pfa, int32_t n_guard, int32_t n_train,
                         int32_t min_delay, double min_doppler, blah2hip_hit_t *d_hits, uint32_t cap,

@@ -228,6 +228,96 @@ def bearing_degrees(index, offset, angles_deg, wrap=False):
     return deg if deg.ndim else float(deg)
 
 
+def cfar_pfa(alpha, n, looks=1):
+    """The false-alarm probability of the threshold ``alpha * (tot / n)`` over ``n`` training cells when every cell is the
+    sum of ``looks`` looks of noise (the cell under test Gamma(L), the training sum Gamma(nL)): with ``t = alpha / n`` and
+    ``m = n L``, ``sum_{k<L} C(m+k-1, k) t^k / (1+t)^(m+k)``, term by term in the log domain as blah2hip_cfar_alpha
+    evaluates it.  Pure Python."""
+    import math
+    L, m, t = int(looks), int(n) * int(looks), float(alpha) / int(n)
+    lt, l1 = math.log(t), math.log1p(t)
+    lg = -m * l1
+    s = math.exp(lg)
+    for k in range(1, L):
+        lg += math.log((m + k - 1) / k) + lt - l1
+        s += math.exp(lg)
+    return s
+
+
+def cfar_alpha(pfa, looks=1, max_n=1):
+    """blah2hip_cfar_alpha restated in pure Python: the detectors' threshold factors ``alpha[n]``, ``n = 1 .. max_n``
+    (``alpha[0]`` is NaN), for cells that are sums of ``looks`` looks.  One look: ``n (pfa^(-1/n) - 1)``.  More:
+    ``cfar_pfa(alpha, n, looks) = pfa`` by bisection until the interval no longer splits (its upper end).  float64
+    ``[max_n + 1]``."""
+    import math
+    pfa, L = float(pfa), int(looks)
+    if not 1 <= L <= _lib.MAX_CFAR_LOOKS:
+        raise ValueError("looks outside [1, MAX_CFAR_LOOKS]")
+    out = np.full(int(max_n) + 1, np.nan)
+    if L == 1:
+        for n in range(1, int(max_n) + 1):
+            out[n] = n * (math.pow(pfa, -1.0 / n) - 1)
+        return out
+    if not 0.0 < pfa < 1.0:
+        raise ValueError("pfa outside (0, 1) with more than one look")
+    for n in range(1, int(max_n) + 1):
+        lo, hi = 0.0, 1.0
+        while cfar_pfa(n * hi, n, L) > pfa:
+            hi *= 2.0
+        while True:
+            mid = 0.5 * (lo + hi)
+            if mid == lo or mid == hi:
+                break
+            if cfar_pfa(n * mid, n, L) > pfa:
+                lo = mid
+            else:
+                hi = mid
+        out[n] = n * hi
+    return out
+
+
+def cfar_alpha_table(pfa, looks, max_n):
+    """blah2hip_cfar_alpha itself (host arithmetic of the library, no GPU touched): float64 ``[max_n + 1]``."""
+    out = np.empty(int(max_n) + 1, dtype=np.float64)
+    check(_lib.load().blah2hip_cfar_alpha(float(pfa), int(looks), int(max_n), _ptr(out)))
+    return out
+
+
+def integrate_ends(n_cpi, window, hop=None, start=0):
+    """The CPI counts ``g`` at which a window of ``window`` CPIs ends among the CPIs ``start .. start + n_cpi - 1`` of an
+    integrator with hop ``hop`` (None: 1): every ``g >= window - 1`` with ``(g - (window - 1)) % hop == 0``."""
+    W, H = int(window), int(hop) if hop is not None else 1
+    return [g for g in range(int(start), int(start) + int(n_cpi)) if g >= W - 1 and (g - (W - 1)) % H == 0]
+
+
+def integrate_maps(maps, w=None, window=1, hop=None):
+    """blah2hip_nci_process_dev restated in fp64 NumPy for a fresh integrator.  ``maps``: complex ``[K, n_cpi, nD, nC]``,
+    ``w``: the ``K`` channel weights (None: all 1).  ``p[g] = sum_k w_k |M_k[g]|^2`` and, for every ``g`` of
+    :func:`integrate_ends`, ``sqrt(scale (p[g-W+1] + ... + p[g]))`` with ``scale = 1 / (W sum_k w_k)`` rounded to fp32 as
+    the library rounds it.  Returns float64 ``[n_out, nD, nC]``: the real parts of the output maps (the imaginary parts
+    are zero)."""
+    m = np.asarray(maps).astype(np.complex128)
+    if m.ndim != 4:
+        raise ValueError("maps must be [K, n_cpi, nD, nC]")
+    K, n_cpi = m.shape[:2]
+    W = int(window)
+    wk = np.ones(K, dtype=np.float32) if w is None else np.asarray(w, dtype=np.float32)
+    if wk.shape != (K,):
+        raise ValueError("w must hold one weight per channel")
+    scale = float(np.float32(1.0 / (W * wk.astype(np.float64).sum())))
+    with np.errstate(all="ignore"):
+        p = np.zeros(m.shape[1:])
+        for k in range(K):
+            p = p + float(wk[k]) * (m[k].real ** 2 + m[k].imag ** 2)
+        out = []
+        for g in integrate_ends(n_cpi, W, hop):
+            s = np.zeros(m.shape[2:])
+            for c in range(g - W + 1, g + 1):
+                s = s + p[c]
+            out.append(np.sqrt(scale * s))
+    return np.stack(out) if out else np.zeros((0,) + m.shape[2:])
+
+
 class Map:
     """src/data/Map.h: rows = Doppler, cols = delay.  ``data`` is complex64."""
 
@@ -607,6 +697,12 @@ class Ambiguity:
         mode = {"auto": _lib.MULTI_AUTO, "shared": _lib.MULTI_SHARED, "per_channel": _lib.MULTI_PER_CHANNEL}.get(mode, mode)
         check(self._L.blah2hip_amb_set_option(self._h, _lib.OPT_MULTI_SURV_RANGE, int(mode)))
 
+    def set_cfar_looks(self, looks):
+        """BLAH2HIP_OPT_CFAR_LOOKS: the looks per cell the detectors' threshold factors are made for, 1 (default) for the
+        engine's own maps, ``n_surv * window`` for the maps of a :class:`MapIntegrator` (its ``looks``).  The detector
+        classes set it from their own ``looks`` at every call."""
+        check(self._L.blah2hip_amb_set_option(self._h, _lib.OPT_CFAR_LOOKS, int(looks)))
+
     def read_last(self, cpi=0):
         nD, nC = self.dims.n_doppler_bins, self.dims.n_delay_bins
         out = np.empty((nD, nC), dtype=np.complex64)
@@ -746,12 +842,18 @@ class Ambiguity:
 class CfarDetector1D:
     """src/process/detection/CfarDetector1D.h:46-55."""
 
-    def __init__(self, pfa, nGuard, nTrain, minDelay, minDoppler):
+    def __init__(self, pfa, nGuard, nTrain, minDelay, minDoppler, looks=1):
+        """``looks`` (extension): the looks per cell of the maps this detector runs on -- 1 for the engine's maps,
+        ``MapIntegrator.looks`` for integrated ones; the detector sets the handle's BLAH2HIP_OPT_CFAR_LOOKS to it at
+        every call."""
         for name, v in (("nGuard", nGuard), ("nTrain", nTrain), ("minDelay", minDelay)):
             if not -128 <= int(v) <= 127:  # int8_t in the reference
                 raise ValueError(f"{name} outside int8 range")
+        if not 1 <= int(looks) <= _lib.MAX_CFAR_LOOKS:
+            raise ValueError("looks outside [1, MAX_CFAR_LOOKS]")
         self.pfa, self.nGuard, self.nTrain = float(pfa), int(nGuard), int(nTrain)
         self.minDelay, self.minDoppler = int(minDelay), float(minDoppler)
+        self.looks = int(looks)
 
     def process(self, x: Map) -> Detection:
         """CfarDetector1D::process on ``x.data`` (CfarDetector1D.cpp:23-100).  While ``x`` is still the map the engine holds
@@ -766,10 +868,14 @@ class CfarDetector1D:
         s = np.zeros(cap)
         n = C.c_uint32(0)
         if x.device_copy_is_current():
+            amb.set_cfar_looks(self.looks)
             check(amb._L.blah2hip_cfar1d_process(amb._h, x._cpi_index, self.pfa, self.nGuard, self.nTrain,
                                                  self.minDelay, self.minDoppler, _ptr(d), _ptr(f), _ptr(s),
                                                  cap, C.byref(n)))
         else:
+            if self.looks != 1:
+                raise ValueError("CfarDetector1D.process: a map held by the host runs through blah2hip_cfar1d_map, which is "
+                                 "one-look; run process_dev on the integrated maps on the device")
             L = _lib.load()
             m = np.ascontiguousarray(x.data, dtype=np.complex64)
             dax = np.ascontiguousarray(x.delay, dtype=np.int32)
@@ -784,6 +890,7 @@ class CfarDetector1D:
     def process_dev(self, amb, n_cpi, d_hits, cap, d_count, d_map=None, d_metrics=None, stream=0):
         """Enqueue the detector for n_cpi device-resident maps (None = the engine's internal buffers of the
         last process_dev): hit records into d_hits [n_cpi][cap], counts into d_count [n_cpi]."""
+        amb.set_cfar_looks(self.looks)
         check(amb._L.blah2hip_cfar1d_dev(amb._h, d_map, d_metrics, n_cpi, self.pfa, self.nGuard, self.nTrain,
                                          self.minDelay, self.minDoppler, d_hits, cap, d_count, stream))
 
@@ -809,10 +916,13 @@ class CfarDetector2D:
     SURVEY.md section 8g, and with nGuardDoppler = nTrainDoppler = 0 it returns
     exactly what :class:`CfarDetector1D` returns."""
 
-    def __init__(self, pfa, nGuardDelay, nTrainDelay, nGuardDoppler, nTrainDoppler, minDelay, minDoppler):
+    def __init__(self, pfa, nGuardDelay, nTrainDelay, nGuardDoppler, nTrainDoppler, minDelay, minDoppler, looks=1):
+        if not 1 <= int(looks) <= _lib.MAX_CFAR_LOOKS:
+            raise ValueError("looks outside [1, MAX_CFAR_LOOKS]")
         self.pfa = float(pfa)
         self.p = [int(nGuardDelay), int(nTrainDelay), int(nGuardDoppler), int(nTrainDoppler)]
         self.minDelay, self.minDoppler = int(minDelay), float(minDoppler)
+        self.looks = int(looks)  # as for CfarDetector1D
 
     def process(self, x: Map) -> Detection:
         amb = x._owner
@@ -822,14 +932,122 @@ class CfarDetector2D:
         cap = x.data.size
         d, f, s = np.zeros(cap), np.zeros(cap), np.zeros(cap)
         n = C.c_uint32(0)
+        amb.set_cfar_looks(self.looks)
         check(amb._L.blah2hip_cfar2d_process(amb._h, x._cpi_index, self.pfa, *self.p, self.minDelay,
                                              self.minDoppler, _ptr(d), _ptr(f), _ptr(s), cap, C.byref(n)))
         k = n.value
         return Detection(d[:k].copy(), f[:k].copy(), s[:k].copy())
 
     def process_dev(self, amb, n_cpi, d_hits, cap, d_count, d_map=None, d_metrics=None, stream=0):
+        amb.set_cfar_looks(self.looks)
         check(amb._L.blah2hip_cfar2d_dev(amb._h, d_map, d_metrics, n_cpi, self.pfa, *self.p, self.minDelay,
                                          self.minDoppler, d_hits, cap, d_count, stream))
+
+
+class MapIntegrator:
+    """Non-coherent integration of the maps of ``amb`` over its ``n_surv`` surveillance channels and over a sliding window
+    of ``window`` consecutive CPIs, a window every ``hop`` CPIs (None: 1) -- blah2hip_nci_*.  No reference counterpart.
+    The output maps are ordinary complex maps (RMS level, zero imaginary part) with ``looks`` = ``n_surv * window`` looks
+    per cell: run the detectors on them with ``looks=integrator.looks``.  The CPI counter and the history of the last
+    ``window - 1`` CPIs carry over from call to call; ``close()`` it before its ``amb``."""
+
+    def __init__(self, amb, n_surv=1, window=1, hop=None):
+        h = C.c_void_p()
+        hop = 1 if hop is None else hop
+        check(amb._L.blah2hip_nci_create(amb._h, int(n_surv), int(window), int(hop), C.byref(h)))
+        self._h, self._L, self.amb = h, amb._L, amb
+        self.n_surv, self.window, self.hop = int(n_surv), int(window), int(hop)
+        self.looks = self.n_surv * self.window
+
+    def close(self):
+        if getattr(self, "_h", None):
+            # the integrator reads its ambiguity handle when it is destroyed: once that handle is closed (the wrong order)
+            # the history planes are left to the process rather than freed through a dangling pointer
+            if getattr(self.amb, "_h", None):
+                self._L.blah2hip_nci_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        """Counter 0, history forgotten (host only)."""
+        check(self._L.blah2hip_nci_reset(self._h))
+
+    def set_timing(self, enable=True):
+        """Bracket every launch of the integrator's kernel with an event pair (blah2hip_nci_set_timing)."""
+        check(self._L.blah2hip_nci_set_timing(self._h, 1 if enable else 0))
+
+    def get_timing(self):
+        """``{"nci": (ms, launches)}`` since the last call (synchronises); the metrics kernel behind it counts under the
+        ambiguity handle's ``"metrics"``."""
+        ms = np.zeros(_lib.NK_COUNT, dtype=np.float64)
+        cnt = np.zeros(_lib.NK_COUNT, dtype=np.uint32)
+        check(self._L.blah2hip_nci_get_timing(self._h, _ptr(ms), _ptr(cnt)))
+        return {name: (float(ms[k]), int(cnt[k])) for k, name in _lib.NCI_KERNEL_NAMES.items()}
+
+    def count(self, n_cpi):
+        """``(n_out, first_end)`` the next ``process_dev`` of ``n_cpi`` CPIs will report; changes nothing."""
+        n, f = C.c_uint32(0), C.c_uint64(0)
+        check(self._L.blah2hip_nci_count(self._h, int(n_cpi), C.byref(n), C.byref(f)))
+        return n.value, f.value
+
+    def process_dev(self, d_map, n_cpi, d_out_map, d_out_metrics, out_cap, w=None, stream=0):
+        """Enqueue the next ``n_cpi`` CPIs (blah2hip_nci_process_dev; raw pointers/ints): ``d_map`` the
+        ``[n_surv][n_cpi]`` maps (None: the handle's own), ``w`` the host's channel weights or None, outputs
+        ``d_out_map [n_out]`` maps and ``d_out_metrics [n_out][2]`` with room for ``out_cap`` maps.  Returns
+        ``(n_out, first_end)``: output i is the window that ends at CPI count ``first_end + i * hop``."""
+        wp = None
+        if w is not None:
+            w = np.ascontiguousarray(w, dtype=np.float32)
+            if w.shape != (self.n_surv,):
+                raise ValueError("w must hold one weight per channel")
+            wp = _ptr(w)
+        n, f = C.c_uint32(0), C.c_uint64(0)
+        check(self._L.blah2hip_nci_process_dev(self._h, d_map, int(n_cpi), wp, d_out_map, d_out_metrics, int(out_cap),
+                                               C.byref(n), C.byref(f), stream))
+        return n.value, f.value
+
+    def process(self, maps, w=None):
+        """Host arrays: complex64 ``maps [n_surv, n_cpi, n_doppler, n_delay]`` (``[n_cpi, ...]`` for one channel), the next
+        ``n_cpi`` CPIs; uploads, runs ``process_dev`` and returns one :class:`Map` per window that ended, with its metrics
+        and ``cpi_index`` = the CPI count at which it ended."""
+        amb = self.amb
+        nD, nC = amb.dims.n_doppler_bins, amb.dims.n_delay_bins
+        data = np.ascontiguousarray(maps, dtype=np.complex64)
+        if data.ndim == 3:
+            data = data[None]
+        if data.ndim != 4 or data.shape[0] != self.n_surv or data.shape[2:] != (nD, nC):
+            raise ValueError(f"maps must be [{self.n_surv}, n_cpi, {nD}, {nC}]")
+        n_cpi = data.shape[1]
+        n_out, _ = self.count(n_cpi)
+        out = np.empty((n_out, nD, nC), dtype=np.complex64)
+        met = np.zeros((n_out, 2), dtype=np.float64)
+        L, ctx = self._L, C.c_void_p()
+        check(L.blah2hip_ctx_create(amb.device, C.byref(ctx)))
+        bufs = []
+        try:
+            for nbytes in (data.nbytes, max(out.nbytes, 16), max(met.nbytes, 16)):
+                p = C.c_void_p()
+                check(L.blah2hip_ctx_malloc(ctx, nbytes, C.byref(p)))
+                bufs.append(p)
+            d_in, d_out, d_met = bufs
+            check(L.blah2hip_ctx_h2d(ctx, d_in, _ptr(data), data.nbytes))
+            n_out, first = self.process_dev(d_in, n_cpi, d_out, d_met, n_out, w, L.blah2hip_ctx_stream(ctx))
+            if n_out:
+                check(L.blah2hip_ctx_d2h(ctx, _ptr(out), d_out, out.nbytes))
+                check(L.blah2hip_ctx_d2h(ctx, _ptr(met), d_met, met.nbytes))
+            check(L.blah2hip_ctx_sync(ctx))
+        finally:
+            for p in bufs:
+                L.blah2hip_ctx_free(ctx, p)
+            L.blah2hip_ctx_destroy(ctx)
+        # (an integrated map is not the engine's device copy: no owner)
+        return [Map(None, out[i], amb.delay.copy(), amb.doppler.copy(), float(met[i, 0]), float(met[i, 1]), first + i * self.hop)
+                for i in range(n_out)]
 
 
 class Centroid:

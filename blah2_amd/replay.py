@@ -455,6 +455,8 @@ def replay(capture: _RawCapture, processor, batch: int = 1, dist=None, limit: Op
     rank = dist.get_rank() if dist is not None else 0
     world = dist.get_world_size() if dist is not None else 1
     n = capture.n_cpis if limit is None else min(limit, capture.n_cpis)
+    if hasattr(processor, "shard_check"):
+        processor.shard_check(world)  # (an integrating chain: windows inside a batch, or one rank)
     mine = shard_batches(n, batch, rank, world)
     n_batches = n_batches_hint(n, batch)
     n_rounds = -(-n_batches // world) if n_batches else 0
@@ -588,7 +590,16 @@ class GpuChain:
     slots, like the filtered channel) and the FMT_C32 chain runs on those.  "cs8" replays a :class:`Cs8Pair`: a slot holds
     the batch's x bytes, then its y bytes, in one upload, and the kernels read the int8 pairs as they are (FMT_I8 into the
     filter and the range kernel, FMT_I8X_C32Y into the range kernel behind the filter): no conversion kernel, no fp32
-    planes.  The filter of a cs8 chain is always the two-stage one (the fused kernel has no int8 form)."""
+    planes.  The filter of a cs8 chain is always the two-stage one (the fused kernel has no int8 form).
+
+    ``cfg["integrate"] = {"window": W, "hop": H}`` (H optional, 1) puts a :class:`blah2_amd.MapIntegrator` behind the
+    ambiguity stage on the compute stream: the detector (made for ``looks = W``) and the finisher run on the maps of the
+    windows that end in the batch, and the result of CPI g is that window's -- its metrics, detections and (``want_map``)
+    map, with ``"window": W`` -- or ``{"integrating": True}`` where no window ends at g.  A window that holds a skipped
+    CPI is itself ``{"skipped": True}``.  The CPI count and the history run on from batch to batch; :meth:`run_batches`
+    starts a capture at count 0, :meth:`reset_integrator` does so for a caller of ``chain(iq)``.  Ranks that take the
+    batches round-robin see no consecutive CPIs across a batch's end: :meth:`shard_check` then asks for H == W and a batch
+    of whole windows, and every batch starts at count 0.  Without the key the chain is the one described above."""
 
     def __init__(self, cfg: dict, device: int = 0, batch: int = 1, want_map: bool = False, depth: int = 3,
                  reader_threads: int = 4, hit_copy: int = 4096, read_mode: str = "memmove", numa: bool = True,
@@ -667,9 +678,19 @@ class GpuChain:
             if self.fused_fir:
                 self.amb.set_fir(self.wh)
         self.cfar = self.centroid = self.interp = None
+        self.nci = None
+        looks = {}
+        if cfg.get("integrate"):
+            int_c = cfg["integrate"]
+            W, H = int(int_c["window"]), int(int_c.get("hop") or 1)
+            self.nci = blah2_amd.MapIntegrator(self.amb, 1, W, H)  # (refuses a window outside [1, 16] or a hop of 0)
+            self._per_batch = False  # shard_check: every batch starts at count 0
+            self._g = 0              # CPIs the integrator has been handed since its last reset
+            self._ok_tail = []       # filter flags of the last W - 1 CPIs collected
+            looks = {"looks": self.nci.looks}
         if det_c.get("enable", False):
             self.cfar = blah2_amd.CfarDetector1D(det_c["pfa"], det_c["nGuard"], det_c["nTrain"], det_c["minDelay"],
-                                                 det_c["minDoppler"])
+                                                 det_c["minDoppler"], **looks)
             if "nCentroid" in det_c:  # blah2.cpp:176-181
                 self.centroid = blah2_amd.Centroid(det_c["nCentroid"], det_c["nCentroid"], 1 / (n / self.fs))
                 self.interp = blah2_amd.Interpolate(True, True)
@@ -743,6 +764,10 @@ class GpuChain:
                 # time the GPU spent computing (`busy_ms`), the rest of the wall clock it waited for the host link
                 "started": torch.cuda.Event(enable_timing=True), "computed": torch.cuda.Event(enable_timing=True),
             }
+            if self.nci is not None:  # the integrated maps and their metrics: what the detector and the download read
+                s["d_imap"] = torch.zeros((B, nD, nC), dtype=torch.complex64, device=dev)
+                s["d_imet"] = torch.zeros((B, 2), dtype=torch.float64, device=dev)
+                s["nci"] = (0, 0, 0)  # (count before the batch, windows that end in it, count at which the first ends)
             self.slots.append(s)
 
     def _fmt_in(self):
@@ -848,29 +873,38 @@ class GpuChain:
                 self.wh.process_dev_fmt(fmt, x, y, cnt, n, self.yf.data_ptr(), n, slot["d_ok"].data_ptr(), st)
                 amb.process_dev(fmt_yf, x, self.yf.data_ptr(), cnt, n, slot["d_map"].data_ptr(),
                                 slot["d_met"].data_ptr(), st)
-            if self.cfar is not None:
-                self.cfar.process_dev(amb, cnt, slot["d_hits"].data_ptr(), self.cap, slot["d_cnt"].data_ptr(),
-                                      slot["d_map"].data_ptr(), slot["d_met"].data_ptr(), st)
+            n_maps, maps, mets = cnt, slot["d_map"], slot["d_met"]  # what the detector and the download read
+            if self.nci is not None:
+                if self._per_batch:
+                    self.reset_integrator()
+                n_maps, first = self.nci.process_dev(maps.data_ptr(), cnt, slot["d_imap"].data_ptr(), slot["d_imet"].data_ptr(),
+                                                     self.batch, None, st)
+                slot["nci"] = (self._g, n_maps, first)
+                self._g += cnt
+                maps, mets = slot["d_imap"], slot["d_imet"]
+            if self.cfar is not None and n_maps:
+                self.cfar.process_dev(amb, n_maps, slot["d_hits"].data_ptr(), self.cap, slot["d_cnt"].data_ptr(),
+                                      maps.data_ptr(), mets.data_ptr(), st)
                 if self.finisher is not None:
-                    self.finisher.process_dev(amb, cnt, slot["d_hits"].data_ptr(), self.cap, slot["d_cnt"].data_ptr(),
+                    self.finisher.process_dev(amb, n_maps, slot["d_hits"].data_ptr(), self.cap, slot["d_cnt"].data_ptr(),
                                               slot["d_dets"].data_ptr(), self.cap, slot["d_dcnt"].data_ptr(),
-                                              slot["d_map"].data_ptr(), slot["d_met"].data_ptr(), st)
+                                              maps.data_ptr(), mets.data_ptr(), st)
             slot["computed"].record(self.compute)
         with torch.cuda.stream(self.copy):
             self.copy.wait_event(slot["computed"])
-            slot["h_met"][:cnt].copy_(slot["d_met"][:cnt], non_blocking=True)
+            slot["h_met"][:n_maps].copy_(mets[:n_maps], non_blocking=True)
             if self.wh is not None:
                 nok = cnt * self.clutter_blocks
                 slot["h_ok"][:nok].copy_(slot["d_ok"][:nok], non_blocking=True)
             if self.cfar is not None:
-                slot["h_cnt"][:cnt].copy_(slot["d_cnt"][:cnt], non_blocking=True)  # (device path: for the capacity check)
+                slot["h_cnt"][:n_maps].copy_(slot["d_cnt"][:n_maps], non_blocking=True)  # (device path: for the capacity check)
                 if self.finisher is not None:
-                    slot["h_dcnt"][:cnt].copy_(slot["d_dcnt"][:cnt], non_blocking=True)
-                    slot["h_dets"][:cnt].copy_(slot["d_dets"][:cnt, :self.hit_copy], non_blocking=True)
+                    slot["h_dcnt"][:n_maps].copy_(slot["d_dcnt"][:n_maps], non_blocking=True)
+                    slot["h_dets"][:n_maps].copy_(slot["d_dets"][:n_maps, :self.hit_copy], non_blocking=True)
                 else:
-                    slot["h_hits"][:cnt].copy_(slot["d_hits"][:cnt, :self.hit_copy], non_blocking=True)
+                    slot["h_hits"][:n_maps].copy_(slot["d_hits"][:n_maps, :self.hit_copy], non_blocking=True)
             if self.need_map:
-                slot["h_map"][:cnt].copy_(slot["d_map"][:cnt], non_blocking=True)
+                slot["h_map"][:n_maps].copy_(maps[:n_maps], non_blocking=True)
             slot["downloaded"].record(self.copy)
 
     def _collect(self, slot: dict, k0: int, cnt: int) -> List[dict]:
@@ -882,11 +916,34 @@ class GpuChain:
         ok_h = (slot["h_ok"].numpy()[:cnt * self.clutter_blocks].reshape(cnt, self.clutter_blocks).all(axis=1)
                 if self.wh is not None else np.ones(cnt, dtype=bool))
         res = []
-        for b in range(cnt):
-            if not ok_h[b]:
+        # integrating: CPI c of the batch has a result where a window ends at it, the window's map is number `at` of the
+        # slot's buffers, and the window is skipped when the filter failed on any of its CPIs
+        at_of = skip_of = None
+        if self.nci is not None:
+            g0, n_out, first = slot["nci"]
+            W, H = self.nci.window, self.nci.hop
+            if self._per_batch:
+                self._ok_tail = []
+            flags = self._ok_tail + [bool(v) for v in ok_h]  # flags[-cnt + c] is CPI c's
+            at_of = {first - g0 + i * H: i for i in range(n_out)}
+            skip_of = {c: not all(flags[len(flags) - cnt + c - W + 1:len(flags) - cnt + c + 1]) for c in at_of}
+            self._ok_tail = flags[len(flags) - (W - 1):] if W > 1 else []
+        for c in range(cnt):
+            b = c
+            if at_of is not None:
+                if c not in at_of:
+                    res.append({"integrating": True, "cpi": k0 + c})
+                    continue
+                if skip_of[c]:
+                    res.append({"skipped": True, "cpi": k0 + c})
+                    continue
+                b = at_of[c]
+            elif not ok_h[b]:
                 res.append({"skipped": True, "cpi": k0 + b})
                 continue
-            r = {"noisePower": float(met_h[b, 0]), "maxPower": float(met_h[b, 1]), "cpi": k0 + b}
+            r = {"noisePower": float(met_h[b, 0]), "maxPower": float(met_h[b, 1]), "cpi": k0 + c}
+            if at_of is not None:
+                r["window"] = self.nci.window
             if self.cfar is not None:
                 k = int(slot["h_cnt"][b])
                 if k > self.cap:
@@ -926,6 +983,7 @@ class GpuChain:
         threads) the moment the previous read has ended, before this thread enqueues, synchronises, converts and yields:
         the reader threads never wait for Python.  A capture of another layout than the chain's is a ValueError."""
         self._check_capture(capture)
+        self.reset_integrator()
         batches = list(batches)
         D, n = self.depth, len(batches)
         reads = {}
@@ -974,6 +1032,25 @@ class GpuChain:
             r.pop("cpi", None)
         return out
 
+    def reset_integrator(self):
+        """The integrator (``cfg["integrate"]``) back at CPI count 0, its history forgotten; nothing without one.  Call it
+        with no batch in flight."""
+        if self.nci is not None:
+            self.nci.reset()
+            self._g, self._ok_tail = 0, []
+
+    def shard_check(self, world: int):
+        """:func:`replay` over ``world`` ranks deals the batches round-robin, so a rank does not see the CPIs in front of
+        its batch: an integrating chain then needs windows that do not overlap and do not cross a batch's end (hop ==
+        window, batch a multiple of the window), and starts every batch at count 0.  ValueError otherwise."""
+        if self.nci is None or world <= 1:
+            return
+        W, H = self.nci.window, self.nci.hop
+        if H != W or self.batch % W != 0:
+            raise ValueError(f"integrate over {world} ranks: the batches go round-robin, so windows must not overlap or cross a "
+                             f"batch's end: hop == window and batch % window == 0 (window {W}, hop {H}, batch {self.batch})")
+        self._per_batch = True
+
     def release_all(self):
         """Unregister whatever is still registered (before the capture's mapping goes away)."""
         self.torch.cuda.synchronize(self.dev)
@@ -984,6 +1061,8 @@ class GpuChain:
         self._bg.shutdown(wait=True)
         self.pool.shutdown(wait=True)
         self.release_all()
+        if self.nci is not None:
+            self.nci.close()
 
 
 def gpu_processor(cfg: dict, device: int = 0, batch: int = 1, want_map: bool = False, **kw) -> GpuChain:
@@ -1056,6 +1135,10 @@ def main(argv=None):
     ap.add_argument("--clutter-blocks", type=int, default=None, metavar="B",
                     help="clutter filter with taps per block: cut each CPI into B equal blocks (overrides process.clutter.blocks "
                          "of the config; 1 = one tap set per CPI); the chain then runs the two-stage filter")
+    ap.add_argument("--integrate", default=None, metavar="W[:H]",
+                    help="non-coherent integration of the maps over a sliding window of W consecutive CPIs (1 ... 16), a "
+                         "window every H CPIs (default 1); the detector's thresholds are made for W looks.  CPIs at which no "
+                         "window ends give no frame.  Several ranks: H == W and --batch a multiple of W")
     ap.add_argument("--connect", action="store_true",
                     help="with --json: send the documents to network.ip:ports.map / ports.detection of the config, "
                          "framed like Socket::sendData, instead of printing them")
@@ -1080,6 +1163,14 @@ def main(argv=None):
         if a.clutter_blocks < 1:
             ap.error("--clutter-blocks takes a block count >= 1")
         cfg["clutter"] = dict(cfg.get("clutter") or {}, blocks=a.clutter_blocks)
+    if a.integrate is not None:
+        try:
+            wh_ = [int(v) for v in a.integrate.split(":")]
+            if not 1 <= len(wh_) <= 2 or min(wh_) < 1:
+                raise ValueError
+        except ValueError:
+            ap.error("--integrate takes W or W:H, a window and a hop in CPIs, both >= 1")
+        cfg["integrate"] = {"window": wh_[0], "hop": wh_[1] if len(wh_) == 2 else 1}
     dist = None
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -1101,13 +1192,13 @@ def main(argv=None):
     t_cpi_ms = int(round(1000.0 * n / fs))
 
     def serialise(r):  # on the rank that owns the CPI: Map::to_json + delay_bin_to_km there, documents on the wire
-        if r.get("skipped") or not a.json:
+        if r.get("skipped") or r.get("integrating") or not a.json:
             return r
         # replay has no wall clock: CPI k is stamped k * tCpi in ms (blah2.cpp uses the capture time in ms)
         return {"cpi": r["cpi"], "frames": frames_for(r, proc.amb, fs, r["cpi"] * t_cpi_ms)}
 
     def emit(r):  # rank 0, file order, as the rounds complete: a write per document
-        if r.get("skipped"):
+        if r.get("skipped") or (a.json and r.get("integrating")):
             return
         if not a.json:
             sys.stdout.write(json.dumps(r) + "\n")

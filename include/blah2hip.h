@@ -195,6 +195,12 @@ int blah2hip_amb_get_axes(blah2hip_amb_t h, int32_t *delay, double *doppler);
                                        * the kernel does not cover it: F != 1024, asymmetric Doppler limits, a format other than
                                        * FMT_C32 / FMT_I8, another range kernel forced; a lone channel has nothing to share and runs
                                        * the per-channel path) or _PER_CHANNEL (the two-channel range stage once per channel) */
+#define BLAH2HIP_OPT_CFAR_LOOKS (BLAH2HIP_OPT_RANGE_WALK + 1) /* = 13: looks per cell L the detectors' threshold factors are made for (blah2hip_cfar_alpha), 1 (default) ..
+                                       * BLAH2HIP_MAX_CFAR_LOOKS: L = n_surv * window for the maps of blah2hip_nci_process_dev.  Read by
+                                       * blah2hip_cfar1d_dev / _cfar2d_dev / *_process and by *_prepare at the time of the call: the table is
+                                       * cached per (pfa, looks, size).  1 builds the table, and gives the bits, of a handle that never saw the
+                                       * option.  blah2hip_cfar1d_map takes no handle and stays one-look */
+#define BLAH2HIP_MAX_CFAR_LOOKS 1024
 #define BLAH2HIP_MULTI_AUTO 0
 #define BLAH2HIP_MULTI_SHARED 1
 #define BLAH2HIP_MULTI_PER_CHANNEL 2
@@ -479,6 +485,63 @@ int blah2hip_amb_bearing_dev(blah2hip_amb_t h, const void *d_map, uint32_t n_sur
                              const float *d_steer, uint32_t n_grid, uint32_t flags,
                              blah2hip_bearing_t *d_out, void *stream);
 
+/* ---- non-coherent integration over channels and CPIs (no reference counterpart) ----
+ * Two ways to more sensitivity than one map gives, in one pass: the sum of |M_k|^2 over the surveillance channels, which
+ * unlike the beams above needs no phase calibration of the array, and the sum over a sliding window of W consecutive CPIs.
+ * With the maps M_k[g] of CPI g, channel weights w_k >= 0 (receivers of unequal gain; default 1), window W and hop H:
+ *   p[g][cell]   = sum_k w_k |M_k[g][cell]|^2                            fp32, k ascending
+ *   out[g][cell] = ( sqrtf(scale * (p[g-W+1] + ... + p[g])), 0 )          fp32, oldest CPI first
+ *   scale        = 1 / (W * sum_k w_k), rounded to fp32 on the host
+ * for every g >= W - 1 with (g - (W - 1)) % H == 0; g counts the CPIs the integrator has seen since its creation or its
+ * last reset, across calls (H > W: the CPIs between two windows are not used).  The output is an ordinary complex map --
+ * the RMS level in the real part, a zero imaginary part -- so |z|^2 is the normalised sum and 10 log10|z| its level, and
+ * blah2hip_cfar1d_dev, blah2hip_cfar2d_dev, blah2hip_detect_dev, blah2hip_amb_db_dev and the JSON writers run on the n_out
+ * output maps unchanged, as virtual CPIs 0 .. n_out - 1.  Under noise a cell of the sum is Gamma distributed with
+ * L = n_surv * W looks, not exponential: set BLAH2HIP_OPT_CFAR_LOOKS to L for the detectors' pfa to hold
+ * (blah2hip_cfar_alpha).  With unequal weights L is only nominal -- the sum is no longer Gamma(L), its effective looks are
+ * (sum w)^2 / sum w^2 -- and the caller chooses the value.
+ * No running sums: every window is added up on its own, so nothing drifts, and a NaN or Inf cell of CPI g touches the
+ * windows that contain g and no other.  The integrator keeps p of the last W - 1 CPIs as fp32 planes, 4 (W - 1) cells bytes,
+ * written with the values the call summed: the bits of out[g], and of its metrics, do not depend on how the CPIs were cut
+ * into calls.  Per cell a term passes n_surv + 2 roundings on its way into p, at most W - 1 additions, the scale and the
+ * square root; all terms are non-negative, so the error is below (n_surv * W + 8) 2^-24 of the cell. */
+#define BLAH2HIP_MAX_NCI_WINDOW 16
+typedef struct blah2hip_nci_s *blah2hip_nci_t;
+/* An integrator for the maps of `amb` (its geometry; n_surv channels per CPI, window W, hop H), counter 0.  Allocates the
+ * history planes.  BLAH2HIP_ERR_INVALID: a NULL argument, n_surv outside [1, BLAH2HIP_MAX_SURV], window outside
+ * [1, BLAH2HIP_MAX_NCI_WINDOW], hop == 0.  (BLAH2HIP_ERR_UNSUPPORTED: the handle has fewer metrics partials per map than
+ * the kernel has workgroups, one per 512 cells; no geometry the engine plans today.) */
+int blah2hip_nci_create(blah2hip_amb_t amb, uint32_t n_surv, uint32_t window, uint32_t hop, blah2hip_nci_t *out);
+/* Waits for the device (enqueued calls use the history) and frees it.  Call it BEFORE blah2hip_amb_destroy of its handle. */
+int blah2hip_nci_destroy(blah2hip_nci_t n);
+/* g = 0 and the history forgotten: the next window needs W new CPIs.  Host only, enqueues nothing (calls enqueued
+ * earlier are not affected). */
+int blah2hip_nci_reset(blah2hip_nci_t n);
+/* What blah2hip_nci_process_dev would report for the next n_cpi CPIs, without enqueuing or counting anything: *n_out, the
+ * windows that end inside them, and *first_end, the g of the first window that ends at or behind the counter (inside the
+ * n_cpi CPIs exactly when *n_out > 0; the later ones follow every H).  Pure functions of the counter, n_cpi, W and H;
+ * either pointer may be NULL. */
+int blah2hip_nci_count(blah2hip_nci_t n, uint32_t n_cpi, uint32_t *n_out, uint64_t *first_end);
+/* The next n_cpi CPIs.  d_map: [n_surv][n_cpi][n_doppler][n_delay] complex fp32 as blah2hip_amb_process_multi_dev writes
+ * it (n_surv = 1: a single channel's maps; beam maps work as well; NULL = the handle's internal map).  w: HOST array
+ * [n_surv] of fp32 weights, read at the call and carried in the launch arguments, or NULL for all 1.  Output: d_out_map
+ * [n_out][n_doppler][n_delay], window after window, and d_out_metrics [n_out][2], Map::set_metrics of every output map on
+ * the cells as written.  *n_out and *first_end as blah2hip_nci_count reports them (either may be NULL): they are computed
+ * on the host, so the call only enqueues -- no allocation, upload or synchronisation -- and can be captured in a graph
+ * (a replay repeats the launch, not the count).  n_out may be 0, while the window fills: nothing is written to the
+ * outputs (they may be NULL), the history is still updated.
+ * One kernel (nci_kernel, BLAH2HIP_NK_NCI) reads every input cell once, whatever W and H are, reads the history planes at
+ * its start and writes them at its end; metrics_kernel finishes the metrics in index order (no floating-point atomics:
+ * two calls give the same bits).  The per-workgroup partials live in the ambiguity handle's buffers, so calls on one
+ * handle -- this one, the process calls, the beam former -- must be ordered on the device.
+ * BLAH2HIP_ERR_INVALID, with nothing enqueued and the counter unchanged: a NULL handle, n_cpi == 0, n_surv * n_cpi above
+ * max_batch, n_out above out_cap or above max_batch, a weight that is negative or not finite, weights that add up to 0, a
+ * NULL output while n_out > 0, a map that is not 8-byte aligned, an output that overlaps the input maps (the handle's
+ * internal map when d_map is NULL). */
+int blah2hip_nci_process_dev(blah2hip_nci_t n, const void *d_map, uint32_t n_cpi, const float *w,
+                             void *d_out_map, double *d_out_metrics, uint32_t out_cap,
+                             uint32_t *n_out, uint64_t *first_end, void *stream);
+
 /* ---- CfarDetector1D (CfarDetector1D.h:46-55) ---------------------------- */
 /* dev: d_map/d_metrics as written by blah2hip_amb_process_dev (NULL = the
  * handle's internal buffers).  d_hits: [n_cpi][cap]; d_count: [n_cpi], zeroed
@@ -488,12 +551,26 @@ int blah2hip_cfar1d_dev(blah2hip_amb_t h, const void *d_map, const double *d_met
                         uint32_t n_cpi, double pfa, int32_t n_guard, int32_t n_train,
                         int32_t min_delay, double min_doppler, blah2hip_hit_t *d_hits,
                         uint32_t cap, uint32_t *d_count, void *stream);
-/* Builds the threshold table alpha[n] = n (pfa^(-1/n) - 1) for this (pfa, n_train) ahead of
+/* Builds the threshold table alpha[n] = n (pfa^(-1/n) - 1) (BLAH2HIP_OPT_CFAR_LOOKS above 1: blah2hip_cfar_alpha's for
+ * the option's value at this call) for this (pfa, n_train) ahead of
  * time (one blocking upload).  blah2hip_cfar1d_dev does it on the first call with a new
  * tuple and only enqueues afterwards.  A table built by *_prepare stays resident for the handle's lifetime (a graph
  * captured after it may replay at any time); the tables the dev calls build on their own are a cache of eight, least
  * recently used first out. */
 int blah2hip_cfar1d_prepare(blah2hip_amb_t h, double pfa, int32_t n_train);
+/* The detectors' threshold factors for cells that are sums of `looks` looks (the output maps of blah2hip_nci_process_dev:
+ * looks = n_surv * window), what BLAH2HIP_OPT_CFAR_LOOKS makes the tables from.  Host arithmetic only: no GPU is touched.
+ * alpha[n], n = 1 .. max_n, for the threshold alpha[n] * (tot / n) over n training cells; alpha[0] = NaN (a cell without
+ * training cells never exceeds); alpha: max_n + 1 doubles.  Under noise a cell of the sum is Gamma(L) and the training sum
+ * Gamma(nL); with t = alpha / n and m = nL
+ *   Pfa(t) = sum_{k=0}^{L-1} C(m+k-1, k) t^k / (1+t)^(m+k)
+ * looks == 1: (1+t)^-n, solved in closed form: n (pfa^(-1/n) - 1) with the libm pow the reference calls
+ * (CfarDetector1D.cpp:76), bit for bit what the detectors have always tabulated, for any pfa.  looks > 1: Pfa(t) = pfa by
+ * bisection in fp64 until the interval no longer splits, Pfa evaluated term by term in the log domain (no lgamma); the
+ * result back-substitutes to pfa within 1e-10 of it.  The one-look factor on a sum of L looks is far too high: at L = 4,
+ * n = 8, pfa = 1e-3 it is 10.97 where 3.824 holds the pfa -- 4.6 dB of sensitivity.
+ * BLAH2HIP_ERR_INVALID: a NULL table, looks outside [1, BLAH2HIP_MAX_CFAR_LOOKS], pfa outside (0, 1) with looks > 1. */
+int blah2hip_cfar_alpha(double pfa, uint32_t looks, uint32_t max_n, double *alpha);
 /* host: runs the detector on CPI `cpi` of the handle's internal map and
  * returns Detection's three vectors (delay bins, Doppler Hz, snr) in the
  * reference's emission order (row-major, CfarDetector1D.cpp:36-92). */
@@ -827,6 +904,12 @@ int blah2hip_amb_get_timing(blah2hip_amb_t h, double *ms_total, uint32_t *launch
 #define BLAH2HIP_CK_COUNT 4
 int blah2hip_clutter_set_timing(blah2hip_clutter_t h, int enable);
 int blah2hip_clutter_get_timing(blah2hip_clutter_t h, double *ms_total, uint32_t *launches);
+/* the same for the integrator's kernel, on the integrator: its launches are bracketed there and the ambiguity handle's
+ * BLAH2HIP_K_* slots stay as they are (the metrics_kernel behind it counts under the ambiguity handle's BLAH2HIP_K_METRICS) */
+#define BLAH2HIP_NK_NCI 0 /* nci_kernel (blah2hip_nci_process_dev) */
+#define BLAH2HIP_NK_COUNT 1
+int blah2hip_nci_set_timing(blah2hip_nci_t n, int enable);
+int blah2hip_nci_get_timing(blah2hip_nci_t n, double *ms_total, uint32_t *launches);
 
 #ifdef __cplusplus
 }
