@@ -41,6 +41,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 using namespace blah2;
@@ -65,6 +66,11 @@ __device__ __forceinline__ uint32_t xs_index(uint32_t i, const XsMap &m)
 {
   uint32_t j = (i >= m.thresh) ? i - m.sub : i + m.wrapC;
   return j >= m.N ? j - m.N : j;
+}
+inline XsMap xs_map(int32_t delayMin, uint32_t N)
+{
+  const uint32_t thresh = delayMin > 0 ? (uint32_t)delayMin : 0u;
+  return {N, thresh, (uint32_t)delayMin, (uint32_t)(((1ull << 32) - (uint64_t)thresh) % N)};
 }
 // n < 2N -> n mod N
 __device__ __forceinline__ uint32_t wrapN(uint32_t n, uint32_t N) { return n >= N ? n - N : n; }
@@ -165,25 +171,73 @@ __device__ __forceinline__ bool xs_window_plain(int src0, int F, const XsMap &m,
   return src0 >= 0 && (uint32_t)src0 >= m.thresh && (uint64_t)*j0 + (uint32_t)*cnt <= m.N;
 }
 
+// ---- the FFT correlations: one kernel pair for one channel and for several against ONE reference -------------------------
+// r = xs against xs belongs to the reference alone, and so does the spectrum every b_k is formed against.  Both kernels
+// carry the surveillance channel as a compile-time tile:
+//   WITH_R, NB = 1: r and b_0 of (x, y_0).  The per-channel call (launch_clutter: rows = 2, row0 = 1, the layout
+//     [nCpi][2][nJobs][nBins]) and the first pass of blah2hip_clutter_process_multi_dev_fmt are this one instantiation
+//     (half-window: two, see PAIR there);
+//   !WITH_R, NB = 1 | 2: the channels behind the first, one or two per pass: the reference's spectrum once more (one
+//     transform per segment), then one window transform and accB_c += Y_c conj(.) per channel.  No xs window transform and
+//     no r accumulation: their registers hold the second channel, so no instantiation needs more than the first pass.
+// Per channel the segment walk, the job count and the order of the accumulation are the first pass's: r and every b_k are
+// the bits of the per-channel call.  Transforms per segment for K channels: windowed 3 + (K - 1) + ceil((K - 1) / 2)
+// against 3K, half-window 2 + (K - 1) + ceil((K - 1) / 2) against 2K.
+constexpr int CORR_TILE = 2;
 struct CorrArgs {
-  const void *x, *y; // InC32, InI8: the two planes; InI16: x = the interleaved buffer, y unused
+  const void *x;  // InC32, InI8: the reference plane; InI16: the interleaved buffer (the y planes are not read)
+  const void *y0; // this pass's first surveillance plane
   int64_t cpiStride;
   uint32_t N;
   XsMap xs;
-  int32_t nBins, segLen, nSeg, nJobs;
+  int32_t nBins;
+  union { // the form's segmentation in one place
+    struct { int32_t segLen, nSeg; } win; // windowed: the plan's segments
+    struct { int32_t nSeg, per; } half;   // half-window: nSeg = ceil(N / (F/2)), per = segments per workgroup
+  };
+  int32_t nJobs;
   const cf *tw;
-  cf *partial; // [nCpi][2][nJobs][nBins]
+  cf *partial;        // [nCpi][rows][nJobs][nBins]: row 0 = r, row 1 + k = b_k
   float scale;
+  // KEEP x ... scale where they are and add new fields behind `scale`: these are the offsets the single-channel kernels'
+  // arguments had.  With the planes as an array in front and both forms' fields side by side, 9 of 15 timed cases of the
+  // <true, 1> kernels were 0.1 ... 1.4 % slower, their vector code unchanged (mechanism not known)
+  int32_t rows;       // rows of `partial` per CPI
+  const void *y1;     // the pass's second plane (NB = 2)
+  int32_t row0;       // the row of y0's b
+  __device__ __forceinline__ const void *y(int c) const { return c ? y1 : y0; } // c is a constant after unrolling
 };
 
+// the end of both kernels: inverse transform of one accumulator, its first nBins lags into the workgroup's row of the partials
+// (one call per accumulator: a runtime-selected register array would be demoted to scratch)
+template <int R3> __device__ __forceinline__ void corr_finish(const CorrArgs &a, int t, cf *acc, int rows, int row, const cf *tw1, const cf *tw3, cf *P, cf *Q)
+{
+  using W = WgFft<R3>;
+  W::inv_s1(t, acc, tw3, P);
+  __syncthreads();
+  W::inv_s2(t, acc, P, Q);
+  __syncthreads();
+  W::inv_s3(t, acc, tw1, Q);
+  const int cpi = blockIdx.y;
+  cf *dst = a.partial + (((size_t)cpi * rows + row) * a.nJobs + blockIdx.x) * a.nBins;
+#pragma unroll
+  for (int c = 0; c < 16; c++) {
+    const int k = t + W::T * c;
+    if (k < a.nBins) dst[k] = cmake(acc[c].x * a.scale, acc[c].y * a.scale);
+  }
+  __syncthreads();
+}
+
 // grid (nJobs, nCpi): per segment FFT(x' = zero-padded xs segment) ONCE, then the
-// xs window (-> r) and the y window (-> b) against it; both partial correlations
+// xs window (-> r) and the y windows (-> b_c) against it; the partial correlations
 // accumulate in registers across the workgroup's segments.
 // (F = 4096: built for ONE workgroup of 256 threads per SIMD set -- 257 registers are what the three live windows, two
 // accumulators and two twiddle sets need there, and at the two-workgroup cap of 256 one value went to scratch in every
-// build of rounds 2-5.  That instantiation only runs for filters of 2050 ... 4081 taps: the half-window form takes the rest.)
-template <int R3, class In> __global__ __launch_bounds__(16 * R3, R3 == 16 ? 1 : 2) void clutter_corr_kernel(CorrArgs a)
+// build of rounds 2-5.  With r that instantiation only runs for filters of 2050 ... 4081 taps: the half-window form takes the rest.)
+template <int R3, class In, bool WITH_R, int NB>
+__global__ __launch_bounds__(16 * R3, R3 == 16 ? 1 : 2) void clutter_corr_kernel(CorrArgs a)
 {
+  static_assert(NB >= 1 && NB <= CORR_TILE && (!WITH_R || NB == 1), "r rides with the first channel alone");
   using W = WgFft<R3>;
   constexpr int T = W::T;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -191,92 +245,87 @@ template <int R3, class In> __global__ __launch_bounds__(16 * R3, R3 == 16 ? 1 :
   cf *Q = P + W::A_ELEMS;
   const int t = threadIdx.x;
   const int cpi = blockIdx.y;
-  const typename ChanOf<In>::type X = ChanOf<In>::x(a.x, a.y, (int64_t)cpi * a.cpiStride);
-  const typename ChanOf<In>::type Y = ChanOf<In>::y(a.x, a.y, (int64_t)cpi * a.cpiStride);
+  const typename ChanOf<In>::type X = ChanOf<In>::x(a.x, nullptr, (int64_t)cpi * a.cpiStride);
   cf tw1[15], tw3[16];
   W::load_twiddles(t, a.tw, tw1, tw3);
 
-  cf accR[16], accB[16];
+  cf accR[16], accB[NB][16];
 #pragma unroll
-  for (int e = 0; e < 16; e++) { accR[e] = cmake(0.f, 0.f); accB[e] = cmake(0.f, 0.f); }
-  const SegWalk sw = seg_walk(a.nSeg);
+  for (int e = 0; e < 16; e++) {
+    accR[e] = cmake(0.f, 0.f);
+#pragma unroll
+    for (int c = 0; c < NB; c++) accB[c][e] = cmake(0.f, 0.f);
+  }
+  const SegWalk sw = seg_walk(a.win.nSeg);
   for (int r = sw.first; r < sw.count; r += sw.step) {
     const int g = sw.base + r;
-    const uint32_t n0 = (uint32_t)g * (uint32_t)a.segLen;
-    // all 32 loads of the segment first (the y window is consumed last) -- except at F = 4096, where the kernel sits at the
-    // 256-register cap: there the y window is requested inside the second transform (its 32 registers are free until
-    // then), which removed the one spilled register (8 bytes of scratch per lane) of rounds 2-5; this instantiation
-    // only runs for filters of 2050 ... 4081 taps (the half-window form takes the others)
-    cf v[16], wv[16], yw[16];
+    const uint32_t n0 = (uint32_t)g * (uint32_t)a.win.segLen;
+    cf v[16], wv[16], yw[NB][16];
     uint32_t j0;
     int xcnt;
     const bool whole = (uint64_t)n0 + 16 * T <= a.N; // the window does not run around the end of the CPI
     const bool plain = whole && xs_window_plain((int)n0, 16 * T, a.xs, &j0, &xcnt); // all but a CPI's first and last windows: immediates only
-    auto load_y = [&]() {
+    auto load_y = [&](int c) { // c is a constant after unrolling
       if (plain) {
         using CY = typename BufChanOf<In>::Y;
-        const __amdgpu_buffer_rsrc_t yd = make_rsrc_b(BufChanOf<In>::y(a.x, a.y, (int64_t)cpi * a.cpiStride + n0), 16 * T * CY::STRIDE);
+        const __amdgpu_buffer_rsrc_t yd = make_rsrc_b(BufChanOf<In>::y(a.x, a.y(c), (int64_t)cpi * a.cpiStride + n0), 16 * T * CY::STRIDE);
 #pragma unroll
-        for (int k = 0; k < 16; k++) yw[k] = RawBuiltin<CY>::cvt(RawBuiltin<CY>::ld(yd, (t + T * k) * CY::STRIDE, 0));
+        for (int k = 0; k < 16; k++) yw[c][k] = RawBuiltin<CY>::cvt(RawBuiltin<CY>::ld(yd, (t + T * k) * CY::STRIDE, 0));
       } else {
+        const typename ChanOf<In>::type Y = ChanOf<In>::y(a.x, a.y(c), (int64_t)cpi * a.cpiStride);
 #pragma unroll
-        for (int k = 0; k < 16; k++) yw[k] = Y[wrapWin(n0 + (uint32_t)(t + T * k), a.N)]; // y window (mode b)
+        for (int k = 0; k < 16; k++) yw[c][k] = Y[wrapWin(n0 + (uint32_t)(t + T * k), a.N)];
       }
     };
     if (plain) {
       using CX = typename BufChanOf<In>::X;
-      const __amdgpu_buffer_rsrc_t xd = make_rsrc_b(BufChanOf<In>::x(a.x, a.y, (int64_t)cpi * a.cpiStride + j0), 16 * T * CX::STRIDE);
+      const __amdgpu_buffer_rsrc_t xd = make_rsrc_b(BufChanOf<In>::x(a.x, nullptr, (int64_t)cpi * a.cpiStride + j0), 16 * T * CX::STRIDE);
 #pragma unroll
       for (int k = 0; k < 16; k++) wv[k] = RawBuiltin<CX>::cvt(RawBuiltin<CX>::ld(xd, (t + T * k) * CX::STRIDE, 0));
     } else {
 #pragma unroll
-      for (int k = 0; k < 16; k++) wv[k] = X[xs_index(wrapWin(n0 + (uint32_t)(t + T * k), a.N), a.xs)]; // xs window (mode r): circular index, n0 + m < N + F
+      for (int k = 0; k < 16; k++) wv[k] = X[xs_index(wrapWin(n0 + (uint32_t)(t + T * k), a.N), a.xs)];
     }
-    if (R3 < 16) load_y();
+    // all the loads of the segment first (the y window is consumed last) -- except at F = 4096 with r, where the kernel sits
+    // at the 256-register cap: there the y window is requested inside the second transform (its 32 registers are free until
+    // then), which removed the one spilled register (8 bytes of scratch per lane) of rounds 2-5
+    if (!WITH_R || R3 < 16) load_y(0);
 #pragma unroll
     for (int k = 0; k < 16; k++) {
       const int m = t + T * k;
-      v[k] = (m < a.segLen && n0 + (uint32_t)m < a.N) ? wv[k] : cmake(0.f, 0.f); // x' = the same samples, cut to the segment
+      v[k] = (m < a.win.segLen && n0 + (uint32_t)m < a.N) ? wv[k] : cmake(0.f, 0.f); // x' = the same samples, cut to the segment
     }
     W::fwd_s1(t, v, tw1, P);
     __syncthreads();
     W::fwd_s2(t, v, P, Q);
     __syncthreads();
     W::fwd_s3(t, v, tw3, Q); // v = X' spectrum
-    W::fwd_s1(t, wv, tw1, P);
-    __syncthreads();
-    W::fwd_s2(t, wv, P, Q);
-    if (R3 == 16) load_y(); // behind the second transform's last exchange write: wv's 32 registers are about to be consumed
-    __syncthreads();
-    W::fwd_s3(t, wv, tw3, Q);
+    if (WITH_R) {
+      W::fwd_s1(t, wv, tw1, P);
+      __syncthreads();
+      W::fwd_s2(t, wv, P, Q);
+      if (R3 == 16) load_y(0); // behind the second transform's last exchange write: wv's 32 registers are about to be consumed
+      __syncthreads();
+      W::fwd_s3(t, wv, tw3, Q);
 #pragma unroll
-    for (int e = 0; e < 16; e++) accR[e] = cmacc(accR[e], wv[e], v[e]);
-    W::fwd_s1(t, yw, tw1, P);
-    __syncthreads();
-    W::fwd_s2(t, yw, P, Q);
-    __syncthreads();
-    W::fwd_s3(t, yw, tw3, Q);
+      for (int e = 0; e < 16; e++) accR[e] = cmacc(accR[e], wv[e], v[e]);
+    }
 #pragma unroll
-    for (int e = 0; e < 16; e++) accB[e] = cmacc(accB[e], yw[e], v[e]);
-    __syncthreads();
-  }
-  // two explicit calls (a runtime-selected register array would be demoted to scratch)
-  auto finish = [&](cf *acc, int mode) {
-    W::inv_s1(t, acc, tw3, P);
-    __syncthreads();
-    W::inv_s2(t, acc, P, Q);
-    __syncthreads();
-    W::inv_s3(t, acc, tw1, Q);
-    cf *dst = a.partial + (((size_t)cpi * 2 + mode) * a.nJobs + blockIdx.x) * a.nBins;
+    for (int c = 0; c < NB; c++) {
+      W::fwd_s1(t, yw[c], tw1, P);
+      __syncthreads();
+      W::fwd_s2(t, yw[c], P, Q);
+      if (c + 1 < NB) load_y(c + 1); // the next channel's window behind this transform's last exchange write: five register sets, as with r
+      __syncthreads();
+      W::fwd_s3(t, yw[c], tw3, Q);
 #pragma unroll
-    for (int c = 0; c < 16; c++) {
-      const int k = t + T * c;
-      if (k < a.nBins) dst[k] = cmake(acc[c].x * a.scale, acc[c].y * a.scale);
+      for (int e = 0; e < 16; e++) accB[c][e] = cmacc(accB[c][e], yw[c][e], v[e]);
     }
     __syncthreads();
-  };
-  finish(accR, 0);
-  finish(accB, 1);
+  }
+  if (WITH_R) corr_finish<R3>(a, t, accR, a.rows, 0, tw1, tw3, P, Q);
+  corr_finish<R3>(a, t, accB[0], a.rows, a.row0, tw1, tw3, P, Q);
+  if (NB > 1) corr_finish<R3>(a, t, accB[NB - 1], a.rows, a.row0 + 1, tw1, tw3, P, Q);
 }
 
 // Half-window form of the same correlations, for filters with many taps (nBins - 1 <= F/2): cut the
@@ -292,19 +341,18 @@ template <int R3, class In> __global__ __launch_bounds__(16 * R3, R3 == 16 ? 1 :
 // CIRCULAR correlations over N -- the pairs whose later sample wraps to the head of the CPI -- is one
 // more product, tail (last nBins-1 samples of xs) against head (first nBins-1 of xs / y) shifted by
 // tau = nBins - 1, i.e. times W_F^(tau m), done by the last workgroup.  Mathematically identical.
-struct CorrHalfArgs {
-  const void *x, *y;
-  int64_t cpiStride;
-  uint32_t N;
-  XsMap xs;
-  int32_t nBins, nSeg, per, nJobs; // nSeg = ceil(N / (F/2)), per = segments per workgroup
-  const cf *tw;
-  cf *partial; // [nCpi][2][nJobs][nBins]
-  float scale;
-};
-
-template <int R3, class In> __global__ __launch_bounds__(16 * R3, 2) void clutter_corr_half_kernel(CorrHalfArgs a)
+// In the passes without r, z = X_g + (-1)^m X_{g-1} takes the previous segment's registers as soon as it is formed, and the
+// channels' transforms follow one after the other against it: five register sets at NB = 2, the count of the pass with r.
+// (F = 4096 with two channels: built for ONE workgroup per SIMD set, like the windowed kernel -- at the 256-register cap
+// of two the allocator put 1 value of the segment loop and 62 of the wrap-around product into scratch.)
+// PAIR: the per-channel call's instantiation, its partials [nCpi][2][nJobs][nBins] known at compile time (rows = 2, row0 = 1).
+// With the rows as run-time arguments this kernel's vector code was the same and the launch 0.5 ... 1.8 % slower at F = 2048 on
+// int8 planes (every one of 6 legs above every one of 18); with PAIR nothing is left that differs from what was measured fast.
+template <int R3, class In, bool WITH_R, int NB, bool PAIR = false>
+__global__ __launch_bounds__(16 * R3, (R3 == 16 && NB == 2) ? 1 : 2) void clutter_corr_half_kernel(CorrArgs a)
 {
+  static_assert(NB >= 1 && NB <= CORR_TILE && (!WITH_R || NB == 1), "r rides with the first channel alone");
+  static_assert(!PAIR || WITH_R, "the pair of rows is r and b");
   using W = WgFft<R3>;
   constexpr int T = W::T, L = W::F / 2;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -312,8 +360,7 @@ template <int R3, class In> __global__ __launch_bounds__(16 * R3, 2) void clutte
   cf *Q = P + W::A_ELEMS;
   const int t = threadIdx.x;
   const int cpi = blockIdx.y;
-  const typename ChanOf<In>::type X = ChanOf<In>::x(a.x, a.y, (int64_t)cpi * a.cpiStride);
-  const typename ChanOf<In>::type Y = ChanOf<In>::y(a.x, a.y, (int64_t)cpi * a.cpiStride);
+  const typename ChanOf<In>::type X = ChanOf<In>::x(a.x, nullptr, (int64_t)cpi * a.cpiStride);
   cf tw1[15], tw3[16];
   W::load_twiddles(t, a.tw, tw1, tw3);
   // (-1)^m for this thread's spectrum registers: m = q + 16 r + 256 s with q = (t + T j) / 16 and T a
@@ -337,257 +384,6 @@ template <int R3, class In> __global__ __launch_bounds__(16 * R3, 2) void clutte
     uint32_t j0;
     int cnt;
     if (xs_window_plain((int)n0, (int)len, a.xs, &j0, &cnt) && cnt == (int)len) {
-      const __amdgpu_buffer_rsrc_t d = make_rsrc_b(BufChanOf<In>::x(a.x, a.y, (int64_t)cpi * a.cpiStride + j0), (int)len * CX::STRIDE);
-#pragma unroll
-      for (int k = 0; k < 8; k++) v[k] = RawBuiltin<CX>::cvt(RawBuiltin<CX>::ld(d, (t + T * k) * CX::STRIDE, 0));
-    } else {
-#pragma unroll
-      for (int k = 0; k < 8; k++) {
-        const uint32_t m = (uint32_t)(t + T * k);
-        const bool inr = m < len;
-        const cf s = X[xs_index(inr ? n0 + m : 0u, a.xs)];
-        v[k] = inr ? s : cmake(0.f, 0.f);
-      }
-    }
-#pragma unroll
-    for (int k = 8; k < 16; k++) v[k] = cmake(0.f, 0.f);
-  };
-  auto load_y = [&](uint32_t n0, uint32_t len, cf *v) {
-    const __amdgpu_buffer_rsrc_t d = make_rsrc_b(BufChanOf<In>::y(a.x, a.y, (int64_t)cpi * a.cpiStride + n0), (int)len * CY::STRIDE);
-#pragma unroll
-    for (int k = 0; k < 8; k++) v[k] = RawBuiltin<CY>::cvt(RawBuiltin<CY>::ld(d, (t + T * k) * CY::STRIDE, 0));
-#pragma unroll
-    for (int k = 8; k < 16; k++) v[k] = cmake(0.f, 0.f);
-  };
-  auto seg_len = [&](int g) { return min((uint32_t)L, a.N - (uint32_t)g * (uint32_t)L); };
-
-  cf accR[16], accB[16], prevX[16];
-#pragma unroll
-  for (int e = 0; e < 16; e++) { accR[e] = cmake(0.f, 0.f); accB[e] = cmake(0.f, 0.f); prevX[e] = cmake(0.f, 0.f); }
-  const int g0 = blockIdx.x * a.per, g1 = min(g0 + a.per, a.nSeg);
-  if (g0 > 0 && g0 < g1) { // the segment in front of the run (a full one)
-    load_xs((uint32_t)(g0 - 1) * (uint32_t)L, (uint32_t)L, prevX);
-    fwd(prevX);
-  }
-  for (int g = g0; g < g1; g++) {
-    const uint32_t n0 = (uint32_t)g * (uint32_t)L, len = seg_len(g);
-    cf v[16], yv[16];
-    load_xs(n0, len, v);
-    load_y(n0, len, yv);
-    fwd(v);
-    fwd(yv);
-#pragma unroll
-    for (int e = 0; e < 16; e++) {
-      const cf z = cmake(v[e].x + sgn * prevX[e].x, v[e].y + sgn * prevX[e].y); // X_g + (-1)^m X_{g-1}
-      accR[e] = cmacc(accR[e], v[e], z);
-      accB[e] = cmacc(accB[e], yv[e], z);
-      prevX[e] = v[e];
-    }
-  }
-  if (blockIdx.x == (unsigned)a.nJobs - 1 && a.nBins > 1) { // the wrap-around pairs
-    const uint32_t tau = (uint32_t)a.nBins - 1;
-    cf v[16], yv[16];
-    load_xs(a.N - tau, tau, prevX); // tail of xs
-    load_xs(0u, tau, v);            // head of xs
-    load_y(0u, tau, yv);            // head of y
-    fwd(prevX);
-    fwd(v);
-    fwd(yv);
-#pragma unroll
-    for (int j = 0; j < W::NP; j++)
-#pragma unroll
-      for (int sidx = 0; sidx < R3; sidx++) {
-        const int e = j * R3 + sidx;
-        const int p16 = t + T * j;                         // 16 q + r
-        const int m = (p16 >> 4) + 16 * (p16 & 15) + 256 * sidx;
-        const cf ph = a.tw[((uint32_t)m * tau) & (W::F - 1)]; // W_F^(tau m): the head sits tau samples behind the tail
-        const cf z = cmulc(prevX[e], ph);                  // conj(phase) * X_tail
-        accR[e] = cmacc(accR[e], v[e], z);
-        accB[e] = cmacc(accB[e], yv[e], z);
-      }
-  }
-  auto finish = [&](cf *acc, int mode) {
-    W::inv_s1(t, acc, tw3, P);
-    __syncthreads();
-    W::inv_s2(t, acc, P, Q);
-    __syncthreads();
-    W::inv_s3(t, acc, tw1, Q);
-    cf *dst = a.partial + (((size_t)cpi * 2 + mode) * a.nJobs + blockIdx.x) * a.nBins;
-#pragma unroll
-    for (int c = 0; c < 16; c++) {
-      const int k = t + T * c;
-      if (k < a.nBins) dst[k] = cmake(acc[c].x * a.scale, acc[c].y * a.scale);
-    }
-    __syncthreads();
-  };
-  finish(accR, 0);
-  finish(accB, 1);
-}
-
-// ---- several surveillance channels against ONE reference (blah2hip_clutter_process_multi_dev_fmt) --------------------
-// r = xs against xs belongs to the reference alone, and so does the spectrum every b_k is formed against.  The two kernels
-// below are clutter_corr_kernel and clutter_corr_half_kernel with the channel as a compile-time tile:
-//   WITH_R, NB = 1: the parent's work on (x, y_0) -- r and b_0 -- written into the wider partial layout;
-//   !WITH_R, NB = 1 | 2: the channels behind the first, one or two per pass: the reference's spectrum once more (one
-//     transform per segment), then one window transform and accB_c += Y_c conj(.) per channel.  No xs window transform and
-//     no r accumulation: their registers hold the second channel, so no instantiation needs more than its parent.
-// Per channel the segment walk, the job count and the order of the accumulation are the parent's: r and every b_k are
-// the bits of the per-channel call.  Transforms per segment for K channels: windowed 3 + (K - 1) + ceil((K - 1) / 2)
-// against 3K, half-window 2 + (K - 1) + ceil((K - 1) / 2) against 2K.
-constexpr int CORR_TILE = 2;
-struct CorrMultiArgs {
-  const void *x;            // the reference plane
-  const void *y[CORR_TILE]; // this pass's surveillance planes
-  int64_t cpiStride;
-  uint32_t N;
-  XsMap xs;
-  int32_t nBins, segLen, nSeg, per, nJobs; // windowed: segLen, nSeg as CorrArgs; half-window: nSeg, per as CorrHalfArgs
-  const cf *tw;
-  cf *partial;        // [nCpi][rows][nJobs][nBins]: row 0 = r, row 1 + k = b_k
-  float scale;
-  int32_t rows, row0; // row0: the row of y[0]'s b
-};
-
-template <int R3, class In, bool WITH_R, int NB>
-__global__ __launch_bounds__(16 * R3, R3 == 16 ? 1 : 2) void clutter_corr_multi_kernel(CorrMultiArgs a)
-{
-  static_assert(NB >= 1 && NB <= CORR_TILE && (!WITH_R || NB == 1), "r rides with the first channel alone");
-  using W = WgFft<R3>;
-  constexpr int T = W::T;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  cf *P = reinterpret_cast<cf *>(smem);
-  cf *Q = P + W::A_ELEMS;
-  const int t = threadIdx.x;
-  const int cpi = blockIdx.y;
-  const typename ChanOf<In>::type X = ChanOf<In>::x(a.x, nullptr, (int64_t)cpi * a.cpiStride);
-  cf tw1[15], tw3[16];
-  W::load_twiddles(t, a.tw, tw1, tw3);
-
-  cf accR[16], accB[NB][16];
-#pragma unroll
-  for (int e = 0; e < 16; e++) {
-    accR[e] = cmake(0.f, 0.f);
-#pragma unroll
-    for (int c = 0; c < NB; c++) accB[c][e] = cmake(0.f, 0.f);
-  }
-  const SegWalk sw = seg_walk(a.nSeg);
-  for (int r = sw.first; r < sw.count; r += sw.step) {
-    const int g = sw.base + r;
-    const uint32_t n0 = (uint32_t)g * (uint32_t)a.segLen;
-    cf v[16], wv[16], yw[NB][16];
-    uint32_t j0;
-    int xcnt;
-    const bool whole = (uint64_t)n0 + 16 * T <= a.N;
-    const bool plain = whole && xs_window_plain((int)n0, 16 * T, a.xs, &j0, &xcnt);
-    auto load_y = [&](int c) { // c is a constant after unrolling
-      if (plain) {
-        using CY = typename BufChanOf<In>::Y;
-        const __amdgpu_buffer_rsrc_t yd = make_rsrc_b(BufChanOf<In>::y(a.x, a.y[c], (int64_t)cpi * a.cpiStride + n0), 16 * T * CY::STRIDE);
-#pragma unroll
-        for (int k = 0; k < 16; k++) yw[c][k] = RawBuiltin<CY>::cvt(RawBuiltin<CY>::ld(yd, (t + T * k) * CY::STRIDE, 0));
-      } else {
-        const typename ChanOf<In>::type Y = ChanOf<In>::y(a.x, a.y[c], (int64_t)cpi * a.cpiStride);
-#pragma unroll
-        for (int k = 0; k < 16; k++) yw[c][k] = Y[wrapWin(n0 + (uint32_t)(t + T * k), a.N)];
-      }
-    };
-    if (plain) {
-      using CX = typename BufChanOf<In>::X;
-      const __amdgpu_buffer_rsrc_t xd = make_rsrc_b(BufChanOf<In>::x(a.x, nullptr, (int64_t)cpi * a.cpiStride + j0), 16 * T * CX::STRIDE);
-#pragma unroll
-      for (int k = 0; k < 16; k++) wv[k] = RawBuiltin<CX>::cvt(RawBuiltin<CX>::ld(xd, (t + T * k) * CX::STRIDE, 0));
-    } else {
-#pragma unroll
-      for (int k = 0; k < 16; k++) wv[k] = X[xs_index(wrapWin(n0 + (uint32_t)(t + T * k), a.N), a.xs)];
-    }
-    // the y windows with the xs window, as the parent requests them (at F = 4096 with r: inside the second transform)
-    if (!WITH_R || R3 < 16) load_y(0);
-#pragma unroll
-    for (int k = 0; k < 16; k++) {
-      const int m = t + T * k;
-      v[k] = (m < a.segLen && n0 + (uint32_t)m < a.N) ? wv[k] : cmake(0.f, 0.f);
-    }
-    W::fwd_s1(t, v, tw1, P);
-    __syncthreads();
-    W::fwd_s2(t, v, P, Q);
-    __syncthreads();
-    W::fwd_s3(t, v, tw3, Q); // v = X' spectrum
-    if (WITH_R) {
-      W::fwd_s1(t, wv, tw1, P);
-      __syncthreads();
-      W::fwd_s2(t, wv, P, Q);
-      if (R3 == 16) load_y(0);
-      __syncthreads();
-      W::fwd_s3(t, wv, tw3, Q);
-#pragma unroll
-      for (int e = 0; e < 16; e++) accR[e] = cmacc(accR[e], wv[e], v[e]);
-    }
-#pragma unroll
-    for (int c = 0; c < NB; c++) {
-      W::fwd_s1(t, yw[c], tw1, P);
-      __syncthreads();
-      W::fwd_s2(t, yw[c], P, Q);
-      if (c + 1 < NB) load_y(c + 1); // the next channel's window behind this transform's last exchange write: five register sets, as the parent
-      __syncthreads();
-      W::fwd_s3(t, yw[c], tw3, Q);
-#pragma unroll
-      for (int e = 0; e < 16; e++) accB[c][e] = cmacc(accB[c][e], yw[c][e], v[e]);
-    }
-    __syncthreads();
-  }
-  auto finish = [&](cf *acc, int row) {
-    W::inv_s1(t, acc, tw3, P);
-    __syncthreads();
-    W::inv_s2(t, acc, P, Q);
-    __syncthreads();
-    W::inv_s3(t, acc, tw1, Q);
-    cf *dst = a.partial + (((size_t)cpi * a.rows + row) * a.nJobs + blockIdx.x) * a.nBins;
-#pragma unroll
-    for (int c = 0; c < 16; c++) {
-      const int k = t + T * c;
-      if (k < a.nBins) dst[k] = cmake(acc[c].x * a.scale, acc[c].y * a.scale);
-    }
-    __syncthreads();
-  };
-  if (WITH_R) finish(accR, 0);
-  finish(accB[0], a.row0);
-  if (NB > 1) finish(accB[NB - 1], a.row0 + 1);
-}
-
-// The half-window form.  z = X_g + (-1)^m X_{g-1} takes the previous segment's registers as soon as it is formed, and the
-// channels' transforms follow one after the other against it: five register sets at NB = 2, the parent's count.
-// (F = 4096 with two channels: built for ONE workgroup per SIMD set, like clutter_corr_kernel<16> -- at the 256-register cap
-// of two the allocator put 1 value of the segment loop and 62 of the wrap-around product into scratch.)
-template <int R3, class In, bool WITH_R, int NB>
-__global__ __launch_bounds__(16 * R3, (R3 == 16 && NB == 2) ? 1 : 2) void clutter_corr_half_multi_kernel(CorrMultiArgs a)
-{
-  static_assert(NB >= 1 && NB <= CORR_TILE && (!WITH_R || NB == 1), "r rides with the first channel alone");
-  using W = WgFft<R3>;
-  constexpr int T = W::T, L = W::F / 2;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  cf *P = reinterpret_cast<cf *>(smem);
-  cf *Q = P + W::A_ELEMS;
-  const int t = threadIdx.x;
-  const int cpi = blockIdx.y;
-  const typename ChanOf<In>::type X = ChanOf<In>::x(a.x, nullptr, (int64_t)cpi * a.cpiStride);
-  cf tw1[15], tw3[16];
-  W::load_twiddles(t, a.tw, tw1, tw3);
-  const float sgn = ((t >> 4) & 1) ? -1.f : 1.f;
-
-  auto fwd = [&](cf *v) {
-    W::fwd_s1(t, v, tw1, P);
-    __syncthreads();
-    W::fwd_s2(t, v, P, Q);
-    __syncthreads();
-    W::fwd_s3(t, v, tw3, Q);
-    __syncthreads();
-  };
-  using CX = typename BufChanOf<In>::X;
-  using CY = typename BufChanOf<In>::Y;
-  auto load_xs = [&](uint32_t n0, uint32_t len, cf *v) {
-    uint32_t j0;
-    int cnt;
-    if (xs_window_plain((int)n0, (int)len, a.xs, &j0, &cnt) && cnt == (int)len) {
       const __amdgpu_buffer_rsrc_t d = make_rsrc_b(BufChanOf<In>::x(a.x, nullptr, (int64_t)cpi * a.cpiStride + j0), (int)len * CX::STRIDE);
 #pragma unroll
       for (int k = 0; k < 8; k++) v[k] = RawBuiltin<CX>::cvt(RawBuiltin<CX>::ld(d, (t + T * k) * CX::STRIDE, 0));
@@ -604,7 +400,7 @@ __global__ __launch_bounds__(16 * R3, (R3 == 16 && NB == 2) ? 1 : 2) void clutte
     for (int k = 8; k < 16; k++) v[k] = cmake(0.f, 0.f);
   };
   auto load_y = [&](int c, uint32_t n0, uint32_t len, cf *v) {
-    const __amdgpu_buffer_rsrc_t d = make_rsrc_b(BufChanOf<In>::y(a.x, a.y[c], (int64_t)cpi * a.cpiStride + n0), (int)len * CY::STRIDE);
+    const __amdgpu_buffer_rsrc_t d = make_rsrc_b(BufChanOf<In>::y(a.x, a.y(c), (int64_t)cpi * a.cpiStride + n0), (int)len * CY::STRIDE);
 #pragma unroll
     for (int k = 0; k < 8; k++) v[k] = RawBuiltin<CY>::cvt(RawBuiltin<CY>::ld(d, (t + T * k) * CY::STRIDE, 0));
 #pragma unroll
@@ -620,8 +416,8 @@ __global__ __launch_bounds__(16 * R3, (R3 == 16 && NB == 2) ? 1 : 2) void clutte
 #pragma unroll
     for (int c = 0; c < NB; c++) accB[c][e] = cmake(0.f, 0.f);
   }
-  const int g0 = blockIdx.x * a.per, g1 = min(g0 + a.per, a.nSeg);
-  if (g0 > 0 && g0 < g1) {
+  const int g0 = blockIdx.x * a.half.per, g1 = min(g0 + a.half.per, a.half.nSeg);
+  if (g0 > 0 && g0 < g1) { // the segment in front of the run (a full one)
     load_xs((uint32_t)(g0 - 1) * (uint32_t)L, (uint32_t)L, prevX);
     fwd(prevX);
   }
@@ -629,70 +425,76 @@ __global__ __launch_bounds__(16 * R3, (R3 == 16 && NB == 2) ? 1 : 2) void clutte
     const uint32_t n0 = (uint32_t)g * (uint32_t)L, len = seg_len(g);
     cf v[16], yv[16];
     load_xs(n0, len, v);
-    if (WITH_R) load_y(0, n0, len, yv); // with the xs segment, as the parent requests it
+    if (WITH_R) load_y(0, n0, len, yv); // with the xs segment: both requests in front of the first transform
     fwd(v);
-#pragma unroll
-    for (int e = 0; e < 16; e++) {
-      const cf z = cmake(v[e].x + sgn * prevX[e].x, v[e].y + sgn * prevX[e].y); // X_g + (-1)^m X_{g-1}
-      if (WITH_R) accR[e] = cmacc(accR[e], v[e], z);
-      prevX[e] = z;
-    }
-#pragma unroll
-    for (int c = 0; c < NB; c++) {
-      if (!WITH_R || c > 0) load_y(c, n0, len, yv);
+    if constexpr (WITH_R) {
+      // both transforms, then ONE pass over the registers: z never leaves its register pair and X_g takes X_{g-1}'s place
+      // as it is consumed
       fwd(yv);
 #pragma unroll
-      for (int e = 0; e < 16; e++) accB[c][e] = cmacc(accB[c][e], yv[e], prevX[e]);
-    }
+      for (int e = 0; e < 16; e++) {
+        const cf z = cmake(v[e].x + sgn * prevX[e].x, v[e].y + sgn * prevX[e].y); // X_g + (-1)^m X_{g-1}
+        accR[e] = cmacc(accR[e], v[e], z);
+        accB[0][e] = cmacc(accB[0][e], yv[e], z);
+        prevX[e] = v[e];
+      }
+    } else {
 #pragma unroll
-    for (int e = 0; e < 16; e++) prevX[e] = v[e];
+      for (int e = 0; e < 16; e++) prevX[e] = cmake(v[e].x + sgn * prevX[e].x, v[e].y + sgn * prevX[e].y); // z, kept for every channel
+#pragma unroll
+      for (int c = 0; c < NB; c++) {
+        load_y(c, n0, len, yv);
+        fwd(yv);
+#pragma unroll
+        for (int e = 0; e < 16; e++) accB[c][e] = cmacc(accB[c][e], yv[e], prevX[e]);
+      }
+#pragma unroll
+      for (int e = 0; e < 16; e++) prevX[e] = v[e];
+    }
   }
   if (blockIdx.x == (unsigned)a.nJobs - 1 && a.nBins > 1) { // the wrap-around pairs
     const uint32_t tau = (uint32_t)a.nBins - 1;
     cf v[16], yv[16];
     load_xs(a.N - tau, tau, prevX); // tail of xs
+    if (WITH_R) { // all three requests in front of the transforms: this workgroup ends the launch
+      load_xs(0u, tau, v);    // head of xs
+      load_y(0, 0u, tau, yv); // head of y
+    }
     fwd(prevX);
+    if (WITH_R) {
+      fwd(v);
+      fwd(yv);
+    }
 #pragma unroll
     for (int j = 0; j < W::NP; j++)
 #pragma unroll
       for (int sidx = 0; sidx < R3; sidx++) {
         const int e = j * R3 + sidx;
-        const int p16 = t + T * j;
+        const int p16 = t + T * j;                         // 16 q + r
         const int m = (p16 >> 4) + 16 * (p16 & 15) + 256 * sidx;
-        const cf ph = a.tw[((uint32_t)m * tau) & (W::F - 1)];
-        prevX[e] = cmulc(prevX[e], ph); // conj(phase) * X_tail
+        const cf ph = a.tw[((uint32_t)m * tau) & (W::F - 1)]; // W_F^(tau m): the head sits tau samples behind the tail
+        const cf z = cmulc(prevX[e], ph);                  // conj(phase) * X_tail
+        if constexpr (WITH_R) {
+          accR[e] = cmacc(accR[e], v[e], z);
+          accB[0][e] = cmacc(accB[0][e], yv[e], z);
+        } else {
+          prevX[e] = z; // kept for every channel
+        }
       }
-    if (WITH_R) {
-      load_xs(0u, tau, v); // head of xs
-      fwd(v);
+    if constexpr (!WITH_R) {
 #pragma unroll
-      for (int e = 0; e < 16; e++) accR[e] = cmacc(accR[e], v[e], prevX[e]);
-    }
+      for (int c = 0; c < NB; c++) {
+        load_y(c, 0u, tau, yv); // head of y
+        fwd(yv);
 #pragma unroll
-    for (int c = 0; c < NB; c++) {
-      load_y(c, 0u, tau, yv); // head of y
-      fwd(yv);
-#pragma unroll
-      for (int e = 0; e < 16; e++) accB[c][e] = cmacc(accB[c][e], yv[e], prevX[e]);
+        for (int e = 0; e < 16; e++) accB[c][e] = cmacc(accB[c][e], yv[e], prevX[e]);
+      }
     }
   }
-  auto finish = [&](cf *acc, int row) {
-    W::inv_s1(t, acc, tw3, P);
-    __syncthreads();
-    W::inv_s2(t, acc, P, Q);
-    __syncthreads();
-    W::inv_s3(t, acc, tw1, Q);
-    cf *dst = a.partial + (((size_t)cpi * a.rows + row) * a.nJobs + blockIdx.x) * a.nBins;
-#pragma unroll
-    for (int c = 0; c < 16; c++) {
-      const int k = t + T * c;
-      if (k < a.nBins) dst[k] = cmake(acc[c].x * a.scale, acc[c].y * a.scale);
-    }
-    __syncthreads();
-  };
-  if (WITH_R) finish(accR, 0);
-  finish(accB[0], a.row0);
-  if (NB > 1) finish(accB[NB - 1], a.row0 + 1);
+  const int rows = PAIR ? 2 : a.rows, row0 = PAIR ? 1 : a.row0;
+  if (WITH_R) corr_finish<R3>(a, t, accR, rows, 0, tw1, tw3, P, Q);
+  corr_finish<R3>(a, t, accB[0], rows, row0, tw1, tw3, P, Q);
+  if (NB > 1) corr_finish<R3>(a, t, accB[NB - 1], rows, row0 + 1, tw1, tw3, P, Q);
 }
 
 // ---- reduction of the partials (fp64), then the Toeplitz solve -----------------
@@ -1747,6 +1549,38 @@ void clutter_grids(const blah2hip_clutter_s *h, uint32_t nCpi, int *nJobs, int *
   *firGrid = std::min(h->firGrid, up8((2 * slots + (int)nCpi - 1) / (int)nCpi));
 }
 
+// The run-time transform length (r3 = F / 256) and sample format as compile-time arguments: f(R3, In) with R3 a
+// std::integral_constant and In a value of the format's type.  WITH_I16 = false for the multi entry point, which has
+// refused BLAH2HIP_FMT_I16 by then: nothing of its path is instantiated for InI16.
+template <bool WITH_I16 = true, class F> int dispatch_r3_fmt(int r3, int fmt, F &&f)
+{
+  auto on_fmt = [&](auto R3) {
+    if constexpr (WITH_I16)
+      if (fmt == BLAH2HIP_FMT_I16) return f(R3, InI16{});
+    if (fmt == BLAH2HIP_FMT_I8) return f(R3, InI8{});
+    return f(R3, InC32{});
+  };
+  switch (r3) {
+  case 4: return on_fmt(std::integral_constant<int, 4>{});
+  case 8: return on_fmt(std::integral_constant<int, 8>{});
+  default: return on_fmt(std::integral_constant<int, 16>{});
+  }
+}
+
+// the plan's part of the correlation kernels' arguments; the caller adds the planes, the partials and their rows
+CorrArgs corr_args(const blah2hip_clutter_s *h, const XsMap &xs, int nJobs, int64_t stride)
+{
+  CorrArgs ca{};
+  ca.cpiStride = stride; ca.N = h->N; ca.xs = xs; ca.nBins = h->nBins; ca.nJobs = nJobs;
+  ca.tw = h->d_tw; ca.scale = 1.0f / (float)h->F;
+  if (h->corrHalf) {
+    ca.half.nSeg = (int)((h->N + (uint32_t)(h->F / 2) - 1) / (uint32_t)(h->F / 2)); ca.half.per = (ca.half.nSeg + nJobs - 1) / nJobs;
+  } else {
+    ca.win.segLen = h->segLen; ca.win.nSeg = h->nSeg;
+  }
+  return ca;
+}
+
 // groups > 1 (the block form, launch_clutter_blocks, where the caller's CPIs do not lie back to back): the nCpi CPIs are
 // `groups` runs of nCpi / groups CPIs, `stride` apart inside a run, run q starting groupStride samples behind run q - 1.
 // The correlations are then one launch per run into that run's rows of the partials; the reduction and the solve stay one
@@ -1758,13 +1592,9 @@ template <int R3, class In> int launch_clutter(blah2hip_clutter_s *h, const void
   using W = WgFft<R3>;
   const size_t lds = (size_t)(W::A_ELEMS + W::B_ELEMS) * sizeof(cf);
   // once per (device, kernel), see capi.hip
-  CHIP(blah2hip_ensure_lds_((const void *)clutter_corr_kernel<R3, In>, (int)lds));
+  CHIP(blah2hip_ensure_lds_((const void *)clutter_corr_kernel<R3, In, true, 1>, (int)lds));
   CHIP(blah2hip_ensure_lds_((const void *)clutter_fir_kernel<R3, In>, (int)lds));
-  XsMap xs;
-  xs.N = h->N;
-  xs.thresh = h->delayMin > 0 ? (uint32_t)h->delayMin : 0u;
-  xs.sub = (uint32_t)h->delayMin;
-  xs.wrapC = (uint32_t)(((1ull << 32) - (uint64_t)(h->delayMin > 0 ? h->delayMin : 0)) % h->N);
+  const XsMap xs = xs_map(h->delayMin, h->N);
   // Workgroups per CPI shrink as the batch grows: a correlation workgroup ends with two
   // inverse transforms and a partial write, a FIR workgroup starts with the transform of
   // the taps -- per-workgroup costs that a long walk over segments amortises.  Two
@@ -1779,21 +1609,14 @@ template <int R3, class In> int launch_clutter(blah2hip_clutter_s *h, const void
     const int64_t qoff = (int64_t)q * groupStride * BufChanOf<In>::X::STRIDE;
     const void *qx = (const char *)px + qoff;
     const void *qy = py ? (const char *)py + qoff : nullptr;
-    cf *qpartial = h->d_partial + (size_t)q * perRun * 2 * nJobs * h->nBins;
+    CorrArgs ca = corr_args(h, xs, nJobs, stride);
+    ca.x = qx; ca.y0 = ca.y1 = qy; ca.rows = 2; ca.row0 = 1; // r and b: [nCpi][2][nJobs][nBins]
+    ca.partial = h->d_partial + (size_t)q * perRun * 2 * nJobs * h->nBins;
     if (h->corrHalf) {
-      CHIP(blah2hip_ensure_lds_((const void *)clutter_corr_half_kernel<R3, In>, (int)lds));
-      CorrHalfArgs ha;
-      ha.x = qx; ha.y = qy; ha.cpiStride = stride; ha.N = h->N; ha.xs = xs;
-      ha.nBins = h->nBins; ha.nSeg = (int)((h->N + (uint32_t)(h->F / 2) - 1) / (uint32_t)(h->F / 2));
-      ha.per = (ha.nSeg + nJobs - 1) / nJobs; ha.nJobs = nJobs;
-      ha.tw = h->d_tw; ha.partial = qpartial; ha.scale = 1.0f / (float)h->F;
-      hipLaunchKernelGGL((clutter_corr_half_kernel<R3, In>), dim3(nJobs, perRun), dim3(W::T), lds, st, ha);
+      CHIP(blah2hip_ensure_lds_((const void *)clutter_corr_half_kernel<R3, In, true, 1, true>, (int)lds));
+      hipLaunchKernelGGL((clutter_corr_half_kernel<R3, In, true, 1, true>), dim3(nJobs, perRun), dim3(W::T), lds, st, ca);
     } else {
-      CorrArgs ca;
-      ca.x = qx; ca.y = qy; ca.cpiStride = stride; ca.N = h->N; ca.xs = xs;
-      ca.nBins = h->nBins; ca.segLen = h->segLen; ca.nSeg = h->nSeg; ca.nJobs = nJobs;
-      ca.tw = h->d_tw; ca.partial = qpartial; ca.scale = 1.0f / (float)h->F;
-      hipLaunchKernelGGL((clutter_corr_kernel<R3, In>), dim3(nJobs, perRun), dim3(W::T), lds, st, ca);
+      hipLaunchKernelGGL((clutter_corr_kernel<R3, In, true, 1>), dim3(nJobs, perRun), dim3(W::T), lds, st, ca);
     }
   }
   CHIP(hipGetLastError());
@@ -1884,10 +1707,7 @@ template <int R3, class In> int launch_clutter_blocks(blah2hip_clutter_s *h, con
   if (corr_direct(c)) { // short blocks: r and b lag by lag in fp64, straight into the solve's input
     CorrDirectArgs da;
     da.x = px; da.y = py; da.cpiStride = stride;
-    da.xs.N = L;
-    da.xs.thresh = c->delayMin > 0 ? (uint32_t)c->delayMin : 0u;
-    da.xs.sub = (uint32_t)c->delayMin;
-    da.xs.wrapC = (uint32_t)(((1ull << 32) - (uint64_t)(c->delayMin > 0 ? c->delayMin : 0)) % L);
+    da.xs = xs_map(c->delayMin, L);
     da.nBins = c->nBins; da.B = (int32_t)B; da.lagTiles = (c->nBins + 255) / 256; da.rb = c->d_rb;
     CHIP(c->timer.tic(BLAH2HIP_CK_CORR, st));
     hipLaunchKernelGGL((clutter_corr_direct_kernel<In>), dim3(V * (uint32_t)da.lagTiles, 2), dim3(256), 0, st, da);
@@ -1916,10 +1736,7 @@ template <int R3, class In> int launch_clutter_blocks(blah2hip_clutter_s *h, con
   CHIP(blah2hip_ensure_lds_((const void *)clutter_fir_blocks_kernel<R3, In>, (int)lds));
   FirBlocksArgs fa;
   fa.x = px; fa.y = py; fa.yout = yout; fa.cpiStride = stride; fa.outStride = outStride;
-  fa.xs.N = h->N;
-  fa.xs.thresh = h->delayMin > 0 ? (uint32_t)h->delayMin : 0u;
-  fa.xs.sub = (uint32_t)h->delayMin;
-  fa.xs.wrapC = (uint32_t)(((1ull << 32) - (uint64_t)(h->delayMin > 0 ? h->delayMin : 0)) % h->N);
+  fa.xs = xs_map(h->delayMin, h->N);
   fa.nBins = c->nBins; fa.segLen = c->segLen; fa.nSeg = c->nSeg; // the child's plan: segments of a block
   fa.L = (int32_t)L; fa.B = (int32_t)B; fa.nVirt = (int32_t)V;
   // workgroups per virtual CPI: two resident generations over the launch (clutter_grids), at most one per segment
@@ -1932,23 +1749,6 @@ template <int R3, class In> int launch_clutter_blocks(blah2hip_clutter_s *h, con
   CHIP(hipGetLastError());
   CHIP(h->timer.toc(BLAH2HIP_CK_FIR, st));
   return BLAH2HIP_OK;
-}
-
-template <class In> int dispatch_blocks(blah2hip_clutter_s *h, const void *px, const void *py, uint32_t nCpi, int64_t stride,
-                                        cf *yout, int64_t outStride, int32_t *ok, hipStream_t st)
-{
-  switch (h->blk->r3) {
-  case 4: return launch_clutter_blocks<4, In>(h, px, py, nCpi, stride, yout, outStride, ok, st);
-  case 8: return launch_clutter_blocks<8, In>(h, px, py, nCpi, stride, yout, outStride, ok, st);
-  default: return launch_clutter_blocks<16, In>(h, px, py, nCpi, stride, yout, outStride, ok, st);
-  }
-}
-int process_blocks(blah2hip_clutter_s *h, int fmt, const void *px, const void *py, uint32_t nCpi, int64_t stride, cf *yout,
-                   int64_t outStride, int32_t *ok, hipStream_t st)
-{
-  if (fmt == BLAH2HIP_FMT_I16) return dispatch_blocks<InI16>(h, px, nullptr, nCpi, stride, yout, outStride, ok, st);
-  if (fmt == BLAH2HIP_FMT_I8) return dispatch_blocks<InI8>(h, px, py, nCpi, stride, yout, outStride, ok, st);
-  return dispatch_blocks<InC32>(h, px, py, nCpi, stride, yout, outStride, ok, st);
 }
 
 // ---- several surveillance channels against one reference ----------------------------------------------------------------
@@ -2012,42 +1812,35 @@ template <int R3, class In> int launch_clutter_multi(blah2hip_clutter_s *h, cons
 {
   using W = WgFft<R3>;
   const size_t lds = (size_t)(W::A_ELEMS + W::B_ELEMS) * sizeof(cf);
-  XsMap xs;
-  xs.N = h->N;
-  xs.thresh = h->delayMin > 0 ? (uint32_t)h->delayMin : 0u;
-  xs.sub = (uint32_t)h->delayMin;
-  xs.wrapC = (uint32_t)(((1ull << 32) - (uint64_t)(h->delayMin > 0 ? h->delayMin : 0)) % h->N);
+  const XsMap xs = xs_map(h->delayMin, h->N);
   int nJobs, firGrid;
   clutter_grids(h, nCpi, &nJobs, &firGrid);
   const int rows = (int)((K + 2) & ~1u);
 
-  CorrMultiArgs ca;
-  ca.x = px; ca.cpiStride = stride; ca.N = h->N; ca.xs = xs; ca.nBins = h->nBins; ca.nJobs = nJobs;
-  ca.tw = h->d_tw; ca.partial = h->d_partialM; ca.scale = 1.0f / (float)h->F; ca.rows = rows;
+  CorrArgs ca = corr_args(h, xs, nJobs, stride);
+  ca.x = px; ca.partial = h->d_partialM; ca.rows = rows;
   if (h->corrHalf) {
-    ca.segLen = 0; ca.nSeg = (int)((h->N + (uint32_t)(h->F / 2) - 1) / (uint32_t)(h->F / 2)); ca.per = (ca.nSeg + nJobs - 1) / nJobs;
-    CHIP(blah2hip_ensure_lds_((const void *)clutter_corr_half_multi_kernel<R3, In, true, 1>, (int)lds));
-    CHIP(blah2hip_ensure_lds_((const void *)clutter_corr_half_multi_kernel<R3, In, false, 1>, (int)lds));
-    CHIP(blah2hip_ensure_lds_((const void *)clutter_corr_half_multi_kernel<R3, In, false, 2>, (int)lds));
+    CHIP(blah2hip_ensure_lds_((const void *)clutter_corr_half_kernel<R3, In, true, 1>, (int)lds));
+    CHIP(blah2hip_ensure_lds_((const void *)clutter_corr_half_kernel<R3, In, false, 1>, (int)lds));
+    CHIP(blah2hip_ensure_lds_((const void *)clutter_corr_half_kernel<R3, In, false, 2>, (int)lds));
   } else {
-    ca.segLen = h->segLen; ca.nSeg = h->nSeg; ca.per = 0;
-    CHIP(blah2hip_ensure_lds_((const void *)clutter_corr_multi_kernel<R3, In, true, 1>, (int)lds));
-    CHIP(blah2hip_ensure_lds_((const void *)clutter_corr_multi_kernel<R3, In, false, 1>, (int)lds));
-    CHIP(blah2hip_ensure_lds_((const void *)clutter_corr_multi_kernel<R3, In, false, 2>, (int)lds));
+    CHIP(blah2hip_ensure_lds_((const void *)clutter_corr_kernel<R3, In, true, 1>, (int)lds));
+    CHIP(blah2hip_ensure_lds_((const void *)clutter_corr_kernel<R3, In, false, 1>, (int)lds));
+    CHIP(blah2hip_ensure_lds_((const void *)clutter_corr_kernel<R3, In, false, 2>, (int)lds));
   }
   const dim3 cg(nJobs, nCpi), cb(W::T);
   CHIP(h->timer.tic(BLAH2HIP_CK_CORR, st));
   for (uint32_t k = 0; k < K;) { // r and b_0, then the other channels in pairs
     const uint32_t nb = k == 0 ? 1u : std::min<uint32_t>(CORR_TILE, K - k);
-    ca.y[0] = pys[k]; ca.y[1] = pys[k + nb - 1]; ca.row0 = 1 + (int)k;
+    ca.y0 = pys[k]; ca.y1 = pys[k + nb - 1]; ca.row0 = 1 + (int)k;
     if (h->corrHalf) {
-      if (k == 0) hipLaunchKernelGGL((clutter_corr_half_multi_kernel<R3, In, true, 1>), cg, cb, lds, st, ca);
-      else if (nb == 1) hipLaunchKernelGGL((clutter_corr_half_multi_kernel<R3, In, false, 1>), cg, cb, lds, st, ca);
-      else hipLaunchKernelGGL((clutter_corr_half_multi_kernel<R3, In, false, 2>), cg, cb, lds, st, ca);
+      if (k == 0) hipLaunchKernelGGL((clutter_corr_half_kernel<R3, In, true, 1>), cg, cb, lds, st, ca);
+      else if (nb == 1) hipLaunchKernelGGL((clutter_corr_half_kernel<R3, In, false, 1>), cg, cb, lds, st, ca);
+      else hipLaunchKernelGGL((clutter_corr_half_kernel<R3, In, false, 2>), cg, cb, lds, st, ca);
     } else {
-      if (k == 0) hipLaunchKernelGGL((clutter_corr_multi_kernel<R3, In, true, 1>), cg, cb, lds, st, ca);
-      else if (nb == 1) hipLaunchKernelGGL((clutter_corr_multi_kernel<R3, In, false, 1>), cg, cb, lds, st, ca);
-      else hipLaunchKernelGGL((clutter_corr_multi_kernel<R3, In, false, 2>), cg, cb, lds, st, ca);
+      if (k == 0) hipLaunchKernelGGL((clutter_corr_kernel<R3, In, true, 1>), cg, cb, lds, st, ca);
+      else if (nb == 1) hipLaunchKernelGGL((clutter_corr_kernel<R3, In, false, 1>), cg, cb, lds, st, ca);
+      else hipLaunchKernelGGL((clutter_corr_kernel<R3, In, false, 2>), cg, cb, lds, st, ca);
     }
     k += nb;
   }
@@ -2210,6 +2003,44 @@ int long_process(blah2hip_clutter_s *h, const cf *d_x, const cf *d_y, uint32_t n
   h->lastOk = ok;
   h->lastStream = st;
   return BLAH2HIP_OK;
+}
+
+// blah2hip_clutter_process_dev_fmt, and with `estimate` blah2hip_clutter_estimate_dev_fmt: no output plane, the taps only
+int filter_one_channel(blah2hip_clutter_t h, int fmt, const void *d_x, const void *d_y, uint32_t n_cpi, uint64_t cpi_stride,
+                       void *d_y_out, uint64_t out_stride, int32_t *d_ok, void *stream, bool estimate)
+{
+  if (!h || !d_x || (!estimate && !d_y_out)) CFAIL(BLAH2HIP_ERR_INVALID, "NULL argument");
+  if (fmt != BLAH2HIP_FMT_C32 && fmt != BLAH2HIP_FMT_I16 && fmt != BLAH2HIP_FMT_I8)
+    CFAIL(BLAH2HIP_ERR_INVALID, "clutter filter input: BLAH2HIP_FMT_C32, BLAH2HIP_FMT_I16 or BLAH2HIP_FMT_I8");
+  if (fmt != BLAH2HIP_FMT_I16 && !d_y) CFAIL(BLAH2HIP_ERR_INVALID, "NULL argument");
+  if (n_cpi == 0 || n_cpi > h->maxBatch) CFAIL(BLAH2HIP_ERR_INVALID, "n_cpi outside [1, max_batch]");
+  if (estimate) {
+    if (n_cpi > 1 && cpi_stride < h->N) CFAIL(BLAH2HIP_ERR_INVALID, "cpi_stride < nSamples");
+  } else {
+#ifndef B2_EXPERIMENT_ALIASED_CPIS // tools/gpu_cfg3_bytes.py
+    if (n_cpi > 1 && (cpi_stride < h->N || out_stride < h->N)) CFAIL(BLAH2HIP_ERR_INVALID, "cpi_stride / out_stride < nSamples");
+#endif
+  }
+  CHIP(hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  int32_t *ok = d_ok ? d_ok : (h->blk ? h->blk->d_ok : h->d_ok);
+  // in-place operation (FMT_C32, d_y_out == d_y) is safe: every output sample is read (as y) by the one
+  // thread that writes it, and x is never written
+  const int64_t cs = (int64_t)cpi_stride, os = (int64_t)out_stride;
+  cf *yo = (cf *)d_y_out;
+  if (fmt == BLAH2HIP_FMT_I16) d_y = nullptr; // the surveillance channel rides in the reference's words
+  if (h->blk) // d_ok: [n_cpi][n_blocks]
+    return dispatch_r3_fmt(h->blk->r3, fmt, [&](auto R3, auto in) {
+      return launch_clutter_blocks<decltype(R3)::value, decltype(in)>(h, d_x, d_y, n_cpi, cs, yo, os, ok, st);
+    });
+  if (h->subCorr) {
+    if (fmt == BLAH2HIP_FMT_I8) CFAIL(BLAH2HIP_ERR_UNSUPPORTED, "a long filter (more than 4081 taps) takes fp32 planes only, not BLAH2HIP_FMT_I8");
+    if (fmt != BLAH2HIP_FMT_C32) CFAIL(BLAH2HIP_ERR_UNSUPPORTED, "a long filter (more than 4081 taps) takes fp32 planes only");
+    return long_process(h, (const cf *)d_x, (const cf *)d_y, n_cpi, cs, yo, os, ok, st);
+  }
+  return dispatch_r3_fmt(h->r3, fmt, [&](auto R3, auto in) {
+    return launch_clutter<decltype(R3)::value, decltype(in)>(h, d_x, d_y, n_cpi, cs, yo, os, ok, st);
+  });
 }
 
 } // namespace
@@ -2547,86 +2378,13 @@ int blah2hip_clutter_get_timing(blah2hip_clutter_t h, double *ms_total, uint32_t
 int blah2hip_clutter_process_dev_fmt(blah2hip_clutter_t h, int fmt, const void *d_x, const void *d_y, uint32_t n_cpi,
                                      uint64_t cpi_stride, void *d_y_out, uint64_t out_stride, int32_t *d_ok, void *stream)
 {
-  if (!h || !d_x || !d_y_out) CFAIL(BLAH2HIP_ERR_INVALID, "NULL argument");
-  if (fmt != BLAH2HIP_FMT_C32 && fmt != BLAH2HIP_FMT_I16 && fmt != BLAH2HIP_FMT_I8)
-    CFAIL(BLAH2HIP_ERR_INVALID, "clutter filter input: BLAH2HIP_FMT_C32, BLAH2HIP_FMT_I16 or BLAH2HIP_FMT_I8");
-  if (fmt != BLAH2HIP_FMT_I16 && !d_y) CFAIL(BLAH2HIP_ERR_INVALID, "NULL argument");
-  if (n_cpi == 0 || n_cpi > h->maxBatch) CFAIL(BLAH2HIP_ERR_INVALID, "n_cpi outside [1, max_batch]");
-#ifndef B2_EXPERIMENT_ALIASED_CPIS // tools/gpu_cfg3_bytes.py
-  if (n_cpi > 1 && (cpi_stride < h->N || out_stride < h->N)) CFAIL(BLAH2HIP_ERR_INVALID, "cpi_stride / out_stride < nSamples");
-#endif
-  CHIP(hipSetDevice(h->device));
-  hipStream_t st = (hipStream_t)stream;
-  int32_t *ok = d_ok ? d_ok : (h->blk ? h->blk->d_ok : h->d_ok);
-  // in-place operation (FMT_C32, d_y_out == d_y) is safe: every output sample is read (as y) by the one
-  // thread that writes it, and x is never written
-  const int64_t cs = (int64_t)cpi_stride, os = (int64_t)out_stride;
-  cf *yo = (cf *)d_y_out;
-  if (h->blk) return process_blocks(h, fmt, d_x, d_y, n_cpi, cs, yo, os, ok, st); // d_ok: [n_cpi][n_blocks]
-  if (h->subCorr) {
-    if (fmt == BLAH2HIP_FMT_I8) CFAIL(BLAH2HIP_ERR_UNSUPPORTED, "a long filter (more than 4081 taps) takes fp32 planes only, not BLAH2HIP_FMT_I8");
-    if (fmt != BLAH2HIP_FMT_C32) CFAIL(BLAH2HIP_ERR_UNSUPPORTED, "a long filter (more than 4081 taps) takes fp32 planes only");
-    return long_process(h, (const cf *)d_x, (const cf *)d_y, n_cpi, cs, yo, os, ok, st);
-  }
-  if (fmt == BLAH2HIP_FMT_I16) {
-    switch (h->r3) {
-    case 4: return launch_clutter<4, InI16>(h, d_x, nullptr, n_cpi, cs, yo, os, ok, st);
-    case 8: return launch_clutter<8, InI16>(h, d_x, nullptr, n_cpi, cs, yo, os, ok, st);
-    default: return launch_clutter<16, InI16>(h, d_x, nullptr, n_cpi, cs, yo, os, ok, st);
-    }
-  }
-  if (fmt == BLAH2HIP_FMT_I8) {
-    switch (h->r3) {
-    case 4: return launch_clutter<4, InI8>(h, d_x, d_y, n_cpi, cs, yo, os, ok, st);
-    case 8: return launch_clutter<8, InI8>(h, d_x, d_y, n_cpi, cs, yo, os, ok, st);
-    default: return launch_clutter<16, InI8>(h, d_x, d_y, n_cpi, cs, yo, os, ok, st);
-    }
-  }
-  switch (h->r3) {
-  case 4: return launch_clutter<4, InC32>(h, d_x, d_y, n_cpi, cs, yo, os, ok, st);
-  case 8: return launch_clutter<8, InC32>(h, d_x, d_y, n_cpi, cs, yo, os, ok, st);
-  default: return launch_clutter<16, InC32>(h, d_x, d_y, n_cpi, cs, yo, os, ok, st);
-  }
+  return filter_one_channel(h, fmt, d_x, d_y, n_cpi, cpi_stride, d_y_out, out_stride, d_ok, stream, false);
 }
 
 int blah2hip_clutter_estimate_dev_fmt(blah2hip_clutter_t h, int fmt, const void *d_x, const void *d_y, uint32_t n_cpi,
                                       uint64_t cpi_stride, int32_t *d_ok, void *stream)
 {
-  if (!h || !d_x) CFAIL(BLAH2HIP_ERR_INVALID, "NULL argument");
-  if (fmt != BLAH2HIP_FMT_C32 && fmt != BLAH2HIP_FMT_I16 && fmt != BLAH2HIP_FMT_I8)
-    CFAIL(BLAH2HIP_ERR_INVALID, "clutter filter input: BLAH2HIP_FMT_C32, BLAH2HIP_FMT_I16 or BLAH2HIP_FMT_I8");
-  if (fmt != BLAH2HIP_FMT_I16 && !d_y) CFAIL(BLAH2HIP_ERR_INVALID, "NULL argument");
-  if (n_cpi == 0 || n_cpi > h->maxBatch) CFAIL(BLAH2HIP_ERR_INVALID, "n_cpi outside [1, max_batch]");
-  if (n_cpi > 1 && cpi_stride < h->N) CFAIL(BLAH2HIP_ERR_INVALID, "cpi_stride < nSamples");
-  CHIP(hipSetDevice(h->device));
-  hipStream_t st = (hipStream_t)stream;
-  int32_t *ok = d_ok ? d_ok : (h->blk ? h->blk->d_ok : h->d_ok);
-  const int64_t cs = (int64_t)cpi_stride;
-  if (h->blk) return process_blocks(h, fmt, d_x, d_y, n_cpi, cs, nullptr, 0, ok, st);
-  if (h->subCorr) {
-    if (fmt == BLAH2HIP_FMT_I8) CFAIL(BLAH2HIP_ERR_UNSUPPORTED, "a long filter (more than 4081 taps) takes fp32 planes only, not BLAH2HIP_FMT_I8");
-    if (fmt != BLAH2HIP_FMT_C32) CFAIL(BLAH2HIP_ERR_UNSUPPORTED, "a long filter (more than 4081 taps) takes fp32 planes only");
-    return long_process(h, (const cf *)d_x, (const cf *)d_y, n_cpi, cs, nullptr, 0, ok, st);
-  }
-  if (fmt == BLAH2HIP_FMT_I16) {
-    switch (h->r3) {
-    case 4: return launch_clutter<4, InI16>(h, d_x, nullptr, n_cpi, cs, nullptr, 0, ok, st);
-    case 8: return launch_clutter<8, InI16>(h, d_x, nullptr, n_cpi, cs, nullptr, 0, ok, st);
-    default: return launch_clutter<16, InI16>(h, d_x, nullptr, n_cpi, cs, nullptr, 0, ok, st);
-    }
-  }
-  if (fmt == BLAH2HIP_FMT_I8) {
-    switch (h->r3) {
-    case 4: return launch_clutter<4, InI8>(h, d_x, d_y, n_cpi, cs, nullptr, 0, ok, st);
-    case 8: return launch_clutter<8, InI8>(h, d_x, d_y, n_cpi, cs, nullptr, 0, ok, st);
-    default: return launch_clutter<16, InI8>(h, d_x, d_y, n_cpi, cs, nullptr, 0, ok, st);
-    }
-  }
-  switch (h->r3) {
-  case 4: return launch_clutter<4, InC32>(h, d_x, d_y, n_cpi, cs, nullptr, 0, ok, st);
-  case 8: return launch_clutter<8, InC32>(h, d_x, d_y, n_cpi, cs, nullptr, 0, ok, st);
-  default: return launch_clutter<16, InC32>(h, d_x, d_y, n_cpi, cs, nullptr, 0, ok, st);
-  }
+  return filter_one_channel(h, fmt, d_x, d_y, n_cpi, cpi_stride, nullptr, 0, d_ok, stream, true);
 }
 
 int blah2hip_clutter_process_multi_dev_fmt(blah2hip_clutter_t h, int fmt, const void *d_x, const void *const *d_y, uint32_t n_surv,
@@ -2665,18 +2423,10 @@ int blah2hip_clutter_process_multi_dev_fmt(blah2hip_clutter_t h, int fmt, const 
         CHIP(hipMemcpy2DAsync(h->d_rbM, rows * n * sizeof(dcx), h->d_rb, 2 * n * sizeof(dcx), n * sizeof(dcx), n_cpi, hipMemcpyDeviceToDevice, st));
       CHIP(hipMemcpy2DAsync(h->d_rbM + (1 + k) * n, rows * n * sizeof(dcx), h->d_rb + n, 2 * n * sizeof(dcx), n * sizeof(dcx), n_cpi, hipMemcpyDeviceToDevice, st));
     }
-  } else if (fmt == BLAH2HIP_FMT_I8) {
-    switch (h->r3) {
-    case 4: rc = launch_clutter_multi<4, InI8>(h, d_x, d_y, n_surv, n_cpi, cs, d_y_out, os, ok, st); break;
-    case 8: rc = launch_clutter_multi<8, InI8>(h, d_x, d_y, n_surv, n_cpi, cs, d_y_out, os, ok, st); break;
-    default: rc = launch_clutter_multi<16, InI8>(h, d_x, d_y, n_surv, n_cpi, cs, d_y_out, os, ok, st); break;
-    }
   } else {
-    switch (h->r3) {
-    case 4: rc = launch_clutter_multi<4, InC32>(h, d_x, d_y, n_surv, n_cpi, cs, d_y_out, os, ok, st); break;
-    case 8: rc = launch_clutter_multi<8, InC32>(h, d_x, d_y, n_surv, n_cpi, cs, d_y_out, os, ok, st); break;
-    default: rc = launch_clutter_multi<16, InC32>(h, d_x, d_y, n_surv, n_cpi, cs, d_y_out, os, ok, st); break;
-    }
+    rc = dispatch_r3_fmt<false>(h->r3, fmt, [&](auto R3, auto in) {
+      return launch_clutter_multi<decltype(R3)::value, decltype(in)>(h, d_x, d_y, n_surv, n_cpi, cs, d_y_out, os, ok, st);
+    });
   }
   if (rc) return rc;
   h->lastSurv = n_surv; h->lastNCpi = n_cpi;
