@@ -43,9 +43,11 @@ LEAK_OFF, LEAK_AUTO, LEAK_ALWAYS = 0, 1, 2
 CFAR2D_AUTO, CFAR2D_TILE, CFAR2D_SAT, CFAR2D_STREAM = 0, 1, 2, 3
 CLUTTER_OPT_SOLVE_K, CLUTTER_OPT_FFT_LEN, CLUTTER_OPT_CORR, CLUTTER_OPT_SOLVE_FORM, CLUTTER_OPT_SOLVE_E, CLUTTER_OPT_FIR_CARRY = 1, 2, 3, 4, 5, 6
 CLUTTER_OPT_SOLVE_SPIN_LIMIT = 7
+CLUTTER_OPT_CORR_GRID = 8
 CLUTTER_SOLVE_AUTO, CLUTTER_SOLVE_STEPWISE, CLUTTER_SOLVE_LOOKAHEAD = 0, 1, 2
 CLUTTER_INFO_SOLVE_FORM, CLUTTER_INFO_SOLVE_E, CLUTTER_INFO_SOLVE_G, CLUTTER_INFO_SOLVE_FAULT, CLUTTER_INFO_SOLVE_RETRIES = 1, 2, 3, 4, 5
 CLUTTER_INFO_CORR_FORM, CLUTTER_INFO_FIR_CARRY, CLUTTER_INFO_CHUNKS, CLUTTER_INFO_BLOCKS = 6, 7, 8, 9
+CLUTTER_INFO_CORR_GRID = 10
 CLUTTER_CORR_AUTO, CLUTTER_CORR_HALF, CLUTTER_CORR_WINDOW, CLUTTER_CORR_DIRECT = 0, 1, 2, 3
 DOP_AUTO, DOP_TILE8, DOP_TILE16, DOP_TILEM, DOP_COLUMN, DOP_DIRECT, DOP_TILEW, DOP_TILEW2, DOP_TILE16WG, DOP_SUB4, DOP_TILE8K, DOP_TILEW4 = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11
 DOP_PFA513 = 12

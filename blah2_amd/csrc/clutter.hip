@@ -1310,6 +1310,8 @@ struct blah2hip_clutter_s {
   bool corrHalf = false;     // half-window correlation (2 transforms per F/2 samples) instead of the windowed one
   int fftLenForce = 0;       // BLAH2HIP_CLUTTER_OPT_FFT_LEN (0 = planner)
   int corrForce = 0;         // BLAH2HIP_CLUTTER_OPT_CORR
+  int corrGrid = 0;          // BLAH2HIP_CLUTTER_OPT_CORR_GRID (0 = clutter_grids' own; a re-plan returns to 0)
+  int lastCorrGrid = 0;      // BLAH2HIP_CLUTTER_INFO_CORR_GRID
   int32_t *lastOk = nullptr; // where the last process call wrote its flags
   hipStream_t lastStream = nullptr; // ... and the stream it was enqueued on (blah2hip_clutter_get_info waits for that one only)
   KernelTimer<BLAH2HIP_CK_COUNT> timer;
@@ -1323,6 +1325,7 @@ struct blah2hip_clutter_s {
   // several surveillance channels on one reference (blah2hip_clutter_process_multi_dev_fmt): built by the first such call
   // for the channels it asks for, kept apart from d_w / d_rb (an ambiguity handle may hold d_w, blah2hip_amb_set_fir)
   uint32_t multiK = 0;         // channels the buffers below hold
+  size_t multiJobs = 0;        // n_cpi x (workgroups per CPI) that d_partialM holds
   cf *d_partialM = nullptr;    // [n_cpi][rows][nJobs][nBins], rows = 1 + K rounded up to even: r, b_0 .. b_{K-1}
   dcx *d_rbM = nullptr;        // [n_cpi][rows][nBins]
   cf *d_wM = nullptr;          // [K][n_cpi][nBins]: virtual CPI k n_cpi + c
@@ -1347,7 +1350,7 @@ hipError_t multi_free(blah2hip_clutter_s *h)
     if (*p) { hipError_t e = hipFree(*p); if (e != hipSuccess) return e; }
     *p = nullptr;
   }
-  h->multiK = 0;
+  h->multiK = 0; h->multiJobs = 0;
   if (h->lastSurv) { h->lastSurv = 0; h->lastOk = nullptr; }
   return hipSuccess;
 }
@@ -1448,6 +1451,7 @@ int clutter_plan(blah2hip_clutter_s *h)
   if (h->corrForce == BLAH2HIP_CLUTTER_CORR_WINDOW) h->corrHalf = false;
   auto up8 = [](int v) { return std::max(8, (v + 7) & ~7); };
   h->nJobs = up8(std::min(h->nSeg, 2 * h->numCU)); // partial correlations per CPI (x2 modes in one workgroup)
+  h->corrGrid = 0; // a forced grid was checked against the previous plan's nJobs
   h->firGrid = up8(std::min(h->nSeg, 8 * h->numCU));
   std::vector<cf> tw(h->F);
   for (int k = 0; k < h->F; k++) {
@@ -1540,13 +1544,15 @@ __global__ void solve_epoch_kernel(uint32_t *epoch)
 }
 
 // workgroups per CPI of the correlation and FIR kernels at a batch of nCpi (see launch_clutter)
-void clutter_grids(const blah2hip_clutter_s *h, uint32_t nCpi, int *nJobs, int *firGrid)
+// planned: the planner's nJobs whatever BLAH2HIP_CLUTTER_OPT_CORR_GRID says (multi_alloc: the buffer must hold those too)
+void clutter_grids(const blah2hip_clutter_s *h, uint32_t nCpi, int *nJobs, int *firGrid, bool planned = false)
 {
   const int slots = 4 * h->numCU; // residency of these kernels: 4 workgroups per CU (LDS)
   // (multiples of 8: the segment walk is XCD-aware, see seg_walk)
   auto up8 = [](int v) { return std::max(8, (v + 7) & ~7); };
   *nJobs = std::min(h->nJobs, up8((2 * slots + (int)nCpi - 1) / (int)nCpi));
   *firGrid = std::min(h->firGrid, up8((2 * slots + (int)nCpi - 1) / (int)nCpi));
+  if (h->corrGrid && !planned) *nJobs = h->corrGrid; // a multiple of 8 up to h->nJobs (blah2hip_clutter_set_option)
 }
 
 // The run-time transform length (r3 = F / 256) and sample format as compile-time arguments: f(R3, In) with R3 a
@@ -1602,6 +1608,7 @@ template <int R3, class In> int launch_clutter(blah2hip_clutter_s *h, const void
   int nJobs, firGrid;
   clutter_grids(h, nCpi, &nJobs, &firGrid);
   if (h->stages & 1) {
+  h->lastCorrGrid = nJobs;
   CHIP(h->timer.tic(BLAH2HIP_CK_CORR, st));
   const uint32_t perRun = nCpi / groups;
   for (uint32_t q = 0; q < groups; q++) {
@@ -1722,6 +1729,7 @@ template <int R3, class In> int launch_clutter_blocks(blah2hip_clutter_s *h, con
     c->lastSurv = 0;
     c->lastOk = ok;
     c->lastStream = st;
+    c->lastCorrGrid = 0;
   } else {
     c->stages = 3;
     const int rc_ = launch_clutter<R3, In>(c, px, py, V, (int64_t)L, nullptr, 0, ok, st, flat ? 1u : nCpi, stride);
@@ -1752,22 +1760,31 @@ template <int R3, class In> int launch_clutter_blocks(blah2hip_clutter_s *h, con
 }
 
 // ---- several surveillance channels against one reference ----------------------------------------------------------------
-// Buffers for K channels (the first multi call, or one that asks for more channels than the handle has seen): blocking.
+// Buffers for K channels (the first multi call, one that asks for more channels than the handle has seen, or the first
+// with a forced correlation grid that the partials do not hold): blocking.
 int multi_alloc(blah2hip_clutter_s *h, uint32_t K)
 {
-  if (K <= h->multiK) return BLAH2HIP_OK;
+  const size_t forced = (size_t)h->maxBatch * (size_t)h->corrGrid;
+  if (K <= h->multiK && forced <= h->multiJobs) return BLAH2HIP_OK;
+  // the largest n_cpi x (workgroups per CPI) a launch can have: by the planner's grids always (a forced grid may be taken
+  // back with the buffers in place), and by a forced grid at the whole batch where that is more
+  size_t jobs = 0;
+  if (!h->subCorr) {
+    for (uint32_t c = 1; c <= h->maxBatch; c++) {
+      int nJobs, firGrid;
+      clutter_grids(h, c, &nJobs, &firGrid, true);
+      jobs = std::max(jobs, (size_t)c * nJobs);
+    }
+    jobs = std::max(jobs, forced);
+  }
+  K = std::max(K, h->multiK);
   CHIP(hipDeviceSynchronize()); // smaller buffers may still be in use by enqueued work
   CHIP(multi_free(h));
   const size_t rows = (K + 2) & ~1u, n = (size_t)h->nBins;
   if (!h->subCorr) {
-    size_t jobs = 0; // the largest n_cpi x (workgroups per CPI) a launch can have
-    for (uint32_t c = 1; c <= h->maxBatch; c++) {
-      int nJobs, firGrid;
-      clutter_grids(h, c, &nJobs, &firGrid);
-      jobs = std::max(jobs, (size_t)c * nJobs);
-    }
     CHIP(hipMalloc(&h->d_partialM, jobs * rows * n * sizeof(cf)));
     CHIP(hipMemset(h->d_partialM, 0, jobs * rows * n * sizeof(cf))); // (the padding row of an even K is summed like the others)
+    h->multiJobs = jobs;
   }
   CHIP(hipMalloc(&h->d_rbM, (size_t)h->maxBatch * rows * n * sizeof(dcx)));
   CHIP(hipMemset(h->d_rbM, 0, (size_t)h->maxBatch * rows * n * sizeof(dcx)));
@@ -1815,6 +1832,7 @@ template <int R3, class In> int launch_clutter_multi(blah2hip_clutter_s *h, cons
   const XsMap xs = xs_map(h->delayMin, h->N);
   int nJobs, firGrid;
   clutter_grids(h, nCpi, &nJobs, &firGrid);
+  h->lastCorrGrid = nJobs;
   const int rows = (int)((K + 2) & ~1u);
 
   CorrArgs ca = corr_args(h, xs, nJobs, stride);
@@ -2193,6 +2211,7 @@ int blah2hip_clutter_get_info(blah2hip_clutter_t h, int what, int64_t *value)
   }
   case BLAH2HIP_CLUTTER_INFO_FIR_CARRY: *value = (h->subFir ? h->subFir : h)->firCarry ? 1 : 0; return BLAH2HIP_OK;
   case BLAH2HIP_CLUTTER_INFO_CHUNKS: *value = h->nChunks; return BLAH2HIP_OK;
+  case BLAH2HIP_CLUTTER_INFO_CORR_GRID: *value = (h->subCorr ? h->subCorr : h)->lastCorrGrid; return BLAH2HIP_OK;
   case BLAH2HIP_CLUTTER_INFO_SOLVE_FAULT:
   case BLAH2HIP_CLUTTER_INFO_SOLVE_RETRIES: {
     // the stream the handle's last call ran on, not the device (a poll in a pipeline must not stall other streams and
@@ -2273,6 +2292,14 @@ int blah2hip_clutter_set_option(blah2hip_clutter_t h, int option, int64_t value)
   case BLAH2HIP_CLUTTER_OPT_SOLVE_SPIN_LIMIT:
     if (value < 0 || value > (int64_t)0x7fffffff) CFAIL(BLAH2HIP_ERR_INVALID, "polls per bounded wait: 0 (default) ... 2^31 - 1");
     h->spinLimit = value ? (uint32_t)value : sla::SPIN_LIMIT;
+    return BLAH2HIP_OK;
+  case BLAH2HIP_CLUTTER_OPT_CORR_GRID:
+    if (value != 0 && (value < 8 || value > (int64_t)h->nJobs || (value & 7))) {
+      const std::string msg = "correlation grid: 0 (planner) or a multiple of 8 from 8 to " + std::to_string(h->nJobs) +
+                              ", the plan's workgroups per CPI";
+      CFAIL(BLAH2HIP_ERR_INVALID, msg.c_str());
+    }
+    h->corrGrid = (int)value; // (the multi-channel partials follow in multi_alloc, at the next multi call)
     return BLAH2HIP_OK;
   case BLAH2HIP_CLUTTER_OPT_FIR_CARRY: {
     if (value != 0 && value != 1) CFAIL(BLAH2HIP_ERR_INVALID, "FIR carry: 0 or 1");

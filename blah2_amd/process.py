@@ -1155,6 +1155,7 @@ class WienerHopf:
         nb, fl, sl = C.c_uint32(), C.c_uint32(), C.c_uint32()
         check(L.blah2hip_clutter_get_dims(h, C.byref(nb), C.byref(fl), C.byref(sl)))
         self.nBins, self.fft_len, self.seg_len = nb.value, fl.value, sl.value
+        self._corr_grid = 0  # BLAH2HIP_CLUTTER_OPT_CORR_GRID as last set (the library has no read-back; a re-plan returns it to 0)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1228,19 +1229,36 @@ class WienerHopf:
 
     def set_fft_len(self, F):
         """Force the transform length of the correlation / FIR kernels (0 = planner)."""
+        self._corr_grid = 0
         check(self._L.blah2hip_clutter_set_option(self._h, _lib.CLUTTER_OPT_FFT_LEN, int(F)))
         self._refresh_dims()
 
     def set_fir_carry(self, on):
         """Blocks of F/2 samples with the window overlap carried in registers (filters with nBins - 1 just under F/2); re-plans."""
+        self._corr_grid = 0
         check(self._L.blah2hip_clutter_set_option(self._h, _lib.CLUTTER_OPT_FIR_CARRY, 1 if on else 0))
 
     def set_corr_form(self, which):
         """'auto' / 'half' / 'window' (``_lib.CLUTTER_CORR_*``)."""
         if isinstance(which, str):
             which = {"auto": _lib.CLUTTER_CORR_AUTO, "half": _lib.CLUTTER_CORR_HALF, "window": _lib.CLUTTER_CORR_WINDOW}[which]
+        self._corr_grid = 0
         check(self._L.blah2hip_clutter_set_option(self._h, _lib.CLUTTER_OPT_CORR, int(which)))
         self._refresh_dims()
+
+    def set_corr_grid(self, grid):
+        """Workgroups per CPI of the correlation kernels (tests): 0 = the planner's, else a multiple of 8 from 8 to the
+        plan's own count.  Fewer workgroups than segments make each walk several segments.  An option that re-plans
+        (``set_fft_len``, ``set_corr_form``, ``set_fir_carry``) returns the handle to 0."""
+        check(self._L.blah2hip_clutter_set_option(self._h, _lib.CLUTTER_OPT_CORR_GRID, int(grid)))
+        self._corr_grid = int(grid)
+
+    def last_corr_grid(self):
+        """Workgroups per CPI of the last FFT correlation launch (``_lib.CLUTTER_INFO_CORR_GRID``): the planner's at that
+        batch or the forced one; 0 before the first launch."""
+        v = C.c_int64(0)
+        check(self._L.blah2hip_clutter_get_info(self._h, _lib.CLUTTER_INFO_CORR_GRID, C.byref(v)))
+        return int(v.value)
 
     def set_solve_indices_per_thread(self, k):
         check(self._L.blah2hip_clutter_set_option(self._h, _lib.CLUTTER_OPT_SOLVE_K, int(k)))
@@ -1290,7 +1308,8 @@ class WienerHopf:
 
     def plan_info(self):
         """The plan the next call runs: {'corr' ('half' / 'window'; 'direct': blocks shorter than two filter lengths, fp64 lag sums), 'carry' (the FIR kernel carries the window overlap in
-        registers), 'chunks' (chunks of 2048 taps of a long filter, else 0)}."""
+        registers), 'chunks' (chunks of 2048 taps of a long filter, else 0), 'corr_grid' (the forced workgroups per CPI of the
+        correlation kernels, 0 = the planner's; ``last_corr_grid`` tells what a launch used)}."""
         out = {}
         for name, what in (("corr", _lib.CLUTTER_INFO_CORR_FORM), ("carry", _lib.CLUTTER_INFO_FIR_CARRY),
                            ("chunks", _lib.CLUTTER_INFO_CHUNKS)):
@@ -1299,6 +1318,7 @@ class WienerHopf:
             out[name] = int(v.value)
         out["corr"] = {_lib.CLUTTER_CORR_HALF: "half", _lib.CLUTTER_CORR_DIRECT: "direct"}.get(out["corr"], "window")
         out["carry"] = bool(out["carry"])
+        out["corr_grid"] = self._corr_grid
         return out
 
     def read_last(self, cpi=0):

@@ -758,6 +758,14 @@ int blah2hip_clutter_process_multi_dev_fmt(blah2hip_clutter_t h, int fmt, const 
  * A CPI whose solve gave up is solved again by the one-workgroup kernel enqueued behind it, so a low limit changes the
  * time, not the result. */
 #define BLAH2HIP_CLUTTER_OPT_SOLVE_SPIN_LIMIT 7
+/* CORR_GRID (tests): workgroups per CPI of the correlation kernels and partials per CPI of the reduction behind them.
+ * 0 (default) = the planner's: min(nJobs, two resident generations over the launch's CPIs), nJobs = min(segments, 2 CUs)
+ * rounded up to 8.  Any other value must be a multiple of 8 from 8 to that nJobs (the segment walk gives every XCD an
+ * eighth of the grid); it holds for every launch of the handle, at any batch, until it is set again or an option that
+ * re-plans (FFT_LEN, CORR, FIR_CARRY) returns the handle to 0.  Fewer workgroups than segments make each walk several
+ * segments; the sums are the same, their order in fp32 is not.  Not blocking; the next
+ * blah2hip_clutter_process_multi_dev_fmt builds its partials again (blocking) where the forced grid needs more of them. */
+#define BLAH2HIP_CLUTTER_OPT_CORR_GRID 8
 #define BLAH2HIP_CLUTTER_SOLVE_AUTO 0
 #define BLAH2HIP_CLUTTER_SOLVE_STEPWISE 1
 #define BLAH2HIP_CLUTTER_SOLVE_LOOKAHEAD 2
@@ -781,6 +789,9 @@ int blah2hip_clutter_set_option(blah2hip_clutter_t h, int option, int64_t value)
 #define BLAH2HIP_CLUTTER_INFO_CHUNKS 8
 /* blocks per CPI (blah2hip_clutter_create_ex), 1 for every other handle */
 #define BLAH2HIP_CLUTTER_INFO_BLOCKS 9
+/* workgroups per CPI of the handle's last FFT correlation launch (the planner's at that batch, or BLAH2HIP_CLUTTER_OPT_CORR_GRID);
+ * 0 before the first, and for the fp64 lag sums of short blocks (BLAH2HIP_CLUTTER_CORR_DIRECT) */
+#define BLAH2HIP_CLUTTER_INFO_CORR_GRID 10
 int blah2hip_clutter_get_info(blah2hip_clutter_t h, int what, int64_t *value);
 /* The filter's Toeplitz solve on its own: n_cpi systems toeplitz(r) w = b given as rb = [n_cpi][2][nBins] complex fp64 (r then b,
  * interleaved re, im; the layout blah2hip_clutter_read_last returns), taps to w ([n_cpi][nBins] complex fp32), ok[c] = 0

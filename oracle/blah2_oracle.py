@@ -395,15 +395,10 @@ def spectrum_process(x, n, bandwidth):
 
 
 # --------------------------------------------------------------------------
-def wiener_hopf(x, y, delay_min, delay_max, return_filter=False):
-    """``WienerHopf::process`` (src/process/clutter/WienerHopf.cpp:58-163).
-
-    Returns (ok, y_filtered).  x is not modified.  ``nBins = delayMax-delayMin``
-    (no +1, :12).  With ``return_filter`` also the taps w, the matrix's first
-    column r (A[i][j] = r[i-j]) and the right-hand side b of A w = b.
-    """
-    import scipy.linalg as sla
-
+def wiener_hopf_normal_equations(x, y, delay_min, delay_max):
+    """The first half of :func:`wiener_hopf` (WienerHopf.cpp:58-108): the shifted reference channel xs, the matrix's first
+    column r and the right-hand side b, without the factorisation (for tests of the correlations alone: the lines are the
+    ones ``wiener_hopf`` runs, so r and b are its bits)."""
     x = np.asarray(x, dtype=np.complex128)
     y = np.asarray(y, dtype=np.complex128)
     n = x.shape[0]
@@ -417,13 +412,29 @@ def wiener_hopf(x, y, delay_min, delay_max, return_filter=False):
     FY = _fft.fft(y)
     # :76-84  a[k] = conj(backward(|X|^2)[k]) / N ;  backward = N * ifft
     r = _fft.ifft(FX * np.conj(FX))[:n_bins]
+    # :100-108
+    b = _fft.ifft(FY * np.conj(FX))[:n_bins]
+    return xs, r, b
+
+
+def wiener_hopf(x, y, delay_min, delay_max, return_filter=False):
+    """``WienerHopf::process`` (src/process/clutter/WienerHopf.cpp:58-163).
+
+    Returns (ok, y_filtered).  x is not modified.  ``nBins = delayMax-delayMin``
+    (no +1, :12).  With ``return_filter`` also the taps w, the matrix's first
+    column r (A[i][j] = r[i-j]) and the right-hand side b of A w = b.
+    """
+    import scipy.linalg as sla
+
+    y = np.asarray(y, dtype=np.complex128)
+    n = y.shape[0]
+    n_bins = delay_max - delay_min
+    xs, r, b = wiener_hopf_normal_equations(x, y, delay_min, delay_max)
     a = np.conj(r)
     # :85-97  A = toeplitz(a) (symmetric), then conj of the strict lower triangle
     A = sla.toeplitz(a, a)
     low = np.tril_indices(n_bins, -1)
     A[low] = np.conj(A[low])
-    # :100-108
-    b = _fft.ifft(FY * np.conj(FX))[:n_bins]
     # :111-122  upper Cholesky, two triangular solves
     try:
         U = sla.cholesky(A, lower=False)

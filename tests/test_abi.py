@@ -66,5 +66,6 @@ def test_python_constants_mirror_the_header():
             checked += 1
     assert checked >= 30
     for must in ("RANGE_WAVE1K", "DOP_TILE16WG", "OPT_FFT_LEN", "FMT_I16X_C32Y", "CLUTTER_OPT_CORR",
-                 "OPT_CFAR2D_SEG_ROWS", "OPT_CFAR2D_GRID", "INFO_CFAR2D_SEG_ROWS", "INFO_CFAR2D_GRID"):
+                 "OPT_CFAR2D_SEG_ROWS", "OPT_CFAR2D_GRID", "INFO_CFAR2D_SEG_ROWS", "INFO_CFAR2D_GRID",
+                 "CLUTTER_OPT_CORR_GRID", "CLUTTER_INFO_CORR_GRID"):
         assert must in defs and getattr(_lib, must) == defs[must], must
