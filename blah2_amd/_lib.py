@@ -139,6 +139,14 @@ SYMBOLS = {
     "blah2hip_cfar2d_dev": (C.c_int, [_vp, _vp, _vp, _u32, _dbl, _i32, _i32, _i32, _i32, _i32, _dbl, _vp, _u32, _vp, _vp]),
     "blah2hip_cfar2d_process": (C.c_int, [_vp, _u32, _dbl, _i32, _i32, _i32, _i32, _i32, _dbl, _vp, _vp, _vp, _u32,
                                           C.POINTER(_u32)]),
+    "blah2hip_oscfar_alpha": (C.c_int, [_dbl, _u32, _u32, _u32, _vp, _vp]),
+    "blah2hip_oscfar1d_dev": (C.c_int, [_vp, _vp, _vp, _u32, _dbl, _u32, _i32, _i32, _i32, _dbl, _vp, _u32, _vp, _vp]),
+    "blah2hip_oscfar1d_prepare": (C.c_int, [_vp, _dbl, _u32, _i32]),
+    "blah2hip_oscfar1d_process": (C.c_int, [_vp, _u32, _dbl, _u32, _i32, _i32, _i32, _dbl, _vp, _vp, _vp, _u32, C.POINTER(_u32)]),
+    "blah2hip_oscfar2d_dev": (C.c_int, [_vp, _vp, _vp, _u32, _dbl, _u32, _i32, _i32, _i32, _i32, _i32, _dbl, _vp, _u32, _vp, _vp]),
+    "blah2hip_oscfar2d_prepare": (C.c_int, [_vp, _dbl, _u32, _i32, _i32, _i32, _i32]),
+    "blah2hip_oscfar2d_process": (C.c_int, [_vp, _u32, _dbl, _u32, _i32, _i32, _i32, _i32, _i32, _dbl, _vp, _vp, _vp, _u32,
+                                            C.POINTER(_u32)]),
     "blah2hip_centroid": (C.c_int, [_vp, _vp, _vp, _u32, C.c_uint16, C.c_uint16, _dbl, _vp, _vp, _vp, C.POINTER(_u32)]),
     "blah2hip_interpolate": (C.c_int, [_vp, _vp, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _dbl, C.c_int, C.c_int,
                                        _vp, _vp, _vp, C.POINTER(_u32)]),

@@ -106,6 +106,8 @@ struct blah2hip_amb_s {
   // ---- written by detect.hip; bearingGridLast by array.hip
   struct AlphaTable { double pfa; uint32_t looks; size_t n; double *d; bool pinned; }; // pinned: handed out by *_prepare, never evicted
   std::vector<AlphaTable> alphaTables; // CFAR threshold factors, one per (pfa, looks, size) seen
+  struct OsTable { double pfa; uint32_t looks, rank; size_t n; double *d; bool pinned; }; // d: alpha[n + 1], then rank[n + 1] words
+  std::vector<OsTable> osTables;    // ordered-statistic factors and ranks, one per (pfa, looks, rank_permille, size) seen
   double *d_sat = nullptr;          // 2-D CFAR summed-area table [max_batch][nD+1][nDelay+1], allocated at its first use
   blah2hip_hit_t *d_hits = nullptr; // the *_process calls' hit list, grown to the map's cell count
   uint32_t hitCap = 0;

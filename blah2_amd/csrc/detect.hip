@@ -1,8 +1,10 @@
-// Detection behind include/blah2hip.h: 1-D and 2-D CFAR with their threshold-table cache and summed-area table, Centroid
-// and Interpolate on the host and on the device.  Host code; the kernels are cfar_kernels.hpp's and detect_kernels.hpp's.
+// Detection behind include/blah2hip.h: 1-D and 2-D CFAR (cell-averaging and ordered-statistic) with their threshold-table
+// caches and summed-area table, Centroid and Interpolate on the host and on the device.  Host code; the kernels are
+// cfar_kernels.hpp's, oscfar_kernels.hpp's and detect_kernels.hpp's.
 #include "amb_handle.hpp"
 #include "cfar_kernels.hpp"
 #include "detect_kernels.hpp"
+#include "oscfar_kernels.hpp"
 
 #include <cmath>
 #include <thread>
@@ -90,6 +92,204 @@ int alpha_table(blah2hip_amb_s *h, double pfa, size_t maxN, const double **out, 
   if (e != hipSuccess) { (void)hipFree(t.d); return fail(BLAH2HIP_ERR_HIP, std::string("alpha table upload: ") + hipGetErrorString(e)); }
   T.push_back(t);
   *out = t.d;
+  return BLAH2HIP_OK;
+}
+
+// ---- ordered-statistic factors (blah2hip_oscfar_alpha; the formulas are in include/blah2hip.h) ----
+uint32_t os_rank(uint64_t n, uint32_t permille)
+{
+  return (uint32_t)std::max<uint64_t>(1, (n * permille + 999) / 1000);
+}
+
+// one look: log Pfa(alpha; n, k) = -sum_{i<k} log1p(alpha / (n - i))
+double os_logpfa1(double alpha, uint32_t n, uint32_t k)
+{
+  double s = 0.0;
+  for (uint32_t i = 0; i < k; i++) s -= std::log1p(alpha / (double)(n - i));
+  return s;
+}
+
+double os_alpha1(double pfa, uint32_t n, uint32_t k)
+{
+  const double lp = std::log(pfa);
+  double lo = 0.0, hi = 1.0;
+  while (os_logpfa1(hi, n, k) > lp) hi *= 2.0;
+  for (;;) {
+    const double mid = 0.5 * (lo + hi);
+    if (mid == lo || mid == hi) break;
+    if (os_logpfa1(mid, n, k) > lp) lo = mid;
+    else hi = mid;
+  }
+  return hi;
+}
+
+// Q_L(t) = e^-t sum_{j<L} t^j / j!, summed outwards from its largest term (no overflow for any t and L); lf[j] = log j!
+double os_q(double t, uint32_t L, const double *lf)
+{
+  if (!(t > 0.0)) return 1.0;
+  const uint32_t js = (uint32_t)std::min<double>((double)(L - 1), std::floor(t));
+  double s = 1.0, r = 1.0;
+  for (uint32_t j = js; j + 1 < L; j++) { r *= t / (double)(j + 1); s += r; }
+  r = 1.0;
+  for (uint32_t j = js; j > 0; j--) { r *= (double)j / t; s += r; }
+  return std::exp(-t + (double)js * std::log(t) - lf[js]) * s;
+}
+
+// P_L(x) = 1 - Q_L(x) from its own series e^-x x^L / L! (1 + x/(L+1) + x^2/((L+1)(L+2)) + ...), for x < L (no cancellation)
+double os_p_series(double x, uint32_t L, const double *lf)
+{
+  if (!(x > 0.0)) return 0.0;
+  double s = 1.0, r = 1.0;
+  for (uint32_t m = 1; m < 100000; m++) {
+    r *= x / (double)(L + m);
+    s += r;
+    if (r < 1e-17 * s) break;
+  }
+  return std::exp(-x + (double)L * std::log(x) - lf[L]) * s;
+}
+
+// log of the density of the k-th smallest of n Gamma(L) variables at x, without its constant n! / ((k-1)! (n-k)!)
+double os_logdens(double x, uint32_t n, uint32_t k, uint32_t L, const double *lf)
+{
+  double P, Q;
+  if (x < (double)L) { P = os_p_series(x, L, lf); Q = 1.0 - P; }
+  else { Q = os_q(x, L, lf); P = 1.0 - Q; }
+  double g = -x - lf[L - 1];
+  if (L > 1) g += (double)(L - 1) * std::log(x);
+  if (k > 1) g += (double)(k - 1) * std::log(P);
+  if (n > k) g += (double)(n - k) * std::log(Q);
+  return g;
+}
+
+constexpr int OS_COARSE = 4096, OS_FINE = 16384; // grid points of a scan for the integrand's support; Simpson intervals over it
+constexpr double OS_CUT = 60.0;                  // the support: within e^-60 of the largest value
+
+// Simpson nodes x and weights times density w for int f_(k)(x) Q_L(alpha x) dx at alpha >= alpha0: the interval on which
+// f_(k)(x) Q_L(alpha0 x) is within e^-60 of its largest value (Q_L(alpha x) falls as alpha rises, so the interval holds
+// the integrand of every larger alpha), found by two scans of OS_COARSE points, the second inside the first one's result
+struct OsNodes { std::vector<double> x, w; };
+
+void os_nodes(OsNodes &N, double alpha0, double logc, uint32_t n, uint32_t k, uint32_t L, const double *lf)
+{
+  auto G = [&](double x) {
+    double g = os_logdens(x, n, k, L, lf);
+    if (alpha0 > 0.0) g += std::log(os_q(alpha0 * x, L, lf));
+    return g;
+  };
+  double a = 0.0, b = (double)L + 40.0 * std::sqrt((double)L) + 100.0;
+  std::vector<double> g(OS_COARSE + 1);
+  for (int pass = 0; pass < 2; pass++) {
+    const double hc = (b - a) / OS_COARSE;
+    int imax = 0;
+    for (int i = 0; i <= OS_COARSE; i++) {
+      g[i] = G(a + hc * i);
+      if (g[i] > g[imax]) imax = i;
+    }
+    int ilo = imax, ihi = imax;
+    while (ilo > 0 && !(g[ilo] < g[imax] - OS_CUT)) ilo--;
+    while (ihi < OS_COARSE && !(g[ihi] < g[imax] - OS_CUT)) ihi++;
+    b = a + hc * ihi;
+    a = a + hc * ilo;
+  }
+  const double h = (b - a) / OS_FINE;
+  N.x.resize(OS_FINE + 1);
+  N.w.resize(OS_FINE + 1);
+  for (int i = 0; i <= OS_FINE; i++) {
+    N.x[i] = a + h * i;
+    const double simpson = (i == 0 || i == OS_FINE) ? 1.0 : ((i & 1) ? 4.0 : 2.0);
+    N.w[i] = simpson * (h / 3.0) * std::exp(logc + os_logdens(N.x[i], n, k, L, lf));
+  }
+}
+
+double os_pfa_nodes(const OsNodes &N, double alpha, uint32_t L, const double *lf)
+{
+  double s = 0.0;
+  for (int i = 0; i <= OS_FINE; i++) s += N.w[i] * os_q(alpha * N.x[i], L, lf);
+  return s;
+}
+
+// alpha[n] for L > 1 looks: Pfa(alpha) = int f_(k)(x) Q_L(alpha x) dx = pfa.  The bracket [hi / 2, hi] by doubling, each
+// trial on nodes of its own; then a bisection on the nodes of the bracket's lower end until the interval no longer
+// splits.  The upper end is returned.
+double os_alpha_looks(double pfa, uint32_t n, uint32_t k, uint32_t L, const double *lf)
+{
+  double logc = 0.0; // log( n! / ((k-1)! (n-k)!) ) = sum_{i<k} log(n - i) - log (k-1)!
+  for (uint32_t i = 0; i < k; i++) logc += std::log((double)(n - i));
+  for (uint32_t i = 2; i < k; i++) logc -= std::log((double)i);
+  OsNodes N;
+  double lo = 0.0, hi = 1.0;
+  for (;;) {
+    os_nodes(N, hi, logc, n, k, L, lf);
+    if (!(os_pfa_nodes(N, hi, L, lf) > pfa) || hi > 1e300) break;
+    lo = hi;
+    hi *= 2.0;
+  }
+  os_nodes(N, lo, logc, n, k, L, lf);
+  for (;;) {
+    const double mid = 0.5 * (lo + hi);
+    if (mid == lo || mid == hi) break;
+    if (os_pfa_nodes(N, mid, L, lf) > pfa) lo = mid;
+    else hi = mid;
+  }
+  return hi;
+}
+
+// The ordered-statistic detectors' tables: alpha[maxN + 1] doubles, then rank[maxN + 1] words, in one device allocation; a
+// cache of their own keyed by (pfa, looks, rank, size) with the rules of alpha_table above (eight unpinned entries, least
+// recently used first out, *_prepare pins), which it never touches.
+constexpr size_t OS_TABLES_MAX = 8;
+
+int os_table(blah2hip_amb_s *h, double pfa, uint32_t permille, size_t maxN, const double **alpha, const uint32_t **rank,
+             hipStream_t st = nullptr, bool pin = false)
+{
+  auto &T = h->osTables;
+  const uint32_t looks = h->cfarLooks;
+  for (size_t i = 0; i < T.size(); i++)
+    if (T[i].pfa == pfa && T[i].looks == looks && T[i].rank == permille && T[i].n == maxN) {
+      blah2hip_amb_s::OsTable t = T[i];
+      t.pinned = t.pinned || pin;
+      T.erase(T.begin() + (long)i);
+      T.push_back(t); // most recently used last
+      *alpha = t.d;
+      *rank = reinterpret_cast<const uint32_t *>(t.d + (maxN + 1));
+      return BLAH2HIP_OK;
+    }
+  if (st) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+      return fail(BLAH2HIP_ERR_INVALID, "ordered-statistic table of this (pfa, rank, window) is not resident: call "
+                                        "blah2hip_oscfar1d_prepare / blah2hip_oscfar2d_prepare before capturing the stream");
+  }
+  const size_t bytes = (maxN + 1) * (sizeof(double) + sizeof(uint32_t));
+  std::vector<double> host((bytes + sizeof(double) - 1) / sizeof(double));
+  int rc;
+  if ((rc = blah2hip_oscfar_alpha(pfa, looks, permille, (uint32_t)maxN, host.data(),
+                                  reinterpret_cast<uint32_t *>(host.data() + (maxN + 1)))))
+    return rc;
+  size_t unpinned = 0;
+  for (const auto &e : T) unpinned += e.pinned ? 0 : 1;
+  if (unpinned >= OS_TABLES_MAX) {
+    HIPCHK(hipDeviceSynchronize()); // the oldest unpinned table may still be read by enqueued work
+    for (size_t i = 0; i < T.size(); i++)
+      if (!T[i].pinned) {
+        (void)hipFree(T[i].d);
+        T.erase(T.begin() + (long)i);
+        break;
+      }
+  }
+  blah2hip_amb_s::OsTable t{pfa, looks, permille, maxN, nullptr, pin};
+  HIPCHK(hipMalloc(&t.d, host.size() * sizeof(double)));
+  hipError_t e = hipMemcpy(t.d, host.data(), bytes, hipMemcpyHostToDevice);
+  if (e != hipSuccess) { (void)hipFree(t.d); return fail(BLAH2HIP_ERR_HIP, std::string("ordered-statistic table upload: ") + hipGetErrorString(e)); }
+  T.push_back(t);
+  *alpha = t.d;
+  *rank = reinterpret_cast<const uint32_t *>(t.d + (maxN + 1));
+  return BLAH2HIP_OK;
+}
+
+int os_check_rank(uint32_t permille)
+{
+  if (permille < 1 || permille > 1000) return fail(BLAH2HIP_ERR_INVALID, "rank_permille outside [1, 1000]");
   return BLAH2HIP_OK;
 }
 
@@ -506,6 +706,190 @@ int blah2hip_cfar2d_process(blah2hip_amb_t h, uint32_t cpi, double pfa, int32_t 
   if ((rc = ensure_hits(h, cells))) return rc;
   rc = blah2hip_cfar2d_dev(h, h->d_map + cells * cpi, h->d_metrics + 2 * cpi, 1, pfa, ngd, ntd, ngf, ntf,
                            min_delay, min_doppler, h->d_hits, h->hitCap, h->d_count, h->stream);
+  if (rc) return rc;
+  return hits_to_host(h, delay, doppler, snr, cap, count);
+}
+
+// ------------------------------------------------------ ordered statistic --
+// Host arithmetic only.  One look: a bisection per n on the logarithm of the product formula.  More looks: per n the nodes
+// and weights of the quadrature once, then a bisection of about 60 sums over them; the entries are computed on their own,
+// in interleaved slices for up to eight threads when the table is long.
+int blah2hip_oscfar_alpha(double pfa, uint32_t looks, uint32_t rank_permille, uint32_t max_n, double *alpha, uint32_t *rank)
+{
+  if (!alpha) return fail(BLAH2HIP_ERR_INVALID, "NULL table");
+  if (looks == 0 || looks > BLAH2HIP_MAX_CFAR_LOOKS) return fail(BLAH2HIP_ERR_INVALID, "looks outside [1, BLAH2HIP_MAX_CFAR_LOOKS]");
+  if (rank_permille < 1 || rank_permille > 1000) return fail(BLAH2HIP_ERR_INVALID, "rank_permille outside [1, 1000]");
+  if (!(pfa > 0.0 && pfa < 1.0)) return fail(BLAH2HIP_ERR_INVALID, "pfa outside (0, 1)");
+  alpha[0] = std::nan("");
+  if (rank) rank[0] = 0;
+  for (uint64_t n = 1; n <= max_n; n++)
+    if (rank) rank[n] = os_rank(n, rank_permille);
+  std::vector<double> lf(looks + 1, 0.0); // log j!
+  for (uint32_t j = 2; j <= looks; j++) lf[j] = lf[j - 1] + std::log((double)j);
+  // (one look costs about 60 k log1p per entry: only a long 2-D table is worth the threads)
+  const bool threads = looks == 1 ? max_n >= 512 : max_n >= 16;
+  const uint32_t nThreads = !threads ? 1u : std::min(8u, std::max(1u, std::thread::hardware_concurrency()));
+  auto slice = [=, &lf](uint32_t first) {
+    for (uint64_t n = 1 + first; n <= max_n; n += nThreads) {
+      const uint32_t k = os_rank(n, rank_permille);
+      alpha[n] = looks == 1 ? os_alpha1(pfa, (uint32_t)n, k) : os_alpha_looks(pfa, (uint32_t)n, k, looks, lf.data());
+    }
+  };
+  std::vector<std::thread> pool;
+  uint32_t started = 1;
+  try {
+    for (; started < nThreads; started++) pool.emplace_back(slice, started);
+  } catch (const std::exception &) { // no thread to be had: the slices that are left run here
+  }
+  slice(0);
+  for (uint32_t t = started; t < nThreads; t++) slice(t);
+  for (auto &t : pool) t.join();
+  return BLAH2HIP_OK;
+}
+
+int blah2hip_oscfar1d_dev(blah2hip_amb_t h, const void *d_map, const double *d_metrics, uint32_t n_cpi, double pfa,
+                          uint32_t rank_permille, int32_t n_guard, int32_t n_train, int32_t min_delay, double min_doppler,
+                          blah2hip_hit_t *d_hits, uint32_t cap, uint32_t *d_count, void *stream)
+{
+  if (!h || !d_hits || !d_count) return fail(BLAH2HIP_ERR_INVALID, "NULL argument");
+  if (n_cpi == 0 || n_cpi > h->dims.max_batch) return fail(BLAH2HIP_ERR_INVALID, "n_cpi outside [1, max_batch]");
+  if (n_guard < 0 || n_guard > 127 || n_train < 0 || n_train > 127 || min_delay < -128 || min_delay > 127)
+    return fail(BLAH2HIP_ERR_INVALID, "nGuard/nTrain/minDelay outside int8 range");
+  int rc;
+  if ((rc = os_check_rank(rank_permille))) return rc;
+  HIPCHK(hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  OsCfarArgs oa;
+  CfarArgs &a = oa.c;
+  if ((rc = os_table(h, pfa, rank_permille, (size_t)(2 * n_train), &a.alpha, &oa.rank, st))) return rc;
+  HIPCHK(hipMemsetAsync(d_count, 0, n_cpi * sizeof(uint32_t), st));
+  a.map = d_map ? (const cf *)d_map : h->d_map;
+  a.metrics = d_metrics ? d_metrics : h->d_metrics;
+  a.doppler = h->d_doppler;
+  a.hits = d_hits;
+  a.count = d_count;
+  a.nD = (int32_t)h->dims.n_doppler_bins;
+  a.nDelay = (int32_t)h->dims.n_delay_bins;
+  a.delayMin = h->delayMin;
+  a.delayAxis = nullptr; // the engine's own axis: delayMin + j
+  a.nGuard = n_guard; a.nTrain = n_train; a.minDelay = min_delay;
+  a.minDoppler = min_doppler;
+  a.cap = cap;
+  if ((rc = tic(h, BLAH2HIP_K_CFAR, st))) return rc;
+  {
+    // the row as fp64 |z|^2 in LDS while it fits (150 KB: 19 200 delay bins), straight from L2 beyond: cfar1d_kernel's limit
+    const size_t rowBytes = (size_t)a.nDelay * sizeof(double);
+    if (rowBytes <= 150 * 1024) {
+      if (rowBytes > 48 * 1024) LDSCFG(oscfar1d_kernel<true>, 150 * 1024);
+      hipLaunchKernelGGL(oscfar1d_kernel<true>, dim3(a.nD, n_cpi), dim3(256), rowBytes, st, oa);
+    } else {
+      hipLaunchKernelGGL(oscfar1d_kernel<false>, dim3(a.nD, n_cpi), dim3(256), 0, st, oa);
+    }
+  }
+  HIPCHK(hipGetLastError());
+  if ((rc = toc(h, BLAH2HIP_K_CFAR, st))) return rc;
+  return BLAH2HIP_OK;
+}
+
+int blah2hip_oscfar1d_prepare(blah2hip_amb_t h, double pfa, uint32_t rank_permille, int32_t n_train)
+{
+  if (!h) return fail(BLAH2HIP_ERR_INVALID, "NULL handle");
+  if (n_train < 0 || n_train > 127) return fail(BLAH2HIP_ERR_INVALID, "nTrain outside int8 range");
+  int rc;
+  if ((rc = os_check_rank(rank_permille))) return rc;
+  HIPCHK(hipSetDevice(h->device));
+  const double *d = nullptr;
+  const uint32_t *r = nullptr;
+  return os_table(h, pfa, rank_permille, (size_t)(2 * n_train), &d, &r, nullptr, true);
+}
+
+int blah2hip_oscfar1d_process(blah2hip_amb_t h, uint32_t cpi, double pfa, uint32_t rank_permille, int32_t n_guard,
+                              int32_t n_train, int32_t min_delay, double min_doppler, double *delay, double *doppler,
+                              double *snr, uint32_t cap, uint32_t *count)
+{
+  if (!h || !count) return fail(BLAH2HIP_ERR_INVALID, "NULL argument");
+  if (cpi >= h->dims.max_batch) return fail(BLAH2HIP_ERR_INVALID, "cpi index out of range");
+  HIPCHK(hipSetDevice(h->device));
+  const size_t cells = (size_t)h->dims.n_doppler_bins * h->dims.n_delay_bins;
+  int rc;
+  if ((rc = ensure_hits(h, cells))) return rc;
+  rc = blah2hip_oscfar1d_dev(h, h->d_map + cells * cpi, h->d_metrics + 2 * cpi, 1, pfa, rank_permille, n_guard, n_train,
+                             min_delay, min_doppler, h->d_hits, h->hitCap, h->d_count, h->stream);
+  if (rc) return rc;
+  return hits_to_host(h, delay, doppler, snr, cap, count);
+}
+
+static int os2d_check(blah2hip_amb_t h, uint32_t rank_permille, int32_t ngd, int32_t ntd, int32_t ngf, int32_t ntf)
+{
+  if (!h) return fail(BLAH2HIP_ERR_INVALID, "NULL handle");
+  for (int32_t v : {ngd, ntd, ngf, ntf})
+    if (v < 0 || v > 127) return fail(BLAH2HIP_ERR_INVALID, "guard/train sizes outside [0, 127]");
+  int rc;
+  if ((rc = os_check_rank(rank_permille))) return rc;
+  if (ngf + ntf > C2T_MAX_HR || ngd + ntd > C2T_MAX_HC)
+    return fail(BLAH2HIP_ERR_UNSUPPORTED, "ordered-statistic 2-D window beyond the tile's halo (nGf + nTf <= 24, nGd + nTd <= 40): "
+                                          "a rank has no summed-area form");
+  return BLAH2HIP_OK;
+}
+
+int blah2hip_oscfar2d_dev(blah2hip_amb_t h, const void *d_map, const double *d_metrics, uint32_t n_cpi, double pfa,
+                          uint32_t rank_permille, int32_t ngd, int32_t ntd, int32_t ngf, int32_t ntf, int32_t min_delay,
+                          double min_doppler, blah2hip_hit_t *d_hits, uint32_t cap, uint32_t *d_count, void *stream)
+{
+  if (!h || !d_hits || !d_count) return fail(BLAH2HIP_ERR_INVALID, "NULL argument");
+  if (n_cpi == 0 || n_cpi > h->dims.max_batch) return fail(BLAH2HIP_ERR_INVALID, "n_cpi outside [1, max_batch]");
+  if (min_delay < -128 || min_delay > 127) return fail(BLAH2HIP_ERR_INVALID, "minDelay outside int8 range");
+  int rc;
+  if ((rc = os2d_check(h, rank_permille, ngd, ntd, ngf, ntf))) return rc;
+  HIPCHK(hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  OsCfar2dArgs oa;
+  Cfar2dArgs &a = oa.d;
+  if ((rc = os_table(h, pfa, rank_permille, (size_t)(2 * (ngd + ntd) + 1) * (2 * (ngf + ntf) + 1), &a.alpha, &oa.rank, st))) return rc;
+  HIPCHK(hipMemsetAsync(d_count, 0, n_cpi * sizeof(uint32_t), st));
+  a.map = d_map ? (const cf *)d_map : h->d_map;
+  a.metrics = d_metrics ? d_metrics : h->d_metrics;
+  a.doppler = h->d_doppler;
+  a.sat = nullptr;
+  a.hits = d_hits;
+  a.count = d_count;
+  a.nD = (int32_t)h->dims.n_doppler_bins; a.nDelay = (int32_t)h->dims.n_delay_bins; a.delayMin = h->delayMin;
+  a.ngD = ngd; a.ntD = ntd; a.ngF = ngf; a.ntF = ntf; a.minDelay = min_delay;
+  a.minDoppler = min_doppler;
+  a.cap = cap;
+  const size_t lds = o2_lds_bytes(ngd + ntd, ngf + ntf);
+  if (lds > 48 * 1024) LDSCFG(oscfar2d_kernel, o2_lds_bytes(C2T_MAX_HC, C2T_MAX_HR)); // once per (device, kernel): its largest use
+  if ((rc = tic(h, BLAH2HIP_K_CFAR, st))) return rc;
+  hipLaunchKernelGGL(oscfar2d_kernel, dim3((a.nDelay + O2_COLS - 1) / O2_COLS, (a.nD + O2_ROWS - 1) / O2_ROWS, n_cpi), dim3(256),
+                     lds, st, oa);
+  HIPCHK(hipGetLastError());
+  if ((rc = toc(h, BLAH2HIP_K_CFAR, st))) return rc;
+  return BLAH2HIP_OK;
+}
+
+int blah2hip_oscfar2d_prepare(blah2hip_amb_t h, double pfa, uint32_t rank_permille, int32_t ngd, int32_t ntd, int32_t ngf,
+                              int32_t ntf)
+{
+  int rc;
+  if ((rc = os2d_check(h, rank_permille, ngd, ntd, ngf, ntf))) return rc;
+  HIPCHK(hipSetDevice(h->device));
+  const double *d = nullptr;
+  const uint32_t *r = nullptr;
+  return os_table(h, pfa, rank_permille, (size_t)(2 * (ngd + ntd) + 1) * (2 * (ngf + ntf) + 1), &d, &r, nullptr, true);
+}
+
+int blah2hip_oscfar2d_process(blah2hip_amb_t h, uint32_t cpi, double pfa, uint32_t rank_permille, int32_t ngd, int32_t ntd,
+                              int32_t ngf, int32_t ntf, int32_t min_delay, double min_doppler, double *delay,
+                              double *doppler, double *snr, uint32_t cap, uint32_t *count)
+{
+  if (!h || !count) return fail(BLAH2HIP_ERR_INVALID, "NULL argument");
+  if (cpi >= h->dims.max_batch) return fail(BLAH2HIP_ERR_INVALID, "cpi index out of range");
+  HIPCHK(hipSetDevice(h->device));
+  const size_t cells = (size_t)h->dims.n_doppler_bins * h->dims.n_delay_bins;
+  int rc;
+  if ((rc = ensure_hits(h, cells))) return rc;
+  rc = blah2hip_oscfar2d_dev(h, h->d_map + cells * cpi, h->d_metrics + 2 * cpi, 1, pfa, rank_permille, ngd, ntd, ngf, ntf,
+                             min_delay, min_doppler, h->d_hits, h->hitCap, h->d_count, h->stream);
   if (rc) return rc;
   return hits_to_host(h, delay, doppler, snr, cap, count);
 }

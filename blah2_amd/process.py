@@ -283,6 +283,224 @@ def cfar_alpha_table(pfa, looks, max_n):
     return out
 
 
+def oscfar_rank(n, rank_permille=750):
+    """``k(n) = max(1, ceil(n * rank_permille / 1000))`` in integer arithmetic: which of ``n`` training cells, counted from
+    the smallest, the ordered-statistic detectors take."""
+    if not 1 <= int(rank_permille) <= 1000:
+        raise ValueError("rank_permille outside [1, 1000]")
+    return max(1, (int(n) * int(rank_permille) + 999) // 1000)
+
+
+_OS_COARSE, _OS_FINE, _OS_CUT = 4096, 16384, 60.0
+
+
+def _os_logfact(L):
+    lf = np.zeros(L + 1)
+    for j in range(2, L + 1):
+        lf[j] = lf[j - 1] + np.log(float(j))
+    return lf
+
+
+def _os_q(t, L, lf):
+    """``Q_L(t) = e^-t sum_{j<L} t^j / j!`` for an array ``t >= 0``, term by term in the log domain."""
+    t = np.asarray(t, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        lt = np.log(t)
+        s = np.exp(-t)
+        for j in range(1, L):
+            s = s + np.exp(-t + j * lt - lf[j])
+    return s
+
+
+def _os_logdens(x, n, k, L, lf):
+    """log of the density of the k-th smallest of n Gamma(L) variables, without its constant."""
+    x = np.asarray(x, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        lx = np.log(x)
+        small = x < L
+        r = np.ones_like(x)
+        s = np.ones_like(x)
+        for m in range(1, 100000):  # P_L(x) from its own series where x < L: no cancellation
+            r = np.where(small, r * x / (L + m), 0.0)
+            s = s + r
+            if not (r >= 1e-17 * s).any():
+                break
+        Ps = np.where(x > 0, np.exp(-x + L * lx - lf[L]) * s, 0.0)
+        Qq = _os_q(x, L, lf)
+        P = np.where(small, Ps, 1.0 - Qq)
+        Q = np.where(small, 1.0 - Ps, Qq)
+        g = -x - lf[L - 1]
+        if L > 1:
+            g = g + (L - 1) * lx
+        if k > 1:
+            g = g + (k - 1) * np.log(P)
+        if n > k:
+            g = g + (n - k) * np.log(Q)
+    return g
+
+
+def _os_nodes(n, k, L, lf, alpha0=0.0):
+    """Simpson nodes ``x`` and weights times density ``w`` of blah2hip_oscfar_alpha's quadrature for (n, k, L) at factors
+    ``>= alpha0`` (os_nodes in csrc/detect.hip)."""
+    logc = 0.0
+    for i in range(k):
+        logc += np.log(float(n - i))
+    for i in range(2, k):
+        logc -= np.log(float(i))
+
+    def G(x):
+        g = _os_logdens(x, n, k, L, lf)
+        if alpha0 > 0.0:
+            with np.errstate(all="ignore"):
+                g = g + np.log(_os_q(alpha0 * x, L, lf))
+        return g
+    a, b = 0.0, L + 40.0 * np.sqrt(float(L)) + 100.0
+    for _ in range(2):
+        hc = (b - a) / _OS_COARSE
+        g = G(a + hc * np.arange(_OS_COARSE + 1))
+        imax = int(np.nanargmax(g))
+        ilo = ihi = imax
+        while ilo > 0 and not g[ilo] < g[imax] - _OS_CUT:
+            ilo -= 1
+        while ihi < _OS_COARSE and not g[ihi] < g[imax] - _OS_CUT:
+            ihi += 1
+        a, b = a + hc * ilo, a + hc * ihi
+    h = (b - a) / _OS_FINE
+    i = np.arange(_OS_FINE + 1)
+    x = a + h * i
+    simpson = np.where(i % 2 == 1, 4.0, 2.0)
+    simpson[0] = simpson[-1] = 1.0
+    with np.errstate(all="ignore"):
+        w = simpson * (h / 3.0) * np.exp(logc + _os_logdens(x, n, k, L, lf))
+    return x, w
+
+
+def oscfar_pfa(alpha, n, k, looks=1, quadrature=False):
+    """The false-alarm probability of the ordered-statistic threshold ``alpha * x_(k)``, the k-th smallest of ``n`` training
+    cells, when every cell is the sum of ``looks`` looks of noise.  One look: ``prod_{i<k} (n - i) / (n - i + alpha)``,
+    evaluated as blah2hip_oscfar_alpha does, through ``-sum log1p(alpha / (n - i))``.  More looks (or ``quadrature=True``):
+    ``int f_(k)(x) Q_L(alpha x) dx`` by the library's composite Simpson rule (include/blah2hip.h).  NumPy on the host."""
+    import math
+    n, k, L = int(n), int(k), int(looks)
+    if not 1 <= k <= n:
+        raise ValueError("k outside [1, n]")
+    if L == 1 and not quadrature:
+        s = 0.0
+        for i in range(k):
+            s -= math.log1p(float(alpha) / (n - i))
+        return math.exp(s)
+    lf = _os_logfact(L)
+    x, w = _os_nodes(n, k, L, lf, float(alpha))
+    return float(np.sum(w * _os_q(float(alpha) * x, L, lf)))
+
+
+def oscfar_alpha(pfa, looks=1, rank_permille=750, max_n=1, quadrature=False):
+    """blah2hip_oscfar_alpha restated with NumPy on the host: ``(alpha float64 [max_n + 1], rank uint32 [max_n + 1])`` with
+    ``alpha[0]`` NaN, ``rank[n] = oscfar_rank(n, rank_permille)`` and ``oscfar_pfa(alpha[n], n, rank[n], looks) = pfa`` by
+    bisection until the interval no longer splits (its upper end).  ``quadrature=True`` takes one look through the
+    quadrature of the other looks as well."""
+    import math
+    pfa, L = float(pfa), int(looks)
+    if not 1 <= L <= _lib.MAX_CFAR_LOOKS:
+        raise ValueError("looks outside [1, MAX_CFAR_LOOKS]")
+    if not 0.0 < pfa < 1.0:
+        raise ValueError("pfa outside (0, 1)")
+    alpha = np.full(int(max_n) + 1, np.nan)
+    rank = np.zeros(int(max_n) + 1, dtype=np.uint32)
+    lf = _os_logfact(L)
+    lp = math.log(pfa)
+    for n in range(1, int(max_n) + 1):
+        k = rank[n] = oscfar_rank(n, rank_permille)
+        k = int(k)
+        if L == 1 and not quadrature:
+            def above(a):
+                s = 0.0
+                for i in range(k):
+                    s -= math.log1p(a / (n - i))
+                return s > lp
+            lo, hi = 0.0, 1.0
+            while above(hi):
+                hi *= 2.0
+        else:
+            def above_at(a, nodes):
+                return float(np.sum(nodes[1] * _os_q(a * nodes[0], L, lf))) > pfa
+            lo, hi = 0.0, 1.0
+            while above_at(hi, _os_nodes(n, k, L, lf, hi)) and hi <= 1e300:  # each trial on nodes of its own
+                lo = hi
+                hi *= 2.0
+            nodes = _os_nodes(n, k, L, lf, lo)
+
+            def above(a):
+                return above_at(a, nodes)
+        while True:
+            mid = 0.5 * (lo + hi)
+            if mid == lo or mid == hi:
+                break
+            if above(mid):
+                lo = mid
+            else:
+                hi = mid
+        alpha[n] = hi
+    return alpha, rank
+
+
+def oscfar_alpha_table(pfa, looks, rank_permille, max_n):
+    """blah2hip_oscfar_alpha itself (host arithmetic of the library, no GPU touched): ``(alpha float64 [max_n + 1], rank
+    uint32 [max_n + 1])``."""
+    alpha = np.empty(int(max_n) + 1, dtype=np.float64)
+    rank = np.empty(int(max_n) + 1, dtype=np.uint32)
+    check(_lib.load().blah2hip_oscfar_alpha(float(pfa), int(looks), int(rank_permille), int(max_n), _ptr(alpha), _ptr(rank)))
+    return alpha, rank
+
+
+def oscfar_window(window):
+    """``(nGd, nTd, nGf, nTf)`` of a 1-D ``(nGuard, nTrain)`` or a 2-D window."""
+    w = tuple(int(v) for v in window)
+    if len(w) == 2:
+        w = (w[0], w[1], 0, 0)
+    if len(w) != 4 or min(w) < 0:
+        raise ValueError("window: (nGuard, nTrain) or (nGuardDelay, nTrainDelay, nGuardDoppler, nTrainDoppler)")
+    return w
+
+
+def oscfar_hits(map, delay, doppler, noise_power, alpha, rank, window, min_delay=-128, min_doppler=0.0):
+    """The ordered-statistic detectors' rule restated in fp64 NumPy for one map ``[nD, nC]`` with its axes, taking the
+    tables ``alpha`` and ``rank`` as arguments (``oscfar_alpha_table`` or ``oscfar_alpha`` for the window's cell count):
+    with ``p = re^2 + im^2`` and the in-bounds training cells of a cell (the window's rectangle minus its guard box, never
+    delay column 0), ``hit <=> n >= 1 and #{alpha[n] * p_i < p_c} >= rank[n]``, on the cells with ``delay >= min_delay`` in
+    the rows that do not have ``|doppler| < min_doppler``.  ``window``: ``(nGuard, nTrain)`` or the 2-D
+    ``(nGd, nTd, nGf, nTf)``.  Returns ``(row, col, snr)`` in row-major order, ``snr = 5 log10(p) - noise_power``."""
+    gd, td, gf, tf = oscfar_window(window)
+    hC, hR = gd + td, gf + tf
+    m = np.asarray(map)
+    re, im = m.real.astype(np.float64), m.imag.astype(np.float64)
+    p = re * re + im * im
+    nD, nC = p.shape
+    alpha = np.asarray(alpha, dtype=np.float64)
+    rank = np.asarray(rank).astype(np.int64)
+    T = np.full((nD + 2 * hR, nC + 2 * hC), np.inf)  # a cell that does not train is never below
+    T[hR:hR + nD, hC + 1:hC + nC] = p[:, 1:]
+    V = np.zeros(T.shape, dtype=bool)
+    V[hR:hR + nD, hC + 1:hC + nC] = True
+    offsets = [(dr, dc) for dr in range(-hR, hR + 1) for dc in range(-hC, hC + 1) if not (abs(dr) <= gf and abs(dc) <= gd)]
+    n = np.zeros((nD, nC), dtype=np.int64)
+    for dr, dc in offsets:
+        n += V[hR + dr:hR + dr + nD, hC + dc:hC + dc + nC]
+    if n.max(initial=0) >= alpha.size or n.max(initial=0) >= rank.size:
+        raise ValueError("the tables are shorter than the window's cell count")
+    an = alpha[n]
+    below = np.zeros((nD, nC), dtype=np.int64)
+    with np.errstate(all="ignore"):
+        for dr, dc in offsets:
+            below += an * T[hR + dr:hR + dr + nD, hC + dc:hC + dc + nC] < p
+        tested = ~(np.abs(np.asarray(doppler, dtype=np.float64)) < float(min_doppler))[:, None] \
+            & (np.asarray(delay) >= int(min_delay))[None, :]
+        hit = tested & (n >= 1) & (below >= rank[n])
+        row, col = np.nonzero(hit)
+        snr = 5.0 * np.log10(p[row, col]) - float(noise_power)
+    return row.astype(np.int32), col.astype(np.int32), snr
+
+
 def integrate_ends(n_cpi, window, hop=None, start=0):
     """The CPI counts ``g`` at which a window of ``window`` CPIs ends among the CPIs ``start .. start + n_cpi - 1`` of an
     integrator with hop ``hop`` (None: 1): every ``g >= window - 1`` with ``(g - (window - 1)) % hop == 0``."""
@@ -942,6 +1160,120 @@ class CfarDetector2D:
         amb.set_cfar_looks(self.looks)
         check(amb._L.blah2hip_cfar2d_dev(amb._h, d_map, d_metrics, n_cpi, self.pfa, *self.p, self.minDelay,
                                          self.minDoppler, d_hits, cap, d_count, stream))
+
+
+def _rank_permille(rank):
+    """A rank given as a fraction of the training cells (0.75) in the library's unit, 1 .. 1000."""
+    pm = int(round(float(rank) * 1000.0))
+    if not 1 <= pm <= 1000:
+        raise ValueError("rank outside [0.001, 1]")
+    return pm
+
+
+def _detect_host_map(amb, x, enqueue):
+    """A detector's ``*_dev`` entry point on a map held by the host: uploads ``x.data`` and ``x.noisePower`` beside a hit
+    list of the map's size, runs ``enqueue(d_map, d_metrics, d_hits, cap, d_count, stream)`` and returns the hits in the
+    reference's emission order.  ``amb`` gives the geometry and the axes; the map must have its shape."""
+    data = np.ascontiguousarray(x.data, dtype=np.complex64)
+    if data.shape != (amb.dims.n_doppler_bins, amb.dims.n_delay_bins):
+        raise ValueError(f"the map must be [{amb.dims.n_doppler_bins}, {amb.dims.n_delay_bins}]")
+    met = np.array([float(x.noisePower), float(x.maxPower)], dtype=np.float64)
+    cap = data.size
+    hits = np.zeros(cap, dtype=HIT_DTYPE)
+    cnt = np.zeros(1, dtype=np.uint32)
+    L, ctx = amb._L, C.c_void_p()
+    check(L.blah2hip_ctx_create(amb.device, C.byref(ctx)))
+    bufs = []
+    try:
+        for nbytes in (data.nbytes, met.nbytes, hits.nbytes, cnt.nbytes):
+            p = C.c_void_p()
+            check(L.blah2hip_ctx_malloc(ctx, nbytes, C.byref(p)))
+            bufs.append(p)
+        d_map, d_met, d_hits, d_cnt = bufs
+        check(L.blah2hip_ctx_h2d(ctx, d_map, _ptr(data), data.nbytes))
+        check(L.blah2hip_ctx_h2d(ctx, d_met, _ptr(met), met.nbytes))
+        enqueue(d_map, d_met, d_hits, cap, d_cnt, L.blah2hip_ctx_stream(ctx))
+        check(L.blah2hip_ctx_d2h(ctx, _ptr(cnt), d_cnt, cnt.nbytes))
+        check(L.blah2hip_ctx_d2h(ctx, _ptr(hits), d_hits, hits.nbytes))
+        check(L.blah2hip_ctx_sync(ctx))
+    finally:
+        for p in bufs:
+            L.blah2hip_ctx_free(ctx, p)
+        L.blah2hip_ctx_destroy(ctx)
+    return hits_to_detection(amb, hits, int(cnt[0]), cap)
+
+
+class OsCfarDetector1D:
+    """Ordered-statistic CFAR along delay (blah2hip_oscfar1d_*): the geometry of :class:`CfarDetector1D`, the threshold
+    ``alpha[n]`` times the k-th smallest training cell, ``k = oscfar_rank(n, 1000 rank)``.  No reference class.
+    :func:`oscfar_hits` is the same rule in NumPy."""
+
+    def __init__(self, pfa, nGuard, nTrain, minDelay, minDoppler, rank=0.75, looks=1):
+        for name, v in (("nGuard", nGuard), ("nTrain", nTrain), ("minDelay", minDelay)):
+            if not -128 <= int(v) <= 127:
+                raise ValueError(f"{name} outside int8 range")
+        if not 1 <= int(looks) <= _lib.MAX_CFAR_LOOKS:
+            raise ValueError("looks outside [1, MAX_CFAR_LOOKS]")
+        self.pfa, self.nGuard, self.nTrain = float(pfa), int(nGuard), int(nTrain)
+        self.minDelay, self.minDoppler = int(minDelay), float(minDoppler)
+        self.rank_permille = _rank_permille(rank)
+        self.looks = int(looks)  # as for CfarDetector1D
+
+    def process(self, x: Map, amb=None) -> Detection:
+        """On the engine's device copy while ``x`` still is that map, else on an upload of ``x.data`` (``amb``: the handle
+        that gives the geometry when the map has no owner)."""
+        amb = amb if amb is not None else x._owner
+        if x._owner is amb and x.device_copy_is_current():
+            cap = x.data.size
+            d, f, s = np.zeros(cap), np.zeros(cap), np.zeros(cap)
+            n = C.c_uint32(0)
+            amb.set_cfar_looks(self.looks)
+            check(amb._L.blah2hip_oscfar1d_process(amb._h, x._cpi_index, self.pfa, self.rank_permille, self.nGuard, self.nTrain,
+                                                   self.minDelay, self.minDoppler, _ptr(d), _ptr(f), _ptr(s), cap, C.byref(n)))
+            k = n.value
+            return Detection(d[:k].copy(), f[:k].copy(), s[:k].copy())
+        return _detect_host_map(amb, x, lambda d_map, d_met, d_hits, cap, d_cnt, st:
+                                self.process_dev(amb, 1, d_hits, cap, d_cnt, d_map, d_met, st))
+
+    def process_dev(self, amb, n_cpi, d_hits, cap, d_count, d_map=None, d_metrics=None, stream=0):
+        """Enqueue the detector for n_cpi device-resident maps, like :meth:`CfarDetector1D.process_dev`."""
+        amb.set_cfar_looks(self.looks)
+        check(amb._L.blah2hip_oscfar1d_dev(amb._h, d_map, d_metrics, n_cpi, self.pfa, self.rank_permille, self.nGuard,
+                                           self.nTrain, self.minDelay, self.minDoppler, d_hits, cap, d_count, stream))
+
+
+class OsCfarDetector2D:
+    """Ordered-statistic CFAR over the window of :class:`CfarDetector2D` (blah2hip_oscfar2d_*); with nGuardDoppler =
+    nTrainDoppler = 0 it returns what :class:`OsCfarDetector1D` returns.  Windows beyond a halo of 40 delay columns or 24
+    Doppler rows are refused (ERR_UNSUPPORTED)."""
+
+    def __init__(self, pfa, nGuardDelay, nTrainDelay, nGuardDoppler, nTrainDoppler, minDelay, minDoppler, rank=0.75, looks=1):
+        if not 1 <= int(looks) <= _lib.MAX_CFAR_LOOKS:
+            raise ValueError("looks outside [1, MAX_CFAR_LOOKS]")
+        self.pfa = float(pfa)
+        self.p = [int(nGuardDelay), int(nTrainDelay), int(nGuardDoppler), int(nTrainDoppler)]
+        self.minDelay, self.minDoppler = int(minDelay), float(minDoppler)
+        self.rank_permille = _rank_permille(rank)
+        self.looks = int(looks)
+
+    def process(self, x: Map, amb=None) -> Detection:
+        amb = amb if amb is not None else x._owner
+        if x._owner is amb and x.device_copy_is_current():
+            cap = x.data.size
+            d, f, s = np.zeros(cap), np.zeros(cap), np.zeros(cap)
+            n = C.c_uint32(0)
+            amb.set_cfar_looks(self.looks)
+            check(amb._L.blah2hip_oscfar2d_process(amb._h, x._cpi_index, self.pfa, self.rank_permille, *self.p, self.minDelay,
+                                                   self.minDoppler, _ptr(d), _ptr(f), _ptr(s), cap, C.byref(n)))
+            k = n.value
+            return Detection(d[:k].copy(), f[:k].copy(), s[:k].copy())
+        return _detect_host_map(amb, x, lambda d_map, d_met, d_hits, cap, d_cnt, st:
+                                self.process_dev(amb, 1, d_hits, cap, d_cnt, d_map, d_met, st))
+
+    def process_dev(self, amb, n_cpi, d_hits, cap, d_count, d_map=None, d_metrics=None, stream=0):
+        amb.set_cfar_looks(self.looks)
+        check(amb._L.blah2hip_oscfar2d_dev(amb._h, d_map, d_metrics, n_cpi, self.pfa, self.rank_permille, *self.p,
+                                           self.minDelay, self.minDoppler, d_hits, cap, d_count, stream))
 
 
 class MapIntegrator:

@@ -599,7 +599,11 @@ class GpuChain:
     CPI is itself ``{"skipped": True}``.  The CPI count and the history run on from batch to batch; :meth:`run_batches`
     starts a capture at count 0, :meth:`reset_integrator` does so for a caller of ``chain(iq)``.  Ranks that take the
     batches round-robin see no consecutive CPIs across a batch's end: :meth:`shard_check` then asks for H == W and a batch
-    of whole windows, and every batch starts at count 0.  Without the key the chain is the one described above."""
+    of whole windows, and every batch starts at count 0.  Without the key the chain is the one described above.
+
+    ``cfg["detection"]["cfar"] = "os"`` (default "ca") builds :class:`blah2_amd.OsCfarDetector1D` at
+    ``cfg["detection"]["rank"]`` (default 0.75) in the place of ``CfarDetector1D``, for the integrator's looks as well; the
+    hit buffers, the finisher and the results are the same."""
 
     def __init__(self, cfg: dict, device: int = 0, batch: int = 1, want_map: bool = False, depth: int = 3,
                  reader_threads: int = 4, hit_copy: int = 4096, read_mode: str = "memmove", numa: bool = True,
@@ -689,8 +693,17 @@ class GpuChain:
             self._ok_tail = []       # filter flags of the last W - 1 CPIs collected
             looks = {"looks": self.nci.looks}
         if det_c.get("enable", False):
-            self.cfar = blah2_amd.CfarDetector1D(det_c["pfa"], det_c["nGuard"], det_c["nTrain"], det_c["minDelay"],
-                                                 det_c["minDoppler"], **looks)
+            # detection: {cfar: ca | os, rank: 0.75}: the cell-averaging detector of the reference (default), or the
+            # ordered-statistic one at that rank on the same window; both leave the same hit lists
+            kind = str(det_c.get("cfar", "ca")).lower()
+            if kind not in ("ca", "os"):
+                raise ValueError(f"detection.cfar {kind!r}: 'ca' or 'os'")
+            if kind == "os":
+                self.cfar = blah2_amd.OsCfarDetector1D(det_c["pfa"], det_c["nGuard"], det_c["nTrain"], det_c["minDelay"],
+                                                       det_c["minDoppler"], rank=float(det_c.get("rank", 0.75)), **looks)
+            else:
+                self.cfar = blah2_amd.CfarDetector1D(det_c["pfa"], det_c["nGuard"], det_c["nTrain"], det_c["minDelay"],
+                                                     det_c["minDoppler"], **looks)
             if "nCentroid" in det_c:  # blah2.cpp:176-181
                 self.centroid = blah2_amd.Centroid(det_c["nCentroid"], det_c["nCentroid"], 1 / (n / self.fs))
                 self.interp = blah2_amd.Interpolate(True, True)
@@ -1139,6 +1152,10 @@ def main(argv=None):
                     help="non-coherent integration of the maps over a sliding window of W consecutive CPIs (1 ... 16), a "
                          "window every H CPIs (default 1); the detector's thresholds are made for W looks.  CPIs at which no "
                          "window ends give no frame.  Several ranks: H == W and --batch a multiple of W")
+    ap.add_argument("--cfar", default=None, metavar="KIND[:RANK]",
+                    help="the detector: ca (cell averaging, the reference's) or os[:RANK] (ordered statistic: the threshold "
+                         "from the RANK-th part of the sorted training cells, default 0.75); overrides "
+                         "process.detection.cfar / .rank of the config")
     ap.add_argument("--connect", action="store_true",
                     help="with --json: send the documents to network.ip:ports.map / ports.detection of the config, "
                          "framed like Socket::sendData, instead of printing them")
@@ -1171,6 +1188,16 @@ def main(argv=None):
         except ValueError:
             ap.error("--integrate takes W or W:H, a window and a hop in CPIs, both >= 1")
         cfg["integrate"] = {"window": wh_[0], "hop": wh_[1] if len(wh_) == 2 else 1}
+    if a.cfar is not None:
+        kind, _, rank_ = a.cfar.partition(":")
+        try:
+            if kind not in ("ca", "os") or (rank_ and (kind != "os" or not 0.001 <= float(rank_) <= 1.0)):
+                raise ValueError
+        except ValueError:
+            ap.error("--cfar takes ca, os or os:RANK with RANK in [0.001, 1]")
+        cfg["detection"] = dict(cfg.get("detection") or {}, cfar=kind)
+        if rank_:
+            cfg["detection"]["rank"] = float(rank_)
     dist = None
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:

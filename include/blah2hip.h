@@ -613,6 +613,62 @@ int blah2hip_cfar2d_process(blah2hip_amb_t h, uint32_t cpi, double pfa, int32_t 
                             int32_t min_delay, double min_doppler, double *delay, double *doppler,
                             double *snr, uint32_t cap, uint32_t *count);
 
+/* ---- Ordered-statistic CFAR (OS-CFAR, Rohling; NOT in the reference) -------
+ * The detectors above average their training cells; a second echo, a clutter edge or a sidelobe inside the training window
+ * raises that mean and masks the cell under test.  Here the threshold is alpha[n] * x_(k), the k-th smallest of the n
+ * in-bounds training cells: a handful of interferers in the window do not move it.  With p = |z|^2 formed in fp64 as the
+ * detectors above form it, training cells p_1 .. p_n of the cell under test c, and
+ *   k(n) = max(1, ceil(n * rank_permille / 1000))                 integer arithmetic, rank_permille in 1 .. 1000
+ *   hit  <=>  n >= 1  and  #{ i : alpha[n] * p_i < p_c } >= k(n)   product and compare in fp64
+ * This is p_c > alpha[n] * x_(k) (multiplying by a positive factor and rounding is monotone) stated as a count: no sort.
+ * The rule is the contract and fixes the special values: a NaN or +Inf training cell is never below (it costs its window
+ * one rank, not the detection), a NaN cell under test never hits, a +Inf cell hits when k of its training cells are finite,
+ * an all-zero map has no hits.  |z|^2 of fp32 parts has exact products in fp64 and rounds once, alpha * p_i is one
+ * multiply: the decision is the same bits on the device and in an fp64 restatement with the same table (process.py:
+ * oscfar_hits).
+ *
+ * blah2hip_oscfar_alpha: the tables, host arithmetic only (no GPU is touched).  alpha[0] = NaN, rank[0] = 0; for
+ * n = 1 .. max_n rank[n] = k(n) and alpha[n] solves Pfa(alpha; n, k) = pfa for cells that are sums of `looks` looks of noise:
+ *   looks == 1:  Pfa = prod_{i=0}^{k-1} (n - i) / (n - i + alpha), solved by bisection on its logarithm
+ *                -sum log1p(alpha / (n - i)) until the interval no longer splits (its upper end);
+ *   looks = L > 1 (the maps of blah2hip_nci_process_dev, Gamma(L) cells):
+ *                Pfa = int f_(k)(x) Q_L(alpha x) dx,  Q_L(t) = e^-t sum_{j<L} t^j / j!,
+ *                f_(k)(x) = n! / ((k-1)! (n-k)!) P^(k-1) Q_L(x)^(n-k) x^(L-1) e^-x / (L-1)!,  P = 1 - Q_L(x),
+ *                the density of the k-th smallest of n Gamma(L) variables; composite Simpson, 16384 intervals over the
+ *                interval on which the integrand is within e^-60 of its largest value.  alpha: the bracket [hi / 2, hi] by
+ *                doubling (every trial on an interval of its own), then the same bisection on the interval of the
+ *                bracket's lower end, which holds the integrand of every larger alpha.
+ * alpha: max_n + 1 doubles; rank: max_n + 1 words, or NULL.  BLAH2HIP_ERR_INVALID: a NULL table, looks outside
+ * [1, BLAH2HIP_MAX_CFAR_LOOKS], rank_permille outside [1, 1000], pfa outside (0, 1). */
+int blah2hip_oscfar_alpha(double pfa, uint32_t looks, uint32_t rank_permille, uint32_t max_n, double *alpha, uint32_t *rank);
+/* The 1-D detector: geometry, quirks and output conventions of blah2hip_cfar1d_dev / _prepare / _process (leading cells
+ * never train on delay column 0, min_delay / min_doppler skips, count may exceed cap, row-major emission order of _process),
+ * n_train up to 127.  The tables (alpha and rank, uploaded together) are made for the handle's BLAH2HIP_OPT_CFAR_LOOKS at
+ * the time of the call and live in a cache of their own keyed by (pfa, looks, rank_permille, size) with the rules of the
+ * averaging detectors' cache (eight entries, least recently used first out, _prepare pins), which these calls do not touch:
+ * _dev only enqueues after the first call with a new tuple.  Timing counts under BLAH2HIP_K_CFAR. */
+int blah2hip_oscfar1d_dev(blah2hip_amb_t h, const void *d_map, const double *d_metrics, uint32_t n_cpi, double pfa,
+                          uint32_t rank_permille, int32_t n_guard, int32_t n_train, int32_t min_delay, double min_doppler,
+                          blah2hip_hit_t *d_hits, uint32_t cap, uint32_t *d_count, void *stream);
+int blah2hip_oscfar1d_prepare(blah2hip_amb_t h, double pfa, uint32_t rank_permille, int32_t n_train);
+int blah2hip_oscfar1d_process(blah2hip_amb_t h, uint32_t cpi, double pfa, uint32_t rank_permille, int32_t n_guard,
+                              int32_t n_train, int32_t min_delay, double min_doppler, double *delay, double *doppler,
+                              double *snr, uint32_t cap, uint32_t *count);
+/* The 2-D detector on the window of blah2hip_cfar2d_*: the rectangle minus the guard box, in-bounds cells only, delay
+ * column 0 never trains; with n_guard_doppler = n_train_doppler = 0 it reports the 1-D detector's hits.  One kernel with a
+ * tile and its halo in LDS: n_guard_doppler + n_train_doppler <= 24 and n_guard_delay + n_train_delay <= 40; a wider window
+ * is BLAH2HIP_ERR_UNSUPPORTED (a rank has no summed-area form).  BLAH2HIP_OPT_CFAR2D_KERNEL does not apply. */
+int blah2hip_oscfar2d_dev(blah2hip_amb_t h, const void *d_map, const double *d_metrics, uint32_t n_cpi, double pfa,
+                          uint32_t rank_permille, int32_t n_guard_delay, int32_t n_train_delay, int32_t n_guard_doppler,
+                          int32_t n_train_doppler, int32_t min_delay, double min_doppler, blah2hip_hit_t *d_hits,
+                          uint32_t cap, uint32_t *d_count, void *stream);
+int blah2hip_oscfar2d_prepare(blah2hip_amb_t h, double pfa, uint32_t rank_permille, int32_t n_guard_delay,
+                              int32_t n_train_delay, int32_t n_guard_doppler, int32_t n_train_doppler);
+int blah2hip_oscfar2d_process(blah2hip_amb_t h, uint32_t cpi, double pfa, uint32_t rank_permille, int32_t n_guard_delay,
+                              int32_t n_train_delay, int32_t n_guard_doppler, int32_t n_train_doppler, int32_t min_delay,
+                              double min_doppler, double *delay, double *doppler, double *snr, uint32_t cap,
+                              uint32_t *count);
+
 /* ---- Centroid / Interpolate (host-side, tens of detections) -------------- */
 /* Centroid::process (src/process/detection/Centroid.cpp:19-73): keeps a
  * detection unless a stronger one lies strictly inside its
