@@ -2,10 +2,14 @@
 nci_kernel), the detectors' thresholds for the looks of the sum (BLAH2HIP_OPT_CFAR_LOOKS) and the replay chain behind it.
 
 No reference counterpart; the check is the fp64 NumPy restatement ``integrate_maps``.  The kernel reads any buffer with the
-map layout, so most cases feed crafted maps: cell (k, c, ...) of channel k and CPI c is ``level(k, c) exp(i phi)`` with
-``level = 1 + 0.25 ((3 k + 5 c) mod 7)`` and a random phase -- every term of a sum is of the size of the sum, so a dropped,
-doubled or swapped channel or CPI moves every cell by far more than the bound.  The handle is only there for its
-dimensions.
+map layout, so most cases feed crafted maps (tests/integrate_crafted.py ``maps``): cell (k, c, i) of channel k and CPI c is
+``level(k, c) u exp(i phi)`` with ``level = 1 + 0.25 ((3 k + 5 c) mod 7)``, ``u`` uniform in [0.7, 1.4] per (k, c, cell) and
+a random phase -- every term of a sum is of the size of the sum, so a dropped or doubled channel or CPI moves every cell by
+far more than the bound; a swapped one does so only where the two differ, which is what ``u`` is for (``level`` alone is the
+same in every cell of a plane and has period 7 in c, and the kernel never sees the phase).  The handle is only there for its
+dimensions.  The same kernel at every window and ring length, under every cut into calls, on maps 8 bytes off a 16-byte
+boundary and with its metrics on a moving peak: tests/test_integrate_crafted_gpu.py, with the CPU proof of what those cases
+reach and catch in tests/test_integrate_crafted_model.py.
 
 Bounds
   * cells: ``|out - ref| <= (K W + 8) 2^-24 ref``, derived, not measured: all terms are non-negative, so a relative
@@ -24,6 +28,8 @@ import ctypes as C
 
 import numpy as np
 import pytest
+
+import integrate_crafted as IC
 
 pytestmark = pytest.mark.gpu
 
@@ -80,11 +86,8 @@ def untouched(whole):
 
 
 def crafted(K, n_cpi, nD, nC, seed):
-    rng = np.random.default_rng(seed)
-    k, c = np.arange(K)[:, None], np.arange(n_cpi)[None, :]
-    level = 1.0 + 0.25 * ((3 * k + 5 * c) % 7)
-    z = level[:, :, None, None] * np.exp(2j * np.pi * rng.uniform(0, 1, (K, n_cpi, nD, nC)))
-    return z.astype(np.complex64)
+    """integrate_crafted.maps: the levels under a factor drawn per (k, c, cell), so that no two cells are alike."""
+    return IC.maps(K, n_cpi, nD, nC, seed)
 
 
 def shape_of(amb):
