@@ -31,6 +31,11 @@ OPT_CFAR2D_SEG_ROWS, OPT_CFAR2D_GRID = 9, 10
 OPT_MULTI_SURV_RANGE = 11
 OPT_RANGE_WALK = 12
 OPT_CFAR_LOOKS = 13
+OPT_TAPER_SEG_ROWS = 14
+MAX_TAPER_SIDE = 4
+TAPER_NONE, TAPER_HANN, TAPER_HAMMING, TAPER_BLACKMAN, TAPER_BLACKMAN_HARRIS, TAPER_NUTTALL, TAPER_FLATTOP = 0, 1, 2, 3, 4, 5, 6
+TAPER_KINDS = {"none": TAPER_NONE, "hann": TAPER_HANN, "hamming": TAPER_HAMMING, "blackman": TAPER_BLACKMAN,
+               "blackmanharris": TAPER_BLACKMAN_HARRIS, "nuttall": TAPER_NUTTALL, "flattop": TAPER_FLATTOP}
 MAX_CFAR_LOOKS = 1024
 MAX_NCI_WINDOW = 16
 WALK_AUTO, WALK_STATIC, WALK_TICKET = 0, 1, 2
@@ -63,6 +68,7 @@ INFO_HOT_COLUMNS, INFO_HOT_COLUMNS_MISSED = 10, 11
 INFO_CFAR2D_SEG_ROWS, INFO_CFAR2D_GRID = 12, 13
 INFO_DETECT_GRID, INFO_DETECT_TILED = 14, 15
 INFO_BEARING_GRID = 16
+INFO_TAPER_GRID = 17
 
 
 class Blah2HipError(RuntimeError):
@@ -129,6 +135,8 @@ SYMBOLS = {
     "blah2hip_nci_process_dev": (C.c_int, [_vp, _vp, _u32, _vp, _vp, _vp, _u32, C.POINTER(_u32), C.POINTER(C.c_uint64), _vp]),
     "blah2hip_nci_set_timing": (C.c_int, [_vp, C.c_int]),
     "blah2hip_nci_get_timing": (C.c_int, [_vp, _vp, _vp]),
+    "blah2hip_doppler_taper": (C.c_int, [C.c_int, C.c_int, _vp, C.POINTER(_u32)]),
+    "blah2hip_amb_taper_dev": (C.c_int, [_vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp]),
     "blah2hip_cfar_alpha": (C.c_int, [_dbl, _u32, _u32, _vp]),
     "blah2hip_cfar1d_dev": (C.c_int, [_vp, _vp, _vp, _u32, _dbl, _i32, _i32, _i32, _dbl, _vp, _u32, _vp, _vp]),
     "blah2hip_cfar1d_prepare": (C.c_int, [_vp, _dbl, _i32]),

@@ -1,6 +1,6 @@
 // Internal to the library: what the units behind include/blah2hip.h share.  The ambiguity handle, whose fields every
 // unit reads directly (no accessors), the error and launch-check helpers, and the few engine functions (capi.hip)
-// that another unit calls.  Host code only: capi.hip, array.hip, detect.hip and context.hip all include it.
+// that another unit calls.  Host code only: capi.hip, array.hip, detect.hip, integrate.hip, taper.hip and context.hip all include it.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -54,6 +54,7 @@ struct blah2hip_amb_s {
   int leakMode = 1;                 // BLAH2HIP_OPT_LEAK_COMPENSATION: 0 off, 1 auto (applied where it can reach 3e-5 of the mean level), 2 always
   int hotMode = 1;                  // BLAH2HIP_OPT_HOT_COLUMNS: 0 off, 1 auto (CPIs long enough for a peak HOT_RATIO above the mean level), 2 always
   uint32_t cfarLooks = 1;           // BLAH2HIP_OPT_CFAR_LOOKS: looks per cell the detectors' threshold factors are made for (detect.hip)
+  int taperSegRows = 0;             // BLAH2HIP_OPT_TAPER_SEG_ROWS (0 = the launch's own choice, taper.hip)
 
   // ---- device buffers allocated by create (capi.hip) and freed by destroy, which frees every buffer of the handle
   cf *d_tw = nullptr;
@@ -103,7 +104,7 @@ struct blah2hip_amb_s {
   int lastLeakLags = 0;             // BLAH2HIP_INFO_LEAK_LAGS: lags corrected by the last process call (0 = not applied)
   double lastLeakMax = 0.0;         // BLAH2HIP_INFO_LEAK_MAX_E12: the largest |g| of the calibration the last call ran under
 
-  // ---- written by detect.hip; bearingGridLast by array.hip
+  // ---- written by detect.hip; bearingGridLast by array.hip, taperGridLast by taper.hip
   struct AlphaTable { double pfa; uint32_t looks; size_t n; double *d; bool pinned; }; // pinned: handed out by *_prepare, never evicted
   std::vector<AlphaTable> alphaTables; // CFAR threshold factors, one per (pfa, looks, size) seen
   struct OsTable { double pfa; uint32_t looks, rank; size_t n; double *d; bool pinned; }; // d: alpha[n + 1], then rank[n + 1] words
@@ -114,6 +115,7 @@ struct blah2hip_amb_s {
   int cfar2dSegRowsLast = 0, cfar2dGridLast = 0; // BLAH2HIP_INFO_CFAR2D_SEG_ROWS / _GRID
   int detGridLast = 0, detTiledLast = 0; // BLAH2HIP_INFO_DETECT_GRID / _TILED
   int bearingGridLast = 0;          // BLAH2HIP_INFO_BEARING_GRID
+  int taperGridLast = 0;            // BLAH2HIP_INFO_TAPER_GRID
 
   // ---- every unit brackets its launches (tic / toc below)
   blah2::KernelTimer<BLAH2HIP_K_COUNT> timer;

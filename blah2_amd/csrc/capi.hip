@@ -1144,6 +1144,10 @@ int blah2hip_amb_set_option(blah2hip_amb_t h, int option, int64_t value)
     if (value < 1 || value > BLAH2HIP_MAX_CFAR_LOOKS) return fail(BLAH2HIP_ERR_INVALID, "CFAR looks outside [1, BLAH2HIP_MAX_CFAR_LOOKS]");
     h->cfarLooks = (uint32_t)value;
     return BLAH2HIP_OK;
+  case BLAH2HIP_OPT_TAPER_SEG_ROWS:
+    if (value < 0 || value > 65535) return fail(BLAH2HIP_ERR_INVALID, "taper rows per segment outside [0, 65535]");
+    h->taperSegRows = (int)value;
+    return BLAH2HIP_OK;
   default: return fail(BLAH2HIP_ERR_INVALID, "unknown option");
   }
 }
@@ -1181,6 +1185,7 @@ int blah2hip_amb_get_info(blah2hip_amb_t h, int key, int64_t *value)
   case BLAH2HIP_INFO_DETECT_GRID: *value = h->detGridLast; return BLAH2HIP_OK;
   case BLAH2HIP_INFO_DETECT_TILED: *value = h->detTiledLast; return BLAH2HIP_OK;
   case BLAH2HIP_INFO_BEARING_GRID: *value = h->bearingGridLast; return BLAH2HIP_OK;
+  case BLAH2HIP_INFO_TAPER_GRID: *value = h->taperGridLast; return BLAH2HIP_OK;
   case BLAH2HIP_INFO_LEAK_LAGS: *value = h->lastLeakLags; return BLAH2HIP_OK;
   case BLAH2HIP_INFO_LEAK_MAX_E12: *value = (int64_t)std::llround(h->lastLeakMax * 1e12); return BLAH2HIP_OK;
   case BLAH2HIP_INFO_HOT_COLUMNS: { // of the last call's first CPI; waits for the device

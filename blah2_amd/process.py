@@ -11,6 +11,7 @@ blah2.cpp lives in blah2_amd/host/.)
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -536,6 +537,84 @@ def integrate_maps(maps, w=None, window=1, hop=None):
     return np.stack(out) if out else np.zeros((0,) + m.shape[2:])
 
 
+# a_0 .. a_P of the cosine-sum windows w[i] = sum_p (-1)^p a_p cos(2 pi p i / n): blah2hip_doppler_taper's table
+TAPER_COEFFS = {
+    "none": (1.0,),
+    "hann": (0.5, 0.5),
+    "hamming": (0.54, 0.46),
+    "blackman": (0.42, 0.5, 0.08),
+    "blackmanharris": (0.35875, 0.48829, 0.14128, 0.01168),
+    "nuttall": (0.3635819, 0.4891775, 0.1365995, 0.0106411),
+    "flattop": (0.21557895, 0.41663158, 0.277263158, 0.083578947, 0.006947368),
+}
+
+
+def _taper_coeffs(name):
+    try:
+        return TAPER_COEFFS[str(name).lower()]
+    except KeyError:
+        raise ValueError(f"unknown Doppler window {name!r}: one of {', '.join(TAPER_COEFFS)}") from None
+
+
+def doppler_taper(name, normalise=False):
+    """The taps ``t_0 .. t_P`` (fp64) of the circular Doppler stencil that equals the named slow-time window:
+    ``t_0 = a_0``, ``t_m = (-1)^m a_m / 2``.  ``normalise`` divides by ``a_0``, so that an echo on a Doppler bin keeps its
+    amplitude.  ``blah2hip_doppler_taper`` returns their fp32 roundings (:func:`doppler_taper_f32`)."""
+    a = _taper_coeffs(name)
+    t = np.array([a[0]] + [(-0.5 if m & 1 else 0.5) * a[m] for m in range(1, len(a))], dtype=np.float64)
+    return t / a[0] if normalise else t
+
+
+def doppler_taper_f32(name, normalise=False):
+    """``blah2hip_doppler_taper``: the library's own fp32 taps of a named window, ``n_side + 1`` of them."""
+    key = str(name).lower()
+    _taper_coeffs(key)
+    taps = np.zeros(_lib.MAX_TAPER_SIDE + 1, dtype=np.float32)
+    n_side = C.c_uint32(0)
+    check(_lib.load().blah2hip_doppler_taper(_lib.TAPER_KINDS[key], int(bool(normalise)), _ptr(taps), C.byref(n_side)))
+    return taps[:n_side.value + 1].copy()
+
+
+def doppler_window(name, n):
+    """``w[i] = sum_p (-1)^p a_p cos(2 pi p i / n)``, ``i = 0 .. n - 1``: the periodic ("DFT-even") form,
+    ``scipy.signal.get_window(name, n, fftbins=True)``."""
+    a = _taper_coeffs(name)
+    i = np.arange(int(n), dtype=np.float64)
+    w = np.zeros(int(n))
+    for p_, ap in enumerate(a):
+        w += (-1.0) ** p_ * ap * np.cos(2.0 * np.pi * p_ * i / int(n))
+    return w
+
+
+def taper_maps(maps, taps):
+    """blah2hip_amb_taper_dev restated in fp64 NumPy: the circular stencil along axis -2 (the Doppler rows) of ``maps``,
+    ``M'[j] = t_0 M[j] + sum_m t_m (M[j - m] + M[j + m])`` with the rows taken modulo nD."""
+    m = np.asarray(maps)
+    m = m.astype(np.complex128 if np.iscomplexobj(m) else np.float64)
+    t = np.asarray(taps, dtype=np.float64)
+    if t.ndim != 1 or t.size < 1:
+        raise ValueError("taps must be t_0 .. t_P")
+    if m.ndim < 2 or m.shape[-2] < 2 * (t.size - 1) + 1:
+        raise ValueError("fewer Doppler rows than the stencil has taps")
+    with np.errstate(all="ignore"):
+        out = t[0] * m
+        for k in range(1, t.size):
+            out = out + t[k] * np.roll(m, k, axis=-2)
+            out = out + t[k] * np.roll(m, -k, axis=-2)
+    return out
+
+
+def taper_gains(taps):
+    """What a stencil does to echoes and noise: ``(coherent_gain, noise_power_gain, enbw_bins, snr_loss_db)`` -- the
+    amplitude gain ``t_0`` of an echo on a Doppler bin, the power gain ``t_0^2 + 2 sum t_m^2`` of white noise, their ratio
+    ``noise / coherent^2`` (the equivalent noise bandwidth in bins) and ``10 log10`` of it (the SNR an on-bin echo loses)."""
+    t = np.asarray(taps, dtype=np.float64)
+    coherent = float(t[0])
+    noise = float(t[0] ** 2 + 2.0 * np.sum(t[1:] ** 2))
+    enbw = noise / coherent ** 2
+    return coherent, noise, enbw, 10.0 * math.log10(enbw)
+
+
 class Map:
     """src/data/Map.h: rows = Doppler, cols = delay.  ``data`` is complex64."""
 
@@ -963,6 +1042,20 @@ class Ambiguity:
         """Doppler rows per segment of the 2-D stream kernel (0 = its cost model); ``info(INFO_CFAR2D_SEG_ROWS)`` reports
         what the last launch used."""
         check(self._L.blah2hip_amb_set_option(self._h, _lib.OPT_CFAR2D_SEG_ROWS, int(n)))
+
+    def taper_dev(self, d_map, n_maps, taps, d_out_map, d_out_metrics, stream=0):
+        """The Doppler stencil ``taps`` (``t_0 .. t_P``, host, rounded to fp32: :func:`doppler_taper`) over ``n_maps`` maps on
+        the device (blah2hip_amb_taper_dev; raw pointers/ints): ``d_map`` None is the handle's own map; the outputs are
+        ``[n_maps][nD][nDelay]`` complex64 and ``[n_maps][2]`` float64 and must not overlap the input.  Enqueues only."""
+        t = np.ascontiguousarray(taps, dtype=np.float32)
+        if t.ndim != 1 or t.size < 1:
+            raise ValueError("taps must be t_0 .. t_P")
+        check(self._L.blah2hip_amb_taper_dev(self._h, d_map, n_maps, _ptr(t), t.size - 1, d_out_map, d_out_metrics, stream))
+
+    def set_taper_seg_rows(self, n):
+        """Doppler rows per segment of the taper kernel (0 = the launch's own choice); ``info(INFO_TAPER_GRID)`` reports the
+        workgroups per map of the last launch."""
+        check(self._L.blah2hip_amb_set_option(self._h, _lib.OPT_TAPER_SEG_ROWS, int(n)))
 
     def set_cfar2d_grid(self, n):
         """Workgroup cap of the persistent 2-D tile kernel (0 = one per CU); ``info(INFO_CFAR2D_GRID)`` reports the grid of

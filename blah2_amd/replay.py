@@ -603,7 +603,13 @@ class GpuChain:
 
     ``cfg["detection"]["cfar"] = "os"`` (default "ca") builds :class:`blah2_amd.OsCfarDetector1D` at
     ``cfg["detection"]["rank"]`` (default 0.75) in the place of ``CfarDetector1D``, for the integrator's looks as well; the
-    hit buffers, the finisher and the results are the same."""
+    hit buffers, the finisher and the results are the same.
+
+    ``cfg["ambiguity"]["window"]`` names a Doppler taper (``blah2_amd.doppler_taper``: hann, hamming, blackman,
+    blackmanharris, nuttall, flattop; ``NAME:norm`` divides the taps by a_0): one stencil kernel directly behind the
+    ambiguity stage on the compute stream (``Ambiguity.taper_dev``), and everything after it -- the integrator, the
+    detector, the finisher, the downloaded maps and metrics -- reads the tapered buffers.  The stage holds no state.
+    Without the key, or with ``none``, nothing is allocated or launched."""
 
     def __init__(self, cfg: dict, device: int = 0, batch: int = 1, want_map: bool = False, depth: int = 3,
                  reader_threads: int = 4, hit_copy: int = 4096, read_mode: str = "memmove", numa: bool = True,
@@ -665,6 +671,14 @@ class GpuChain:
         self.fs, self.n = int(cfg["fs"]), int(cfg["n_samples"])
         n, B = self.n, int(batch)
         self.batch, self.depth, self.want_map = B, max(2, int(depth)), bool(want_map)
+        # ambiguity: {window: NAME[:norm]}: the Doppler taper's taps (None: no taper stage)
+        self.taper = None
+        win = str(amb_c.get("window") or "none").lower()
+        name, _, norm = win.partition(":")
+        if norm not in ("", "norm"):
+            raise ValueError(f"ambiguity.window {win!r}: NAME or NAME:norm")
+        if name != "none" or norm:
+            self.taper = blah2_amd.doppler_taper_f32(name, norm == "norm")  # (refuses an unknown name)
         self.amb = blah2_amd.Ambiguity(amb_c["delayMin"], amb_c["delayMax"], amb_c["dopplerMin"], amb_c["dopplerMax"],
                                        self.fs, n, True, device=device, max_batch=B)
         nD, nC = self.amb.get_n_doppler_bins(), self.amb.get_n_delay_bins()
@@ -682,6 +696,9 @@ class GpuChain:
             if self.fused_fir:
                 self.amb.set_fir(self.wh)
         self.cfar = self.centroid = self.interp = None
+        if self.taper is not None and nD < 2 * (len(self.taper) - 1) + 1:
+            self.amb.close()
+            raise ValueError(f"ambiguity.window {win!r}: a stencil of {2 * len(self.taper) - 1} taps on {nD} Doppler bins")
         self.nci = None
         looks = {}
         if cfg.get("integrate"):
@@ -777,6 +794,9 @@ class GpuChain:
                 # time the GPU spent computing (`busy_ms`), the rest of the wall clock it waited for the host link
                 "started": torch.cuda.Event(enable_timing=True), "computed": torch.cuda.Event(enable_timing=True),
             }
+            if self.taper is not None:  # the tapered maps and their metrics: what everything behind the ambiguity stage reads
+                s["d_tmap"] = torch.zeros((B, nD, nC), dtype=torch.complex64, device=dev)
+                s["d_tmet"] = torch.zeros((B, 2), dtype=torch.float64, device=dev)
             if self.nci is not None:  # the integrated maps and their metrics: what the detector and the download read
                 s["d_imap"] = torch.zeros((B, nD, nC), dtype=torch.complex64, device=dev)
                 s["d_imet"] = torch.zeros((B, 2), dtype=torch.float64, device=dev)
@@ -887,6 +907,9 @@ class GpuChain:
                 amb.process_dev(fmt_yf, x, self.yf.data_ptr(), cnt, n, slot["d_map"].data_ptr(),
                                 slot["d_met"].data_ptr(), st)
             n_maps, maps, mets = cnt, slot["d_map"], slot["d_met"]  # what the detector and the download read
+            if self.taper is not None:
+                amb.taper_dev(maps.data_ptr(), cnt, self.taper, slot["d_tmap"].data_ptr(), slot["d_tmet"].data_ptr(), st)
+                maps, mets = slot["d_tmap"], slot["d_tmet"]
             if self.nci is not None:
                 if self._per_batch:
                     self.reset_integrator()
@@ -1152,6 +1175,10 @@ def main(argv=None):
                     help="non-coherent integration of the maps over a sliding window of W consecutive CPIs (1 ... 16), a "
                          "window every H CPIs (default 1); the detector's thresholds are made for W looks.  CPIs at which no "
                          "window ends give no frame.  Several ranks: H == W and --batch a multiple of W")
+    ap.add_argument("--doppler-window", default=None, metavar="NAME[:norm]",
+                    help="Doppler taper behind the ambiguity stage: none, hann, hamming, blackman, blackmanharris, nuttall or "
+                         "flattop; :norm divides the taps by a_0 (an echo on a Doppler bin keeps its amplitude); overrides "
+                         "process.ambiguity.window of the config")
     ap.add_argument("--cfar", default=None, metavar="KIND[:RANK]",
                     help="the detector: ca (cell averaging, the reference's) or os[:RANK] (ordered statistic: the threshold "
                          "from the RANK-th part of the sorted training cells, default 0.75); overrides "
@@ -1188,6 +1215,12 @@ def main(argv=None):
         except ValueError:
             ap.error("--integrate takes W or W:H, a window and a hop in CPIs, both >= 1")
         cfg["integrate"] = {"window": wh_[0], "hop": wh_[1] if len(wh_) == 2 else 1}
+    if a.doppler_window is not None:
+        from .process import TAPER_COEFFS
+        name_, _, norm_ = a.doppler_window.lower().partition(":")
+        if name_ not in TAPER_COEFFS or norm_ not in ("", "norm"):
+            ap.error(f"--doppler-window takes NAME or NAME:norm, NAME one of {', '.join(TAPER_COEFFS)}")
+        cfg["ambiguity"] = dict(cfg["ambiguity"], window=a.doppler_window.lower())
     if a.cfar is not None:
         kind, _, rank_ = a.cfar.partition(":")
         try:

@@ -201,6 +201,10 @@ int blah2hip_amb_get_axes(blah2hip_amb_t h, int32_t *delay, double *doppler);
                                        * cached per (pfa, looks, size).  1 builds the table, and gives the bits, of a handle that never saw the
                                        * option.  blah2hip_cfar1d_map takes no handle and stays one-look */
 #define BLAH2HIP_MAX_CFAR_LOOKS 1024
+#define BLAH2HIP_OPT_TAPER_SEG_ROWS (BLAH2HIP_OPT_CFAR_LOOKS + 1) /* = 14: Doppler rows per segment of taper_kernel (blah2hip_amb_taper_dev: a workgroup walks one segment of one
+                                       * strip of 256 columns); 0 = the launch's own choice (32 rows); larger values are clipped to the map,
+                                       * smaller ones raised until a map's workgroups fit the handle's metrics partials.  For tests: seams
+                                       * and the wrap from row n_doppler - 1 to row 0 fall where a small fixture would not put them */
 #define BLAH2HIP_MULTI_AUTO 0
 #define BLAH2HIP_MULTI_SHARED 1
 #define BLAH2HIP_MULTI_PER_CHANNEL 2
@@ -253,6 +257,7 @@ int blah2hip_amb_set_option(blah2hip_amb_t h, int option, int64_t value);
 #define BLAH2HIP_INFO_DETECT_TILED 15        /* 1: that launch spread a CPI's hits over several workgroups (cap beyond one LDS tile of 1024
                                               * hits), 0: one workgroup per CPI */
 #define BLAH2HIP_INFO_BEARING_GRID 16         /* workgroups per list of the last blah2hip_amb_bearing_dev launch */
+#define BLAH2HIP_INFO_TAPER_GRID 17            /* workgroups per map of the last blah2hip_amb_taper_dev launch */
 int blah2hip_amb_get_info(blah2hip_amb_t h, int key, int64_t *value);
 
 /* Ambiguity::process + Map::set_metrics on host buffers (blah2.cpp:278-279).
@@ -541,6 +546,49 @@ int blah2hip_nci_count(blah2hip_nci_t n, uint32_t n_cpi, uint32_t *n_out, uint64
 int blah2hip_nci_process_dev(blah2hip_nci_t n, const void *d_map, uint32_t n_cpi, const float *w,
                              void *d_out_map, double *d_out_metrics, uint32_t out_cap,
                              uint32_t *n_out, uint64_t *first_end, void *stream);
+
+/* ---- Doppler taper (no reference counterpart: Ambiguity.cpp:152-169 transforms the pulses unwindowed) ----
+ * A cosine-sum slow-time window  w[i] = sum_{p=0..P} (-1)^p a_p cos(2 pi p i / n_doppler),  i = pulse 0 .. n_doppler - 1 (the
+ * periodic, "DFT-even" form), multiplied onto the range rows in front of the Doppler transform equals a real, symmetric
+ * (2P + 1)-tap CIRCULAR stencil along the Doppler rows of the finished map,
+ *   M'[j][d] = t_0 M[j][d] + sum_{m=1..P} t_m ( M[(j-m) mod n_doppler][d] + M[(j+m) mod n_doppler][d] ),
+ *   t_0 = a_0,  t_m = (-1)^m a_m / 2
+ * (the map's row order is a rotation of the transform's, so circular neighbours stay neighbours and rows 0 and
+ * n_doppler - 1 are adjacent -- for odd n_doppler and for the explicit even n_doppler_bins alike).  The taper is therefore
+ * one kernel over maps that are already on the device, and composes with everything that takes a d_map / d_metrics pair:
+ * the integrator, the detectors, the finisher, the beam former.  Arithmetic, per component, fp32, in this order:
+ *   acc = t_0 * M[j];   for m = 1 .. P:  acc = fmaf(t_m, M[j-m], acc);  acc = fmaf(t_m, M[j+m], acc)
+ * -- 2P + 1 roundings, each at most 2^-24 of B = sum_m |t_m| |M[j+m]| (m = -P .. P), in one fixed order: equal inputs give
+ * equal bits at every placement, segmentation and cut into calls; n_side = 0 with t_0 = 1 copies the cells bit for bit.
+ * A NaN cell makes the 2P + 1 cells of its column whose stencil holds it NaN and no other.  Along delay the cells stay
+ * independent (the 1-D detectors' pfa holds); along Doppler neighbours within P bins are correlated. */
+#define BLAH2HIP_MAX_TAPER_SIDE 4
+#define BLAH2HIP_TAPER_NONE 0            /* t_0 = 1, n_side 0 */
+#define BLAH2HIP_TAPER_HANN 1            /* a = 0.5, 0.5 */
+#define BLAH2HIP_TAPER_HAMMING 2         /* a = 0.54, 0.46 */
+#define BLAH2HIP_TAPER_BLACKMAN 3        /* a = 0.42, 0.5, 0.08 */
+#define BLAH2HIP_TAPER_BLACKMAN_HARRIS 4 /* a = 0.35875, 0.48829, 0.14128, 0.01168 */
+#define BLAH2HIP_TAPER_NUTTALL 5         /* a = 0.3635819, 0.4891775, 0.1365995, 0.0106411 */
+#define BLAH2HIP_TAPER_FLATTOP 6         /* a = 0.21557895, 0.41663158, 0.277263158, 0.083578947, 0.006947368 */
+/* Host only: the taps t_0 .. t_4 of a named window (those behind n_side are 0) and its half width.  normalise != 0 divides
+ * by a_0: an echo on a Doppler bin keeps its amplitude.  taps: BLAH2HIP_MAX_TAPER_SIDE + 1 floats, the fp32 roundings of
+ * the fp64 values.  BLAH2HIP_ERR_INVALID: an unknown kind, a NULL argument. */
+int blah2hip_doppler_taper(int kind, int normalise, float *taps, uint32_t *n_side);
+/* M' = stencil(M) for n_maps maps [n_doppler][n_delay] complex fp32 -- CPIs, virtual CPIs of channels or beams: any maps of
+ * this handle's geometry.  d_map NULL = the handle's internal map.  taps: HOST array of n_side + 1 floats, read at the call
+ * and carried in the launch arguments (any real taps, not only the named windows').  Outputs: d_out_map [n_maps][n_doppler]
+ * [n_delay] and d_out_metrics [n_maps][2], Map::set_metrics of every output map on the cells as written.  Enqueues only --
+ * taper_kernel (BLAH2HIP_K_BEAM) and metrics_kernel (BLAH2HIP_K_METRICS), which finishes the metrics in index order (no
+ * floating-point atomics) -- with no upload, allocation or synchronisation, and can be captured in a graph.  The grid
+ * depends on the map's geometry and BLAH2HIP_OPT_TAPER_SEG_ROWS alone, never on n_maps: a map's cells and metrics are the
+ * same bits however the maps are cut into calls.  The per-workgroup partials live in the handle's buffers, so calls on
+ * one handle must be ordered on the device.  Maps may sit at any 8-byte aligned address: every access is 8 bytes per lane,
+ * 512 contiguous bytes a wave, the same kernel and the same bits at every placement.
+ * BLAH2HIP_ERR_INVALID, with nothing enqueued: a NULL handle, n_side above BLAH2HIP_MAX_TAPER_SIDE, n_doppler below
+ * 2 n_side + 1, n_maps 0 or above max_batch, NULL taps or outputs, a tap that is not finite, a map that is not 8-byte
+ * aligned, an output that overlaps the input maps (the stencil cannot run in place). */
+int blah2hip_amb_taper_dev(blah2hip_amb_t h, const void *d_map, uint32_t n_maps, const float *taps, uint32_t n_side,
+                           void *d_out_map, double *d_out_metrics, void *stream);
 
 /* ---- CfarDetector1D (CfarDetector1D.h:46-55) ---------------------------- */
 /* dev: d_map/d_metrics as written by blah2hip_amb_process_dev (NULL = the
@@ -949,12 +997,13 @@ int blah2hip_amb_result_ptrs(blah2hip_amb_t h, const void **d_map, const double 
 /* ---- per-kernel timing (HIP events on the launch stream) ---------------- */
 #define BLAH2HIP_K_RANGE 0
 #define BLAH2HIP_K_DOPPLER 1
-#define BLAH2HIP_K_METRICS 2
+#define BLAH2HIP_K_METRICS 2   /* metrics_kernel: behind the Doppler kernels, the beam former, the integrator and the Doppler taper */
 #define BLAH2HIP_K_CFAR 3     /* cfar1d_kernel, cfar2d_tile_kernel or cfar2d_kernel */
 #define BLAH2HIP_K_SAT_ROWS 4 /* 2-D CFAR through the summed-area table (large windows): row prefix sums */
 #define BLAH2HIP_K_SAT_COLS 5 /* ... column prefix sums */
 #define BLAH2HIP_K_ROTATE 6   /* Doppler-centre shift (asymmetric limits only) */
-#define BLAH2HIP_K_BEAM 7     /* beamform_kernel (blah2hip_amb_beamform_dev; its metrics_kernel counts under _METRICS), beam_samples_kernel */
+#define BLAH2HIP_K_BEAM 7     /* beamform_kernel (blah2hip_amb_beamform_dev; its metrics_kernel counts under _METRICS), beam_samples_kernel,
+                               * taper_kernel (blah2hip_amb_taper_dev; its metrics_kernel counts under _METRICS too) */
 #define BLAH2HIP_K_COV 8      /* array_cov_kernel or sample_cov_kernel + cov_fold_kernel (blah2hip_amb_covariance_dev, _sample_covariance_dev) */
 #define BLAH2HIP_K_BEARING 9  /* bearing_kernel (blah2hip_amb_bearing_dev) */
 #define BLAH2HIP_K_COUNT 10
