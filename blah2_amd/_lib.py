@@ -69,6 +69,8 @@ INFO_CFAR2D_SEG_ROWS, INFO_CFAR2D_GRID = 12, 13
 INFO_DETECT_GRID, INFO_DETECT_TILED = 14, 15
 INFO_BEARING_GRID = 16
 INFO_TAPER_GRID = 17
+INFO_MIGRATE_GRID = 18
+MAX_MIGRATION = 512
 
 
 class Blah2HipError(RuntimeError):
@@ -137,6 +139,9 @@ SYMBOLS = {
     "blah2hip_nci_get_timing": (C.c_int, [_vp, _vp, _vp]),
     "blah2hip_doppler_taper": (C.c_int, [C.c_int, C.c_int, _vp, C.POINTER(_u32)]),
     "blah2hip_amb_taper_dev": (C.c_int, [_vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp]),
+    "blah2hip_migration_table": (C.c_int, [_vp, _dbl, _vp]),
+    "blah2hip_amb_set_migration": (C.c_int, [_vp, _vp]),
+    "blah2hip_amb_migrate_dev": (C.c_int, [_vp, _vp, _u32, _vp, _vp, _vp]),
     "blah2hip_cfar_alpha": (C.c_int, [_dbl, _u32, _u32, _vp]),
     "blah2hip_cfar1d_dev": (C.c_int, [_vp, _vp, _vp, _u32, _dbl, _i32, _i32, _i32, _dbl, _vp, _u32, _vp, _vp]),
     "blah2hip_cfar1d_prepare": (C.c_int, [_vp, _dbl, _i32]),

@@ -86,9 +86,9 @@ def _build_hip_locked(force, verbose):
     # (a library that came with the tree and has no stamp beside it was built by this script with the default flags)
     if not force and not _newer(LIB, deps) and (same_flags or (not os.path.exists(stamp) and not extra_flags())):
         return LIB
-    # one hipcc per translation unit (every csrc/*.hip), side by side, then one link (8 CPUs, the nine units at once: capi.hip,
+    # one hipcc per translation unit (every csrc/*.hip), side by side, then one link (8 CPUs, the ten units at once: capi.hip,
     # the longest, is done 84-89 s after the start, clutter.hip after 72-82 s, array.hip after 32-43 s, the others --
-    # integrate.hip with its sixteen windows and taper.hip with its five stencils among them -- within 12 s)
+    # integrate.hip with its sixteen windows, taper.hip with its five stencils and migrate.hip among them -- within 12 s)
     procs = []
     try:
         for src in srcs:

@@ -101,10 +101,11 @@ struct blah2hip_amb_s {
   bool lastHot = false;             // the last process call launched hot_columns_kernel
   hipStream_t lastHotStream = nullptr; // ... on this stream (BLAH2HIP_INFO_HOT_COLUMNS waits for that one only)
   uint32_t lastHotCpis = 0;         // ... over this many CPIs
+  uint32_t lastMaps = 0;            // maps (virtual CPIs) of the last process call: what d_R holds (0 = no call yet; migrate.hip)
   int lastLeakLags = 0;             // BLAH2HIP_INFO_LEAK_LAGS: lags corrected by the last process call (0 = not applied)
   double lastLeakMax = 0.0;         // BLAH2HIP_INFO_LEAK_MAX_E12: the largest |g| of the calibration the last call ran under
 
-  // ---- written by detect.hip; bearingGridLast by array.hip, taperGridLast by taper.hip
+  // ---- written by detect.hip; bearingGridLast by array.hip, taperGridLast by taper.hip, the migration fields by migrate.hip
   struct AlphaTable { double pfa; uint32_t looks; size_t n; double *d; bool pinned; }; // pinned: handed out by *_prepare, never evicted
   std::vector<AlphaTable> alphaTables; // CFAR threshold factors, one per (pfa, looks, size) seen
   struct OsTable { double pfa; uint32_t looks, rank; size_t n; double *d; bool pinned; }; // d: alpha[n + 1], then rank[n + 1] words
@@ -116,6 +117,9 @@ struct blah2hip_amb_s {
   int detGridLast = 0, detTiledLast = 0; // BLAH2HIP_INFO_DETECT_GRID / _TILED
   int bearingGridLast = 0;          // BLAH2HIP_INFO_BEARING_GRID
   int taperGridLast = 0;            // BLAH2HIP_INFO_TAPER_GRID
+  double *d_migrate = nullptr;      // [nD] half walks (blah2hip_amb_set_migration), allocated at its first use, freed by destroy
+  bool migrateSet = false;          // ... and whether a table is set
+  int migrateGridLast = 0;          // BLAH2HIP_INFO_MIGRATE_GRID
 
   // ---- every unit brackets its launches (tic / toc below)
   blah2::KernelTimer<BLAH2HIP_K_COUNT> timer;

@@ -615,6 +615,66 @@ def taper_gains(taps):
     return coherent, noise, enbw, 10.0 * math.log10(enbw)
 
 
+def migration_table(dims, fc):
+    """``blah2hip_migration_table`` restated: the physical half walks ``h[j] = -0.5 * doppler[j] * n_corr / fc`` (fp64, samples
+    per pulse divided by 2) of a geometry.  ``dims``: anything with ``doppler`` and ``n_corr`` (the oracle's
+    ``ambiguity_dims``), or an :class:`Ambiguity`.  Positive Doppler is an approaching target: its delay decreases."""
+    fc = float(fc)
+    if not math.isfinite(fc) or not fc > 0.0:
+        raise ValueError("the carrier frequency must be finite and positive")
+    doppler = np.asarray(dims.doppler, dtype=np.float64)
+    n_corr = dims.dims.n_corr if isinstance(dims, Ambiguity) else dims.n_corr
+    return -0.5 * doppler * float(n_corr) / fc
+
+
+def migration_shifts(half_walk, nD):
+    """The shifts ``s[j, i] = rint(h[j] * (2 i - (nD - 1)))`` as int64 ``[len(h), nD]``: one fp64 multiply, ties to even --
+    the bits the library works out on the device."""
+    h = np.asarray(half_walk, dtype=np.float64).reshape(-1, 1)
+    t = (2 * np.arange(int(nD), dtype=np.int64) - (int(nD) - 1)).astype(np.float64).reshape(1, -1)
+    return np.rint(h * t).astype(np.int64)
+
+
+def range_map(dims, x, y):
+    """The range half of ``Ambiguity::process`` (Ambiguity.cpp:92-146) in fp64: ``R[i][d]``, pulse ``i``, delay column ``d``,
+    complex128 ``[n_doppler_bins, n_delay_bins]`` -- what the Doppler transform of the map reads.  ``dims``: the oracle's
+    ``ambiguity_dims``."""
+    x = np.asarray(x, dtype=np.complex128)
+    y = np.asarray(y, dtype=np.complex128)
+    nD, nC, nfft = int(dims.n_doppler_bins), int(dims.n_corr), int(dims.nfft)
+    if dims.doppler_middle != 0:  # :95-102: the reference channel is rotated to the middle of the Doppler limits
+        i = np.arange(x.shape[0], dtype=np.float64)
+        x = x * np.exp(1j * 2.0 * np.pi * dims.doppler_middle * (i / dims.fs))
+    used = nD * nC
+    X = np.fft.fft(x[:used].reshape(nD, nC), n=nfft, axis=1)
+    Y = np.fft.fft(y[:used].reshape(nD, nC), n=nfft, axis=1)
+    Z = np.fft.ifft(Y * np.conj(X), axis=1)
+    lag = (int(dims.delay_min) + np.arange(int(dims.n_delay_bins))) % nfft  # :132-146
+    return Z[:, lag]
+
+
+def migrate_maps(R, half_walk):
+    """blah2hip_amb_migrate_dev restated in fp64 NumPy for EVERY row (the library copies the zero-shift rows from its input
+    map instead): ``M'[j][d] = sum_i [0 <= d + s(j,i) < nDelay] R[i][d + s(j,i)] W[(i src(j)) mod nD]`` with
+    ``src(j) = (j + nD // 2 + 1) % nD`` and the shifts of :func:`migration_shifts`.  ``R``: complex ``[..., nD, nDelay]``."""
+    R = np.asarray(R).astype(np.complex128)
+    nD, nDelay = R.shape[-2:]
+    h = np.asarray(half_walk, dtype=np.float64)
+    if h.shape != (nD,):
+        raise ValueError("half_walk must hold one entry per Doppler row")
+    s = migration_shifts(h, nD)
+    i = np.arange(nD)
+    d = np.arange(nDelay)
+    out = np.zeros(R.shape, dtype=np.complex128)
+    for j in range(nD):
+        w = np.exp(-2j * np.pi * ((i * ((j + nD // 2 + 1) % nD)) % nD) / nD)
+        c = d[None, :] + s[j][:, None]  # [pulse, column]
+        ok = (c >= 0) & (c < nDelay)
+        g = np.take_along_axis(R, np.broadcast_to(np.clip(c, 0, nDelay - 1), R.shape), axis=-1)
+        out[..., j, :] = np.sum(np.where(ok, g, 0.0) * w[:, None], axis=-2)
+    return out
+
+
 class Map:
     """src/data/Map.h: rows = Doppler, cols = delay.  ``data`` is complex64."""
 
@@ -1051,6 +1111,30 @@ class Ambiguity:
         if t.ndim != 1 or t.size < 1:
             raise ValueError("taps must be t_0 .. t_P")
         check(self._L.blah2hip_amb_taper_dev(self._h, d_map, n_maps, _ptr(t), t.size - 1, d_out_map, d_out_metrics, stream))
+
+    def set_migration(self, half_walk):
+        """The table of fp64 half walks (``[n_doppler_bins]``: :func:`migration_table`, or any finite table) that
+        :meth:`migrate_dev` sums along (blah2hip_amb_set_migration); None clears it."""
+        if half_walk is None:
+            check(self._L.blah2hip_amb_set_migration(self._h, None))
+            return
+        t = np.ascontiguousarray(half_walk, dtype=np.float64)
+        if t.shape != (self.dims.n_doppler_bins,):
+            raise ValueError("half_walk must hold one entry per Doppler row")
+        check(self._L.blah2hip_amb_set_migration(self._h, _ptr(t)))
+
+    def migration_table(self, fc):
+        """blah2hip_migration_table: the library's own physical table for the carrier ``fc`` (Hz)."""
+        t = np.zeros(self.dims.n_doppler_bins, dtype=np.float64)
+        check(self._L.blah2hip_migration_table(self._h, float(fc), _ptr(t)))
+        return t
+
+    def migrate_dev(self, d_map, n_maps, d_out_map, d_out_metrics, stream=0):
+        """Range-migration compensation of the first ``n_maps`` maps of the last ``process_dev`` / ``process_multi_dev`` call
+        (blah2hip_amb_migrate_dev; raw pointers/ints): ``d_map`` is that call's map buffer (None: the handle's own),
+        ``d_out_map`` the same pointer or a disjoint ``[n_maps][nD][nDelay]`` complex64 buffer, ``d_out_metrics``
+        ``[n_maps][2]`` float64.  Enqueues only."""
+        check(self._L.blah2hip_amb_migrate_dev(self._h, d_map, n_maps, d_out_map, d_out_metrics, stream))
 
     def set_taper_seg_rows(self, n):
         """Doppler rows per segment of the taper kernel (0 = the launch's own choice); ``info(INFO_TAPER_GRID)`` reports the

@@ -57,6 +57,7 @@ from __future__ import annotations
 
 import ctypes as C
 import json
+import math
 import os
 import time
 import pickle
@@ -609,7 +610,14 @@ class GpuChain:
     blackmanharris, nuttall, flattop; ``NAME:norm`` divides the taps by a_0): one stencil kernel directly behind the
     ambiguity stage on the compute stream (``Ambiguity.taper_dev``), and everything after it -- the integrator, the
     detector, the finisher, the downloaded maps and metrics -- reads the tapered buffers.  The stage holds no state.
-    Without the key, or with ``none``, nothing is allocated or launched."""
+    Without the key, or with ``none``, nothing is allocated or launched.
+
+    ``cfg["ambiguity"]["migration"] = {"fc": HZ}`` compensates range migration for the carrier ``fc``
+    (``Ambiguity.migration_table`` / ``migrate_dev``): one kernel directly behind the ambiguity stage on the compute stream,
+    in front of the taper, rewrites the batch's maps and metrics in place from the range map that the ambiguity stage left on
+    the handle (every configuration of this chain runs ``process_dev``, so there always is one); everything after it reads
+    the result.  ValueError: no ``fc``, an ``fc`` that is not positive and finite, or a geometry whose outermost Doppler row
+    walks more than BLAH2HIP_MAX_MIGRATION cells.  Without the key nothing is allocated or launched."""
 
     def __init__(self, cfg: dict, device: int = 0, batch: int = 1, want_map: bool = False, depth: int = 3,
                  reader_threads: int = 4, hit_copy: int = 4096, read_mode: str = "memmove", numa: bool = True,
@@ -679,9 +687,27 @@ class GpuChain:
             raise ValueError(f"ambiguity.window {win!r}: NAME or NAME:norm")
         if name != "none" or norm:
             self.taper = blah2_amd.doppler_taper_f32(name, norm == "norm")  # (refuses an unknown name)
+        # ambiguity: {migration: {fc: HZ}}: range-migration compensation for that carrier (False: no such stage)
+        self.migrate = False
+        mig = amb_c.get("migration")
+        mig = None if mig is False else mig
+        if mig is not None:
+            fc = mig.get("fc") if isinstance(mig, dict) else None
+            if fc is None:
+                raise ValueError("ambiguity.migration needs the carrier frequency: {fc: HZ}")
+            fc = float(fc)
+            if not math.isfinite(fc) or not fc > 0.0:
+                raise ValueError(f"ambiguity.migration: fc = {fc!r} is not a positive, finite frequency")
         self.amb = blah2_amd.Ambiguity(amb_c["delayMin"], amb_c["delayMax"], amb_c["dopplerMin"], amb_c["dopplerMax"],
                                        self.fs, n, True, device=device, max_batch=B)
         nD, nC = self.amb.get_n_doppler_bins(), self.amb.get_n_delay_bins()
+        if mig is not None:
+            try:
+                self.amb.set_migration(self.amb.migration_table(fc))
+            except blah2_amd.Blah2HipError as e:
+                self.amb.close()
+                raise ValueError(f"ambiguity.migration at fc = {fc:g} Hz: {e}") from None
+            self.migrate = True
         self.wh = None
         self.fused_fir = False
         # clutter: {blocks: K}: taps per block of n / K samples (the filter's history runs on across the blocks); a CPI
@@ -907,6 +933,8 @@ class GpuChain:
                 amb.process_dev(fmt_yf, x, self.yf.data_ptr(), cnt, n, slot["d_map"].data_ptr(),
                                 slot["d_met"].data_ptr(), st)
             n_maps, maps, mets = cnt, slot["d_map"], slot["d_met"]  # what the detector and the download read
+            if self.migrate:  # in place, from the range map the call above left on the handle
+                amb.migrate_dev(maps.data_ptr(), cnt, maps.data_ptr(), mets.data_ptr(), st)
             if self.taper is not None:
                 amb.taper_dev(maps.data_ptr(), cnt, self.taper, slot["d_tmap"].data_ptr(), slot["d_tmet"].data_ptr(), st)
                 maps, mets = slot["d_tmap"], slot["d_tmet"]
@@ -1179,6 +1207,10 @@ def main(argv=None):
                     help="Doppler taper behind the ambiguity stage: none, hann, hamming, blackman, blackmanharris, nuttall or "
                          "flattop; :norm divides the taps by a_0 (an echo on a Doppler bin keeps its amplitude); overrides "
                          "process.ambiguity.window of the config")
+    ap.add_argument("--migration", nargs="?", const=True, default=None, metavar="FC_HZ",
+                    help="range-migration compensation behind the ambiguity stage (in front of the taper) for the carrier "
+                         "FC_HZ; without a value the config's capture.fc.  process.ambiguity.migration: true in the config "
+                         "does the same")
     ap.add_argument("--cfar", default=None, metavar="KIND[:RANK]",
                     help="the detector: ca (cell averaging, the reference's) or os[:RANK] (ordered statistic: the threshold "
                          "from the RANK-th part of the sorted training cells, default 0.75); overrides "
@@ -1221,6 +1253,23 @@ def main(argv=None):
         if name_ not in TAPER_COEFFS or norm_ not in ("", "norm"):
             ap.error(f"--doppler-window takes NAME or NAME:norm, NAME one of {', '.join(TAPER_COEFFS)}")
         cfg["ambiguity"] = dict(cfg["ambiguity"], window=a.doppler_window.lower())
+    # process.ambiguity.migration: true, or --migration [FC_HZ]: the chain's {"fc": HZ}, the carrier from capture.fc by default
+    mig_ = a.migration if a.migration is not None else cfg["ambiguity"].get("migration")
+    if mig_:
+        fc_ = mig_.get("fc") if isinstance(mig_, dict) else None if mig_ is True else mig_
+        if fc_ is None:
+            fc_ = y["capture"].get("fc")
+        try:
+            fc_ = float(fc_) if fc_ is not None else None
+        except (TypeError, ValueError):
+            ap.error("--migration takes a carrier frequency in Hz")
+        if fc_ is None:
+            ap.error("range-migration compensation needs a carrier: --migration FC_HZ, or capture.fc in the config")
+        if not math.isfinite(fc_) or not fc_ > 0.0:
+            ap.error("the carrier frequency of --migration / capture.fc must be positive and finite")
+        cfg["ambiguity"] = dict(cfg["ambiguity"], migration={"fc": fc_})
+    elif "migration" in cfg["ambiguity"]:
+        cfg["ambiguity"] = {k: v for k, v in cfg["ambiguity"].items() if k != "migration"}
     if a.cfar is not None:
         kind, _, rank_ = a.cfar.partition(":")
         try:

@@ -258,6 +258,7 @@ int blah2hip_amb_set_option(blah2hip_amb_t h, int option, int64_t value);
                                               * hits), 0: one workgroup per CPI */
 #define BLAH2HIP_INFO_BEARING_GRID 16         /* workgroups per list of the last blah2hip_amb_bearing_dev launch */
 #define BLAH2HIP_INFO_TAPER_GRID 17            /* workgroups per map of the last blah2hip_amb_taper_dev launch */
+#define BLAH2HIP_INFO_MIGRATE_GRID 18          /* workgroups per map of the last blah2hip_amb_migrate_dev launch */
 int blah2hip_amb_get_info(blah2hip_amb_t h, int key, int64_t *value);
 
 /* Ambiguity::process + Map::set_metrics on host buffers (blah2.cpp:278-279).
@@ -589,6 +590,45 @@ int blah2hip_doppler_taper(int kind, int normalise, float *taps, uint32_t *n_sid
  * aligned, an output that overlaps the input maps (the stencil cannot run in place). */
 int blah2hip_amb_taper_dev(blah2hip_amb_t h, const void *d_map, uint32_t n_maps, const float *taps, uint32_t n_side,
                            void *d_out_map, double *d_out_metrics, void *stream);
+
+/* ---- Range-migration compensation (no reference counterpart: Ambiguity.cpp:152-169 sums the pulses of one delay column) ----
+ * A target's bistatic delay drifts over a CPI by -f n_used / fc samples (f Doppler, fc carrier), so a fast echo leaves its
+ * delay column part-way through the Doppler sum and smears over the cells it walks through.  The compensation is a second
+ * Doppler sum over the range map of the last process call, which stays on the handle, taken along the walk.  With
+ *   R[i][d]   the range map of one (virtual) CPI: pulse i, delay column d = 0 .. n_delay - 1,
+ *   src(j)  = (j + n_doppler/2 + 1) % n_doppler   (the map's row order),   W[m] = exp(-2 pi i m / n_doppler),
+ *   h[j]      a table of fp64 HALF WALKS: samples per pulse, divided by 2,
+ *   t(i)    = 2 i - (n_doppler - 1)                                   (an integer, for odd and even n_doppler alike)
+ *   s(j,i)  = (int) rint( h[j] * (double) t(i) )                      (one fp64 multiply, ties to even)
+ *   M'[j][d] = sum_i [0 <= d + s(j,i) < n_delay]  R[i][d + s(j,i)] W[(i src(j)) mod n_doppler]
+ * A term whose column falls outside the map contributes zero: no wrap, no clamp.  The shift is to the nearest cell (no
+ * interpolation).  A ZERO-SHIFT row -- rint(h[j] (n_doppler - 1)) == 0, so every s(j,i) is 0 -- is copied bit for bit from
+ * the input map: the rows around zero Doppler keep what the hot-column and leak machinery wrote.  Every other row is
+ * overwritten by the sum, in doppler_dft_kernel's arithmetic without its first-pulse subtraction: fp32 complex
+ * multiply-adds, blocks of 32 pulses summed into a running sum, in one fixed order, so equal inputs give equal bits at every
+ * placement and every n_maps. */
+#define BLAH2HIP_MAX_MIGRATION 512 /* the largest |rint(h[j] (n_doppler - 1))| a table may hold: cells walked from the middle of the CPI to its end */
+/* Host only: the physical table of the handle's own Doppler axis, half_walk[j] = -0.5 * doppler[j] * n_corr / fc for
+ * j = 0 .. n_doppler - 1.  Positive Doppler is an approaching target, whose delay decreases; the echo lands at its mid-CPI
+ * delay.  BLAH2HIP_ERR_INVALID: a NULL argument, fc not finite or not positive. */
+int blah2hip_migration_table(blah2hip_amb_t h, double fc, double *half_walk);
+/* Copies a HOST table of n_doppler half walks into a device buffer the handle owns (allocated at the first call; the call
+ * waits for the device, like blah2hip_amb_set_fir's tables).  Any finite table is allowed, not only the physical one.  NULL
+ * clears the table.  BLAH2HIP_ERR_INVALID, with the table that was set left as it was: an entry that is not finite, or
+ * max_j |rint(h[j] (n_doppler - 1))| above BLAH2HIP_MAX_MIGRATION. */
+int blah2hip_amb_set_migration(blah2hip_amb_t h, const double *half_walk);
+/* M' for maps 0 .. n_maps - 1 of the handle's range map AS THE LAST blah2hip_amb_process_dev / _process_multi_dev CALL LEFT
+ * IT (virtual CPIs k * n_cpi + c).  d_map: that call's map buffer (NULL = the handle's own), read in zero-shift rows only.
+ * d_out_map [n_maps][n_doppler][n_delay] may be the same pointer (in place) or a disjoint buffer; d_out_metrics [n_maps][2]
+ * is Map::set_metrics of every output map on the cells as written.  Enqueues only -- migrate_kernel (BLAH2HIP_K_DOPPLER)
+ * and metrics_kernel (BLAH2HIP_K_METRICS), which finishes the metrics in index order (no floating-point atomics) -- with
+ * no upload, allocation or synchronisation, and can be captured in a graph.  The grid depends on the geometry alone, never
+ * on n_maps.  The per-workgroup partials live in the handle's buffers, so calls on one handle must be ordered on the device.
+ * BLAH2HIP_ERR_INVALID, with nothing enqueued: a NULL handle, no table set, no process call yet, n_maps 0 or above the
+ * maps of the last process call, NULL outputs, a map that is not 8-byte aligned, output maps that overlap the input maps
+ * without being the same pointer, a metrics buffer inside a map. */
+int blah2hip_amb_migrate_dev(blah2hip_amb_t h, const void *d_map, uint32_t n_maps, void *d_out_map, double *d_out_metrics,
+                             void *stream);
 
 /* ---- CfarDetector1D (CfarDetector1D.h:46-55) ---------------------------- */
 /* dev: d_map/d_metrics as written by blah2hip_amb_process_dev (NULL = the
@@ -997,7 +1037,7 @@ int blah2hip_amb_result_ptrs(blah2hip_amb_t h, const void **d_map, const double 
 /* ---- per-kernel timing (HIP events on the launch stream) ---------------- */
 #define BLAH2HIP_K_RANGE 0
 #define BLAH2HIP_K_DOPPLER 1
-#define BLAH2HIP_K_METRICS 2   /* metrics_kernel: behind the Doppler kernels, the beam former, the integrator and the Doppler taper */
+#define BLAH2HIP_K_METRICS 2   /* metrics_kernel: behind the Doppler kernels, the beam former, the integrator, the Doppler taper and migrate_kernel */
 #define BLAH2HIP_K_CFAR 3     /* cfar1d_kernel, cfar2d_tile_kernel or cfar2d_kernel */
 #define BLAH2HIP_K_SAT_ROWS 4 /* 2-D CFAR through the summed-area table (large windows): row prefix sums */
 #define BLAH2HIP_K_SAT_COLS 5 /* ... column prefix sums */
