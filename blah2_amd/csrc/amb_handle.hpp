@@ -1,6 +1,7 @@
 // Internal to the library: what the units behind include/blah2hip.h share.  The ambiguity handle, whose fields every
 // unit reads directly (no accessors), the error and launch-check helpers, and the few engine functions (capi.hip)
-// that another unit calls.  Host code only: capi.hip, array.hip, detect.hip, integrate.hip, taper.hip and context.hip all include it.
+// that another unit calls.  Host code only: capi.hip, array.hip, detect.hip, integrate.hip, taper.hip, migrate.hip and
+// context.hip all include it.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -106,10 +107,11 @@ struct blah2hip_amb_s {
   double lastLeakMax = 0.0;         // BLAH2HIP_INFO_LEAK_MAX_E12: the largest |g| of the calibration the last call ran under
 
   // ---- written by detect.hip; bearingGridLast by array.hip, taperGridLast by taper.hip, the migration fields by migrate.hip
-  struct AlphaTable { double pfa; uint32_t looks; size_t n; double *d; bool pinned; }; // pinned: handed out by *_prepare, never evicted
-  std::vector<AlphaTable> alphaTables; // CFAR threshold factors, one per (pfa, looks, size) seen
-  struct OsTable { double pfa; uint32_t looks, rank; size_t n; double *d; bool pinned; }; // d: alpha[n + 1], then rank[n + 1] words
-  std::vector<OsTable> osTables;    // ordered-statistic factors and ranks, one per (pfa, looks, rank_permille, size) seen
+  // a threshold table of detect.hip's cfar_table(); d: alpha[n + 1], then with a rank (permille) rank[n + 1] words; pinned:
+  // handed out by *_prepare, never evicted.  Two lists, each with its own budget; destroy (capi.hip) frees both.
+  struct CfarTable { double pfa; uint32_t looks, rank; size_t n; double *d; bool pinned; };
+  std::vector<CfarTable> alphaTables; // cell averaging (rank 0): one per (pfa, looks, size) seen
+  std::vector<CfarTable> osTables;    // ordered statistic: one per (pfa, looks, rank_permille, size) seen
   double *d_sat = nullptr;          // 2-D CFAR summed-area table [max_batch][nD+1][nDelay+1], allocated at its first use
   blah2hip_hit_t *d_hits = nullptr; // the *_process calls' hit list, grown to the map's cell count
   uint32_t hitCap = 0;
@@ -161,6 +163,13 @@ static inline int toc(blah2hip_amb_s *h, int k, hipStream_t st)
 {
   HIPCHK(h->timer.toc(k, st));
   return BLAH2HIP_OK;
+}
+
+// whether the byte ranges [a, a + na) and [b, b + nb) share a byte: what the calls with caller-owned outputs refuse
+static inline bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
+{
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a0 < b0 + nb && b0 < a0 + na;
 }
 
 // Workgroups per CPI of a launch that strides over `units` accesses a CPI: eight a CU over the launch of n_cpi CPIs, each

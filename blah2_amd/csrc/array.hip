@@ -10,12 +10,6 @@ using namespace blah2;
 
 namespace {
 
-bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-  return a0 < b0 + nb && b0 < a0 + na;
-}
-
 // The counts the array calls share, in the order each of them checks them: channels, beams (NO_BEAMS: the call has none),
 // CPIs and, with `batch`, the channel maps against the handle's max_batch
 constexpr uint32_t NO_BEAMS = ~0u;

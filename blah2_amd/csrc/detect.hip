@@ -6,269 +6,57 @@
 #include "detect_kernels.hpp"
 #include "oscfar_kernels.hpp"
 
-#include <cmath>
-#include <thread>
+#include "cfar_alpha.hpp"
 
 using namespace blah2;
 
 namespace {
 
-// CFAR threshold factors alpha[n] = n*(pfa^(-1/n) - 1), n = 1..maxN, evaluated with the
-// same libm pow the reference calls (CfarDetector1D.cpp:76).  A small per-handle cache keyed by
-// (pfa, maxN), least recently used first out (a caller that adapts pfa per CPI does not grow device
-// memory): a hit only hands out the pointer; a miss allocates and uploads (blocking), which is
-// refused while `st` is being captured into a graph -- *_prepare is the call for that.  A table *_prepare has handed out
-// lives as long as the handle (`pin`): a graph captured afterwards has its address baked in, and no synchronisation
-// at eviction time protects a later replay.  Only unpinned tables are evicted.
-// The looks per cell are the handle's BLAH2HIP_OPT_CFAR_LOOKS at the time of the call and part of the key; one look is the
-// expression above, more go through blah2hip_cfar_alpha's bisection (below).
-constexpr size_t ALPHA_TABLES_MAX = 8;
+// The detectors' threshold tables on the device, one cache for both kinds.  Cell averaging (permille 0, h->alphaTables,
+// `rank` unused): blah2hip_cfar_alpha's alpha[0 .. maxN], keyed by (pfa, looks, size); a larger table serves a smaller
+// request.  Ordered statistic (h->osTables): blah2hip_oscfar_alpha's alpha[maxN + 1] doubles, then rank[maxN + 1] words, in
+// one allocation, keyed by (pfa, looks, rank, size); the size must match, because the rank words sit behind alpha[maxN].
+// The looks are the handle's BLAH2HIP_OPT_CFAR_LOOKS at the time of the call.  Each list keeps its least recently used
+// entry first and holds eight unpinned ones (a caller that adapts pfa per CPI does not grow device memory); a call never
+// touches the other list.  A hit only hands out the pointers; a miss allocates and uploads (blocking), which is refused
+// while `st` is being captured into a graph -- *_prepare is the call for that.  A table *_prepare has handed out lives as
+// long as the handle (`pin`): a graph captured afterwards has its address baked in, and no synchronisation at eviction
+// time protects a later replay.  Only unpinned tables are evicted.
+constexpr size_t CFAR_TABLES_MAX = 8;
 
-// Pfa(t) of a cell that is the sum of L looks against the mean of n training cells of L looks each, threshold factor
-// alpha = n t, m = n L: sum_{k < L} C(m + k - 1, k) t^k / (1 + t)^(m + k), term by term in the log domain (the first term
-// alone underflows for large m, and lgamma's absolute error at m ~ 1e5 would show in the result)
-double pfa_of_looks(double t, double m, uint32_t L)
+int cfar_table(blah2hip_amb_s *h, double pfa, uint32_t permille, size_t maxN, const double **alpha, const uint32_t **rank,
+               hipStream_t st = nullptr, bool pin = false)
 {
-  const double lt = std::log(t), l1 = std::log1p(t);
-  double lg = -m * l1, s = std::exp(lg);
-  for (uint32_t k = 1; k < L; k++) {
-    lg += std::log((m + (double)k - 1.0) / (double)k) + lt - l1;
-    s += std::exp(lg);
-  }
-  return s;
-}
-
-// alpha[n] for L > 1 looks: Pfa(t) = pfa by bisection in fp64 until the interval no longer splits; the upper end is returned
-double alpha_of_looks(double pfa, uint32_t n, uint32_t L)
-{
-  const double m = (double)n * (double)L;
-  double lo = 0.0, hi = 1.0;
-  while (pfa_of_looks(hi, m, L) > pfa) hi *= 2.0;
-  for (;;) {
-    const double mid = 0.5 * (lo + hi);
-    if (mid == lo || mid == hi) break;
-    if (pfa_of_looks(mid, m, L) > pfa) lo = mid;
-    else hi = mid;
-  }
-  return (double)n * hi;
-}
-
-int alpha_table(blah2hip_amb_s *h, double pfa, size_t maxN, const double **out, hipStream_t st = nullptr, bool pin = false)
-{
-  auto &T = h->alphaTables;
+  const bool os = permille != 0;
+  auto &T = os ? h->osTables : h->alphaTables;
   const uint32_t looks = h->cfarLooks;
   for (size_t i = 0; i < T.size(); i++)
-    if (T[i].pfa == pfa && T[i].looks == looks && T[i].n >= maxN) {
-      blah2hip_amb_s::AlphaTable t = T[i];
-      t.pinned = t.pinned || pin;
-      T.erase(T.begin() + (long)i);
-      T.push_back(t); // most recently used last
-      *out = t.d;
-      return BLAH2HIP_OK;
-    }
-  if (st) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-      return fail(BLAH2HIP_ERR_INVALID, "threshold table of this (pfa, window) is not resident: call blah2hip_cfar1d_prepare / "
-                                        "blah2hip_cfar2d_prepare before capturing the stream");
-  }
-  std::vector<double> alpha(maxN + 1);
-  int rc;
-  if ((rc = blah2hip_cfar_alpha(pfa, looks, (uint32_t)maxN, alpha.data()))) return rc;
-  size_t unpinned = 0;
-  for (const auto &e : T) unpinned += e.pinned ? 0 : 1;
-  if (unpinned >= ALPHA_TABLES_MAX) {
-    HIPCHK(hipDeviceSynchronize()); // the oldest unpinned table may still be read by enqueued work
-    for (size_t i = 0; i < T.size(); i++)
-      if (!T[i].pinned) {
-        (void)hipFree(T[i].d);
-        T.erase(T.begin() + (long)i);
-        break;
-      }
-  }
-  blah2hip_amb_s::AlphaTable t{pfa, looks, maxN, nullptr, pin};
-  HIPCHK(hipMalloc(&t.d, (maxN + 1) * sizeof(double)));
-  hipError_t e = hipMemcpy(t.d, alpha.data(), (maxN + 1) * sizeof(double), hipMemcpyHostToDevice);
-  if (e != hipSuccess) { (void)hipFree(t.d); return fail(BLAH2HIP_ERR_HIP, std::string("alpha table upload: ") + hipGetErrorString(e)); }
-  T.push_back(t);
-  *out = t.d;
-  return BLAH2HIP_OK;
-}
-
-// ---- ordered-statistic factors (blah2hip_oscfar_alpha; the formulas are in include/blah2hip.h) ----
-uint32_t os_rank(uint64_t n, uint32_t permille)
-{
-  return (uint32_t)std::max<uint64_t>(1, (n * permille + 999) / 1000);
-}
-
-// one look: log Pfa(alpha; n, k) = -sum_{i<k} log1p(alpha / (n - i))
-double os_logpfa1(double alpha, uint32_t n, uint32_t k)
-{
-  double s = 0.0;
-  for (uint32_t i = 0; i < k; i++) s -= std::log1p(alpha / (double)(n - i));
-  return s;
-}
-
-double os_alpha1(double pfa, uint32_t n, uint32_t k)
-{
-  const double lp = std::log(pfa);
-  double lo = 0.0, hi = 1.0;
-  while (os_logpfa1(hi, n, k) > lp) hi *= 2.0;
-  for (;;) {
-    const double mid = 0.5 * (lo + hi);
-    if (mid == lo || mid == hi) break;
-    if (os_logpfa1(mid, n, k) > lp) lo = mid;
-    else hi = mid;
-  }
-  return hi;
-}
-
-// Q_L(t) = e^-t sum_{j<L} t^j / j!, summed outwards from its largest term (no overflow for any t and L); lf[j] = log j!
-double os_q(double t, uint32_t L, const double *lf)
-{
-  if (!(t > 0.0)) return 1.0;
-  const uint32_t js = (uint32_t)std::min<double>((double)(L - 1), std::floor(t));
-  double s = 1.0, r = 1.0;
-  for (uint32_t j = js; j + 1 < L; j++) { r *= t / (double)(j + 1); s += r; }
-  r = 1.0;
-  for (uint32_t j = js; j > 0; j--) { r *= (double)j / t; s += r; }
-  return std::exp(-t + (double)js * std::log(t) - lf[js]) * s;
-}
-
-// P_L(x) = 1 - Q_L(x) from its own series e^-x x^L / L! (1 + x/(L+1) + x^2/((L+1)(L+2)) + ...), for x < L (no cancellation)
-double os_p_series(double x, uint32_t L, const double *lf)
-{
-  if (!(x > 0.0)) return 0.0;
-  double s = 1.0, r = 1.0;
-  for (uint32_t m = 1; m < 100000; m++) {
-    r *= x / (double)(L + m);
-    s += r;
-    if (r < 1e-17 * s) break;
-  }
-  return std::exp(-x + (double)L * std::log(x) - lf[L]) * s;
-}
-
-// log of the density of the k-th smallest of n Gamma(L) variables at x, without its constant n! / ((k-1)! (n-k)!)
-double os_logdens(double x, uint32_t n, uint32_t k, uint32_t L, const double *lf)
-{
-  double P, Q;
-  if (x < (double)L) { P = os_p_series(x, L, lf); Q = 1.0 - P; }
-  else { Q = os_q(x, L, lf); P = 1.0 - Q; }
-  double g = -x - lf[L - 1];
-  if (L > 1) g += (double)(L - 1) * std::log(x);
-  if (k > 1) g += (double)(k - 1) * std::log(P);
-  if (n > k) g += (double)(n - k) * std::log(Q);
-  return g;
-}
-
-constexpr int OS_COARSE = 4096, OS_FINE = 16384; // grid points of a scan for the integrand's support; Simpson intervals over it
-constexpr double OS_CUT = 60.0;                  // the support: within e^-60 of the largest value
-
-// Simpson nodes x and weights times density w for int f_(k)(x) Q_L(alpha x) dx at alpha >= alpha0: the interval on which
-// f_(k)(x) Q_L(alpha0 x) is within e^-60 of its largest value (Q_L(alpha x) falls as alpha rises, so the interval holds
-// the integrand of every larger alpha), found by two scans of OS_COARSE points, the second inside the first one's result
-struct OsNodes { std::vector<double> x, w; };
-
-void os_nodes(OsNodes &N, double alpha0, double logc, uint32_t n, uint32_t k, uint32_t L, const double *lf)
-{
-  auto G = [&](double x) {
-    double g = os_logdens(x, n, k, L, lf);
-    if (alpha0 > 0.0) g += std::log(os_q(alpha0 * x, L, lf));
-    return g;
-  };
-  double a = 0.0, b = (double)L + 40.0 * std::sqrt((double)L) + 100.0;
-  std::vector<double> g(OS_COARSE + 1);
-  for (int pass = 0; pass < 2; pass++) {
-    const double hc = (b - a) / OS_COARSE;
-    int imax = 0;
-    for (int i = 0; i <= OS_COARSE; i++) {
-      g[i] = G(a + hc * i);
-      if (g[i] > g[imax]) imax = i;
-    }
-    int ilo = imax, ihi = imax;
-    while (ilo > 0 && !(g[ilo] < g[imax] - OS_CUT)) ilo--;
-    while (ihi < OS_COARSE && !(g[ihi] < g[imax] - OS_CUT)) ihi++;
-    b = a + hc * ihi;
-    a = a + hc * ilo;
-  }
-  const double h = (b - a) / OS_FINE;
-  N.x.resize(OS_FINE + 1);
-  N.w.resize(OS_FINE + 1);
-  for (int i = 0; i <= OS_FINE; i++) {
-    N.x[i] = a + h * i;
-    const double simpson = (i == 0 || i == OS_FINE) ? 1.0 : ((i & 1) ? 4.0 : 2.0);
-    N.w[i] = simpson * (h / 3.0) * std::exp(logc + os_logdens(N.x[i], n, k, L, lf));
-  }
-}
-
-double os_pfa_nodes(const OsNodes &N, double alpha, uint32_t L, const double *lf)
-{
-  double s = 0.0;
-  for (int i = 0; i <= OS_FINE; i++) s += N.w[i] * os_q(alpha * N.x[i], L, lf);
-  return s;
-}
-
-// alpha[n] for L > 1 looks: Pfa(alpha) = int f_(k)(x) Q_L(alpha x) dx = pfa.  The bracket [hi / 2, hi] by doubling, each
-// trial on nodes of its own; then a bisection on the nodes of the bracket's lower end until the interval no longer
-// splits.  The upper end is returned.
-double os_alpha_looks(double pfa, uint32_t n, uint32_t k, uint32_t L, const double *lf)
-{
-  double logc = 0.0; // log( n! / ((k-1)! (n-k)!) ) = sum_{i<k} log(n - i) - log (k-1)!
-  for (uint32_t i = 0; i < k; i++) logc += std::log((double)(n - i));
-  for (uint32_t i = 2; i < k; i++) logc -= std::log((double)i);
-  OsNodes N;
-  double lo = 0.0, hi = 1.0;
-  for (;;) {
-    os_nodes(N, hi, logc, n, k, L, lf);
-    if (!(os_pfa_nodes(N, hi, L, lf) > pfa) || hi > 1e300) break;
-    lo = hi;
-    hi *= 2.0;
-  }
-  os_nodes(N, lo, logc, n, k, L, lf);
-  for (;;) {
-    const double mid = 0.5 * (lo + hi);
-    if (mid == lo || mid == hi) break;
-    if (os_pfa_nodes(N, mid, L, lf) > pfa) lo = mid;
-    else hi = mid;
-  }
-  return hi;
-}
-
-// The ordered-statistic detectors' tables: alpha[maxN + 1] doubles, then rank[maxN + 1] words, in one device allocation; a
-// cache of their own keyed by (pfa, looks, rank, size) with the rules of alpha_table above (eight unpinned entries, least
-// recently used first out, *_prepare pins), which it never touches.
-constexpr size_t OS_TABLES_MAX = 8;
-
-int os_table(blah2hip_amb_s *h, double pfa, uint32_t permille, size_t maxN, const double **alpha, const uint32_t **rank,
-             hipStream_t st = nullptr, bool pin = false)
-{
-  auto &T = h->osTables;
-  const uint32_t looks = h->cfarLooks;
-  for (size_t i = 0; i < T.size(); i++)
-    if (T[i].pfa == pfa && T[i].looks == looks && T[i].rank == permille && T[i].n == maxN) {
-      blah2hip_amb_s::OsTable t = T[i];
+    if (T[i].pfa == pfa && T[i].looks == looks && T[i].rank == permille && (os ? T[i].n == maxN : T[i].n >= maxN)) {
+      blah2hip_amb_s::CfarTable t = T[i];
       t.pinned = t.pinned || pin;
       T.erase(T.begin() + (long)i);
       T.push_back(t); // most recently used last
       *alpha = t.d;
-      *rank = reinterpret_cast<const uint32_t *>(t.d + (maxN + 1));
+      if (os) *rank = reinterpret_cast<const uint32_t *>(t.d + (maxN + 1));
       return BLAH2HIP_OK;
     }
   if (st) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-      return fail(BLAH2HIP_ERR_INVALID, "ordered-statistic table of this (pfa, rank, window) is not resident: call "
-                                        "blah2hip_oscfar1d_prepare / blah2hip_oscfar2d_prepare before capturing the stream");
+      return fail(BLAH2HIP_ERR_INVALID,
+                  os ? "ordered-statistic table of this (pfa, rank, window) is not resident: call "
+                       "blah2hip_oscfar1d_prepare / blah2hip_oscfar2d_prepare before capturing the stream"
+                     : "threshold table of this (pfa, window) is not resident: call blah2hip_cfar1d_prepare / "
+                       "blah2hip_cfar2d_prepare before capturing the stream");
   }
-  const size_t bytes = (maxN + 1) * (sizeof(double) + sizeof(uint32_t));
+  const size_t bytes = (maxN + 1) * (sizeof(double) + (os ? sizeof(uint32_t) : 0));
   std::vector<double> host((bytes + sizeof(double) - 1) / sizeof(double));
-  int rc;
-  if ((rc = blah2hip_oscfar_alpha(pfa, looks, permille, (uint32_t)maxN, host.data(),
-                                  reinterpret_cast<uint32_t *>(host.data() + (maxN + 1)))))
-    return rc;
+  int rc = os ? blah2hip_oscfar_alpha(pfa, looks, permille, (uint32_t)maxN, host.data(), reinterpret_cast<uint32_t *>(host.data() + (maxN + 1)))
+              : blah2hip_cfar_alpha(pfa, looks, (uint32_t)maxN, host.data());
+  if (rc) return rc;
   size_t unpinned = 0;
   for (const auto &e : T) unpinned += e.pinned ? 0 : 1;
-  if (unpinned >= OS_TABLES_MAX) {
+  if (unpinned >= CFAR_TABLES_MAX) {
     HIPCHK(hipDeviceSynchronize()); // the oldest unpinned table may still be read by enqueued work
     for (size_t i = 0; i < T.size(); i++)
       if (!T[i].pinned) {
@@ -277,14 +65,50 @@ int os_table(blah2hip_amb_s *h, double pfa, uint32_t permille, size_t maxN, cons
         break;
       }
   }
-  blah2hip_amb_s::OsTable t{pfa, looks, permille, maxN, nullptr, pin};
+  blah2hip_amb_s::CfarTable t{pfa, looks, permille, maxN, nullptr, pin};
   HIPCHK(hipMalloc(&t.d, host.size() * sizeof(double)));
   hipError_t e = hipMemcpy(t.d, host.data(), bytes, hipMemcpyHostToDevice);
-  if (e != hipSuccess) { (void)hipFree(t.d); return fail(BLAH2HIP_ERR_HIP, std::string("ordered-statistic table upload: ") + hipGetErrorString(e)); }
+  if (e != hipSuccess) {
+    (void)hipFree(t.d);
+    return fail(BLAH2HIP_ERR_HIP, std::string(os ? "ordered-statistic table upload: " : "alpha table upload: ") + hipGetErrorString(e));
+  }
   T.push_back(t);
   *alpha = t.d;
-  *rank = reinterpret_cast<const uint32_t *>(t.d + (maxN + 1));
+  if (os) *rank = reinterpret_cast<const uint32_t *>(t.d + (maxN + 1));
   return BLAH2HIP_OK;
+}
+
+// ---- the checks the entry points share, in the order each entry point makes them ----
+int check_dev(const blah2hip_amb_s *h, const blah2hip_hit_t *d_hits, const uint32_t *d_count, uint32_t n_cpi)
+{
+  if (!h || !d_hits || !d_count) return fail(BLAH2HIP_ERR_INVALID, "NULL argument");
+  if (n_cpi == 0 || n_cpi > h->dims.max_batch) return fail(BLAH2HIP_ERR_INVALID, "n_cpi outside [1, max_batch]");
+  return BLAH2HIP_OK;
+}
+
+// CfarDetector1D's ctor parameters are int8_t (CfarDetector1D.h:46)
+int check_1d(int32_t n_guard, int32_t n_train, int32_t min_delay)
+{
+  if (n_guard < 0 || n_guard > 127 || n_train < 0 || n_train > 127 || min_delay < -128 || min_delay > 127)
+    return fail(BLAH2HIP_ERR_INVALID, "nGuard/nTrain/minDelay outside int8 range");
+  return BLAH2HIP_OK;
+}
+
+// the four sizes of a 2-D window, and minDelay for the calls that have one: oscfar2d_dev looks at minDelay first
+int check_2d(int32_t ngd, int32_t ntd, int32_t ngf, int32_t ntf, int32_t min_delay = 0, bool delay_first = false)
+{
+  const bool delayBad = min_delay < -128 || min_delay > 127;
+  if (delay_first && delayBad) return fail(BLAH2HIP_ERR_INVALID, "minDelay outside int8 range");
+  for (int32_t v : {ngd, ntd, ngf, ntf})
+    if (v < 0 || v > 127) return fail(BLAH2HIP_ERR_INVALID, "guard/train sizes outside [0, 127]");
+  if (delayBad) return fail(BLAH2HIP_ERR_INVALID, "minDelay outside int8 range");
+  return BLAH2HIP_OK;
+}
+
+// training cells of a full 2-D window, plus the cell under test: the size of its table
+size_t window_cells(int32_t ngd, int32_t ntd, int32_t ngf, int32_t ntf)
+{
+  return (size_t)(2 * (ngd + ntd) + 1) * (2 * (ngf + ntf) + 1);
 }
 
 int os_check_rank(uint32_t permille)
@@ -370,6 +194,59 @@ int ensure_sat(blah2hip_amb_s *h)
   return BLAH2HIP_OK;
 }
 
+// Which kernel a cell-averaging 2-D window runs on under the handle's BLAH2HIP_OPT_CFAR2D_KERNEL: the stream kernel, else the
+// tile kernel, else the summed-area table, which is allocated here (a no-op once it is).  A forced kernel never runs another
+// one: what it cannot do is refused.  blah2hip_cfar2d_prepare asks with min_doppler 0, which skips no rows.
+int cfar2d_choose(blah2hip_amb_s *h, int ngd, int ntd, int ngf, int ntf, double min_doppler, bool *stream, bool *tile)
+{
+  *stream = cfar2d_use_stream(h, ngd, ntd, ngf, ntf, min_doppler);
+  *tile = cfar2d_use_tile(h, ngd, ntd, ngf, ntf);
+  if (h->cfar2dForce == BLAH2HIP_CFAR2D_TILE && !*tile)
+    return fail(BLAH2HIP_ERR_UNSUPPORTED, "2-D window beyond the tile kernel's halo (nGf + nTf <= 24, nGd + nTd <= 40)");
+  if (h->cfar2dForce == BLAH2HIP_CFAR2D_STREAM && !cfar2d_stream_shape(ngd, ntd, ngf, ntf))
+    return fail(BLAH2HIP_ERR_UNSUPPORTED, "the stream kernel is not instantiated for this 2-D window (C2S_SHAPES in cfar_kernels.hpp)");
+  // the handle's Doppler axis is monotonic (Ambiguity.cpp:60-66), so this cannot fail today
+  if (h->cfar2dForce == BLAH2HIP_CFAR2D_STREAM && !*stream)
+    return fail(BLAH2HIP_ERR_UNSUPPORTED, "the stream kernel needs the rows below minDoppler to be one interval of the Doppler axis");
+  return *stream || *tile ? BLAH2HIP_OK : ensure_sat(h);
+}
+
+// What CfarArgs and Cfar2dArgs have in common (d_map, d_metrics NULL: the handle's own), behind the zeroing of the counts
+template <class Args>
+int start_args(Args &a, const blah2hip_amb_s *h, const void *d_map, const double *d_metrics, uint32_t n_cpi, int32_t min_delay,
+               double min_doppler, blah2hip_hit_t *d_hits, uint32_t cap, uint32_t *d_count, hipStream_t st)
+{
+  HIPCHK(hipMemsetAsync(d_count, 0, n_cpi * sizeof(uint32_t), st));
+  a.map = d_map ? (const cf *)d_map : h->d_map;
+  a.metrics = d_metrics ? d_metrics : h->d_metrics;
+  a.doppler = h->d_doppler;
+  a.hits = d_hits;
+  a.count = d_count;
+  a.nD = (int32_t)h->dims.n_doppler_bins;
+  a.nDelay = (int32_t)h->dims.n_delay_bins;
+  a.delayMin = h->delayMin;
+  a.minDelay = min_delay;
+  a.minDoppler = min_doppler;
+  a.cap = cap;
+  return BLAH2HIP_OK;
+}
+
+// A 1-D detector's launch, one workgroup per Doppler row: the row as fp64 |z|^2 in LDS while it fits (150 KB: 19 200 delay
+// bins), straight from L2 beyond.  The attribute is set once per (device, kernel), to its largest use.
+template <class Args>
+int launch_rows(void (*staged)(Args), void (*unstaged)(Args), const Args &a, int nD, int nDelay, uint32_t n_cpi, hipStream_t st)
+{
+  const size_t rowBytes = (size_t)nDelay * sizeof(double);
+  if (rowBytes <= 150 * 1024) {
+    if (rowBytes > 48 * 1024) LDSCFG(staged, 150 * 1024);
+    hipLaunchKernelGGL(staged, dim3(nD, n_cpi), dim3(256), rowBytes, st, a);
+  } else {
+    hipLaunchKernelGGL(unstaged, dim3(nD, n_cpi), dim3(256), 0, st, a);
+  }
+  HIPCHK(hipGetLastError());
+  return BLAH2HIP_OK;
+}
+
 // the *_process calls' hit list on the device: worst case every cell fires; sized for that once
 int ensure_hits(blah2hip_amb_s *h, size_t cells)
 {
@@ -412,38 +289,70 @@ int hits_to_host(blah2hip_amb_s *h, double *delay, double *doppler, double *snr,
   return emit_hits(hits, h->delayAxis[0], h->dopplerAxis.data(), delay, doppler, snr, cap, count);
 }
 
+// A *_process call: enqueue(map, metrics) runs the detector's *_dev call on a one-CPI view of the handle's buffers, into
+// h->d_hits / h->d_count on the handle's stream
+template <class Enqueue>
+int process_one(blah2hip_amb_s *h, uint32_t cpi, double *delay, double *doppler, double *snr, uint32_t cap, uint32_t *count,
+                Enqueue enqueue)
+{
+  if (!h || !count) return fail(BLAH2HIP_ERR_INVALID, "NULL argument");
+  if (cpi >= h->dims.max_batch) return fail(BLAH2HIP_ERR_INVALID, "cpi index out of range");
+  HIPCHK(hipSetDevice(h->device));
+  const size_t cells = (size_t)h->dims.n_doppler_bins * h->dims.n_delay_bins;
+  int rc;
+  if ((rc = ensure_hits(h, cells))) return rc;
+  if ((rc = enqueue(h->d_map + cells * cpi, h->d_metrics + 2 * cpi))) return rc;
+  return hits_to_host(h, delay, doppler, snr, cap, count);
+}
+
+// blah2hip_cfar1d_dev and, with `os`, blah2hip_oscfar1d_dev: one call but for the rank, its table and the kernel
+int cfar1d_enqueue(bool os, blah2hip_amb_s *h, const void *d_map, const double *d_metrics, uint32_t n_cpi, double pfa,
+                   uint32_t permille, int32_t n_guard, int32_t n_train, int32_t min_delay, double min_doppler,
+                   blah2hip_hit_t *d_hits, uint32_t cap, uint32_t *d_count, void *stream)
+{
+  int rc;
+  if ((rc = check_dev(h, d_hits, d_count, n_cpi)) || (rc = check_1d(n_guard, n_train, min_delay))) return rc;
+  if (os && (rc = os_check_rank(permille))) return rc;
+  HIPCHK(hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  OsCfarArgs oa;
+  CfarArgs &a = oa.c;
+  oa.rank = nullptr; // cell averaging (permille 0) has no ranks: cfar_table leaves this alone and cfar1d_kernel takes oa.c only
+  if ((rc = cfar_table(h, pfa, permille, (size_t)(2 * n_train), &a.alpha, &oa.rank, st))) return rc;
+  if ((rc = start_args(a, h, d_map, d_metrics, n_cpi, min_delay, min_doppler, d_hits, cap, d_count, st))) return rc;
+  a.delayAxis = nullptr; // the engine's own axis: delayMin + j
+  a.nGuard = n_guard; a.nTrain = n_train;
+  if ((rc = tic(h, BLAH2HIP_K_CFAR, st))) return rc;
+  rc = os ? launch_rows(oscfar1d_kernel<true>, oscfar1d_kernel<false>, oa, a.nD, a.nDelay, n_cpi, st)
+          : launch_rows(cfar1d_kernel<true>, cfar1d_kernel<false>, a, a.nD, a.nDelay, n_cpi, st);
+  return rc ? rc : toc(h, BLAH2HIP_K_CFAR, st);
+}
+
+// ... and blah2hip_cfar1d_prepare / blah2hip_oscfar1d_prepare
+int cfar1d_pin(bool os, blah2hip_amb_s *h, double pfa, uint32_t permille, int32_t n_train)
+{
+  if (!h) return fail(BLAH2HIP_ERR_INVALID, "NULL handle");
+  if (n_train < 0 || n_train > 127) return fail(BLAH2HIP_ERR_INVALID, "nTrain outside int8 range");
+  int rc;
+  if (os && (rc = os_check_rank(permille))) return rc;
+  HIPCHK(hipSetDevice(h->device));
+  const double *d = nullptr;
+  const uint32_t *r = nullptr;
+  return cfar_table(h, pfa, permille, (size_t)(2 * n_train), &d, &r, nullptr, true);
+}
+
 } // namespace
 
 extern "C" {
 
 // ------------------------------------------------------------------- CFAR --
-// Host arithmetic only.  One look: the reference's expression with the same libm pow, whatever pfa is.  More looks: a
-// bisection per n of about 55 evaluations of `looks` terms each; long tables (a 2-D window at hundreds of looks) are cut
-// into interleaved slices for up to eight threads -- every entry is computed on its own, so the slices do not change it.
+// Host arithmetic only (cfar_alpha.hpp)
 int blah2hip_cfar_alpha(double pfa, uint32_t looks, uint32_t max_n, double *alpha)
 {
   if (!alpha) return fail(BLAH2HIP_ERR_INVALID, "NULL table");
   if (looks == 0 || looks > BLAH2HIP_MAX_CFAR_LOOKS) return fail(BLAH2HIP_ERR_INVALID, "looks outside [1, BLAH2HIP_MAX_CFAR_LOOKS]");
   if (looks > 1 && !(pfa > 0.0 && pfa < 1.0)) return fail(BLAH2HIP_ERR_INVALID, "pfa outside (0, 1) with more than one look");
-  alpha[0] = std::nan("");
-  if (looks == 1) {
-    for (size_t n = 1; n <= max_n; n++) alpha[n] = (double)n * (pow(pfa, -1.0 / (double)n) - 1);
-    return BLAH2HIP_OK;
-  }
-  const uint64_t terms = (uint64_t)max_n * looks;
-  const uint32_t nThreads = terms < 50000 ? 1u : std::min(8u, std::max(1u, std::thread::hardware_concurrency()));
-  auto slice = [=](uint32_t first) {
-    for (uint64_t n = 1 + first; n <= max_n; n += nThreads) alpha[n] = alpha_of_looks(pfa, (uint32_t)n, looks);
-  };
-  std::vector<std::thread> pool;
-  uint32_t started = 1;
-  try {
-    for (; started < nThreads; started++) pool.emplace_back(slice, started);
-  } catch (const std::exception &) { // no thread to be had: the slices that are left run here
-  }
-  slice(0);
-  for (uint32_t t = started; t < nThreads; t++) slice(t);
-  for (auto &t : pool) t.join();
+  cfar_alpha_fill(pfa, looks, max_n, alpha);
   return BLAH2HIP_OK;
 }
 
@@ -452,64 +361,17 @@ int blah2hip_cfar1d_dev(blah2hip_amb_t h, const void *d_map, const double *d_met
                         int32_t min_delay, double min_doppler, blah2hip_hit_t *d_hits, uint32_t cap,
                         uint32_t *d_count, void *stream)
 {
-  if (!h || !d_hits || !d_count) return fail(BLAH2HIP_ERR_INVALID, "NULL argument");
-  if (n_cpi == 0 || n_cpi > h->dims.max_batch) return fail(BLAH2HIP_ERR_INVALID, "n_cpi outside [1, max_batch]");
-  // CfarDetector1D's ctor parameters are int8_t (CfarDetector1D.h:46)
-  if (n_guard < 0 || n_guard > 127 || n_train < 0 || n_train > 127 || min_delay < -128 || min_delay > 127)
-    return fail(BLAH2HIP_ERR_INVALID, "nGuard/nTrain/minDelay outside int8 range");
-  HIPCHK(hipSetDevice(h->device));
-  hipStream_t st = (hipStream_t)stream;
-  const double *d_alpha = nullptr;
-  int rc;
-  if ((rc = alpha_table(h, pfa, (size_t)(2 * n_train), &d_alpha, st))) return rc;
-  HIPCHK(hipMemsetAsync(d_count, 0, n_cpi * sizeof(uint32_t), st));
-  CfarArgs a;
-  a.map = d_map ? (const cf *)d_map : h->d_map;
-  a.metrics = d_metrics ? d_metrics : h->d_metrics;
-  a.doppler = h->d_doppler;
-  a.alpha = d_alpha;
-  a.hits = d_hits;
-  a.count = d_count;
-  a.nD = (int32_t)h->dims.n_doppler_bins;
-  a.nDelay = (int32_t)h->dims.n_delay_bins;
-  a.delayMin = h->delayMin;
-  a.delayAxis = nullptr; // the engine's own axis: delayMin + j
-  a.nGuard = n_guard; a.nTrain = n_train; a.minDelay = min_delay;
-  a.minDoppler = min_doppler;
-  a.cap = cap;
-  if ((rc = tic(h, BLAH2HIP_K_CFAR, st))) return rc;
-  {
-    // the row as fp64 |z|^2 in LDS while it fits (150 KB: 19 200 delay bins), straight from L2 beyond
-    const size_t rowBytes = (size_t)a.nDelay * sizeof(double);
-    if (rowBytes <= 150 * 1024) {
-      if (rowBytes > 48 * 1024) LDSCFG(cfar1d_kernel<true>, 150 * 1024); // the attribute is set once per (device, kernel): its largest use
-      hipLaunchKernelGGL(cfar1d_kernel<true>, dim3(a.nD, n_cpi), dim3(256), rowBytes, st, a);
-    } else {
-      hipLaunchKernelGGL(cfar1d_kernel<false>, dim3(a.nD, n_cpi), dim3(256), 0, st, a);
-    }
-  }
-  HIPCHK(hipGetLastError());
-  if ((rc = toc(h, BLAH2HIP_K_CFAR, st))) return rc;
-  return BLAH2HIP_OK;
+  return cfar1d_enqueue(false, h, d_map, d_metrics, n_cpi, pfa, 0, n_guard, n_train, min_delay, min_doppler, d_hits, cap, d_count, stream);
 }
 
 int blah2hip_cfar1d_process(blah2hip_amb_t h, uint32_t cpi, double pfa, int32_t n_guard,
                             int32_t n_train, int32_t min_delay, double min_doppler, double *delay,
                             double *doppler, double *snr, uint32_t cap, uint32_t *count)
 {
-  if (!h || !count) return fail(BLAH2HIP_ERR_INVALID, "NULL argument");
-  if (cpi >= h->dims.max_batch) return fail(BLAH2HIP_ERR_INVALID, "cpi index out of range");
-  HIPCHK(hipSetDevice(h->device));
-  const size_t cells = (size_t)h->dims.n_doppler_bins * h->dims.n_delay_bins;
-  int rc;
-  if ((rc = ensure_hits(h, cells))) return rc;
-  // run on a one-CPI view of the internal buffers
-  const cf *m = h->d_map + cells * cpi;
-  const double *met = h->d_metrics + 2 * cpi;
-  rc = blah2hip_cfar1d_dev(h, m, met, 1, pfa, n_guard, n_train, min_delay, min_doppler, h->d_hits,
-                           h->hitCap, h->d_count, h->stream);
-  if (rc) return rc;
-  return hits_to_host(h, delay, doppler, snr, cap, count);
+  return process_one(h, cpi, delay, doppler, snr, cap, count, [&](const cf *m, const double *met) {
+    return blah2hip_cfar1d_dev(h, m, met, 1, pfa, n_guard, n_train, min_delay, min_doppler, h->d_hits, h->hitCap, h->d_count,
+                               h->stream);
+  });
 }
 
 // CfarDetector1D::process on a map that lives on the HOST (any Map<complex<double>>, not only one
@@ -521,8 +383,8 @@ int blah2hip_cfar1d_map(const float *map, uint32_t n_doppler, uint32_t n_delay, 
 {
   if (!map || !delay_axis || !doppler_axis || !count) return fail(BLAH2HIP_ERR_INVALID, "NULL argument");
   if (n_doppler == 0 || n_delay == 0) return fail(BLAH2HIP_ERR_INVALID, "empty map");
-  if (n_guard < 0 || n_guard > 127 || n_train < 0 || n_train > 127 || min_delay < -128 || min_delay > 127)
-    return fail(BLAH2HIP_ERR_INVALID, "nGuard/nTrain/minDelay outside int8 range");
+  int rc;
+  if ((rc = check_1d(n_guard, n_train, min_delay))) return rc;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
     return fail(BLAH2HIP_ERR_NO_DEVICE, "no HIP device visible (the HIP path is the only path)");
@@ -530,8 +392,7 @@ int blah2hip_cfar1d_map(const float *map, uint32_t n_doppler, uint32_t n_delay, 
   HIPCHK(hipSetDevice(device));
   const size_t cells = (size_t)n_doppler * n_delay;
   std::vector<double> alpha(2 * n_train + 1);
-  alpha[0] = std::nan("");
-  for (int n = 1; n <= 2 * n_train; n++) alpha[n] = n * (pow(pfa, -1.0 / n) - 1);
+  if ((rc = blah2hip_cfar_alpha(pfa, 1, (uint32_t)(2 * n_train), alpha.data()))) return rc; // one look: any pfa
   const double met[2] = {noise_power, 0.0};
   char *pool = nullptr; // one allocation: map | hits | doppler | alpha | metrics | delay axis | count
   const size_t oMap = 0, oHits = oMap + cells * sizeof(cf), oDop = oHits + cells * sizeof(blah2hip_hit_t),
@@ -558,20 +419,13 @@ int blah2hip_cfar1d_map(const float *map, uint32_t n_doppler, uint32_t n_delay, 
     a.delayAxis = (const int32_t *)(pool + oAxis); // x->delay[j] of a caller-built map need not be delay[0] + j (CfarDetector1D.cpp:53)
     a.nGuard = n_guard; a.nTrain = n_train; a.minDelay = min_delay; a.minDoppler = min_doppler;
     a.cap = (uint32_t)cells;
-    const size_t rowBytes = (size_t)a.nDelay * sizeof(double);
-    if (rowBytes <= 150 * 1024) {
-      if (rowBytes > 48 * 1024) HIPCHK(blah2hip_ensure_lds_((const void *)cfar1d_kernel<true>, 150 * 1024));
-      hipLaunchKernelGGL(cfar1d_kernel<true>, dim3(a.nD, 1), dim3(256), rowBytes, 0, a);
-    } else {
-      hipLaunchKernelGGL(cfar1d_kernel<false>, dim3(a.nD, 1), dim3(256), 0, 0, a);
-    }
-    HIPCHK(hipGetLastError());
+    if (int lrc = launch_rows(cfar1d_kernel<true>, cfar1d_kernel<false>, a, a.nD, a.nDelay, 1, nullptr)) return lrc;
     HIPCHK(hipMemcpy(&n, pool + oCnt, sizeof(uint32_t), hipMemcpyDeviceToHost)); // synchronises with the null stream
     hits.resize(n);
     if (n) HIPCHK(hipMemcpy(hits.data(), pool + oHits, n * sizeof(blah2hip_hit_t), hipMemcpyDeviceToHost));
     return BLAH2HIP_OK;
   };
-  const int rc = run();
+  rc = run();
   (void)hipFree(pool);
   if (rc) return rc;
   return emit_hits(hits, delay_axis[0], doppler_axis, delay, doppler, snr, cap, count);
@@ -583,48 +437,25 @@ int blah2hip_cfar2d_dev(blah2hip_amb_t h, const void *d_map, const double *d_met
                         double min_doppler, blah2hip_hit_t *d_hits, uint32_t cap, uint32_t *d_count,
                         void *stream)
 {
-  if (!h || !d_hits || !d_count) return fail(BLAH2HIP_ERR_INVALID, "NULL argument");
-  if (n_cpi == 0 || n_cpi > h->dims.max_batch) return fail(BLAH2HIP_ERR_INVALID, "n_cpi outside [1, max_batch]");
-  for (int32_t v : {ngd, ntd, ngf, ntf})
-    if (v < 0 || v > 127) return fail(BLAH2HIP_ERR_INVALID, "guard/train sizes outside [0, 127]");
-  if (min_delay < -128 || min_delay > 127) return fail(BLAH2HIP_ERR_INVALID, "minDelay outside int8 range");
+  int rc;
+  if ((rc = check_dev(h, d_hits, d_count, n_cpi)) || (rc = check_2d(ngd, ntd, ngf, ntf, min_delay))) return rc;
   HIPCHK(hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream;
-  const int nD = (int)h->dims.n_doppler_bins, nC = (int)h->dims.n_delay_bins;
-  int rc;
-  if (h->cfar2dForce == BLAH2HIP_CFAR2D_TILE && !cfar2d_use_tile(h, ngd, ntd, ngf, ntf))
-    return fail(BLAH2HIP_ERR_UNSUPPORTED, "2-D window beyond the tile kernel's halo (nGf + nTf <= 24, nGd + nTd <= 40)");
-  if (h->cfar2dForce == BLAH2HIP_CFAR2D_STREAM && !cfar2d_stream_shape(ngd, ntd, ngf, ntf))
-    return fail(BLAH2HIP_ERR_UNSUPPORTED, "the stream kernel is not instantiated for this 2-D window (C2S_SHAPES in cfar_kernels.hpp)");
-  {
-    int lo, hi; // the handle's Doppler axis is monotonic (Ambiguity.cpp:60-66), so this cannot fail today; a forced kernel never runs another one
-    if (h->cfar2dForce == BLAH2HIP_CFAR2D_STREAM && !cfar2d_dead_rows(h, min_doppler, &lo, &hi))
-      return fail(BLAH2HIP_ERR_UNSUPPORTED, "the stream kernel needs the rows below minDoppler to be one interval of the Doppler axis");
-  }
-  if (!cfar2d_use_stream(h, ngd, ntd, ngf, ntf, min_doppler) && !cfar2d_use_tile(h, ngd, ntd, ngf, ntf) && (rc = ensure_sat(h))) return rc; // no-op once allocated
-  const double *d_alpha = nullptr;
-  if ((rc = alpha_table(h, pfa, (size_t)(2 * (ngd + ntd) + 1) * (2 * (ngf + ntf) + 1), &d_alpha, st))) return rc;
-  HIPCHK(hipMemsetAsync(d_count, 0, n_cpi * sizeof(uint32_t), st));
+  bool useStream, useTile;
+  if ((rc = cfar2d_choose(h, ngd, ntd, ngf, ntf, min_doppler, &useStream, &useTile))) return rc;
   Cfar2dArgs a;
-  a.map = d_map ? (const cf *)d_map : h->d_map;
-  a.metrics = d_metrics ? d_metrics : h->d_metrics;
-  a.doppler = h->d_doppler;
-  a.alpha = d_alpha;
+  if ((rc = cfar_table(h, pfa, 0, window_cells(ngd, ntd, ngf, ntf), &a.alpha, nullptr, st))) return rc;
+  if ((rc = start_args(a, h, d_map, d_metrics, n_cpi, min_delay, min_doppler, d_hits, cap, d_count, st))) return rc;
   a.sat = h->d_sat;
-  a.hits = d_hits;
-  a.count = d_count;
-  a.nD = nD; a.nDelay = nC; a.delayMin = h->delayMin;
-  a.ngD = ngd; a.ntD = ntd; a.ngF = ngf; a.ntF = ntf; a.minDelay = min_delay;
-  a.minDoppler = min_doppler;
-  a.cap = cap;
-  if (cfar2d_use_stream(h, ngd, ntd, ngf, ntf, min_doppler)) {
+  a.ngD = ngd; a.ntD = ntd; a.ngF = ngf; a.ntF = ntf;
+  const int nD = a.nD, nC = a.nDelay;
+  if (useStream) {
     if ((rc = tic(h, BLAH2HIP_K_CFAR, st))) return rc;
     cfar2d_stream_launch(h, a, n_cpi, st);
     HIPCHK(hipGetLastError());
-    if ((rc = toc(h, BLAH2HIP_K_CFAR, st))) return rc;
-    return BLAH2HIP_OK;
+    return toc(h, BLAH2HIP_K_CFAR, st);
   }
-  if (cfar2d_use_tile(h, ngd, ntd, ngf, ntf)) {
+  if (useTile) {
     Cfar2dTileArgs ta;
     ta.d = a;
     ta.nCpi = (int32_t)n_cpi;
@@ -633,7 +464,7 @@ int blah2hip_cfar2d_dev(blah2hip_amb_t h, const void *d_map, const double *d_met
     ta.tilesY = (nD + ta.rowsOut - 1) / ta.rowsOut;
     const int hC = ngd + ntd;
     // the whole threshold table in LDS when it fits beside the tile (the default 17 x 9 window: 154 entries)
-    const int64_t tableN = (int64_t)(2 * (ngd + ntd) + 1) * (2 * (ngf + ntf) + 1) + 1;
+    const int64_t tableN = (int64_t)window_cells(ngd, ntd, ngf, ntf) + 1;
     ta.alphaLds = (tableN <= 2048 && c2t_lds_bytes(hC, (int)tableN) <= 160 * 1024) ? (int32_t)tableN : 0;
     const size_t lds = c2t_lds_bytes(hC, ta.alphaLds);
     const int64_t nAll = (int64_t)ta.tilesX * ta.tilesY * n_cpi;
@@ -652,8 +483,7 @@ int blah2hip_cfar2d_dev(blah2hip_amb_t h, const void *d_map, const double *d_met
     else rc = ta.alphaLds ? launch(cfar2d_tile_kernel<3, true>) : launch(cfar2d_tile_kernel<3, false>);
     if (rc) return rc;
     HIPCHK(hipGetLastError());
-    if ((rc = toc(h, BLAH2HIP_K_CFAR, st))) return rc;
-    return BLAH2HIP_OK;
+    return toc(h, BLAH2HIP_K_CFAR, st);
   }
   h->cfar2dGridLast = h->cfar2dSegRowsLast = 0;
   if ((rc = tic(h, BLAH2HIP_K_SAT_ROWS, st))) return rc;
@@ -665,85 +495,45 @@ int blah2hip_cfar2d_dev(blah2hip_amb_t h, const void *d_map, const double *d_met
   if ((rc = tic(h, BLAH2HIP_K_CFAR, st))) return rc;
   hipLaunchKernelGGL(cfar2d_kernel, dim3((nC + 255) / 256, nD, n_cpi), dim3(256), 0, st, a);
   HIPCHK(hipGetLastError());
-  if ((rc = toc(h, BLAH2HIP_K_CFAR, st))) return rc;
-  return BLAH2HIP_OK;
+  return toc(h, BLAH2HIP_K_CFAR, st);
 }
 
 int blah2hip_cfar1d_prepare(blah2hip_amb_t h, double pfa, int32_t n_train)
 {
-  if (!h) return fail(BLAH2HIP_ERR_INVALID, "NULL handle");
-  if (n_train < 0 || n_train > 127) return fail(BLAH2HIP_ERR_INVALID, "nTrain outside int8 range");
-  HIPCHK(hipSetDevice(h->device));
-  const double *d = nullptr;
-  return alpha_table(h, pfa, (size_t)(2 * n_train), &d, nullptr, true);
+  return cfar1d_pin(false, h, pfa, 0, n_train);
 }
 
 int blah2hip_cfar2d_prepare(blah2hip_amb_t h, double pfa, int32_t ngd, int32_t ntd, int32_t ngf, int32_t ntf)
 {
   if (!h) return fail(BLAH2HIP_ERR_INVALID, "NULL handle");
-  for (int32_t v : {ngd, ntd, ngf, ntf})
-    if (v < 0 || v > 127) return fail(BLAH2HIP_ERR_INVALID, "guard/train sizes outside [0, 127]");
-  HIPCHK(hipSetDevice(h->device));
   int rc;
-  if (h->cfar2dForce == BLAH2HIP_CFAR2D_TILE && !cfar2d_use_tile(h, ngd, ntd, ngf, ntf))
-    return fail(BLAH2HIP_ERR_UNSUPPORTED, "2-D window beyond the tile kernel's halo (nGf + nTf <= 24, nGd + nTd <= 40)");
-  if (h->cfar2dForce == BLAH2HIP_CFAR2D_STREAM && !cfar2d_stream_shape(ngd, ntd, ngf, ntf))
-    return fail(BLAH2HIP_ERR_UNSUPPORTED, "the stream kernel is not instantiated for this 2-D window (C2S_SHAPES in cfar_kernels.hpp)");
-  if (!cfar2d_use_stream(h, ngd, ntd, ngf, ntf, 0.0) && !cfar2d_use_tile(h, ngd, ntd, ngf, ntf) && (rc = ensure_sat(h))) return rc;
+  if ((rc = check_2d(ngd, ntd, ngf, ntf))) return rc;
+  HIPCHK(hipSetDevice(h->device));
+  bool useStream, useTile;
+  if ((rc = cfar2d_choose(h, ngd, ntd, ngf, ntf, 0.0, &useStream, &useTile))) return rc;
   const double *d = nullptr;
-  return alpha_table(h, pfa, (size_t)(2 * (ngd + ntd) + 1) * (2 * (ngf + ntf) + 1), &d, nullptr, true);
+  return cfar_table(h, pfa, 0, window_cells(ngd, ntd, ngf, ntf), &d, nullptr, nullptr, true);
 }
 
 int blah2hip_cfar2d_process(blah2hip_amb_t h, uint32_t cpi, double pfa, int32_t ngd, int32_t ntd,
                             int32_t ngf, int32_t ntf, int32_t min_delay, double min_doppler, double *delay,
                             double *doppler, double *snr, uint32_t cap, uint32_t *count)
 {
-  if (!h || !count) return fail(BLAH2HIP_ERR_INVALID, "NULL argument");
-  if (cpi >= h->dims.max_batch) return fail(BLAH2HIP_ERR_INVALID, "cpi index out of range");
-  HIPCHK(hipSetDevice(h->device));
-  const size_t cells = (size_t)h->dims.n_doppler_bins * h->dims.n_delay_bins;
-  int rc;
-  if ((rc = ensure_hits(h, cells))) return rc;
-  rc = blah2hip_cfar2d_dev(h, h->d_map + cells * cpi, h->d_metrics + 2 * cpi, 1, pfa, ngd, ntd, ngf, ntf,
-                           min_delay, min_doppler, h->d_hits, h->hitCap, h->d_count, h->stream);
-  if (rc) return rc;
-  return hits_to_host(h, delay, doppler, snr, cap, count);
+  return process_one(h, cpi, delay, doppler, snr, cap, count, [&](const cf *m, const double *met) {
+    return blah2hip_cfar2d_dev(h, m, met, 1, pfa, ngd, ntd, ngf, ntf, min_delay, min_doppler, h->d_hits, h->hitCap, h->d_count,
+                               h->stream);
+  });
 }
 
 // ------------------------------------------------------ ordered statistic --
-// Host arithmetic only.  One look: a bisection per n on the logarithm of the product formula.  More looks: per n the nodes
-// and weights of the quadrature once, then a bisection of about 60 sums over them; the entries are computed on their own,
-// in interleaved slices for up to eight threads when the table is long.
+// Host arithmetic only (cfar_alpha.hpp)
 int blah2hip_oscfar_alpha(double pfa, uint32_t looks, uint32_t rank_permille, uint32_t max_n, double *alpha, uint32_t *rank)
 {
   if (!alpha) return fail(BLAH2HIP_ERR_INVALID, "NULL table");
   if (looks == 0 || looks > BLAH2HIP_MAX_CFAR_LOOKS) return fail(BLAH2HIP_ERR_INVALID, "looks outside [1, BLAH2HIP_MAX_CFAR_LOOKS]");
   if (rank_permille < 1 || rank_permille > 1000) return fail(BLAH2HIP_ERR_INVALID, "rank_permille outside [1, 1000]");
   if (!(pfa > 0.0 && pfa < 1.0)) return fail(BLAH2HIP_ERR_INVALID, "pfa outside (0, 1)");
-  alpha[0] = std::nan("");
-  if (rank) rank[0] = 0;
-  for (uint64_t n = 1; n <= max_n; n++)
-    if (rank) rank[n] = os_rank(n, rank_permille);
-  std::vector<double> lf(looks + 1, 0.0); // log j!
-  for (uint32_t j = 2; j <= looks; j++) lf[j] = lf[j - 1] + std::log((double)j);
-  // (one look costs about 60 k log1p per entry: only a long 2-D table is worth the threads)
-  const bool threads = looks == 1 ? max_n >= 512 : max_n >= 16;
-  const uint32_t nThreads = !threads ? 1u : std::min(8u, std::max(1u, std::thread::hardware_concurrency()));
-  auto slice = [=, &lf](uint32_t first) {
-    for (uint64_t n = 1 + first; n <= max_n; n += nThreads) {
-      const uint32_t k = os_rank(n, rank_permille);
-      alpha[n] = looks == 1 ? os_alpha1(pfa, (uint32_t)n, k) : os_alpha_looks(pfa, (uint32_t)n, k, looks, lf.data());
-    }
-  };
-  std::vector<std::thread> pool;
-  uint32_t started = 1;
-  try {
-    for (; started < nThreads; started++) pool.emplace_back(slice, started);
-  } catch (const std::exception &) { // no thread to be had: the slices that are left run here
-  }
-  slice(0);
-  for (uint32_t t = started; t < nThreads; t++) slice(t);
-  for (auto &t : pool) t.join();
+  oscfar_alpha_fill(pfa, looks, rank_permille, max_n, alpha, rank);
   return BLAH2HIP_OK;
 }
 
@@ -751,81 +541,30 @@ int blah2hip_oscfar1d_dev(blah2hip_amb_t h, const void *d_map, const double *d_m
                           uint32_t rank_permille, int32_t n_guard, int32_t n_train, int32_t min_delay, double min_doppler,
                           blah2hip_hit_t *d_hits, uint32_t cap, uint32_t *d_count, void *stream)
 {
-  if (!h || !d_hits || !d_count) return fail(BLAH2HIP_ERR_INVALID, "NULL argument");
-  if (n_cpi == 0 || n_cpi > h->dims.max_batch) return fail(BLAH2HIP_ERR_INVALID, "n_cpi outside [1, max_batch]");
-  if (n_guard < 0 || n_guard > 127 || n_train < 0 || n_train > 127 || min_delay < -128 || min_delay > 127)
-    return fail(BLAH2HIP_ERR_INVALID, "nGuard/nTrain/minDelay outside int8 range");
-  int rc;
-  if ((rc = os_check_rank(rank_permille))) return rc;
-  HIPCHK(hipSetDevice(h->device));
-  hipStream_t st = (hipStream_t)stream;
-  OsCfarArgs oa;
-  CfarArgs &a = oa.c;
-  if ((rc = os_table(h, pfa, rank_permille, (size_t)(2 * n_train), &a.alpha, &oa.rank, st))) return rc;
-  HIPCHK(hipMemsetAsync(d_count, 0, n_cpi * sizeof(uint32_t), st));
-  a.map = d_map ? (const cf *)d_map : h->d_map;
-  a.metrics = d_metrics ? d_metrics : h->d_metrics;
-  a.doppler = h->d_doppler;
-  a.hits = d_hits;
-  a.count = d_count;
-  a.nD = (int32_t)h->dims.n_doppler_bins;
-  a.nDelay = (int32_t)h->dims.n_delay_bins;
-  a.delayMin = h->delayMin;
-  a.delayAxis = nullptr; // the engine's own axis: delayMin + j
-  a.nGuard = n_guard; a.nTrain = n_train; a.minDelay = min_delay;
-  a.minDoppler = min_doppler;
-  a.cap = cap;
-  if ((rc = tic(h, BLAH2HIP_K_CFAR, st))) return rc;
-  {
-    // the row as fp64 |z|^2 in LDS while it fits (150 KB: 19 200 delay bins), straight from L2 beyond: cfar1d_kernel's limit
-    const size_t rowBytes = (size_t)a.nDelay * sizeof(double);
-    if (rowBytes <= 150 * 1024) {
-      if (rowBytes > 48 * 1024) LDSCFG(oscfar1d_kernel<true>, 150 * 1024);
-      hipLaunchKernelGGL(oscfar1d_kernel<true>, dim3(a.nD, n_cpi), dim3(256), rowBytes, st, oa);
-    } else {
-      hipLaunchKernelGGL(oscfar1d_kernel<false>, dim3(a.nD, n_cpi), dim3(256), 0, st, oa);
-    }
-  }
-  HIPCHK(hipGetLastError());
-  if ((rc = toc(h, BLAH2HIP_K_CFAR, st))) return rc;
-  return BLAH2HIP_OK;
+  return cfar1d_enqueue(true, h, d_map, d_metrics, n_cpi, pfa, rank_permille, n_guard, n_train, min_delay, min_doppler, d_hits, cap,
+                        d_count, stream);
 }
 
 int blah2hip_oscfar1d_prepare(blah2hip_amb_t h, double pfa, uint32_t rank_permille, int32_t n_train)
 {
-  if (!h) return fail(BLAH2HIP_ERR_INVALID, "NULL handle");
-  if (n_train < 0 || n_train > 127) return fail(BLAH2HIP_ERR_INVALID, "nTrain outside int8 range");
-  int rc;
-  if ((rc = os_check_rank(rank_permille))) return rc;
-  HIPCHK(hipSetDevice(h->device));
-  const double *d = nullptr;
-  const uint32_t *r = nullptr;
-  return os_table(h, pfa, rank_permille, (size_t)(2 * n_train), &d, &r, nullptr, true);
+  return cfar1d_pin(true, h, pfa, rank_permille, n_train);
 }
 
 int blah2hip_oscfar1d_process(blah2hip_amb_t h, uint32_t cpi, double pfa, uint32_t rank_permille, int32_t n_guard,
                               int32_t n_train, int32_t min_delay, double min_doppler, double *delay, double *doppler,
                               double *snr, uint32_t cap, uint32_t *count)
 {
-  if (!h || !count) return fail(BLAH2HIP_ERR_INVALID, "NULL argument");
-  if (cpi >= h->dims.max_batch) return fail(BLAH2HIP_ERR_INVALID, "cpi index out of range");
-  HIPCHK(hipSetDevice(h->device));
-  const size_t cells = (size_t)h->dims.n_doppler_bins * h->dims.n_delay_bins;
-  int rc;
-  if ((rc = ensure_hits(h, cells))) return rc;
-  rc = blah2hip_oscfar1d_dev(h, h->d_map + cells * cpi, h->d_metrics + 2 * cpi, 1, pfa, rank_permille, n_guard, n_train,
-                             min_delay, min_doppler, h->d_hits, h->hitCap, h->d_count, h->stream);
-  if (rc) return rc;
-  return hits_to_host(h, delay, doppler, snr, cap, count);
+  return process_one(h, cpi, delay, doppler, snr, cap, count, [&](const cf *m, const double *met) {
+    return blah2hip_oscfar1d_dev(h, m, met, 1, pfa, rank_permille, n_guard, n_train, min_delay, min_doppler, h->d_hits,
+                                 h->hitCap, h->d_count, h->stream);
+  });
 }
 
-static int os2d_check(blah2hip_amb_t h, uint32_t rank_permille, int32_t ngd, int32_t ntd, int32_t ngf, int32_t ntf)
+// what the 2-D ordered-statistic calls check after the handle: the window's sizes (min_delay: see check_2d), the rank, the halo
+static int os2d_check(uint32_t rank_permille, int32_t ngd, int32_t ntd, int32_t ngf, int32_t ntf, int32_t min_delay = 0)
 {
-  if (!h) return fail(BLAH2HIP_ERR_INVALID, "NULL handle");
-  for (int32_t v : {ngd, ntd, ngf, ntf})
-    if (v < 0 || v > 127) return fail(BLAH2HIP_ERR_INVALID, "guard/train sizes outside [0, 127]");
   int rc;
-  if ((rc = os_check_rank(rank_permille))) return rc;
+  if ((rc = check_2d(ngd, ntd, ngf, ntf, min_delay, true)) || (rc = os_check_rank(rank_permille))) return rc;
   if (ngf + ntf > C2T_MAX_HR || ngd + ntd > C2T_MAX_HC)
     return fail(BLAH2HIP_ERR_UNSUPPORTED, "ordered-statistic 2-D window beyond the tile's halo (nGf + nTf <= 24, nGd + nTd <= 40): "
                                           "a rank has no summed-area form");
@@ -836,62 +575,45 @@ int blah2hip_oscfar2d_dev(blah2hip_amb_t h, const void *d_map, const double *d_m
                           uint32_t rank_permille, int32_t ngd, int32_t ntd, int32_t ngf, int32_t ntf, int32_t min_delay,
                           double min_doppler, blah2hip_hit_t *d_hits, uint32_t cap, uint32_t *d_count, void *stream)
 {
-  if (!h || !d_hits || !d_count) return fail(BLAH2HIP_ERR_INVALID, "NULL argument");
-  if (n_cpi == 0 || n_cpi > h->dims.max_batch) return fail(BLAH2HIP_ERR_INVALID, "n_cpi outside [1, max_batch]");
-  if (min_delay < -128 || min_delay > 127) return fail(BLAH2HIP_ERR_INVALID, "minDelay outside int8 range");
   int rc;
-  if ((rc = os2d_check(h, rank_permille, ngd, ntd, ngf, ntf))) return rc;
+  if ((rc = check_dev(h, d_hits, d_count, n_cpi)) || (rc = os2d_check(rank_permille, ngd, ntd, ngf, ntf, min_delay))) return rc;
   HIPCHK(hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream;
   OsCfar2dArgs oa;
   Cfar2dArgs &a = oa.d;
-  if ((rc = os_table(h, pfa, rank_permille, (size_t)(2 * (ngd + ntd) + 1) * (2 * (ngf + ntf) + 1), &a.alpha, &oa.rank, st))) return rc;
-  HIPCHK(hipMemsetAsync(d_count, 0, n_cpi * sizeof(uint32_t), st));
-  a.map = d_map ? (const cf *)d_map : h->d_map;
-  a.metrics = d_metrics ? d_metrics : h->d_metrics;
-  a.doppler = h->d_doppler;
+  if ((rc = cfar_table(h, pfa, rank_permille, window_cells(ngd, ntd, ngf, ntf), &a.alpha, &oa.rank, st))) return rc;
+  if ((rc = start_args(a, h, d_map, d_metrics, n_cpi, min_delay, min_doppler, d_hits, cap, d_count, st))) return rc;
   a.sat = nullptr;
-  a.hits = d_hits;
-  a.count = d_count;
-  a.nD = (int32_t)h->dims.n_doppler_bins; a.nDelay = (int32_t)h->dims.n_delay_bins; a.delayMin = h->delayMin;
-  a.ngD = ngd; a.ntD = ntd; a.ngF = ngf; a.ntF = ntf; a.minDelay = min_delay;
-  a.minDoppler = min_doppler;
-  a.cap = cap;
+  a.ngD = ngd; a.ntD = ntd; a.ngF = ngf; a.ntF = ntf;
   const size_t lds = o2_lds_bytes(ngd + ntd, ngf + ntf);
   if (lds > 48 * 1024) LDSCFG(oscfar2d_kernel, o2_lds_bytes(C2T_MAX_HC, C2T_MAX_HR)); // once per (device, kernel): its largest use
   if ((rc = tic(h, BLAH2HIP_K_CFAR, st))) return rc;
   hipLaunchKernelGGL(oscfar2d_kernel, dim3((a.nDelay + O2_COLS - 1) / O2_COLS, (a.nD + O2_ROWS - 1) / O2_ROWS, n_cpi), dim3(256),
                      lds, st, oa);
   HIPCHK(hipGetLastError());
-  if ((rc = toc(h, BLAH2HIP_K_CFAR, st))) return rc;
-  return BLAH2HIP_OK;
+  return toc(h, BLAH2HIP_K_CFAR, st);
 }
 
 int blah2hip_oscfar2d_prepare(blah2hip_amb_t h, double pfa, uint32_t rank_permille, int32_t ngd, int32_t ntd, int32_t ngf,
                               int32_t ntf)
 {
+  if (!h) return fail(BLAH2HIP_ERR_INVALID, "NULL handle");
   int rc;
-  if ((rc = os2d_check(h, rank_permille, ngd, ntd, ngf, ntf))) return rc;
+  if ((rc = os2d_check(rank_permille, ngd, ntd, ngf, ntf))) return rc;
   HIPCHK(hipSetDevice(h->device));
   const double *d = nullptr;
   const uint32_t *r = nullptr;
-  return os_table(h, pfa, rank_permille, (size_t)(2 * (ngd + ntd) + 1) * (2 * (ngf + ntf) + 1), &d, &r, nullptr, true);
+  return cfar_table(h, pfa, rank_permille, window_cells(ngd, ntd, ngf, ntf), &d, &r, nullptr, true);
 }
 
 int blah2hip_oscfar2d_process(blah2hip_amb_t h, uint32_t cpi, double pfa, uint32_t rank_permille, int32_t ngd, int32_t ntd,
                               int32_t ngf, int32_t ntf, int32_t min_delay, double min_doppler, double *delay,
                               double *doppler, double *snr, uint32_t cap, uint32_t *count)
 {
-  if (!h || !count) return fail(BLAH2HIP_ERR_INVALID, "NULL argument");
-  if (cpi >= h->dims.max_batch) return fail(BLAH2HIP_ERR_INVALID, "cpi index out of range");
-  HIPCHK(hipSetDevice(h->device));
-  const size_t cells = (size_t)h->dims.n_doppler_bins * h->dims.n_delay_bins;
-  int rc;
-  if ((rc = ensure_hits(h, cells))) return rc;
-  rc = blah2hip_oscfar2d_dev(h, h->d_map + cells * cpi, h->d_metrics + 2 * cpi, 1, pfa, rank_permille, ngd, ntd, ngf, ntf,
-                             min_delay, min_doppler, h->d_hits, h->hitCap, h->d_count, h->stream);
-  if (rc) return rc;
-  return hits_to_host(h, delay, doppler, snr, cap, count);
+  return process_one(h, cpi, delay, doppler, snr, cap, count, [&](const cf *m, const double *met) {
+    return blah2hip_oscfar2d_dev(h, m, met, 1, pfa, rank_permille, ngd, ntd, ngf, ntf, min_delay, min_doppler, h->d_hits,
+                                 h->hitCap, h->d_count, h->stream);
+  });
 }
 
 // ------------------------------------------------- centroid / interpolate --

@@ -19,12 +19,6 @@ struct blah2hip_nci_s {
 
 namespace {
 
-bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-  return a0 < b0 + nb && b0 < a0 + na;
-}
-
 // The windows that end inside the next n_cpi CPIs: a window ends at every g >= W - 1 with (g - (W - 1)) % H == 0.
 // first: the g of the first of them at or behind the counter, whether it lies inside the n_cpi CPIs or not.
 void windows_in(const blah2hip_nci_s *n, uint32_t n_cpi, uint32_t *n_out, uint64_t *first)

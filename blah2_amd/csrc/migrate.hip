@@ -8,16 +8,6 @@
 
 using namespace blah2;
 
-namespace {
-
-bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-  return a0 < b0 + nb && b0 < a0 + na;
-}
-
-} // namespace
-
 extern "C" {
 
 int blah2hip_migration_table(blah2hip_amb_t h, double fc, double *half_walk)

@@ -9,12 +9,6 @@ using namespace blah2;
 
 namespace {
 
-bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-  return a0 < b0 + nb && b0 < a0 + na;
-}
-
 // a_0 .. a_P of w[i] = sum_p (-1)^p a_p cos(2 pi p i / n)
 struct Window { int kind; uint32_t P; double a[BLAH2HIP_MAX_TAPER_SIDE + 1]; };
 const Window WINDOWS[] = {

@@ -342,7 +342,7 @@ def _os_logdens(x, n, k, L, lf):
 
 def _os_nodes(n, k, L, lf, alpha0=0.0):
     """Simpson nodes ``x`` and weights times density ``w`` of blah2hip_oscfar_alpha's quadrature for (n, k, L) at factors
-    ``>= alpha0`` (os_nodes in csrc/detect.hip)."""
+    ``>= alpha0`` (os_nodes in csrc/cfar_alpha.hpp)."""
     logc = 0.0
     for i in range(k):
         logc += np.log(float(n - i))
@@ -1234,51 +1234,28 @@ class Ambiguity:
         return {name: (float(ms[k]), int(cnt[k])) for k, name in _lib.KERNEL_NAMES.items()}
 
 
-class CfarDetector1D:
-    """src/process/detection/CfarDetector1D.h:46-55."""
+class _Cfar:
+    """What the four detectors share.  A subclass names its entry points (``_entry`` + ``_process`` / ``_dev``) and gives
+    its own arguments in ``_args()``, in the order every entry point of the library takes them."""
 
-    def __init__(self, pfa, nGuard, nTrain, minDelay, minDoppler, looks=1):
-        """``looks`` (extension): the looks per cell of the maps this detector runs on -- 1 for the engine's maps,
-        ``MapIntegrator.looks`` for integrated ones; the detector sets the handle's BLAH2HIP_OPT_CFAR_LOOKS to it at
-        every call."""
-        for name, v in (("nGuard", nGuard), ("nTrain", nTrain), ("minDelay", minDelay)):
+    _entry = None
+
+    def _init(self, pfa, minDelay, minDoppler, looks, int8=()):
+        for name, v in int8:
             if not -128 <= int(v) <= 127:  # int8_t in the reference
                 raise ValueError(f"{name} outside int8 range")
         if not 1 <= int(looks) <= _lib.MAX_CFAR_LOOKS:
             raise ValueError("looks outside [1, MAX_CFAR_LOOKS]")
-        self.pfa, self.nGuard, self.nTrain = float(pfa), int(nGuard), int(nTrain)
-        self.minDelay, self.minDoppler = int(minDelay), float(minDoppler)
-        self.looks = int(looks)
+        self.pfa, self.minDelay, self.minDoppler, self.looks = float(pfa), int(minDelay), float(minDoppler), int(looks)
 
-    def process(self, x: Map) -> Detection:
-        """CfarDetector1D::process on ``x.data`` (CfarDetector1D.cpp:23-100).  While ``x`` is still the map the engine holds
-        on the device (no later process call, cells untouched) it runs there without an upload; any other Map -- built or
-        modified by the caller, or outlived by a newer CPI -- is uploaded and runs through the same kernel
-        (blah2hip_cfar1d_map), like the C++ class does."""
-        amb = x._owner
-        cells = x.data.size
-        cap = cells
-        d = np.zeros(cap)
-        f = np.zeros(cap)
-        s = np.zeros(cap)
+    def _process_device_copy(self, amb, x):
+        """``*_process`` on the map the engine still holds on the device."""
+        cap = x.data.size
+        d, f, s = np.zeros(cap), np.zeros(cap), np.zeros(cap)
         n = C.c_uint32(0)
-        if x.device_copy_is_current():
-            amb.set_cfar_looks(self.looks)
-            check(amb._L.blah2hip_cfar1d_process(amb._h, x._cpi_index, self.pfa, self.nGuard, self.nTrain,
-                                                 self.minDelay, self.minDoppler, _ptr(d), _ptr(f), _ptr(s),
-                                                 cap, C.byref(n)))
-        else:
-            if self.looks != 1:
-                raise ValueError("CfarDetector1D.process: a map held by the host runs through blah2hip_cfar1d_map, which is "
-                                 "one-look; run process_dev on the integrated maps on the device")
-            L = _lib.load()
-            m = np.ascontiguousarray(x.data, dtype=np.complex64)
-            dax = np.ascontiguousarray(x.delay, dtype=np.int32)
-            fax = np.ascontiguousarray(x.doppler, dtype=np.float64)
-            dev = amb.device if amb is not None else 0
-            check(L.blah2hip_cfar1d_map(_ptr(m), m.shape[0], m.shape[1], _ptr(dax), _ptr(fax), float(x.noisePower), self.pfa,
-                                        self.nGuard, self.nTrain, self.minDelay, self.minDoppler, dev, _ptr(d), _ptr(f),
-                                        _ptr(s), cap, C.byref(n)))
+        amb.set_cfar_looks(self.looks)
+        check(getattr(amb._L, self._entry + "_process")(amb._h, x._cpi_index, *self._args(), _ptr(d), _ptr(f), _ptr(s), cap,
+                                                        C.byref(n)))
         k = n.value
         return Detection(d[:k].copy(), f[:k].copy(), s[:k].copy())
 
@@ -1286,8 +1263,48 @@ class CfarDetector1D:
         """Enqueue the detector for n_cpi device-resident maps (None = the engine's internal buffers of the
         last process_dev): hit records into d_hits [n_cpi][cap], counts into d_count [n_cpi]."""
         amb.set_cfar_looks(self.looks)
-        check(amb._L.blah2hip_cfar1d_dev(amb._h, d_map, d_metrics, n_cpi, self.pfa, self.nGuard, self.nTrain,
-                                         self.minDelay, self.minDoppler, d_hits, cap, d_count, stream))
+        check(getattr(amb._L, self._entry + "_dev")(amb._h, d_map, d_metrics, n_cpi, *self._args(), d_hits, cap, d_count, stream))
+
+
+class CfarDetector1D(_Cfar):
+    """src/process/detection/CfarDetector1D.h:46-55."""
+
+    _entry = "blah2hip_cfar1d"
+
+    def __init__(self, pfa, nGuard, nTrain, minDelay, minDoppler, looks=1):
+        """``looks`` (extension): the looks per cell of the maps this detector runs on -- 1 for the engine's maps,
+        ``MapIntegrator.looks`` for integrated ones; the detector sets the handle's BLAH2HIP_OPT_CFAR_LOOKS to it at
+        every call."""
+        self._init(pfa, minDelay, minDoppler, looks, (("nGuard", nGuard), ("nTrain", nTrain), ("minDelay", minDelay)))
+        self.nGuard, self.nTrain = int(nGuard), int(nTrain)
+
+    def _args(self):
+        return (self.pfa, self.nGuard, self.nTrain, self.minDelay, self.minDoppler)
+
+    def process(self, x: Map) -> Detection:
+        """CfarDetector1D::process on ``x.data`` (CfarDetector1D.cpp:23-100).  While ``x`` is still the map the engine holds
+        on the device (no later process call, cells untouched) it runs there without an upload; any other Map -- built or
+        modified by the caller, or outlived by a newer CPI -- is uploaded and runs through the same kernel
+        (blah2hip_cfar1d_map), like the C++ class does."""
+        amb = x._owner
+        if x.device_copy_is_current():
+            return self._process_device_copy(amb, x)
+        if self.looks != 1:
+            raise ValueError("CfarDetector1D.process: a map held by the host runs through blah2hip_cfar1d_map, which is "
+                             "one-look; run process_dev on the integrated maps on the device")
+        cap = x.data.size
+        d, f, s = np.zeros(cap), np.zeros(cap), np.zeros(cap)
+        n = C.c_uint32(0)
+        L = _lib.load()
+        m = np.ascontiguousarray(x.data, dtype=np.complex64)
+        dax = np.ascontiguousarray(x.delay, dtype=np.int32)
+        fax = np.ascontiguousarray(x.doppler, dtype=np.float64)
+        dev = amb.device if amb is not None else 0
+        check(L.blah2hip_cfar1d_map(_ptr(m), m.shape[0], m.shape[1], _ptr(dax), _ptr(fax), float(x.noisePower), self.pfa,
+                                    self.nGuard, self.nTrain, self.minDelay, self.minDoppler, dev, _ptr(d), _ptr(f),
+                                    _ptr(s), cap, C.byref(n)))
+        k = n.value
+        return Detection(d[:k].copy(), f[:k].copy(), s[:k].copy())
 
 
 def hits_to_detection(amb, hits, count, cap):
@@ -1305,38 +1322,26 @@ def hits_to_detection(amb, hits, count, cap):
 HIT_DTYPE = np.dtype([("row", np.int32), ("col", np.int32), ("snr", np.float64)])
 
 
-class CfarDetector2D:
+class CfarDetector2D(_Cfar):
     """2-D cell-averaging CFAR (BASELINE.json configs[2]).  Not a reference class:
     the reference only has the 1-D detector; this is its extension as defined in
     SURVEY.md section 8g, and with nGuardDoppler = nTrainDoppler = 0 it returns
     exactly what :class:`CfarDetector1D` returns."""
 
+    _entry = "blah2hip_cfar2d"
+
     def __init__(self, pfa, nGuardDelay, nTrainDelay, nGuardDoppler, nTrainDoppler, minDelay, minDoppler, looks=1):
-        if not 1 <= int(looks) <= _lib.MAX_CFAR_LOOKS:
-            raise ValueError("looks outside [1, MAX_CFAR_LOOKS]")
-        self.pfa = float(pfa)
+        self._init(pfa, minDelay, minDoppler, looks)  # looks: as for CfarDetector1D
         self.p = [int(nGuardDelay), int(nTrainDelay), int(nGuardDoppler), int(nTrainDoppler)]
-        self.minDelay, self.minDoppler = int(minDelay), float(minDoppler)
-        self.looks = int(looks)  # as for CfarDetector1D
+
+    def _args(self):
+        return (self.pfa, *self.p, self.minDelay, self.minDoppler)
 
     def process(self, x: Map) -> Detection:
-        amb = x._owner
         if not x.device_copy_is_current():
             raise ValueError("CfarDetector2D.process: this Map is no longer the engine's device copy (a later process call, or "
                              "its cells were changed); the 2-D detector has no host-map entry point")
-        cap = x.data.size
-        d, f, s = np.zeros(cap), np.zeros(cap), np.zeros(cap)
-        n = C.c_uint32(0)
-        amb.set_cfar_looks(self.looks)
-        check(amb._L.blah2hip_cfar2d_process(amb._h, x._cpi_index, self.pfa, *self.p, self.minDelay,
-                                             self.minDoppler, _ptr(d), _ptr(f), _ptr(s), cap, C.byref(n)))
-        k = n.value
-        return Detection(d[:k].copy(), f[:k].copy(), s[:k].copy())
-
-    def process_dev(self, amb, n_cpi, d_hits, cap, d_count, d_map=None, d_metrics=None, stream=0):
-        amb.set_cfar_looks(self.looks)
-        check(amb._L.blah2hip_cfar2d_dev(amb._h, d_map, d_metrics, n_cpi, self.pfa, *self.p, self.minDelay,
-                                         self.minDoppler, d_hits, cap, d_count, stream))
+        return self._process_device_copy(x._owner, x)
 
 
 def _rank_permille(rank):
@@ -1380,77 +1385,60 @@ def _detect_host_map(amb, x, enqueue):
     return hits_to_detection(amb, hits, int(cnt[0]), cap)
 
 
-class OsCfarDetector1D:
+class _OsCfar(_Cfar):
+    """The ordered-statistic detectors: a rank, and a ``process`` that also takes maps held by the host."""
+
+    def _process_any(self, x, amb):
+        """The device copy while ``x`` still is that map, else an upload of ``x.data``."""
+        amb = amb if amb is not None else x._owner
+        if x._owner is amb and x.device_copy_is_current():
+            return self._process_device_copy(amb, x)
+        return _detect_host_map(amb, x, lambda d_map, d_met, d_hits, cap, d_cnt, st:
+                                self.process_dev(amb, 1, d_hits, cap, d_cnt, d_map, d_met, st))
+
+
+class OsCfarDetector1D(_OsCfar):
     """Ordered-statistic CFAR along delay (blah2hip_oscfar1d_*): the geometry of :class:`CfarDetector1D`, the threshold
     ``alpha[n]`` times the k-th smallest training cell, ``k = oscfar_rank(n, 1000 rank)``.  No reference class.
     :func:`oscfar_hits` is the same rule in NumPy."""
 
+    _entry = "blah2hip_oscfar1d"
+
     def __init__(self, pfa, nGuard, nTrain, minDelay, minDoppler, rank=0.75, looks=1):
-        for name, v in (("nGuard", nGuard), ("nTrain", nTrain), ("minDelay", minDelay)):
-            if not -128 <= int(v) <= 127:
-                raise ValueError(f"{name} outside int8 range")
-        if not 1 <= int(looks) <= _lib.MAX_CFAR_LOOKS:
-            raise ValueError("looks outside [1, MAX_CFAR_LOOKS]")
-        self.pfa, self.nGuard, self.nTrain = float(pfa), int(nGuard), int(nTrain)
-        self.minDelay, self.minDoppler = int(minDelay), float(minDoppler)
+        self._init(pfa, minDelay, minDoppler, looks, (("nGuard", nGuard), ("nTrain", nTrain), ("minDelay", minDelay)))
+        self.nGuard, self.nTrain = int(nGuard), int(nTrain)
         self.rank_permille = _rank_permille(rank)
-        self.looks = int(looks)  # as for CfarDetector1D
+
+    def _args(self):
+        return (self.pfa, self.rank_permille, self.nGuard, self.nTrain, self.minDelay, self.minDoppler)
 
     def process(self, x: Map, amb=None) -> Detection:
         """On the engine's device copy while ``x`` still is that map, else on an upload of ``x.data`` (``amb``: the handle
         that gives the geometry when the map has no owner)."""
-        amb = amb if amb is not None else x._owner
-        if x._owner is amb and x.device_copy_is_current():
-            cap = x.data.size
-            d, f, s = np.zeros(cap), np.zeros(cap), np.zeros(cap)
-            n = C.c_uint32(0)
-            amb.set_cfar_looks(self.looks)
-            check(amb._L.blah2hip_oscfar1d_process(amb._h, x._cpi_index, self.pfa, self.rank_permille, self.nGuard, self.nTrain,
-                                                   self.minDelay, self.minDoppler, _ptr(d), _ptr(f), _ptr(s), cap, C.byref(n)))
-            k = n.value
-            return Detection(d[:k].copy(), f[:k].copy(), s[:k].copy())
-        return _detect_host_map(amb, x, lambda d_map, d_met, d_hits, cap, d_cnt, st:
-                                self.process_dev(amb, 1, d_hits, cap, d_cnt, d_map, d_met, st))
+        return self._process_any(x, amb)
 
     def process_dev(self, amb, n_cpi, d_hits, cap, d_count, d_map=None, d_metrics=None, stream=0):
         """Enqueue the detector for n_cpi device-resident maps, like :meth:`CfarDetector1D.process_dev`."""
-        amb.set_cfar_looks(self.looks)
-        check(amb._L.blah2hip_oscfar1d_dev(amb._h, d_map, d_metrics, n_cpi, self.pfa, self.rank_permille, self.nGuard,
-                                           self.nTrain, self.minDelay, self.minDoppler, d_hits, cap, d_count, stream))
+        super().process_dev(amb, n_cpi, d_hits, cap, d_count, d_map, d_metrics, stream)
 
 
-class OsCfarDetector2D:
+class OsCfarDetector2D(_OsCfar):
     """Ordered-statistic CFAR over the window of :class:`CfarDetector2D` (blah2hip_oscfar2d_*); with nGuardDoppler =
     nTrainDoppler = 0 it returns what :class:`OsCfarDetector1D` returns.  Windows beyond a halo of 40 delay columns or 24
     Doppler rows are refused (ERR_UNSUPPORTED)."""
 
+    _entry = "blah2hip_oscfar2d"
+
     def __init__(self, pfa, nGuardDelay, nTrainDelay, nGuardDoppler, nTrainDoppler, minDelay, minDoppler, rank=0.75, looks=1):
-        if not 1 <= int(looks) <= _lib.MAX_CFAR_LOOKS:
-            raise ValueError("looks outside [1, MAX_CFAR_LOOKS]")
-        self.pfa = float(pfa)
+        self._init(pfa, minDelay, minDoppler, looks)
         self.p = [int(nGuardDelay), int(nTrainDelay), int(nGuardDoppler), int(nTrainDoppler)]
-        self.minDelay, self.minDoppler = int(minDelay), float(minDoppler)
         self.rank_permille = _rank_permille(rank)
-        self.looks = int(looks)
+
+    def _args(self):
+        return (self.pfa, self.rank_permille, *self.p, self.minDelay, self.minDoppler)
 
     def process(self, x: Map, amb=None) -> Detection:
-        amb = amb if amb is not None else x._owner
-        if x._owner is amb and x.device_copy_is_current():
-            cap = x.data.size
-            d, f, s = np.zeros(cap), np.zeros(cap), np.zeros(cap)
-            n = C.c_uint32(0)
-            amb.set_cfar_looks(self.looks)
-            check(amb._L.blah2hip_oscfar2d_process(amb._h, x._cpi_index, self.pfa, self.rank_permille, *self.p, self.minDelay,
-                                                   self.minDoppler, _ptr(d), _ptr(f), _ptr(s), cap, C.byref(n)))
-            k = n.value
-            return Detection(d[:k].copy(), f[:k].copy(), s[:k].copy())
-        return _detect_host_map(amb, x, lambda d_map, d_met, d_hits, cap, d_cnt, st:
-                                self.process_dev(amb, 1, d_hits, cap, d_cnt, d_map, d_met, st))
-
-    def process_dev(self, amb, n_cpi, d_hits, cap, d_count, d_map=None, d_metrics=None, stream=0):
-        amb.set_cfar_looks(self.looks)
-        check(amb._L.blah2hip_oscfar2d_dev(amb._h, d_map, d_metrics, n_cpi, self.pfa, self.rank_permille, *self.p,
-                                           self.minDelay, self.minDoppler, d_hits, cap, d_count, stream))
+        return self._process_any(x, amb)
 
 
 class MapIntegrator:
