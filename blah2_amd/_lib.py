@@ -71,6 +71,8 @@ INFO_BEARING_GRID = 16
 INFO_TAPER_GRID = 17
 INFO_MIGRATE_GRID = 18
 MAX_MIGRATION = 512
+INFO_RATE_GRID = 19
+MAX_RATES = 16
 
 
 class Blah2HipError(RuntimeError):
@@ -142,6 +144,9 @@ SYMBOLS = {
     "blah2hip_migration_table": (C.c_int, [_vp, _dbl, _vp]),
     "blah2hip_amb_set_migration": (C.c_int, [_vp, _vp]),
     "blah2hip_amb_migrate_dev": (C.c_int, [_vp, _vp, _u32, _vp, _vp, _vp]),
+    "blah2hip_doppler_rate": (C.c_int, [_vp, _dbl, _dbl, C.POINTER(_dbl)]),
+    "blah2hip_amb_set_rates": (C.c_int, [_vp, _vp, _u32]),
+    "blah2hip_amb_rate_bank_dev": (C.c_int, [_vp, _vp, _u32, _vp, _vp, _vp, _vp]),
     "blah2hip_cfar_alpha": (C.c_int, [_dbl, _u32, _u32, _vp]),
     "blah2hip_cfar1d_dev": (C.c_int, [_vp, _vp, _vp, _u32, _dbl, _i32, _i32, _i32, _dbl, _vp, _u32, _vp, _vp]),
     "blah2hip_cfar1d_prepare": (C.c_int, [_vp, _dbl, _i32]),

@@ -1,7 +1,7 @@
 // Internal to the library: what the units behind include/blah2hip.h share.  The ambiguity handle, whose fields every
 // unit reads directly (no accessors), the error and launch-check helpers, and the few engine functions (capi.hip)
-// that another unit calls.  Host code only: capi.hip, array.hip, detect.hip, integrate.hip, taper.hip, migrate.hip and
-// context.hip all include it.
+// that another unit calls.  Host code only: capi.hip, array.hip, detect.hip, integrate.hip, taper.hip, migrate.hip, rate.hip
+// and context.hip all include it.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -106,7 +106,7 @@ struct blah2hip_amb_s {
   int lastLeakLags = 0;             // BLAH2HIP_INFO_LEAK_LAGS: lags corrected by the last process call (0 = not applied)
   double lastLeakMax = 0.0;         // BLAH2HIP_INFO_LEAK_MAX_E12: the largest |g| of the calibration the last call ran under
 
-  // ---- written by detect.hip; bearingGridLast by array.hip, taperGridLast by taper.hip, the migration fields by migrate.hip
+  // ---- written by detect.hip; bearingGridLast by array.hip, taperGridLast by taper.hip, the migration fields by migrate.hip, the rate fields by rate.hip
   // a threshold table of detect.hip's cfar_table(); d: alpha[n + 1], then with a rank (permille) rank[n + 1] words; pinned:
   // handed out by *_prepare, never evicted.  Two lists, each with its own budget; destroy (capi.hip) frees both.
   struct CfarTable { double pfa; uint32_t looks, rank; size_t n; double *d; bool pinned; };
@@ -122,6 +122,9 @@ struct blah2hip_amb_s {
   double *d_migrate = nullptr;      // [nD] half walks (blah2hip_amb_set_migration), allocated at its first use, freed by destroy
   bool migrateSet = false;          // ... and whether a table is set
   int migrateGridLast = 0;          // BLAH2HIP_INFO_MIGRATE_GRID
+  cf *d_rates = nullptr;            // [BLAH2HIP_MAX_RATES][nD] chirps c_k[i] (blah2hip_amb_set_rates, rate.hip), allocated at its first use, freed by destroy
+  uint32_t nRates = 0, zeroRates = 0; // ... hypotheses of the bank that is set (0 = none), and bit k: q[k] == 0
+  int rateGridLast = 0;             // BLAH2HIP_INFO_RATE_GRID
 
   // ---- every unit brackets its launches (tic / toc below)
   blah2::KernelTimer<BLAH2HIP_K_COUNT> timer;

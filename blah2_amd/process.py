@@ -675,6 +675,79 @@ def migrate_maps(R, half_walk):
     return out
 
 
+def doppler_rate(dims, fc, accel):
+    """``blah2hip_doppler_rate`` restated: the Doppler rate ``q = -accel * fc / 299792458 * T**2`` in bins drifted over the CPI
+    of ``T = n_doppler_bins * n_corr / fs`` seconds, for the carrier ``fc`` (Hz) and the second derivative ``accel`` of the
+    bistatic range (m/s^2).  ``dims``: anything with ``n_doppler_bins``, ``n_corr`` and ``fs`` (the oracle's
+    ``ambiguity_dims``), or an :class:`Ambiguity`.  A receding acceleration lowers the Doppler: ``q`` is negative."""
+    if isinstance(dims, Ambiguity):
+        return dims.doppler_rate(fc, accel)
+    fc, accel = float(fc), float(accel)
+    if not math.isfinite(fc) or not fc > 0.0:
+        raise ValueError("the carrier frequency must be finite and positive")
+    if not math.isfinite(accel):
+        raise ValueError("the acceleration must be finite")
+    T = float(dims.n_doppler_bins) * float(dims.n_corr) / float(dims.fs)
+    return -accel * fc / 299792458.0 * T * T
+
+
+def rate_bank(q_max, step=1.0):
+    """The symmetric bank ``-n step .. n step`` with ``n = floor(q_max / step)``: fp64, ascending, 0 in the middle.
+    ValueError above ``BLAH2HIP_MAX_RATES`` = 16 entries (so at most 15 here), or for a ``q_max`` or ``step`` that is not
+    finite, a negative ``q_max``, a ``step`` that is not positive."""
+    q_max, step = float(q_max), float(step)
+    if not (math.isfinite(q_max) and math.isfinite(step)) or q_max < 0.0 or not step > 0.0:
+        raise ValueError("rate_bank needs a finite q_max >= 0 and a finite step > 0")
+    n = int(math.floor(q_max / step * (1.0 + 1e-12)))
+    if 2 * n + 1 > _lib.MAX_RATES:
+        raise ValueError(f"a bank of {2 * n + 1} rates: at most {_lib.MAX_RATES}")
+    return np.arange(-n, n + 1, dtype=np.float64) * step
+
+
+def rate_chirps(q, nD):
+    """The chirp table of ``blah2hip_amb_set_rates`` in fp64: ``c[k, i] = exp(-1j * theta_k(i))`` with
+    ``theta_k(i) = pi * q[k] * t(i)**2 / (4 nD**2)``, ``t(i) = 2 i - (nD - 1)``; complex128 ``[len(q), nD]``.  The library
+    rounds its real and imaginary parts to fp32."""
+    q = np.atleast_1d(np.asarray(q, dtype=np.float64))
+    nD = int(nD)
+    t = 2 * np.arange(nD, dtype=np.int64) - (nD - 1)
+    th = np.pi * q[:, None] * (t * t).astype(np.float64)[None, :] / (4.0 * float(nD) * float(nD))
+    return np.cos(th) + 1j * (-np.sin(th))
+
+
+def rate_bank_maps(R, q, half_walk=None):
+    """blah2hip_amb_rate_bank_dev restated in fp64 NumPy for EVERY row (the library takes a zero rate's candidate in a
+    zero-shift row from its input map instead): ``M_k[j][d] = sum_i [0 <= d + s(j,i) < nDelay] R[i][d + s(j,i)] c_k[i]
+    W[(i src(j)) mod nD]`` with the chirps of :func:`rate_chirps` and the shifts of :func:`migration_shifts` (``half_walk``
+    None: no walk).  ``R``: complex ``[..., nD, nDelay]``.  Returns ``(maps, index, all_hypotheses)``: the strongest
+    hypothesis per cell ``[..., nD, nDelay]``, its index (uint8, the smallest of equals) and every ``M_k``
+    ``[K, ..., nD, nDelay]``."""
+    R = np.asarray(R).astype(np.complex128)
+    nD = R.shape[-2]
+    q = np.atleast_1d(np.asarray(q, dtype=np.float64))
+    if q.ndim != 1 or not 1 <= q.size <= 256:  # (the library's banks end at BLAH2HIP_MAX_RATES; the restatement's need not)
+        raise ValueError("a bank holds 1 .. 256 rates")
+    nDelay = R.shape[-1]
+    h = np.zeros(nD) if half_walk is None else np.asarray(half_walk, dtype=np.float64)
+    if h.shape != (nD,):
+        raise ValueError("half_walk must hold one entry per Doppler row")
+    c = rate_chirps(q, nD)
+    s = migration_shifts(h, nD)
+    i = np.arange(nD)
+    d = np.arange(nDelay)
+    every = np.zeros((q.size,) + R.shape, dtype=np.complex128)
+    for j in range(nD):  # migrate_maps' row, gathered once for the whole bank
+        w = np.exp(-2j * np.pi * ((i * ((j + nD // 2 + 1) % nD)) % nD) / nD)
+        col = d[None, :] + s[j][:, None]  # [pulse, column]
+        ok = (col >= 0) & (col < nDelay)
+        g = np.where(ok, np.take_along_axis(R, np.broadcast_to(np.clip(col, 0, nDelay - 1), R.shape), axis=-1), 0.0)
+        for k in range(q.size):
+            every[k, ..., j, :] = np.sum(g * (c[k] * w)[:, None], axis=-2)
+    index = np.argmax(np.abs(every) ** 2, axis=0).astype(np.uint8)  # the first of equals
+    maps = np.take_along_axis(every, index[None].astype(np.int64), axis=0)[0]
+    return maps, index, every
+
+
 class Map:
     """src/data/Map.h: rows = Doppler, cols = delay.  ``data`` is complex64."""
 
@@ -1135,6 +1208,32 @@ class Ambiguity:
         ``d_out_map`` the same pointer or a disjoint ``[n_maps][nD][nDelay]`` complex64 buffer, ``d_out_metrics``
         ``[n_maps][2]`` float64.  Enqueues only."""
         check(self._L.blah2hip_amb_migrate_dev(self._h, d_map, n_maps, d_out_map, d_out_metrics, stream))
+
+    def doppler_rate(self, fc, accel):
+        """blah2hip_doppler_rate: the Doppler rate in bins drifted over this handle's CPI for the carrier ``fc`` (Hz) and the
+        second derivative ``accel`` of the bistatic range (m/s^2)."""
+        q = C.c_double()
+        check(self._L.blah2hip_doppler_rate(self._h, float(fc), float(accel), C.byref(q)))
+        return q.value
+
+    def set_rates(self, q):
+        """The bank of fp64 Doppler rates (bins drifted over the CPI: :func:`rate_bank`, :func:`doppler_rate`, at most 16) that
+        :meth:`rate_bank_dev` tries per cell (blah2hip_amb_set_rates); None or an empty list clears it."""
+        if q is None or np.size(q) == 0:
+            check(self._L.blah2hip_amb_set_rates(self._h, None, 0))
+            return
+        t = np.ascontiguousarray(np.atleast_1d(q), dtype=np.float64)
+        if t.ndim != 1:
+            raise ValueError("the bank is a list of rates")
+        check(self._L.blah2hip_amb_set_rates(self._h, _ptr(t), t.size))
+
+    def rate_bank_dev(self, d_map, n_maps, d_out_map, d_out_index, d_out_metrics, stream=0):
+        """The Doppler-rate bank over the first ``n_maps`` maps of the last ``process_dev`` / ``process_multi_dev`` call, along
+        the walk of the migration table if one is set (blah2hip_amb_rate_bank_dev; raw pointers/ints): ``d_map`` is that
+        call's map buffer (None: the handle's own), ``d_out_map`` the same pointer or a disjoint ``[n_maps][nD][nDelay]``
+        complex64 buffer, ``d_out_index`` ``[n_maps][nD][nDelay]`` uint8 or None, ``d_out_metrics`` ``[n_maps][2]`` float64.
+        Enqueues only."""
+        check(self._L.blah2hip_amb_rate_bank_dev(self._h, d_map, n_maps, d_out_map, d_out_index, d_out_metrics, stream))
 
     def set_taper_seg_rows(self, n):
         """Doppler rows per segment of the taper kernel (0 = the launch's own choice); ``info(INFO_TAPER_GRID)`` reports the

@@ -617,7 +617,16 @@ class GpuChain:
     in front of the taper, rewrites the batch's maps and metrics in place from the range map that the ambiguity stage left on
     the handle (every configuration of this chain runs ``process_dev``, so there always is one); everything after it reads
     the result.  ValueError: no ``fc``, an ``fc`` that is not positive and finite, or a geometry whose outermost Doppler row
-    walks more than BLAH2HIP_MAX_MIGRATION cells.  Without the key nothing is allocated or launched."""
+    walks more than BLAH2HIP_MAX_MIGRATION cells.  Without the key nothing is allocated or launched.
+
+    ``cfg["ambiguity"]["dopplerRate"] = QMAX`` or ``{"max": QMAX, "step": S}`` runs the Doppler-rate bank
+    ``blah2_amd.rate_bank(QMAX, S)`` (bins drifted over the CPI, at most 16 hypotheses; ``Ambiguity.set_rates`` /
+    ``rate_bank_dev``) in place behind the ambiguity stage and in front of the taper: every cell becomes the strongest of the
+    bank's de-chirped Doppler sums.  With ``migration`` configured too, its table is set on the handle and this one kernel
+    sums along the walk as well, INSTEAD of ``migrate_dev`` (two stages would each overwrite the other).  The maximum over K
+    hypotheses multiplies the false-alarm rate by at most K, so the detector is made with ``pfa / K`` (the union bound).
+    ValueError, naming the key: a bank of more than 16 rates, a ``max`` or ``step`` that is not a finite number (``max`` >= 0,
+    ``step`` > 0), a bank the library refuses (|q| above the Doppler bins).  Without the key nothing is launched."""
 
     def __init__(self, cfg: dict, device: int = 0, batch: int = 1, want_map: bool = False, depth: int = 3,
                  reader_threads: int = 4, hit_copy: int = 4096, read_mode: str = "memmove", numa: bool = True,
@@ -698,9 +707,30 @@ class GpuChain:
             fc = float(fc)
             if not math.isfinite(fc) or not fc > 0.0:
                 raise ValueError(f"ambiguity.migration: fc = {fc!r} is not a positive, finite frequency")
+        # ambiguity: {dopplerRate: QMAX | {max: QMAX, step: S}}: the bank -QMAX .. QMAX of Doppler rates (None: no such stage)
+        self.rates = None
+        rate = amb_c.get("dopplerRate")
+        rate = None if rate is False else rate
+        if rate is not None:
+            try:
+                if isinstance(rate, bool):
+                    raise ValueError("QMAX or {max: QMAX, step: S}")
+                q_max, step = (rate.get("max"), rate.get("step", 1.0)) if isinstance(rate, dict) else (rate, 1.0)
+                if q_max is None:
+                    raise ValueError("{max: QMAX, step: S} needs max")
+                rates = blah2_amd.rate_bank(float(q_max), float(step))
+            except (TypeError, ValueError) as e:
+                raise ValueError(f"ambiguity.dopplerRate = {rate!r}: {e}") from None
         self.amb = blah2_amd.Ambiguity(amb_c["delayMin"], amb_c["delayMax"], amb_c["dopplerMin"], amb_c["dopplerMax"],
                                        self.fs, n, True, device=device, max_batch=B)
         nD, nC = self.amb.get_n_doppler_bins(), self.amb.get_n_delay_bins()
+        if rate is not None:
+            try:
+                self.amb.set_rates(rates)
+            except blah2_amd.Blah2HipError as e:
+                self.amb.close()
+                raise ValueError(f"ambiguity.dopplerRate = {rate!r} on {nD} Doppler bins: {e}") from None
+            self.rates = rates
         if mig is not None:
             try:
                 self.amb.set_migration(self.amb.migration_table(fc))
@@ -741,11 +771,14 @@ class GpuChain:
             kind = str(det_c.get("cfar", "ca")).lower()
             if kind not in ("ca", "os"):
                 raise ValueError(f"detection.cfar {kind!r}: 'ca' or 'os'")
+            # a cell of the rate bank's map is the strongest of K hypotheses, which multiplies the false-alarm rate by at
+            # most K: the thresholds are made for pfa / K (the union bound)
+            pfa = det_c["pfa"] if self.rates is None else det_c["pfa"] / len(self.rates)
             if kind == "os":
-                self.cfar = blah2_amd.OsCfarDetector1D(det_c["pfa"], det_c["nGuard"], det_c["nTrain"], det_c["minDelay"],
+                self.cfar = blah2_amd.OsCfarDetector1D(pfa, det_c["nGuard"], det_c["nTrain"], det_c["minDelay"],
                                                        det_c["minDoppler"], rank=float(det_c.get("rank", 0.75)), **looks)
             else:
-                self.cfar = blah2_amd.CfarDetector1D(det_c["pfa"], det_c["nGuard"], det_c["nTrain"], det_c["minDelay"],
+                self.cfar = blah2_amd.CfarDetector1D(pfa, det_c["nGuard"], det_c["nTrain"], det_c["minDelay"],
                                                      det_c["minDoppler"], **looks)
             if "nCentroid" in det_c:  # blah2.cpp:176-181
                 self.centroid = blah2_amd.Centroid(det_c["nCentroid"], det_c["nCentroid"], 1 / (n / self.fs))
@@ -933,7 +966,9 @@ class GpuChain:
                 amb.process_dev(fmt_yf, x, self.yf.data_ptr(), cnt, n, slot["d_map"].data_ptr(),
                                 slot["d_met"].data_ptr(), st)
             n_maps, maps, mets = cnt, slot["d_map"], slot["d_met"]  # what the detector and the download read
-            if self.migrate:  # in place, from the range map the call above left on the handle
+            if self.rates is not None:  # in place too; along the migration table's walk when one is set: one sum for both
+                amb.rate_bank_dev(maps.data_ptr(), cnt, maps.data_ptr(), None, mets.data_ptr(), st)
+            elif self.migrate:  # in place, from the range map the call above left on the handle
                 amb.migrate_dev(maps.data_ptr(), cnt, maps.data_ptr(), mets.data_ptr(), st)
             if self.taper is not None:
                 amb.taper_dev(maps.data_ptr(), cnt, self.taper, slot["d_tmap"].data_ptr(), slot["d_tmet"].data_ptr(), st)
@@ -1211,6 +1246,12 @@ def main(argv=None):
                     help="range-migration compensation behind the ambiguity stage (in front of the taper) for the carrier "
                          "FC_HZ; without a value the config's capture.fc.  process.ambiguity.migration: true in the config "
                          "does the same")
+    ap.add_argument("--doppler-rate", default=None, metavar="QMAX[:STEP]",
+                    help="Doppler-rate (acceleration) bank behind the ambiguity stage, in front of the taper: every cell becomes "
+                         "the strongest of the hypotheses -QMAX ... QMAX in steps of STEP (default 1), in Doppler bins drifted "
+                         "over the CPI, at most 16 of them; with --migration the same kernel sums along the range walk too.  The "
+                         "maximum over K hypotheses multiplies the false-alarm rate by at most K, so the detector is made with "
+                         "pfa / K (the union bound).  Overrides process.ambiguity.dopplerRate (QMAX or {max: QMAX, step: STEP})")
     ap.add_argument("--cfar", default=None, metavar="KIND[:RANK]",
                     help="the detector: ca (cell averaging, the reference's) or os[:RANK] (ordered statistic: the threshold "
                          "from the RANK-th part of the sorted training cells, default 0.75); overrides "
@@ -1270,6 +1311,16 @@ def main(argv=None):
         cfg["ambiguity"] = dict(cfg["ambiguity"], migration={"fc": fc_})
     elif "migration" in cfg["ambiguity"]:
         cfg["ambiguity"] = {k: v for k, v in cfg["ambiguity"].items() if k != "migration"}
+    if a.doppler_rate is not None:
+        try:
+            qs_ = [float(v) for v in a.doppler_rate.split(":")]
+            if not 1 <= len(qs_) <= 2:
+                raise ValueError
+            from .process import rate_bank
+            rate_bank(*qs_)
+        except ValueError:
+            ap.error("--doppler-rate takes QMAX or QMAX:STEP, QMAX >= 0 and STEP > 0 in Doppler bins, at most 16 hypotheses")
+        cfg["ambiguity"] = dict(cfg["ambiguity"], dopplerRate={"max": qs_[0], "step": qs_[1] if len(qs_) == 2 else 1.0})
     if a.cfar is not None:
         kind, _, rank_ = a.cfar.partition(":")
         try:

@@ -259,6 +259,7 @@ int blah2hip_amb_set_option(blah2hip_amb_t h, int option, int64_t value);
 #define BLAH2HIP_INFO_BEARING_GRID 16         /* workgroups per list of the last blah2hip_amb_bearing_dev launch */
 #define BLAH2HIP_INFO_TAPER_GRID 17            /* workgroups per map of the last blah2hip_amb_taper_dev launch */
 #define BLAH2HIP_INFO_MIGRATE_GRID 18          /* workgroups per map of the last blah2hip_amb_migrate_dev launch */
+#define BLAH2HIP_INFO_RATE_GRID 19             /* workgroups per map of the last blah2hip_amb_rate_bank_dev launch */
 int blah2hip_amb_get_info(blah2hip_amb_t h, int key, int64_t *value);
 
 /* Ambiguity::process + Map::set_metrics on host buffers (blah2.cpp:278-279).
@@ -629,6 +630,52 @@ int blah2hip_amb_set_migration(blah2hip_amb_t h, const double *half_walk);
  * without being the same pointer, a metrics buffer inside a map. */
 int blah2hip_amb_migrate_dev(blah2hip_amb_t h, const void *d_map, uint32_t n_maps, void *d_out_map, double *d_out_metrics,
                              void *stream);
+
+/* ---- Doppler-rate bank (no reference counterpart: Ambiguity.cpp:152-169 sums every pulse with one fixed Doppler) ----
+ * A target whose bistatic range accelerates by a m/s^2 drifts in Doppler by -a fc / c Hz per second: over the CPI of
+ * T = n_doppler n_corr / fs seconds that is q = -a fc / c T^2 Doppler bins, and the echo smears over |q| rows.  The bank is a
+ * third Doppler sum over the range map of the last process call, which de-chirps every pulse for each of K hypotheses of q,
+ * walks the delay columns like the migration block above IN THE SAME SUM (two separate stages would each overwrite the
+ * other), and keeps the strongest hypothesis per cell.  With the migration block's R, src, W, t and
+ *   s(j,i)    = (int) rint( h[j] * (double) t(i) ), or 0 for every (j, i) when no migration table is set on the handle,
+ *   q[k]        a BANK of K <= BLAH2HIP_MAX_RATES fp64 Doppler rates in BINS DRIFTED OVER THE CPI; positive: the Doppler rises
+ *               through the CPI.  Chirp and walk are referenced to mid-CPI: the echo lands at its mid-CPI Doppler and delay,
+ *   theta_k(i) = pi * q[k] * (double)(t(i) * t(i)) / (4.0 * n_doppler * n_doppler)             (fp64, on the host)
+ *   c_k[i]    = ( (float) cos theta_k(i), (float) (-sin theta_k(i)) )                          (an fp32 table [K][n_doppler])
+ *   M_k[j][d] = sum_i [0 <= d + s(j,i) < n_delay]  ( R[i][d + s(j,i)] c_k[i] ) W[(i src(j)) mod n_doppler]
+ *   k*(j,d)   = the smallest k with the largest power p = x x + y y (fp32) of M_k[j][d]
+ *   out[j][d] = M_k*[j][d],   index[j][d] = (uint8) k*
+ * The arithmetic is migrate_kernel's: fp32 complex multiply-adds in pulse order, a block of 32 pulses summed on its own and
+ * added into a running sum, the range cell multiplied by the chirp first and by the twiddle second.  The order of the
+ * additions depends on (j, k, i) alone: equal inputs give equal bits at every placement, every n_maps and for a hypothesis
+ * at any position in the bank.  A candidate with q[k] == 0 in a ZERO-SHIFT row (rint(h[j] (n_doppler - 1)) == 0, or no table
+ * set) is THE INPUT MAP'S CELL, bit for bit: it keeps what the hot-column and leak machinery wrote at the direct path; every
+ * other candidate is the sum above.  So the bank {0} with no table returns the input maps, and the bank {0} with a table
+ * returns blah2hip_amb_migrate_dev's maps (on maps without zero cells: c = (1, -0) may change the sign of a zero).  A term
+ * whose column falls outside the map contributes zero.  The quadratic RANGE term of an acceleration is not modelled: it is
+ * a t^2 / 2 = 1.25 m at 1 g and +-0.5 s, against a delay cell of 30 m or more. */
+#define BLAH2HIP_MAX_RATES 16 /* hypotheses in a bank */
+/* Host only: q = -accel * fc / 299792458 * T^2 with T = n_doppler * n_corr / fs; accel is the second derivative of the
+ * bistatic range in m/s^2.  BLAH2HIP_ERR_INVALID: a NULL argument, fc not finite or not positive, accel not finite. */
+int blah2hip_doppler_rate(blah2hip_amb_t h, double fc, double accel, double *q);
+/* Builds the chirp table of the bank q[0 .. n_rates - 1] in fp64 on the host and copies it into a device buffer the handle
+ * owns (allocated at the first call, freed by destroy; the call waits for the device, like blah2hip_amb_set_migration).
+ * NULL or n_rates 0 clears the bank.  Duplicates are allowed; the lower index wins ties.  BLAH2HIP_ERR_INVALID, with the bank
+ * that was set left as it was: n_rates above BLAH2HIP_MAX_RATES, an entry that is not finite, |q| above n_doppler (beyond
+ * that the chirp's end frequency passes half the slow-time rate). */
+int blah2hip_amb_set_rates(blah2hip_amb_t h, const double *q, uint32_t n_rates);
+/* out, index and metrics for maps 0 .. n_maps - 1 of the handle's range map as the last process call left it:
+ * blah2hip_amb_migrate_dev's contract throughout.  d_map: that call's map buffer (NULL = the handle's own), read only where
+ * a candidate is the input cell.  d_out_map [n_maps][n_doppler][n_delay] may be the same pointer (in place) or a disjoint
+ * buffer; d_out_index [n_maps][n_doppler][n_delay] uint8 may be NULL; d_out_metrics [n_maps][2] is Map::set_metrics of
+ * every output map on the cells as written.  The migration table set on the handle at the time of the call is the walk.
+ * Enqueues only -- rate_bank_kernel (BLAH2HIP_K_DOPPLER) and metrics_kernel (BLAH2HIP_K_METRICS) -- with no upload,
+ * allocation or synchronisation, and can be captured in a graph.  The grid, ceil(n_delay / 64) ceil(n_doppler / 16)
+ * workgroups per map (BLAH2HIP_INFO_RATE_GRID), depends on the geometry alone, never on n_maps; the bank goes in passes
+ * inside a workgroup.  BLAH2HIP_ERR_INVALID, with nothing enqueued: every case of blah2hip_amb_migrate_dev but "no table
+ * set"; no bank set; an index plane that overlaps a map or the metrics. */
+int blah2hip_amb_rate_bank_dev(blah2hip_amb_t h, const void *d_map, uint32_t n_maps, void *d_out_map, uint8_t *d_out_index,
+                               double *d_out_metrics, void *stream);
 
 /* ---- CfarDetector1D (CfarDetector1D.h:46-55) ---------------------------- */
 /* dev: d_map/d_metrics as written by blah2hip_amb_process_dev (NULL = the
@@ -1037,7 +1084,7 @@ int blah2hip_amb_result_ptrs(blah2hip_amb_t h, const void **d_map, const double 
 /* ---- per-kernel timing (HIP events on the launch stream) ---------------- */
 #define BLAH2HIP_K_RANGE 0
 #define BLAH2HIP_K_DOPPLER 1
-#define BLAH2HIP_K_METRICS 2   /* metrics_kernel: behind the Doppler kernels, the beam former, the integrator, the Doppler taper and migrate_kernel */
+#define BLAH2HIP_K_METRICS 2   /* metrics_kernel: behind the Doppler kernels, the beam former, the integrator, the Doppler taper, migrate_kernel and rate_bank_kernel */
 #define BLAH2HIP_K_CFAR 3     /* cfar1d_kernel, cfar2d_tile_kernel or cfar2d_kernel */
 #define BLAH2HIP_K_SAT_ROWS 4 /* 2-D CFAR through the summed-area table (large windows): row prefix sums */
 #define BLAH2HIP_K_SAT_COLS 5 /* ... column prefix sums */
