@@ -20,8 +20,8 @@ KERNEL_NAMES = {K_RANGE: "range", K_DOPPLER: "doppler", K_METRICS: "metrics", K_
                 K_SAT_ROWS: "sat_rows", K_SAT_COLS: "sat_cols", K_ROTATE: "rotate", K_BEAM: "beam", K_COV: "cov",
                 K_BEARING: "bearing"}
 CK_CORR, CK_REDUCE, CK_SOLVE, CK_FIR, CK_COUNT = 0, 1, 2, 3, 4
-NK_NCI, NK_COUNT = 0, 1
-NCI_KERNEL_NAMES = {NK_NCI: "nci"}
+NK_NCI, NK_TRACK_POWER, NK_TRACK_SUM, NK_COUNT = 0, 1, 2, 3
+NCI_KERNEL_NAMES = {NK_NCI: "nci", NK_TRACK_POWER: "track_power", NK_TRACK_SUM: "track_sum"}
 CLUTTER_KERNEL_NAMES = {CK_CORR: "clutter_corr", CK_REDUCE: "clutter_reduce", CK_SOLVE: "clutter_solve",
                         CK_FIR: "clutter_fir"}
 OPT_DOPPLER_KERNEL, OPT_RANGE_GRID, OPT_RANGE_KERNEL, OPT_DOPPLER_GRID, OPT_FFT_LEN, OPT_CFAR2D_KERNEL = 1, 2, 3, 4, 5, 6
@@ -73,6 +73,8 @@ INFO_MIGRATE_GRID = 18
 MAX_MIGRATION = 512
 INFO_RATE_GRID = 19
 MAX_RATES = 16
+INFO_TRACK_GRID, INFO_TRACK_MAX_SHIFT = 20, 21
+MAX_TRACK_SHIFT = 1048576
 
 
 class Blah2HipError(RuntimeError):
@@ -137,6 +139,9 @@ SYMBOLS = {
     "blah2hip_nci_reset": (C.c_int, [_vp]),
     "blah2hip_nci_count": (C.c_int, [_vp, _u32, C.POINTER(_u32), C.POINTER(C.c_uint64)]),
     "blah2hip_nci_process_dev": (C.c_int, [_vp, _vp, _u32, _vp, _vp, _vp, _u32, C.POINTER(_u32), C.POINTER(C.c_uint64), _vp]),
+    "blah2hip_nci_walk_table": (C.c_int, [_vp, _dbl, _dbl, _vp]),
+    "blah2hip_nci_set_tracks": (C.c_int, [_vp, _vp, _vp, _u32, _u32]),
+    "blah2hip_nci_process_tracks_dev": (C.c_int, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32, C.POINTER(_u32), C.POINTER(C.c_uint64), _vp]),
     "blah2hip_nci_set_timing": (C.c_int, [_vp, C.c_int]),
     "blah2hip_nci_get_timing": (C.c_int, [_vp, _vp, _vp]),
     "blah2hip_doppler_taper": (C.c_int, [C.c_int, C.c_int, _vp, C.POINTER(_u32)]),

@@ -125,6 +125,7 @@ struct blah2hip_amb_s {
   cf *d_rates = nullptr;            // [BLAH2HIP_MAX_RATES][nD] chirps c_k[i] (blah2hip_amb_set_rates, rate.hip), allocated at its first use, freed by destroy
   uint32_t nRates = 0, zeroRates = 0; // ... hypotheses of the bank that is set (0 = none), and bit k: q[k] == 0
   int rateGridLast = 0;             // BLAH2HIP_INFO_RATE_GRID
+  int trackGridLast = 0, trackShiftLast = 0; // BLAH2HIP_INFO_TRACK_GRID / _TRACK_MAX_SHIFT (integrate.hip)
 
   // ---- every unit brackets its launches (tic / toc below)
   blah2::KernelTimer<BLAH2HIP_K_COUNT> timer;

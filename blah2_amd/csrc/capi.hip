@@ -1188,6 +1188,8 @@ int blah2hip_amb_get_info(blah2hip_amb_t h, int key, int64_t *value)
   case BLAH2HIP_INFO_TAPER_GRID: *value = h->taperGridLast; return BLAH2HIP_OK;
   case BLAH2HIP_INFO_MIGRATE_GRID: *value = h->migrateGridLast; return BLAH2HIP_OK;
   case BLAH2HIP_INFO_RATE_GRID: *value = h->rateGridLast; return BLAH2HIP_OK;
+  case BLAH2HIP_INFO_TRACK_GRID: *value = h->trackGridLast; return BLAH2HIP_OK;
+  case BLAH2HIP_INFO_TRACK_MAX_SHIFT: *value = h->trackShiftLast; return BLAH2HIP_OK;
   case BLAH2HIP_INFO_LEAK_LAGS: *value = h->lastLeakLags; return BLAH2HIP_OK;
   case BLAH2HIP_INFO_LEAK_MAX_E12: *value = (int64_t)std::llround(h->lastLeakMax * 1e12); return BLAH2HIP_OK;
   case BLAH2HIP_INFO_HOT_COLUMNS: { // of the last call's first CPI; waits for the device

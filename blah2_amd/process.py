@@ -537,6 +537,100 @@ def integrate_maps(maps, w=None, window=1, hop=None):
     return np.stack(out) if out else np.zeros((0,) + m.shape[2:])
 
 
+def nci_walk_table(dims, fc, spacing=1.0):
+    """``blah2hip_nci_walk_table`` restated: the physical walk between CPIs ``walk[j] = -doppler[j] * n_corr *
+    n_doppler_bins * spacing / fc`` (fp64, evaluated left to right: the library's bits) in delay cells per CPI, negative for
+    an approaching target.  ``spacing``: the distance between CPI starts in CPI lengths.  ``dims``: anything with
+    ``doppler``, ``n_corr`` and ``n_doppler_bins`` (the oracle's ``ambiguity_dims``), or an :class:`Ambiguity`, whose
+    table the library itself computes."""
+    fc, spacing = float(fc), float(spacing)
+    if not math.isfinite(fc) or not fc > 0.0:
+        raise ValueError("the carrier frequency must be finite and positive")
+    if not math.isfinite(spacing) or not spacing > 0.0:
+        raise ValueError("the CPI spacing must be finite and positive")
+    if isinstance(dims, Ambiguity):
+        walk = np.zeros(dims.dims.n_doppler_bins, dtype=np.float64)
+        check(dims._L.blah2hip_nci_walk_table(dims._h, fc, spacing, _ptr(walk)))
+        return walk
+    doppler = np.asarray(dims.doppler, dtype=np.float64)
+    return -doppler * float(dims.n_corr) * float(dims.n_doppler_bins) * spacing / fc
+
+
+def track_tables(walk, q, window):
+    """The integer tables ``blah2hip_nci_set_tracks`` builds, ``(jr, s)`` as int32 ``[K, W, nD]``:
+    ``r = rint(q[k] * a)``, ``jr = j - r`` (-1 where it leaves ``[0, nD)``, with ``s`` 0 there) and
+    ``s = rint(-0.5 * a * (walk[j] + walk[jr]))``, in fp64 with ties to even.  ``walk``: ``[nD]``; ``q``: the bank (None:
+    ``{0}``)."""
+    walk = np.asarray(walk, dtype=np.float64)
+    q = np.zeros(1) if q is None or np.size(q) == 0 else np.atleast_1d(np.asarray(q, dtype=np.float64))
+    if walk.ndim != 1 or q.ndim != 1:
+        raise ValueError("walk must be [nD] and q a bank of rates")
+    if not (np.isfinite(walk).all() and np.isfinite(q).all()):
+        raise ValueError("walk and q must be finite")
+    nD, W = walk.size, int(window)
+    j = np.arange(nD, dtype=np.int64)
+    jr = np.full((q.size, W, nD), -1, dtype=np.int32)
+    s = np.zeros((q.size, W, nD), dtype=np.int32)
+    for k in range(q.size):
+        for a in range(W):
+            src = j - int(np.rint(q[k] * float(a)))
+            ok = (src >= 0) & (src < nD)
+            sh = np.rint(-0.5 * float(a) * (walk[j[ok]] + walk[src[ok]]))
+            if sh.size and np.abs(sh).max() > _lib.MAX_TRACK_SHIFT:
+                raise ValueError(f"a shift above {_lib.MAX_TRACK_SHIFT} cells")
+            jr[k, a, ok] = src[ok]
+            s[k, a, ok] = sh
+    return jr, s
+
+
+def integrate_tracks(maps, walk, q, w=None, window=1, hop=None):
+    """blah2hip_nci_process_tracks_dev restated in fp64 NumPy for a fresh integrator.  ``maps``: complex
+    ``[K, n_cpi, nD, nC]``; ``walk``: ``[nD]`` delay cells per CPI (None: zero); ``q``: the bank of Doppler rows per CPI
+    (None: ``{0}``); ``w``, ``window``, ``hop`` as in :func:`integrate_maps`.  For every window end ``g`` of
+    :func:`integrate_ends`: ``S_k[j, d] = sum_a p[g - a][jr, d + s]`` over the ages ``a = W - 1 .. 0`` with the tables of
+    :func:`track_tables`, a term outside the map contributing zero.  Returns ``(levels, index, sums)``:
+    ``sqrt(scale S_k*)`` float64 ``[n_out, nD, nC]``, ``k*`` uint8 (the smallest ``k`` with the largest sum; NaN sums never
+    win against ``S_0``) and every ``S_k`` ``[K_bank, n_out, nD, nC]``."""
+    m = np.asarray(maps).astype(np.complex128)
+    if m.ndim != 4:
+        raise ValueError("maps must be [K, n_cpi, nD, nC]")
+    K, n_cpi, nD, nC = m.shape
+    W = int(window)
+    wk = np.ones(K, dtype=np.float32) if w is None else np.asarray(w, dtype=np.float32)
+    if wk.shape != (K,):
+        raise ValueError("w must hold one weight per channel")
+    walk = np.zeros(nD) if walk is None else np.asarray(walk, dtype=np.float64)
+    if walk.shape != (nD,):
+        raise ValueError("walk must hold one entry per Doppler row")
+    jr, s = track_tables(walk, q, W)
+    Kb = jr.shape[0]
+    scale = float(np.float32(1.0 / (W * wk.astype(np.float64).sum())))
+    ends = integrate_ends(n_cpi, W, hop)
+    d = np.arange(nC, dtype=np.int64)
+    with np.errstate(all="ignore"):
+        p = np.zeros(m.shape[1:])
+        for k in range(K):
+            p = p + float(wk[k]) * (m[k].real ** 2 + m[k].imag ** 2)
+        sums = np.zeros((Kb, len(ends), nD, nC))
+        for o, g in enumerate(ends):
+            for k in range(Kb):
+                acc = np.zeros((nD, nC))
+                for a in range(W - 1, -1, -1):
+                    col = d[None, :] + s[k, a].astype(np.int64)[:, None]
+                    ok = (jr[k, a] >= 0)[:, None] & (col >= 0) & (col < nC)
+                    src = p[g - a][np.clip(jr[k, a], 0, nD - 1)[:, None], np.clip(col, 0, nC - 1)]
+                    acc = acc + np.where(ok, src, 0.0)
+                sums[k, o] = acc
+        index = np.zeros((len(ends), nD, nC), dtype=np.uint8)
+        best = sums[0].copy() if Kb else np.zeros((0, nD, nC))
+        for k in range(1, Kb):
+            win = sums[k] > best
+            best = np.where(win, sums[k], best)
+            index[win] = k
+        levels = np.sqrt(scale * best)
+    return levels, index, sums
+
+
 # a_0 .. a_P of the cosine-sum windows w[i] = sum_p (-1)^p a_p cos(2 pi p i / n): blah2hip_doppler_taper's table
 TAPER_COEFFS = {
     "none": (1.0,),
@@ -1554,6 +1648,43 @@ class MapIntegrator:
         self._h, self._L, self.amb = h, amb._L, amb
         self.n_surv, self.window, self.hop = int(n_surv), int(window), int(hop)
         self.looks = self.n_surv * self.window
+        self.n_rates = 0  # hypotheses of the tracks that are set (0: none, the plain window sum)
+
+    def set_tracks(self, walk=None, q=None, max_cpi=1):
+        """Integrate along tracks from now on (blah2hip_nci_set_tracks): ``walk [n_doppler]`` delay cells an echo of each row
+        moves later per CPI (None: zero; :func:`nci_walk_table` is the physical table), ``q`` the bank of Doppler rows it
+        rises per CPI (None: ``{0}``), ``max_cpi`` the most CPIs one ``process_tracks_dev`` call brings.  Waits for the
+        device, resets the counter.  A cell of the output is the largest of ``n_rates`` sums of ``looks`` looks: make the
+        detector with ``looks`` and ``pfa / n_rates``."""
+        nD = self.amb.dims.n_doppler_bins
+        wp = qp = None
+        n_q = 0
+        if walk is not None:
+            walk = np.ascontiguousarray(walk, dtype=np.float64)
+            if walk.shape != (nD,):
+                raise ValueError(f"walk must hold {nD} entries, one per Doppler row")
+            wp = _ptr(walk)
+        if q is not None and np.size(q):
+            q = np.ascontiguousarray(np.atleast_1d(q), dtype=np.float64)
+            if q.ndim != 1:
+                raise ValueError("q must be a bank of rates")
+            qp, n_q = _ptr(q), q.size
+        check(self._L.blah2hip_nci_set_tracks(self._h, wp, qp, n_q, int(max_cpi)))
+        self.n_rates = max(n_q, 1)
+
+    def process_tracks_dev(self, d_map, n_cpi, d_out_map, d_out_index, d_out_metrics, out_cap, w=None, stream=0):
+        """``process_dev`` along the tracks (blah2hip_nci_process_tracks_dev): the same arguments and return value, with
+        ``d_out_index`` the uint8 plane ``[n_out][n_doppler][n_delay]`` of winning hypotheses, or None."""
+        wp = None
+        if w is not None:
+            w = np.ascontiguousarray(w, dtype=np.float32)
+            if w.shape != (self.n_surv,):
+                raise ValueError("w must hold one weight per channel")
+            wp = _ptr(w)
+        n, f = C.c_uint32(0), C.c_uint64(0)
+        check(self._L.blah2hip_nci_process_tracks_dev(self._h, d_map, int(n_cpi), wp, d_out_map, d_out_index, d_out_metrics,
+                                                      int(out_cap), C.byref(n), C.byref(f), stream))
+        return n.value, f.value
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1579,11 +1710,13 @@ class MapIntegrator:
 
     def get_timing(self):
         """``{"nci": (ms, launches)}`` since the last call (synchronises); the metrics kernel behind it counts under the
-        ambiguity handle's ``"metrics"``."""
+        ambiguity handle's ``"metrics"``.  With tracks set also ``"track_power"`` and ``"track_sum"``, the two kernels of
+        ``process_tracks_dev``."""
         ms = np.zeros(_lib.NK_COUNT, dtype=np.float64)
         cnt = np.zeros(_lib.NK_COUNT, dtype=np.uint32)
         check(self._L.blah2hip_nci_get_timing(self._h, _ptr(ms), _ptr(cnt)))
-        return {name: (float(ms[k]), int(cnt[k])) for k, name in _lib.NCI_KERNEL_NAMES.items()}
+        return {name: (float(ms[k]), int(cnt[k])) for k, name in _lib.NCI_KERNEL_NAMES.items()
+                if k == _lib.NK_NCI or self.n_rates}
 
     def count(self, n_cpi):
         """``(n_out, first_end)`` the next ``process_dev`` of ``n_cpi`` CPIs will report; changes nothing."""
@@ -1632,7 +1765,10 @@ class MapIntegrator:
                 bufs.append(p)
             d_in, d_out, d_met = bufs
             check(L.blah2hip_ctx_h2d(ctx, d_in, _ptr(data), data.nbytes))
-            n_out, first = self.process_dev(d_in, n_cpi, d_out, d_met, n_out, w, L.blah2hip_ctx_stream(ctx))
+            if self.n_rates:  # tracks are set: the window sums along them (the index plane is not returned)
+                n_out, first = self.process_tracks_dev(d_in, n_cpi, d_out, None, d_met, n_out, w, L.blah2hip_ctx_stream(ctx))
+            else:
+                n_out, first = self.process_dev(d_in, n_cpi, d_out, d_met, n_out, w, L.blah2hip_ctx_stream(ctx))
             if n_out:
                 check(L.blah2hip_ctx_d2h(ctx, _ptr(out), d_out, out.nbytes))
                 check(L.blah2hip_ctx_d2h(ctx, _ptr(met), d_met, met.nbytes))

@@ -602,6 +602,14 @@ class GpuChain:
     batches round-robin see no consecutive CPIs across a batch's end: :meth:`shard_check` then asks for H == W and a batch
     of whole windows, and every batch starts at count 0.  Without the key the chain is the one described above.
 
+    ``cfg["integrate"]["tracks"] = {"fc": HZ, "rate": QMAX | {"max": QMAX, "step": S}}`` takes the window sums ALONG THE
+    TRACKS of the echoes (``MapIntegrator.set_tracks`` / ``process_tracks_dev``): the walk in delay between CPIs for the
+    carrier ``fc`` (``blah2_amd.nci_walk_table``, back-to-back CPIs) under the bank ``blah2_amd.rate_bank(QMAX, S)`` of
+    Doppler drifts in rows per CPI -- without ``rate`` the bank {0}, the walk only.  The detector is made with
+    ``looks = W`` and ``pfa / K`` for the K hypotheses (the union bound).  ValueError, naming the key: no ``fc`` or one that
+    is not positive and finite, a bank above 16 rates, a table the library refuses.  The multi-rank rule is unchanged.
+    Without the key nothing new is launched.
+
     ``cfg["detection"]["cfar"] = "os"`` (default "ca") builds :class:`blah2_amd.OsCfarDetector1D` at
     ``cfg["detection"]["rank"]`` (default 0.75) in the place of ``CfarDetector1D``, for the integrator's looks as well; the
     hit buffers, the finisher and the results are the same.
@@ -765,6 +773,31 @@ class GpuChain:
             self._g = 0              # CPIs the integrator has been handed since its last reset
             self._ok_tail = []       # filter flags of the last W - 1 CPIs collected
             looks = {"looks": self.nci.looks}
+            # integrate: {tracks: {fc: HZ, rate: QMAX | {max: QMAX, step: S}}}: the window sums along the walk between CPIs
+            # for the carrier fc, under the bank of Doppler drifts in rows per CPI (no rate: the bank {0}, the walk only)
+            trk = int_c.get("tracks")
+            if trk is not None and trk is not False:
+                try:
+                    if not isinstance(trk, dict) or trk.get("fc") is None:
+                        raise ValueError("needs the carrier frequency: {fc: HZ}")
+                    fc_t = float(trk["fc"])
+                    if not math.isfinite(fc_t) or not fc_t > 0.0:
+                        raise ValueError(f"fc = {fc_t!r} is not a positive, finite frequency")
+                    rate_t = trk.get("rate")
+                    bank = None
+                    if rate_t is not None and rate_t is not False:
+                        if isinstance(rate_t, bool):
+                            raise ValueError("rate: QMAX or {max: QMAX, step: S}")
+                        q_max, step = (rate_t.get("max"), rate_t.get("step", 1.0)) if isinstance(rate_t, dict) else (rate_t, 1.0)
+                        if q_max is None:
+                            raise ValueError("rate: {max: QMAX, step: S} needs max")
+                        bank = blah2_amd.rate_bank(float(q_max), float(step))
+                    self.nci.set_tracks(blah2_amd.nci_walk_table(self.amb, fc_t), bank, max_cpi=B)
+                except (TypeError, ValueError, blah2_amd.Blah2HipError) as e:
+                    self.nci.close()
+                    self.amb.close()
+                    raise ValueError(f"integrate.tracks = {trk!r}: {e}") from None
+        self.nci_tracks = self.nci is not None and self.nci.n_rates > 0
         if det_c.get("enable", False):
             # detection: {cfar: ca | os, rank: 0.75}: the cell-averaging detector of the reference (default), or the
             # ordered-statistic one at that rank on the same window; both leave the same hit lists
@@ -774,6 +807,8 @@ class GpuChain:
             # a cell of the rate bank's map is the strongest of K hypotheses, which multiplies the false-alarm rate by at
             # most K: the thresholds are made for pfa / K (the union bound)
             pfa = det_c["pfa"] if self.rates is None else det_c["pfa"] / len(self.rates)
+            if self.nci_tracks:  # ... and of the integrator's hypotheses along the tracks, likewise
+                pfa = pfa / self.nci.n_rates
             if kind == "os":
                 self.cfar = blah2_amd.OsCfarDetector1D(pfa, det_c["nGuard"], det_c["nTrain"], det_c["minDelay"],
                                                        det_c["minDoppler"], rank=float(det_c.get("rank", 0.75)), **looks)
@@ -976,8 +1011,12 @@ class GpuChain:
             if self.nci is not None:
                 if self._per_batch:
                     self.reset_integrator()
-                n_maps, first = self.nci.process_dev(maps.data_ptr(), cnt, slot["d_imap"].data_ptr(), slot["d_imet"].data_ptr(),
-                                                     self.batch, None, st)
+                if self.nci_tracks:
+                    n_maps, first = self.nci.process_tracks_dev(maps.data_ptr(), cnt, slot["d_imap"].data_ptr(), None,
+                                                                slot["d_imet"].data_ptr(), self.batch, None, st)
+                else:
+                    n_maps, first = self.nci.process_dev(maps.data_ptr(), cnt, slot["d_imap"].data_ptr(), slot["d_imet"].data_ptr(),
+                                                         self.batch, None, st)
                 slot["nci"] = (self._g, n_maps, first)
                 self._g += cnt
                 maps, mets = slot["d_imap"], slot["d_imet"]
@@ -1238,6 +1277,11 @@ def main(argv=None):
                     help="non-coherent integration of the maps over a sliding window of W consecutive CPIs (1 ... 16), a "
                          "window every H CPIs (default 1); the detector's thresholds are made for W looks.  CPIs at which no "
                          "window ends give no frame.  Several ranks: H == W and --batch a multiple of W")
+    ap.add_argument("--integrate-tracks", nargs="?", const=True, default=None, metavar="QMAX[:STEP]",
+                    help="with --integrate: take the window sums along the echoes' tracks -- the walk in delay between CPIs "
+                         "for the carrier capture.fc of the config, under the bank -QMAX ... QMAX of Doppler drifts in rows "
+                         "per CPI in steps of STEP (default 1), at most 16 of them; without a value the walk only.  The "
+                         "detector is made with W looks and pfa / K for the K hypotheses")
     ap.add_argument("--doppler-window", default=None, metavar="NAME[:norm]",
                     help="Doppler taper behind the ambiguity stage: none, hann, hamming, blackman, blackmanharris, nuttall or "
                          "flattop; :norm divides the taps by a_0 (an echo on a Doppler bin keeps its amplitude); overrides "
@@ -1288,6 +1332,23 @@ def main(argv=None):
         except ValueError:
             ap.error("--integrate takes W or W:H, a window and a hop in CPIs, both >= 1")
         cfg["integrate"] = {"window": wh_[0], "hop": wh_[1] if len(wh_) == 2 else 1}
+    if a.integrate_tracks is not None:
+        if not cfg.get("integrate"):
+            ap.error("--integrate-tracks belongs to --integrate W[:H]")
+        trk_ = {"fc": (cfg["integrate"].get("tracks") or {}).get("fc", y["capture"].get("fc"))}
+        if trk_["fc"] is None:
+            ap.error("--integrate-tracks needs a carrier: capture.fc in the config")
+        if a.integrate_tracks is not True:
+            try:
+                qs_ = [float(v) for v in a.integrate_tracks.split(":")]
+                if not 1 <= len(qs_) <= 2:
+                    raise ValueError
+                from .process import rate_bank
+                rate_bank(*qs_)
+            except ValueError:
+                ap.error("--integrate-tracks takes QMAX or QMAX:STEP, QMAX >= 0 and STEP > 0 in Doppler rows per CPI, at most 16 hypotheses")
+            trk_["rate"] = {"max": qs_[0], "step": qs_[1] if len(qs_) == 2 else 1.0}
+        cfg["integrate"] = dict(cfg["integrate"], tracks=trk_)
     if a.doppler_window is not None:
         from .process import TAPER_COEFFS
         name_, _, norm_ = a.doppler_window.lower().partition(":")

@@ -260,6 +260,8 @@ int blah2hip_amb_set_option(blah2hip_amb_t h, int option, int64_t value);
 #define BLAH2HIP_INFO_TAPER_GRID 17            /* workgroups per map of the last blah2hip_amb_taper_dev launch */
 #define BLAH2HIP_INFO_MIGRATE_GRID 18          /* workgroups per map of the last blah2hip_amb_migrate_dev launch */
 #define BLAH2HIP_INFO_RATE_GRID 19             /* workgroups per map of the last blah2hip_amb_rate_bank_dev launch */
+#define BLAH2HIP_INFO_TRACK_GRID 20            /* workgroups per output map of the last track_sum_kernel launch (blah2hip_nci_process_tracks_dev) */
+#define BLAH2HIP_INFO_TRACK_MAX_SHIFT 21       /* the largest |s(j,k,a)| of the table the last blah2hip_nci_set_tracks on this handle's maps built */
 int blah2hip_amb_get_info(blah2hip_amb_t h, int key, int64_t *value);
 
 /* Ambiguity::process + Map::set_metrics on host buffers (blah2.cpp:278-279).
@@ -544,7 +546,7 @@ int blah2hip_nci_count(blah2hip_nci_t n, uint32_t n_cpi, uint32_t *n_out, uint64
  * BLAH2HIP_ERR_INVALID, with nothing enqueued and the counter unchanged: a NULL handle, n_cpi == 0, n_surv * n_cpi above
  * max_batch, n_out above out_cap or above max_batch, a weight that is negative or not finite, weights that add up to 0, a
  * NULL output while n_out > 0, a map that is not 8-byte aligned, an output that overlaps the input maps (the handle's
- * internal map when d_map is NULL). */
+ * internal map when d_map is NULL), an integrator with tracks set (blah2hip_nci_set_tracks: its history lives in the ring). */
 int blah2hip_nci_process_dev(blah2hip_nci_t n, const void *d_map, uint32_t n_cpi, const float *w,
                              void *d_out_map, double *d_out_metrics, uint32_t out_cap,
                              uint32_t *n_out, uint64_t *first_end, void *stream);
@@ -676,6 +678,69 @@ int blah2hip_amb_set_rates(blah2hip_amb_t h, const double *q, uint32_t n_rates);
  * set"; no bank set; an index plane that overlaps a map or the metrics. */
 int blah2hip_amb_rate_bank_dev(blah2hip_amb_t h, const void *d_map, uint32_t n_maps, void *d_out_map, uint8_t *d_out_index,
                                double *d_out_metrics, void *stream);
+
+/* ---- Integration along tracks (no reference counterpart: blah2 detects on single maps) ----
+ * The integrator above sums a window of W CPIs IN THE SAME CELL.  Between CPIs an echo walks in delay (W times further than
+ * inside one CPI, the migration block above) and, where it accelerates, climbs in Doppler (the rate bank above), so the
+ * window sum of a fast or accelerating echo is a streak with a single look's level in every cell.  With tracks set, the
+ * window sum is taken along the path an echo of each cell would have come, for a bank of Doppler-drift hypotheses, and the
+ * strongest hypothesis is kept per cell.  p[c][j][d] = sum_k w_k |M_k[c][j][d]|^2 exactly as above (nci_power's fp32
+ * arithmetic and order; c the CPI count, j the Doppler row, d the delay column).  With
+ *   walk[j]   j = 0 .. n_doppler - 1: fp64 delay cells by which an echo in row j moves LATER per CPI (negative for an
+ *             approaching target); any finite table,
+ *   q[k]      k = 0 .. K - 1, K <= BLAH2HIP_MAX_RATES: fp64 Doppler rows the echo RISES per CPI (rows ascend in Doppler, as
+ *             the handle's axis does),
+ *   a         the age 0 .. W - 1: CPI g - a of the window that ends at g,
+ * the tables are built in fp64 ON THE HOST and uploaded as int32 pairs [K][W][n_doppler]:
+ *   r(k,a)    = (int) rint(q[k] * (double)a)
+ *   jr(j,k,a) = j - r(k,a)                      no wrap: a row outside [0, n_doppler) contributes zero
+ *   s(j,k,a)  = (int) rint(-0.5 * (double)a * (walk[j] + walk[jr]))    ties to even; the mean of the two rows' walks
+ *   S_k[g][j][d] = sum_{a = W-1 .. 0, oldest first} [row valid][0 <= d+s < n_delay] p[g-a][jr][d+s]   fp32, __fadd_rn, from
+ *                  the oldest valid term (a term that is left out adds +0, which changes no bit)
+ *   k*  = 0 at the start; k replaces it only when S_k > S_k* (fp32 compare): the smallest k with the largest sum
+ *   out[g][j][d] = ( sqrtf(scale * S_k*), 0 ),  index[g][j][d] = (uint8) k*,  scale = 1 / (W sum_k w_k) as above
+ * a = 0 is the cell itself (s = 0, jr = j): an echo is reported at its position in the NEWEST CPI.  A term outside the map
+ * contributes zero and scale does not change: cells near the edges are lower, as in migrate_kernel.  A NaN S_0 stays, with
+ * index 0; a NaN S_k with k > 0 never wins (the compare is false).  A NaN or Inf cell of p reaches exactly the outputs whose
+ * tracks pass through it.  With walk == 0 and the bank {0} the output maps are blah2hip_nci_process_dev's bit for bit (the
+ * same additions in the same order); the metrics agree to 1e-3 dB only, because the partials' grid differs.  The error of a
+ * cell against the fp64 value of the hypothesis the device names is the integrator's bound, (n_surv W + 8) 2^-24 of the cell:
+ * all terms are non-negative and the selection adds no rounding.  Where two hypotheses lie closer than that, the device
+ * may name either.
+ * Statistics: under noise a cell is the largest of K Gamma(L) sums, L = n_surv W.  Make the detector with looks = L and
+ * pfa / K (the union bound, as for the rate bank). */
+#define BLAH2HIP_MAX_TRACK_SHIFT 1048576 /* the largest |s(j,k,a)| a table may hold, 2^20: the table is int32 and the kernel forms d + s in
+                                          * int32, which cannot overflow below that (n_delay at or above 2^31 - 2^20 is refused too) */
+/* Host only: the physical walk of the handle's own Doppler axis, walk[j] = -doppler[j] * n_corr * n_doppler * cpi_spacing / fc
+ * for j = 0 .. n_doppler - 1 (evaluated left to right in fp64).  cpi_spacing: the distance between CPI starts in CPI lengths,
+ * 1 for back-to-back CPIs.  BLAH2HIP_ERR_INVALID: a NULL argument, fc or cpi_spacing not finite or not positive. */
+int blah2hip_nci_walk_table(blah2hip_amb_t amb, double fc, double cpi_spacing, double *walk);
+/* Sets the tracks of an integrator: builds the (jr, s) tables from the HOST arrays walk [n_doppler] (NULL: all zero) and
+ * q [n_rates] (NULL or n_rates 0: the bank {0}), uploads them, and allocates a ring of W - 1 + max_cpi fp32 planes of p,
+ * indexed by g mod (W - 1 + max_cpi), in the place of the history planes.  max_cpi: the most CPIs one
+ * blah2hip_nci_process_tracks_dev call will bring.  The call waits for the device (like blah2hip_amb_set_migration) and resets the
+ * counter.  Duplicate rates are allowed; the lower index wins ties.  From then on the integrator refuses
+ * blah2hip_nci_process_dev (its history lives in the ring); tracks cannot be cleared.
+ * BLAH2HIP_ERR_INVALID, with what was set left as it was: a NULL handle, an entry that is not finite, n_rates above
+ * BLAH2HIP_MAX_RATES, |q[k]| (W - 1) >= n_doppler, max_cpi == 0, n_surv * max_cpi above max_batch, a largest |s| above
+ * BLAH2HIP_MAX_TRACK_SHIFT.  (BLAH2HIP_ERR_UNSUPPORTED: fewer metrics partials per map than track_sum_kernel has workgroups,
+ * ceil(n_delay / 64) ceil(n_doppler / 8), one per 512 cells; no geometry the engine plans today.) */
+int blah2hip_nci_set_tracks(blah2hip_nci_t n, const double *walk, const double *q, uint32_t n_rates, uint32_t max_cpi);
+/* The next n_cpi CPIs along the tracks: blah2hip_nci_process_dev's contract throughout -- arguments, counting, n_out == 0 while
+ * the window fills, enqueue only (no allocation, upload or synchronisation; can be captured in a graph), the same refusals
+ * with nothing written and the counter unchanged -- with d_out_index [n_out][n_doppler][n_delay] uint8, the winning
+ * hypothesis of every cell, which may be NULL.  blah2hip_nci_count and _reset work unchanged.
+ * Two kernels: track_power_kernel (BLAH2HIP_NK_TRACK_POWER) reads every input cell once and writes p of the call's CPIs into
+ * the ring; track_sum_kernel (BLAH2HIP_NK_TRACK_SUM) takes the window sums -- one launch for all n_out windows, reading the
+ * (jr, s) pairs by scalar loads and the ring by 4-byte-per-lane loads at d + s -- and leaves one metrics partial per workgroup
+ * and output map, which metrics_kernel folds in index order (no floating-point atomics).  The workgroups per CPI group and
+ * per output map (BLAH2HIP_INFO_TRACK_GRID) depend on the geometry alone, never on n_cpi, the counter or n_out: outputs,
+ * index and metrics are the same bits however the CPIs are cut into calls.
+ * BLAH2HIP_ERR_INVALID in addition: no tracks set, n_cpi above the max_cpi of blah2hip_nci_set_tracks, an index plane that
+ * overlaps a map or the metrics. */
+int blah2hip_nci_process_tracks_dev(blah2hip_nci_t n, const void *d_map, uint32_t n_cpi, const float *w,
+                                    void *d_out_map, uint8_t *d_out_index, double *d_out_metrics, uint32_t out_cap,
+                                    uint32_t *n_out, uint64_t *first_end, void *stream);
 
 /* ---- CfarDetector1D (CfarDetector1D.h:46-55) ---------------------------- */
 /* dev: d_map/d_metrics as written by blah2hip_amb_process_dev (NULL = the
@@ -1110,7 +1175,9 @@ int blah2hip_clutter_get_timing(blah2hip_clutter_t h, double *ms_total, uint32_t
 /* the same for the integrator's kernel, on the integrator: its launches are bracketed there and the ambiguity handle's
  * BLAH2HIP_K_* slots stay as they are (the metrics_kernel behind it counts under the ambiguity handle's BLAH2HIP_K_METRICS) */
 #define BLAH2HIP_NK_NCI 0 /* nci_kernel (blah2hip_nci_process_dev) */
-#define BLAH2HIP_NK_COUNT 1
+#define BLAH2HIP_NK_TRACK_POWER 1 /* track_power_kernel (blah2hip_nci_process_tracks_dev) */
+#define BLAH2HIP_NK_TRACK_SUM 2   /* track_sum_kernel (blah2hip_nci_process_tracks_dev) */
+#define BLAH2HIP_NK_COUNT 3
 int blah2hip_nci_set_timing(blah2hip_nci_t n, int enable);
 int blah2hip_nci_get_timing(blah2hip_nci_t n, double *ms_total, uint32_t *launches);
 
