@@ -7,7 +7,10 @@ No reference counterpart; the checks are
     columns and leak compensation off, on six geometries (65 x 44; 65 x 45, an odd cell count; 129 x 111, two column strips;
     2049 x 40, 65 blocks of pulses; the explicit even 64 bins; asymmetric Doppler limits) and five tables (physical; reversed;
     walks beyond the map's last column; exactly +-BLAH2HIP_MAX_MIGRATION; neighbouring rows with opposite walks), 3 CPIs a
-    call with NaN gaps between the planes' CPIs, in place and out of place, the outputs between guard words;
+    call with NaN gaps between the planes' CPIs, in place and out of place, the outputs between guard words; and on five
+    geometries off the grid of 32 pulses (21 x 64, 48 x 65, 81 x 200, 95 x 64, 7 x 64: last blocks of 21, 16, 17, 31 and 7
+    pulses, last row groups of as many rows, a strip of exactly 64 columns, one of a single column, two interior strips),
+    whose reach tests/test_migrate_model.py proves;
   * zero-shift rows are the process call's bits (hot columns and leak compensation forced on); two calls give the same bits;
     map 0 of a call of one map is map 0 of a call of three;
   * metrics within 1e-3 dB of fp64 Map::set_metrics of the device's own output, with a peak planted along a migrated row's walk;
@@ -20,6 +23,11 @@ rows, 1.2e-6 .. 2.2e-6 at 2049 x 40, the same in place and out of place.  Metric
 maxPower 6.5e-7 dB from fp64 set_metrics of the device's own cells.  Scene: 61.699 dB on the device and in the restatement,
 45.1 dB at that cell of the standard map.  With both options forced on, the scene's direct path still does not pass the
 hot-column test (0 columns rewritten): the bit-for-bit check of the zero-shift rows holds whatever wrote them.  No defect was found.
+Off the grid of 32 pulses: 1.6e-7 .. 5.0e-7 of the peak on the 19 cases of the five new geometries (largest: 95 x 64, ``limit``),
+the same in place and out of place; the planted peak at (80, 150) of 81 x 200: noisePower 4.3e-7 dB, maxPower 6.7e-7 dB; two
+calls and one map of three give equal bits at 95 x 64.  A library built with pulses 16 .. 31 of a partial block left out of the
+staging passed every case from before and failed six of the new ones (21 x 64, 81 x 200 and 95 x 64 with runs of more than 16
+pulses).  No defect was found.
 """
 import numpy as np
 import pytest
@@ -144,9 +152,11 @@ def check_metrics(out, met, tag):
 
 
 # ---- 1. cells ---------------------------------------------------------------------------------------------------------------
-CELLS = {"g65x44": 4, "g65x45": 4, "g129x111": 9, "g2049x40": 15, "g64x44": 4, "gasym": 4}
+CELLS = MS.CELLS
 TABLES = ("physical", "reversed", "beyond", "limit", "jagged")
-CASES = [(g, t) for g in CELLS for t in TABLES if g != "g2049x40" or t in ("physical", "limit", "jagged")]
+CASES = [(g, t) for g in CELLS if g not in MS.EDGE_GEOMS for t in TABLES if g != "g2049x40" or t in ("physical", "limit", "jagged")]
+# Doppler lengths off the 32-pulse grid; tests/test_migrate_model.py shows which block, run and window edges each of them runs
+CASES += MS.EDGE_MIGRATE_CASES
 
 
 @pytest.mark.parametrize("geom,table", CASES, ids=[f"{g}-{t}" for g, t in CASES])
@@ -202,8 +212,16 @@ def test_zero_shift_rows_keep_the_hot_column_and_leak_values(b2, torch):
 
 
 def test_equal_inputs_give_equal_bits_at_every_n_maps(b2, torch):
-    dims, x, y, stride, R = inputs(b2, "g65x45", 3, seed=55)
-    amb = handle(b2, "g65x45")
+    equal_bits_at_every_n_maps(b2, torch, "g65x45")
+
+
+def test_equal_inputs_give_equal_bits_with_a_last_block_of_31_pulses(b2, torch):
+    equal_bits_at_every_n_maps(b2, torch, "g95x64")  # and a last row group of 31 rows
+
+
+def equal_bits_at_every_n_maps(b2, torch, geom):
+    dims, x, y, stride, R = inputs(b2, geom, 3, seed=55)
+    amb = handle(b2, geom)
     amb.set_migration(MS.tables(dims, 4)["physical"])
     maps, _, _ = process(torch, b2, amb, x, y, stride, 3)
     a, ma = migrate(torch, amb, maps, 3, False)
@@ -217,14 +235,20 @@ def test_equal_inputs_give_equal_bits_at_every_n_maps(b2, torch):
 
 # ---- 3. metrics -------------------------------------------------------------------------------------------------------------
 def test_metrics_with_a_peak_planted_along_a_walk(b2, torch):
-    geom = "g129x111"
+    planted_peak(b2, torch, "g129x111", 3, 70)  # a migrated row, a column of the second strip
+
+
+def test_metrics_with_a_peak_planted_in_the_last_row_group_and_the_third_strip(b2, torch):
+    planted_peak(b2, torch, "g81x200", 80, 150)  # 81 rows: the last block has 17 pulses, the last row group 17 rows
+
+
+def planted_peak(b2, torch, geom, row, col):
     dims = MS.dims_of(geom)
     nD, nC = dims.n_doppler_bins, dims.n_corr
     x, y, stride = MS.impulse_cpis(dims, 2, seed=9)
     h = MS.tables(dims, CELLS[geom])["physical"]
     s = b2.migration_shifts(h, nD)
-    row, col = 3, 70  # a migrated row, a column of the second strip
-    assert s[row, 0] != 0
+    assert s[row, 0] != 0 and col + s[row].min() >= 0 and col + s[row].max() < dims.n_delay_bins
     i = np.arange(nD)
     w = np.exp(-2j * np.pi * ((i * ((row + nD // 2 + 1) % nD)) % nD) / nD)
     y = y.copy()
@@ -239,7 +263,7 @@ def test_metrics_with_a_peak_planted_along_a_walk(b2, torch):
     check_metrics(out, met, "planted")
     for c in range(2):
         noise, peak = MS.set_metrics64(out[c])
-        print(f"planted peak, map {c}: noisePower off by {abs(met[c, 0] - noise):.2e} dB, maxPower by {abs(met[c, 1] - peak):.2e} dB")
+        print(f"planted peak {geom} ({row}, {col}), map {c}: noisePower off by {abs(met[c, 0] - noise):.2e} dB, maxPower by {abs(met[c, 1] - peak):.2e} dB")
 
 
 # ---- 4. several channels ----------------------------------------------------------------------------------------------------

@@ -10,8 +10,15 @@ to these restatements.
     of rint, centre off by one pulse, no shift -- misses PEAK_TOL by at least 10 x, so the GPU gate tells them apart.
   * The moving-echo scene (b) on the restatement: the compensated level at (62, 23) is at least the static echo's - 1.5 dB, the
     standard map's row maximum is at most the static echo's - 10 dB, and the compensated map's global argmax is (62, 23).
+  * Doppler lengths off the grid of 32 pulses (MS.EDGE_GEOMS).  ``reach`` shows that the GPU cases on them run blocks of 7, 16, 17,
+    21 and 31 pulses, a run of 17 .. 31 pulses, a wide window staged in runs whose last is short, a window that leaves the map on
+    both sides at once and an interior strip's window that leaves it on neither.  Five block-edge mutants -- partial last block
+    dropped, padded with its last pulse, its pulses 16 .. 31 dropped; a partial last row group on the last row's walk; reads
+    across a strip seam zero -- each miss PEAK_TOL by 100 x or more (derived: one pulse is at least 0.5 against a peak of at most
+    1.5 nD) on every GPU case where they change a read that lands in the map; the variant table above also runs at 95 x 64.
 
-Measured here.  Zero-shift rows against ambiguity_process: 4.7e-16 of the peak.  fp32 emulation against fp64: 1.7e-7 of the peak
+Measured here.  Block-edge mutants: the smallest miss is 4.6e-2 of the peak, 4645 x the gate (the last pulse repeated at 95 x 64,
+physical table).  Zero-shift rows against ambiguity_process: 4.7e-16 of the peak.  fp32 emulation against fp64: 1.7e-7 of the peak
 at 65 x 44 (walk 4), 2.6e-7 at 2049 x 40 (walk 15, a spread of rows).  Smallest miss of a wrong variant: 0.14 of the peak (centre
 off by one pulse at 2049 x 40), 0.45 at 65 x 44.  Scene (b), seed 5: the same echo without walk 62.7 dB; standard map 45.1 dB at the
 cell and 48.3 dB at the row's maximum (-14.4 dB); compensated map 61.7 dB at (62, 23) (-1.0 dB), which is its global argmax.
@@ -169,7 +176,7 @@ def variant_sum(R, h, which, rows):
     return doppler_sum(R, s, rows)
 
 
-@pytest.mark.parametrize("geom,cells", [("g65x44", 4), ("g2049x40", 15)])
+@pytest.mark.parametrize("geom,cells", [("g65x44", 4), ("g2049x40", 15), ("g95x64", 4)])
 def test_the_gate_tells_every_wrong_variant_from_the_kernel_arithmetic(geom, cells):
     dims = MS.dims_of(geom)
     x, y, _ = MS.impulse_cpis(dims, 1, seed=21)
@@ -194,6 +201,83 @@ def test_the_gate_tells_every_wrong_variant_from_the_kernel_arithmetic(geom, cel
         miss = np.max(np.abs(got - ref)) / peak
         print(f"{geom}: variant {which} misses by {miss:.3f} of the peak")
         assert miss >= 10 * PEAK_TOL, which
+
+
+# ---- Doppler lengths and windows off the 32-pulse grid ------------------------------------------------------------------------
+def test_reach_restates_the_window_arithmetic():
+    """reach() on cases worked out by hand from migrate_kernel's lines."""
+    # no table: one window of the strip's own four tiles, whole runs
+    b = MS.reach(21, 64, None, 16)
+    assert [(x["strip"], x["group"], x["block"]) for x in b] == [(0, 0, 0), (0, 1, 0)]
+    assert all((x["nb"], x["t0"], x["t1"], x["Wc"], x["P"], x["pn"], x["live"]) == (21, 0, 3, 64, 32, (21,), False) for x in b)
+    # 48 x 65, half walk 4 / 47 in every row: shifts -4 .. 1 in block 0 (t = -47 .. 15), 1 .. 4 in block 1 (t = 17 .. 47)
+    b = MS.reach(48, 65, np.full(48, 4.0 / 47.0), 32)
+    assert len(b) == 2 * 2 * 2 and all(x["live"] and x["nTiles"] == 5 and not x["interior"] for x in b)
+    first = {(x["strip"], x["block"]): (x["nb"], x["t0"], x["t1"], x["pn"]) for x in b if x["group"] == 1}
+    assert first == {(0, 0): (32, -1, 4, (32,)), (0, 1): (16, 0, 4, (16,)), (1, 0): (32, 3, 8, (32,)), (1, 1): (16, 4, 8, (16,))}
+    # the widest window: +-512 in one group, 64 + 1024 columns in 68 tiles -> 3 pulses a run, 7 pulses in runs of 3, 3, 1
+    b = MS.reach(7, 64, MS.tables(MS.dims_of("g7x64"), 4)["limit"], 32)
+    assert len(b) == 1 and (b[0]["t0"], b[0]["t1"], b[0]["Wc"], b[0]["P"], b[0]["pn"]) == (-32, 35, 1088, 3, (3, 3, 1))
+
+
+def test_the_gpu_cases_reach_every_block_and_window_edge():
+    """migrate_kernel's groups of 32 rows: the (geometry, table) cases of tests/test_migrate_gpu.py on the new geometries run
+    every item of MS.REACH_ITEMS, in a group that stages (one with a migrated row).  tests/test_rate_bank_model.py has the same
+    for rate_bank_kernel's groups of 16."""
+    import test_migrate_gpu as G
+    assert [c for c in G.CASES if c[0] in MS.EDGE_GEOMS] == MS.EDGE_MIGRATE_CASES
+    found = MS.reach_suppliers(MS.EDGE_MIGRATE_CASES, 32, live_only=True)
+    for item, by in found.items():
+        print(f"32-row groups, {item}: {', '.join(f'{g}-{t}' for g, t in by) or 'NO CASE'}")
+    for item, by in found.items():
+        assert by, f"no case of 32-row groups runs: {item}"
+    # the partial row groups themselves: 7, 16, 17, 21 and 31 live rows
+    assert {MS.SHAPES[g][0] % 32 for g, _ in MS.EDGE_MIGRATE_CASES} == {21, 16, 17, 31, 7}
+
+
+@pytest.mark.parametrize("geom,table", MS.EDGE_MIGRATE_CASES, ids=lambda v: v)
+def test_the_gate_tells_every_block_edge_mutant(geom, table):
+    """A kernel that drops, repeats or halves a partial last block, clamps the walks of a partial last row group or loses the
+    reads across a strip seam misses PEAK_TOL by 100 x or more wherever it differs from the truth at all.  Derived: on the
+    impulse-reference CPIs one lost or repeated pulse moves a cell by at least 0.5 against a peak of at most 1.5 nD, 3.5e-3 of
+    the peak at nD = 95."""
+    dims = MS.dims_of(geom)
+    x, y, _ = MS.impulse_cpis(dims, 1, seed=21)
+    R = range_map(dims, x, y)
+    nD = dims.n_doppler_bins
+    h = MS.tables(dims, MS.CELLS[geom])[table]
+    s = migration_shifts(h, nD)
+    rows = ~MS.zero_rows(h, nD)
+    ref = MS.block_edge_sum(R, s, None, rows)
+    assert np.array_equal(ref, doppler_sum(R, s, rows))
+    assert np.max(np.abs(ref - migrate_maps(R, h))[rows]) <= 1e-12 * nD
+    peak = np.max(np.abs(ref))
+    assert peak <= 1.5 * nD
+    differ = 0
+    for which in MS.BLOCK_EDGE_MUTANTS:
+        got = MS.block_edge_sum(R, s, which, rows)
+        if MS.block_edge_identity(which, s, dims.n_delay_bins, rows, 32):
+            assert np.array_equal(got, ref), which
+            print(f"{geom} {table}: mutant {which} is the identity here")
+            continue
+        differ += 1
+        miss = np.max(np.abs(got - ref)) / peak
+        print(f"{geom} {table}: mutant {which} misses by {miss:.2e} of the peak, {miss / PEAK_TOL:.0f} x the gate")
+        assert miss >= 100 * PEAK_TOL, which
+    assert nD % 32 != 0 and differ >= 2  # a partial block and a partial row group at every new geometry
+
+
+def test_every_block_edge_mutant_differs_on_some_new_geometry():
+    """None of the five is the identity everywhere: each is told on at least two of the new geometries."""
+    for which in MS.BLOCK_EDGE_MUTANTS:
+        hit = set()
+        for geom, table in MS.EDGE_MIGRATE_CASES:
+            dims = MS.dims_of(geom)
+            h = MS.tables(dims, MS.CELLS[geom])[table]
+            s = migration_shifts(h, dims.n_doppler_bins)
+            if not MS.block_edge_identity(which, s, dims.n_delay_bins, ~MS.zero_rows(h, dims.n_doppler_bins), 32):
+                hit.add(geom)
+        assert len(hit) >= 2, (which, hit)
 
 
 def test_the_moving_echo_scene():

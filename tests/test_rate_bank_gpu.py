@@ -10,11 +10,13 @@ No reference counterpart; the checks are
     compensation off.  Five geometries with banks of 5 and 16 (65 x 44; 65 x 45; 129 x 111, two column strips and nine row
     groups; the even 64 bins; asymmetric Doppler limits) and 2049 x 40 with a bank of 3; single hypotheses at +-0.5 and +-3,
     -2 .. 2, 16 unevenly spaced rates up to +-nD/4, a bank with duplicates whose later copies the index never names; no table,
-    the physical one, ``limit`` and ``jagged``.  3 CPIs a call (one at 2049 x 40, whose fp64 restatement takes seconds per CPI)
+    the physical one, ``limit`` and ``jagged``.  Nine more cases on the geometries off the grid of 32 pulses (21 x 64, 48 x 65,
+    81 x 200, 95 x 64, 7 x 64: row groups of 5, 15, 1 and 7 live rows, blocks of 7 .. 31 pulses), whose reach
+    tests/test_rate_bank_model.py proves.  3 CPIs a call (one at 2049 x 40, whose fp64 restatement takes seconds per CPI)
     with NaN gaps between the planes' CPIs, in place and out of place, the outputs between guard words, the maps behind
     n_maps untouched, every index below K, the metrics within 1e-3 dB of fp64 Map::set_metrics of the device's own output;
   * bits: bank {0} with no table is the process call's maps (hot columns and leak compensation forced on); bank {0} with a
-    table is migrate_dev's maps; two calls give the same bits; map 0 of a call of one map is map 0 of a call of three; a
+    table is migrate_dev's maps, at 65 x 45 and at 95 x 64 (a block of 31 pulses, runs of fewer than 32); two calls give the same bits; map 0 of a call of one map is map 0 of a call of three; a
     single-hypothesis bank {q} equals a larger bank's cells wherever that bank's index names q;
   * the index plane: NULL is accepted and changes no map bit; a peak planted on a chirped walk is named by its rate;
   * process_multi_dev with 2 channels x 2 CPIs;
@@ -29,6 +31,12 @@ peak below the strongest (0 in most cases: the device and the restatement name t
 noisePower 5.7e-7 dB, maxPower 1.7e-6 dB from fp64 set_metrics of the device's own cells.  Scene: 61.444 dB on the device and in
 the restatement, 45.5 dB at that cell of the standard map.  As in the migration tests, the scene's direct path does not pass
 the hot-column test with both options forced on (0 columns rewritten): the bit checks hold whatever wrote the cells.
+Off the grid of 32 pulses: 1.7e-7 .. 3.3e-7 of the peak from the named hypothesis on the nine new cases (largest: 48 x 65, ``dup``,
+``limit``), the named hypothesis at most 1.5e-8 of the peak below the strongest, the same in place and out of place; bank {0} is
+migrate_dev bit for bit at 95 x 64 under ``physical`` and ``jagged``; the planted peak at (80, 150) of 81 x 200 is named by its
+rate, noisePower 4.9e-7 dB, maxPower 1.1e-6 dB.  A library built with the rows of a partial last group on the last row's walk
+passed every case from before and failed 21 x 64 ``jagged``, 95 x 64 ``limit``, 7 x 64 ``physical`` and both bank-{0} cases at
+95 x 64.  No defect was found.
 """
 import numpy as np
 import pytest
@@ -117,7 +125,7 @@ def check_cells(out, index, every, tag):
 
 
 # ---- 1. cells ---------------------------------------------------------------------------------------------------------------
-CELLS = {"g65x44": 4, "g65x45": 4, "g129x111": 9, "g2049x40": 15, "g64x44": 4, "gasym": 4}
+CELLS = MS.CELLS
 CASES = [("g65x44", "m2to2", "none"), ("g65x44", "uneven16", "physical"), ("g65x44", "p0.5", "limit"), ("g65x44", "m3", "jagged"),
          ("g65x44", "dup", "physical"),
          ("g65x45", "m2to2", "physical"), ("g65x45", "uneven16", "jagged"), ("g65x45", "m0.5", "none"),
@@ -125,6 +133,8 @@ CASES = [("g65x44", "m2to2", "none"), ("g65x44", "uneven16", "physical"), ("g65x
          ("g64x44", "m2to2", "jagged"), ("g64x44", "uneven16", "limit"),
          ("gasym", "m2to2", "physical"), ("gasym", "uneven16", "none"),
          ("g2049x40", "three", "physical")]
+# Doppler lengths off the 32-pulse grid; tests/test_rate_bank_model.py shows which block, run and window edges each of them runs
+CASES += MS.EDGE_RATE_CASES
 
 
 @pytest.mark.parametrize("geom,bank,table", CASES, ids=[f"{g}-{b}-{t}" for g, b, t in CASES])
@@ -180,12 +190,13 @@ def test_the_bank_of_zero_without_a_table_is_the_process_call(b2, torch):
     amb.set_migration(None)
 
 
-@pytest.mark.parametrize("table", ["physical", "jagged"])
-def test_the_bank_of_zero_with_a_table_is_migrate_dev(b2, torch, table):
-    geom = "g65x45"
+# g95x64: the two kernels must add a block of 31 pulses, and under ``jagged`` runs of fewer than 32, in the same order
+@pytest.mark.parametrize("geom,table", [("g65x45", "physical"), ("g65x45", "jagged"), ("g95x64", "physical"), ("g95x64", "jagged")],
+                         ids=["physical", "jagged", "g95x64-physical", "g95x64-jagged"])
+def test_the_bank_of_zero_with_a_table_is_migrate_dev(b2, torch, geom, table):
     dims, x, y, stride, R = inputs(b2, geom, 3, seed=55)
     amb = handle(b2, geom)
-    amb.set_migration(MS.tables(dims, 4)[table])
+    amb.set_migration(MS.tables(dims, CELLS[geom])[table])
     amb.set_rates([0.0])
     maps, _, std = process(torch, b2, amb, x, y, stride, 3)
     assert (std.view(np.float32) != 0).all()  # no zero cells: c = (1, -0) keeps every bit
@@ -236,15 +247,22 @@ def test_equal_inputs_give_equal_bits(b2, torch):
 
 # ---- 3. the index plane and the metrics ---------------------------------------------------------------------------------------
 def test_a_peak_planted_on_a_chirped_walk_is_named_by_its_rate(b2, torch):
-    geom = "g129x111"
+    planted_peak(b2, torch, "g129x111", 3, 70)  # a migrated row, a column of the second strip
+
+
+def test_a_peak_planted_in_the_last_row_group_and_the_third_strip_is_named_by_its_rate(b2, torch):
+    planted_peak(b2, torch, "g81x200", 80, 150)  # 81 rows: the last block has 17 pulses, the last row group is row 80 alone
+
+
+def planted_peak(b2, torch, geom, row, col):
     dims = MS.dims_of(geom)
     nD, nC = dims.n_doppler_bins, dims.n_corr
     x, y, stride = MS.impulse_cpis(dims, 2, seed=9)
     h = MS.tables(dims, CELLS[geom])["physical"]
     s = b2.migration_shifts(h, nD)
     q = np.array([-2.0, -1.0, 0.0, 1.0, 2.0])
-    row, col, k = 3, 70, 4  # a migrated row, a column of the second strip, the rate +2
-    assert s[row, 0] != 0
+    k = 4  # the rate +2
+    assert s[row, 0] != 0 and col + s[row].min() >= 0 and col + s[row].max() < dims.n_delay_bins
     i = np.arange(nD)
     w = np.exp(-2j * np.pi * ((i * ((row + nD // 2 + 1) % nD)) % nD) / nD)
     c = b2.rate_chirps(q, nD)[k]
@@ -262,7 +280,7 @@ def test_a_peak_planted_on_a_chirped_walk_is_named_by_its_rate(b2, torch):
     check_metrics(out, met, "planted")
     for m in range(2):
         noise, peak = MS.set_metrics64(out[m])
-        print(f"planted peak, map {m}: noisePower off by {abs(met[m, 0] - noise):.2e} dB, maxPower by {abs(met[m, 1] - peak):.2e} dB")
+        print(f"planted peak {geom} ({row}, {col}), map {m}: noisePower off by {abs(met[m, 0] - noise):.2e} dB, maxPower by {abs(met[m, 1] - peak):.2e} dB")
     amb.set_rates(None)
     amb.set_migration(None)
 

@@ -12,8 +12,13 @@ to these restatements.
     to the library's 16): the compensated level at (62, 23) is at least the static echo's - 2 dB, (62, 23) is the global argmax,
     the winning hypothesis is the scene's q, and the global maxima of the standard, the migration-only and the chirp-only maps
     are each at most the static echo's - 6 dB.
+  * Doppler lengths off the grid of 32 pulses (MS.EDGE_GEOMS), with rate_bank_kernel's groups of 16 rows: ``reach`` shows that the
+    GPU cases on them run every block, run and window edge of MS.REACH_ITEMS; the five block-edge mutants of
+    MS.block_edge_sum, with the chirp in the sum, each miss PEAK_TOL by 100 x or more at the weakest and the strongest rate of
+    every GPU case where they change a read that lands in the map; the variant table above also runs at 95 x 64.
 
-Measured here (printed by the tests).  fp32 emulation against fp64: 1.6e-7 .. 1.7e-7 of the peak at 65 x 44, 1.9e-7 .. 2.2e-7 at
+Measured here (printed by the tests).  Block-edge mutants: the smallest miss is 4.8e-2 of the peak, 4813 x the gate (the last
+pulse repeated at 95 x 64, no table, q = 0.5).  fp32 emulation against fp64: 1.6e-7 .. 1.7e-7 of the peak at 65 x 44, 1.9e-7 .. 2.2e-7 at
 2049 x 40; the fp32 chirp table alone 1.4e-8 .. 2.0e-8.  Smallest miss of a wrong variant: 1.7e-4 of the peak (the denominator
 variant at 2049 x 40, q = 0.5); at 65 x 44 the smallest is 5.2e-3 (denominator, q = 0.5).  Scene, seed 5: the same echo static
 62.7 dB; standard map 45.5 dB at the cell, global maximum 48.4 dB (-14.3 dB); migration alone 53.6 dB at the cell, global maximum
@@ -200,7 +205,7 @@ def variant_chirp(q, nD, which):
     return np.exp(-1j * np.pi * q * t * t / den)
 
 
-@pytest.mark.parametrize("geom,cells", [("g65x44", 4), ("g2049x40", 15)])
+@pytest.mark.parametrize("geom,cells", [("g65x44", 4), ("g2049x40", 15), ("g95x64", 4)])
 def test_the_gate_tells_every_wrong_variant_from_the_kernel_arithmetic(geom, cells):
     dims = MS.dims_of(geom)
     x, y, _ = MS.impulse_cpis(dims, 1, seed=21)
@@ -226,6 +231,59 @@ def test_the_gate_tells_every_wrong_variant_from_the_kernel_arithmetic(geom, cel
             miss = np.max(np.abs(chirped_sum(R, s, variant_chirp(q, nD, which), rows) - ref)) / peak
             print(f"{geom} q={q}: variant {which} misses by {miss:.2e} of the peak")
             assert miss >= 10 * PEAK_TOL, (which, q)
+
+
+# ---- Doppler lengths and windows off the 32-pulse grid ------------------------------------------------------------------------
+def test_the_gpu_cases_reach_every_block_and_window_edge():
+    """rate_bank_kernel's groups of 16 rows: the (geometry, bank, table) cases of tests/test_rate_bank_gpu.py on the new
+    geometries run every item of MS.REACH_ITEMS.  Every bank among them holds a rate other than 0, so every group stages."""
+    import test_rate_bank_gpu as G
+    assert [c for c in G.CASES if c[0] in MS.EDGE_GEOMS] == MS.EDGE_RATE_CASES
+    assert all(np.any(np.asarray(G.banks(MS.SHAPES[g][0])[b]) != 0) for g, b, _ in MS.EDGE_RATE_CASES)
+    found = MS.reach_suppliers([(g, t) for g, _, t in MS.EDGE_RATE_CASES], 16, live_only=False)
+    for item, by in found.items():
+        print(f"16-row groups, {item}: {', '.join(f'{g}-{t}' for g, t in by) or 'NO CASE'}")
+    for item, by in found.items():
+        assert by, f"no case of 16-row groups runs: {item}"
+    # the chirps[] rows behind a partial block and the vmask of a partial group: blocks of 7 .. 31 pulses, groups of 1 .. 15 rows
+    assert {MS.SHAPES[g][0] % 32 for g, _, _ in MS.EDGE_RATE_CASES} == {21, 16, 17, 31, 7}
+    assert {MS.SHAPES[g][0] % 16 for g, _, _ in MS.EDGE_RATE_CASES} == {5, 0, 1, 15, 7}
+
+
+@pytest.mark.parametrize("geom,bank,table", MS.EDGE_RATE_CASES, ids=[f"{g}-{b}-{t}" for g, b, t in MS.EDGE_RATE_CASES])
+def test_the_gate_tells_every_block_edge_mutant(geom, bank, table):
+    """With the chirp in the sum and groups of 16 rows: a kernel that drops, repeats or halves a partial last block, clamps the
+    walks of a partial last row group or loses the reads across a strip seam misses PEAK_TOL by 100 x or more wherever it differs
+    from the truth at all, at the case's weakest and strongest rate.  Derived: on the impulse-reference CPIs one lost or repeated
+    pulse moves a cell by at least 0.5 (the chirp has modulus 1) against a peak of at most 1.5 nD, 3.5e-3 at nD = 95."""
+    import test_rate_bank_gpu as G
+    dims = MS.dims_of(geom)
+    x, y, _ = MS.impulse_cpis(dims, 1, seed=21)
+    R = range_map(dims, x, y)
+    nD = dims.n_doppler_bins
+    h = None if table == "none" else MS.tables(dims, MS.CELLS[geom])[table]
+    s = migration_shifts(np.zeros(nD) if h is None else h, nD)
+    bank_q = np.asarray(G.banks(nD)[bank], dtype=np.float64)
+    nonzero = bank_q[bank_q != 0]
+    for q in sorted({float(nonzero[np.argmin(np.abs(nonzero))]), float(nonzero[np.argmax(np.abs(nonzero))])}):
+        c = rate_chirps(q, nD)[0]
+        ref = MS.block_edge_sum(R, s, None, chirp=c, rows_per_group=16)
+        assert np.array_equal(ref, chirped_sum(R, s, c))
+        assert np.max(np.abs(ref - rate_bank_maps(R, [q], h)[2][0])) <= 1e-12 * nD
+        peak = np.max(np.abs(ref))
+        assert peak <= 1.5 * nD
+        differ = 0
+        for which in MS.BLOCK_EDGE_MUTANTS:
+            got = MS.block_edge_sum(R, s, which, chirp=c, rows_per_group=16)
+            if MS.block_edge_identity(which, s, dims.n_delay_bins, None, 16):
+                assert np.array_equal(got, ref), which
+                print(f"{geom} {table} q={q:.3g}: mutant {which} is the identity here")
+                continue
+            differ += 1
+            miss = np.max(np.abs(got - ref)) / peak
+            print(f"{geom} {table} q={q:.3g}: mutant {which} misses by {miss:.2e} of the peak, {miss / PEAK_TOL:.0f} x the gate")
+            assert miss >= 100 * PEAK_TOL, (which, q)
+        assert differ >= 2  # a partial block at every new geometry: dropped and repeated always differ
 
 
 _scene = {}
