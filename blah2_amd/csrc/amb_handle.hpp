@@ -1,6 +1,6 @@
 // Internal to the library: what the units behind include/blah2hip.h share.  The ambiguity handle, whose fields every
 // unit reads directly (no accessors), the error and launch-check helpers, and the few engine functions (capi.hip)
-// that another unit calls.  Host code only: capi.hip, array.hip, detect.hip, integrate.hip, taper.hip, migrate.hip, rate.hip
+// that another unit calls.  Host code only: capi.hip, array.hip, detect.hip, integrate.hip, taper.hip, walk.hip
 // and context.hip all include it.
 #pragma once
 
@@ -102,11 +102,11 @@ struct blah2hip_amb_s {
   bool lastHot = false;             // the last process call launched hot_columns_kernel
   hipStream_t lastHotStream = nullptr; // ... on this stream (BLAH2HIP_INFO_HOT_COLUMNS waits for that one only)
   uint32_t lastHotCpis = 0;         // ... over this many CPIs
-  uint32_t lastMaps = 0;            // maps (virtual CPIs) of the last process call: what d_R holds (0 = no call yet; migrate.hip)
+  uint32_t lastMaps = 0;            // maps (virtual CPIs) of the last process call: what d_R holds (0 = no call yet; walk.hip)
   int lastLeakLags = 0;             // BLAH2HIP_INFO_LEAK_LAGS: lags corrected by the last process call (0 = not applied)
   double lastLeakMax = 0.0;         // BLAH2HIP_INFO_LEAK_MAX_E12: the largest |g| of the calibration the last call ran under
 
-  // ---- written by detect.hip; bearingGridLast by array.hip, taperGridLast by taper.hip, the migration fields by migrate.hip, the rate fields by rate.hip
+  // ---- written by detect.hip; bearingGridLast by array.hip, taperGridLast by taper.hip, the migration and rate fields by walk.hip
   // a threshold table of detect.hip's cfar_table(); d: alpha[n + 1], then with a rank (permille) rank[n + 1] words; pinned:
   // handed out by *_prepare, never evicted.  Two lists, each with its own budget; destroy (capi.hip) frees both.
   struct CfarTable { double pfa; uint32_t looks, rank; size_t n; double *d; bool pinned; };
@@ -122,7 +122,7 @@ struct blah2hip_amb_s {
   double *d_migrate = nullptr;      // [nD] half walks (blah2hip_amb_set_migration), allocated at its first use, freed by destroy
   bool migrateSet = false;          // ... and whether a table is set
   int migrateGridLast = 0;          // BLAH2HIP_INFO_MIGRATE_GRID
-  cf *d_rates = nullptr;            // [BLAH2HIP_MAX_RATES][nD] chirps c_k[i] (blah2hip_amb_set_rates, rate.hip), allocated at its first use, freed by destroy
+  cf *d_rates = nullptr;            // [BLAH2HIP_MAX_RATES][nD] chirps c_k[i] (blah2hip_amb_set_rates, walk.hip), allocated at its first use, freed by destroy
   uint32_t nRates = 0, zeroRates = 0; // ... hypotheses of the bank that is set (0 = none), and bit k: q[k] == 0
   int rateGridLast = 0;             // BLAH2HIP_INFO_RATE_GRID
   int trackGridLast = 0, trackShiftLast = 0; // BLAH2HIP_INFO_TRACK_GRID / _TRACK_MAX_SHIFT (integrate.hip)

@@ -747,25 +747,34 @@ def range_map(dims, x, y):
     return Z[:, lag]
 
 
+def _walk_rows(R, h):
+    """The row gather of :func:`migrate_maps` and :func:`rate_bank_maps`: for every Doppler row ``j`` of the complex128
+    ``R[..., nD, nDelay]``, ``(j, g, w)`` with ``g[..., i, d] = [0 <= d + s(j,i) < nDelay] R[..., i, d + s(j,i)]`` (the shifts of
+    :func:`migration_shifts` for the half walks ``h``) and the row's twiddles ``w[i] = W[(i src(j)) mod nD]``,
+    ``src(j) = (j + nD // 2 + 1) % nD``.  ``migrate_maps`` sums ``g w`` over the pulses: the ``q = 0`` hypothesis of the bank."""
+    nD, nDelay = R.shape[-2:]
+    s = migration_shifts(h, nD)
+    i = np.arange(nD)
+    d = np.arange(nDelay)
+    for j in range(nD):
+        w = np.exp(-2j * np.pi * ((i * ((j + nD // 2 + 1) % nD)) % nD) / nD)
+        c = d[None, :] + s[j][:, None]  # [pulse, column]
+        ok = (c >= 0) & (c < nDelay)
+        yield j, np.where(ok, np.take_along_axis(R, np.broadcast_to(np.clip(c, 0, nDelay - 1), R.shape), axis=-1), 0.0), w
+
+
 def migrate_maps(R, half_walk):
     """blah2hip_amb_migrate_dev restated in fp64 NumPy for EVERY row (the library copies the zero-shift rows from its input
     map instead): ``M'[j][d] = sum_i [0 <= d + s(j,i) < nDelay] R[i][d + s(j,i)] W[(i src(j)) mod nD]`` with
     ``src(j) = (j + nD // 2 + 1) % nD`` and the shifts of :func:`migration_shifts`.  ``R``: complex ``[..., nD, nDelay]``."""
     R = np.asarray(R).astype(np.complex128)
-    nD, nDelay = R.shape[-2:]
+    nD = R.shape[-2]
     h = np.asarray(half_walk, dtype=np.float64)
     if h.shape != (nD,):
         raise ValueError("half_walk must hold one entry per Doppler row")
-    s = migration_shifts(h, nD)
-    i = np.arange(nD)
-    d = np.arange(nDelay)
     out = np.zeros(R.shape, dtype=np.complex128)
-    for j in range(nD):
-        w = np.exp(-2j * np.pi * ((i * ((j + nD // 2 + 1) % nD)) % nD) / nD)
-        c = d[None, :] + s[j][:, None]  # [pulse, column]
-        ok = (c >= 0) & (c < nDelay)
-        g = np.take_along_axis(R, np.broadcast_to(np.clip(c, 0, nDelay - 1), R.shape), axis=-1)
-        out[..., j, :] = np.sum(np.where(ok, g, 0.0) * w[:, None], axis=-2)
+    for j, g, w in _walk_rows(R, h):
+        out[..., j, :] = np.sum(g * w[:, None], axis=-2)
     return out
 
 
@@ -821,20 +830,12 @@ def rate_bank_maps(R, q, half_walk=None):
     q = np.atleast_1d(np.asarray(q, dtype=np.float64))
     if q.ndim != 1 or not 1 <= q.size <= 256:  # (the library's banks end at BLAH2HIP_MAX_RATES; the restatement's need not)
         raise ValueError("a bank holds 1 .. 256 rates")
-    nDelay = R.shape[-1]
     h = np.zeros(nD) if half_walk is None else np.asarray(half_walk, dtype=np.float64)
     if h.shape != (nD,):
         raise ValueError("half_walk must hold one entry per Doppler row")
     c = rate_chirps(q, nD)
-    s = migration_shifts(h, nD)
-    i = np.arange(nD)
-    d = np.arange(nDelay)
     every = np.zeros((q.size,) + R.shape, dtype=np.complex128)
-    for j in range(nD):  # migrate_maps' row, gathered once for the whole bank
-        w = np.exp(-2j * np.pi * ((i * ((j + nD // 2 + 1) % nD)) % nD) / nD)
-        col = d[None, :] + s[j][:, None]  # [pulse, column]
-        ok = (col >= 0) & (col < nDelay)
-        g = np.where(ok, np.take_along_axis(R, np.broadcast_to(np.clip(col, 0, nDelay - 1), R.shape), axis=-1), 0.0)
+    for j, g, w in _walk_rows(R, h):  # gathered once for the whole bank
         for k in range(q.size):
             every[k, ..., j, :] = np.sum(g * (c[k] * w)[:, None], axis=-2)
     index = np.argmax(np.abs(every) ** 2, axis=0).astype(np.uint8)  # the first of equals

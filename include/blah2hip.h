@@ -623,7 +623,7 @@ int blah2hip_amb_set_migration(blah2hip_amb_t h, const double *half_walk);
 /* M' for maps 0 .. n_maps - 1 of the handle's range map AS THE LAST blah2hip_amb_process_dev / _process_multi_dev CALL LEFT
  * IT (virtual CPIs k * n_cpi + c).  d_map: that call's map buffer (NULL = the handle's own), read in zero-shift rows only.
  * d_out_map [n_maps][n_doppler][n_delay] may be the same pointer (in place) or a disjoint buffer; d_out_metrics [n_maps][2]
- * is Map::set_metrics of every output map on the cells as written.  Enqueues only -- migrate_kernel (BLAH2HIP_K_DOPPLER)
+ * is Map::set_metrics of every output map on the cells as written.  Enqueues only -- walk_sum_kernel<8, 1> (BLAH2HIP_K_DOPPLER)
  * and metrics_kernel (BLAH2HIP_K_METRICS), which finishes the metrics in index order (no floating-point atomics) -- with
  * no upload, allocation or synchronisation, and can be captured in a graph.  The grid depends on the geometry alone, never
  * on n_maps.  The per-workgroup partials live in the handle's buffers, so calls on one handle must be ordered on the device.
@@ -647,8 +647,8 @@ int blah2hip_amb_migrate_dev(blah2hip_amb_t h, const void *d_map, uint32_t n_map
  *   M_k[j][d] = sum_i [0 <= d + s(j,i) < n_delay]  ( R[i][d + s(j,i)] c_k[i] ) W[(i src(j)) mod n_doppler]
  *   k*(j,d)   = the smallest k with the largest power p = x x + y y (fp32) of M_k[j][d]
  *   out[j][d] = M_k*[j][d],   index[j][d] = (uint8) k*
- * The arithmetic is migrate_kernel's: fp32 complex multiply-adds in pulse order, a block of 32 pulses summed on its own and
- * added into a running sum, the range cell multiplied by the chirp first and by the twiddle second.  The order of the
+ * The arithmetic is walk_sum_kernel's (blah2hip_amb_migrate_dev's kernel body): fp32 complex multiply-adds in pulse order, a
+ * block of 32 pulses summed on its own and added into a running sum, the range cell multiplied by the chirp first and by the twiddle second.  The order of the
  * additions depends on (j, k, i) alone: equal inputs give equal bits at every placement, every n_maps and for a hypothesis
  * at any position in the bank.  A candidate with q[k] == 0 in a ZERO-SHIFT row (rint(h[j] (n_doppler - 1)) == 0, or no table
  * set) is THE INPUT MAP'S CELL, bit for bit: it keeps what the hot-column and leak machinery wrote at the direct path; every
@@ -671,7 +671,7 @@ int blah2hip_amb_set_rates(blah2hip_amb_t h, const double *q, uint32_t n_rates);
  * a candidate is the input cell.  d_out_map [n_maps][n_doppler][n_delay] may be the same pointer (in place) or a disjoint
  * buffer; d_out_index [n_maps][n_doppler][n_delay] uint8 may be NULL; d_out_metrics [n_maps][2] is Map::set_metrics of
  * every output map on the cells as written.  The migration table set on the handle at the time of the call is the walk.
- * Enqueues only -- rate_bank_kernel (BLAH2HIP_K_DOPPLER) and metrics_kernel (BLAH2HIP_K_METRICS) -- with no upload,
+ * Enqueues only -- walk_sum_kernel<4, 2> (BLAH2HIP_K_DOPPLER) and metrics_kernel (BLAH2HIP_K_METRICS) -- with no upload,
  * allocation or synchronisation, and can be captured in a graph.  The grid, ceil(n_delay / 64) ceil(n_doppler / 16)
  * workgroups per map (BLAH2HIP_INFO_RATE_GRID), depends on the geometry alone, never on n_maps; the bank goes in passes
  * inside a workgroup.  BLAH2HIP_ERR_INVALID, with nothing enqueued: every case of blah2hip_amb_migrate_dev but "no table
@@ -700,7 +700,7 @@ int blah2hip_amb_rate_bank_dev(blah2hip_amb_t h, const void *d_map, uint32_t n_m
  *   k*  = 0 at the start; k replaces it only when S_k > S_k* (fp32 compare): the smallest k with the largest sum
  *   out[g][j][d] = ( sqrtf(scale * S_k*), 0 ),  index[g][j][d] = (uint8) k*,  scale = 1 / (W sum_k w_k) as above
  * a = 0 is the cell itself (s = 0, jr = j): an echo is reported at its position in the NEWEST CPI.  A term outside the map
- * contributes zero and scale does not change: cells near the edges are lower, as in migrate_kernel.  A NaN S_0 stays, with
+ * contributes zero and scale does not change: cells near the edges are lower, as in walk_sum_kernel.  A NaN S_0 stays, with
  * index 0; a NaN S_k with k > 0 never wins (the compare is false).  A NaN or Inf cell of p reaches exactly the outputs whose
  * tracks pass through it.  With walk == 0 and the bank {0} the output maps are blah2hip_nci_process_dev's bit for bit (the
  * same additions in the same order); the metrics agree to 1e-3 dB only, because the partials' grid differs.  The error of a
@@ -1149,7 +1149,7 @@ int blah2hip_amb_result_ptrs(blah2hip_amb_t h, const void **d_map, const double 
 /* ---- per-kernel timing (HIP events on the launch stream) ---------------- */
 #define BLAH2HIP_K_RANGE 0
 #define BLAH2HIP_K_DOPPLER 1
-#define BLAH2HIP_K_METRICS 2   /* metrics_kernel: behind the Doppler kernels, the beam former, the integrator, the Doppler taper, migrate_kernel and rate_bank_kernel */
+#define BLAH2HIP_K_METRICS 2   /* metrics_kernel: behind the Doppler kernels, the beam former, the integrator, the Doppler taper and walk_sum_kernel */
 #define BLAH2HIP_K_CFAR 3     /* cfar1d_kernel, cfar2d_tile_kernel or cfar2d_kernel */
 #define BLAH2HIP_K_SAT_ROWS 4 /* 2-D CFAR through the summed-area table (large windows): row prefix sums */
 #define BLAH2HIP_K_SAT_COLS 5 /* ... column prefix sums */

@@ -13,7 +13,7 @@ in the middle of the CPI and falls by 8 samples over it, pulse by pulse (a phase
 pulse); white noise of sigma 0.3.  fc = f nCorr nD / 8 makes the physical table walk those 8 samples.
 
 (c) Geometries off the grid of 32 pulses (EDGE_GEOMS: 21 x 64, 48 x 65, 81 x 200, 95 x 64, 7 x 64, by explicit bin counts) with
-the cases the GPU tests run on them; ``reach``, the window arithmetic of migrate_kernel and rate_bank_kernel restated, which
+the cases the GPU tests run on them; ``reach``, the window arithmetic of walk_sum_kernel's two shapes restated, which
 says what blocks, runs and windows a (geometry, table) case makes the kernels run; and ``block_edge_sum``, the definition with
 the five ways of getting a partial last block, a partial last row group or a strip seam wrong.
 """
@@ -114,11 +114,11 @@ def zero_rows(half, nD):
 
 
 def reach(nD, nDelay, half, rows_per_group, cols=64, blk=32, lds_cells=4096):
-    """The window arithmetic of migrate_kernel (rows_per_group 32) and rate_bank_kernel (16) restated: one dict for every
+    """The window arithmetic of walk_sum_kernel<8, 1> (rows_per_group 32) and walk_sum_kernel<4, 2> (16) restated: one dict for every
     (strip, row group, block of pulses) with ``nb`` the block's pulses, ``t0`` and ``t1`` the first and last 16-column tile of
     its window, ``Wc = 16 (t1 - t0 + 1)`` the staged cells of one pulse, ``P = min(32, lds_cells // Wc)`` the pulses of a run and
     ``pn`` the run lengths; with ``nTiles``, ``interior`` (the strip touches neither edge of the map) and ``live`` (a row of
-    the group lies in the map and has a shift: migrate_kernel stages nothing for a group of copied rows).  Rows behind the
+    the group lies in the map and has a shift: walk_sum_kernel<8, 1> stages nothing for a group of copied rows).  Rows behind the
     map take the last row's half walk, as in the kernels.  ``half`` None is no table: every shift is 0."""
     h = np.zeros(nD) if half is None else np.asarray(half, dtype=np.float64)
     assert h.shape == (nD,)

@@ -1,4 +1,4 @@
-"""GPU: migrate_kernel (blah2hip_amb_set_migration / blah2hip_amb_migrate_dev, Ambiguity.set_migration / migrate_dev) on the
+"""GPU: walk_sum_kernel<8, 1> (blah2hip_amb_set_migration / blah2hip_amb_migrate_dev, Ambiguity.set_migration / migrate_dev) on the
 impulse-reference CPIs and the moving-echo scene of tests/migrate_scenes.py.  tests/test_migrate_model.py shows on the CPU that
 the gate used here tells the kernel's arithmetic from every wrong walk (sign, wrap, floor, truncate, centre, none).
 

@@ -205,7 +205,7 @@ def test_the_gate_tells_every_wrong_variant_from_the_kernel_arithmetic(geom, cel
 
 # ---- Doppler lengths and windows off the 32-pulse grid ------------------------------------------------------------------------
 def test_reach_restates_the_window_arithmetic():
-    """reach() on cases worked out by hand from migrate_kernel's lines."""
+    """reach() on cases worked out by hand from walk_sum_kernel's lines."""
     # no table: one window of the strip's own four tiles, whole runs
     b = MS.reach(21, 64, None, 16)
     assert [(x["strip"], x["group"], x["block"]) for x in b] == [(0, 0, 0), (0, 1, 0)]
@@ -221,9 +221,9 @@ def test_reach_restates_the_window_arithmetic():
 
 
 def test_the_gpu_cases_reach_every_block_and_window_edge():
-    """migrate_kernel's groups of 32 rows: the (geometry, table) cases of tests/test_migrate_gpu.py on the new geometries run
+    """walk_sum_kernel<8, 1>'s groups of 32 rows: the (geometry, table) cases of tests/test_migrate_gpu.py on the new geometries run
     every item of MS.REACH_ITEMS, in a group that stages (one with a migrated row).  tests/test_rate_bank_model.py has the same
-    for rate_bank_kernel's groups of 16."""
+    for walk_sum_kernel<4, 2>'s groups of 16."""
     import test_migrate_gpu as G
     assert [c for c in G.CASES if c[0] in MS.EDGE_GEOMS] == MS.EDGE_MIGRATE_CASES
     found = MS.reach_suppliers(MS.EDGE_MIGRATE_CASES, 32, live_only=True)

@@ -1,4 +1,4 @@
-"""GPU: rate_bank_kernel (blah2hip_doppler_rate / blah2hip_amb_set_rates / blah2hip_amb_rate_bank_dev, Ambiguity.doppler_rate /
+"""GPU: walk_sum_kernel<4, 2> (blah2hip_doppler_rate / blah2hip_amb_set_rates / blah2hip_amb_rate_bank_dev, Ambiguity.doppler_rate /
 set_rates / rate_bank_dev) on the impulse-reference CPIs of tests/migrate_scenes.py and the accelerating scene of
 tests/rate_scenes.py, in the guarded arenas of tests/test_migrate_gpu.py.  tests/test_rate_bank_model.py shows on the CPU that
 the gate used here tells the kernel's arithmetic from every wrong chirp (sign, centre, denominator, origin, none, half the rate).

@@ -12,7 +12,7 @@ to these restatements.
     to the library's 16): the compensated level at (62, 23) is at least the static echo's - 2 dB, (62, 23) is the global argmax,
     the winning hypothesis is the scene's q, and the global maxima of the standard, the migration-only and the chirp-only maps
     are each at most the static echo's - 6 dB.
-  * Doppler lengths off the grid of 32 pulses (MS.EDGE_GEOMS), with rate_bank_kernel's groups of 16 rows: ``reach`` shows that the
+  * Doppler lengths off the grid of 32 pulses (MS.EDGE_GEOMS), with walk_sum_kernel<4, 2>'s groups of 16 rows: ``reach`` shows that the
     GPU cases on them run every block, run and window edge of MS.REACH_ITEMS; the five block-edge mutants of
     MS.block_edge_sum, with the chirp in the sum, each miss PEAK_TOL by 100 x or more at the weakest and the strongest rate of
     every GPU case where they change a read that lands in the map; the variant table above also runs at 95 x 64.
@@ -235,7 +235,7 @@ def test_the_gate_tells_every_wrong_variant_from_the_kernel_arithmetic(geom, cel
 
 # ---- Doppler lengths and windows off the 32-pulse grid ------------------------------------------------------------------------
 def test_the_gpu_cases_reach_every_block_and_window_edge():
-    """rate_bank_kernel's groups of 16 rows: the (geometry, bank, table) cases of tests/test_rate_bank_gpu.py on the new
+    """walk_sum_kernel<4, 2>'s groups of 16 rows: the (geometry, bank, table) cases of tests/test_rate_bank_gpu.py on the new
     geometries run every item of MS.REACH_ITEMS.  Every bank among them holds a rate other than 0, so every group stages."""
     import test_rate_bank_gpu as G
     assert [c for c in G.CASES if c[0] in MS.EDGE_GEOMS] == MS.EDGE_RATE_CASES

@@ -94,7 +94,7 @@ def test_chain_is_process_dev_and_rate_bank_dev_on_the_same_batches(b2, torch, c
     try:
         nD, nC = amb.get_n_doppler_bins(), amb.get_n_delay_bins()
         cells = nD * nC
-        # what the chain set and launched: the bank, the table only when asked for, one second-sum kernel and never migrate_kernel
+        # what the chain set and launched: the bank, the table only when asked for, one second-sum kernel and never migrate_dev's
         assert np.array_equal(held["rates"], bank) and held["migrate"] is migration
         assert held["rate_grid"] == -(-nC // 64) * -(-nD // 16) and held["migrate_grid"] == 0
         assert held["pfa"] == DET["pfa"] / K  # the union bound over the K hypotheses

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Time per launch of migrate_kernel against the direct Doppler kernel of the same handle, in the same process.
+"""Time per launch of walk_sum_kernel<8, 1> (blah2hip_amb_migrate_dev) against the direct Doppler kernel of the same handle, in the same process.
 
     python tools/gpu_migrate_time.py [--launches 100] [--warmup 50] [--out profiles/r18_migrate_time.json]
 
@@ -11,7 +11,7 @@ left on the handle.
 
 The yardstick is doppler_dft_kernel (BLAH2HIP_DOP_DIRECT forced, hot columns and leak compensation off, so that the Doppler
 bracket holds that one kernel) over the same CPIs on the same handle: the same complex multiply-adds per cell -- nD of them
--- without the walk.  migrate_kernel sums only the rows that are not zero-shift rows, so the yardstick's time is scaled by
+-- without the walk.  The kernel sums only the rows that are not zero-shift rows, so the yardstick's time is scaled by
 their share.  `migrate_over_yardstick` above 1.5 is a finding to explain.  The kernel is never compared with its own earlier
 runs.  `us_per_map` is what the stage adds to a chain per CPI.  One process; run it under a time limit."""
 import argparse

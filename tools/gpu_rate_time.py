@@ -1,17 +1,17 @@
 #!/usr/bin/env python3
-"""Time per launch of rate_bank_kernel against migrate_kernel on the same handle and range map, in the same process.
+"""Time per launch of walk_sum_kernel<4, 2> (the rate bank) against walk_sum_kernel<8, 1> (migrate_dev) on the same handle and range map, in the same process.
 
     python tools/gpu_rate_time.py [--launches 100] [--warmup 50] [--out profiles/r19_rate_time.json]
 
 Two geometries: configs[1]'s 513 x 411 maps, 256 CPIs a call, and configs[2]'s 1025 x 2048 maps, 16 a call, each with the
-physical migration table for fc = 204.64 MHz set, and banks of K = 1 ({0}: migrate_kernel's own sums with the chirp multiply
+physical migration table for fc = 204.64 MHz set, and banks of K = 1 ({0}: migrate_dev's own sums with the chirp multiply
 added), 5 (-2 .. 2) and 16 (-8 .. 7).  The kernel's time is blah2hip_amb_set_timing's BLAH2HIP_K_DOPPLER around the one launch of
 blah2hip_amb_rate_bank_dev (its metrics_kernel counts under BLAH2HIP_K_METRICS and is reported beside it), read after every
 launch: the median of `--launches` launches behind `--warmup` untimed ones, out of place, with the index plane, on the range
 map one process call left on the handle.
 
-The yardstick is migrate_kernel (blah2hip_amb_migrate_dev) timed the same way on that handle and range map, scaled to the same
-number of row sums: the bank sums K nD rows less the copied ones (a zero rate in a zero-shift row), migrate_kernel its migrated
+The yardstick is walk_sum_kernel<8, 1> (blah2hip_amb_migrate_dev) timed the same way on that handle and range map, scaled to the same
+number of row sums: the bank sums K nD rows less the copied ones (a zero rate in a zero-shift row), migrate_dev its migrated
 rows.  `per_row_sum_over_migrate` is (rate_us / row_sums) / (migrate_us / migrated_rows); above 1.0 is a finding to explain
 from the source and the resource report.  The kernel is never compared with its own earlier runs.  `us_per_map` is what the
 stage adds to a chain per CPI.  One process; run it under a time limit."""
@@ -98,7 +98,7 @@ def main():
                     "row_sums": row_sums, "workgroups_per_map": amb.info(_lib.INFO_RATE_GRID),
                     "rate_us_median": rate_us, "rate_us_min": min(t["doppler"]), "metrics_us_median": met_us,
                     "us_per_map": (rate_us + met_us) / n_maps, "rate_tflops": 16.0 * nD * row_sums * nC * n_maps / rate_us / 1e6,
-                    "yardstick_kernel": "migrate_kernel", "migrate_us_median": mig_us, "migrate_us_min": min(mig["doppler"]),
+                    "yardstick_kernel": "walk_sum_kernel<8, 1>", "migrate_us_median": mig_us, "migrate_us_min": min(mig["doppler"]),
                     "migrated_rows": migrated, "migrate_workgroups_per_map": amb.info(_lib.INFO_MIGRATE_GRID),
                     "per_row_sum_over_migrate": (rate_us / row_sums) / (mig_us / migrated)}
             print(json.dumps(case), flush=True)

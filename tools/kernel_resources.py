@@ -6,7 +6,7 @@
 
 One unit a call: the library is several .hip files (capi.hip holds the range and Doppler kernels, clutter.hip the clutter
 filter's, spectrum.hip the spectrum analyser's, array.hip the beam kernels, detect.hip the detectors', integrate.hip,
-taper.hip, migrate.hip and rate.hip a family each), so the whole library is a loop over blah2_amd/csrc/*.hip.  Host-only headers
+taper.hip and walk.hip a family each), so the whole library is a loop over blah2_amd/csrc/*.hip.  Host-only headers
 such as cfar_alpha.hpp hold no kernel and do not show up.
 """
 import os
