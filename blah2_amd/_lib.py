@@ -75,6 +75,8 @@ INFO_RATE_GRID = 19
 MAX_RATES = 16
 INFO_TRACK_GRID, INFO_TRACK_MAX_SHIFT = 20, 21
 MAX_TRACK_SHIFT = 1048576
+MAX_CMAP_MEMORY = 64
+CMAP_NORMALISE = 1
 
 
 class Blah2HipError(RuntimeError):
@@ -170,6 +172,15 @@ SYMBOLS = {
     "blah2hip_oscfar2d_prepare": (C.c_int, [_vp, _dbl, _u32, _i32, _i32, _i32, _i32]),
     "blah2hip_oscfar2d_process": (C.c_int, [_vp, _u32, _dbl, _u32, _i32, _i32, _i32, _i32, _i32, _dbl, _vp, _vp, _vp, _u32,
                                             C.POINTER(_u32)]),
+    "blah2hip_cmap_alpha": (C.c_int, [_dbl, _u32, _u32, _vp]),
+    "blah2hip_cmap_create": (C.c_int, [_vp, _u32, _u32, C.POINTER(_vp)]),
+    "blah2hip_cmap_destroy": (C.c_int, [_vp]),
+    "blah2hip_cmap_reset": (C.c_int, [_vp]),
+    "blah2hip_cmap_age": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
+    "blah2hip_cmap_prepare": (C.c_int, [_vp, _dbl]),
+    "blah2hip_cmap_process_dev": (C.c_int, [_vp, _vp, _vp, _u32, _dbl, _i32, _dbl, _vp, _u32, _vp, _vp, _vp, _vp]),
+    "blah2hip_cmap_gate_dev": (C.c_int, [_vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp]),
+    "blah2hip_cmap_read_background": (C.c_int, [_vp, _vp]),
     "blah2hip_centroid": (C.c_int, [_vp, _vp, _vp, _u32, C.c_uint16, C.c_uint16, _dbl, _vp, _vp, _vp, C.POINTER(_u32)]),
     "blah2hip_interpolate": (C.c_int, [_vp, _vp, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _dbl, C.c_int, C.c_int,
                                        _vp, _vp, _vp, C.POINTER(_u32)]),

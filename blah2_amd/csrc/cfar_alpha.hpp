@@ -1,5 +1,5 @@
-// The detectors' threshold arithmetic behind blah2hip_cfar_alpha and blah2hip_oscfar_alpha (detect.hip validates and calls
-// cfar_alpha_fill / oscfar_alpha_fill).  Host only, C++17 and libm, no HIP: tests/host/emulate_cfar_alpha.cpp compiles it
+// The detectors' threshold arithmetic behind blah2hip_cfar_alpha, blah2hip_oscfar_alpha and blah2hip_cmap_alpha (detect.hip
+// validates and calls cfar_alpha_fill / oscfar_alpha_fill / cmap_alpha_fill).  Host only, C++17 and libm, no HIP: tests/host/emulate_cfar_alpha.cpp compiles it
 // on its own.  The formulas are in include/blah2hip.h.  Everything here has internal linkage (the unnamed namespace): the
 // library exports none of it, and nothing the compiler emits out of line -- the thread objects of run_slices included --
 // can be interposed.
@@ -233,6 +233,42 @@ inline void oscfar_alpha_fill(double pfa, uint32_t looks, uint32_t rank_permille
       alpha[n] = looks == 1 ? os_alpha1(pfa, (uint32_t)n, k) : os_alpha_looks(pfa, (uint32_t)n, k, looks, lf.data());
     }
   });
+}
+
+// ---- clutter map ----
+// log Pfa(alpha) of a cell against alpha b at age a > T, b the map's average of memory T (include/blah2hip.h):
+// -sum_i log1p(alpha c_i) over the weights w (1 - w)^m, m = 0 .. a - T - 1, newest first, then T times (1 - w)^(a - T) / T,
+// w = 1 / T; the powers by repeated multiplication, the sum in this order (process.py: clutter_map_alpha does the same
+// operations)
+inline double cmap_logpfa(double alpha, uint32_t a, uint32_t T)
+{
+  const double w = 1.0 / (double)T, q = 1.0 - w;
+  double g = 1.0, s = 0.0;
+  for (uint32_t m = 0; m < a - T; m++) {
+    s -= std::log1p(alpha * (w * g));
+    g *= q;
+  }
+  return s - (double)T * std::log1p(alpha * (g / (double)T));
+}
+
+// blah2hip_cmap_alpha past its checks.  a <= T: the mean of a values, a (pfa^(-1/a) - 1) as cfar_alpha_fill has it.
+// T < a <= 16 T: a bisection of about 60 evaluations of a - T + 1 terms each; entries beyond 16 T repeat that one.
+inline void cmap_alpha_fill(double pfa, uint32_t T, uint32_t max_age, double *alpha)
+{
+  alpha[0] = std::nan("");
+  const double lp = std::log(pfa);
+  const uint32_t last = std::min<uint64_t>(max_age, 16ull * T);
+  for (uint32_t a = 1; a <= std::min(last, T); a++) alpha[a] = (double)a * (pow(pfa, -1.0 / (double)a) - 1);
+  const uint64_t terms = last > T ? (uint64_t)(last - T) * (last - T) / 2 : 0;
+  const uint32_t nThreads = terms < 50000 ? 1u : table_threads();
+  run_slices(nThreads, [=](uint32_t first) {
+    for (uint64_t a = (uint64_t)T + 1 + first; a <= last; a += nThreads) {
+      double hi = 1.0;
+      while (cmap_logpfa(hi, (uint32_t)a, T) > lp) hi *= 2.0;
+      alpha[a] = bisect_upper(0.0, hi, [&](double x) { return cmap_logpfa(x, (uint32_t)a, T) > lp; });
+    }
+  });
+  for (uint64_t a = (uint64_t)last + 1; a <= max_age; a++) alpha[a] = alpha[last];
 }
 
 } // namespace

@@ -1,14 +1,26 @@
 // Detection behind include/blah2hip.h: 1-D and 2-D CFAR (cell-averaging and ordered-statistic) with their threshold-table
-// caches and summed-area table, Centroid and Interpolate on the host and on the device.  Host code; the kernels are
-// cfar_kernels.hpp's, oscfar_kernels.hpp's and detect_kernels.hpp's.
+// caches and summed-area table, the clutter map and its gate, Centroid and Interpolate on the host and on the device.  Host
+// code; the kernels are cfar_kernels.hpp's, oscfar_kernels.hpp's, cmap_kernels.hpp's and detect_kernels.hpp's.
 #include "amb_handle.hpp"
 #include "cfar_kernels.hpp"
+#include "cmap_kernels.hpp"
 #include "detect_kernels.hpp"
 #include "oscfar_kernels.hpp"
 
 #include "cfar_alpha.hpp"
 
 using namespace blah2;
+
+// The clutter map of ONE ambiguity handle (its geometry, buffers and timer): the memory, the age, the plane b and the
+// threshold tables of the pfa values it has seen
+struct blah2hip_cmap_s {
+  blah2hip_amb_s *amb = nullptr;
+  uint32_t memory = 0, flags = 0;
+  uint64_t age = 0;      // CPIs absorbed since the creation or the last reset
+  float *d_bg = nullptr; // [cells]: b
+  struct Table { double pfa; double *d; bool pinned; };
+  std::vector<Table> tables; // alpha[0 .. 16 T] per pfa, least recently used first
+};
 
 namespace {
 
@@ -341,9 +353,218 @@ int cfar1d_pin(bool os, blah2hip_amb_s *h, double pfa, uint32_t permille, int32_
   return cfar_table(h, pfa, permille, (size_t)(2 * n_train), &d, &r, nullptr, true);
 }
 
+// The clutter map's table of this pfa on the device: cfar_table's rules (a hit hands out the pointer, a miss builds and
+// uploads, blocking, and is refused while `st` is being captured; eight unpinned tables, what *_prepare made stays)
+int cmap_table(blah2hip_cmap_s *cm, double pfa, const double **alpha, hipStream_t st = nullptr, bool pin = false)
+{
+  auto &T = cm->tables;
+  for (size_t i = 0; i < T.size(); i++)
+    if (T[i].pfa == pfa) {
+      blah2hip_cmap_s::Table t = T[i];
+      t.pinned = t.pinned || pin;
+      T.erase(T.begin() + (long)i);
+      T.push_back(t);
+      *alpha = t.d;
+      return BLAH2HIP_OK;
+    }
+  if (st) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+      return fail(BLAH2HIP_ERR_INVALID, "clutter-map table of this pfa is not resident: call blah2hip_cmap_prepare before capturing the stream");
+  }
+  const uint32_t last = CMAP_AGES * cm->memory;
+  std::vector<double> host(last + 1);
+  cmap_alpha_fill(pfa, cm->memory, last, host.data());
+  size_t unpinned = 0;
+  for (const auto &e : T) unpinned += e.pinned ? 0 : 1;
+  if (unpinned >= CFAR_TABLES_MAX) {
+    HIPCHK(hipDeviceSynchronize()); // the oldest unpinned table may still be read by enqueued work
+    for (size_t i = 0; i < T.size(); i++)
+      if (!T[i].pinned) {
+        (void)hipFree(T[i].d);
+        T.erase(T.begin() + (long)i);
+        break;
+      }
+  }
+  blah2hip_cmap_s::Table t{pfa, nullptr, pin};
+  HIPCHK(hipMalloc(&t.d, host.size() * sizeof(double)));
+  hipError_t e = hipMemcpy(t.d, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    (void)hipFree(t.d);
+    return fail(BLAH2HIP_ERR_HIP, std::string("clutter-map table upload: ") + hipGetErrorString(e));
+  }
+  T.push_back(t);
+  *alpha = t.d;
+  return BLAH2HIP_OK;
+}
+
+int cmap_check_pfa(double pfa)
+{
+  if (!(pfa > 0.0 && pfa < 1.0)) return fail(BLAH2HIP_ERR_INVALID, "pfa outside (0, 1)");
+  return BLAH2HIP_OK;
+}
+
 } // namespace
 
 extern "C" {
+
+// ------------------------------------------------------------ clutter map --
+// Host arithmetic only (cfar_alpha.hpp)
+int blah2hip_cmap_alpha(double pfa, uint32_t memory, uint32_t max_age, double *alpha)
+{
+  if (!alpha) return fail(BLAH2HIP_ERR_INVALID, "NULL table");
+  if (memory == 0 || memory > BLAH2HIP_MAX_CMAP_MEMORY) return fail(BLAH2HIP_ERR_INVALID, "memory outside [1, BLAH2HIP_MAX_CMAP_MEMORY]");
+  if (int rc = cmap_check_pfa(pfa)) return rc;
+  cmap_alpha_fill(pfa, memory, max_age, alpha);
+  return BLAH2HIP_OK;
+}
+
+int blah2hip_cmap_create(blah2hip_amb_t amb, uint32_t memory, uint32_t flags, blah2hip_cmap_t *out)
+{
+  if (!amb || !out) return fail(BLAH2HIP_ERR_INVALID, "NULL argument");
+  if (memory == 0 || memory > BLAH2HIP_MAX_CMAP_MEMORY) return fail(BLAH2HIP_ERR_INVALID, "memory outside [1, BLAH2HIP_MAX_CMAP_MEMORY]");
+  if (flags & ~(uint32_t)BLAH2HIP_CMAP_NORMALISE) return fail(BLAH2HIP_ERR_INVALID, "unknown flag bits");
+  const size_t cells = (size_t)amb->dims.n_doppler_bins * amb->dims.n_delay_bins;
+  if (cells >= (1ull << 32)) return fail(BLAH2HIP_ERR_UNSUPPORTED, "clutter map: more than 2^32 - 1 cells");
+  HIPCHK(hipSetDevice(amb->device));
+  blah2hip_cmap_s *cm = new blah2hip_cmap_s;
+  cm->amb = amb;
+  cm->memory = memory;
+  cm->flags = flags;
+  hipError_t e = hipMalloc(&cm->d_bg, cells * sizeof(float));
+  if (e == hipSuccess) e = hipMemset(cm->d_bg, 0, cells * sizeof(float)); // what blah2hip_cmap_read_background shows before the first CPI
+  if (e != hipSuccess) {
+    (void)hipFree(cm->d_bg);
+    delete cm;
+    return fail(BLAH2HIP_ERR_HIP, std::string("hipMalloc(clutter map): ") + hipGetErrorString(e));
+  }
+  *out = cm;
+  return BLAH2HIP_OK;
+}
+
+int blah2hip_cmap_destroy(blah2hip_cmap_t cm)
+{
+  if (!cm) return BLAH2HIP_OK;
+  int rc = BLAH2HIP_OK;
+  (void)hipSetDevice(cm->amb->device);
+  (void)hipDeviceSynchronize(); // enqueued calls may still use the plane and the tables
+  if (hipFree(cm->d_bg) != hipSuccess) rc = fail(BLAH2HIP_ERR_HIP, "hipFree(clutter map)");
+  for (auto &t : cm->tables)
+    if (hipFree(t.d) != hipSuccess) rc = fail(BLAH2HIP_ERR_HIP, "hipFree(clutter-map table)");
+  delete cm;
+  return rc;
+}
+
+int blah2hip_cmap_reset(blah2hip_cmap_t cm)
+{
+  if (!cm) return fail(BLAH2HIP_ERR_INVALID, "NULL handle");
+  cm->age = 0; // the plane keeps its bytes: the first CPI of the new count overwrites them unread
+  return BLAH2HIP_OK;
+}
+
+int blah2hip_cmap_age(blah2hip_cmap_t cm, uint64_t *age)
+{
+  if (!cm || !age) return fail(BLAH2HIP_ERR_INVALID, "NULL argument");
+  *age = cm->age;
+  return BLAH2HIP_OK;
+}
+
+int blah2hip_cmap_prepare(blah2hip_cmap_t cm, double pfa)
+{
+  if (!cm) return fail(BLAH2HIP_ERR_INVALID, "NULL handle");
+  if (int rc = cmap_check_pfa(pfa)) return rc;
+  HIPCHK(hipSetDevice(cm->amb->device));
+  const double *d = nullptr;
+  return cmap_table(cm, pfa, &d, nullptr, true);
+}
+
+int blah2hip_cmap_process_dev(blah2hip_cmap_t cm, const void *d_map, const double *d_metrics, uint32_t n_cpi, double pfa,
+                              int32_t min_delay, double min_doppler, blah2hip_hit_t *d_hits, uint32_t cap, uint32_t *d_count,
+                              uint8_t *d_out_exceed, float *d_out_level, void *stream)
+{
+  if (!cm) return fail(BLAH2HIP_ERR_INVALID, "NULL handle");
+  blah2hip_amb_s *h = cm->amb;
+  if (n_cpi == 0 || n_cpi > h->dims.max_batch) return fail(BLAH2HIP_ERR_INVALID, "n_cpi outside [1, max_batch]");
+  int rc;
+  if ((rc = cmap_check_pfa(pfa))) return rc;
+  if ((d_hits == nullptr) != (d_count == nullptr)) return fail(BLAH2HIP_ERR_INVALID, "d_hits and d_count: both or neither");
+  if (d_hits && cap == 0) return fail(BLAH2HIP_ERR_INVALID, "cap is 0");
+  const cf *map = d_map ? (const cf *)d_map : h->d_map;
+  if ((uintptr_t)map & 7) return fail(BLAH2HIP_ERR_INVALID, "a map is not 8-byte aligned");
+  if (h->cfarLooks > 1)
+    return fail(BLAH2HIP_ERR_UNSUPPORTED, "clutter map: the thresholds are made for one look per cell (BLAH2HIP_OPT_CFAR_LOOKS is above 1)");
+  HIPCHK(hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  CmapArgs a;
+  if ((rc = cmap_table(cm, pfa, &a.alpha, st))) return rc;
+  if (d_count) HIPCHK(hipMemsetAsync(d_count, 0, n_cpi * sizeof(uint32_t), st));
+  const size_t cells = (size_t)h->dims.n_doppler_bins * h->dims.n_delay_bins;
+  a.map = map;
+  a.metrics = d_metrics ? d_metrics : h->d_metrics;
+  a.doppler = h->d_doppler;
+  a.bg = cm->d_bg;
+  a.hits = d_hits;
+  a.count = d_count;
+  a.exceed = d_out_exceed;
+  a.level = d_out_level;
+  a.cells = (uint32_t)cells;
+  a.nCpi = n_cpi;
+  a.nDelay = (int32_t)h->dims.n_delay_bins;
+  a.delayMin = h->delayMin;
+  a.minDelay = min_delay;
+  a.minDoppler = min_doppler;
+  a.cap = cap;
+  // The age travels in the launch arguments: a captured graph repeats the launch, not the count.  Nothing looks beyond
+  // age 16 T (the table's last entry, k = T), so the argument stops there.
+  a.age0 = (uint32_t)std::min<uint64_t>(cm->age, (uint64_t)CMAP_AGES * cm->memory);
+  a.memory = cm->memory;
+  a.normalise = (cm->flags & BLAH2HIP_CMAP_NORMALISE) ? 1u : 0u;
+  const uint32_t G = (uint32_t)(((cells + 1) / 2 + 255) / 256);
+  if ((rc = tic(h, BLAH2HIP_K_CFAR, st))) return rc;
+  hipLaunchKernelGGL(cmap_kernel, dim3(G), dim3(256), 0, st, a);
+  HIPCHK(hipGetLastError());
+  if ((rc = toc(h, BLAH2HIP_K_CFAR, st))) return rc;
+  cm->age += n_cpi;
+  return BLAH2HIP_OK;
+}
+
+int blah2hip_cmap_gate_dev(blah2hip_cmap_t cm, const uint8_t *d_exceed, uint32_t n_cpi, const blah2hip_hit_t *d_hits, uint32_t cap,
+                           const uint32_t *d_count, blah2hip_hit_t *d_hits_out, uint32_t *d_count_out, void *stream)
+{
+  if (!cm || !d_exceed || !d_hits || !d_count || !d_hits_out || !d_count_out) return fail(BLAH2HIP_ERR_INVALID, "NULL argument");
+  blah2hip_amb_s *h = cm->amb;
+  if (n_cpi == 0 || n_cpi > h->dims.max_batch) return fail(BLAH2HIP_ERR_INVALID, "n_cpi outside [1, max_batch]");
+  if (cap == 0) return fail(BLAH2HIP_ERR_INVALID, "cap is 0");
+  const size_t listBytes = (size_t)n_cpi * cap * sizeof(blah2hip_hit_t), countBytes = n_cpi * sizeof(uint32_t);
+  if (ranges_overlap(d_hits, listBytes, d_hits_out, listBytes) || ranges_overlap(d_count, countBytes, d_count_out, countBytes))
+    return fail(BLAH2HIP_ERR_INVALID, "gate: the output list overlaps the input list (the compaction cannot run in place)");
+  HIPCHK(hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  GateArgs a;
+  a.exceed = d_exceed;
+  a.hits = d_hits;
+  a.count = d_count;
+  a.out = d_hits_out;
+  a.countOut = d_count_out;
+  a.nD = (int32_t)h->dims.n_doppler_bins;
+  a.nDelay = (int32_t)h->dims.n_delay_bins;
+  a.cap = cap;
+  int rc;
+  if ((rc = tic(h, BLAH2HIP_K_CFAR, st))) return rc;
+  hipLaunchKernelGGL(hits_gate_kernel, dim3(n_cpi), dim3(256), 0, st, a);
+  HIPCHK(hipGetLastError());
+  return toc(h, BLAH2HIP_K_CFAR, st);
+}
+
+int blah2hip_cmap_read_background(blah2hip_cmap_t cm, float *b)
+{
+  if (!cm || !b) return fail(BLAH2HIP_ERR_INVALID, "NULL argument");
+  blah2hip_amb_s *h = cm->amb;
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(b, cm->d_bg, (size_t)h->dims.n_doppler_bins * h->dims.n_delay_bins * sizeof(float), hipMemcpyDeviceToHost));
+  return BLAH2HIP_OK;
+}
 
 // ------------------------------------------------------------------- CFAR --
 // Host arithmetic only (cfar_alpha.hpp)

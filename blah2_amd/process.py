@@ -502,6 +502,150 @@ def oscfar_hits(map, delay, doppler, noise_power, alpha, rank, window, min_delay
     return row.astype(np.int32), col.astype(np.int32), snr
 
 
+def clutter_map_weights(age, memory):
+    """The weights ``c_i`` of the clutter map's average ``b = sum_i c_i u_i`` at age ``age >= 1`` (the CPIs absorbed) with
+    memory ``T``, newest value first: ``age`` times ``1 / age`` while ``age <= T``; beyond, ``w (1 - w)^m`` for
+    ``m = 0 .. age - T - 1`` and ``T`` times ``(1 - w)^(age - T) / T``, ``w = 1 / T`` (the powers by repeated
+    multiplication, as blah2hip_cmap_alpha forms them).  float64 ``[age]``; they add up to 1."""
+    a, T = int(age), int(memory)
+    if a < 1 or not 1 <= T <= _lib.MAX_CMAP_MEMORY:
+        raise ValueError("age below 1 or memory outside [1, MAX_CMAP_MEMORY]")
+    if a <= T:
+        return np.full(a, 1.0 / a)
+    w = 1.0 / T
+    q = 1.0 - w
+    out, g = [], 1.0
+    for _ in range(a - T):
+        out.append(w * g)
+        g *= q
+    return np.array(out + [g / T] * T)
+
+
+def _cmap_logpfa(alpha, a, T):
+    """cmap_logpfa of cfar_alpha.hpp, operation for operation (libm's log1p, the sum in the same order)."""
+    import math
+    w = 1.0 / T
+    q = 1.0 - w
+    g, s = 1.0, 0.0
+    for _ in range(a - T):
+        s -= math.log1p(alpha * (w * g))
+        g *= q
+    return s - T * math.log1p(alpha * (g / T))
+
+
+def clutter_map_pfa(alpha, age, memory):
+    """The false-alarm probability of ``u > alpha b`` under noise at age ``age`` with memory ``memory``:
+    ``prod_i 1 / (1 + alpha c_i)`` over :func:`clutter_map_weights`, through the sum of ``log1p``."""
+    import math
+    a, T = int(age), int(memory)
+    if a <= T:
+        return math.exp(-a * math.log1p(float(alpha) / a))
+    return math.exp(_cmap_logpfa(float(alpha), a, T))
+
+
+def clutter_map_alpha(pfa, memory, max_age):
+    """blah2hip_cmap_alpha restated in pure Python: the clutter map's threshold factors ``alpha[a]``, ``a = 1 .. max_age``
+    (``alpha[0]`` is NaN).  ``a <= T``: ``a (pfa^(-1/a) - 1)``.  Beyond: ``clutter_map_pfa(alpha, a, T) = pfa`` by bisection on
+    its logarithm until the interval no longer splits (its upper end); entries beyond ``16 T`` repeat that one.  float64
+    ``[max_age + 1]``."""
+    import math
+    pfa, T, n = float(pfa), int(memory), int(max_age)
+    if not 1 <= T <= _lib.MAX_CMAP_MEMORY:
+        raise ValueError("memory outside [1, MAX_CMAP_MEMORY]")
+    if not 0.0 < pfa < 1.0:
+        raise ValueError("pfa outside (0, 1)")
+    out = np.full(n + 1, np.nan)
+    last = min(n, 16 * T)
+    lp = math.log(pfa)
+    for a in range(1, last + 1):
+        if a <= T:
+            out[a] = a * (math.pow(pfa, -1.0 / a) - 1)
+            continue
+        lo, hi = 0.0, 1.0
+        while _cmap_logpfa(hi, a, T) > lp:
+            hi *= 2.0
+        while True:
+            mid = 0.5 * (lo + hi)
+            if mid == lo or mid == hi:
+                break
+            if _cmap_logpfa(mid, a, T) > lp:
+                lo = mid
+            else:
+                hi = mid
+        out[a] = hi
+    out[last + 1:] = out[last]
+    return out
+
+
+def clutter_map_alpha_table(pfa, memory, max_age):
+    """blah2hip_cmap_alpha itself (host arithmetic of the library, no GPU touched): float64 ``[max_age + 1]``."""
+    out = np.empty(int(max_age) + 1, dtype=np.float64)
+    check(_lib.load().blah2hip_cmap_alpha(float(pfa), int(memory), int(max_age), _ptr(out)))
+    return out
+
+
+def clutter_map(maps, levels, alpha, memory, state=None, detail=False):
+    """The clutter-map detector of include/blah2hip.h restated in fp64 NumPy.  ``maps``: complex ``[n_cpi, n_doppler,
+    n_delay]`` in time order; ``levels``: ``[n_cpi]`` factors ``s[c]`` (the device's ``d_out_level``, or ``10 ** (-noisePower /
+    5)``), None for the detector without normalisation; ``alpha``: the table of :func:`clutter_map_alpha` for at least
+    ``min(last age, 16 T)`` entries; ``state``: the dict an earlier call returned through this argument (``{"b", "age",
+    "umax"}``; None or empty: age 0).  Per CPI ``u = |M|^2 s``, ``exceeds <=> age >= 1 and u > alpha[min(age, 16 T)] b``,
+    then ``b = u`` at age 0 and ``b += r (u - b)`` with ``r`` the fp32 quotient ``1 / min(age + 1, T)`` otherwise; a cell
+    whose ``u`` is not finite neither exceeds nor updates (at age 0 it starts from ``b = 0``).  Returns ``(exceed uint8
+    [n_cpi, n_doppler, n_delay], b float64 [n_doppler, n_delay])`` and updates ``state`` (``umax``: the largest ``u`` a cell
+    has absorbed).  ``detail``: a third value ``{"u", "thr"}``, both ``[n_cpi, ...]``: ``u`` and ``alpha b`` at the decision
+    (``thr`` is NaN at age 0)."""
+    m = np.asarray(maps)
+    if m.ndim != 3:
+        raise ValueError("maps must be [n_cpi, n_doppler, n_delay]")
+    T = int(memory)
+    if not 1 <= T <= _lib.MAX_CMAP_MEMORY:
+        raise ValueError("memory outside [1, MAX_CMAP_MEMORY]")
+    alpha = np.asarray(alpha, dtype=np.float64)
+    state = {} if state is None else state
+    age = int(state.get("age", 0))
+    b = np.zeros(m.shape[1:]) if age == 0 else np.array(state["b"], dtype=np.float64)
+    umax = np.zeros(m.shape[1:]) if age == 0 else np.array(state["umax"], dtype=np.float64)
+    exceed = np.zeros(m.shape, dtype=np.uint8)
+    us, thrs = [], []
+    for c in range(m.shape[0]):
+        re, im = m[c].real.astype(np.float64), m[c].imag.astype(np.float64)
+        with np.errstate(invalid="ignore", over="ignore"):
+            u = re * re + im * im
+            if levels is not None:
+                u = u * float(levels[c])
+            fin = np.isfinite(u)
+            thr = np.full(u.shape, np.nan)
+            if age >= 1:
+                thr = alpha[min(age, 16 * T)] * b
+                exceed[c] = fin & (u > thr)
+            if age == 0:
+                b = np.where(fin, u, 0.0)
+            else:
+                r = float(np.float32(1.0) / np.float32(min(age + 1, T)))
+                b = np.where(fin, b + r * (np.where(fin, u, 0.0) - b), b)
+            umax = np.where(fin, np.maximum(umax, np.where(fin, u, 0.0)), umax)
+        if detail:
+            us.append(u)
+            thrs.append(thr)
+        age += 1
+    state.update(b=b, age=age, umax=umax)
+    if detail:
+        return exceed, b, {"u": np.array(us), "thr": np.array(thrs)}
+    return exceed, b
+
+
+def gate_hits(hits, count, exceed):
+    """hits_gate_kernel restated: of the first ``min(count, cap)`` records of ``hits`` (:data:`HIT_DTYPE` ``[cap]``, one
+    CPI) those inside the map whose byte of ``exceed [n_doppler, n_delay]`` is not zero, in their order."""
+    h = np.asarray(hits)[:min(int(count), len(hits))]
+    ex = np.asarray(exceed)
+    inside = (h["row"] >= 0) & (h["row"] < ex.shape[0]) & (h["col"] >= 0) & (h["col"] < ex.shape[1])
+    keep = inside.copy()
+    keep[inside] = ex[h["row"][inside], h["col"][inside]] != 0
+    return h[keep]
+
+
 def integrate_ends(n_cpi, window, hop=None, start=0):
     """The CPI counts ``g`` at which a window of ``window`` CPIs ends among the CPIs ``start .. start + n_cpi - 1`` of an
     integrator with hop ``hop`` (None: 1): every ``g >= window - 1`` with ``(g - (window - 1)) % hop == 0``."""
@@ -1781,6 +1925,69 @@ class MapIntegrator:
         # (an integrated map is not the engine's device copy: no owner)
         return [Map(None, out[i], amb.delay.copy(), amb.doppler.copy(), float(met[i, 0]), float(met[i, 1]), first + i * self.hop)
                 for i in range(n_out)]
+
+
+class ClutterMapDetector:
+    """Clutter-map CFAR on the maps of ``amb`` (blah2hip_cmap_*; no reference counterpart): every cell against
+    ``alpha[age]`` times the exponentially weighted average of its own past power, memory ``memory`` CPIs, at false-alarm
+    probability ``pfa``.  ``normalise``: the cells are scaled by each CPI's level first (BLAH2HIP_CMAP_NORMALISE).  On its
+    own it leaves hit lists like the other detectors'; its exceed plane gates theirs (``gate_dev``): a cell that is bright
+    in every CPI is not reported, an echo that moves through cells is.  The average and the age carry over from call to
+    call; ``close()`` it before its ``amb``."""
+
+    def __init__(self, amb, pfa, memory, minDelay, minDoppler, normalise=True):
+        if not -128 <= int(minDelay) <= 127:  # int8_t in the reference's detector
+            raise ValueError("minDelay outside int8 range")
+        h = C.c_void_p()
+        check(amb._L.blah2hip_cmap_create(amb._h, int(memory), _lib.CMAP_NORMALISE if normalise else 0, C.byref(h)))
+        self._h, self._L, self.amb = h, amb._L, amb
+        self.pfa, self.memory, self.minDelay, self.minDoppler = float(pfa), int(memory), int(minDelay), float(minDoppler)
+        self.normalise = bool(normalise)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            if getattr(self.amb, "_h", None):  # (as MapIntegrator.close: never through a closed handle)
+                self._L.blah2hip_cmap_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def prepare(self):
+        """The threshold table of ``pfa`` onto the device ahead of time (blah2hip_cmap_prepare; blocking)."""
+        check(self._L.blah2hip_cmap_prepare(self._h, self.pfa))
+
+    def reset(self):
+        """Age 0: the next CPI starts the average anew (host only)."""
+        check(self._L.blah2hip_cmap_reset(self._h))
+
+    def age(self):
+        """CPIs absorbed since the creation or the last reset."""
+        a = C.c_uint64(0)
+        check(self._L.blah2hip_cmap_age(self._h, C.byref(a)))
+        return a.value
+
+    def background(self):
+        """``b``: float32 ``[n_doppler, n_delay]`` (waits for the device)."""
+        out = np.empty((self.amb.dims.n_doppler_bins, self.amb.dims.n_delay_bins), dtype=np.float32)
+        check(self._L.blah2hip_cmap_read_background(self._h, _ptr(out)))
+        return out
+
+    def process_dev(self, n_cpi, d_hits, cap, d_count, d_map=None, d_metrics=None, d_exceed=None, d_level=None, stream=0):
+        """Enqueue the next ``n_cpi`` CPIs (blah2hip_cmap_process_dev; raw pointers/ints): hit records into ``d_hits [n_cpi]
+        [cap]`` and counts into ``d_count [n_cpi]`` (both None: no list), the uint8 plane ``d_exceed [n_cpi][n_doppler]
+        [n_delay]`` and the levels ``d_level [n_cpi]`` when given.  ``d_map`` / ``d_metrics``: None = the engine's own."""
+        check(self._L.blah2hip_cmap_process_dev(self._h, d_map, d_metrics, int(n_cpi), self.pfa, self.minDelay, self.minDoppler,
+                                                d_hits, int(cap), d_count, d_exceed, d_level, stream))
+
+    def gate_dev(self, d_exceed, n_cpi, d_hits, cap, d_count, d_hits_out, d_count_out, stream=0):
+        """Enqueue the gate (blah2hip_cmap_gate_dev): the records of ``d_hits`` whose cell has a non-zero byte in
+        ``d_exceed``, in their order, into ``d_hits_out [n_cpi][cap]`` / ``d_count_out [n_cpi]``."""
+        check(self._L.blah2hip_cmap_gate_dev(self._h, d_exceed, int(n_cpi), d_hits, int(cap), d_count, d_hits_out, d_count_out,
+                                             stream))
 
 
 class Centroid:

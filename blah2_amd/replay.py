@@ -614,6 +614,17 @@ class GpuChain:
     ``cfg["detection"]["rank"]`` (default 0.75) in the place of ``CfarDetector1D``, for the integrator's looks as well; the
     hit buffers, the finisher and the results are the same.
 
+    ``cfg["detection"]["clutterMap"] = {"memory": T, "mode": "gate" | "detect"}`` puts a
+    :class:`blah2_amd.ClutterMapDetector` of memory T CPIs (normalised, at the detector's pfa -- ``pfa / K`` behind a rate
+    bank) on the buffers the detector reads.  ``gate`` (default): the configured detector runs as before, cmap_kernel writes
+    the batch's exceed planes, and the gate keeps the hits whose cell exceeded its own history -- the finisher and the
+    downloads read the gated list, so an echo that sits in one cell CPI after CPI stops being reported after the first
+    frames and one that moves stays.  ``detect``: the clutter map's own hit list takes the detector's place.  The history
+    runs on from batch to batch (a skipped CPI's map is absorbed like any other); :meth:`run_batches` starts a capture at
+    age 0.  ValueError, naming ``detection.clutterMap``: a memory outside [1, 64], an unknown mode, detection not enabled,
+    ``integrate`` configured (the thresholds are one-look), and -- from :meth:`shard_check` -- more than one rank (the
+    batches go round-robin: no rank sees consecutive CPIs).  Without the key nothing is allocated or launched.
+
     ``cfg["ambiguity"]["window"]`` names a Doppler taper (``blah2_amd.doppler_taper``: hann, hamming, blackman,
     blackmanharris, nuttall, flattop; ``NAME:norm`` divides the taps by a_0): one stencil kernel directly behind the
     ambiguity stage on the compute stream (``Ambiguity.taper_dev``), and everything after it -- the integrator, the
@@ -798,6 +809,28 @@ class GpuChain:
                     self.amb.close()
                     raise ValueError(f"integrate.tracks = {trk!r}: {e}") from None
         self.nci_tracks = self.nci is not None and self.nci.n_rates > 0
+        # detection: {clutterMap: {memory: T, mode: gate | detect}}: every cell against its own history (None: no such stage)
+        self.cmap, self.cmap_mode = None, None
+        cm_c = det_c.get("clutterMap")
+        cm_c = None if cm_c is False else cm_c
+        if cm_c is not None:
+            try:
+                if not isinstance(cm_c, dict) or isinstance(cm_c.get("memory"), bool) or not isinstance(cm_c.get("memory"), int):
+                    raise ValueError("{memory: T, mode: gate | detect} with T a number of CPIs")
+                if not 1 <= cm_c["memory"] <= blah2_amd._lib.MAX_CMAP_MEMORY:
+                    raise ValueError(f"memory outside [1, {blah2_amd._lib.MAX_CMAP_MEMORY}]")
+                self.cmap_mode = str(cm_c.get("mode", "gate")).lower()
+                if self.cmap_mode not in ("gate", "detect"):
+                    raise ValueError(f"mode {self.cmap_mode!r}: 'gate' or 'detect'")
+                if not det_c.get("enable", False):
+                    raise ValueError("detection is not enabled")
+                if self.nci is not None:
+                    raise ValueError("integrate is configured, and the clutter map's thresholds are made for one look per cell")
+            except ValueError as e:
+                if self.nci is not None:
+                    self.nci.close()
+                self.amb.close()
+                raise ValueError(f"detection.clutterMap = {cm_c!r}: {e}") from None
         if det_c.get("enable", False):
             # detection: {cfar: ca | os, rank: 0.75}: the cell-averaging detector of the reference (default), or the
             # ordered-statistic one at that rank on the same window; both leave the same hit lists
@@ -815,6 +848,8 @@ class GpuChain:
             else:
                 self.cfar = blah2_amd.CfarDetector1D(pfa, det_c["nGuard"], det_c["nTrain"], det_c["minDelay"],
                                                      det_c["minDoppler"], **looks)
+            if cm_c is not None:
+                self.cmap = blah2_amd.ClutterMapDetector(self.amb, pfa, cm_c["memory"], det_c["minDelay"], det_c["minDoppler"])
             if "nCentroid" in det_c:  # blah2.cpp:176-181
                 self.centroid = blah2_amd.Centroid(det_c["nCentroid"], det_c["nCentroid"], 1 / (n / self.fs))
                 self.interp = blah2_amd.Interpolate(True, True)
@@ -895,6 +930,12 @@ class GpuChain:
                 s["d_imap"] = torch.zeros((B, nD, nC), dtype=torch.complex64, device=dev)
                 s["d_imet"] = torch.zeros((B, 2), dtype=torch.float64, device=dev)
                 s["nci"] = (0, 0, 0)  # (count before the batch, windows that end in it, count at which the first ends)
+            if self.cmap is not None and self.cmap_mode == "gate":  # the exceed planes, the gated list, the detector's own counts
+                s["d_exc"] = torch.zeros((B, nD, nC), dtype=torch.uint8, device=dev)
+                s["d_ghits"] = torch.zeros((B, self.cap, 2), dtype=torch.float64, device=dev)
+                s["d_gcnt"] = torch.zeros(B, dtype=torch.int32, device=dev)
+                s["h_rcnt"] = torch.zeros(B, dtype=torch.int32).pin_memory()
+            s["hits"], s["cnt"] = s["d_hits"], s["d_cnt"]  # the list the finisher and the downloads read
             self.slots.append(s)
 
     def _fmt_in(self):
@@ -1021,10 +1062,19 @@ class GpuChain:
                 self._g += cnt
                 maps, mets = slot["d_imap"], slot["d_imet"]
             if self.cfar is not None and n_maps:
-                self.cfar.process_dev(amb, n_maps, slot["d_hits"].data_ptr(), self.cap, slot["d_cnt"].data_ptr(),
-                                      maps.data_ptr(), mets.data_ptr(), st)
+                if self.cmap_mode == "detect":  # the clutter map's own list in the detector's place
+                    self.cmap.process_dev(n_maps, slot["d_hits"].data_ptr(), self.cap, slot["d_cnt"].data_ptr(),
+                                          maps.data_ptr(), mets.data_ptr(), None, None, st)
+                else:
+                    self.cfar.process_dev(amb, n_maps, slot["d_hits"].data_ptr(), self.cap, slot["d_cnt"].data_ptr(),
+                                          maps.data_ptr(), mets.data_ptr(), st)
+                if self.cmap_mode == "gate":  # the exceed planes, no list; then the detector's hits whose cell exceeded
+                    self.cmap.process_dev(n_maps, None, 0, None, maps.data_ptr(), mets.data_ptr(), slot["d_exc"].data_ptr(), None, st)
+                    self.cmap.gate_dev(slot["d_exc"].data_ptr(), n_maps, slot["d_hits"].data_ptr(), self.cap, slot["d_cnt"].data_ptr(),
+                                       slot["d_ghits"].data_ptr(), slot["d_gcnt"].data_ptr(), st)
+                    slot["hits"], slot["cnt"] = slot["d_ghits"], slot["d_gcnt"]
                 if self.finisher is not None:
-                    self.finisher.process_dev(amb, n_maps, slot["d_hits"].data_ptr(), self.cap, slot["d_cnt"].data_ptr(),
+                    self.finisher.process_dev(amb, n_maps, slot["hits"].data_ptr(), self.cap, slot["cnt"].data_ptr(),
                                               slot["d_dets"].data_ptr(), self.cap, slot["d_dcnt"].data_ptr(),
                                               maps.data_ptr(), mets.data_ptr(), st)
             slot["computed"].record(self.compute)
@@ -1035,12 +1085,14 @@ class GpuChain:
                 nok = cnt * self.clutter_blocks
                 slot["h_ok"][:nok].copy_(slot["d_ok"][:nok], non_blocking=True)
             if self.cfar is not None:
-                slot["h_cnt"][:n_maps].copy_(slot["d_cnt"][:n_maps], non_blocking=True)  # (device path: for the capacity check)
+                slot["h_cnt"][:n_maps].copy_(slot["cnt"][:n_maps], non_blocking=True)  # (device path: for the capacity check)
+                if self.cmap_mode == "gate":  # the gated count never passes the capacity: the check needs the detector's own
+                    slot["h_rcnt"][:n_maps].copy_(slot["d_cnt"][:n_maps], non_blocking=True)
                 if self.finisher is not None:
                     slot["h_dcnt"][:n_maps].copy_(slot["d_dcnt"][:n_maps], non_blocking=True)
                     slot["h_dets"][:n_maps].copy_(slot["d_dets"][:n_maps, :self.hit_copy], non_blocking=True)
                 else:
-                    slot["h_hits"][:n_maps].copy_(slot["d_hits"][:n_maps, :self.hit_copy], non_blocking=True)
+                    slot["h_hits"][:n_maps].copy_(slot["hits"][:n_maps, :self.hit_copy], non_blocking=True)
             if self.need_map:
                 slot["h_map"][:n_maps].copy_(maps[:n_maps], non_blocking=True)
             slot["downloaded"].record(self.copy)
@@ -1084,8 +1136,9 @@ class GpuChain:
                 r["window"] = self.nci.window
             if self.cfar is not None:
                 k = int(slot["h_cnt"][b])
-                if k > self.cap:
-                    raise b2.Blah2HipError(b2._lib.ERR_CAPACITY, f"{k} detections in one CPI, capacity {self.cap}")
+                k_raw = int(slot["h_rcnt"][b]) if self.cmap_mode == "gate" else k
+                if k_raw > self.cap:
+                    raise b2.Blah2HipError(b2._lib.ERR_CAPACITY, f"{k_raw} detections in one CPI, capacity {self.cap}")
                 if self.finisher is not None:  # the final records, made on the device: sorted into emission order, no library call
                     kd = int(slot["h_dcnt"][b])
                     if kd > self.hit_copy:  # rare: beyond what the pipelined copy carries
@@ -1099,7 +1152,7 @@ class GpuChain:
                     res.append(r)
                     continue
                 if k > self.hit_copy:  # rare: more hits than the pipelined copy carries -- fetch this CPI's records now
-                    recs = slot["d_hits"][b, :k].cpu().numpy()
+                    recs = slot["hits"][b, :k].cpu().numpy()
                 else:
                     recs = slot["h_hits"][b, :max(k, 1)].numpy()
                 det = b2.hits_to_detection(amb, recs.view(b2.HIT_DTYPE).reshape(-1), k, self.cap)
@@ -1122,6 +1175,8 @@ class GpuChain:
         the reader threads never wait for Python.  A capture of another layout than the chain's is a ValueError."""
         self._check_capture(capture)
         self.reset_integrator()
+        if self.cmap is not None:
+            self.cmap.reset()  # a new capture: age 0
         batches = list(batches)
         D, n = self.depth, len(batches)
         reads = {}
@@ -1180,7 +1235,11 @@ class GpuChain:
     def shard_check(self, world: int):
         """:func:`replay` over ``world`` ranks deals the batches round-robin, so a rank does not see the CPIs in front of
         its batch: an integrating chain then needs windows that do not overlap and do not cross a batch's end (hop ==
-        window, batch a multiple of the window), and starts every batch at count 0.  ValueError otherwise."""
+        window, batch a multiple of the window), and starts every batch at count 0.  ValueError otherwise.  A clutter map
+        needs every CPI in order, whatever the batch: more than one rank is a ValueError."""
+        if self.cmap is not None and world > 1:
+            raise ValueError(f"detection.clutterMap over {world} ranks: the batches go round-robin, so no rank sees the "
+                             "consecutive CPIs a cell's history is made of")
         if self.nci is None or world <= 1:
             return
         W, H = self.nci.window, self.nci.hop
@@ -1201,6 +1260,8 @@ class GpuChain:
         self.release_all()
         if self.nci is not None:
             self.nci.close()
+        if self.cmap is not None:
+            self.cmap.close()
 
 
 def gpu_processor(cfg: dict, device: int = 0, batch: int = 1, want_map: bool = False, **kw) -> GpuChain:
@@ -1300,6 +1361,11 @@ def main(argv=None):
                     help="the detector: ca (cell averaging, the reference's) or os[:RANK] (ordered statistic: the threshold "
                          "from the RANK-th part of the sorted training cells, default 0.75); overrides "
                          "process.detection.cfar / .rank of the config")
+    ap.add_argument("--clutter-map", default=None, metavar="T[:detect]",
+                    help="a clutter-map CFAR of memory T CPIs (1 .. 64) behind the detector: every cell against the average "
+                         "of its own past power, so what sits in one cell CPI after CPI is no longer reported.  T gates the "
+                         "detector's hits, T:detect reports the clutter map's own.  One rank, not with --integrate.  "
+                         "Overrides process.detection.clutterMap ({memory: T, mode: gate | detect})")
     ap.add_argument("--connect", action="store_true",
                     help="with --json: send the documents to network.ip:ports.map / ports.detection of the config, "
                          "framed like Socket::sendData, instead of printing them")
@@ -1392,6 +1458,18 @@ def main(argv=None):
         cfg["detection"] = dict(cfg.get("detection") or {}, cfar=kind)
         if rank_:
             cfg["detection"]["rank"] = float(rank_)
+    if a.clutter_map is not None:
+        mem_, sep_, mode_ = a.clutter_map.partition(":")
+        try:
+            if not 1 <= int(mem_) <= 64 or (sep_ and mode_ not in ("gate", "detect")):
+                raise ValueError
+        except ValueError:
+            ap.error("--clutter-map takes T or T:detect (T:gate is the default), T a memory of 1 .. 64 CPIs")
+        if cfg.get("integrate"):
+            ap.error("--clutter-map does not go with integration: its thresholds are made for one look per cell")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            ap.error("--clutter-map needs the CPIs in order: one rank")
+        cfg["detection"] = dict(cfg.get("detection") or {}, clutterMap={"memory": int(mem_), "mode": mode_ or "gate"})
     dist = None
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:

@@ -869,6 +869,93 @@ int blah2hip_oscfar2d_process(blah2hip_amb_t h, uint32_t cpi, double pfa, uint32
                               double min_doppler, double *delay, double *doppler, double *snr, uint32_t cap,
                               uint32_t *count);
 
+/* ---- Clutter-map CFAR (Nitzberg; NOT in the reference) and the gate behind the spatial detectors -------
+ * The detectors above compare a cell with its neighbours in the same map, so whatever stands out from its surroundings
+ * is reported in every CPI: a clutter discrete the filter left, the direct path's residue, an interferer's Doppler line.
+ * Here a cell is thresholded against an exponentially weighted average b of its OWN past power: a cell that is always
+ * bright is never reported, an echo that moves through cells is.  Per CPI c of a call, in time order, for every cell:
+ *   p = fmaf(re, re, im * im)                     fp32, nci_power's form
+ *   u = p * s[c]  with BLAH2HIP_CMAP_NORMALISE,   s[c] = (float) exp10(-noisePower[c] / 5) formed in fp64 from
+ *                                                 d_metrics[c][0]; noisePower is the mean of 10 log10|z|, so s is one over
+ *                                                 the squared geometric-mean amplitude of the map: the illuminator's
+ *                                                 content moves the whole map's level from CPI to CPI, and u is what is
+ *                                                 stationary.  Without the flag u = p.
+ *   a = a0 + c                                    the map's age: the CPIs it has absorbed since create or reset (a0: a
+ *                                                 host counter across calls)
+ *   exceeds  <=>  a >= 1  and  (double)u > alpha[min(a, 16 T)] * (double)b        product and compare in fp64
+ *   then, hit or not:  k = min(a + 1, T),  r = 1.f / (float)k (fp32 division),
+ *                      b = u at a == 0,  b = fmaf(r, u - b, b) otherwise
+ * -- the running mean of the first T CPIs, the exponential average of weight 1 / T after them: at every age the estimate
+ * of the lowest variance, with a threshold factor that is exact at every age.  T is the memory, 1 ..
+ * BLAH2HIP_MAX_CMAP_MEMORY.  A cell whose u is NaN or +-Inf neither exceeds nor updates.  At a == 0 the plane's old content
+ * is not read (reset clears nothing); a cell that is not finite then starts from b = 0.  An all-zero map has no exceeding
+ * cell (0 > alpha * 0 is false).
+ * A cell that exceeds is a HIT when it passes the min_delay / min_doppler skips of blah2hip_cfar1d_dev (the same row and
+ * delay tests), with snr = 5 log10(p) - noisePower[c] as there; hits are appended through d_count[c] in arbitrary order and
+ * the count may exceed cap.  The optional plane d_out_exceed [n_cpi][n_doppler][n_delay] of uint8 gets 1 where the cell
+ * exceeds and 0 elsewhere, skips or not.  d_out_level [n_cpi] floats, when not NULL, gets s[c] (1 without the flag), so
+ * that a restatement can be fed the device's own factor.
+ *
+ * Thresholds.  Under noise u is exponential and b = sum_i c_i u_i over independent past values, so
+ *   Pfa(alpha) = prod_i 1 / (1 + alpha c_i).
+ * The weights at age a:  a <= T: a times 1 / a, which gives alpha = a (pfa^(-1/a) - 1), blah2hip_cfar_alpha's one-look
+ * value for n = a;  a > T: w (1 - w)^m for m = 0 .. a - T - 1 and T times (1 - w)^(a - T) / T, with w = 1 / T.
+ * blah2hip_cmap_alpha: host arithmetic only (no GPU is touched).  alpha[0] = NaN; alpha[a], a = 1 .. max_age, solves
+ * Pfa = pfa by bisection on -sum log1p(alpha c_i) until the interval no longer splits (its upper end); entries beyond 16 T
+ * repeat the one at 16 T (the difference to the entry before it is below 1.5e-14 there for T = 4 .. 64).  alpha:
+ * max_age + 1 doubles.  pfa = 1e-2, T = 8: alpha[1 .. 8] = 99, 18, 10.9248, 8.6491, 7.5594, 6.9266, 6.5149, 6.2262,
+ * alpha[16] = 5.45031, alpha[128] = 5.33810.  BLAH2HIP_ERR_INVALID: a NULL table, memory outside
+ * [1, BLAH2HIP_MAX_CMAP_MEMORY], pfa outside (0, 1).
+ * Error of b against the same recursion in fp64 (u from the fp32 cells and the device's s[c] in fp64, r the fp32 quotient):
+ * with eps = 2^-24 and U the largest u the cell has absorbed, u arrives with 3 eps U (two roundings in p, one with the
+ * level) and enters with weight r, the difference u - b rounds once (eps U, weight r), the fma's result once (eps U), and
+ * the step damps the error e that is there by 1 - r:  e' <= (1 - r) e + (4 r + 1) eps U.  From e = 3 eps U at a == 0 this
+ * gives, by induction over the steps (k never falls),  |b - b_fp64| <= (k + 4) 2^-24 U,  k = min(a, T) after a CPIs.
+ * Integrated maps (more than one look per cell) are not built: a call while the ambiguity handle's
+ * BLAH2HIP_OPT_CFAR_LOOKS is above 1 is BLAH2HIP_ERR_UNSUPPORTED. */
+#define BLAH2HIP_MAX_CMAP_MEMORY 64
+#define BLAH2HIP_CMAP_NORMALISE 1 /* flag of blah2hip_cmap_create: u = p * s[c] */
+typedef struct blah2hip_cmap_s *blah2hip_cmap_t;
+int blah2hip_cmap_alpha(double pfa, uint32_t memory, uint32_t max_age, double *alpha);
+/* A clutter map for the maps of `amb` (its geometry), age 0; allocates the plane b, 4 bytes a cell.
+ * BLAH2HIP_ERR_INVALID: a NULL argument, memory outside [1, BLAH2HIP_MAX_CMAP_MEMORY], unknown flag bits. */
+int blah2hip_cmap_create(blah2hip_amb_t amb, uint32_t memory, uint32_t flags, blah2hip_cmap_t *out);
+/* Waits for the device (enqueued calls use the plane and the tables) and frees them.  Call it BEFORE blah2hip_amb_destroy
+ * of its handle. */
+int blah2hip_cmap_destroy(blah2hip_cmap_t cm);
+/* Age 0: the next CPI starts the average anew.  Host only, enqueues nothing (calls enqueued earlier are not affected). */
+int blah2hip_cmap_reset(blah2hip_cmap_t cm);
+/* *age: the CPIs absorbed since the creation or the last reset (the calls enqueued so far included). */
+int blah2hip_cmap_age(blah2hip_cmap_t cm, uint64_t *age);
+/* Builds and uploads alpha[0 .. 16 T] for this pfa ahead of time (blocking).  blah2hip_cmap_process_dev does it on the first
+ * call with a new pfa and only enqueues afterwards; the tables follow the rules of the detectors' cache (eight per clutter
+ * map, least recently used first out, a table built by _prepare stays for the handle's lifetime). */
+int blah2hip_cmap_prepare(blah2hip_cmap_t cm, double pfa);
+/* The next n_cpi CPIs.  d_map / d_metrics as blah2hip_cfar1d_dev takes them (NULL = the ambiguity handle's internal
+ * buffers).  d_hits [n_cpi][cap] and d_count [n_cpi] (zeroed by the call) may BOTH be NULL for gate-only use;
+ * d_out_exceed and d_out_level may be NULL.  One kernel (cmap_kernel; timing counts under BLAH2HIP_K_CFAR) reads every
+ * map cell once, reads b at its start (not at age 0) and writes it once at its end: 8 n_cpi + 8 bytes a cell and call, and
+ * n_cpi more with the exceed plane.  The bits of b, of the exceed planes and of the levels, and the hit sets, do not
+ * depend on how the CPIs were cut into calls.  Calls on one clutter map must be ordered on the device.
+ * The age lives in the launch arguments and is counted on the host, so the call only enqueues and can be captured in a
+ * graph -- a replay repeats the launch, not the count.
+ * BLAH2HIP_ERR_INVALID, with nothing enqueued and the age and the plane as they were: a NULL handle, n_cpi outside
+ * [1, max_batch], pfa outside (0, 1), exactly one of d_hits / d_count NULL, cap == 0 with a list, a map that is not
+ * 8-byte aligned. */
+int blah2hip_cmap_process_dev(blah2hip_cmap_t cm, const void *d_map, const double *d_metrics, uint32_t n_cpi, double pfa,
+                              int32_t min_delay, double min_doppler, blah2hip_hit_t *d_hits, uint32_t cap, uint32_t *d_count,
+                              uint8_t *d_out_exceed, float *d_out_level, void *stream);
+/* The gate: d_hits_out [n_cpi][cap] gets the records of d_hits [n_cpi][cap] whose cell has a non-zero byte in d_exceed
+ * [n_cpi][n_doppler][n_delay], in their order (a stable compaction, one workgroup per CPI: hits_gate_kernel), and
+ * d_count_out [n_cpi] their number.  A count beyond cap means the first cap records are the list; a record outside the map
+ * is dropped.  BLAH2HIP_ERR_INVALID: a NULL argument, n_cpi outside [1, max_batch], cap == 0, an output that overlaps its
+ * input (the compaction cannot run in place). */
+int blah2hip_cmap_gate_dev(blah2hip_cmap_t cm, const uint8_t *d_exceed, uint32_t n_cpi, const blah2hip_hit_t *d_hits,
+                           uint32_t cap, const uint32_t *d_count, blah2hip_hit_t *d_hits_out, uint32_t *d_count_out,
+                           void *stream);
+/* Waits for the device and downloads b: [n_doppler][n_delay] floats (zero before the first CPI). */
+int blah2hip_cmap_read_background(blah2hip_cmap_t cm, float *b);
+
 /* ---- Centroid / Interpolate (host-side, tens of detections) -------------- */
 /* Centroid::process (src/process/detection/Centroid.cpp:19-73): keeps a
  * detection unless a stronger one lies strictly inside its
