@@ -77,6 +77,12 @@ INFO_TRACK_GRID, INFO_TRACK_MAX_SHIFT = 20, 21
 MAX_TRACK_SHIFT = 1048576
 MAX_CMAP_MEMORY = 64
 CMAP_NORMALISE = 1
+MAX_ATOMS = 32
+CLEAN_OPT_GRAM_GRID = 1
+CLEAN_INFO_GRAM_GRID, CLEAN_INFO_SUBTRACT_GRID = 1, 2
+CLK_ATOMS, CLK_GRAM, CLK_FOLD, CLK_SOLVE, CLK_SUBTRACT, CLK_COUNT = 0, 1, 2, 3, 4, 5
+CLEAN_KERNEL_NAMES = {CLK_ATOMS: "clean_atoms", CLK_GRAM: "clean_gram", CLK_FOLD: "clean_fold", CLK_SOLVE: "clean_solve",
+                      CLK_SUBTRACT: "clean_subtract"}
 
 
 class Blah2HipError(RuntimeError):
@@ -98,6 +104,10 @@ class Hit(C.Structure):
 
 class Det(C.Structure):
     _fields_ = [("row", C.c_int32), ("col", C.c_int32), ("delay", C.c_double), ("doppler", C.c_double), ("snr", C.c_double)]
+
+
+class Atom(C.Structure):
+    _fields_ = [("delay", C.c_int32), ("reserved", C.c_int32), ("doppler", C.c_double)]
 
 
 class Bearing(C.Structure):
@@ -181,6 +191,17 @@ SYMBOLS = {
     "blah2hip_cmap_process_dev": (C.c_int, [_vp, _vp, _vp, _u32, _dbl, _i32, _dbl, _vp, _u32, _vp, _vp, _vp, _vp]),
     "blah2hip_cmap_gate_dev": (C.c_int, [_vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp]),
     "blah2hip_cmap_read_background": (C.c_int, [_vp, _vp]),
+    "blah2hip_clean_create": (C.c_int, [_u32, _dbl, _i32, _i32, C.c_int, _u32, C.POINTER(_vp)]),
+    "blah2hip_clean_destroy": (C.c_int, [_vp]),
+    "blah2hip_clean_set_option": (C.c_int, [_vp, C.c_int, C.c_int64]),
+    "blah2hip_clean_get_info": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int64)]),
+    "blah2hip_clean_atoms_dev": (C.c_int, [_vp, _vp, _vp, _u32, _vp, _u32, _dbl, _u32, _i32, _i32, _vp, _u32, _vp, _vp, _vp]),
+    "blah2hip_clean_fit_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _u32, C.c_uint64, _vp, _u32, _vp, _dbl, _vp, _vp, _vp]),
+    "blah2hip_clean_subtract_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _u32, C.c_uint64, _vp, _u32, _vp, _vp, _vp, _vp, C.c_uint64, _vp]),
+    "blah2hip_clean_process_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _u32, C.c_uint64, _vp, _u32, _vp, _dbl, _vp, _vp, _vp, C.c_uint64, _vp]),
+    "blah2hip_clean_read_last": (C.c_int, [_vp, _u32, _vp, _vp, _vp, _vp]),
+    "blah2hip_clean_set_timing": (C.c_int, [_vp, C.c_int]),
+    "blah2hip_clean_get_timing": (C.c_int, [_vp, _vp, _vp]),
     "blah2hip_centroid": (C.c_int, [_vp, _vp, _vp, _u32, C.c_uint16, C.c_uint16, _dbl, _vp, _vp, _vp, C.POINTER(_u32)]),
     "blah2hip_interpolate": (C.c_int, [_vp, _vp, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _dbl, C.c_int, C.c_int,
                                        _vp, _vp, _vp, C.POINTER(_u32)]),

@@ -2067,6 +2067,191 @@ def dets_to_detection(recs, count, cap_out):
     return Detection(d["delay"], d["doppler"], d["snr"])
 
 
+ATOM_DTYPE = np.dtype([("delay", np.int32), ("reserved", np.int32), ("doppler", np.float64)])
+
+
+def _atom_pairs(atoms):
+    """Atoms as a list of ``(delay int, doppler float)``: from an :data:`ATOM_DTYPE` array or any sequence of pairs."""
+    if isinstance(atoms, np.ndarray) and atoms.dtype.names:
+        return [(int(d), float(f)) for d, f in zip(atoms["delay"], atoms["doppler"])]
+    return [(int(d), float(f)) for d, f in atoms]
+
+
+def clean_atoms(dets, count, snr_min_db, max_echoes, side_delay, side_doppler, delay_lo, delay_hi, cpi, cap_atoms=_lib.MAX_ATOMS):
+    """blah2hip_clean_atoms_dev restated: one CPI's final records (:data:`DET_DTYPE`; ``count`` beyond their number: all of
+    them) -> ``(atoms`` :data:`ATOM_DTYPE` ``[n], used [m] int)``.  The records with ``snr >= snr_min_db``, strongest first,
+    ties by lower row, then lower col, then lower index, ``max_echoes`` at the most; each becomes the cluster
+    ``(rint(delay) + i, doppler + j 0.5 / cpi)``, ``|i| <= side_delay``, ``|j| <= side_doppler``, in the order echo, i, j.
+    Members outside ``[delay_lo, delay_hi]`` are dropped; an echo whose remaining members do not fit into ``cap_atoms`` is
+    dropped whole, as is one with none left.  ``used``: the indices of the records that gave atoms, in their order."""
+    d = np.asarray(dets)[:min(int(count), len(dets))]
+    idx = [i for i in range(len(d)) if d["snr"][i] >= snr_min_db]
+    idx.sort(key=lambda i: (-d["snr"][i], d["row"][i], d["col"][i], i))
+    atoms, used = [], []
+    for i in idx[:int(max_echoes)]:
+        dc = np.rint(d["delay"][i])
+        members = [(int(dc + a), float(d["doppler"][i]) + j * 0.5 / cpi)
+                   for a in range(-int(side_delay), int(side_delay) + 1) if delay_lo <= dc + a <= delay_hi
+                   for j in range(-int(side_doppler), int(side_doppler) + 1)]
+        if members and len(atoms) + len(members) <= cap_atoms:
+            atoms += members
+            used.append(i)
+    out = np.zeros(len(atoms), dtype=ATOM_DTYPE)
+    for k, (dl, f) in enumerate(atoms):
+        out[k] = (dl, 0, f)
+    return out, np.asarray(used, dtype=np.int64)
+
+
+def clean_replicas(x, atoms, fs):
+    """``S [P, N]`` complex128: ``S[p][n] = x[n - d_p] exp(+2j pi f_p n / fs)`` for ``0 <= n - d_p < N``, 0 elsewhere (nothing
+    wraps).  A noiseless ``y = S[p]`` peaks in the map cell whose axis values are ``(d_p, f_p)``."""
+    x = np.asarray(x, dtype=np.complex128)
+    N = x.shape[0]
+    n = np.arange(N)
+    pairs = _atom_pairs(atoms)
+    S = np.zeros((len(pairs), N), dtype=np.complex128)
+    for p, (d, f) in enumerate(pairs):
+        i = n - d
+        ok = (i >= 0) & (i < N)
+        S[p, ok] = x[i[ok]] * np.exp(2j * np.pi * ((f * n[ok].astype(np.float64) / fs) % 1.0))
+    return S
+
+
+def clean_fit(x, y, atoms, fs, loading):
+    """blah2hip_clean_fit_dev restated in fp64: ``G = S^H S``, ``b = S^H y``, ``(G + loading (tr G / P) I) a = b`` through
+    :func:`_cholesky_loaded`.  Returns ``(a [P], ok, G [P, P], b [P])``; ``ok`` is 0 (and ``a`` zero) where a pivot is not
+    finite or not above 2^-46 of its loaded diagonal entry (exactly dependent atoms fail without loading), ``a`` is not finite or an atom's Doppler is not finite.  No atoms: ``ok = 1``."""
+    pairs = _atom_pairs(atoms)
+    P = len(pairs)
+    if P and not np.all(np.isfinite([f for _, f in pairs])):
+        return np.zeros(P, dtype=np.complex128), 0, np.zeros((P, P), dtype=np.complex128), np.zeros(P, dtype=np.complex128)
+    S = clean_replicas(x, pairs, fs)
+    G = np.conj(S) @ S.T
+    b = np.conj(S) @ np.asarray(y, dtype=np.complex128)
+    if P == 0:
+        return np.zeros(0, dtype=np.complex128), 1, G, b
+    with np.errstate(all="ignore"):
+        L, good = _cholesky_loaded(G[None], loading)
+        L = L[0]
+        v = _forward_solve(L, b)
+        a = np.zeros(P, dtype=np.complex128)
+        for i in range(P - 1, -1, -1):  # L^H a = v
+            s = v[i]
+            for p in range(P - 1, i, -1):
+                s = s - np.conj(L[p, i]) * a[p]
+            a[i] = s / L[i, i].real
+        # a pivot must be positive beyond the rounding of its own sum: above 2^-46 of its loaded diagonal entry
+        diag = G.diagonal().real + float(loading) * (G.diagonal().real.sum() / P)
+        pivots = bool(np.all(L.diagonal().real ** 2 > 2.0 ** -46 * diag))
+    ok = int(bool(good[0]) and pivots and bool(np.all(np.isfinite(a))))
+    if not ok:
+        a = np.zeros(P, dtype=np.complex128)
+    return a, ok, G, b
+
+
+def clean_subtract(x, y, atoms, a, fs):
+    """``y - sum_p a_p S[p]`` in fp64 (blah2hip_clean_subtract_dev restated)."""
+    y = np.asarray(y, dtype=np.complex128)
+    a = np.asarray(a, dtype=np.complex128)
+    if a.size == 0:
+        return y.copy()
+    return y - a @ clean_replicas(x, atoms, fs)
+
+
+def merge_clean_detections(first, used, second, side_delay, cpi):
+    """The two passes' lists of one CPI as one (:data:`DET_DTYPE`): the echoes that were cancelled -- ``first[used]`` --
+    then the pass-2 records, less any within ``side_delay + 1`` delay bins and one Doppler bin (``1 / cpi``) of a cancelled
+    echo: what is left of it in the second map is its residual, not a new target."""
+    first = np.asarray(first)
+    second = np.asarray(second)
+    gone = first[np.asarray(used, dtype=np.int64)] if len(used) else first[:0]
+    keep = np.ones(len(second), dtype=bool)
+    for g in gone:
+        keep &= ~((np.abs(second["delay"] - g["delay"]) <= side_delay + 1) & (np.abs(second["doppler"] - g["doppler"]) <= 1.0 / cpi))
+    return np.concatenate([gone, second[keep]])
+
+
+class EchoCanceller:
+    """Strong-echo cancellation on the samples (blah2hip_clean_*; no reference counterpart): the amplitudes of a list of
+    atoms ``(delay, Doppler)`` fitted to the surveillance samples by least squares, their replicas subtracted.  CPIs of
+    ``n_samples`` samples at ``fs`` Hz, atom delays in ``[delay_lo, delay_hi]`` (a span of at most 4095).  The ``*_dev``
+    methods take raw device pointers and only enqueue."""
+
+    def __init__(self, n_samples, fs, delay_lo, delay_hi, device=0, max_batch=1):
+        L = _lib.load()
+        h = C.c_void_p()
+        check(L.blah2hip_clean_create(int(n_samples), float(fs), int(delay_lo), int(delay_hi), int(device), int(max_batch), C.byref(h)))
+        self._h, self._L = h, L
+        self.n_samples, self.fs, self.delay_lo, self.delay_hi = int(n_samples), float(fs), int(delay_lo), int(delay_hi)
+        self.max_batch = int(max_batch)
+        self._last_cap = 0
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.blah2hip_clean_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_option(self, option, value):
+        check(self._L.blah2hip_clean_set_option(self._h, int(option), int(value)))
+
+    def get_info(self, what):
+        v = C.c_int64(0)
+        check(self._L.blah2hip_clean_get_info(self._h, int(what), C.byref(v)))
+        return v.value
+
+    def atoms_dev(self, amb, d_dets, cap, d_count, n_cpi, snr_min_db, max_echoes, side_delay, side_doppler, d_atoms, cap_atoms,
+                  d_atom_count, d_used, stream=0):
+        """Enqueue blah2hip_clean_atoms_dev: final records ``d_dets [n_cpi][cap]`` / ``d_count [n_cpi]`` of ``amb`` ->
+        ``d_atoms [n_cpi][cap_atoms]`` (:data:`ATOM_DTYPE`), ``d_atom_count [n_cpi]``, ``d_used [n_cpi][cap_atoms]`` int32
+        (:func:`clean_atoms`)."""
+        check(self._L.blah2hip_clean_atoms_dev(self._h, amb._h, d_dets, int(cap), d_count, int(n_cpi), float(snr_min_db), int(max_echoes),
+                                               int(side_delay), int(side_doppler), d_atoms, int(cap_atoms), d_atom_count, d_used, stream))
+
+    def fit_dev(self, fmt, d_x, d_y, n_cpi, cpi_stride, d_atoms, cap_atoms, d_atom_count, loading, d_amp, d_ok, stream=0):
+        """Enqueue blah2hip_clean_fit_dev: ``d_amp [n_cpi][cap_atoms]`` (re, im) doubles, ``d_ok [n_cpi]`` int32."""
+        check(self._L.blah2hip_clean_fit_dev(self._h, int(fmt), d_x, d_y, int(n_cpi), int(cpi_stride), d_atoms, int(cap_atoms),
+                                             d_atom_count, float(loading), d_amp, d_ok, stream))
+        self._last_cap = int(cap_atoms)
+
+    def subtract_dev(self, fmt, d_x, d_y, n_cpi, cpi_stride, d_atoms, cap_atoms, d_atom_count, d_amp, d_ok, d_y_out, out_stride,
+                     stream=0):
+        """Enqueue blah2hip_clean_subtract_dev; ``d_y_out`` may be ``d_y``."""
+        check(self._L.blah2hip_clean_subtract_dev(self._h, int(fmt), d_x, d_y, int(n_cpi), int(cpi_stride), d_atoms, int(cap_atoms),
+                                                  d_atom_count, d_amp, d_ok, d_y_out, int(out_stride), stream))
+
+    def process_dev(self, fmt, d_x, d_y, n_cpi, cpi_stride, d_atoms, cap_atoms, d_atom_count, loading, d_amp, d_ok, d_y_out,
+                    out_stride, stream=0):
+        """Enqueue the fit, then the subtraction (blah2hip_clean_process_dev)."""
+        check(self._L.blah2hip_clean_process_dev(self._h, int(fmt), d_x, d_y, int(n_cpi), int(cpi_stride), d_atoms, int(cap_atoms),
+                                                 d_atom_count, float(loading), d_amp, d_ok, d_y_out, int(out_stride), stream))
+        self._last_cap = int(cap_atoms)
+
+    def read_last(self, cpi=0):
+        """``(G [cap, cap], b [cap], amp [cap] complex128, ok)`` of CPI ``cpi`` of the last fit, ``cap`` its ``cap_atoms``
+        (waits for the device)."""
+        cap = self._last_cap
+        G, b, a = np.zeros((cap, cap), dtype=np.complex128), np.zeros(cap, dtype=np.complex128), np.zeros(cap, dtype=np.complex128)
+        ok = C.c_int32(0)
+        check(self._L.blah2hip_clean_read_last(self._h, int(cpi), _ptr(G), _ptr(b), _ptr(a), C.byref(ok)))
+        return G, b, a, ok.value
+
+    def set_timing(self, enable=True):
+        check(self._L.blah2hip_clean_set_timing(self._h, int(bool(enable))))
+
+    def get_timing(self):
+        """``{kernel name: (ms_total, launches)}`` since the last call (waits for the device)."""
+        ms = (C.c_double * _lib.CLK_COUNT)()
+        n = (C.c_uint32 * _lib.CLK_COUNT)()
+        check(self._L.blah2hip_clean_get_timing(self._h, ms, n))
+        return {_lib.CLEAN_KERNEL_NAMES[k]: (ms[k], n[k]) for k in range(_lib.CLK_COUNT)}
+
+
 # the fused kernel (range_fir_kernel) convolves a CPI with ONE tap set
 _FIR_BLOCKS_REASON = "the fused FIR takes one tap set per CPI: a clutter filter with blocks > 1 runs the two-stage chain"
 

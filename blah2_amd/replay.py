@@ -645,7 +645,18 @@ class GpuChain:
     sums along the walk as well, INSTEAD of ``migrate_dev`` (two stages would each overwrite the other).  The maximum over K
     hypotheses multiplies the false-alarm rate by at most K, so the detector is made with ``pfa / K`` (the union bound).
     ValueError, naming the key: a bank of more than 16 rates, a ``max`` or ``step`` that is not a finite number (``max`` >= 0,
-    ``step`` > 0), a bank the library refuses (|q| above the Doppler bins).  Without the key nothing is launched."""
+    ``step`` > 0), a bank the library refuses (|q| above the Doppler bins).  Without the key nothing is launched.
+
+    ``cfg["detection"]["clean"] = {"snr": dB, "echoes": E, "sideDelay": 1, "sideDoppler": 0, "loading": 1e-6}`` cancels strong
+    echoes on the samples (``blah2_amd.EchoCanceller``): behind the finisher the detections of at least ``snr`` dB, ``echoes``
+    at the most, become clusters of atoms, their amplitudes are fitted to the fp32 surveillance plane by least squares and
+    their replicas subtracted in place, and everything from the ambiguity stage on runs a second time.  A result carries the
+    second pass's map and metrics, the merged list (``blah2_amd.merge_clean_detections``: the cancelled echoes from pass 1,
+    then pass 2's detections less their residuals) and ``cancelled``, their number.  A configured fused FIR runs as the
+    two-stage filter so that the filtered plane exists.  ValueError, naming the key: values outside their ranges, no device
+    finisher (no ``nCentroid``, or ``detect="host"``), ``integrate`` or ``clutterMap`` configured (either would absorb every
+    CPI twice), no fp32 surveillance plane at that point (int16 or int8 words and no clutter filter).  Without the key
+    nothing is allocated or launched."""
 
     def __init__(self, cfg: dict, device: int = 0, batch: int = 1, want_map: bool = False, depth: int = 3,
                  reader_threads: int = 4, hit_copy: int = 4096, read_mode: str = "memmove", numa: bool = True,
@@ -862,6 +873,45 @@ class GpuChain:
         self.need_map = self.want_map or self.detect == "host"
         dev = self.dev = torch.device("cuda", device)
         self.cap = int(det_c.get("capacity", min(nD * nC, 1 << 16)))
+        # detection: {clean: {snr: dB, echoes: E, sideDelay: 1, sideDoppler: 0, loading: 1e-6}}: strong-echo cancellation
+        # on the samples and a second pass of everything from the ambiguity stage on (None: no such stage)
+        self.clean, self.clean_cfg = None, None
+        cl_c = det_c.get("clean")
+        cl_c = None if cl_c is False else cl_c
+        if cl_c is not None:
+            try:
+                if not isinstance(cl_c, dict) or isinstance(cl_c.get("snr"), bool) or not isinstance(cl_c.get("snr"), (int, float)):
+                    raise ValueError("{snr: dB, echoes: E, sideDelay: 1, sideDoppler: 0, loading: 1e-6} with snr a number of dB")
+                cc = {"snr": float(cl_c["snr"]), "echoes": int(cl_c.get("echoes", 4)), "sideDelay": int(cl_c.get("sideDelay", 1)),
+                      "sideDoppler": int(cl_c.get("sideDoppler", 0)), "loading": float(cl_c.get("loading", 1e-6))}
+                if not math.isfinite(cc["snr"]):
+                    raise ValueError("snr is not finite")
+                if not 1 <= cc["echoes"] <= blah2_amd._lib.MAX_ATOMS:
+                    raise ValueError(f"echoes outside [1, {blah2_amd._lib.MAX_ATOMS}]")
+                if not 0 <= cc["sideDelay"] <= 2 or not 0 <= cc["sideDoppler"] <= 1:
+                    raise ValueError("sideDelay outside [0, 2] or sideDoppler outside [0, 1]")
+                if not math.isfinite(cc["loading"]) or cc["loading"] < 0:
+                    raise ValueError("loading must be finite and not negative")
+                if self.finisher is None:
+                    raise ValueError("it reads the final detection lists on the device: detection with nCentroid, and not --detect host")
+                if self.nci is not None:
+                    raise ValueError("integrate is configured: the integrator's window would see every CPI twice")
+                if self.cmap is not None:
+                    raise ValueError("clutterMap is configured: its history would absorb every CPI twice")
+                if self.wh is None and self.layout != "usrp":
+                    raise ValueError("the surveillance channel is not an fp32 plane at that point: it takes a C32 (USRP) "
+                                     "capture or an enabled clutter filter, whose output is one")
+                self.clean = blah2_amd.EchoCanceller(n, self.fs, amb_c["delayMin"], amb_c["delayMax"], device=device, max_batch=B)
+            except (ValueError, blah2_amd.Blah2HipError) as e:
+                for h_ in (self.nci, self.cmap, self.wh):
+                    if h_ is not None:
+                        h_.close()
+                self.amb.close()
+                raise ValueError(f"detection.clean = {cl_c!r}: {e}") from None
+            self.clean_cfg = cc
+            if self.fused_fir:  # the filtered channel has to exist as a plane: the two-stage chain
+                self.amb.set_fir(None)
+                self.fused_fir = False
         self.hit_copy = min(self.cap, int(hit_copy))
         self.compute = torch.cuda.Stream(device=dev)
         self.copy = torch.cuda.Stream(device=dev)
@@ -935,6 +985,19 @@ class GpuChain:
                 s["d_ghits"] = torch.zeros((B, self.cap, 2), dtype=torch.float64, device=dev)
                 s["d_gcnt"] = torch.zeros(B, dtype=torch.int32, device=dev)
                 s["h_rcnt"] = torch.zeros(B, dtype=torch.int32).pin_memory()
+            if self.clean is not None:  # pass 1's final list, the atoms made of it, the fit; what _collect merges
+                A = blah2_amd._lib.MAX_ATOMS
+                s["d_dets1"] = torch.zeros((B, self.cap, 4), dtype=torch.float64, device=dev)
+                s["d_dcnt1"] = torch.zeros(B, dtype=torch.int32, device=dev)
+                s["d_atoms"] = torch.zeros((B, A, 2), dtype=torch.float64, device=dev)  # blah2hip_atom_t records, 16 bytes
+                s["d_acnt"] = torch.zeros(B, dtype=torch.int32, device=dev)
+                s["d_used"] = torch.zeros((B, A), dtype=torch.int32, device=dev)
+                s["d_amp"] = torch.zeros((B, A, 2), dtype=torch.float64, device=dev)
+                s["d_cok"] = torch.zeros(B, dtype=torch.int32, device=dev)
+                s["h_dets1"] = torch.zeros((B, self.hit_copy, 4), dtype=torch.float64).pin_memory()
+                s["h_dcnt1"] = torch.zeros(B, dtype=torch.int32).pin_memory()
+                s["h_used"] = torch.zeros((B, A), dtype=torch.int32).pin_memory()
+                s["h_cok"] = torch.zeros(B, dtype=torch.int32).pin_memory()
             s["hits"], s["cnt"] = s["d_hits"], s["d_cnt"]  # the list the finisher and the downloads read
             self.slots.append(s)
 
@@ -1041,42 +1104,60 @@ class GpuChain:
                 self.wh.process_dev_fmt(fmt, x, y, cnt, n, self.yf.data_ptr(), n, slot["d_ok"].data_ptr(), st)
                 amb.process_dev(fmt_yf, x, self.yf.data_ptr(), cnt, n, slot["d_map"].data_ptr(),
                                 slot["d_met"].data_ptr(), st)
-            n_maps, maps, mets = cnt, slot["d_map"], slot["d_met"]  # what the detector and the download read
-            if self.rates is not None:  # in place too; along the migration table's walk when one is set: one sum for both
-                amb.rate_bank_dev(maps.data_ptr(), cnt, maps.data_ptr(), None, mets.data_ptr(), st)
-            elif self.migrate:  # in place, from the range map the call above left on the handle
-                amb.migrate_dev(maps.data_ptr(), cnt, maps.data_ptr(), mets.data_ptr(), st)
-            if self.taper is not None:
-                amb.taper_dev(maps.data_ptr(), cnt, self.taper, slot["d_tmap"].data_ptr(), slot["d_tmet"].data_ptr(), st)
-                maps, mets = slot["d_tmap"], slot["d_tmet"]
-            if self.nci is not None:
-                if self._per_batch:
-                    self.reset_integrator()
-                if self.nci_tracks:
-                    n_maps, first = self.nci.process_tracks_dev(maps.data_ptr(), cnt, slot["d_imap"].data_ptr(), None,
-                                                                slot["d_imet"].data_ptr(), self.batch, None, st)
-                else:
-                    n_maps, first = self.nci.process_dev(maps.data_ptr(), cnt, slot["d_imap"].data_ptr(), slot["d_imet"].data_ptr(),
-                                                         self.batch, None, st)
-                slot["nci"] = (self._g, n_maps, first)
-                self._g += cnt
-                maps, mets = slot["d_imap"], slot["d_imet"]
-            if self.cfar is not None and n_maps:
-                if self.cmap_mode == "detect":  # the clutter map's own list in the detector's place
-                    self.cmap.process_dev(n_maps, slot["d_hits"].data_ptr(), self.cap, slot["d_cnt"].data_ptr(),
-                                          maps.data_ptr(), mets.data_ptr(), None, None, st)
-                else:
-                    self.cfar.process_dev(amb, n_maps, slot["d_hits"].data_ptr(), self.cap, slot["d_cnt"].data_ptr(),
-                                          maps.data_ptr(), mets.data_ptr(), st)
-                if self.cmap_mode == "gate":  # the exceed planes, no list; then the detector's hits whose cell exceeded
-                    self.cmap.process_dev(n_maps, None, 0, None, maps.data_ptr(), mets.data_ptr(), slot["d_exc"].data_ptr(), None, st)
-                    self.cmap.gate_dev(slot["d_exc"].data_ptr(), n_maps, slot["d_hits"].data_ptr(), self.cap, slot["d_cnt"].data_ptr(),
-                                       slot["d_ghits"].data_ptr(), slot["d_gcnt"].data_ptr(), st)
-                    slot["hits"], slot["cnt"] = slot["d_ghits"], slot["d_gcnt"]
-                if self.finisher is not None:
-                    self.finisher.process_dev(amb, n_maps, slot["hits"].data_ptr(), self.cap, slot["cnt"].data_ptr(),
-                                              slot["d_dets"].data_ptr(), self.cap, slot["d_dcnt"].data_ptr(),
+            def behind(dets, dcnt):  # everything behind the ambiguity stage, on the maps it has just left; the final records into dets / dcnt
+                n_maps, maps, mets = cnt, slot["d_map"], slot["d_met"]  # what the detector and the download read
+                if self.rates is not None:  # in place too; along the migration table's walk when one is set: one sum for both
+                    amb.rate_bank_dev(maps.data_ptr(), cnt, maps.data_ptr(), None, mets.data_ptr(), st)
+                elif self.migrate:  # in place, from the range map the call above left on the handle
+                    amb.migrate_dev(maps.data_ptr(), cnt, maps.data_ptr(), mets.data_ptr(), st)
+                if self.taper is not None:
+                    amb.taper_dev(maps.data_ptr(), cnt, self.taper, slot["d_tmap"].data_ptr(), slot["d_tmet"].data_ptr(), st)
+                    maps, mets = slot["d_tmap"], slot["d_tmet"]
+                if self.nci is not None:
+                    if self._per_batch:
+                        self.reset_integrator()
+                    if self.nci_tracks:
+                        n_maps, first = self.nci.process_tracks_dev(maps.data_ptr(), cnt, slot["d_imap"].data_ptr(), None,
+                                                                    slot["d_imet"].data_ptr(), self.batch, None, st)
+                    else:
+                        n_maps, first = self.nci.process_dev(maps.data_ptr(), cnt, slot["d_imap"].data_ptr(), slot["d_imet"].data_ptr(),
+                                                             self.batch, None, st)
+                    slot["nci"] = (self._g, n_maps, first)
+                    self._g += cnt
+                    maps, mets = slot["d_imap"], slot["d_imet"]
+                if self.cfar is not None and n_maps:
+                    if self.cmap_mode == "detect":  # the clutter map's own list in the detector's place
+                        self.cmap.process_dev(n_maps, slot["d_hits"].data_ptr(), self.cap, slot["d_cnt"].data_ptr(),
+                                              maps.data_ptr(), mets.data_ptr(), None, None, st)
+                    else:
+                        self.cfar.process_dev(amb, n_maps, slot["d_hits"].data_ptr(), self.cap, slot["d_cnt"].data_ptr(),
                                               maps.data_ptr(), mets.data_ptr(), st)
+                    if self.cmap_mode == "gate":  # the exceed planes, no list; then the detector's hits whose cell exceeded
+                        self.cmap.process_dev(n_maps, None, 0, None, maps.data_ptr(), mets.data_ptr(), slot["d_exc"].data_ptr(), None, st)
+                        self.cmap.gate_dev(slot["d_exc"].data_ptr(), n_maps, slot["d_hits"].data_ptr(), self.cap, slot["d_cnt"].data_ptr(),
+                                           slot["d_ghits"].data_ptr(), slot["d_gcnt"].data_ptr(), st)
+                        slot["hits"], slot["cnt"] = slot["d_ghits"], slot["d_gcnt"]
+                    if self.finisher is not None:
+                        self.finisher.process_dev(amb, n_maps, slot["hits"].data_ptr(), self.cap, slot["cnt"].data_ptr(),
+                                                  dets.data_ptr(), self.cap, dcnt.data_ptr(),
+                                                  maps.data_ptr(), mets.data_ptr(), st)
+                return n_maps, maps, mets
+
+            if self.clean is None:
+                n_maps, maps, mets = behind(slot["d_dets"], slot["d_dcnt"])
+            else:
+                # pass 1, its strongest detections as atoms, their replicas fitted to and taken out of the surveillance plane
+                # (in place: the plane is this batch's alone on the in-order stream), then everything again: pass 2
+                cc, A = self.clean_cfg, b2._lib.MAX_ATOMS
+                behind(slot["d_dets1"], slot["d_dcnt1"])
+                fy, py = (fmt_yf, self.yf.data_ptr()) if self.wh is not None else (fmt, y)
+                self.clean.atoms_dev(amb, slot["d_dets1"].data_ptr(), self.cap, slot["d_dcnt1"].data_ptr(), cnt, cc["snr"], cc["echoes"],
+                                     cc["sideDelay"], cc["sideDoppler"], slot["d_atoms"].data_ptr(), A, slot["d_acnt"].data_ptr(),
+                                     slot["d_used"].data_ptr(), st)
+                self.clean.process_dev(fy, x, py, cnt, n, slot["d_atoms"].data_ptr(), A, slot["d_acnt"].data_ptr(), cc["loading"],
+                                       slot["d_amp"].data_ptr(), slot["d_cok"].data_ptr(), py, n, st)
+                amb.process_dev(fy, x, py, cnt, n, slot["d_map"].data_ptr(), slot["d_met"].data_ptr(), st)
+                n_maps, maps, mets = behind(slot["d_dets"], slot["d_dcnt"])
             slot["computed"].record(self.compute)
         with torch.cuda.stream(self.copy):
             self.copy.wait_event(slot["computed"])
@@ -1091,6 +1172,11 @@ class GpuChain:
                 if self.finisher is not None:
                     slot["h_dcnt"][:n_maps].copy_(slot["d_dcnt"][:n_maps], non_blocking=True)
                     slot["h_dets"][:n_maps].copy_(slot["d_dets"][:n_maps, :self.hit_copy], non_blocking=True)
+                    if self.clean is not None:
+                        slot["h_dcnt1"][:n_maps].copy_(slot["d_dcnt1"][:n_maps], non_blocking=True)
+                        slot["h_dets1"][:n_maps].copy_(slot["d_dets1"][:n_maps, :self.hit_copy], non_blocking=True)
+                        slot["h_used"][:n_maps].copy_(slot["d_used"][:n_maps], non_blocking=True)
+                        slot["h_cok"][:n_maps].copy_(slot["d_cok"][:n_maps], non_blocking=True)
                 else:
                     slot["h_hits"][:n_maps].copy_(slot["hits"][:n_maps, :self.hit_copy], non_blocking=True)
             if self.need_map:
@@ -1146,6 +1232,21 @@ class GpuChain:
                     else:
                         recs = slot["h_dets"][b, :max(kd, 1)].numpy()
                     det = b2.dets_to_detection(recs.view(b2.DET_DTYPE).reshape(-1), kd, self.cap)
+                    if self.clean is not None:  # the cancelled echoes from pass 1, then pass 2's list less their residuals
+                        k1 = int(slot["h_dcnt1"][b])
+                        if k1 > self.cap:
+                            raise b2.Blah2HipError(b2._lib.ERR_CAPACITY, f"{k1} detections in one CPI, capacity {self.cap}")
+                        rec1 = (slot["d_dets1"][b, :k1].cpu().numpy() if k1 > self.hit_copy else slot["h_dets1"][b, :max(k1, 1)].numpy())
+                        first = rec1.view(b2.DET_DTYPE).reshape(-1)[:k1]
+                        used = [int(u) for u in slot["h_used"][b].numpy() if u >= 0] if int(slot["h_cok"][b]) else []
+                        second = np.zeros(len(det.delay), dtype=b2.DET_DTYPE)
+                        second["delay"], second["doppler"], second["snr"] = det.delay, det.doppler, det.snr
+                        m = b2.merge_clean_detections(first, used, second, self.clean_cfg["sideDelay"], amb.dims.cpi)
+                        r.update(delay=m["delay"].tolist(), doppler=m["doppler"].tolist(), snr=m["snr"].tolist(), cancelled=len(used))
+                        if self.want_map:
+                            r["map"] = slot["h_map"][b].numpy().copy()
+                        res.append(r)
+                        continue
                     r.update(delay=det.delay.tolist(), doppler=det.doppler.tolist(), snr=det.snr.tolist())
                     if self.want_map:
                         r["map"] = slot["h_map"][b].numpy().copy()
@@ -1262,6 +1363,8 @@ class GpuChain:
             self.nci.close()
         if self.cmap is not None:
             self.cmap.close()
+        if getattr(self, "clean", None) is not None:
+            self.clean.close()
 
 
 def gpu_processor(cfg: dict, device: int = 0, batch: int = 1, want_map: bool = False, **kw) -> GpuChain:
@@ -1366,6 +1469,13 @@ def main(argv=None):
                          "of its own past power, so what sits in one cell CPI after CPI is no longer reported.  T gates the "
                          "detector's hits, T:detect reports the clutter map's own.  One rank, not with --integrate.  "
                          "Overrides process.detection.clutterMap ({memory: T, mode: gate | detect})")
+    ap.add_argument("--clean", default=None, metavar="SNR_DB[:MAX_ECHOES]",
+                    help="strong-echo cancellation: the detections of at least SNR_DB (at most MAX_ECHOES of them, default 4) "
+                         "are fitted to the surveillance samples by least squares and subtracted, and the chain runs again "
+                         "from the ambiguity stage on; the frames carry the second pass's maps and the merged list.  Needs "
+                         "device detection and an fp32 surveillance plane (a USRP capture or the clutter filter); not with "
+                         "--integrate or --clutter-map.  Overrides process.detection.clean ({snr, echoes, sideDelay, "
+                         "sideDoppler, loading})")
     ap.add_argument("--connect", action="store_true",
                     help="with --json: send the documents to network.ip:ports.map / ports.detection of the config, "
                          "framed like Socket::sendData, instead of printing them")
@@ -1470,6 +1580,21 @@ def main(argv=None):
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
             ap.error("--clutter-map needs the CPIs in order: one rank")
         cfg["detection"] = dict(cfg.get("detection") or {}, clutterMap={"memory": int(mem_), "mode": mode_ or "gate"})
+    if a.clean is not None:
+        snr_, sep_, ech_ = a.clean.partition(":")
+        try:
+            snr_ = float(snr_)
+            ech_ = int(ech_) if sep_ else 4
+            if not math.isfinite(snr_) or not 1 <= ech_ <= 32:
+                raise ValueError
+        except ValueError:
+            ap.error("--clean takes SNR_DB or SNR_DB:MAX_ECHOES, a threshold in dB and 1 .. 32 echoes")
+        if cfg.get("integrate"):
+            ap.error("--clean does not go with --integrate: the integrator's window would see every CPI twice")
+        if (cfg.get("detection") or {}).get("clutterMap"):
+            ap.error("--clean does not go with --clutter-map: its history would absorb every CPI twice")
+        cfg["detection"] = dict(cfg.get("detection") or {},
+                                clean=dict((cfg.get("detection") or {}).get("clean") or {}, snr=snr_, echoes=ech_))
     dist = None
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:

@@ -1233,6 +1233,103 @@ int blah2hip_deblock_c32_dev(const void *d_raw, uint32_t block, uint64_t first, 
  * map [max_batch][n_doppler][n_delay] complex fp32 and metrics [max_batch][2] doubles */
 int blah2hip_amb_result_ptrs(blah2hip_amb_t h, const void **d_map, const double **d_metrics);
 
+/* ---- strong-echo cancellation: least-squares CLEAN on the samples ---------
+ * No reference counterpart.  An echo a x[n - d] exp(2 pi i f n / fs) leaves the waveform's own sidelobes in every cell
+ * of the map, about n_samples below its peak; the clutter filter removes them at zero Doppler only.  This stage fits
+ * the complex amplitudes of a list of ATOMS (d_p, f_p) to the surveillance samples by least squares and subtracts their
+ * replicas, so that a second pass of the ambiguity stage sees the floor without them.
+ *
+ * Definitions (fp64 semantics; blah2_amd.process.clean_replicas / clean_fit / clean_subtract restate them in NumPy).
+ * Per CPI, P <= BLAH2HIP_MAX_ATOMS atoms; d_p an integer delay in samples (the units of the map's delay axis; it may be
+ * negative), f_p a Doppler in Hz on the map's doppler axis, on a bin or not:
+ *   s_p[n] = x[n - d_p] exp(+2 pi i f_p n / fs)   for 0 <= n - d_p < n_samples, 0 elsewhere (nothing wraps)
+ *   G[p][q] = sum_n conj(s_p[n]) s_q[n],   b[p] = sum_n conj(s_p[n]) y[n]
+ *   G_l = G + loading (tr G / P) I   (the loading rule of blah2hip_amb_mvdr_weights_dev),   G_l a = b
+ *   y_out[n] = y[n] - sum_p a_p s_p[n]
+ * A noiseless y = s_p peaks in the map cell whose axis values are (d_p, f_p), also on a handle with
+ * doppler_middle != 0.  ok = 1 when the Cholesky factor of G_l exists (every pivot finite and above 2^-46 of its
+ * loaded diagonal entry: positive beyond the rounding of its own sum) and a is finite; with ok = 0 the amplitudes are 0 and y_out = y bit for bit.  P = 0: ok = 1, y_out = y bit for bit.
+ *
+ * x is the reference channel in its format, y the surveillance channel as an fp32 plane -- as the clutter filter, a
+ * beam former or a C32 capture leaves it: fmt is BLAH2HIP_FMT_C32, _I16X_C32Y or _I8X_C32Y (any other:
+ * BLAH2HIP_ERR_UNSUPPORTED).  CPI c of either plane starts c * cpi_stride samples in.  Alignment: fp32 planes 8 bytes,
+ * the .rspduo words 4, int8 pairs 2; atoms, amplitudes 8; counts, ok, used 4. */
+#define BLAH2HIP_MAX_ATOMS 32
+typedef struct blah2hip_clean_s *blah2hip_clean_t;
+typedef struct blah2hip_atom {
+  int32_t delay;    /* samples */
+  int32_t reserved; /* 0 */
+  double doppler;   /* Hz */
+} blah2hip_atom_t;
+/* A canceller for CPIs of n_samples (<= 2^26) samples at fs Hz whose atoms' delays lie in [delay_lo, delay_hi].
+ * delay_hi - delay_lo above 4095 is BLAH2HIP_ERR_UNSUPPORTED: the kernels keep a chunk of x plus that halo in LDS.
+ * Everything is allocated here (per-workgroup partials, G, b, the amplitudes of max_batch CPIs): the *_dev entry points
+ * only enqueue on `stream` and can be captured in a graph.  BLAH2HIP_ERR_INVALID: NULL out, n_samples 0 or above 2^26,
+ * fs not finite or not positive, delay_hi < delay_lo, a limit beyond 2^26, a device index out of range. */
+int blah2hip_clean_create(uint32_t n_samples, double fs, int32_t delay_lo, int32_t delay_hi, int device, uint32_t max_batch,
+                          blah2hip_clean_t *out);
+int blah2hip_clean_destroy(blah2hip_clean_t h); /* waits for the device first */
+/* BLAH2HIP_CLEAN_OPT_GRAM_GRID: workgroups per CPI of clean_gram_kernel; 0 = the engine's choice (eight a CU over the
+ * call).  Whatever is set, a launch has at most one workgroup per chunk of 1024 samples and no more than the handle
+ * holds partials for; BLAH2HIP_CLEAN_INFO_GRAM_GRID reads back what the last fit launched, _SUBTRACT_GRID the last
+ * subtraction's.  G and b depend on the grid in their last bits only (the fp64 partials are added in a fixed order). */
+#define BLAH2HIP_CLEAN_OPT_GRAM_GRID 1
+#define BLAH2HIP_CLEAN_INFO_GRAM_GRID 1
+#define BLAH2HIP_CLEAN_INFO_SUBTRACT_GRID 2
+int blah2hip_clean_set_option(blah2hip_clean_t h, int option, int64_t value);
+int blah2hip_clean_get_info(blah2hip_clean_t h, int what, int64_t *value);
+/* From final detection lists to atoms; one kernel (clean_atoms_kernel).  d_dets [n_cpi][cap] / d_count [n_cpi] as
+ * blah2hip_detect_dev leaves them (a count beyond cap: the first cap records are the list); amb gives the CPI length
+ * (dims.cpi) of the Doppler step.  Per CPI the records with snr >= snr_min_db are taken, the strongest first, ties by
+ * lower row, then lower col (then lower index), so the result does not depend on the list's order; max_echoes
+ * (<= BLAH2HIP_MAX_ATOMS) of them at the most.  Each expands to the cluster (rint(delay) + i, doppler + j 0.5 / cpi),
+ * |i| <= side_delay <= 2, |j| <= side_doppler <= 1, written in the order echo, i, j.  A member whose delay is outside
+ * [delay_lo, delay_hi] is dropped; an echo whose remaining members do not all fit behind the atoms already written is
+ * dropped whole (later, smaller clusters may still fit), as is one with no member left.  d_atoms [n_cpi][cap_atoms],
+ * d_atom_count [n_cpi] (never above cap_atoms), d_used [n_cpi][cap_atoms]: the indices into the CPI's list of the
+ * detections that gave atoms, in their order, -1 behind them -- what the merge of the two passes' lists needs.
+ * BLAH2HIP_ERR_INVALID, nothing enqueued: NULL pointer, n_cpi outside [1, max_batch], cap 0, cap_atoms outside
+ * [1, BLAH2HIP_MAX_ATOMS], max_echoes above BLAH2HIP_MAX_ATOMS, a side outside its range, snr_min_db NaN, a buffer off
+ * its alignment, an output overlapping an input or another output. */
+int blah2hip_clean_atoms_dev(blah2hip_clean_t h, blah2hip_amb_t amb, const blah2hip_det_t *d_dets, uint32_t cap, const uint32_t *d_count,
+                             uint32_t n_cpi, double snr_min_db, uint32_t max_echoes, int32_t side_delay, int32_t side_doppler,
+                             blah2hip_atom_t *d_atoms, uint32_t cap_atoms, uint32_t *d_atom_count, int32_t *d_used, void *stream);
+/* The fit: three kernels.  clean_gram_kernel reads x and y once per CPI: a workgroup walks chunks of 1024 samples,
+ * stages the chunk's x window plus the halo delay_hi - delay_lo in LDS, forms the replicas of 128 samples at a time and
+ * accumulates the lower triangle of G and b in 4 x 4 register blocks -- fp32 products, fp32 sums over runs of at most 32
+ * products, every longer addition in fp64, no floating-point atomics -- and leaves one partial per workgroup;
+ * clean_fold_kernel adds the partials in a fixed order -- in index order within 64 contiguous blocks, then the block
+ * sums in block order -- (two calls give the same bits; G has exact conjugate symmetry and
+ * a real diagonal); clean_solve_kernel factors G_l and solves in fp64.  Replica accuracy: the phase comes from fp64
+ * reductions of frac(f n0 / fs) at multiples of 128 samples times a 128-entry table per atom, never from an fp32 product
+ * f n: |error| <= 8 2^-24 |x| per sample at every n < n_samples <= 2^26 and |f| <= fs / 2 (clean_kernels.hpp derives
+ * 5.8).  d_atom_count[c] beyond cap_atoms: the first cap_atoms atoms are used.  An atom whose delay is outside
+ * [delay_lo, delay_hi] or whose Doppler is not finite sets that CPI's ok = 0 (no replica of it is formed).
+ * d_amp [n_cpi][cap_atoms] (re, im) doubles, zeros behind the CPI's atoms; d_ok [n_cpi] int32.
+ * BLAH2HIP_ERR_INVALID, nothing enqueued: NULL pointer, n_cpi outside [1, max_batch], cap_atoms outside
+ * [1, BLAH2HIP_MAX_ATOMS], cpi_stride < n_samples with n_cpi > 1, a buffer off its alignment, loading negative or not
+ * finite, an output overlapping an input or the other output. */
+int blah2hip_clean_fit_dev(blah2hip_clean_t h, int fmt, const void *d_x, const void *d_y, uint32_t n_cpi, uint64_t cpi_stride,
+                           const blah2hip_atom_t *d_atoms, uint32_t cap_atoms, const uint32_t *d_atom_count, double loading,
+                           double *d_amp, int32_t *d_ok, void *stream);
+/* The subtraction: one kernel (clean_subtract_kernel), the same staging and the same replicas as the fit's.  Per sample
+ * y - sum_p a_p s_p is an fp32 chain of fused multiply-adds in atom order, the amplitudes rounded once to fp32:
+ * |y_out - (y - S a)| <= about (P + 9) 2^-24 (|y| + sum_p |a_p| |x|) per sample.  16-byte accesses where a CPI's y and
+ * output rows both start on 16 bytes, single samples otherwise.  CPIs with ok = 0 or no atoms are copied, or skipped
+ * when in place.  d_y_out may be d_y (with out_stride == cpi_stride where n_cpi > 1); the samples of the stride gap are
+ * not written.  BLAH2HIP_ERR_INVALID as for the fit, and: out_stride < n_samples with n_cpi > 1, the output overlapping
+ * an input other than by that alias. */
+int blah2hip_clean_subtract_dev(blah2hip_clean_t h, int fmt, const void *d_x, const void *d_y, uint32_t n_cpi, uint64_t cpi_stride,
+                                const blah2hip_atom_t *d_atoms, uint32_t cap_atoms, const uint32_t *d_atom_count, const double *d_amp,
+                                const int32_t *d_ok, void *d_y_out, uint64_t out_stride, void *stream);
+/* blah2hip_clean_fit_dev followed by blah2hip_clean_subtract_dev; every refusal of either comes before anything is enqueued */
+int blah2hip_clean_process_dev(blah2hip_clean_t h, int fmt, const void *d_x, const void *d_y, uint32_t n_cpi, uint64_t cpi_stride,
+                               const blah2hip_atom_t *d_atoms, uint32_t cap_atoms, const uint32_t *d_atom_count, double loading,
+                               double *d_amp, int32_t *d_ok, void *d_y_out, uint64_t out_stride, void *stream);
+/* For tests and diagnosis: waits for the device, then copies CPI `cpi` of the last fit to the host: G [cap][cap] and
+ * b [cap] (re, im) doubles with cap = that fit's cap_atoms, the amplitudes [cap] and ok.  Any output may be NULL. */
+int blah2hip_clean_read_last(blah2hip_clean_t h, uint32_t cpi, double *G, double *b, double *amp, int32_t *ok);
+
 /* ---- per-kernel timing (HIP events on the launch stream) ---------------- */
 #define BLAH2HIP_K_RANGE 0
 #define BLAH2HIP_K_DOPPLER 1
@@ -1267,6 +1364,15 @@ int blah2hip_clutter_get_timing(blah2hip_clutter_t h, double *ms_total, uint32_t
 #define BLAH2HIP_NK_COUNT 3
 int blah2hip_nci_set_timing(blah2hip_nci_t n, int enable);
 int blah2hip_nci_get_timing(blah2hip_nci_t n, double *ms_total, uint32_t *launches);
+/* the same for the echo canceller's kernels, on its handle */
+#define BLAH2HIP_CLK_ATOMS 0    /* clean_atoms_kernel */
+#define BLAH2HIP_CLK_GRAM 1     /* clean_gram_kernel */
+#define BLAH2HIP_CLK_FOLD 2     /* clean_fold_kernel */
+#define BLAH2HIP_CLK_SOLVE 3    /* clean_solve_kernel */
+#define BLAH2HIP_CLK_SUBTRACT 4 /* clean_subtract_kernel */
+#define BLAH2HIP_CLK_COUNT 5
+int blah2hip_clean_set_timing(blah2hip_clean_t h, int enable);
+int blah2hip_clean_get_timing(blah2hip_clean_t h, double *ms_total, uint32_t *launches);
 
 #ifdef __cplusplus
 }
