@@ -17,7 +17,8 @@ from .process import doppler_rate, rate_bank, rate_bank_maps, rate_chirps  # noq
 from .process import integrate_tracks, nci_walk_table, track_tables  # noqa: F401
 from .process import ClutterMapDetector, clutter_map, clutter_map_alpha, clutter_map_alpha_table, clutter_map_pfa, clutter_map_weights, gate_hits  # noqa: F401
 from .process import ATOM_DTYPE, EchoCanceller, clean_atoms, clean_fit, clean_replicas, clean_subtract, merge_clean_detections  # noqa: F401
+from .process import Channelizer, ddc, ddc_design, ddc_taps  # noqa: F401
 
-__all__ = ["Ambiguity", "Centroid", "Interpolate", "CfarDetector1D", "CfarDetector2D", "Detection", "Map", "WienerHopf", "SpectrumAnalyser", "next_hamming", "Blah2HipError",
+__all__ =["Ambiguity", "Centroid", "Interpolate", "CfarDetector1D", "CfarDetector2D", "Detection", "Map", "WienerHopf", "SpectrumAnalyser", "next_hamming", "Blah2HipError",
            "FMT_C32", "FMT_I16", "FMT_F16", "FMT_I16X_C32Y", "FMT_I8", "FMT_I8X_C32Y", "deblock_c32_dev", "device_count", "load",
            "DetectionFinisher", "dets_to_detection", "DET_DTYPE", "BEARING_DTYPE", "bearing", "bearing_degrees", "uca_steering"]

@@ -83,6 +83,10 @@ CLEAN_INFO_GRAM_GRID, CLEAN_INFO_SUBTRACT_GRID = 1, 2
 CLK_ATOMS, CLK_GRAM, CLK_FOLD, CLK_SOLVE, CLK_SUBTRACT, CLK_COUNT = 0, 1, 2, 3, 4, 5
 CLEAN_KERNEL_NAMES = {CLK_ATOMS: "clean_atoms", CLK_GRAM: "clean_gram", CLK_FOLD: "clean_fold", CLK_SOLVE: "clean_solve",
                       CLK_SUBTRACT: "clean_subtract"}
+MAX_DDC_CARRIERS, MAX_DDC_DECIM, MAX_DDC_TAPS = 8, 64, 1024
+DDC_INFO_TILE, DDC_INFO_NEXT_SAMPLE = 1, 2
+DK_DDC, DK_TAIL, DK_COUNT = 0, 1, 2
+DDC_KERNEL_NAMES = {DK_DDC: "ddc", DK_TAIL: "ddc_tail"}
 
 
 class Blah2HipError(RuntimeError):
@@ -202,6 +206,15 @@ SYMBOLS = {
     "blah2hip_clean_read_last": (C.c_int, [_vp, _u32, _vp, _vp, _vp, _vp]),
     "blah2hip_clean_set_timing": (C.c_int, [_vp, C.c_int]),
     "blah2hip_clean_get_timing": (C.c_int, [_vp, _vp, _vp]),
+    "blah2hip_ddc_design": (C.c_int, [_u32, _u32, _dbl, _dbl, _vp]),
+    "blah2hip_ddc_create": (C.c_int, [_dbl, _u32, _vp, _u32, _vp, _u32, _u32, _u32, C.c_int, C.POINTER(_vp)]),
+    "blah2hip_ddc_destroy": (C.c_int, [_vp]),
+    "blah2hip_ddc_reset": (C.c_int, [_vp, C.c_uint64, _vp]),
+    "blah2hip_ddc_process_dev": (C.c_int, [_vp, C.c_int, _vp, _vp, _u32, _u32, C.c_uint64, _vp, _vp, C.c_uint64, C.c_uint64, _vp]),
+    "blah2hip_ddc_read_taps": (C.c_int, [_vp, _u32, _vp]),
+    "blah2hip_ddc_get_info": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int64)]),
+    "blah2hip_ddc_set_timing": (C.c_int, [_vp, C.c_int]),
+    "blah2hip_ddc_get_timing": (C.c_int, [_vp, _vp, _vp]),
     "blah2hip_centroid": (C.c_int, [_vp, _vp, _vp, _u32, C.c_uint16, C.c_uint16, _dbl, _vp, _vp, _vp, C.POINTER(_u32)]),
     "blah2hip_interpolate": (C.c_int, [_vp, _vp, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _dbl, C.c_int, C.c_int,
                                        _vp, _vp, _vp, C.POINTER(_u32)]),

@@ -89,7 +89,7 @@ def _build_hip_locked(force, verbose):
     # one hipcc per translation unit (every csrc/*.hip), side by side, then one link (8 CPUs, the ten units at once: capi.hip,
     # the longest, is done 84-89 s after the start, clutter.hip after 72-82 s, array.hip after 32-43 s, the others --
     # integrate.hip with its sixteen windows, taper.hip with its five stencils and walk.hip among them -- within 12 s;
-    # clean.hip, the eleventh, compiles alone in 3 s)
+    # clean.hip, the eleventh, compiles alone in 3 s, ddc.hip, the twelfth, in 6 s)
     procs = []
     try:
         for src in srcs:

@@ -2252,6 +2252,188 @@ class EchoCanceller:
         return {_lib.CLEAN_KERNEL_NAMES[k]: (ms[k], n[k]) for k in range(_lib.CLK_COUNT)}
 
 
+def _bessel_i0(x):
+    """I0 by its series sum_k ((x / 2)^k / k!)^2 (the library's bessel_i0, term for term)."""
+    x = np.asarray(x, dtype=np.float64)
+    q = 0.25 * x * x
+    term, total = np.ones_like(x), np.ones_like(x)
+    for k in range(1, 1000):
+        term = term * (q / (float(k) * float(k)))
+        total = total + term
+        if np.all(term < 1e-17 * total):
+            break
+    return total
+
+
+def _ddc_sizes(decim, n_taps):
+    if int(decim) != decim or not 1 <= decim <= _lib.MAX_DDC_DECIM:
+        raise ValueError(f"decimation {decim!r} outside [1, {_lib.MAX_DDC_DECIM}]")
+    if int(n_taps) != n_taps or not 1 <= n_taps <= _lib.MAX_DDC_TAPS:
+        raise ValueError(f"n_taps {n_taps!r} outside [1, {_lib.MAX_DDC_TAPS}]")
+    return int(decim), int(n_taps)
+
+
+def ddc_design(decim, n_taps, cutoff=0.8, beta=8.0):
+    """The NumPy twin of blah2hip_ddc_design: the down-converter's low-pass, a Kaiser-windowed sinc in fp64,
+    ``h[t] ~ sinc(2 nu (t - (T-1)/2)) I0(beta sqrt(1 - ((2t - (T-1)) / (T-1))^2))`` with ``nu = cutoff / (2 decim)``,
+    normalised to ``sum h = 1`` and symmetric bit for bit."""
+    D, T = _ddc_sizes(decim, n_taps)
+    if not (0.0 < cutoff <= 1.0):
+        raise ValueError("cutoff outside (0, 1]")
+    if not (math.isfinite(beta) and beta >= 0.0):
+        raise ValueError("beta negative or not finite")
+    nu = cutoff / (2.0 * D)
+    half = (T + 1) // 2
+    k = 2.0 * np.arange(half, dtype=np.float64) - float(T - 1)
+    a = math.pi * nu * k
+    with np.errstate(invalid="ignore", divide="ignore"):
+        sinc = np.where(a == 0.0, 1.0, np.sin(a) / a)
+    rel = k / float(T - 1) if T > 1 else np.zeros(half)
+    v = sinc * _bessel_i0(beta * np.sqrt(np.maximum(0.0, 1.0 - rel * rel)))
+    h = np.empty(T, dtype=np.float64)
+    h[:half] = v
+    h[T - half:] = v[::-1]
+    s = math.fsum(h)
+    if not (math.isfinite(s) and abs(s) > 0.0):
+        raise ValueError("the taps sum to zero")
+    return h / s
+
+
+def ddc_taps(h, f, fs):
+    """``h[t] exp(+2 pi i f t / fs)`` in fp64 (complex128 ``[T]``): the down-converter's taps of the carrier at offset ``f``
+    before their one rounding to fp32 (blah2hip_ddc_read_taps returns the rounded ones)."""
+    h = np.asarray(h, dtype=np.float64)
+    a = float(f) / float(fs)
+    # frac(a t) exactly (integers), about the whole number next to the rounded product, as the library reduces it
+    num, den = a.as_integer_ratio()
+    k = np.rint(a * np.arange(h.shape[0], dtype=np.float64))
+    ang = 2.0 * math.pi * np.array([(num * t - int(k[t]) * den) / den for t in range(h.shape[0])], dtype=np.float64)
+    return h * np.cos(ang) + 1j * (h * np.sin(ang))
+
+
+def _ddc_phasor(r, m0, n):
+    """``exp(-2 pi i frac(r m))`` for ``m = m0 .. m0 + n - 1``, the product r m taken exactly (integers)."""
+    num, den = float(r).as_integer_ratio()
+    fr = np.array([((num * m) % den) / den for m in range(int(m0), int(m0) + int(n))], dtype=np.float64)
+    fr = np.where(fr > 0.5, fr - 1.0, fr)
+    return np.cos(2.0 * math.pi * fr) - 1j * np.sin(2.0 * math.pi * fr)
+
+
+def ddc(u, f, fs, D, h, first_sample=0, history=None, g=None, detail=False):
+    """The fp64 restatement of the down-converter (blah2hip_ddc_process_dev) in the form the kernel runs:
+    ``v[m] = p[m] sum_t g[t] u[m D - t]`` with ``g = fp32(ddc_taps(h, f, fs))``, ``p[m] = exp(-2 pi i frac(r m))``,
+    ``r = f D / fs``, ``m`` the absolute output index ``first_sample / D + 0, 1, ...``.
+
+    ``u``: ``[..., n]`` samples (``n`` a multiple of ``D``; leading axes are channels) that start at absolute index
+    ``first_sample``; ``history``: the ``T - 1`` samples in front of them (``[..., T - 1]``, zeros when None).  ``g``
+    overrides the taps (complex ``[T]``, e.g. the library's read-back).  Returns ``(v [..., n / D], history_out)`` --
+    pass ``history_out`` and ``first_sample + n`` on to continue the stream: the pieces equal the uncut result bit for
+    bit (the sum runs tap by tap in a fixed order, in real arithmetic) -- and with ``detail`` also
+    ``sum_t |g[t]| |u[m D - t]|``, what the contract's bound is made of."""
+    D, T = _ddc_sizes(D, np.asarray(h).shape[0] if g is None else np.asarray(g).shape[0])
+    u = np.asarray(u, dtype=np.complex128)
+    n = u.shape[-1]
+    if n % D or int(first_sample) % D:
+        raise ValueError("the sample count and first_sample must be multiples of the decimation")
+    if g is None:
+        g = ddc_taps(h, f, fs).astype(np.complex64)
+    g = np.asarray(g).astype(np.complex128)
+    lead = u.shape[:-1]
+    if history is None:
+        history = np.zeros(lead + (T - 1,), dtype=np.complex128)
+    history = np.asarray(history, dtype=np.complex128)
+    if history.shape != lead + (T - 1,):
+        raise ValueError(f"history must have shape {lead + (T - 1,)}")
+    ext = np.concatenate([history, u], axis=-1)
+    n_out = n // D
+    er, ei = np.ascontiguousarray(ext.real), np.ascontiguousarray(ext.imag)
+    ar, ai = np.zeros(lead + (n_out,)), np.zeros(lead + (n_out,))
+    S = np.zeros(lead + (n_out,))
+    mag = np.abs(ext) if detail else None
+    for t in range(T - 1, -1, -1):  # u[m D - t] is ext[T - 1 - t + m D]
+        sl = slice(T - 1 - t, T - 1 - t + (n_out - 1) * D + 1, D)
+        gr, gi = g[t].real, g[t].imag
+        ar += gr * er[..., sl]
+        ar -= gi * ei[..., sl]
+        ai += gr * ei[..., sl]
+        ai += gi * er[..., sl]
+        if detail:
+            S += abs(g[t]) * mag[..., sl]
+    p = _ddc_phasor(float(f) * D / float(fs), int(first_sample) // D, n_out)
+    v = (ar * p.real - ai * p.imag) + 1j * (ar * p.imag + ai * p.real)
+    hist_out = ext[..., ext.shape[-1] - (T - 1):].copy()
+    return (v, hist_out, S) if detail else (v, hist_out)
+
+
+class Channelizer:
+    """The digital down-converter on the device (blah2hip_ddc_*; no reference counterpart): up to eight carriers of a
+    two-channel stream mixed to zero, low-passed by the real taps ``h`` and decimated by ``decim`` in one pass over the
+    samples; :func:`ddc` restates it.  ``offsets``: the carriers' offsets in Hz (``|f| <= fs / 2``).  Calls bring at
+    most ``max_rows`` rows of at most ``max_in`` samples; the stream's history is carried from call to call."""
+
+    def __init__(self, fs, decim, h, offsets, max_in, max_rows=1, device=0):
+        L = _lib.load()
+        hh = np.ascontiguousarray(np.asarray(h, dtype=np.float64).ravel())
+        off = np.ascontiguousarray(np.atleast_1d(np.asarray(offsets, dtype=np.float64)).ravel())
+        hd = C.c_void_p()
+        check(L.blah2hip_ddc_create(float(fs), int(decim), _ptr(hh), int(hh.shape[0]), _ptr(off), int(off.shape[0]), int(max_in),
+                                    int(max_rows), int(device), C.byref(hd)))
+        self._h, self._L = hd, L
+        self.fs, self.decim, self.n_taps, self.offsets = float(fs), int(decim), int(hh.shape[0]), off.copy()
+        self.n_carriers, self.max_in, self.max_rows = int(off.shape[0]), int(max_in), int(max_rows)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.blah2hip_ddc_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self, first_sample=0, stream=0):
+        """The next call's first sample is absolute sample ``first_sample`` (a multiple of ``decim``); zero history."""
+        check(self._L.blah2hip_ddc_reset(self._h, int(first_sample), stream))
+
+    def process_dev(self, fmt, d_x, d_y, n_in, n_rows, in_stride, d_out_x, d_out_y, out_stride, carrier_stride, stream=0):
+        """Enqueue blah2hip_ddc_process_dev: ``n_rows`` rows of ``n_in`` samples at ``in_stride`` -> carrier ``c``, row ``r``
+        of either output at ``c * carrier_stride + r * out_stride`` complex fp32 values."""
+        check(self._L.blah2hip_ddc_process_dev(self._h, int(fmt), d_x, d_y, int(n_in), int(n_rows), int(in_stride), d_out_x, d_out_y,
+                                               int(out_stride), int(carrier_stride), stream))
+
+    def taps(self, carrier=0):
+        """``g_c`` as the kernel multiplies with it (complex64 ``[n_taps]``, read back from the device)."""
+        g = np.zeros(self.n_taps, dtype=np.complex64)
+        check(self._L.blah2hip_ddc_read_taps(self._h, int(carrier), _ptr(g)))
+        return g
+
+    def get_info(self, what):
+        v = C.c_int64(0)
+        check(self._L.blah2hip_ddc_get_info(self._h, int(what), C.byref(v)))
+        return v.value
+
+    @property
+    def tile(self):
+        """Outputs per workgroup of this handle."""
+        return self.get_info(_lib.DDC_INFO_TILE)
+
+    @property
+    def next_sample(self):
+        return self.get_info(_lib.DDC_INFO_NEXT_SAMPLE)
+
+    def set_timing(self, enable=True):
+        check(self._L.blah2hip_ddc_set_timing(self._h, int(bool(enable))))
+
+    def get_timing(self):
+        """``{kernel name: (ms_total, launches)}`` since the last call (waits for the device)."""
+        ms = (C.c_double * _lib.DK_COUNT)()
+        n = (C.c_uint32 * _lib.DK_COUNT)()
+        check(self._L.blah2hip_ddc_get_timing(self._h, ms, n))
+        return {_lib.DDC_KERNEL_NAMES[k]: (ms[k], n[k]) for k in range(_lib.DK_COUNT)}
+
+
 # the fused kernel (range_fir_kernel) convolves a CPI with ONE tap set
 _FIR_BLOCKS_REASON = "the fused FIR takes one tap set per CPI: a clutter filter with blocks > 1 runs the two-stage chain"
 

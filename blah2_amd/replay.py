@@ -656,7 +656,17 @@ class GpuChain:
     two-stage filter so that the filtered plane exists.  ValueError, naming the key: values outside their ranges, no device
     finisher (no ``nCentroid``, or ``detect="host"``), ``integrate`` or ``clutterMap`` configured (either would absorb every
     CPI twice), no fp32 surveillance plane at that point (int16 or int8 words and no clutter filter).  Without the key
-    nothing is allocated or launched."""
+    nothing is allocated or launched.
+
+    ``cfg["ddc"] = {"offset": HZ, "decimation": D, "taps": T, "cutoff": 0.8, "beta": 8}`` (``capture.ddc`` of the config,
+    ``--ddc``) puts the digital down-converter in front: ``cfg["fs"]`` and ``cfg["n_samples"]`` stay the capture's, the reader
+    cuts CPIs of ``n_samples`` as before, a batch's raw samples (a USRP batch's de-blocked planes) go through
+    ``blah2_amd.Channelizer`` into one pair of fp32 planes, and everything above is built for ``fs / D`` and ``n_samples / D``
+    and runs on them as an ``FMT_C32`` chain (``self.fs``, ``self.n``; ``self.fs_in``, ``self.n_in`` are the capture's).  A
+    migration or track carrier becomes ``fc + offset``.  ``taps`` defaults to ``16 D`` (at most 1024).  The filter's history
+    runs from batch to batch: ``run_batches`` resets it, wants consecutive batches, and ``shard_check`` refuses several ranks.
+    ValueError, naming ``capture.ddc``: values outside their ranges, a decimation that does not divide ``fs`` and
+    ``n_samples``.  Without the key nothing is allocated or launched."""
 
     def __init__(self, cfg: dict, device: int = 0, batch: int = 1, want_map: bool = False, depth: int = 3,
                  reader_threads: int = 4, hit_copy: int = 4096, read_mode: str = "memmove", numa: bool = True,
@@ -715,8 +725,39 @@ class GpuChain:
     def _build(self, cfg, device, batch, want_map, depth, reader_threads, hit_copy, read_mode):
         torch, blah2_amd = self.torch, self.b2
         amb_c, det_c, clu_c = cfg["ambiguity"], cfg.get("detection", {}), cfg.get("clutter", {})
-        self.fs, self.n = int(cfg["fs"]), int(cfg["n_samples"])
+        # ddc: {offset: HZ, decimation: D, taps: T, cutoff: 0.8, beta: 8}: one carrier of a wideband capture mixed to zero,
+        # low-passed and decimated on the device in front of everything (None: no such stage).  The reader cuts CPIs of
+        # n_in samples at fs_in; the chain behind the down-converter runs at fs_in / D on n_in / D samples.
+        self.fs_in, self.n_in = int(cfg["fs"]), int(cfg["n_samples"])
+        self.ddc, self.ddc_cfg, self.ddc_planes = None, None, None
+        dd = cfg.get("ddc")
+        dd = None if dd is False else dd
+        ddc_D = 1
+        if dd is not None:
+            try:
+                if not isinstance(dd, dict) or dd.get("offset") is None or dd.get("decimation") is None:
+                    raise ValueError("{offset: HZ, decimation: D, taps: T, cutoff: 0.8, beta: 8} with an offset and a decimation")
+                if isinstance(dd["decimation"], bool) or int(dd["decimation"]) != dd["decimation"]:
+                    raise ValueError("decimation is not a whole number")
+                ddc_D = int(dd["decimation"])
+                if not 1 <= ddc_D <= blah2_amd._lib.MAX_DDC_DECIM:
+                    raise ValueError(f"decimation outside [1, {blah2_amd._lib.MAX_DDC_DECIM}]")
+                taps_ = dd.get("taps")
+                dc = {"offset": float(dd["offset"]), "decimation": ddc_D,
+                      "taps": int(taps_) if taps_ is not None else min(16 * ddc_D, blah2_amd._lib.MAX_DDC_TAPS),
+                      "cutoff": float(dd.get("cutoff", 0.8) if dd.get("cutoff") is not None else 0.8),
+                      "beta": float(dd.get("beta", 8.0) if dd.get("beta") is not None else 8.0)}
+                if not math.isfinite(dc["offset"]) or abs(dc["offset"]) > self.fs_in / 2:
+                    raise ValueError("offset not finite or beyond fs / 2")
+                if self.fs_in % ddc_D or self.n_in % ddc_D:
+                    raise ValueError(f"decimation {ddc_D} does not divide fs = {self.fs_in} and the CPI of {self.n_in} samples")
+                ddc_h = blah2_amd.ddc_design(ddc_D, dc["taps"], dc["cutoff"], dc["beta"])  # (refuses sizes, cutoff and beta outside their ranges)
+            except (TypeError, ValueError) as e:
+                raise ValueError(f"capture.ddc = {dd!r}: {e}") from None
+            self.ddc_cfg = dc
+        self.fs, self.n = self.fs_in // ddc_D, self.n_in // ddc_D
         n, B = self.n, int(batch)
+        n_in = self.n_in
         self.batch, self.depth, self.want_map = B, max(2, int(depth)), bool(want_map)
         # ambiguity: {window: NAME[:norm]}: the Doppler taper's taps (None: no taper stage)
         self.taper = None
@@ -734,7 +775,7 @@ class GpuChain:
             fc = mig.get("fc") if isinstance(mig, dict) else None
             if fc is None:
                 raise ValueError("ambiguity.migration needs the carrier frequency: {fc: HZ}")
-            fc = float(fc)
+            fc = float(fc) + (self.ddc_cfg["offset"] if self.ddc_cfg else 0.0)  # (the down-converted carrier's own frequency)
             if not math.isfinite(fc) or not fc > 0.0:
                 raise ValueError(f"ambiguity.migration: fc = {fc!r} is not a positive, finite frequency")
         # ambiguity: {dopplerRate: QMAX | {max: QMAX, step: S}}: the bank -QMAX .. QMAX of Doppler rates (None: no such stage)
@@ -802,7 +843,7 @@ class GpuChain:
                 try:
                     if not isinstance(trk, dict) or trk.get("fc") is None:
                         raise ValueError("needs the carrier frequency: {fc: HZ}")
-                    fc_t = float(trk["fc"])
+                    fc_t = float(trk["fc"]) + (self.ddc_cfg["offset"] if self.ddc_cfg else 0.0)
                     if not math.isfinite(fc_t) or not fc_t > 0.0:
                         raise ValueError(f"fc = {fc_t!r} is not a positive, finite frequency")
                     rate_t = trk.get("rate")
@@ -898,9 +939,9 @@ class GpuChain:
                     raise ValueError("integrate is configured: the integrator's window would see every CPI twice")
                 if self.cmap is not None:
                     raise ValueError("clutterMap is configured: its history would absorb every CPI twice")
-                if self.wh is None and self.layout != "usrp":
+                if self.wh is None and self.layout != "usrp" and self.ddc_cfg is None:
                     raise ValueError("the surveillance channel is not an fp32 plane at that point: it takes a C32 (USRP) "
-                                     "capture or an enabled clutter filter, whose output is one")
+                                     "capture, the down-converter or an enabled clutter filter, whose output is one")
                 self.clean = blah2_amd.EchoCanceller(n, self.fs, amb_c["delayMin"], amb_c["delayMax"], device=device, max_batch=B)
             except (ValueError, blah2_amd.Blah2HipError) as e:
                 for h_ in (self.nci, self.cmap, self.wh):
@@ -939,9 +980,17 @@ class GpuChain:
         self.yf = torch.empty((B, n), dtype=torch.complex64, device=dev) if self.wh is not None and not self.fused_fir else None
         # USRP: a batch's raw bytes are whole block pairs, at most B*n*16 + 32*block of them (a CPI run that starts and ends
         # mid-block); the de-blocked x and y planes are one pair for all slots, like yf
-        self.raw_bytes = (-(-(B * n * 2 * FC32_BYTES + 4 * self.usrp_block * FC32_BYTES) // 16) * 16 if self.layout == "usrp" else
-                          2 * B * n * CS8_BYTES if self.layout == "cs8" else None)  # cs8: the x bytes, then the y bytes
-        self.planes = torch.empty((2, B, n), dtype=torch.complex64, device=dev) if self.layout == "usrp" else None
+        self.raw_bytes = (-(-(B * n_in * 2 * FC32_BYTES + 4 * self.usrp_block * FC32_BYTES) // 16) * 16 if self.layout == "usrp" else
+                          2 * B * n_in * CS8_BYTES if self.layout == "cs8" else None)  # cs8: the x bytes, then the y bytes
+        self.planes = torch.empty((2, B, n_in), dtype=torch.complex64, device=dev) if self.layout == "usrp" else None
+        # the down-converter: one carrier, the history carried from batch to batch; its output planes are one pair for all
+        # slots, like yf
+        if self.ddc_cfg is not None:
+            try:
+                self.ddc = blah2_amd.Channelizer(self.fs_in, ddc_D, ddc_h, [self.ddc_cfg["offset"]], n_in, max_rows=B, device=device)
+            except blah2_amd.Blah2HipError as e:
+                raise ValueError(f"capture.ddc = {dd!r}: {e}") from None
+            self.ddc_planes = torch.empty((2, B, n), dtype=torch.complex64, device=dev)
         self.busy_ms, self.batches_done = 0.0, 0  # kernels' time on the compute stream / batches collected, since construction
         self.slots = []
         on_dev = self.finisher is not None
@@ -950,7 +999,7 @@ class GpuChain:
                 "h_iq": None,  # pinned staging batch of the pread path, allocated when that path first runs
                 "h_ends": torch.empty(4 * PAGE, dtype=torch.uint8).pin_memory(),  # the ragged ends of a mapped batch's (one or two) runs
                 "registered": [],
-                "d_iq": torch.empty((B, n, 4), dtype=torch.int16, device=dev) if self.layout == "rspduo" else
+                "d_iq": torch.empty((B, n_in, 4), dtype=torch.int16, device=dev) if self.layout == "rspduo" else
                         torch.empty(self.raw_bytes, dtype=torch.uint8, device=dev),
                 "first": 0,  # the batch's first sample inside its raw bytes (UsrpFile.extent)
                 "d_met": torch.zeros((B, 2), dtype=torch.float64, device=dev),
@@ -1003,13 +1052,15 @@ class GpuChain:
 
     def _fmt_in(self):
         """The format the filter and the range kernel read: the .rspduo words, the int8 planes, or the de-blocked USRP planes."""
+        if self.ddc_cfg is not None:  # ... or the down-converter's planes
+            return self.b2.FMT_C32
         return {"rspduo": self.b2.FMT_I16, "cs8": self.b2.FMT_I8}.get(self.layout, self.b2.FMT_C32)
 
     def _host_batch(self):
         """The pinned staging batch of the copying read paths."""
         with self._on_node():
             if self.layout == "rspduo":
-                return self.torch.empty((self.batch, self.n, 4), dtype=self.torch.int16).pin_memory()
+                return self.torch.empty((self.batch, self.n_in, 4), dtype=self.torch.int16).pin_memory()
             return self.torch.empty(self.raw_bytes, dtype=self.torch.uint8).pin_memory()
 
     def _check_capture(self, capture):
@@ -1094,7 +1145,11 @@ class GpuChain:
                 fmt, fmt_yf, x, y = b2.FMT_I8, b2.FMT_I8X_C32Y, iq, iq + slot["nbytes"] // 2
             else:  # USRP: the batch's block pairs into the x and y planes first
                 fmt, fmt_yf, x, y = b2.FMT_C32, b2.FMT_C32, self.planes[0].data_ptr(), self.planes[1].data_ptr()
-                b2.deblock_c32_dev(iq, self.usrp_block, slot["first"], n, cnt, x, y, n, st)
+                b2.deblock_c32_dev(iq, self.usrp_block, slot["first"], self.n_in, cnt, x, y, self.n_in, st)
+            if self.ddc is not None:  # the batch's CPIs are consecutive rows of the stream; the chain reads the carrier's planes
+                px, py_ = self.ddc_planes[0].data_ptr(), self.ddc_planes[1].data_ptr()
+                self.ddc.process_dev(fmt, x, y, self.n_in, cnt, self.n_in, px, py_, n, cnt * n, st)
+                fmt, fmt_yf, x, y = b2.FMT_C32, b2.FMT_C32, px, py_
             if self.wh is None:
                 amb.process_dev(fmt, x, y, cnt, n, slot["d_map"].data_ptr(), slot["d_met"].data_ptr(), st)
             elif self.fused_fir:
@@ -1279,6 +1334,10 @@ class GpuChain:
         if self.cmap is not None:
             self.cmap.reset()  # a new capture: age 0
         batches = list(batches)
+        if self.ddc is not None:  # a new capture: zero history, the stream's position at the first batch
+            if any(a[0] + a[1] != b[0] for a, b in zip(batches, batches[1:])):
+                raise ValueError("capture.ddc: the batches are not consecutive CPIs, so the down-converter's history does not carry")
+            self.ddc.reset(batches[0][0] * self.n_in if batches else 0, self.compute.cuda_stream)
         D, n = self.depth, len(batches)
         reads = {}
 
@@ -1341,6 +1400,9 @@ class GpuChain:
         if self.cmap is not None and world > 1:
             raise ValueError(f"detection.clutterMap over {world} ranks: the batches go round-robin, so no rank sees the "
                              "consecutive CPIs a cell's history is made of")
+        if self.ddc is not None and world > 1:
+            raise ValueError(f"capture.ddc over {world} ranks: the batches go round-robin, so no rank sees the "
+                             "consecutive CPIs the filter's history is made of")
         if self.nci is None or world <= 1:
             return
         W, H = self.nci.window, self.nci.hop
@@ -1365,6 +1427,8 @@ class GpuChain:
             self.cmap.close()
         if getattr(self, "clean", None) is not None:
             self.clean.close()
+        if getattr(self, "ddc", None) is not None:
+            self.ddc.close()
 
 
 def gpu_processor(cfg: dict, device: int = 0, batch: int = 1, want_map: bool = False, **kw) -> GpuChain:
@@ -1476,6 +1540,13 @@ def main(argv=None):
                          "device detection and an fp32 surveillance plane (a USRP capture or the clutter filter); not with "
                          "--integrate or --clutter-map.  Overrides process.detection.clean ({snr, echoes, sideDelay, "
                          "sideDoppler, loading})")
+    ap.add_argument("--ddc", default=None, metavar="OFFSET_HZ:DECIM[:TAPS[:CUTOFF[:BETA]]]",
+                    help="wideband captures: mix the carrier OFFSET_HZ off the capture's centre to zero, low-pass (a Kaiser-"
+                         "windowed sinc of TAPS taps, default 16 DECIM and at most 1024, pass band CUTOFF of the output's "
+                         "Nyquist rate, default 0.8, BETA default 8) and decimate by DECIM (1 .. 64, a divisor of capture.fs "
+                         "and of the CPI's samples) on the device; everything behind runs at capture.fs / DECIM, and the "
+                         "migration carrier becomes capture.fc + OFFSET_HZ.  One rank.  Overrides capture.ddc ({offset, "
+                         "decimation, taps, cutoff, beta})")
     ap.add_argument("--connect", action="store_true",
                     help="with --json: send the documents to network.ip:ports.map / ports.detection of the config, "
                          "framed like Socket::sendData, instead of printing them")
@@ -1496,6 +1567,20 @@ def main(argv=None):
     fs = int(y["capture"]["fs"])
     n = int(fs * float(y["process"]["data"]["cpi"]))  # blah2.cpp:142-144
     cfg = dict(y["process"], fs=fs, n_samples=n)
+    if y["capture"].get("ddc"):
+        cfg["ddc"] = dict(y["capture"]["ddc"])
+    if a.ddc is not None:
+        try:
+            parts_ = a.ddc.split(":")
+            if not 2 <= len(parts_) <= 5:
+                raise ValueError
+            cfg["ddc"] = {"offset": float(parts_[0]), "decimation": int(parts_[1])}
+            for key_, conv_, val_ in zip(("taps", "cutoff", "beta"), (int, float, float), parts_[2:]):
+                cfg["ddc"][key_] = conv_(val_)
+        except ValueError:
+            ap.error("--ddc takes OFFSET_HZ:DECIM[:TAPS[:CUTOFF[:BETA]]]")
+    if cfg.get("ddc") and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        ap.error("--ddc / capture.ddc needs the CPIs in order: one rank")
     if a.clutter_blocks is not None:
         if a.clutter_blocks < 1:
             ap.error("--clutter-blocks takes a block count >= 1")
@@ -1619,7 +1704,7 @@ def main(argv=None):
         if r.get("skipped") or r.get("integrating") or not a.json:
             return r
         # replay has no wall clock: CPI k is stamped k * tCpi in ms (blah2.cpp uses the capture time in ms)
-        return {"cpi": r["cpi"], "frames": frames_for(r, proc.amb, fs, r["cpi"] * t_cpi_ms)}
+        return {"cpi": r["cpi"], "frames": frames_for(r, proc.amb, proc.fs, r["cpi"] * t_cpi_ms)}
 
     def emit(r):  # rank 0, file order, as the rounds complete: a write per document
         if r.get("skipped") or (a.json and r.get("integrating")):

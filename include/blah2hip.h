@@ -1330,6 +1330,71 @@ int blah2hip_clean_process_dev(blah2hip_clean_t h, int fmt, const void *d_x, con
  * b [cap] (re, im) doubles with cap = that fit's cap_atoms, the amplitudes [cap] and ok.  Any output may be NULL. */
 int blah2hip_clean_read_last(blah2hip_clean_t h, uint32_t cpi, double *G, double *b, double *amp, int32_t *ok);
 
+/* ---- digital down-converter: mix, low-pass and decimate carriers ----------
+ * No reference counterpart.  A wideband capture holds several carriers; this stage delivers each of up to
+ * BLAH2HIP_MAX_DDC_CARRIERS of them at fs / decim from one pass over the samples, as BLAH2HIP_FMT_C32 planes for the chain
+ * behind it.  It works on a two-channel stream u[n] (the reference x and the surveillance y), n the absolute sample index,
+ * u[n] = 0 for n < first_sample.  With real taps h[0 .. T-1], the decimation D, the carrier offsets f_c (Hz) and the
+ * input rate fs, output m (absolute index; the first is first_sample / D) of carrier c is
+ *   v_c[m] = sum_t h[t] u[m D - t] exp(-2 pi i f_c (m D - t) / fs)  =  p_c[m] sum_t g_c[t] u[m D - t]
+ *   g_c[t] = fp32(h[t] exp(+2 pi i f_c t / fs)),   p_c[m] = exp(-2 pi i frac(r_c m)),   r_c = f_c D / fs in fp64.
+ * The second form is what runs: g_c is made in fp64 at create from exactly reduced arguments and rounded once;
+ * each output gets one phasor, r_c m taken with its exact fused residual -- no fp32 product f n exists.  Both
+ * channels go through the same taps, so the common group delay of (T - 1) / 2 input samples cancels in the map.
+ * blah2_amd.process.ddc restates it in NumPy.  Contract, against that restatement with the read-back g_c:
+ *   |v - v_fp64| <= (3 T + 8) 2^-24 sum_t |g_c[t]| |u[m D - t]|   per output
+ * (csrc/ddc_kernels.hpp derives it).  int16, int8 and fp32 samples convert exactly.
+ * Stream.  A call brings n_rows rows of n_in samples (n_in a multiple of D), consecutive pieces of one stream; the T - 1
+ * samples in front of row 0 are the handle's carried history, zeros after create and reset; a call shorter than the
+ * history shifts it.  An output's bits depend on its absolute index and the samples under its taps only: the same stream
+ * in one call or in any split over rows and calls gives the same bits.  No floating-point atomics. */
+#define BLAH2HIP_MAX_DDC_CARRIERS 8
+#define BLAH2HIP_MAX_DDC_DECIM 64
+#define BLAH2HIP_MAX_DDC_TAPS 1024
+typedef struct blah2hip_ddc_s *blah2hip_ddc_t;
+/* Host only: a Kaiser-windowed sinc in fp64,
+ *   h[t] ~ sinc(2 nu (t - (T-1)/2)) I0(beta sqrt(1 - ((2 t - (T-1)) / (T-1))^2)),   nu = cutoff / (2 decim),
+ * sinc(x) = sin(pi x) / (pi x), I0 by its series, normalised to sum h = 1 and symmetric bit for bit (n_taps = 1: h = 1).
+ * cutoff is the pass band's edge as a fraction of the output's Nyquist rate.  BLAH2HIP_ERR_INVALID: a NULL table,
+ * cutoff outside (0, 1], beta negative or not finite, decim outside [1, BLAH2HIP_MAX_DDC_DECIM], n_taps outside
+ * [1, BLAH2HIP_MAX_DDC_TAPS]. */
+int blah2hip_ddc_design(uint32_t decim, uint32_t n_taps, double cutoff, double beta, double *h);
+/* A down-converter for n_carriers carriers at offset_hz[c] (|f_c| <= fs / 2), calls of at most max_rows (<= 65535) rows of
+ * at most max_in (<= 2^30, a multiple of decim) samples.  Everything is allocated here.  BLAH2HIP_ERR_INVALID: a NULL
+ * argument, sizes beyond the limits above, fs, a tap or an offset not finite, fs not positive, an offset beyond fs / 2,
+ * max_in or max_rows zero or beyond their limits, a device index out of range; the arguments are checked before the
+ * device is looked for. */
+int blah2hip_ddc_create(double fs, uint32_t decim, const double *h, uint32_t n_taps, const double *offset_hz, uint32_t n_carriers,
+                        uint32_t max_in, uint32_t max_rows, int device, blah2hip_ddc_t *out);
+int blah2hip_ddc_destroy(blah2hip_ddc_t h); /* waits for the device first */
+/* The next call's row 0 starts at absolute sample first_sample (a multiple of decim, else BLAH2HIP_ERR_INVALID); the
+ * history is zeroed.  One kernel on `stream`. */
+int blah2hip_ddc_reset(blah2hip_ddc_t h, uint64_t first_sample, void *stream);
+/* Enqueues ddc_kernel and, behind it, ddc_tail_kernel (the new history and the position, both kept on the device, so a
+ * captured graph that is replayed goes on with the stream).  fmt: BLAH2HIP_FMT_C32 (planes d_x, d_y of complex fp32, 8-byte
+ * aligned), BLAH2HIP_FMT_I16 (d_x: words I1 Q1 I2 Q2, 8-byte aligned; d_y is not looked at and may be NULL) or
+ * BLAH2HIP_FMT_I8 (planes of int8 (I, Q) pairs, 2-byte aligned); any other: BLAH2HIP_ERR_UNSUPPORTED.  Row r of the input
+ * starts r * in_stride samples in.  n_out = n_in / decim outputs per row: carrier c, row r of either output plane sits at
+ * c * carrier_stride + r * out_stride complex fp32 values, so that every carrier's output is a BLAH2HIP_FMT_C32 batch as it
+ * stands; values of the gaps are not written, input values of the gaps not read.
+ * A workgroup owns BLAH2HIP_DDC_INFO_TILE consecutive outputs of a row for all carriers and both channels and reads its
+ * input window once, into LDS by polyphase (csrc/ddc_kernels.hpp).
+ * BLAH2HIP_ERR_INVALID, with nothing enqueued and the stream position unchanged: a NULL pointer, n_in zero, above max_in
+ * or no multiple of decim, n_rows zero or above max_rows, in_stride < n_in or out_stride < n_out with n_rows > 1,
+ * carrier_stride below a carrier's extent with n_carriers > 1, a buffer off its alignment, an output overlapping an
+ * input or the other output. */
+int blah2hip_ddc_process_dev(blah2hip_ddc_t h, int fmt, const void *d_x, const void *d_y, uint32_t n_in, uint32_t n_rows, uint64_t in_stride,
+                             void *d_out_x, void *d_out_y, uint64_t out_stride, uint64_t carrier_stride, void *stream);
+/* the 2 n_taps floats (re, im) of g_c as the kernel multiplies with them, read back from the device */
+int blah2hip_ddc_read_taps(blah2hip_ddc_t h, uint32_t carrier, float *g);
+/* BLAH2HIP_DDC_INFO_TILE: outputs per workgroup of this handle (a function of decim and n_taps: the window of
+ * tile * decim + n_taps - 1 samples fits 80 KB of LDS, two workgroups a CU).  _NEXT_SAMPLE: the absolute index of the
+ * next call's first sample, as the calls made through this interface leave it (replays of a captured graph are not
+ * counted here; the device's own position follows them). */
+#define BLAH2HIP_DDC_INFO_TILE 1
+#define BLAH2HIP_DDC_INFO_NEXT_SAMPLE 2
+int blah2hip_ddc_get_info(blah2hip_ddc_t h, int what, int64_t *value);
+
 /* ---- per-kernel timing (HIP events on the launch stream) ---------------- */
 #define BLAH2HIP_K_RANGE 0
 #define BLAH2HIP_K_DOPPLER 1
@@ -1373,6 +1438,12 @@ int blah2hip_nci_get_timing(blah2hip_nci_t n, double *ms_total, uint32_t *launch
 #define BLAH2HIP_CLK_COUNT 5
 int blah2hip_clean_set_timing(blah2hip_clean_t h, int enable);
 int blah2hip_clean_get_timing(blah2hip_clean_t h, double *ms_total, uint32_t *launches);
+/* the same for the down-converter's kernels, on its handle */
+#define BLAH2HIP_DK_DDC 0  /* ddc_kernel */
+#define BLAH2HIP_DK_TAIL 1 /* ddc_tail_kernel */
+#define BLAH2HIP_DK_COUNT 2
+int blah2hip_ddc_set_timing(blah2hip_ddc_t h, int enable);
+int blah2hip_ddc_get_timing(blah2hip_ddc_t h, double *ms_total, uint32_t *launches);
 
 #ifdef __cplusplus
 }
