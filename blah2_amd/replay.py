@@ -55,9 +55,9 @@ pair) and returns a list of B result dicts.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import json
-import math
 import os
 import time
 import pickle
@@ -66,6 +66,8 @@ from concurrent.futures import ThreadPoolExecutor
 from typing import Callable, Iterator, List, Optional, Tuple
 
 import numpy as np
+
+from .chain_plan import _key, plan_chain
 
 BYTES_PER_SAMPLE = 8  # int16 I1 Q1 I2 Q2
 FC32_BYTES = 8  # one complex<float> of a USRP capture
@@ -671,15 +673,11 @@ class GpuChain:
     def __init__(self, cfg: dict, device: int = 0, batch: int = 1, want_map: bool = False, depth: int = 3,
                  reader_threads: int = 4, hit_copy: int = 4096, read_mode: str = "memmove", numa: bool = True,
                  layout: str = "rspduo", usrp_block: Optional[int] = None, detect: Optional[str] = None):
-        if detect not in (None, "device", "host"):
-            raise ValueError(f"detect {detect!r}: 'device' or 'host'")
-        self._detect_arg = detect
-        if layout not in ("rspduo", "usrp", "cs8"):
-            raise ValueError(f"layout {layout!r}: 'rspduo', 'usrp' or 'cs8'")
-        if layout == "usrp" and (usrp_block is None or int(usrp_block) <= 0):
-            raise ValueError("a USRP chain needs the capture's block length (usrp_block > 0)")
-        self.layout = layout
-        self.usrp_block = int(usrp_block) if layout == "usrp" else None
+        p = self.plan = plan_chain(cfg, layout, usrp_block, detect, batch)  # every refusal the dictionary alone decides
+        if read_mode not in ("memmove", "pread", "mapped"):
+            raise ValueError("read_mode: 'memmove', 'pread' or 'mapped'")
+        self.layout, self.usrp_block = p.layout, p.usrp_block
+        self.batch, self.depth, self.want_map = p.batch, max(2, int(depth)), bool(want_map)
         import torch
 
         import blah2_amd
@@ -692,273 +690,108 @@ class GpuChain:
         # own, is not narrowed to the last GPU's node).
         self._node_cpus = device_numa_cpus(torch, device) if numa else None
         self.numa_pinned = bool(self._node_cpus)
-        with self._on_node():
-            self._build(cfg, device, batch, want_map, depth, reader_threads, hit_copy, read_mode)
+        self._handles = []  # (handle, whether close() closes it) in the order made: _own
+        try:
+            with self._on_node():
+                self._make_handles(cfg, device)
+                self._make_streams(device, hit_copy, read_mode)
+                self._make_slots()
+        except BaseException:  # whatever was made so far, last first (the integrator before its ambiguity handle)
+            for h, _ in reversed(self._handles):
+                h.close()
+            raise
+        # the threads last: nothing above leaves one running when it fails
+        self.reader_threads = max(1, reader_threads)
+        self.pool = ThreadPoolExecutor(max_workers=self.reader_threads, initializer=self._pin_worker)
+        self._bg = ThreadPoolExecutor(max_workers=1, initializer=self._pin_worker)  # starts and awaits a batch's read while the main thread works on another
 
-    def _pin_worker(self):
-        if self._node_cpus:
-            try:
-                os.sched_setaffinity(0, self._node_cpus)  # the calling thread only
-            except OSError:
-                pass
+    def _own(self, handle, on_close=True):
+        """Registers a handle the moment it exists; ``on_close``: :meth:`close` closes it (``amb`` and ``wh`` outlive that)."""
+        self._handles.append((handle, on_close))
+        return handle
 
-    def _on_node(self):
-        """The calling thread on the GPU's node for the length of a ``with`` block (pinned allocations), then back."""
-        chain = self
-
-        class _Ctx:
-            def __enter__(self):
-                self.prev = None
-                if chain._node_cpus:
-                    try:
-                        self.prev = os.sched_getaffinity(0)
-                        os.sched_setaffinity(0, chain._node_cpus)
-                    except OSError:
-                        self.prev = None
-
-            def __exit__(self, *exc):
-                if self.prev is not None:
-                    os.sched_setaffinity(0, self.prev)
-                return False
-        return _Ctx()
-
-    def _build(self, cfg, device, batch, want_map, depth, reader_threads, hit_copy, read_mode):
-        torch, blah2_amd = self.torch, self.b2
-        amb_c, det_c, clu_c = cfg["ambiguity"], cfg.get("detection", {}), cfg.get("clutter", {})
-        # ddc: {offset: HZ, decimation: D, taps: T, cutoff: 0.8, beta: 8}: one carrier of a wideband capture mixed to zero,
-        # low-passed and decimated on the device in front of everything (None: no such stage).  The reader cuts CPIs of
-        # n_in samples at fs_in; the chain behind the down-converter runs at fs_in / D on n_in / D samples.
-        self.fs_in, self.n_in = int(cfg["fs"]), int(cfg["n_samples"])
-        self.ddc, self.ddc_cfg, self.ddc_planes = None, None, None
-        dd = cfg.get("ddc")
-        dd = None if dd is False else dd
-        ddc_D = 1
-        if dd is not None:
+    def _make_handles(self, cfg, device):
+        """The plan as handles and detector objects, in the chain's order.  What only a handle can refuse: ValueError, naming the key."""
+        p, b2, B = self.plan, self.b2, self.batch
+        amb_c, det_c, clu_c = cfg["ambiguity"], cfg.get("detection") or {}, cfg.get("clutter") or {}
+        self.fs_in, self.n_in, self.fs, self.n = p.fs_in, p.n_in, p.fs, p.n
+        self.ddc_cfg, self.clean_cfg, self.clutter_blocks = p.ddc, p.clean, p.clutter["blocks"]
+        self.taper = b2.doppler_taper_f32(*p.taper) if p.taper else None  # the Doppler taper's taps (None: no taper stage)
+        self.amb = amb = self._own(b2.Ambiguity(amb_c["delayMin"], amb_c["delayMax"], amb_c["dopplerMin"], amb_c["dopplerMax"],
+                                                self.fs, self.n, True, device=device, max_batch=B), False)
+        nD, nC = amb.get_n_doppler_bins(), amb.get_n_delay_bins()
+        self.rates, self.migrate = p.rates, p.migrate_fc is not None
+        if p.rates is not None:
             try:
-                if not isinstance(dd, dict) or dd.get("offset") is None or dd.get("decimation") is None:
-                    raise ValueError("{offset: HZ, decimation: D, taps: T, cutoff: 0.8, beta: 8} with an offset and a decimation")
-                if isinstance(dd["decimation"], bool) or int(dd["decimation"]) != dd["decimation"]:
-                    raise ValueError("decimation is not a whole number")
-                ddc_D = int(dd["decimation"])
-                if not 1 <= ddc_D <= blah2_amd._lib.MAX_DDC_DECIM:
-                    raise ValueError(f"decimation outside [1, {blah2_amd._lib.MAX_DDC_DECIM}]")
-                taps_ = dd.get("taps")
-                dc = {"offset": float(dd["offset"]), "decimation": ddc_D,
-                      "taps": int(taps_) if taps_ is not None else min(16 * ddc_D, blah2_amd._lib.MAX_DDC_TAPS),
-                      "cutoff": float(dd.get("cutoff", 0.8) if dd.get("cutoff") is not None else 0.8),
-                      "beta": float(dd.get("beta", 8.0) if dd.get("beta") is not None else 8.0)}
-                if not math.isfinite(dc["offset"]) or abs(dc["offset"]) > self.fs_in / 2:
-                    raise ValueError("offset not finite or beyond fs / 2")
-                if self.fs_in % ddc_D or self.n_in % ddc_D:
-                    raise ValueError(f"decimation {ddc_D} does not divide fs = {self.fs_in} and the CPI of {self.n_in} samples")
-                ddc_h = blah2_amd.ddc_design(ddc_D, dc["taps"], dc["cutoff"], dc["beta"])  # (refuses sizes, cutoff and beta outside their ranges)
-            except (TypeError, ValueError) as e:
-                raise ValueError(f"capture.ddc = {dd!r}: {e}") from None
-            self.ddc_cfg = dc
-        self.fs, self.n = self.fs_in // ddc_D, self.n_in // ddc_D
-        n, B = self.n, int(batch)
-        n_in = self.n_in
-        self.batch, self.depth, self.want_map = B, max(2, int(depth)), bool(want_map)
-        # ambiguity: {window: NAME[:norm]}: the Doppler taper's taps (None: no taper stage)
-        self.taper = None
-        win = str(amb_c.get("window") or "none").lower()
-        name, _, norm = win.partition(":")
-        if norm not in ("", "norm"):
-            raise ValueError(f"ambiguity.window {win!r}: NAME or NAME:norm")
-        if name != "none" or norm:
-            self.taper = blah2_amd.doppler_taper_f32(name, norm == "norm")  # (refuses an unknown name)
-        # ambiguity: {migration: {fc: HZ}}: range-migration compensation for that carrier (False: no such stage)
-        self.migrate = False
-        mig = amb_c.get("migration")
-        mig = None if mig is False else mig
-        if mig is not None:
-            fc = mig.get("fc") if isinstance(mig, dict) else None
-            if fc is None:
-                raise ValueError("ambiguity.migration needs the carrier frequency: {fc: HZ}")
-            fc = float(fc) + (self.ddc_cfg["offset"] if self.ddc_cfg else 0.0)  # (the down-converted carrier's own frequency)
-            if not math.isfinite(fc) or not fc > 0.0:
-                raise ValueError(f"ambiguity.migration: fc = {fc!r} is not a positive, finite frequency")
-        # ambiguity: {dopplerRate: QMAX | {max: QMAX, step: S}}: the bank -QMAX .. QMAX of Doppler rates (None: no such stage)
-        self.rates = None
-        rate = amb_c.get("dopplerRate")
-        rate = None if rate is False else rate
-        if rate is not None:
+                amb.set_rates(p.rates)
+            except b2.Blah2HipError as e:
+                raise ValueError(f"ambiguity.dopplerRate = {amb_c['dopplerRate']!r} on {nD} Doppler bins: {e}") from None
+        if p.migrate_fc is not None:
             try:
-                if isinstance(rate, bool):
-                    raise ValueError("QMAX or {max: QMAX, step: S}")
-                q_max, step = (rate.get("max"), rate.get("step", 1.0)) if isinstance(rate, dict) else (rate, 1.0)
-                if q_max is None:
-                    raise ValueError("{max: QMAX, step: S} needs max")
-                rates = blah2_amd.rate_bank(float(q_max), float(step))
-            except (TypeError, ValueError) as e:
-                raise ValueError(f"ambiguity.dopplerRate = {rate!r}: {e}") from None
-        self.amb = blah2_amd.Ambiguity(amb_c["delayMin"], amb_c["delayMax"], amb_c["dopplerMin"], amb_c["dopplerMax"],
-                                       self.fs, n, True, device=device, max_batch=B)
-        nD, nC = self.amb.get_n_doppler_bins(), self.amb.get_n_delay_bins()
-        if rate is not None:
-            try:
-                self.amb.set_rates(rates)
-            except blah2_amd.Blah2HipError as e:
-                self.amb.close()
-                raise ValueError(f"ambiguity.dopplerRate = {rate!r} on {nD} Doppler bins: {e}") from None
-            self.rates = rates
-        if mig is not None:
-            try:
-                self.amb.set_migration(self.amb.migration_table(fc))
-            except blah2_amd.Blah2HipError as e:
-                self.amb.close()
-                raise ValueError(f"ambiguity.migration at fc = {fc:g} Hz: {e}") from None
-            self.migrate = True
-        self.wh = None
-        self.fused_fir = False
-        # clutter: {blocks: K}: taps per block of n / K samples (the filter's history runs on across the blocks); a CPI
-        # has K flags then, and is skipped when any block's matrix is not positive definite
-        self.clutter_blocks = KB = int(clu_c.get("blocks", 1)) if clu_c.get("enable", False) else 1
-        if clu_c.get("enable", False):
-            self.wh = blah2_amd.WienerHopf(clu_c["delayMin"], clu_c["delayMax"], n, device=device, max_batch=B, blocks=KB)
+                amb.set_migration(amb.migration_table(p.migrate_fc))
+            except b2.Blah2HipError as e:
+                raise ValueError(f"ambiguity.migration at fc = {p.migrate_fc:g} Hz: {e}") from None
+        self.wh, self.fused_fir = None, False
+        if p.clutter["enable"]:
+            # a CPI has `blocks` flags, and is skipped when any block's matrix is not positive definite
+            self.wh = self._own(b2.WienerHopf(clu_c["delayMin"], clu_c["delayMax"], self.n, device=device, max_batch=B,
+                                              blocks=self.clutter_blocks), False)
             # the filter's FIR inside the range kernel where one 4096-point transform covers the geometry (range_fir_kernel):
             # the filtered channel never crosses HBM.  clutter: {fused: false} keeps the two-stage chain, and so do blocks
-            # (the fused kernel takes one tap set per CPI: fir_fusable gives that reason).
-            self.fused_fir = bool(clu_c.get("fused", True)) and self.amb.fir_fusable(self.wh, self._fmt_in()) is None
+            # (the fused kernel takes one tap set per CPI: fir_fusable gives that reason) and clean (it needs the plane).
+            self.fused_fir = p.clutter["fused"] and amb.fir_fusable(self.wh, p.fmt_in) is None
             if self.fused_fir:
-                self.amb.set_fir(self.wh)
-        self.cfar = self.centroid = self.interp = None
+                amb.set_fir(self.wh)
         if self.taper is not None and nD < 2 * (len(self.taper) - 1) + 1:
-            self.amb.close()
-            raise ValueError(f"ambiguity.window {win!r}: a stencil of {2 * len(self.taper) - 1} taps on {nD} Doppler bins")
-        self.nci = None
-        looks = {}
-        if cfg.get("integrate"):
-            int_c = cfg["integrate"]
-            W, H = int(int_c["window"]), int(int_c.get("hop") or 1)
-            self.nci = blah2_amd.MapIntegrator(self.amb, 1, W, H)  # (refuses a window outside [1, 16] or a hop of 0)
-            self._per_batch = False  # shard_check: every batch starts at count 0
-            self._g = 0              # CPIs the integrator has been handed since its last reset
-            self._ok_tail = []       # filter flags of the last W - 1 CPIs collected
+            raise ValueError(f"ambiguity.window {str(amb_c['window']).lower()!r}: a stencil of {2 * len(self.taper) - 1} taps "
+                             f"on {nD} Doppler bins")
+        self.nci, looks = None, {}
+        if p.integrate:
+            self.nci = self._own(b2.MapIntegrator(amb, 1, *p.integrate))  # (refuses a window outside [1, 16] or a hop of 0)
+            # shard_check: every batch starts at count 0; CPIs handed over since the last reset; filter flags of the last W - 1 CPIs
+            self._per_batch, self._g, self._ok_tail = False, 0, []
             looks = {"looks": self.nci.looks}
-            # integrate: {tracks: {fc: HZ, rate: QMAX | {max: QMAX, step: S}}}: the window sums along the walk between CPIs
-            # for the carrier fc, under the bank of Doppler drifts in rows per CPI (no rate: the bank {0}, the walk only)
-            trk = int_c.get("tracks")
-            if trk is not None and trk is not False:
+            if p.tracks:
                 try:
-                    if not isinstance(trk, dict) or trk.get("fc") is None:
-                        raise ValueError("needs the carrier frequency: {fc: HZ}")
-                    fc_t = float(trk["fc"]) + (self.ddc_cfg["offset"] if self.ddc_cfg else 0.0)
-                    if not math.isfinite(fc_t) or not fc_t > 0.0:
-                        raise ValueError(f"fc = {fc_t!r} is not a positive, finite frequency")
-                    rate_t = trk.get("rate")
-                    bank = None
-                    if rate_t is not None and rate_t is not False:
-                        if isinstance(rate_t, bool):
-                            raise ValueError("rate: QMAX or {max: QMAX, step: S}")
-                        q_max, step = (rate_t.get("max"), rate_t.get("step", 1.0)) if isinstance(rate_t, dict) else (rate_t, 1.0)
-                        if q_max is None:
-                            raise ValueError("rate: {max: QMAX, step: S} needs max")
-                        bank = blah2_amd.rate_bank(float(q_max), float(step))
-                    self.nci.set_tracks(blah2_amd.nci_walk_table(self.amb, fc_t), bank, max_cpi=B)
-                except (TypeError, ValueError, blah2_amd.Blah2HipError) as e:
-                    self.nci.close()
-                    self.amb.close()
-                    raise ValueError(f"integrate.tracks = {trk!r}: {e}") from None
+                    self.nci.set_tracks(b2.nci_walk_table(amb, p.tracks[0]), p.tracks[1], max_cpi=B)
+                except (ValueError, b2.Blah2HipError) as e:
+                    raise ValueError(f"integrate.tracks = {cfg['integrate']['tracks']!r}: {e}") from None
         self.nci_tracks = self.nci is not None and self.nci.n_rates > 0
-        # detection: {clutterMap: {memory: T, mode: gate | detect}}: every cell against its own history (None: no such stage)
-        self.cmap, self.cmap_mode = None, None
-        cm_c = det_c.get("clutterMap")
-        cm_c = None if cm_c is False else cm_c
-        if cm_c is not None:
-            try:
-                if not isinstance(cm_c, dict) or isinstance(cm_c.get("memory"), bool) or not isinstance(cm_c.get("memory"), int):
-                    raise ValueError("{memory: T, mode: gate | detect} with T a number of CPIs")
-                if not 1 <= cm_c["memory"] <= blah2_amd._lib.MAX_CMAP_MEMORY:
-                    raise ValueError(f"memory outside [1, {blah2_amd._lib.MAX_CMAP_MEMORY}]")
-                self.cmap_mode = str(cm_c.get("mode", "gate")).lower()
-                if self.cmap_mode not in ("gate", "detect"):
-                    raise ValueError(f"mode {self.cmap_mode!r}: 'gate' or 'detect'")
-                if not det_c.get("enable", False):
-                    raise ValueError("detection is not enabled")
-                if self.nci is not None:
-                    raise ValueError("integrate is configured, and the clutter map's thresholds are made for one look per cell")
-            except ValueError as e:
-                if self.nci is not None:
-                    self.nci.close()
-                self.amb.close()
-                raise ValueError(f"detection.clutterMap = {cm_c!r}: {e}") from None
-        if det_c.get("enable", False):
-            # detection: {cfar: ca | os, rank: 0.75}: the cell-averaging detector of the reference (default), or the
-            # ordered-statistic one at that rank on the same window; both leave the same hit lists
-            kind = str(det_c.get("cfar", "ca")).lower()
-            if kind not in ("ca", "os"):
-                raise ValueError(f"detection.cfar {kind!r}: 'ca' or 'os'")
-            # a cell of the rate bank's map is the strongest of K hypotheses, which multiplies the false-alarm rate by at
-            # most K: the thresholds are made for pfa / K (the union bound)
-            pfa = det_c["pfa"] if self.rates is None else det_c["pfa"] / len(self.rates)
-            if self.nci_tracks:  # ... and of the integrator's hypotheses along the tracks, likewise
-                pfa = pfa / self.nci.n_rates
-            if kind == "os":
-                self.cfar = blah2_amd.OsCfarDetector1D(pfa, det_c["nGuard"], det_c["nTrain"], det_c["minDelay"],
-                                                       det_c["minDoppler"], rank=float(det_c.get("rank", 0.75)), **looks)
-            else:
-                self.cfar = blah2_amd.CfarDetector1D(pfa, det_c["nGuard"], det_c["nTrain"], det_c["minDelay"],
-                                                     det_c["minDoppler"], **looks)
-            if cm_c is not None:
-                self.cmap = blah2_amd.ClutterMapDetector(self.amb, pfa, cm_c["memory"], det_c["minDelay"], det_c["minDoppler"])
-            if "nCentroid" in det_c:  # blah2.cpp:176-181
-                self.centroid = blah2_amd.Centroid(det_c["nCentroid"], det_c["nCentroid"], 1 / (n / self.fs))
-                self.interp = blah2_amd.Interpolate(True, True)
-        # where Centroid and Interpolate run (None: not configured)
-        self.detect = (self._detect_arg or "device") if self.centroid is not None else None
-        self.finisher = None
-        if self.detect == "device":
-            self.finisher = blah2_amd.DetectionFinisher(self.centroid.nDelay, self.centroid.nDoppler, self.centroid.resolutionDoppler,
-                                                        self.interp.doDelay, self.interp.doDoppler)
-        self.need_map = self.want_map or self.detect == "host"
+        self.cfar = self.cmap = self.cmap_mode = self.centroid = self.interp = self.finisher = self.clean = self.ddc = None
+        if p.cfar_kind:
+            args = (p.pfa, det_c["nGuard"], det_c["nTrain"], det_c["minDelay"], det_c["minDoppler"])
+            self.cfar = (b2.OsCfarDetector1D(*args, rank=p.rank, **looks) if p.cfar_kind == "os" else
+                         b2.CfarDetector1D(*args, **looks))  # both leave the same hit lists
+            if p.cmap:
+                self.cmap = self._own(b2.ClutterMapDetector(amb, p.pfa, p.cmap[0], det_c["minDelay"], det_c["minDoppler"]))
+                self.cmap_mode = p.cmap[1]
+            if p.centroid is not None:
+                self.centroid = b2.Centroid(p.centroid, p.centroid, 1 / (self.n / self.fs))
+                self.interp = b2.Interpolate(True, True)
+        self.detect = p.detect  # where Centroid and Interpolate run (None: not configured)
+        if p.detect == "device":
+            self.finisher = b2.DetectionFinisher(self.centroid.nDelay, self.centroid.nDoppler, self.centroid.resolutionDoppler,
+                                                 self.interp.doDelay, self.interp.doDoppler)
+        self.need_map = self.want_map or p.detect == "host"
+        self.cap = p.cap if p.cap is not None else min(nD * nC, 1 << 16)
+        try:
+            if p.clean:
+                key = f"detection.clean = {det_c['clean']!r}"
+                self.clean = self._own(b2.EchoCanceller(self.n, self.fs, amb_c["delayMin"], amb_c["delayMax"], device=device, max_batch=B))
+            if p.ddc:  # one carrier, the history carried from batch to batch
+                key = f"capture.ddc = {cfg['ddc']!r}"
+                self.ddc = self._own(b2.Channelizer(self.fs_in, p.ddc["decimation"], p.ddc["h"], [p.ddc["offset"]], self.n_in,
+                                                    max_rows=B, device=device))
+        except b2.Blah2HipError as e:
+            raise ValueError(f"{key}: {e}") from None
+
+    def _make_streams(self, device, hit_copy, read_mode):
+        """The two streams and what the slots share: the planes between the stages (the compute stream is in order)."""
+        torch, B, n, n_in = self.torch, self.batch, self.n, self.n_in
         dev = self.dev = torch.device("cuda", device)
-        self.cap = int(det_c.get("capacity", min(nD * nC, 1 << 16)))
-        # detection: {clean: {snr: dB, echoes: E, sideDelay: 1, sideDoppler: 0, loading: 1e-6}}: strong-echo cancellation
-        # on the samples and a second pass of everything from the ambiguity stage on (None: no such stage)
-        self.clean, self.clean_cfg = None, None
-        cl_c = det_c.get("clean")
-        cl_c = None if cl_c is False else cl_c
-        if cl_c is not None:
-            try:
-                if not isinstance(cl_c, dict) or isinstance(cl_c.get("snr"), bool) or not isinstance(cl_c.get("snr"), (int, float)):
-                    raise ValueError("{snr: dB, echoes: E, sideDelay: 1, sideDoppler: 0, loading: 1e-6} with snr a number of dB")
-                cc = {"snr": float(cl_c["snr"]), "echoes": int(cl_c.get("echoes", 4)), "sideDelay": int(cl_c.get("sideDelay", 1)),
-                      "sideDoppler": int(cl_c.get("sideDoppler", 0)), "loading": float(cl_c.get("loading", 1e-6))}
-                if not math.isfinite(cc["snr"]):
-                    raise ValueError("snr is not finite")
-                if not 1 <= cc["echoes"] <= blah2_amd._lib.MAX_ATOMS:
-                    raise ValueError(f"echoes outside [1, {blah2_amd._lib.MAX_ATOMS}]")
-                if not 0 <= cc["sideDelay"] <= 2 or not 0 <= cc["sideDoppler"] <= 1:
-                    raise ValueError("sideDelay outside [0, 2] or sideDoppler outside [0, 1]")
-                if not math.isfinite(cc["loading"]) or cc["loading"] < 0:
-                    raise ValueError("loading must be finite and not negative")
-                if self.finisher is None:
-                    raise ValueError("it reads the final detection lists on the device: detection with nCentroid, and not --detect host")
-                if self.nci is not None:
-                    raise ValueError("integrate is configured: the integrator's window would see every CPI twice")
-                if self.cmap is not None:
-                    raise ValueError("clutterMap is configured: its history would absorb every CPI twice")
-                if self.wh is None and self.layout != "usrp" and self.ddc_cfg is None:
-                    raise ValueError("the surveillance channel is not an fp32 plane at that point: it takes a C32 (USRP) "
-                                     "capture, the down-converter or an enabled clutter filter, whose output is one")
-                self.clean = blah2_amd.EchoCanceller(n, self.fs, amb_c["delayMin"], amb_c["delayMax"], device=device, max_batch=B)
-            except (ValueError, blah2_amd.Blah2HipError) as e:
-                for h_ in (self.nci, self.cmap, self.wh):
-                    if h_ is not None:
-                        h_.close()
-                self.amb.close()
-                raise ValueError(f"detection.clean = {cl_c!r}: {e}") from None
-            self.clean_cfg = cc
-            if self.fused_fir:  # the filtered channel has to exist as a plane: the two-stage chain
-                self.amb.set_fir(None)
-                self.fused_fir = False
         self.hit_copy = min(self.cap, int(hit_copy))
         self.compute = torch.cuda.Stream(device=dev)
         self.copy = torch.cuda.Stream(device=dev)
-        self.pool = ThreadPoolExecutor(max_workers=max(1, reader_threads), initializer=self._pin_worker)
-        self._bg = ThreadPoolExecutor(max_workers=1, initializer=self._pin_worker)  # starts and awaits a batch's read while the main thread works on another
-        self.reader_threads = max(1, reader_threads)
         # How a batch gets from the page cache to the copy engine (tools/gpu_hostreg.py, tools/replay_bench.py; MI355X host):
         #   "memmove"  reader threads copy out of the file's shared mapping into a pinned ring (page tables filled by madvise
         #              first): 17-19 GB/s per thread on the GPU's NUMA node (12.5 across sockets), FOUR threads keep the link
@@ -970,91 +803,103 @@ class GpuChain:
         #              with the page-table fill of a first pass), so a replay that touches every page once gets 0.60 of the
         #              link from one thread and less from more.  For captures replayed repeatedly out of a mapping that stays
         #              (warm page tables) it reaches 0.94 of it with one thread.
-        if read_mode not in ("memmove", "pread", "mapped"):
-            raise ValueError("read_mode: 'memmove', 'pread' or 'mapped'")
-        self.read_mode = read_mode
         self._hip = _hip_runtime(torch) if read_mode == "mapped" else None
-        if read_mode == "mapped" and self._hip is None:
-            self.read_mode = "memmove"
-        # the filtered surveillance channel (one buffer: the compute stream is in order)
+        self.read_mode = "memmove" if read_mode == "mapped" and self._hip is None else read_mode
+        # the filtered surveillance channel
         self.yf = torch.empty((B, n), dtype=torch.complex64, device=dev) if self.wh is not None and not self.fused_fir else None
         # USRP: a batch's raw bytes are whole block pairs, at most B*n*16 + 32*block of them (a CPI run that starts and ends
         # mid-block); the de-blocked x and y planes are one pair for all slots, like yf
         self.raw_bytes = (-(-(B * n_in * 2 * FC32_BYTES + 4 * self.usrp_block * FC32_BYTES) // 16) * 16 if self.layout == "usrp" else
                           2 * B * n_in * CS8_BYTES if self.layout == "cs8" else None)  # cs8: the x bytes, then the y bytes
         self.planes = torch.empty((2, B, n_in), dtype=torch.complex64, device=dev) if self.layout == "usrp" else None
-        # the down-converter: one carrier, the history carried from batch to batch; its output planes are one pair for all
-        # slots, like yf
-        if self.ddc_cfg is not None:
-            try:
-                self.ddc = blah2_amd.Channelizer(self.fs_in, ddc_D, ddc_h, [self.ddc_cfg["offset"]], n_in, max_rows=B, device=device)
-            except blah2_amd.Blah2HipError as e:
-                raise ValueError(f"capture.ddc = {dd!r}: {e}") from None
-            self.ddc_planes = torch.empty((2, B, n), dtype=torch.complex64, device=dev)
+        # ... and so are the down-converter's output planes
+        self.ddc_planes = torch.empty((2, B, n), dtype=torch.complex64, device=dev) if self.ddc is not None else None
         self.busy_ms, self.batches_done = 0.0, 0  # kernels' time on the compute stream / batches collected, since construction
+
+    def _make_slots(self):
+        """The ring.  Each configured stage declares its device buffers, and with them the pinned host copies that come back:
+        ``slot["down"]`` lists (host key, device key, records per row or None for all, rows per CPI or 0 for one per map) in
+        the order ``_submit`` downloads them.  ``maps``, ``mets``, ``hits`` and ``cnt`` name the buffers that the stages behind
+        the ambiguity stage, and the downloads, read: ``_submit`` points them at the last stage's."""
+        torch, dev, B, cap, hc = self.torch, self.dev, self.batch, self.cap, self.hit_copy
+        shape, A = (B, self.amb.get_n_doppler_bins(), self.amb.get_n_delay_bins()), self.b2._lib.MAX_ATOMS
+        i32, f64, c64 = torch.int32, torch.float64, torch.complex64
         self.slots = []
-        on_dev = self.finisher is not None
         for _ in range(self.depth):
             s = {
                 "h_iq": None,  # pinned staging batch of the pread path, allocated when that path first runs
                 "h_ends": torch.empty(4 * PAGE, dtype=torch.uint8).pin_memory(),  # the ragged ends of a mapped batch's (one or two) runs
                 "registered": [],
-                "d_iq": torch.empty((B, n_in, 4), dtype=torch.int16, device=dev) if self.layout == "rspduo" else
+                "d_iq": torch.empty((B, self.n_in, 4), dtype=torch.int16, device=dev) if self.layout == "rspduo" else
                         torch.empty(self.raw_bytes, dtype=torch.uint8, device=dev),
                 "first": 0,  # the batch's first sample inside its raw bytes (UsrpFile.extent)
-                "d_met": torch.zeros((B, 2), dtype=torch.float64, device=dev),
-                "d_ok": torch.ones(B * KB, dtype=torch.int32, device=dev),
-                "d_hits": torch.zeros((B, self.cap, 2), dtype=torch.float64, device=dev),  # blah2hip_hit_t records, 16 bytes
-                "d_cnt": torch.zeros(B, dtype=torch.int32, device=dev),
-                "d_map": torch.zeros((B, nD, nC), dtype=torch.complex64, device=dev),
-                "h_met": torch.zeros((B, 2), dtype=torch.float64).pin_memory(),
-                "h_ok": torch.ones(B * KB, dtype=torch.int32).pin_memory(),
-                "h_hits": None if on_dev else torch.zeros((B, self.hit_copy, 2), dtype=torch.float64).pin_memory(),
-                # detect="device": blah2hip_det_t records, 32 bytes, as many as the hit list may hold (Centroid only drops)
-                "d_dets": torch.zeros((B, self.cap, 4), dtype=torch.float64, device=dev) if on_dev else None,
-                "d_dcnt": torch.zeros(B, dtype=torch.int32, device=dev) if on_dev else None,
-                "h_dets": torch.zeros((B, self.hit_copy, 4), dtype=torch.float64).pin_memory() if on_dev else None,
-                "h_dcnt": torch.zeros(B, dtype=torch.int32).pin_memory() if on_dev else None,
-                "h_cnt": torch.zeros(B, dtype=torch.int32).pin_memory(),
-                "h_map": torch.zeros((B, nD, nC), dtype=torch.complex64).pin_memory() if self.need_map else None,
+                "h_hits": None, "h_map": None, "down": [],
                 "uploaded": torch.cuda.Event(), "downloaded": torch.cuda.Event(),
                 # the two ends of the batch's kernels on the (in-order) compute stream, timed: their sum over a replay is the
                 # time the GPU spent computing (`busy_ms`), the rest of the wall clock it waited for the host link
                 "started": torch.cuda.Event(enable_timing=True), "computed": torch.cuda.Event(enable_timing=True),
             }
+
+            def stage(bufs, *down, **names):
+                s.update({k: torch.zeros(sh, dtype=dt, device=dev) for k, (sh, dt) in bufs.items()})
+                s.update({name: s[k] for name, k in names.items()})
+                for h, d, cols, per in down:
+                    shape_h = s[d].shape if cols is None else (B, cols) + s[d].shape[2:]
+                    s[h] = torch.zeros(shape_h, dtype=s[d].dtype).pin_memory()
+                    s["down"].append((h, d, cols, per))
+
+            stage({"d_map": (shape, c64), "d_met": ((B, 2), f64)}, ("h_met", "mets", None, 0), maps="d_map", mets="d_met")
+            if self.wh is not None:  # the filter's flags, one per block
+                stage({"d_ok": ((B * self.clutter_blocks,), i32)}, ("h_ok", "d_ok", None, self.clutter_blocks))
+                s["d_ok"].fill_(1)
             if self.taper is not None:  # the tapered maps and their metrics: what everything behind the ambiguity stage reads
-                s["d_tmap"] = torch.zeros((B, nD, nC), dtype=torch.complex64, device=dev)
-                s["d_tmet"] = torch.zeros((B, 2), dtype=torch.float64, device=dev)
+                stage({"d_tmap": (shape, c64), "d_tmet": ((B, 2), f64)})
             if self.nci is not None:  # the integrated maps and their metrics: what the detector and the download read
-                s["d_imap"] = torch.zeros((B, nD, nC), dtype=torch.complex64, device=dev)
-                s["d_imet"] = torch.zeros((B, 2), dtype=torch.float64, device=dev)
+                stage({"d_imap": (shape, c64), "d_imet": ((B, 2), f64)})
                 s["nci"] = (0, 0, 0)  # (count before the batch, windows that end in it, count at which the first ends)
-            if self.cmap is not None and self.cmap_mode == "gate":  # the exceed planes, the gated list, the detector's own counts
-                s["d_exc"] = torch.zeros((B, nD, nC), dtype=torch.uint8, device=dev)
-                s["d_ghits"] = torch.zeros((B, self.cap, 2), dtype=torch.float64, device=dev)
-                s["d_gcnt"] = torch.zeros(B, dtype=torch.int32, device=dev)
-                s["h_rcnt"] = torch.zeros(B, dtype=torch.int32).pin_memory()
-            if self.clean is not None:  # pass 1's final list, the atoms made of it, the fit; what _collect merges
-                A = blah2_amd._lib.MAX_ATOMS
-                s["d_dets1"] = torch.zeros((B, self.cap, 4), dtype=torch.float64, device=dev)
-                s["d_dcnt1"] = torch.zeros(B, dtype=torch.int32, device=dev)
-                s["d_atoms"] = torch.zeros((B, A, 2), dtype=torch.float64, device=dev)  # blah2hip_atom_t records, 16 bytes
-                s["d_acnt"] = torch.zeros(B, dtype=torch.int32, device=dev)
-                s["d_used"] = torch.zeros((B, A), dtype=torch.int32, device=dev)
-                s["d_amp"] = torch.zeros((B, A, 2), dtype=torch.float64, device=dev)
-                s["d_cok"] = torch.zeros(B, dtype=torch.int32, device=dev)
-                s["h_dets1"] = torch.zeros((B, self.hit_copy, 4), dtype=torch.float64).pin_memory()
-                s["h_dcnt1"] = torch.zeros(B, dtype=torch.int32).pin_memory()
-                s["h_used"] = torch.zeros((B, A), dtype=torch.int32).pin_memory()
-                s["h_cok"] = torch.zeros(B, dtype=torch.int32).pin_memory()
-            s["hits"], s["cnt"] = s["d_hits"], s["d_cnt"]  # the list the finisher and the downloads read
+            if self.cfar is not None:  # blah2hip_hit_t records, 16 bytes; the count also for the capacity check
+                stage({"d_hits": ((B, cap, 2), f64), "d_cnt": ((B,), i32)}, ("h_cnt", "cnt", None, 0),
+                      hits="d_hits", cnt="d_cnt")  # the list the finisher and the downloads read
+            if self.cmap_mode == "gate":  # the exceed planes, the gated list; the gated count never passes the capacity: the check needs the detector's own
+                stage({"d_exc": (shape, torch.uint8), "d_ghits": ((B, cap, 2), f64), "d_gcnt": ((B,), i32)}, ("h_rcnt", "d_cnt", None, 0))
+            if self.finisher is not None:  # blah2hip_det_t records, 32 bytes, as many as the hit list may hold (Centroid only drops)
+                stage({"d_dets": ((B, cap, 4), f64), "d_dcnt": ((B,), i32)}, ("h_dcnt", "d_dcnt", None, 0), ("h_dets", "d_dets", hc, 0))
+            elif self.cfar is not None:  # detect="host", or no nCentroid: the first hit_copy hits
+                stage({}, ("h_hits", "hits", hc, 0))
+            if self.clean is not None:  # pass 1's final list, the atoms (blah2hip_atom_t, 16 bytes) made of it, the fit; what _collect merges
+                stage({"d_dets1": ((B, cap, 4), f64), "d_dcnt1": ((B,), i32), "d_atoms": ((B, A, 2), f64), "d_acnt": ((B,), i32),
+                       "d_used": ((B, A), i32), "d_amp": ((B, A, 2), f64), "d_cok": ((B,), i32)},
+                      ("h_dcnt1", "d_dcnt1", None, 0), ("h_dets1", "d_dets1", hc, 0), ("h_used", "d_used", None, 0), ("h_cok", "d_cok", None, 0))
+            if self.need_map:
+                stage({}, ("h_map", "maps", None, 0))
             self.slots.append(s)
 
+    def _pin_worker(self):
+        if self._node_cpus:
+            try:
+                os.sched_setaffinity(0, self._node_cpus)  # the calling thread only
+            except OSError:
+                pass
+
+    @contextlib.contextmanager
+    def _on_node(self):
+        """The calling thread on the GPU's node for the length of a ``with`` block (pinned allocations), then back."""
+        prev = None
+        if self._node_cpus:
+            try:
+                prev = os.sched_getaffinity(0)
+                os.sched_setaffinity(0, self._node_cpus)
+            except OSError:
+                prev = None
+        try:
+            yield
+        finally:
+            if prev is not None:
+                os.sched_setaffinity(0, prev)
+
     def _fmt_in(self):
-        """The format the filter and the range kernel read: the .rspduo words, the int8 planes, or the de-blocked USRP planes."""
-        if self.ddc_cfg is not None:  # ... or the down-converter's planes
-            return self.b2.FMT_C32
-        return {"rspduo": self.b2.FMT_I16, "cs8": self.b2.FMT_I8}.get(self.layout, self.b2.FMT_C32)
+        """The format the filter and the range kernel read: .rspduo words, int8 planes, or the de-blocked or down-converted planes."""
+        return self.plan.fmt_in
 
     def _host_batch(self):
         """The pinned staging batch of the copying read paths."""
@@ -1196,10 +1041,11 @@ class GpuChain:
                         self.finisher.process_dev(amb, n_maps, slot["hits"].data_ptr(), self.cap, slot["cnt"].data_ptr(),
                                                   dets.data_ptr(), self.cap, dcnt.data_ptr(),
                                                   maps.data_ptr(), mets.data_ptr(), st)
-                return n_maps, maps, mets
+                slot["maps"], slot["mets"] = maps, mets
+                return n_maps
 
             if self.clean is None:
-                n_maps, maps, mets = behind(slot["d_dets"], slot["d_dcnt"])
+                n_maps = behind(slot.get("d_dets"), slot.get("d_dcnt"))  # (None without a device finisher)
             else:
                 # pass 1, its strongest detections as atoms, their replicas fitted to and taken out of the surveillance plane
                 # (in place: the plane is this batch's alone on the in-order stream), then everything again: pass 2
@@ -1212,111 +1058,90 @@ class GpuChain:
                 self.clean.process_dev(fy, x, py, cnt, n, slot["d_atoms"].data_ptr(), A, slot["d_acnt"].data_ptr(), cc["loading"],
                                        slot["d_amp"].data_ptr(), slot["d_cok"].data_ptr(), py, n, st)
                 amb.process_dev(fy, x, py, cnt, n, slot["d_map"].data_ptr(), slot["d_met"].data_ptr(), st)
-                n_maps, maps, mets = behind(slot["d_dets"], slot["d_dcnt"])
+                n_maps = behind(slot["d_dets"], slot["d_dcnt"])
             slot["computed"].record(self.compute)
         with torch.cuda.stream(self.copy):
             self.copy.wait_event(slot["computed"])
-            slot["h_met"][:n_maps].copy_(mets[:n_maps], non_blocking=True)
-            if self.wh is not None:
-                nok = cnt * self.clutter_blocks
-                slot["h_ok"][:nok].copy_(slot["d_ok"][:nok], non_blocking=True)
-            if self.cfar is not None:
-                slot["h_cnt"][:n_maps].copy_(slot["cnt"][:n_maps], non_blocking=True)  # (device path: for the capacity check)
-                if self.cmap_mode == "gate":  # the gated count never passes the capacity: the check needs the detector's own
-                    slot["h_rcnt"][:n_maps].copy_(slot["d_cnt"][:n_maps], non_blocking=True)
-                if self.finisher is not None:
-                    slot["h_dcnt"][:n_maps].copy_(slot["d_dcnt"][:n_maps], non_blocking=True)
-                    slot["h_dets"][:n_maps].copy_(slot["d_dets"][:n_maps, :self.hit_copy], non_blocking=True)
-                    if self.clean is not None:
-                        slot["h_dcnt1"][:n_maps].copy_(slot["d_dcnt1"][:n_maps], non_blocking=True)
-                        slot["h_dets1"][:n_maps].copy_(slot["d_dets1"][:n_maps, :self.hit_copy], non_blocking=True)
-                        slot["h_used"][:n_maps].copy_(slot["d_used"][:n_maps], non_blocking=True)
-                        slot["h_cok"][:n_maps].copy_(slot["d_cok"][:n_maps], non_blocking=True)
-                else:
-                    slot["h_hits"][:n_maps].copy_(slot["hits"][:n_maps, :self.hit_copy], non_blocking=True)
-            if self.need_map:
-                slot["h_map"][:n_maps].copy_(maps[:n_maps], non_blocking=True)
+            for h, d, cols, per in slot["down"]:  # every configured stage's pairs, as _make_slots declared them
+                rows = cnt * per if per else n_maps
+                slot[h][:rows].copy_(slot[d][:rows] if cols is None else slot[d][:rows, :cols], non_blocking=True)
             slot["downloaded"].record(self.copy)
 
-    def _collect(self, slot: dict, k0: int, cnt: int) -> List[dict]:
+    def _windows(self, slot: dict, ok_h, cnt: int):
+        """The integrator's bookkeeping for one batch: ({c: at}, {c: skipped}) -- CPI c of the batch has a result where a
+        window ends at it, the window's map is number ``at`` of the slot's buffers, and the window is skipped when the filter
+        failed on any of its CPIs (the flags of the last W - 1 CPIs are kept for the next batch)."""
+        g0, n_out, first = slot["nci"]
+        W, H = self.nci.window, self.nci.hop
+        if self._per_batch:
+            self._ok_tail = []
+        flags = self._ok_tail + [bool(v) for v in ok_h]  # flags[-cnt + c] is CPI c's
+        at_of = {first - g0 + i * H: i for i in range(n_out)}
+        skip_of = {c: not all(flags[len(flags) - cnt + c - W + 1:len(flags) - cnt + c + 1]) for c in at_of}
+        self._ok_tail = flags[len(flags) - (W - 1):] if W > 1 else []
+        return at_of, skip_of
+
+    def _detections(self, slot: dict, b: int, r: dict):
+        """The detections of map ``b`` of the slot into its record ``r``: the device finisher's list (merged with pass 1's
+        behind CLEAN), or the hit list finished on the host."""
         b2, amb = self.b2, self.amb
+        k = int(slot["h_cnt"][b])
+        k_raw = int(slot["h_rcnt"][b]) if self.cmap_mode == "gate" else k
+        if k_raw > self.cap:
+            raise b2.Blah2HipError(b2._lib.ERR_CAPACITY, f"{k_raw} detections in one CPI, capacity {self.cap}")
+        if self.finisher is None:
+            if k > self.hit_copy:  # rare: more hits than the pipelined copy carries -- fetch this CPI's records now
+                recs = slot["hits"][b, :k].cpu().numpy()
+            else:
+                recs = slot["h_hits"][b, :max(k, 1)].numpy()
+            det = b2.hits_to_detection(amb, recs.view(b2.HIT_DTYPE).reshape(-1), k, self.cap)
+            if self.centroid is not None:
+                det = self.centroid.process(det)
+                m = b2.Map(amb, slot["h_map"][b].numpy(), amb.delay, amb.doppler, r["noisePower"], r["maxPower"], b)
+                det = self.interp.process(det, m)
+            r.update(delay=det.get_delay().tolist(), doppler=det.get_doppler().tolist(), snr=det.get_snr().tolist())
+            return
+
+        def final(dets, dcnt):  # the final records, made on the device: sorted into emission order, no library call
+            kd = int(slot["h_" + dcnt][b])
+            if kd > self.cap:
+                raise b2.Blah2HipError(b2._lib.ERR_CAPACITY, f"{kd} detections in one CPI, capacity {self.cap}")
+            if kd > self.hit_copy:  # rare: beyond what the pipelined copy carries
+                return slot["d_" + dets][b, :kd].cpu().numpy().view(b2.DET_DTYPE).reshape(-1), kd
+            return slot["h_" + dets][b, :max(kd, 1)].numpy().view(b2.DET_DTYPE).reshape(-1), kd
+
+        det = b2.dets_to_detection(*final("dets", "dcnt"), self.cap)
+        if self.clean is None:
+            r.update(delay=det.delay.tolist(), doppler=det.doppler.tolist(), snr=det.snr.tolist())
+            return
+        # the cancelled echoes from pass 1, then pass 2's list less their residuals
+        first, k1 = final("dets1", "dcnt1")
+        used = [int(u) for u in slot["h_used"][b].numpy() if u >= 0] if int(slot["h_cok"][b]) else []
+        second = np.zeros(len(det.delay), dtype=b2.DET_DTYPE)
+        second["delay"], second["doppler"], second["snr"] = det.delay, det.doppler, det.snr
+        m = b2.merge_clean_detections(first[:k1], used, second, self.clean_cfg["sideDelay"], amb.dims.cpi)
+        r.update(delay=m["delay"].tolist(), doppler=m["doppler"].tolist(), snr=m["snr"].tolist(), cancelled=len(used))
+
+    def _collect(self, slot: dict, k0: int, cnt: int) -> List[dict]:
         slot["downloaded"].synchronize()
         self.busy_ms += slot["started"].elapsed_time(slot["computed"])
         self.batches_done += 1
         met_h = slot["h_met"].numpy()
         ok_h = (slot["h_ok"].numpy()[:cnt * self.clutter_blocks].reshape(cnt, self.clutter_blocks).all(axis=1)
                 if self.wh is not None else np.ones(cnt, dtype=bool))
+        at_of, skip_of = (self._windows(slot, ok_h, cnt) if self.nci is not None else
+                          ({c: c for c in range(cnt)}, {c: not ok_h[c] for c in range(cnt)}))
         res = []
-        # integrating: CPI c of the batch has a result where a window ends at it, the window's map is number `at` of the
-        # slot's buffers, and the window is skipped when the filter failed on any of its CPIs
-        at_of = skip_of = None
-        if self.nci is not None:
-            g0, n_out, first = slot["nci"]
-            W, H = self.nci.window, self.nci.hop
-            if self._per_batch:
-                self._ok_tail = []
-            flags = self._ok_tail + [bool(v) for v in ok_h]  # flags[-cnt + c] is CPI c's
-            at_of = {first - g0 + i * H: i for i in range(n_out)}
-            skip_of = {c: not all(flags[len(flags) - cnt + c - W + 1:len(flags) - cnt + c + 1]) for c in at_of}
-            self._ok_tail = flags[len(flags) - (W - 1):] if W > 1 else []
         for c in range(cnt):
-            b = c
-            if at_of is not None:
-                if c not in at_of:
-                    res.append({"integrating": True, "cpi": k0 + c})
-                    continue
-                if skip_of[c]:
-                    res.append({"skipped": True, "cpi": k0 + c})
-                    continue
-                b = at_of[c]
-            elif not ok_h[b]:
-                res.append({"skipped": True, "cpi": k0 + b})
+            if c not in at_of or skip_of[c]:
+                res.append({"integrating" if c not in at_of else "skipped": True, "cpi": k0 + c})
                 continue
+            b = at_of[c]
             r = {"noisePower": float(met_h[b, 0]), "maxPower": float(met_h[b, 1]), "cpi": k0 + c}
-            if at_of is not None:
+            if self.nci is not None:
                 r["window"] = self.nci.window
             if self.cfar is not None:
-                k = int(slot["h_cnt"][b])
-                k_raw = int(slot["h_rcnt"][b]) if self.cmap_mode == "gate" else k
-                if k_raw > self.cap:
-                    raise b2.Blah2HipError(b2._lib.ERR_CAPACITY, f"{k_raw} detections in one CPI, capacity {self.cap}")
-                if self.finisher is not None:  # the final records, made on the device: sorted into emission order, no library call
-                    kd = int(slot["h_dcnt"][b])
-                    if kd > self.hit_copy:  # rare: beyond what the pipelined copy carries
-                        recs = slot["d_dets"][b, :kd].cpu().numpy()
-                    else:
-                        recs = slot["h_dets"][b, :max(kd, 1)].numpy()
-                    det = b2.dets_to_detection(recs.view(b2.DET_DTYPE).reshape(-1), kd, self.cap)
-                    if self.clean is not None:  # the cancelled echoes from pass 1, then pass 2's list less their residuals
-                        k1 = int(slot["h_dcnt1"][b])
-                        if k1 > self.cap:
-                            raise b2.Blah2HipError(b2._lib.ERR_CAPACITY, f"{k1} detections in one CPI, capacity {self.cap}")
-                        rec1 = (slot["d_dets1"][b, :k1].cpu().numpy() if k1 > self.hit_copy else slot["h_dets1"][b, :max(k1, 1)].numpy())
-                        first = rec1.view(b2.DET_DTYPE).reshape(-1)[:k1]
-                        used = [int(u) for u in slot["h_used"][b].numpy() if u >= 0] if int(slot["h_cok"][b]) else []
-                        second = np.zeros(len(det.delay), dtype=b2.DET_DTYPE)
-                        second["delay"], second["doppler"], second["snr"] = det.delay, det.doppler, det.snr
-                        m = b2.merge_clean_detections(first, used, second, self.clean_cfg["sideDelay"], amb.dims.cpi)
-                        r.update(delay=m["delay"].tolist(), doppler=m["doppler"].tolist(), snr=m["snr"].tolist(), cancelled=len(used))
-                        if self.want_map:
-                            r["map"] = slot["h_map"][b].numpy().copy()
-                        res.append(r)
-                        continue
-                    r.update(delay=det.delay.tolist(), doppler=det.doppler.tolist(), snr=det.snr.tolist())
-                    if self.want_map:
-                        r["map"] = slot["h_map"][b].numpy().copy()
-                    res.append(r)
-                    continue
-                if k > self.hit_copy:  # rare: more hits than the pipelined copy carries -- fetch this CPI's records now
-                    recs = slot["hits"][b, :k].cpu().numpy()
-                else:
-                    recs = slot["h_hits"][b, :max(k, 1)].numpy()
-                det = b2.hits_to_detection(amb, recs.view(b2.HIT_DTYPE).reshape(-1), k, self.cap)
-                if self.centroid is not None:
-                    det = self.centroid.process(det)
-                    m = b2.Map(amb, slot["h_map"][b].numpy(), amb.delay, amb.doppler, r["noisePower"], r["maxPower"], b)
-                    det = self.interp.process(det, m)
-                r.update(delay=det.get_delay().tolist(), doppler=det.get_doppler().tolist(), snr=det.get_snr().tolist())
+                self._detections(slot, b, r)
             if self.want_map:
                 r["map"] = slot["h_map"][b].numpy().copy()
             res.append(r)
@@ -1397,12 +1222,10 @@ class GpuChain:
         its batch: an integrating chain then needs windows that do not overlap and do not cross a batch's end (hop ==
         window, batch a multiple of the window), and starts every batch at count 0.  ValueError otherwise.  A clutter map
         needs every CPI in order, whatever the batch: more than one rank is a ValueError."""
-        if self.cmap is not None and world > 1:
-            raise ValueError(f"detection.clutterMap over {world} ranks: the batches go round-robin, so no rank sees the "
-                             "consecutive CPIs a cell's history is made of")
-        if self.ddc is not None and world > 1:
-            raise ValueError(f"capture.ddc over {world} ranks: the batches go round-robin, so no rank sees the "
-                             "consecutive CPIs the filter's history is made of")
+        if self.plan.needs_order and world > 1:
+            key, whose = ("detection.clutterMap", "a cell's") if self.cmap is not None else ("capture.ddc", "the filter's")
+            raise ValueError(f"{key} over {world} ranks: the batches go round-robin, so no rank sees the "
+                             f"consecutive CPIs {whose} history is made of")
         if self.nci is None or world <= 1:
             return
         W, H = self.nci.window, self.nci.hop
@@ -1421,14 +1244,9 @@ class GpuChain:
         self._bg.shutdown(wait=True)
         self.pool.shutdown(wait=True)
         self.release_all()
-        if self.nci is not None:
-            self.nci.close()
-        if self.cmap is not None:
-            self.cmap.close()
-        if getattr(self, "clean", None) is not None:
-            self.clean.close()
-        if getattr(self, "ddc", None) is not None:
-            self.ddc.close()
+        for h, on_close in self._handles:
+            if on_close:
+                h.close()
 
 
 def gpu_processor(cfg: dict, device: int = 0, batch: int = 1, want_map: bool = False, **kw) -> GpuChain:
@@ -1569,52 +1387,41 @@ def main(argv=None):
     cfg = dict(y["process"], fs=fs, n_samples=n)
     if y["capture"].get("ddc"):
         cfg["ddc"] = dict(y["capture"]["ddc"])
-    if a.ddc is not None:
+
+    def parsed(flag, form, names, convs, at_least=1, **defaults):
+        """A flag's ``A:B:...`` as the dictionary its config key holds.  Syntax only: plan_chain below weighs the values."""
+        parts = getattr(a, flag).split(":")
         try:
-            parts_ = a.ddc.split(":")
-            if not 2 <= len(parts_) <= 5:
+            if not at_least <= len(parts) <= len(names):
                 raise ValueError
-            cfg["ddc"] = {"offset": float(parts_[0]), "decimation": int(parts_[1])}
-            for key_, conv_, val_ in zip(("taps", "cutoff", "beta"), (int, float, float), parts_[2:]):
-                cfg["ddc"][key_] = conv_(val_)
+            return dict(defaults, **{k: conv(v) for k, conv, v in zip(names, convs, parts)})
         except ValueError:
-            ap.error("--ddc takes OFFSET_HZ:DECIM[:TAPS[:CUTOFF[:BETA]]]")
-    if cfg.get("ddc") and int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        ap.error("--ddc / capture.ddc needs the CPIs in order: one rank")
+            ap.error(f"--{flag.replace('_', '-')} takes {form}")
+
+    def det_(**kw):
+        return dict(cfg.get("detection") or {}, **kw)
+
+    if a.ddc is not None:
+        cfg["ddc"] = parsed("ddc", "OFFSET_HZ:DECIM[:TAPS[:CUTOFF[:BETA]]]", ("offset", "decimation", "taps", "cutoff", "beta"),
+                            (float, int, int, float, float), 2)
     if a.clutter_blocks is not None:
         if a.clutter_blocks < 1:
             ap.error("--clutter-blocks takes a block count >= 1")
         cfg["clutter"] = dict(cfg.get("clutter") or {}, blocks=a.clutter_blocks)
     if a.integrate is not None:
-        try:
-            wh_ = [int(v) for v in a.integrate.split(":")]
-            if not 1 <= len(wh_) <= 2 or min(wh_) < 1:
-                raise ValueError
-        except ValueError:
+        cfg["integrate"] = parsed("integrate", "W or W:H, a window and a hop in CPIs", ("window", "hop"), (int, int), hop=1)
+        if min(cfg["integrate"].values()) < 1:
             ap.error("--integrate takes W or W:H, a window and a hop in CPIs, both >= 1")
-        cfg["integrate"] = {"window": wh_[0], "hop": wh_[1] if len(wh_) == 2 else 1}
     if a.integrate_tracks is not None:
         if not cfg.get("integrate"):
             ap.error("--integrate-tracks belongs to --integrate W[:H]")
-        trk_ = {"fc": (cfg["integrate"].get("tracks") or {}).get("fc", y["capture"].get("fc"))}
+        trk_ = {"fc": (_key(cfg["integrate"], "tracks") or {}).get("fc", y["capture"].get("fc"))}
         if trk_["fc"] is None:
             ap.error("--integrate-tracks needs a carrier: capture.fc in the config")
         if a.integrate_tracks is not True:
-            try:
-                qs_ = [float(v) for v in a.integrate_tracks.split(":")]
-                if not 1 <= len(qs_) <= 2:
-                    raise ValueError
-                from .process import rate_bank
-                rate_bank(*qs_)
-            except ValueError:
-                ap.error("--integrate-tracks takes QMAX or QMAX:STEP, QMAX >= 0 and STEP > 0 in Doppler rows per CPI, at most 16 hypotheses")
-            trk_["rate"] = {"max": qs_[0], "step": qs_[1] if len(qs_) == 2 else 1.0}
+            trk_["rate"] = parsed("integrate_tracks", "QMAX or QMAX:STEP in Doppler rows per CPI", ("max", "step"), (float, float), step=1.0)
         cfg["integrate"] = dict(cfg["integrate"], tracks=trk_)
     if a.doppler_window is not None:
-        from .process import TAPER_COEFFS
-        name_, _, norm_ = a.doppler_window.lower().partition(":")
-        if name_ not in TAPER_COEFFS or norm_ not in ("", "norm"):
-            ap.error(f"--doppler-window takes NAME or NAME:norm, NAME one of {', '.join(TAPER_COEFFS)}")
         cfg["ambiguity"] = dict(cfg["ambiguity"], window=a.doppler_window.lower())
     # process.ambiguity.migration: true, or --migration [FC_HZ]: the chain's {"fc": HZ}, the carrier from capture.fc by default
     mig_ = a.migration if a.migration is not None else cfg["ambiguity"].get("migration")
@@ -1622,27 +1429,17 @@ def main(argv=None):
         fc_ = mig_.get("fc") if isinstance(mig_, dict) else None if mig_ is True else mig_
         if fc_ is None:
             fc_ = y["capture"].get("fc")
-        try:
-            fc_ = float(fc_) if fc_ is not None else None
-        except (TypeError, ValueError):
-            ap.error("--migration takes a carrier frequency in Hz")
         if fc_ is None:
             ap.error("range-migration compensation needs a carrier: --migration FC_HZ, or capture.fc in the config")
-        if not math.isfinite(fc_) or not fc_ > 0.0:
-            ap.error("the carrier frequency of --migration / capture.fc must be positive and finite")
-        cfg["ambiguity"] = dict(cfg["ambiguity"], migration={"fc": fc_})
+        try:
+            cfg["ambiguity"] = dict(cfg["ambiguity"], migration={"fc": float(fc_)})
+        except (TypeError, ValueError):
+            ap.error("--migration takes a carrier frequency in Hz")
     elif "migration" in cfg["ambiguity"]:
         cfg["ambiguity"] = {k: v for k, v in cfg["ambiguity"].items() if k != "migration"}
     if a.doppler_rate is not None:
-        try:
-            qs_ = [float(v) for v in a.doppler_rate.split(":")]
-            if not 1 <= len(qs_) <= 2:
-                raise ValueError
-            from .process import rate_bank
-            rate_bank(*qs_)
-        except ValueError:
-            ap.error("--doppler-rate takes QMAX or QMAX:STEP, QMAX >= 0 and STEP > 0 in Doppler bins, at most 16 hypotheses")
-        cfg["ambiguity"] = dict(cfg["ambiguity"], dopplerRate={"max": qs_[0], "step": qs_[1] if len(qs_) == 2 else 1.0})
+        cfg["ambiguity"] = dict(cfg["ambiguity"], dopplerRate=parsed("doppler_rate", "QMAX or QMAX:STEP in Doppler bins",
+                                                                     ("max", "step"), (float, float), step=1.0))
     if a.cfar is not None:
         kind, _, rank_ = a.cfar.partition(":")
         try:
@@ -1650,36 +1447,19 @@ def main(argv=None):
                 raise ValueError
         except ValueError:
             ap.error("--cfar takes ca, os or os:RANK with RANK in [0.001, 1]")
-        cfg["detection"] = dict(cfg.get("detection") or {}, cfar=kind)
-        if rank_:
-            cfg["detection"]["rank"] = float(rank_)
+        cfg["detection"] = det_(cfar=kind, **({"rank": float(rank_)} if rank_ else {}))
     if a.clutter_map is not None:
-        mem_, sep_, mode_ = a.clutter_map.partition(":")
-        try:
-            if not 1 <= int(mem_) <= 64 or (sep_ and mode_ not in ("gate", "detect")):
-                raise ValueError
-        except ValueError:
-            ap.error("--clutter-map takes T or T:detect (T:gate is the default), T a memory of 1 .. 64 CPIs")
-        if cfg.get("integrate"):
-            ap.error("--clutter-map does not go with integration: its thresholds are made for one look per cell")
-        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-            ap.error("--clutter-map needs the CPIs in order: one rank")
-        cfg["detection"] = dict(cfg.get("detection") or {}, clutterMap={"memory": int(mem_), "mode": mode_ or "gate"})
+        cfg["detection"] = det_(clutterMap=parsed("clutter_map", "T or T:detect (T:gate is the default), T a memory of 1 .. 64 CPIs",
+                                                  ("memory", "mode"), (int, str), mode="gate"))
     if a.clean is not None:
-        snr_, sep_, ech_ = a.clean.partition(":")
-        try:
-            snr_ = float(snr_)
-            ech_ = int(ech_) if sep_ else 4
-            if not math.isfinite(snr_) or not 1 <= ech_ <= 32:
-                raise ValueError
-        except ValueError:
-            ap.error("--clean takes SNR_DB or SNR_DB:MAX_ECHOES, a threshold in dB and 1 .. 32 echoes")
-        if cfg.get("integrate"):
-            ap.error("--clean does not go with --integrate: the integrator's window would see every CPI twice")
-        if (cfg.get("detection") or {}).get("clutterMap"):
-            ap.error("--clean does not go with --clutter-map: its history would absorb every CPI twice")
-        cfg["detection"] = dict(cfg.get("detection") or {},
-                                clean=dict((cfg.get("detection") or {}).get("clean") or {}, snr=snr_, echoes=ech_))
+        cfg["detection"] = det_(clean=dict(_key(cfg.get("detection"), "clean") or {}, **parsed(
+            "clean", "SNR_DB or SNR_DB:MAX_ECHOES, a threshold in dB and 1 .. 32 echoes", ("snr", "echoes"), (float, int), echoes=4)))
+    try:  # everything the dictionary alone decides, before a process group or a device is touched
+        plan = plan_chain(cfg, layout, a.usrp_block, a.detect, a.batch)
+    except ValueError as e:
+        ap.error(str(e))
+    if plan.needs_order and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        ap.error("--ddc / capture.ddc and --clutter-map / detection.clutterMap need the CPIs in order: one rank")
     dist = None
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
