@@ -86,10 +86,11 @@ def _build_hip_locked(force, verbose):
     # (a library that came with the tree and has no stamp beside it was built by this script with the default flags)
     if not force and not _newer(LIB, deps) and (same_flags or (not os.path.exists(stamp) and not extra_flags())):
         return LIB
-    # one hipcc per translation unit (every csrc/*.hip), side by side, then one link (8 CPUs, the ten units at once: capi.hip,
-    # the longest, is done 84-89 s after the start, clutter.hip after 72-82 s, array.hip after 32-43 s, the others --
-    # integrate.hip with its sixteen windows, taper.hip with its five stencils and walk.hip among them -- within 12 s;
-    # clean.hip, the eleventh, compiles alone in 3 s, ddc.hip, the twelfth, in 6 s)
+    # one hipcc per translation unit (every csrc/*.hip), side by side, then one link (8 CPUs, the thirteen units at once:
+    # capi.hip, the longest, is done 49 s after the start, clutter.hip after 42 s, array.hip after 26 s, integrate.hip with
+    # its sixteen windows after 18 s, clutter_solve.hip after 9 s, the eight others within 9 s.  clutter_solve.hip holds every
+    # instantiation of the clutter filter's Toeplitz solve, split out of clutter.hip: alone it compiles in 6 s and clutter.hip
+    # without it in 44-46 s, where the one unit took 46 s -- the correlation and FIR kernels are that unit's compile time)
     procs = []
     try:
         for src in srcs:

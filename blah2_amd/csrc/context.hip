@@ -156,7 +156,7 @@ int blah2hip_stream_read_dev(const void *d_src, size_t bytes, void *d_sink, void
 }
 
 // ------------------------------------------------------- internal hooks --
-// every unit reports errors here (fail() in amb_handle.hpp; clutter.hip, spectrum.hip and capture.hip call it directly)
+// every unit reports errors here (fail() in amb_handle.hpp, CFAIL / CHIP in clutter_handle.hpp; spectrum.hip and capture.hip call it directly)
 void blah2hip_set_error_(const char *msg) { g_err = msg ? msg : ""; }
 
 hipError_t blah2hip_ensure_lds_(const void *kern, int bytes)

@@ -212,7 +212,7 @@ template <int SIGN, int J> B2_HD cf twid32(cf a) { return twid_k<SIGN>(a, w32_c(
 // between dependent packed instructions costs an s_nop from the compiler's hazard recogniser (see cmul).
 // One-wave range kernel -4.6 %, workgroup range kernel -1 % (measured).  The grouped form holds two
 // more registers per group while it runs; a translation unit whose kernels sit at the register cap
-// (clutter.hip: the correlation kernels) defines B2_SPLIT_BUTTERFLIES to keep one statement per add.
+// (clutter.hip: the correlation kernels of clutter_kernels.hpp) defines B2_SPLIT_BUTTERFLIES to keep one statement per add.
 #define B2_SUB " neg_lo:[0,1] neg_hi:[0,1]"
 #define B2_AMI " op_sel:[0,1] op_sel_hi:[1,0] neg_hi:[0,1]" /* a + (-i) b */
 #define B2_API " op_sel:[0,1] op_sel_hi:[1,0] neg_lo:[0,1]" /* a + (+i) b */

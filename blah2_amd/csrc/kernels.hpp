@@ -11,7 +11,8 @@
 //   metrics_kernel                 Map::set_metrics                   Map.cpp:187-206
 //   (the detector kernels live in cfar_kernels.hpp)
 //   rotate_kernel                  Doppler-centre shift               Ambiguity.cpp:95-102
-// The clutter filter and the spectrum analyser live in clutter.hip / spectrum.hip.
+// The clutter filter lives in clutter.hip and clutter_solve.hip (kernels: clutter_kernels.hpp, clutter_solve_kernels.hpp),
+// the spectrum analyser in spectrum.hip.
 //
 // All paths are relative to /root/reference/src.
 #pragma once

@@ -1,5 +1,6 @@
 // Hermitian Toeplitz solve of the clutter filter's normal equations on SEVERAL workgroups per CPI
-// (WienerHopf.cpp:85-122: A = toeplitz(r), chol(A), two triangular solves) -- included by clutter.hip.
+// (WienerHopf.cpp:85-122: A = toeplitz(r), chol(A), two triangular solves) -- included by clutter_solve_kernels.hpp, behind
+// clutter_solve_kernel and its helpers.
 //
 // clutter_solve_kernel (the round-2 form) runs the Schur/Levinson recursion one order at a time in ONE workgroup:
 // nBins dependent orders with a workgroup barrier each (1.7 ms at 2047 taps whatever the batch).  Here the same

@@ -7,7 +7,7 @@ xs the shifted reference as oracle.blah2_oracle.wiener_hopf forms it (the uint32
 
 Used by tests/test_corr_crafted_model.py (CPU: fp64 models of both kernel forms, the mutants) and
 tests/test_corr_crafted_gpu.py.  Here: the geometries, the restatement of the plan and of the two segment walks
-(seg_walk / half.per of csrc/clutter.hip), the census, its exact references (the oracle, and a direct sum over impulse pairs)
+(seg_walk / half.per of csrc/clutter_kernels.hpp), the census, its exact references (the oracle, and a direct sum over impulse pairs)
 and the device planes.  No GPU is touched at import.
 
 The census.  A `place` is an EARLIER sample n (an index of xs).  A full place plants xs at n, n + 1, n + nBins - 1 and every
@@ -70,7 +70,7 @@ BATCH_GEOM = Geom("half1024_33taps_batch64", "half", 1024, 33, -7, 99 * 512 + 7,
 CENSUS_GRID = {BATCH_GEOM.name: 32}
 
 
-# ---- the plan and the walks, restated (csrc/clutter.hip: clutter_plan, clutter_grids, seg_walk, corr_args) -----------------
+# ---- the plan and the walks, restated (csrc/clutter.hip: clutter_plan, clutter_grids, corr_args; clutter_kernels.hpp: seg_walk)
 def up8(v):
     return max(8, (v + 7) & ~7)
 
@@ -122,7 +122,7 @@ def walks_of(g, grid):
 
 
 def xs_indices(N, dmin, off_by_one=False):
-    """xs_index / xs_map of csrc/clutter.hip: xs[i] = x[j[i]], without a division.  off_by_one: the mutant whose branch
+    """xs_index / xs_map of csrc/clutter_kernels.hpp: xs[i] = x[j[i]], without a division.  off_by_one: the mutant whose branch
     changes at thresh + 1."""
     thresh = max(dmin, 0)
     wrap_c = ((1 << 32) - thresh) % N

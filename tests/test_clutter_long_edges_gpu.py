@@ -30,7 +30,7 @@ from test_long_filter_model import xs_of
 
 pytestmark = pytest.mark.gpu
 
-LONG_C = 2048  # csrc/clutter.hip
+LONG_C = 2048  # csrc/clutter_kernels.hpp
 
 
 @pytest.fixture(scope="module")

@@ -1,4 +1,4 @@
-"""GPU: clutter filters of more than 4081 taps (csrc/clutter.hip, "LONG filters"; WienerHopf.cpp:58-163 takes any nBins).
+"""GPU: clutter filters of more than 4081 taps (csrc/clutter_kernels.hpp, "LONG filters"; WienerHopf.cpp:58-163 takes any nBins).
 
 One on-chip transform holds 4081 taps.  Beyond, the engine runs the same kernels chunk by chunk of 2048 lags / taps on
 rotated and shifted copies of the channels and solves the normal equations in one workgroup on vectors in global memory.

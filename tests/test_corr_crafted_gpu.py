@@ -1,4 +1,4 @@
-"""GPU: the clutter filter's FFT correlations (clutter_corr_kernel, clutter_corr_half_kernel, csrc/clutter.hip) on the pair
+"""GPU: the clutter filter's FFT correlations (clutter_corr_kernel, clutter_corr_half_kernel, csrc/clutter_kernels.hpp) on the pair
 census of tests/corr_crafted.py with the correlation grid forced (WienerHopf.set_corr_grid), against r and b of the fp64
 oracle (the normal equations of oracle.blah2_oracle.wiener_hopf).
 

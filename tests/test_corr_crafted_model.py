@@ -1,6 +1,6 @@
 """CPU: what the correlation census of tests/corr_crafted.py can see.
 
-fp64 NumPy models of the two decompositions as the kernels do them (csrc/clutter.hip):
+fp64 NumPy models of the two decompositions as the kernels do them (csrc/clutter_kernels.hpp):
 
   windowed     per segment g of seg_len samples the transform of x' (the window [g S, g S + F) of xs, cut to the segment and
                to the CPI) against the transforms of the whole windows of xs and of every y_c (wrapWin's indices), the

@@ -2,7 +2,7 @@
 """Prototype (NumPy, fp64) of a LOOK-AHEAD form of the Toeplitz solve of the clutter filter -- preparation for a
 multi-CU kernel; not part of the product, nothing imports it.
 
-The device kernel (csrc/clutter.hip: clutter_solve_kernel) runs the Levinson recursion with its inner products replaced
+The device kernel (csrc/clutter_solve_kernels.hpp: clutter_solve_kernel) runs the Levinson recursion with its inner products replaced
 by Schur-type residual recursions: per order m ONE reflection coefficient ef_m and ONE gain dt_m are formed from the
 leading elements, then every index is updated element-wise -- 2047 orders, one workgroup barrier each, 1.6 ms on one CU.
 An order's update of the residual pair (A, C) and of the predictor pair (F, B) is the same 2 x 2 map with a shift,
