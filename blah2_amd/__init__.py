@@ -18,6 +18,7 @@ from .process import integrate_tracks, nci_walk_table, track_tables  # noqa: F40
 from .process import ClutterMapDetector, clutter_map, clutter_map_alpha, clutter_map_alpha_table, clutter_map_pfa, clutter_map_weights, gate_hits  # noqa: F401
 from .process import ATOM_DTYPE, EchoCanceller, clean_atoms, clean_fit, clean_replicas, clean_subtract, merge_clean_detections  # noqa: F401
 from .process import Channelizer, ddc, ddc_design, ddc_taps  # noqa: F401
+from .process import carrier_ratios, carrier_table, fuse_carriers  # noqa: F401
 
 __all__ =["Ambiguity", "Centroid", "Interpolate", "CfarDetector1D", "CfarDetector2D", "Detection", "Map", "WienerHopf", "SpectrumAnalyser", "next_hamming", "Blah2HipError",
            "FMT_C32", "FMT_I16", "FMT_F16", "FMT_I16X_C32Y", "FMT_I8", "FMT_I8X_C32Y", "deblock_c32_dev", "device_count", "load",

@@ -75,6 +75,10 @@ INFO_RATE_GRID = 19
 MAX_RATES = 16
 INFO_TRACK_GRID, INFO_TRACK_MAX_SHIFT = 20, 21
 MAX_TRACK_SHIFT = 1048576
+INFO_CARRIER_GRID = 22
+MAX_CARRIERS = 8
+CARRIER_NEAREST, CARRIER_LINEAR = 0, 1
+CARRIER_INTERPS = {"nearest": CARRIER_NEAREST, "linear": CARRIER_LINEAR}
 MAX_CMAP_MEMORY = 64
 CMAP_NORMALISE = 1
 MAX_ATOMS = 32
@@ -168,6 +172,9 @@ SYMBOLS = {
     "blah2hip_doppler_rate": (C.c_int, [_vp, _dbl, _dbl, C.POINTER(_dbl)]),
     "blah2hip_amb_set_rates": (C.c_int, [_vp, _vp, _u32]),
     "blah2hip_amb_rate_bank_dev": (C.c_int, [_vp, _vp, _u32, _vp, _vp, _vp, _vp]),
+    "blah2hip_carrier_table": (C.c_int, [_vp, _vp, _u32, C.c_int, _vp, _vp, _vp, _vp]),
+    "blah2hip_amb_set_carriers": (C.c_int, [_vp, _vp, _u32, C.c_int]),
+    "blah2hip_amb_fuse_carriers_dev": (C.c_int, [_vp, _vp, _u32, _vp, _vp, _vp, _vp]),
     "blah2hip_cfar_alpha": (C.c_int, [_dbl, _u32, _u32, _vp]),
     "blah2hip_cfar1d_dev": (C.c_int, [_vp, _vp, _vp, _u32, _dbl, _i32, _i32, _i32, _dbl, _vp, _u32, _vp, _vp]),
     "blah2hip_cfar1d_prepare": (C.c_int, [_vp, _dbl, _i32]),

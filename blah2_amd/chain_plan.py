@@ -48,7 +48,7 @@ class ChainPlan:
     fs: int               # ... and the chain's behind the down-converter (the same without one)
     n: int
     fmt_in: int           # the format the filter and the range kernel read
-    ddc: Optional[dict]   # {offset, decimation, taps, cutoff, beta} with the defaults filled in, and "h": the designed low-pass
+    ddc: Optional[dict]   # {offset, decimation, taps, cutoff, beta} with the defaults filled in (offset: carrier 0's), and "h": the designed low-pass
     taper: Optional[tuple]     # (name, norm)
     migrate_fc: Optional[float]
     rates: Optional[np.ndarray]
@@ -64,27 +64,49 @@ class ChainPlan:
     clean: Optional[dict]       # {snr, echoes, sideDelay, sideDoppler, loading}
     needs_order: bool     # a stage with history from CPI to CPI whatever the batch: one rank only
     cap: Optional[int]    # detection.capacity; None: min(cells of the map, 65536), which the ambiguity handle knows
+    carriers: Optional[tuple] = None  # the offsets of several carriers summed on carrier 0's axis; None: one carrier, the chain above
+    carrier_interp: str = "nearest"   # capture.ddc.interp: how a carrier's rows are aligned (nearest | linear)
+    carrier_fc: Optional[float] = None  # capture.fc, with carriers: the ratios are (fc + offset_c) / (fc + offset_0)
 
 
-def _plan_ddc(dd, fs_in, n_in):
+def _plan_ddc(dd, fs_in, n_in, fc=None):
+    """(the down-converter's dictionary, the offsets of several carriers or None, the interpolation).  ``offset`` may be a
+    list: one entry is the scalar, several are carriers summed on the first one's axis, which need ``fc`` (capture.fc)."""
     # The reader cuts CPIs of n_in samples at fs_in; the chain behind the down-converter runs at fs_in / D on n_in / D.
     try:
         if not isinstance(dd, dict) or dd.get("offset") is None or dd.get("decimation") is None:
             raise ValueError("{offset: HZ, decimation: D, taps: T, cutoff: 0.8, beta: 8} with an offset and a decimation")
+        interp = str(dd["interp"]).lower() if dd.get("interp") is not None else "nearest"
+        if interp not in _lib.CARRIER_INTERPS:
+            raise ValueError(f"interp {interp!r}: 'nearest' or 'linear'")
+        carriers, first = None, dd["offset"]
+        if isinstance(first, (list, tuple)):
+            offs = [float(v) for v in first]
+            if not 1 <= len(offs) <= _lib.MAX_CARRIERS:
+                raise ValueError(f"{len(offs)} offsets: a list holds 1 .. {_lib.MAX_CARRIERS} carriers")
+            carriers, first = tuple(offs) if len(offs) > 1 else None, offs[0]
         if isinstance(dd["decimation"], bool) or int(dd["decimation"]) != dd["decimation"]:
             raise ValueError("decimation is not a whole number")
         D = int(dd["decimation"])
         if not 1 <= D <= _lib.MAX_DDC_DECIM:
             raise ValueError(f"decimation outside [1, {_lib.MAX_DDC_DECIM}]")
-        dc = {"offset": float(dd["offset"]), "decimation": D,
+        dc = {"offset": float(first), "decimation": D,
               "taps": int(dd["taps"]) if dd.get("taps") is not None else min(16 * D, _lib.MAX_DDC_TAPS),
               "cutoff": float(dd["cutoff"]) if dd.get("cutoff") is not None else 0.8,
               "beta": float(dd["beta"]) if dd.get("beta") is not None else 8.0}
-        if not math.isfinite(dc["offset"]) or abs(dc["offset"]) > fs_in / 2:
-            raise ValueError("offset not finite or beyond fs / 2")
+        for off in carriers or (dc["offset"],):
+            if not math.isfinite(off) or abs(off) > fs_in / 2:
+                raise ValueError("offset not finite or beyond fs / 2")
         if fs_in % D or n_in % D:
             raise ValueError(f"decimation {D} does not divide fs = {fs_in} and the CPI of {n_in} samples")
-        return dict(dc, h=ddc_design(D, dc["taps"], dc["cutoff"], dc["beta"]))  # (refuses sizes, cutoff and beta outside their ranges)
+        if carriers:
+            if len(set(carriers)) != len(carriers):
+                raise ValueError("two carriers at the same offset")
+            if fc is None or isinstance(fc, bool):
+                raise ValueError("several carriers need capture.fc, the capture's centre frequency: their Doppler axes scale with fc + offset")
+            for off in carriers:
+                _carrier(fc, off)  # (refuses an fc + offset that is not positive and finite)
+        return dict(dc, h=ddc_design(D, dc["taps"], dc["cutoff"], dc["beta"])), carriers, interp  # (refuses sizes, cutoff and beta outside their ranges)
     except (TypeError, ValueError) as e:
         raise ValueError(f"capture.ddc = {dd!r}: {e}") from None
 
@@ -132,7 +154,7 @@ def plan_chain(cfg: dict, layout: str = "rspduo", usrp_block: Optional[int] = No
     amb_c, det_c, clu_c = cfg["ambiguity"], cfg.get("detection") or {}, cfg.get("clutter") or {}
     fs_in, n_in = int(cfg["fs"]), int(cfg["n_samples"])
     dd = _key(cfg, "ddc")
-    ddc = _plan_ddc(dd, fs_in, n_in) if dd is not None else None
+    ddc, carriers, carrier_interp = _plan_ddc(dd, fs_in, n_in, cfg.get("fc")) if dd is not None else (None, None, "nearest")
     D, offset = (ddc["decimation"], ddc["offset"]) if ddc else (1, 0.0)
     # ambiguity: {window: NAME[:norm]}: the Doppler taper
     win = str(amb_c.get("window") or "none").lower()
@@ -207,6 +229,20 @@ def plan_chain(cfg: dict, layout: str = "rspduo", usrp_block: Optional[int] = No
     if cl_c is not None:
         clean = _plan_clean(cl_c, where == "device", integrate, cmap, on or layout == "usrp" or ddc is not None)
         clutter["fused"] = False  # the filtered channel has to exist as a plane: the two-stage chain
+    if carriers:
+        # several carriers: their maps are summed on carrier 0's axis (Ambiguity.fuse_carriers_dev) behind the taper
+        C_ = len(carriers)
+        looks = C_ * (integrate[0] if integrate else 1)
+        for bad, why in ((migrate_fc is not None, "ambiguity.migration is configured: its table is built for one carrier"),
+                         (rates is not None, "ambiguity.dopplerRate is configured: its bank is built for one carrier"),
+                         (tracks is not None, "integrate.tracks is configured: its tables are built for one carrier"),
+                         (cmap is not None, "detection.clutterMap is configured: its thresholds are made for one look per cell"),
+                         (clean is not None, "detection.clean is configured: it fits echoes to one carrier's samples"),
+                         (where == "host", "--detect host: the fused maps' detections are finished on the device"),
+                         (enabled and looks > _lib.MAX_CFAR_LOOKS, f"{looks} looks per cell ({C_} carriers x the integrator's "
+                                                                   f"window), above {_lib.MAX_CFAR_LOOKS}")):
+            if bad:
+                raise ValueError(f"capture.ddc = {dd!r}: {C_} carriers, and {why}")
     fmt_in = _lib.FMT_C32 if ddc else {"rspduo": _lib.FMT_I16, "cs8": _lib.FMT_I8}.get(layout, _lib.FMT_C32)
     return ChainPlan(layout=layout, usrp_block=int(usrp_block) if layout == "usrp" else None, batch=int(batch),
                      fs_in=fs_in, n_in=n_in, fs=fs_in // D, n=n_in // D, fmt_in=fmt_in, ddc=ddc,
@@ -214,4 +250,6 @@ def plan_chain(cfg: dict, layout: str = "rspduo", usrp_block: Optional[int] = No
                      clutter=clutter, integrate=integrate, tracks=tracks, cfar_kind=kind, rank=rank,
                      pfa=pfa, cmap=cmap, centroid=centroid, detect=where, clean=clean,
                      needs_order=cmap is not None or ddc is not None,
-                     cap=int(det_c["capacity"]) if "capacity" in det_c else None)
+                     cap=int(det_c["capacity"]) if "capacity" in det_c else None,
+                     carriers=carriers, carrier_interp=carrier_interp,
+                     carrier_fc=float(cfg["fc"]) if carriers else None)

@@ -1,7 +1,7 @@
 // Internal to the library: what the units behind include/blah2hip.h share.  The ambiguity handle, whose fields every
 // unit reads directly (no accessors), the error and launch-check helpers, and the few engine functions (capi.hip)
-// that another unit calls.  Host code only: capi.hip, array.hip, detect.hip, integrate.hip, taper.hip, walk.hip
-// and context.hip all include it.
+// that another unit calls.  Host code only: capi.hip, array.hip, detect.hip, integrate.hip, taper.hip, walk.hip,
+// carriers.hip and context.hip all include it.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -106,7 +106,8 @@ struct blah2hip_amb_s {
   int lastLeakLags = 0;             // BLAH2HIP_INFO_LEAK_LAGS: lags corrected by the last process call (0 = not applied)
   double lastLeakMax = 0.0;         // BLAH2HIP_INFO_LEAK_MAX_E12: the largest |g| of the calibration the last call ran under
 
-  // ---- written by detect.hip; bearingGridLast by array.hip, taperGridLast by taper.hip, the migration and rate fields by walk.hip
+  // ---- written by detect.hip; bearingGridLast by array.hip, taperGridLast by taper.hip, the migration and rate fields by walk.hip,
+  // the carrier fields by carriers.hip
   // a threshold table of detect.hip's cfar_table(); d: alpha[n + 1], then with a rank (permille) rank[n + 1] words; pinned:
   // handed out by *_prepare, never evicted.  Two lists, each with its own budget; destroy (capi.hip) frees both.
   struct CfarTable { double pfa; uint32_t looks, rank; size_t n; double *d; bool pinned; };
@@ -125,6 +126,9 @@ struct blah2hip_amb_s {
   cf *d_rates = nullptr;            // [BLAH2HIP_MAX_RATES][nD] chirps c_k[i] (blah2hip_amb_set_rates, walk.hip), allocated at its first use, freed by destroy
   uint32_t nRates = 0, zeroRates = 0; // ... hypotheses of the bank that is set (0 = none), and bit k: q[k] == 0
   int rateGridLast = 0;             // BLAH2HIP_INFO_RATE_GRID
+  void *d_carriers = nullptr;       // [BLAH2HIP_MAX_CARRIERS][nD] CarrierEntry (blah2hip_amb_set_carriers, carriers.hip), allocated at its first use, freed by destroy
+  uint32_t nCarriers = 0;           // ... carriers of the table that is set (0 = none)
+  int carrierGridLast = 0;          // BLAH2HIP_INFO_CARRIER_GRID
   int trackGridLast = 0, trackShiftLast = 0; // BLAH2HIP_INFO_TRACK_GRID / _TRACK_MAX_SHIFT (integrate.hip)
 
   // ---- every unit brackets its launches (tic / toc below)

@@ -1028,7 +1028,7 @@ int blah2hip_amb_destroy(blah2hip_amb_t h)
                   (void *)h->d_doppler, h->d_in, (void *)h->d_rot,
                   (void *)h->d_hits, (void *)h->d_count, (void *)h->d_sat, (void *)h->d_dtw, (void *)h->d_chirp,
                   (void *)h->d_bf, (void *)h->d_bfn, (void *)h->d_H, (void *)h->d_dopW64, (void *)h->d_hotCount, (void *)h->d_firK0,
-                  (void *)h->d_detWords, (void *)h->d_rangeWalk, (void *)h->d_migrate, (void *)h->d_rates})
+                  (void *)h->d_detWords, (void *)h->d_rangeWalk, (void *)h->d_migrate, (void *)h->d_rates, h->d_carriers})
     if (p) (void)hipFree(p);
   for (auto &t : h->alphaTables)
     if (t.d) (void)hipFree(t.d);
@@ -1190,6 +1190,7 @@ int blah2hip_amb_get_info(blah2hip_amb_t h, int key, int64_t *value)
   case BLAH2HIP_INFO_RATE_GRID: *value = h->rateGridLast; return BLAH2HIP_OK;
   case BLAH2HIP_INFO_TRACK_GRID: *value = h->trackGridLast; return BLAH2HIP_OK;
   case BLAH2HIP_INFO_TRACK_MAX_SHIFT: *value = h->trackShiftLast; return BLAH2HIP_OK;
+  case BLAH2HIP_INFO_CARRIER_GRID: *value = h->carrierGridLast; return BLAH2HIP_OK;
   case BLAH2HIP_INFO_LEAK_LAGS: *value = h->lastLeakLags; return BLAH2HIP_OK;
   case BLAH2HIP_INFO_LEAK_MAX_E12: *value = (int64_t)std::llround(h->lastLeakMax * 1e12); return BLAH2HIP_OK;
   case BLAH2HIP_INFO_HOT_COLUMNS: { // of the last call's first CPI; waits for the device

@@ -775,6 +775,90 @@ def integrate_tracks(maps, walk, q, w=None, window=1, hop=None):
     return levels, index, sums
 
 
+def carrier_ratios(fc, offsets):
+    """``ratio[c] = (fc + off_c) / (fc + off_0)`` for carriers at ``fc + off_c`` Hz: carrier 0 is the reference, whose
+    Doppler axis the fused maps keep."""
+    off = np.atleast_1d(np.asarray(offsets, dtype=np.float64))
+    f = float(fc) + off
+    if off.ndim != 1 or off.size < 1 or not np.all(np.isfinite(f)) or not np.all(f > 0.0):
+        raise ValueError("every carrier frequency fc + offset must be finite and positive")
+    return f / f[0]
+
+
+def _carrier_interp(interp):
+    if interp in _lib.CARRIER_INTERPS:
+        return _lib.CARRIER_INTERPS[interp]
+    if interp in (_lib.CARRIER_NEAREST, _lib.CARRIER_LINEAR) and not isinstance(interp, bool):
+        return int(interp)
+    raise ValueError(f"unknown carrier interpolation {interp!r} (nearest | linear)")
+
+
+def carrier_table(doppler_axis, ratio, interp="nearest"):
+    """``blah2hip_carrier_table`` restated in fp64 NumPy, its bits: for carrier ``c`` and output row ``j``
+    ``u = (ratio[c] doppler[j] - doppler[0]) / D`` (left to right, ``D`` the axis' mean step), snapped to ``rint(u)`` within
+    1e-9, clamped to ``[0, nD - 1]`` where the carrier does not cover the row.  ``interp``: ``"nearest"`` (``row =
+    floor(u + 0.5)``, weights 1, 0) or ``"linear"`` (``row = floor(u)``, ``a_hi = fp32(u - row)``, ``a_lo = fp32(1 - (u -
+    row))``).  Returns ``{"row": int32 [C, nD], "a_lo", "a_hi": float32 [C, nD], "covered": uint32 [nD]}``.  ValueError where
+    the library returns BLAH2HIP_ERR_INVALID: not 1 .. 8 carriers, a ratio that is not finite or outside [0.5, 2], an
+    unknown interpolation, fewer than two Doppler bins."""
+    mode = _carrier_interp(interp)
+    dop = np.asarray(doppler_axis, dtype=np.float64)
+    r = np.atleast_1d(np.asarray(ratio, dtype=np.float64))
+    if r.ndim != 1 or not 1 <= r.size <= _lib.MAX_CARRIERS:
+        raise ValueError("n_carriers outside [1, 8]")
+    if not np.all(np.isfinite(r)) or not np.all((r >= 0.5) & (r <= 2.0)):
+        raise ValueError("a ratio is not finite or lies outside [0.5, 2]")
+    if dop.ndim != 1 or dop.size < 2:
+        raise ValueError("fewer than two Doppler bins")
+    nD = dop.size
+    top = float(nD - 1)
+    delta = (dop[nD - 1] - dop[0]) / top
+    u = (r[:, None] * dop[None, :] - dop[0]) / delta
+    near = np.rint(u)
+    u = np.where(np.abs(u - near) <= 1e-9, near, u)
+    covered = ((u >= 0.0) & (u <= top)).sum(axis=0).astype(np.uint32)
+    u = np.minimum(np.maximum(u, 0.0), top)
+    if mode == _lib.CARRIER_NEAREST:
+        row = np.floor(u + 0.5)
+        a_lo, a_hi = np.ones(u.shape, dtype=np.float32), np.zeros(u.shape, dtype=np.float32)
+    else:
+        row = np.floor(u)
+        t = u - row
+        a_lo, a_hi = (1.0 - t).astype(np.float32), t.astype(np.float32)
+    return {"row": row.astype(np.int32), "a_lo": a_lo, "a_hi": a_hi, "covered": covered}
+
+
+def fuse_carriers(maps, table, w=None):
+    """blah2hip_amb_fuse_carriers_dev restated in fp64 NumPy.  ``maps``: complex ``[C, n_cpi, nD, nC]``, ``table``:
+    :func:`carrier_table`'s (or the library's own, :meth:`Ambiguity.carrier_table`) with its fp32 ``a_lo``, ``a_hi`` as
+    stored, ``w``: the ``C`` carrier weights (None: all 1).  ``S = sum_c w_c (a_lo |M_c[row]|^2 + a_hi |M_c[row + 1]|^2)``,
+    the second term only where ``a_hi != 0``, and ``sqrt(scale S)`` with ``scale = 1 / sum_c w_c`` rounded to fp32 as the
+    library rounds it.  Returns float64 ``[n_cpi, nD, nC]``: the real parts of the output maps (the imaginary parts are
+    zero)."""
+    m = np.asarray(maps).astype(np.complex128)
+    if m.ndim != 4:
+        raise ValueError("maps must be [C, n_cpi, nD, nC]")
+    C_, _, nD, _ = m.shape
+    row = np.asarray(table["row"])
+    a_lo, a_hi = np.asarray(table["a_lo"], dtype=np.float32), np.asarray(table["a_hi"], dtype=np.float32)
+    if row.shape != (C_, nD) or a_lo.shape != (C_, nD) or a_hi.shape != (C_, nD):
+        raise ValueError("the table must hold one entry per (carrier, Doppler row) of the maps")
+    wc = np.ones(C_, dtype=np.float32) if w is None else np.asarray(w, dtype=np.float32)
+    if wc.shape != (C_,):
+        raise ValueError("w must hold one weight per carrier")
+    scale = float(np.float32(1.0 / wc.astype(np.float64).sum()))
+    with np.errstate(all="ignore"):
+        S = np.zeros(m.shape[1:])
+        for c in range(C_):
+            p = m[c].real ** 2 + m[c].imag ** 2
+            q = a_lo[c].astype(np.float64)[None, :, None] * p[:, row[c], :]
+            hi = np.nonzero(a_hi[c] != 0)[0]  # where a_hi == 0 row + 1 is not read: a NaN there stays out
+            if hi.size:
+                q[:, hi, :] = q[:, hi, :] + a_hi[c, hi].astype(np.float64)[None, :, None] * p[:, row[c, hi] + 1, :]
+            S = S + float(wc[c]) * q
+        return np.sqrt(scale * S)
+
+
 # a_0 .. a_P of the cosine-sum windows w[i] = sum_p (-1)^p a_p cos(2 pi p i / n): blah2hip_doppler_taper's table
 TAPER_COEFFS = {
     "none": (1.0,),
@@ -1447,6 +1531,44 @@ class Ambiguity:
         ``d_out_map`` the same pointer or a disjoint ``[n_maps][nD][nDelay]`` complex64 buffer, ``d_out_metrics``
         ``[n_maps][2]`` float64.  Enqueues only."""
         check(self._L.blah2hip_amb_migrate_dev(self._h, d_map, n_maps, d_out_map, d_out_metrics, stream))
+
+    def carrier_table(self, ratio, interp="nearest"):
+        """blah2hip_carrier_table: the library's own table that aligns carriers of ``ratio[c] = fc_c / fc_ref`` with this
+        handle's Doppler axis, as :func:`carrier_table` returns it."""
+        r = np.ascontiguousarray(np.atleast_1d(ratio), dtype=np.float64)
+        if r.ndim != 1:
+            raise ValueError("ratio is a list of carrier ratios")
+        shape = (r.size, self.dims.n_doppler_bins)
+        row, a_lo, a_hi = np.zeros(shape, dtype=np.int32), np.zeros(shape, dtype=np.float32), np.zeros(shape, dtype=np.float32)
+        covered = np.zeros(shape[1], dtype=np.uint32)
+        check(self._L.blah2hip_carrier_table(self._h, _ptr(r), r.size, _carrier_interp(interp), _ptr(row), _ptr(a_lo), _ptr(a_hi),
+                                             _ptr(covered)))
+        return {"row": row, "a_lo": a_lo, "a_hi": a_hi, "covered": covered}
+
+    def set_carriers(self, ratio, interp="nearest"):
+        """The carrier ratios (at most 8, each in [0.5, 2]) whose table :meth:`fuse_carriers_dev` sums along
+        (blah2hip_amb_set_carriers; waits for the device); None or an empty list clears it."""
+        if ratio is None or np.size(ratio) == 0:
+            check(self._L.blah2hip_amb_set_carriers(self._h, None, 0, 0))
+            return
+        r = np.ascontiguousarray(np.atleast_1d(ratio), dtype=np.float64)
+        if r.ndim != 1:
+            raise ValueError("ratio is a list of carrier ratios")
+        check(self._L.blah2hip_amb_set_carriers(self._h, _ptr(r), r.size, _carrier_interp(interp)))
+        self._n_carriers = r.size
+
+    def fuse_carriers_dev(self, d_map, n_cpi, d_out_map, d_out_metrics, w=None, stream=0):
+        """The carriers' maps summed on this handle's Doppler axis (blah2hip_amb_fuse_carriers_dev; raw pointers/ints):
+        ``d_map`` is ``[C][n_cpi][nD][nDelay]`` complex64 (None: the handle's own map behind a process call of ``C n_cpi``
+        CPIs), ``w`` the ``C`` carrier weights on the host (None: all 1), the outputs ``[n_cpi][nD][nDelay]`` complex64 and
+        ``[n_cpi][2]`` float64, which must not overlap the input.  Enqueues only."""
+        wp = None
+        if w is not None:
+            wk = np.ascontiguousarray(w, dtype=np.float32)
+            if wk.shape != (getattr(self, "_n_carriers", -1),):
+                raise ValueError("w must hold one weight per carrier of the table that is set")
+            wp = _ptr(wk)
+        check(self._L.blah2hip_amb_fuse_carriers_dev(self._h, d_map, n_cpi, wp, d_out_map, d_out_metrics, stream))
 
     def doppler_rate(self, fc, accel):
         """blah2hip_doppler_rate: the Doppler rate in bins drifted over this handle's CPI for the carrier ``fc`` (Hz) and the

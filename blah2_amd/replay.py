@@ -668,7 +668,24 @@ class GpuChain:
     migration or track carrier becomes ``fc + offset``.  ``taps`` defaults to ``16 D`` (at most 1024).  The filter's history
     runs from batch to batch: ``run_batches`` resets it, wants consecutive batches, and ``shard_check`` refuses several ranks.
     ValueError, naming ``capture.ddc``: values outside their ranges, a decimation that does not divide ``fs`` and
-    ``n_samples``.  Without the key nothing is allocated or launched."""
+    ``n_samples``.  Without the key nothing is allocated or launched.
+
+    ``cfg["ddc"]["offset"]`` may be a LIST of up to 8 offsets (``--ddc OFF0,OFF1,...:D``): the carriers of one mast, summed
+    non-coherently on one velocity axis.  A list of one entry is the scalar, bit for bit.  With several, ``cfg["fc"]``
+    (``capture.fc``, the capture's centre frequency) is needed: carrier c's Doppler axis scales with ``fc + offset_c``.
+    The down-converter writes ``[n_car][batch][n]`` planes from its one pass, the clutter filter and the ambiguity stage run
+    over ``n_car * batch`` virtual CPIs (their handles are made for that many), the taper, if configured, runs on all of
+    them, and ``Ambiguity.fuse_carriers_dev`` sums each CPI's ``n_car`` maps along the table of
+    ``blah2_amd.carrier_ratios(fc, offsets)`` (``cfg["ddc"]["interp"]``: ``nearest``, the default, or ``linear``;
+    ``--ddc-interp``) into one map on CARRIER 0's AXIS: the frames' Doppler values are its own.  The integrator, if
+    configured, runs on the fused maps with one channel; the detector is made for ``n_car`` looks (``n_car * W`` behind
+    the integrator).  The outermost rows of the axis are not covered by the carriers above carrier 0's frequency: a
+    result carries ``"carriers": n_car`` and ``"covered": [lo, hi]``, the Doppler interval every carrier covers, and
+    detections outside it are dropped.  A CPI is skipped when the clutter filter fails on any carrier.  ValueError, naming
+    ``capture.ddc``: more than 8 offsets, equal offsets, no ``fc`` or an ``fc + offset`` that is not positive, an unknown
+    ``interp``, a ratio outside [0.5, 2], and several carriers together with ``ambiguity.migration``,
+    ``ambiguity.dopplerRate`` or ``integrate.tracks`` (their tables are built for one carrier), ``detection.clutterMap``
+    (its thresholds are for one look), ``detection.clean`` or ``detect="host"``."""
 
     def __init__(self, cfg: dict, device: int = 0, batch: int = 1, want_map: bool = False, depth: int = 3,
                  reader_threads: int = 4, hit_copy: int = 4096, read_mode: str = "memmove", numa: bool = True,
@@ -717,9 +734,20 @@ class GpuChain:
         self.fs_in, self.n_in, self.fs, self.n = p.fs_in, p.n_in, p.fs, p.n
         self.ddc_cfg, self.clean_cfg, self.clutter_blocks = p.ddc, p.clean, p.clutter["blocks"]
         self.taper = b2.doppler_taper_f32(*p.taper) if p.taper else None  # the Doppler taper's taps (None: no taper stage)
+        # several carriers: the filter and the ambiguity stage see carrier c's CPI b as virtual CPI c * cnt + b
+        self.n_car = n_car = len(p.carriers) if p.carriers else 1
         self.amb = amb = self._own(b2.Ambiguity(amb_c["delayMin"], amb_c["delayMax"], amb_c["dopplerMin"], amb_c["dopplerMax"],
-                                                self.fs, self.n, True, device=device, max_batch=B), False)
+                                                self.fs, self.n, True, device=device, max_batch=B * n_car), False)
         nD, nC = amb.get_n_doppler_bins(), amb.get_n_delay_bins()
+        self.covered = None  # the Doppler interval every carrier covers (None: one carrier)
+        if p.carriers:
+            try:
+                ratio = b2.carrier_ratios(p.carrier_fc, p.carriers)
+                amb.set_carriers(ratio, p.carrier_interp)
+                full = np.nonzero(amb.carrier_table(ratio, p.carrier_interp)["covered"] == n_car)[0]
+            except (ValueError, b2.Blah2HipError) as e:
+                raise ValueError(f"capture.ddc = {cfg['ddc']!r} at fc = {p.carrier_fc:g} Hz: {e}") from None
+            self.covered = (float(amb.doppler[full[0]]), float(amb.doppler[full[-1]]))  # (carrier 0 covers every row)
         self.rates, self.migrate = p.rates, p.migrate_fc is not None
         if p.rates is not None:
             try:
@@ -734,7 +762,7 @@ class GpuChain:
         self.wh, self.fused_fir = None, False
         if p.clutter["enable"]:
             # a CPI has `blocks` flags, and is skipped when any block's matrix is not positive definite
-            self.wh = self._own(b2.WienerHopf(clu_c["delayMin"], clu_c["delayMax"], self.n, device=device, max_batch=B,
+            self.wh = self._own(b2.WienerHopf(clu_c["delayMin"], clu_c["delayMax"], self.n, device=device, max_batch=B * n_car,
                                               blocks=self.clutter_blocks), False)
             # the filter's FIR inside the range kernel where one 4096-point transform covers the geometry (range_fir_kernel):
             # the filtered channel never crosses HBM.  clutter: {fused: false} keeps the two-stage chain, and so do blocks
@@ -756,6 +784,8 @@ class GpuChain:
                     self.nci.set_tracks(b2.nci_walk_table(amb, p.tracks[0]), p.tracks[1], max_cpi=B)
                 except (ValueError, b2.Blah2HipError) as e:
                     raise ValueError(f"integrate.tracks = {cfg['integrate']['tracks']!r}: {e}") from None
+        if p.carriers:  # a cell of the fused map is a sum of one look per carrier, times the integrator's window behind it
+            looks = {"looks": n_car * looks.get("looks", 1)}
         self.nci_tracks = self.nci is not None and self.nci.n_rates > 0
         self.cfar = self.cmap = self.cmap_mode = self.centroid = self.interp = self.finisher = self.clean = self.ddc = None
         if p.cfar_kind:
@@ -778,9 +808,10 @@ class GpuChain:
             if p.clean:
                 key = f"detection.clean = {det_c['clean']!r}"
                 self.clean = self._own(b2.EchoCanceller(self.n, self.fs, amb_c["delayMin"], amb_c["delayMax"], device=device, max_batch=B))
-            if p.ddc:  # one carrier, the history carried from batch to batch
+            if p.ddc:  # every carrier from one pass, the history carried from batch to batch
                 key = f"capture.ddc = {cfg['ddc']!r}"
-                self.ddc = self._own(b2.Channelizer(self.fs_in, p.ddc["decimation"], p.ddc["h"], [p.ddc["offset"]], self.n_in,
+                self.ddc = self._own(b2.Channelizer(self.fs_in, p.ddc["decimation"], p.ddc["h"],
+                                                    list(p.carriers) if p.carriers else [p.ddc["offset"]], self.n_in,
                                                     max_rows=B, device=device))
         except b2.Blah2HipError as e:
             raise ValueError(f"{key}: {e}") from None
@@ -806,14 +837,15 @@ class GpuChain:
         self._hip = _hip_runtime(torch) if read_mode == "mapped" else None
         self.read_mode = "memmove" if read_mode == "mapped" and self._hip is None else read_mode
         # the filtered surveillance channel
-        self.yf = torch.empty((B, n), dtype=torch.complex64, device=dev) if self.wh is not None and not self.fused_fir else None
+        self.yf = torch.empty((B * self.n_car, n), dtype=torch.complex64, device=dev) if self.wh is not None and not self.fused_fir else None
         # USRP: a batch's raw bytes are whole block pairs, at most B*n*16 + 32*block of them (a CPI run that starts and ends
         # mid-block); the de-blocked x and y planes are one pair for all slots, like yf
         self.raw_bytes = (-(-(B * n_in * 2 * FC32_BYTES + 4 * self.usrp_block * FC32_BYTES) // 16) * 16 if self.layout == "usrp" else
                           2 * B * n_in * CS8_BYTES if self.layout == "cs8" else None)  # cs8: the x bytes, then the y bytes
         self.planes = torch.empty((2, B, n_in), dtype=torch.complex64, device=dev) if self.layout == "usrp" else None
         # ... and so are the down-converter's output planes
-        self.ddc_planes = torch.empty((2, B, n), dtype=torch.complex64, device=dev) if self.ddc is not None else None
+        # (several carriers: carrier c's rows follow carrier c - 1's, cnt rows each, so a plane is a batch of n_car * cnt CPIs)
+        self.ddc_planes = torch.empty((2, B * self.n_car, n), dtype=torch.complex64, device=dev) if self.ddc is not None else None
         self.busy_ms, self.batches_done = 0.0, 0  # kernels' time on the compute stream / batches collected, since construction
 
     def _make_slots(self):
@@ -823,6 +855,8 @@ class GpuChain:
         the ambiguity stage, and the downloads, read: ``_submit`` points them at the last stage's."""
         torch, dev, B, cap, hc = self.torch, self.dev, self.batch, self.cap, self.hit_copy
         shape, A = (B, self.amb.get_n_doppler_bins(), self.amb.get_n_delay_bins()), self.b2._lib.MAX_ATOMS
+        V = B * self.n_car  # virtual CPIs in front of the carrier sum (B with one carrier)
+        vshape = (V,) + shape[1:]
         i32, f64, c64 = torch.int32, torch.float64, torch.complex64
         self.slots = []
         for _ in range(self.depth):
@@ -848,12 +882,14 @@ class GpuChain:
                     s[h] = torch.zeros(shape_h, dtype=s[d].dtype).pin_memory()
                     s["down"].append((h, d, cols, per))
 
-            stage({"d_map": (shape, c64), "d_met": ((B, 2), f64)}, ("h_met", "mets", None, 0), maps="d_map", mets="d_met")
-            if self.wh is not None:  # the filter's flags, one per block
-                stage({"d_ok": ((B * self.clutter_blocks,), i32)}, ("h_ok", "d_ok", None, self.clutter_blocks))
+            stage({"d_map": (vshape, c64), "d_met": ((V, 2), f64)}, ("h_met", "mets", None, 0), maps="d_map", mets="d_met")
+            if self.wh is not None:  # the filter's flags, one per block (and carrier)
+                stage({"d_ok": ((V * self.clutter_blocks,), i32)}, ("h_ok", "d_ok", None, self.n_car * self.clutter_blocks))
                 s["d_ok"].fill_(1)
             if self.taper is not None:  # the tapered maps and their metrics: what everything behind the ambiguity stage reads
-                stage({"d_tmap": (shape, c64), "d_tmet": ((B, 2), f64)})
+                stage({"d_tmap": (vshape, c64), "d_tmet": ((V, 2), f64)})
+            if self.n_car > 1:  # the carriers' maps summed on carrier 0's axis: one map per CPI again
+                stage({"d_fmap": (shape, c64), "d_fmet": ((B, 2), f64)}, maps="d_fmap", mets="d_fmet")
             if self.nci is not None:  # the integrated maps and their metrics: what the detector and the download read
                 stage({"d_imap": (shape, c64), "d_imet": ((B, 2), f64)})
                 s["nci"] = (0, 0, 0)  # (count before the batch, windows that end in it, count at which the first ends)
@@ -995,14 +1031,15 @@ class GpuChain:
                 px, py_ = self.ddc_planes[0].data_ptr(), self.ddc_planes[1].data_ptr()
                 self.ddc.process_dev(fmt, x, y, self.n_in, cnt, self.n_in, px, py_, n, cnt * n, st)
                 fmt, fmt_yf, x, y = b2.FMT_C32, b2.FMT_C32, px, py_
+            nv = cnt * self.n_car  # the virtual CPIs the filter and the ambiguity stage see: carrier c's CPI b is c * cnt + b
             if self.wh is None:
-                amb.process_dev(fmt, x, y, cnt, n, slot["d_map"].data_ptr(), slot["d_met"].data_ptr(), st)
+                amb.process_dev(fmt, x, y, nv, n, slot["d_map"].data_ptr(), slot["d_met"].data_ptr(), st)
             elif self.fused_fir:
-                self.wh.estimate_dev_fmt(fmt, x, y, cnt, n, slot["d_ok"].data_ptr(), st)
-                amb.process_dev(fmt, x, y, cnt, n, slot["d_map"].data_ptr(), slot["d_met"].data_ptr(), st)
+                self.wh.estimate_dev_fmt(fmt, x, y, nv, n, slot["d_ok"].data_ptr(), st)
+                amb.process_dev(fmt, x, y, nv, n, slot["d_map"].data_ptr(), slot["d_met"].data_ptr(), st)
             else:
-                self.wh.process_dev_fmt(fmt, x, y, cnt, n, self.yf.data_ptr(), n, slot["d_ok"].data_ptr(), st)
-                amb.process_dev(fmt_yf, x, self.yf.data_ptr(), cnt, n, slot["d_map"].data_ptr(),
+                self.wh.process_dev_fmt(fmt, x, y, nv, n, self.yf.data_ptr(), n, slot["d_ok"].data_ptr(), st)
+                amb.process_dev(fmt_yf, x, self.yf.data_ptr(), nv, n, slot["d_map"].data_ptr(),
                                 slot["d_met"].data_ptr(), st)
             def behind(dets, dcnt):  # everything behind the ambiguity stage, on the maps it has just left; the final records into dets / dcnt
                 n_maps, maps, mets = cnt, slot["d_map"], slot["d_met"]  # what the detector and the download read
@@ -1011,8 +1048,11 @@ class GpuChain:
                 elif self.migrate:  # in place, from the range map the call above left on the handle
                     amb.migrate_dev(maps.data_ptr(), cnt, maps.data_ptr(), mets.data_ptr(), st)
                 if self.taper is not None:
-                    amb.taper_dev(maps.data_ptr(), cnt, self.taper, slot["d_tmap"].data_ptr(), slot["d_tmet"].data_ptr(), st)
+                    amb.taper_dev(maps.data_ptr(), nv, self.taper, slot["d_tmap"].data_ptr(), slot["d_tmet"].data_ptr(), st)
                     maps, mets = slot["d_tmap"], slot["d_tmet"]
+                if self.n_car > 1:  # [n_car][cnt] maps into cnt, on carrier 0's Doppler axis
+                    amb.fuse_carriers_dev(maps.data_ptr(), cnt, slot["d_fmap"].data_ptr(), slot["d_fmet"].data_ptr(), None, st)
+                    maps, mets = slot["d_fmap"], slot["d_fmet"]
                 if self.nci is not None:
                     if self._per_batch:
                         self.reset_integrator()
@@ -1127,8 +1167,8 @@ class GpuChain:
         self.busy_ms += slot["started"].elapsed_time(slot["computed"])
         self.batches_done += 1
         met_h = slot["h_met"].numpy()
-        ok_h = (slot["h_ok"].numpy()[:cnt * self.clutter_blocks].reshape(cnt, self.clutter_blocks).all(axis=1)
-                if self.wh is not None else np.ones(cnt, dtype=bool))
+        ok_h = (slot["h_ok"].numpy()[:self.n_car * cnt * self.clutter_blocks].reshape(self.n_car, cnt, self.clutter_blocks).all(axis=(0, 2))
+                if self.wh is not None else np.ones(cnt, dtype=bool))  # (a CPI is skipped when the filter failed on any carrier)
         at_of, skip_of = (self._windows(slot, ok_h, cnt) if self.nci is not None else
                           ({c: c for c in range(cnt)}, {c: not ok_h[c] for c in range(cnt)}))
         res = []
@@ -1142,6 +1182,11 @@ class GpuChain:
                 r["window"] = self.nci.window
             if self.cfar is not None:
                 self._detections(slot, b, r)
+            if self.covered is not None:  # rows that not every carrier covers keep their looks of noise, but an echo there is not whole
+                r.update(carriers=self.n_car, covered=list(self.covered))
+                if "doppler" in r:
+                    keep = [i for i, f in enumerate(r["doppler"]) if self.covered[0] <= f <= self.covered[1]]
+                    r.update({k: [r[k][i] for i in keep] for k in ("delay", "doppler", "snr")})
             if self.want_map:
                 r["map"] = slot["h_map"][b].numpy().copy()
             res.append(r)
@@ -1358,16 +1403,29 @@ def main(argv=None):
                          "device detection and an fp32 surveillance plane (a USRP capture or the clutter filter); not with "
                          "--integrate or --clutter-map.  Overrides process.detection.clean ({snr, echoes, sideDelay, "
                          "sideDoppler, loading})")
-    ap.add_argument("--ddc", default=None, metavar="OFFSET_HZ:DECIM[:TAPS[:CUTOFF[:BETA]]]",
+    ap.add_argument("--ddc-interp", choices=("nearest", "linear"), default=None,
+                    help="several carriers (--ddc OFF0,OFF1,...:DECIM, at most 8; needs capture.fc): how a carrier's Doppler rows "
+                         "are aligned with carrier 0's axis before the power maps are summed: the nearest row (default; the "
+                         "detector's false-alarm rate holds exactly) or the two rows around it, weighted (loses less of an echo "
+                         "between rows; the detector is conservative).  Overrides capture.ddc.interp")
+    ap.add_argument("--ddc", default=None, metavar="OFFSET_HZ[,OFFSET_HZ...]:DECIM[:TAPS[:CUTOFF[:BETA]]]",
                     help="wideband captures: mix the carrier OFFSET_HZ off the capture's centre to zero, low-pass (a Kaiser-"
                          "windowed sinc of TAPS taps, default 16 DECIM and at most 1024, pass band CUTOFF of the output's "
                          "Nyquist rate, default 0.8, BETA default 8) and decimate by DECIM (1 .. 64, a divisor of capture.fs "
                          "and of the CPI's samples) on the device; everything behind runs at capture.fs / DECIM, and the "
-                         "migration carrier becomes capture.fc + OFFSET_HZ.  One rank.  Overrides capture.ddc ({offset, "
-                         "decimation, taps, cutoff, beta})")
+                         "migration carrier becomes capture.fc + OFFSET_HZ.  Several offsets, at most 8, are the carriers of "
+                         "one mast: their power maps are summed on the first one's Doppler axis (--ddc-interp), which needs "
+                         "capture.fc and excludes --migration, --doppler-rate, --integrate-tracks, --clutter-map, --clean and "
+                         "--detect host.  One rank.  Overrides capture.ddc ({offset, decimation, taps, cutoff, beta, interp})")
     ap.add_argument("--connect", action="store_true",
                     help="with --json: send the documents to network.ip:ports.map / ports.detection of the config, "
                          "framed like Socket::sendData, instead of printing them")
+    # --ddc -16384,16384:4: a value that starts with a negative offset is no number to argparse, which would take it for an option
+    argv, i = list(sys.argv[1:] if argv is None else argv), 0
+    while i + 1 < len(argv):
+        if argv[i] == "--ddc" and len(argv[i + 1]) > 1 and argv[i + 1][0] == "-" and argv[i + 1][1] in "0123456789.":
+            argv[i:i + 2] = ["--ddc=" + argv[i + 1]]
+        i += 1
     a = ap.parse_args(argv)
     y = yaml.safe_load(open(a.config))
     layout = a.format or config_layout(y)
@@ -1387,6 +1445,8 @@ def main(argv=None):
     cfg = dict(y["process"], fs=fs, n_samples=n)
     if y["capture"].get("ddc"):
         cfg["ddc"] = dict(y["capture"]["ddc"])
+    if y["capture"].get("fc") is not None:  # several carriers: their Doppler axes scale with capture.fc + offset
+        cfg["fc"] = y["capture"]["fc"]
 
     def parsed(flag, form, names, convs, at_least=1, **defaults):
         """A flag's ``A:B:...`` as the dictionary its config key holds.  Syntax only: plan_chain below weighs the values."""
@@ -1402,8 +1462,16 @@ def main(argv=None):
         return dict(cfg.get("detection") or {}, **kw)
 
     if a.ddc is not None:
-        cfg["ddc"] = parsed("ddc", "OFFSET_HZ:DECIM[:TAPS[:CUTOFF[:BETA]]]", ("offset", "decimation", "taps", "cutoff", "beta"),
-                            (float, int, int, float, float), 2)
+        def offsets(v):  # OFF, or OFF0,OFF1,...: the list form of capture.ddc.offset
+            return [float(f) for f in v.split(",")] if "," in v else float(v)
+
+        cfg["ddc"] = parsed("ddc", "OFFSET_HZ[,OFFSET_HZ...]:DECIM[:TAPS[:CUTOFF[:BETA]]]", ("offset", "decimation", "taps", "cutoff", "beta"),
+                            (offsets, int, int, float, float), 2,
+                            **({"interp": cfg["ddc"]["interp"]} if (_key(cfg, "ddc") or {}).get("interp") is not None else {}))
+    if a.ddc_interp is not None:
+        if not _key(cfg, "ddc"):
+            ap.error("--ddc-interp belongs to --ddc / capture.ddc")
+        cfg["ddc"] = dict(cfg["ddc"], interp=a.ddc_interp)
     if a.clutter_blocks is not None:
         if a.clutter_blocks < 1:
             ap.error("--clutter-blocks takes a block count >= 1")

@@ -262,6 +262,7 @@ int blah2hip_amb_set_option(blah2hip_amb_t h, int option, int64_t value);
 #define BLAH2HIP_INFO_RATE_GRID 19             /* workgroups per map of the last blah2hip_amb_rate_bank_dev launch */
 #define BLAH2HIP_INFO_TRACK_GRID 20            /* workgroups per output map of the last track_sum_kernel launch (blah2hip_nci_process_tracks_dev) */
 #define BLAH2HIP_INFO_TRACK_MAX_SHIFT 21       /* the largest |s(j,k,a)| of the table the last blah2hip_nci_set_tracks on this handle's maps built */
+#define BLAH2HIP_INFO_CARRIER_GRID 22          /* workgroups per map of the last blah2hip_amb_fuse_carriers_dev launch */
 int blah2hip_amb_get_info(blah2hip_amb_t h, int key, int64_t *value);
 
 /* Ambiguity::process + Map::set_metrics on host buffers (blah2.cpp:278-279).
@@ -1395,6 +1396,62 @@ int blah2hip_ddc_read_taps(blah2hip_ddc_t h, uint32_t carrier, float *g);
 #define BLAH2HIP_DDC_INFO_NEXT_SAMPLE 2
 int blah2hip_ddc_get_info(blah2hip_ddc_t h, int what, int64_t *value);
 
+/* ---- multi-carrier integration: carrier maps summed on one velocity axis (no reference counterpart) ----
+ * A mast radiates several programmes, and the down-converter above delivers each carrier of a wideband capture.  An echo of
+ * bistatic range rate v sits at Doppler -v fc_c / c in carrier c: the same target in ANOTHER ROW of every carrier's map.
+ * Summing the power maps of C carriers gives C looks per cell and evens out the programmes' content, once the rows are
+ * aligned.  This is one table-driven gather-and-sum over maps that are already on the device.
+ *
+ * Table.  C <= BLAH2HIP_MAX_CARRIERS carriers with ratio[c] = fc_c / fc_ref; the output axis is the handle's own
+ * (blah2hip_amb_get_axes, the reference carrier's).  With doppler[0 .. nD), nD >= 2, D = (doppler[nD-1] - doppler[0]) / (nD - 1),
+ * for carrier c and output row j, in fp64, left to right:
+ *   u = (ratio[c] * doppler[j] - doppler[0]) / D;   |u - rint(u)| <= 1e-9: u = rint(u)   (ratio 1 is the exact identity)
+ * Carrier c COVERS row j when 0 <= u <= nD - 1; otherwise u is clamped to that interval: the edge row stands in, so the cell
+ * keeps C looks of noise, and covered[j], the number of carriers that cover row j, tells the caller which rows to distrust.
+ *   BLAH2HIP_CARRIER_NEAREST   row = floor(u + 0.5), a_lo = 1, a_hi = 0
+ *   BLAH2HIP_CARRIER_LINEAR    row = floor(u), t = u - row, a_hi = fp32(t), a_lo = fp32(1 - t)   (row = nD - 1 implies t = 0)
+ * Cell arithmetic.  Input d_map [C][n_cpi][nD][nDelay] complex fp32: what blah2hip_amb_process_dev writes for a batch of
+ * C * n_cpi CPIs when the down-converter's carrier_stride is n_cpi * out_stride.  For CPI i, row j, column d, in fp32:
+ *   S = 0;  for c = 0 .. C - 1:   p_lo = fmaf(re, re, im * im) of M_c[i][row][d]     (the integrator's form)
+ *                                 q = a_lo * p_lo;   a_hi != 0:  q = fmaf(a_hi, p_hi, q), p_hi from row + 1 (else not read)
+ *                                 S = fmaf(w_c, q, S)
+ *   out[i][j][d] = ( sqrtf(scale * S), 0 ),   scale = fp32(1 / sum_c w_c)
+ * -- like the integrator's an ordinary complex map whose |z|^2 is the normalised sum, with Map::set_metrics of the cells as
+ * written.  Every term is non-negative: at most 4 roundings up to q, one per carrier in S, one for the scale, halved by
+ * the square root, plus its own: the error is below (C + 8) 2^-24 of the cell.  With every ratio 1 either interpolation
+ * gives blah2hip_nci_process_dev's bits at window 1 with the same weights.  A NaN cell makes NaN exactly the output cells
+ * whose table entries read it.
+ * Statistics.  NEAREST keeps a cell exactly Gamma(C) under noise, which is what blah2hip_cfar_alpha(pfa, C, ...) assumes
+ * (BLAH2HIP_OPT_CFAR_LOOKS = C); an echo between two rows loses up to 3.9 dB in that carrier.  LINEAR loses less of such an
+ * echo, and its cells have lighter tails than Gamma(C) (a convex mix of two cells has a smaller variance), so a detector made
+ * for C looks is conservative: its false-alarm rate is below pfa. */
+#define BLAH2HIP_MAX_CARRIERS 8
+#define BLAH2HIP_CARRIER_NEAREST 0
+#define BLAH2HIP_CARRIER_LINEAR 1
+/* Host only: the table for this handle's Doppler axis.  row, a_lo, a_hi: [n_carriers][n_doppler]; covered: [n_doppler]; any
+ * output pointer may be NULL.  BLAH2HIP_ERR_INVALID: a NULL handle or ratio, n_carriers outside [1, BLAH2HIP_MAX_CARRIERS],
+ * a ratio that is not finite or lies outside [0.5, 2], an unknown interpolation, n_doppler < 2. */
+int blah2hip_carrier_table(blah2hip_amb_t h, const double *ratio, uint32_t n_carriers, int interp, int32_t *row, float *a_lo,
+                           float *a_hi, uint32_t *covered);
+/* Builds that table and uploads it into a device buffer the handle owns (allocated at the first call, freed by destroy; the
+ * call waits for the device, like blah2hip_amb_set_migration).  n_carriers = 0 clears the table.  BLAH2HIP_ERR_INVALID, with
+ * the table that was set left as it was: blah2hip_carrier_table's cases. */
+int blah2hip_amb_set_carriers(blah2hip_amb_t h, const double *ratio, uint32_t n_carriers, int interp);
+/* The sum for n_cpi CPIs along the table that is set.  d_map: [C][n_cpi][nD][nDelay] (NULL = the handle's internal map behind
+ * a process call of C * n_cpi CPIs).  w: HOST array [C] of fp32 weights, read at the call and carried in the launch
+ * arguments, or NULL for all 1.  Outputs: d_out_map [n_cpi][nD][nDelay] and d_out_metrics [n_cpi][2].  Enqueues only --
+ * carrier_sum_kernel (BLAH2HIP_K_BEAM) and metrics_kernel (BLAH2HIP_K_METRICS), which finishes the metrics in index order
+ * (no floating-point atomics) -- with no upload, allocation or synchronisation, and can be captured in a graph.  The
+ * workgroups per map (BLAH2HIP_INFO_CARRIER_GRID) depend on the map's geometry alone, never on n_cpi: a map's bits and
+ * metrics are the same however the CPIs are cut into calls.  The per-workgroup partials live in the handle's buffers, so
+ * calls on one handle must be ordered on the device.
+ * BLAH2HIP_ERR_INVALID, with nothing enqueued: a NULL handle or output, no table set, n_cpi == 0 or C * n_cpi above
+ * max_batch, a weight that is negative or not finite, weights that add up to 0, a map that is not 8-byte aligned, an output
+ * that overlaps the input maps or the other output (the gather cannot run in place).  BLAH2HIP_ERR_UNSUPPORTED: the handle
+ * has fewer metrics partials per map than the kernel has workgroups (no geometry the engine plans today). */
+int blah2hip_amb_fuse_carriers_dev(blah2hip_amb_t h, const void *d_map, uint32_t n_cpi, const float *w, void *d_out_map,
+                                   double *d_out_metrics, void *stream);
+
 /* ---- per-kernel timing (HIP events on the launch stream) ---------------- */
 #define BLAH2HIP_K_RANGE 0
 #define BLAH2HIP_K_DOPPLER 1
@@ -1404,7 +1461,8 @@ int blah2hip_ddc_get_info(blah2hip_ddc_t h, int what, int64_t *value);
 #define BLAH2HIP_K_SAT_COLS 5 /* ... column prefix sums */
 #define BLAH2HIP_K_ROTATE 6   /* Doppler-centre shift (asymmetric limits only) */
 #define BLAH2HIP_K_BEAM 7     /* beamform_kernel (blah2hip_amb_beamform_dev; its metrics_kernel counts under _METRICS), beam_samples_kernel,
-                               * taper_kernel (blah2hip_amb_taper_dev; its metrics_kernel counts under _METRICS too) */
+                               * taper_kernel (blah2hip_amb_taper_dev; its metrics_kernel counts under _METRICS too),
+                               * carrier_sum_kernel (blah2hip_amb_fuse_carriers_dev; likewise) */
 #define BLAH2HIP_K_COV 8      /* array_cov_kernel or sample_cov_kernel + cov_fold_kernel (blah2hip_amb_covariance_dev, _sample_covariance_dev) */
 #define BLAH2HIP_K_BEARING 9  /* bearing_kernel (blah2hip_amb_bearing_dev) */
 #define BLAH2HIP_K_COUNT 10
