@@ -10,6 +10,8 @@ from ._lib import Blah2HipError, FMT_C32, FMT_F16, FMT_I16, FMT_I16X_C32Y, FMT_I
 from .process import BEARING_DTYPE, DET_DTYPE, HIT_DTYPE, DetectionFinisher, deblock_c32_dev, dets_to_detection, hits_to_detection  # noqa: F401
 from .process import Ambiguity, Centroid, CfarDetector1D, CfarDetector2D, Detection, Interpolate, Map, SpectrumAnalyser, WienerHopf, next_hamming, mvdr_weights, ula_steering, ula_weights, bearing, bearing_degrees, uca_steering, sample_covariance, beam_samples  # noqa: F401
 from .process import MapIntegrator, cfar_alpha, cfar_alpha_table, cfar_pfa, integrate_ends, integrate_maps  # noqa: F401
+from .process import (GoCfarDetector1D, GoCfarDetector2D, gocfar_alpha, gocfar_alpha_table, gocfar_counts,  # noqa: F401
+                      gocfar_hits, gocfar_pfa, gocfar_table_for)
 from .process import OsCfarDetector1D, OsCfarDetector2D, oscfar_alpha, oscfar_alpha_table, oscfar_hits, oscfar_pfa, oscfar_rank  # noqa: F401
 from .process import doppler_taper, doppler_taper_f32, doppler_window, taper_gains, taper_maps  # noqa: F401
 from .process import migrate_maps, migration_shifts, migration_table, range_map  # noqa: F401

@@ -37,6 +37,7 @@ TAPER_NONE, TAPER_HANN, TAPER_HAMMING, TAPER_BLACKMAN, TAPER_BLACKMAN_HARRIS, TA
 TAPER_KINDS = {"none": TAPER_NONE, "hann": TAPER_HANN, "hamming": TAPER_HAMMING, "blackman": TAPER_BLACKMAN,
                "blackmanharris": TAPER_BLACKMAN_HARRIS, "nuttall": TAPER_NUTTALL, "flattop": TAPER_FLATTOP}
 MAX_CFAR_LOOKS = 1024
+CFAR_GO, CFAR_SO = 1, 2  # kind of blah2hip_gocfar*: greatest-of, smallest-of
 MAX_NCI_WINDOW = 16
 WALK_AUTO, WALK_STATIC, WALK_TICKET = 0, 1, 2
 MULTI_AUTO, MULTI_SHARED, MULTI_PER_CHANNEL = 0, 1, 2
@@ -185,6 +186,14 @@ SYMBOLS = {
     "blah2hip_cfar2d_dev": (C.c_int, [_vp, _vp, _vp, _u32, _dbl, _i32, _i32, _i32, _i32, _i32, _dbl, _vp, _u32, _vp, _vp]),
     "blah2hip_cfar2d_process": (C.c_int, [_vp, _u32, _dbl, _i32, _i32, _i32, _i32, _i32, _dbl, _vp, _vp, _vp, _u32,
                                           C.POINTER(_u32)]),
+    "blah2hip_gocfar_alpha": (C.c_int, [_dbl, _u32, _u32, _vp, _vp, _vp]),
+    "blah2hip_gocfar1d_dev": (C.c_int, [_vp, _vp, _vp, _u32, _dbl, _u32, _i32, _i32, _i32, _dbl, _vp, _u32, _vp, _vp]),
+    "blah2hip_gocfar1d_prepare": (C.c_int, [_vp, _dbl, _u32, _i32, _i32]),
+    "blah2hip_gocfar1d_process": (C.c_int, [_vp, _u32, _dbl, _u32, _i32, _i32, _i32, _dbl, _vp, _vp, _vp, _u32, C.POINTER(_u32)]),
+    "blah2hip_gocfar2d_dev": (C.c_int, [_vp, _vp, _vp, _u32, _dbl, _u32, _i32, _i32, _i32, _i32, _dbl, _vp, _u32, _vp, _vp]),
+    "blah2hip_gocfar2d_prepare": (C.c_int, [_vp, _dbl, _u32, _i32, _i32, _i32]),
+    "blah2hip_gocfar2d_process": (C.c_int, [_vp, _u32, _dbl, _u32, _i32, _i32, _i32, _i32, _dbl, _vp, _vp, _vp, _u32,
+                                            C.POINTER(_u32)]),
     "blah2hip_oscfar_alpha": (C.c_int, [_dbl, _u32, _u32, _u32, _vp, _vp]),
     "blah2hip_oscfar1d_dev": (C.c_int, [_vp, _vp, _vp, _u32, _dbl, _u32, _i32, _i32, _i32, _dbl, _vp, _u32, _vp, _vp]),
     "blah2hip_oscfar1d_prepare": (C.c_int, [_vp, _dbl, _u32, _i32]),

@@ -55,7 +55,7 @@ class ChainPlan:
     clutter: dict         # {enable, blocks, fused}: fused is the WISH (fir_fusable decides at build)
     integrate: Optional[tuple]  # (W, H)
     tracks: Optional[tuple]     # (fc, bank or None)
-    cfar_kind: Optional[str]    # "ca" | "os", None: detection not enabled
+    cfar_kind: Optional[str]    # "ca" | "os" | "goca" | "soca", None: detection not enabled
     rank: float
     pfa: Optional[float]  # divided by the rate bank's and the tracks' hypothesis counts (the union bound)
     cmap: Optional[tuple]       # (memory, mode)
@@ -210,13 +210,17 @@ def plan_chain(cfg: dict, layout: str = "rspduo", usrp_block: Optional[int] = No
                 raise ValueError("integrate is configured, and the clutter map's thresholds are made for one look per cell")
         except ValueError as e:
             raise ValueError(f"detection.clutterMap = {cm_c!r}: {e}") from None
-    # detection: {cfar: ca | os, rank: 0.75}.  A cell of the rate bank's map is the strongest of K hypotheses, which multiplies
+    # detection: {cfar: ca | os | goca | soca, rank: 0.75}.  A cell of the rate bank's map is the strongest of K hypotheses, which multiplies
     # the false-alarm rate by at most K: pfa / K (the union bound), and likewise for the hypotheses along the tracks
     kind, pfa, centroid, rank = None, None, None, 0.75
     if enabled:
         kind = str(det_c.get("cfar", "ca")).lower()
-        if kind not in ("ca", "os"):
-            raise ValueError(f"detection.cfar {kind!r}: 'ca' or 'os'")
+        if kind not in ("ca", "os", "goca", "soca"):
+            raise ValueError(f"detection.cfar {kind!r}: 'ca', 'os', 'goca' or 'soca'")
+        if kind in ("goca", "soca") and (integrate or (carriers and len(carriers) > 1)):
+            # greatest-of / smallest-of: the thresholds are made for one look per cell
+            raise ValueError(f"detection.cfar {kind!r}: " + ("integrate is configured" if integrate else "several carriers are summed")
+                             + ", and the greatest-of / smallest-of thresholds are made for one look per cell")
         pfa = det_c["pfa"] if rates is None else det_c["pfa"] / len(rates)
         if tracks is not None:
             pfa = pfa / (1 if tracks[1] is None else len(tracks[1]))

@@ -113,6 +113,9 @@ struct blah2hip_amb_s {
   struct CfarTable { double pfa; uint32_t looks, rank; size_t n; double *d; bool pinned; };
   std::vector<CfarTable> alphaTables; // cell averaging (rank 0): one per (pfa, looks, size) seen
   std::vector<CfarTable> osTables;    // ordered statistic: one per (pfa, looks, rank_permille, size) seen
+  // a greatest-of / smallest-of table of detect.hip's gocfar_table(): (2 hR + 1)(nT + 1)^2 factors for this handle's maps
+  struct GoTable { double pfa; uint32_t kind; int32_t nG, nT, hR; double *d; bool pinned; };
+  std::vector<GoTable> goTables;      // one per (pfa, kind, nGuard, nTrain, hR) seen; its own budget, freed by destroy
   double *d_sat = nullptr;          // 2-D CFAR summed-area table [max_batch][nD+1][nDelay+1], allocated at its first use
   blah2hip_hit_t *d_hits = nullptr; // the *_process calls' hit list, grown to the map's cell count
   uint32_t hitCap = 0;

@@ -1034,6 +1034,8 @@ int blah2hip_amb_destroy(blah2hip_amb_t h)
     if (t.d) (void)hipFree(t.d);
   for (auto &t : h->osTables)
     if (t.d) (void)hipFree(t.d);
+  for (auto &t : h->goTables)
+    if (t.d) (void)hipFree(t.d);
   if (h->h_pin) (void)hipHostFree(h->h_pin);
   leak_clear(h);
   h->timer.destroy();

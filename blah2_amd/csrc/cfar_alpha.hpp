@@ -1,5 +1,6 @@
-// The detectors' threshold arithmetic behind blah2hip_cfar_alpha, blah2hip_oscfar_alpha and blah2hip_cmap_alpha (detect.hip
-// validates and calls cfar_alpha_fill / oscfar_alpha_fill / cmap_alpha_fill).  Host only, C++17 and libm, no HIP: tests/host/emulate_cfar_alpha.cpp compiles it
+// The detectors' threshold arithmetic behind blah2hip_cfar_alpha, blah2hip_oscfar_alpha, blah2hip_cmap_alpha and
+// blah2hip_gocfar_alpha (detect.hip validates and calls cfar_alpha_fill / oscfar_alpha_fill / cmap_alpha_fill /
+// goso_alpha_fill).  Host only, C++17 and libm, no HIP: tests/host/emulate_cfar_alpha.cpp compiles it
 // on its own.  The formulas are in include/blah2hip.h.  Everything here has internal linkage (the unnamed namespace): the
 // library exports none of it, and nothing the compiler emits out of line -- the thread objects of run_slices included --
 // can be interposed.
@@ -269,6 +270,79 @@ inline void cmap_alpha_fill(double pfa, uint32_t T, uint32_t max_age, double *al
     }
   });
   for (uint64_t a = (uint64_t)last + 1; a <= max_age; a++) alpha[a] = alpha[last];
+}
+
+// ---- greatest-of / smallest-of ----
+// One look, halves of a and b training cells (include/blah2hip.h).  T(alpha; a, b) = E[e^(-alpha U); U < V] for the half
+// means U = Gamma(a) / a, V = Gamma(b) / b:  sum_{j<b} C(a-1+j, j) (b/a)^j s^-(a+j),  s = 1 + (alpha + b) / a, term by term in
+// the log domain like pfa_of_looks (at the halo limits the first terms underflow and the sum has 1960 of them).
+inline double goso_t(double alpha, uint32_t a, uint32_t b)
+{
+  const double da = (double)a, db = (double)b;
+  const double ls = std::log(1.0 + (alpha + db) / da), lr = std::log(db / da) - ls;
+  double lg = -da * ls, s = std::exp(lg);
+  for (uint32_t j = 1; j < b; j++) {
+    lg += std::log((da - 1.0 + (double)j) / (double)j) + lr;
+    s += std::exp(lg);
+  }
+  return s;
+}
+
+// E[e^(-alpha U); U > V]: the same series from j = b on.  The whole series sums to (1 + alpha/a)^-a, and that minus goso_t is
+// the textbook form of this quantity; with uneven halves and a small pfa the two are equal to eight digits and more (a = 1,
+// b = 3, pfa 1e-8: 3e-3 each), so the tail is summed instead: positive terms that fall from the first one on (the ratio is
+// below (a + b - 1) / (a + b + alpha)), until what is left is below 1e-17 of the sum.
+inline double goso_tail(double alpha, uint32_t a, uint32_t b)
+{
+  const double da = (double)a, db = (double)b, sv = 1.0 + (alpha + db) / da;
+  const double ls = std::log(sv), lr = std::log(db / da) - ls, q = (db / da) / sv;
+  double lg = -da * ls;
+  for (uint32_t j = 1; j <= b; j++) lg += std::log((da - 1.0 + (double)j) / (double)j) + lr;
+  double s = std::exp(lg);
+  for (uint32_t j = b + 1; j < b + 100000000u; j++) {
+    const double f = (da - 1.0 + (double)j) / (double)j;
+    lg += std::log(f) + lr;
+    const double t = std::exp(lg), r = f * q; // r: no later ratio is larger
+    s += t;
+    if (!(t * r > (1.0 - r) * 1e-17 * s)) break;
+  }
+  return s;
+}
+
+constexpr uint32_t GOSO_GO = 1, GOSO_SO = 2; // BLAH2HIP_CFAR_GO, BLAH2HIP_CFAR_SO
+
+// Pfa(alpha) of the pair of thresholds alpha mu_A, alpha mu_B: smallest-of  T(a, b) + T(b, a);  greatest-of the two tails,
+// which is (1 + alpha/a)^-a + (1 + alpha/b)^-b minus the former.  The halves in ascending size, so that (a, b) and (b, a)
+// give the same bits.
+inline double goso_pfa(double alpha, uint32_t kind, uint32_t a, uint32_t b)
+{
+  if (a > b) std::swap(a, b);
+  if (kind == GOSO_SO) return goso_t(alpha, a, b) + goso_t(alpha, b, a);
+  return goso_tail(alpha, a, b) + goso_tail(alpha, b, a);
+}
+
+inline double goso_alpha(double pfa, uint32_t kind, uint32_t a, uint32_t b)
+{
+  if (a == 0 && b == 0) return std::nan("");
+  if (a == 0 || b == 0) { // one half: the cell-averaging factor over the other (cfar_alpha_fill's expression)
+    const double n = (double)(a + b);
+    return n * (pow(pfa, -1.0 / n) - 1);
+  }
+  double hi = 1.0;
+  while (goso_pfa(hi, kind, a, b) > pfa) hi *= 2.0;
+  return bisect_upper(0.0, hi, [&](double x) { return goso_pfa(x, kind, a, b) > pfa; });
+}
+
+// blah2hip_gocfar_alpha past its checks: alpha[i] for the pair (a[i], b[i]).  A bisection of about 60 evaluations of a + b
+// terms each per pair (greatest-of: a + b logarithms and the tails' few dozen terms); long lists (a 2-D window's pairs at the map's corners) are cut into slices.
+inline void goso_alpha_fill(double pfa, uint32_t kind, uint32_t n_pairs, const uint32_t *a, const uint32_t *b, double *alpha)
+{
+  uint64_t terms = 0;
+  for (uint32_t i = 0; i < n_pairs; i++) terms += (uint64_t)a[i] + b[i];
+  const uint32_t nThreads = terms < 20000 ? 1u : table_threads();
+  run_slices(nThreads, [=](uint32_t first) {
+    for (uint64_t i = first; i < n_pairs; i += nThreads) alpha[i] = goso_alpha(pfa, kind, a[i], b[i]);
+  });
 }
 
 } // namespace

@@ -1,11 +1,15 @@
-// Detection behind include/blah2hip.h: 1-D and 2-D CFAR (cell-averaging and ordered-statistic) with their threshold-table
-// caches and summed-area table, the clutter map and its gate, Centroid and Interpolate on the host and on the device.  Host
-// code; the kernels are cfar_kernels.hpp's, oscfar_kernels.hpp's, cmap_kernels.hpp's and detect_kernels.hpp's.
+// Detection behind include/blah2hip.h: 1-D and 2-D CFAR (cell-averaging, ordered-statistic, greatest-of / smallest-of) with
+// their threshold-table caches and summed-area table, the clutter map and its gate, Centroid and Interpolate on the host and
+// on the device.  Host code; the kernels are cfar_kernels.hpp's, oscfar_kernels.hpp's, gocfar_kernels.hpp's,
+// cmap_kernels.hpp's and detect_kernels.hpp's.
 #include "amb_handle.hpp"
 #include "cfar_kernels.hpp"
 #include "cmap_kernels.hpp"
 #include "detect_kernels.hpp"
+#include "gocfar_kernels.hpp"
 #include "oscfar_kernels.hpp"
+
+#include <map>
 
 #include "cfar_alpha.hpp"
 
@@ -401,6 +405,109 @@ int cmap_table(blah2hip_cmap_s *cm, double pfa, const double **alpha, hipStream_
 int cmap_check_pfa(double pfa)
 {
   if (!(pfa > 0.0 && pfa < 1.0)) return fail(BLAH2HIP_ERR_INVALID, "pfa outside (0, 1)");
+  return BLAH2HIP_OK;
+}
+
+// ---- greatest-of / smallest-of ----
+// The in-bounds training columns of the two halves of delay column j (gocfar_kernels.hpp: the same expressions)
+void gocfar_cols(int j, int nC, int nG, int nT, int *cL, int *cR)
+{
+  *cL = std::max(std::min(j - nG, nC) - std::max(j - nG - nT, 1), 0);
+  *cR = std::min(j + nG + nT + 1, nC) - std::min(j + nG + 1, nC);
+}
+
+// The table of gocfar_kernels.hpp for this handle's maps: alpha[((rows - 1)(nT + 1) + cL)(nT + 1) + cR] for every (rows, cL,
+// cR) a cell of the map has under the window (hR 0: the 1-D detector, rows = 1), NaN elsewhere.  Distinct triples with one
+// (a, b) = (rows cL, rows cR) share one solve.
+void gocfar_host_table(const blah2hip_amb_s *h, double pfa, uint32_t kind, int nG, int nT, int hR, std::vector<double> &tab)
+{
+  const int nD = (int)h->dims.n_doppler_bins, nC = (int)h->dims.n_delay_bins, W = nT + 1;
+  tab.assign((size_t)(2 * hR + 1) * W * W, std::nan(""));
+  std::vector<char> rowsSeen(2 * hR + 2, 0), colsSeen((size_t)W * W, 0);
+  for (int i = 0; i < nD; i++) rowsSeen[std::min(i + hR, nD - 1) - std::max(i - hR, 0) + 1] = 1;
+  for (int j = 0; j < nC; j++) {
+    int cL, cR;
+    gocfar_cols(j, nC, nG, nT, &cL, &cR);
+    colsSeen[(size_t)cL * W + cR] = 1;
+  }
+  std::map<std::pair<uint32_t, uint32_t>, uint32_t> index;
+  std::vector<uint32_t> a, b;
+  for (int rows = 1; rows <= 2 * hR + 1; rows++)
+    for (int c = 0; rowsSeen[rows] && c < W * W; c++)
+      if (colsSeen[c] && c != 0 && index.emplace(std::make_pair((uint32_t)(rows * (c / W)), (uint32_t)(rows * (c % W))), (uint32_t)a.size()).second) {
+        a.push_back((uint32_t)(rows * (c / W)));
+        b.push_back((uint32_t)(rows * (c % W)));
+      }
+  std::vector<double> alpha(a.size());
+  goso_alpha_fill(pfa, kind, (uint32_t)a.size(), a.data(), b.data(), alpha.data());
+  for (int rows = 1; rows <= 2 * hR + 1; rows++)
+    for (int c = 0; rowsSeen[rows] && c < W * W; c++)
+      if (colsSeen[c] && c != 0)
+        tab[(size_t)(rows - 1) * W * W + c] = alpha[index.at(std::make_pair((uint32_t)(rows * (c / W)), (uint32_t)(rows * (c % W))))];
+}
+
+// ... on the device, in a cache of its own (h->goTables) keyed by (pfa, kind, nGuard, nTrain, hR) -- the map's geometry is the
+// handle's -- with cfar_table's rules: a hit hands out the pointer, a miss builds and uploads (blocking) and is refused while
+// `st` is being captured; eight unpinned tables, least recently used first out; what *_prepare made stays.
+int gocfar_table(blah2hip_amb_s *h, double pfa, uint32_t kind, int nG, int nT, int hR, const double **alpha,
+                 hipStream_t st = nullptr, bool pin = false)
+{
+  auto &T = h->goTables;
+  for (size_t i = 0; i < T.size(); i++)
+    if (T[i].pfa == pfa && T[i].kind == kind && T[i].nG == nG && T[i].nT == nT && T[i].hR == hR) {
+      blah2hip_amb_s::GoTable t = T[i];
+      t.pinned = t.pinned || pin;
+      T.erase(T.begin() + (long)i);
+      T.push_back(t);
+      *alpha = t.d;
+      return BLAH2HIP_OK;
+    }
+  if (st) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+      return fail(BLAH2HIP_ERR_INVALID, "greatest-of / smallest-of table of this (pfa, kind, window) is not resident: call "
+                                        "blah2hip_gocfar1d_prepare / blah2hip_gocfar2d_prepare before capturing the stream");
+  }
+  std::vector<double> host;
+  gocfar_host_table(h, pfa, kind, nG, nT, hR, host);
+  size_t unpinned = 0;
+  for (const auto &e : T) unpinned += e.pinned ? 0 : 1;
+  if (unpinned >= CFAR_TABLES_MAX) {
+    HIPCHK(hipDeviceSynchronize()); // the oldest unpinned table may still be read by enqueued work
+    for (size_t i = 0; i < T.size(); i++)
+      if (!T[i].pinned) {
+        (void)hipFree(T[i].d);
+        T.erase(T.begin() + (long)i);
+        break;
+      }
+  }
+  blah2hip_amb_s::GoTable t{pfa, kind, nG, nT, hR, nullptr, pin};
+  HIPCHK(hipMalloc(&t.d, host.size() * sizeof(double)));
+  hipError_t e = hipMemcpy(t.d, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    (void)hipFree(t.d);
+    return fail(BLAH2HIP_ERR_HIP, std::string("greatest-of / smallest-of table upload: ") + hipGetErrorString(e));
+  }
+  T.push_back(t);
+  *alpha = t.d;
+  return BLAH2HIP_OK;
+}
+
+// what the greatest-of / smallest-of calls check after the window's sizes: the kind, pfa, the handle's looks
+int gocfar_check(const blah2hip_amb_s *h, double pfa, uint32_t kind)
+{
+  if (kind != BLAH2HIP_CFAR_GO && kind != BLAH2HIP_CFAR_SO) return fail(BLAH2HIP_ERR_INVALID, "kind: BLAH2HIP_CFAR_GO or BLAH2HIP_CFAR_SO");
+  if (int rc = cmap_check_pfa(pfa)) return rc;
+  if (h->cfarLooks > 1)
+    return fail(BLAH2HIP_ERR_UNSUPPORTED, "greatest-of / smallest-of: the thresholds are made for one look per cell (BLAH2HIP_OPT_CFAR_LOOKS is above 1)");
+  return BLAH2HIP_OK;
+}
+
+int gocfar2d_check(int32_t ngd, int32_t ntd, int32_t hr, int32_t min_delay = 0)
+{
+  if (int rc = check_2d(ngd, ntd, 0, hr, min_delay)) return rc;
+  if (hr > C2T_MAX_HR || ngd + ntd > C2T_MAX_HC)
+    return fail(BLAH2HIP_ERR_UNSUPPORTED, "greatest-of / smallest-of 2-D window beyond the tile's halo (n_rows_doppler <= 24, nGd + nTd <= 40)");
   return BLAH2HIP_OK;
 }
 
@@ -833,6 +940,104 @@ int blah2hip_oscfar2d_process(blah2hip_amb_t h, uint32_t cpi, double pfa, uint32
 {
   return process_one(h, cpi, delay, doppler, snr, cap, count, [&](const cf *m, const double *met) {
     return blah2hip_oscfar2d_dev(h, m, met, 1, pfa, rank_permille, ngd, ntd, ngf, ntf, min_delay, min_doppler, h->d_hits,
+                                 h->hitCap, h->d_count, h->stream);
+  });
+}
+
+// ------------------------------------------------- greatest-of / smallest-of --
+// Host arithmetic only (cfar_alpha.hpp)
+int blah2hip_gocfar_alpha(double pfa, uint32_t kind, uint32_t n_pairs, const uint32_t *a, const uint32_t *b, double *alpha)
+{
+  if (!a || !b || !alpha) return fail(BLAH2HIP_ERR_INVALID, "NULL argument");
+  if (kind != BLAH2HIP_CFAR_GO && kind != BLAH2HIP_CFAR_SO) return fail(BLAH2HIP_ERR_INVALID, "kind: BLAH2HIP_CFAR_GO or BLAH2HIP_CFAR_SO");
+  if (int rc = cmap_check_pfa(pfa)) return rc;
+  goso_alpha_fill(pfa, kind, n_pairs, a, b, alpha);
+  return BLAH2HIP_OK;
+}
+
+int blah2hip_gocfar1d_dev(blah2hip_amb_t h, const void *d_map, const double *d_metrics, uint32_t n_cpi, double pfa, uint32_t kind,
+                          int32_t n_guard, int32_t n_train, int32_t min_delay, double min_doppler, blah2hip_hit_t *d_hits,
+                          uint32_t cap, uint32_t *d_count, void *stream)
+{
+  int rc;
+  if ((rc = check_dev(h, d_hits, d_count, n_cpi)) || (rc = check_1d(n_guard, n_train, min_delay)) || (rc = gocfar_check(h, pfa, kind)))
+    return rc;
+  HIPCHK(hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  GoCfarArgs ga;
+  CfarArgs &a = ga.c;
+  ga.kind = kind;
+  if ((rc = gocfar_table(h, pfa, kind, n_guard, n_train, 0, &a.alpha, st))) return rc;
+  if ((rc = start_args(a, h, d_map, d_metrics, n_cpi, min_delay, min_doppler, d_hits, cap, d_count, st))) return rc;
+  a.delayAxis = nullptr; // the engine's own axis: delayMin + j
+  a.nGuard = n_guard; a.nTrain = n_train;
+  if ((rc = tic(h, BLAH2HIP_K_CFAR, st))) return rc;
+  rc = launch_rows(gocfar1d_kernel<true>, gocfar1d_kernel<false>, ga, a.nD, a.nDelay, n_cpi, st);
+  return rc ? rc : toc(h, BLAH2HIP_K_CFAR, st);
+}
+
+int blah2hip_gocfar1d_prepare(blah2hip_amb_t h, double pfa, uint32_t kind, int32_t n_guard, int32_t n_train)
+{
+  if (!h) return fail(BLAH2HIP_ERR_INVALID, "NULL handle");
+  int rc;
+  if ((rc = check_1d(n_guard, n_train, 0)) || (rc = gocfar_check(h, pfa, kind))) return rc;
+  HIPCHK(hipSetDevice(h->device));
+  const double *d = nullptr;
+  return gocfar_table(h, pfa, kind, n_guard, n_train, 0, &d, nullptr, true);
+}
+
+int blah2hip_gocfar1d_process(blah2hip_amb_t h, uint32_t cpi, double pfa, uint32_t kind, int32_t n_guard, int32_t n_train,
+                              int32_t min_delay, double min_doppler, double *delay, double *doppler, double *snr, uint32_t cap,
+                              uint32_t *count)
+{
+  return process_one(h, cpi, delay, doppler, snr, cap, count, [&](const cf *m, const double *met) {
+    return blah2hip_gocfar1d_dev(h, m, met, 1, pfa, kind, n_guard, n_train, min_delay, min_doppler, h->d_hits, h->hitCap,
+                                 h->d_count, h->stream);
+  });
+}
+
+int blah2hip_gocfar2d_dev(blah2hip_amb_t h, const void *d_map, const double *d_metrics, uint32_t n_cpi, double pfa, uint32_t kind,
+                          int32_t ngd, int32_t ntd, int32_t n_rows_doppler, int32_t min_delay, double min_doppler,
+                          blah2hip_hit_t *d_hits, uint32_t cap, uint32_t *d_count, void *stream)
+{
+  int rc;
+  if ((rc = check_dev(h, d_hits, d_count, n_cpi)) || (rc = gocfar2d_check(ngd, ntd, n_rows_doppler, min_delay)) ||
+      (rc = gocfar_check(h, pfa, kind)))
+    return rc;
+  HIPCHK(hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  GoCfar2dArgs ga;
+  Cfar2dArgs &a = ga.d;
+  ga.kind = kind;
+  if ((rc = gocfar_table(h, pfa, kind, ngd, ntd, n_rows_doppler, &a.alpha, st))) return rc;
+  if ((rc = start_args(a, h, d_map, d_metrics, n_cpi, min_delay, min_doppler, d_hits, cap, d_count, st))) return rc;
+  a.sat = nullptr;
+  a.ngD = ngd; a.ntD = ntd; a.ngF = 0; a.ntF = n_rows_doppler;
+  const size_t lds = g2_lds_bytes(ngd + ntd, n_rows_doppler);
+  if (lds > 48 * 1024) LDSCFG(gocfar2d_kernel, g2_lds_bytes(C2T_MAX_HC, C2T_MAX_HR)); // once per (device, kernel): its largest use
+  if ((rc = tic(h, BLAH2HIP_K_CFAR, st))) return rc;
+  hipLaunchKernelGGL(gocfar2d_kernel, dim3((a.nDelay + G2_COLS - 1) / G2_COLS, (a.nD + G2_ROWS - 1) / G2_ROWS, n_cpi), dim3(256),
+                     lds, st, ga);
+  HIPCHK(hipGetLastError());
+  return toc(h, BLAH2HIP_K_CFAR, st);
+}
+
+int blah2hip_gocfar2d_prepare(blah2hip_amb_t h, double pfa, uint32_t kind, int32_t ngd, int32_t ntd, int32_t n_rows_doppler)
+{
+  if (!h) return fail(BLAH2HIP_ERR_INVALID, "NULL handle");
+  int rc;
+  if ((rc = gocfar2d_check(ngd, ntd, n_rows_doppler)) || (rc = gocfar_check(h, pfa, kind))) return rc;
+  HIPCHK(hipSetDevice(h->device));
+  const double *d = nullptr;
+  return gocfar_table(h, pfa, kind, ngd, ntd, n_rows_doppler, &d, nullptr, true);
+}
+
+int blah2hip_gocfar2d_process(blah2hip_amb_t h, uint32_t cpi, double pfa, uint32_t kind, int32_t ngd, int32_t ntd,
+                              int32_t n_rows_doppler, int32_t min_delay, double min_doppler, double *delay, double *doppler,
+                              double *snr, uint32_t cap, uint32_t *count)
+{
+  return process_one(h, cpi, delay, doppler, snr, cap, count, [&](const cf *m, const double *met) {
+    return blah2hip_gocfar2d_dev(h, m, met, 1, pfa, kind, ngd, ntd, n_rows_doppler, min_delay, min_doppler, h->d_hits,
                                  h->hitCap, h->d_count, h->stream);
   });
 }

@@ -502,6 +502,185 @@ def oscfar_hits(map, delay, doppler, noise_power, alpha, rank, window, min_delay
     return row.astype(np.int32), col.astype(np.int32), snr
 
 
+def gocfar_kind(kind):
+    """``"go"`` / ``"so"`` (or the library's 1 / 2) as the library's number: BLAH2HIP_CFAR_GO, BLAH2HIP_CFAR_SO."""
+    k = {"go": _lib.CFAR_GO, "so": _lib.CFAR_SO}.get(kind.lower()) if isinstance(kind, str) else kind
+    if isinstance(k, bool) or k not in (_lib.CFAR_GO, _lib.CFAR_SO):
+        raise ValueError(f"kind {kind!r}: 'go' or 'so'")
+    return int(k)
+
+
+def _goso_t(alpha, a, b):
+    """``E[exp(-alpha U); U < V]`` for ``U = Gamma(a) / a``, ``V = Gamma(b) / b``: ``sum_{j<b} C(a-1+j, j) (b/a)^j s^-(a+j)``
+    with ``s = 1 + (alpha + b) / a``, term by term in the log domain with the library's operations."""
+    import math
+    da, db = float(a), float(b)
+    ls = math.log(1.0 + (alpha + db) / da)
+    lr = math.log(db / da) - ls
+    lg = -da * ls
+    s = math.exp(lg)
+    for j in range(1, b):
+        lg += math.log((da - 1.0 + float(j)) / float(j)) + lr
+        s += math.exp(lg)
+    return s
+
+
+def _goso_tail(alpha, a, b):
+    """``E[exp(-alpha U); U > V]``: the series of :func:`_goso_t` from ``j = b`` on (the whole series sums to
+    ``(1 + alpha/a)^-a``), positive falling terms until what is left is below 1e-17 of the sum; the library's operations."""
+    import math
+    da, db = float(a), float(b)
+    sv = 1.0 + (alpha + db) / da
+    ls = math.log(sv)
+    lr = math.log(db / da) - ls
+    q = (db / da) / sv
+    lg = -da * ls
+    for j in range(1, b + 1):
+        lg += math.log((da - 1.0 + float(j)) / float(j)) + lr
+    s = math.exp(lg)
+    for j in range(b + 1, b + 100000000):
+        f = (da - 1.0 + float(j)) / float(j)
+        lg += math.log(f) + lr
+        t, r = math.exp(lg), f * q
+        s += t
+        if not t * r > (1.0 - r) * 1e-17 * s:
+            break
+    return s
+
+
+def gocfar_pfa(alpha, kind, a, b):
+    """The false-alarm probability of the greatest-of / smallest-of rule with factor ``alpha`` over halves of ``a >= 1``
+    and ``b >= 1`` training cells of one-look noise (include/blah2hip.h): smallest-of ``T(a, b) + T(b, a)``, greatest-of
+    ``(1 + alpha/a)^-a + (1 + alpha/b)^-b`` minus that, summed as the tails of the two series (no cancellation).  Pure
+    Python, the library's order of operations."""
+    kind, a, b, alpha = gocfar_kind(kind), int(a), int(b), float(alpha)
+    if a < 1 or b < 1:
+        raise ValueError("a and b: at least one cell each")
+    if a > b:
+        a, b = b, a
+    if kind == _lib.CFAR_SO:
+        return _goso_t(alpha, a, b) + _goso_t(alpha, b, a)
+    return _goso_tail(alpha, a, b) + _goso_tail(alpha, b, a)
+
+
+def gocfar_alpha(pfa, kind, a, b):
+    """blah2hip_gocfar_alpha restated in pure Python for one pair: ``gocfar_pfa(alpha, kind, a, b) = pfa`` by bisection
+    until the interval no longer splits (its upper end); with one half empty the cell-averaging factor of the other,
+    ``n (pfa^(-1/n) - 1)``; NaN for ``(0, 0)``."""
+    import math
+    pfa, kind, a, b = float(pfa), gocfar_kind(kind), int(a), int(b)
+    if not 0.0 < pfa < 1.0:
+        raise ValueError("pfa outside (0, 1)")
+    if a < 0 or b < 0:
+        raise ValueError("a and b: not negative")
+    if a == 0 and b == 0:
+        return math.nan
+    if a == 0 or b == 0:
+        n = a + b
+        return n * (math.pow(pfa, -1.0 / n) - 1)
+    lo, hi = 0.0, 1.0
+    while gocfar_pfa(hi, kind, a, b) > pfa:
+        hi *= 2.0
+    while True:
+        mid = 0.5 * (lo + hi)
+        if mid == lo or mid == hi:
+            return hi
+        if gocfar_pfa(mid, kind, a, b) > pfa:
+            lo = mid
+        else:
+            hi = mid
+
+
+def gocfar_alpha_table(pfa, kind, a, b):
+    """blah2hip_gocfar_alpha itself (host arithmetic of the library, no GPU touched) for the pairs ``(a[i], b[i])``:
+    float64 ``[len(a)]``."""
+    a = np.ascontiguousarray(np.atleast_1d(a), dtype=np.uint32)
+    b = np.ascontiguousarray(np.atleast_1d(b), dtype=np.uint32)
+    if a.shape != b.shape or a.ndim != 1:
+        raise ValueError("a and b: two lists of one length")
+    out = np.empty(a.size, dtype=np.float64)
+    check(_lib.load().blah2hip_gocfar_alpha(float(pfa), gocfar_kind(kind), a.size, _ptr(a), _ptr(b), _ptr(out)))
+    return out
+
+
+def gocfar_window(window):
+    """``(nGuard, nTrain, nRowsDoppler)`` of a 1-D ``(nGuard, nTrain)`` or a 2-D window."""
+    w = tuple(int(v) for v in window)
+    if len(w) == 2:
+        w = (w[0], w[1], 0)
+    if len(w) != 3 or min(w) < 0:
+        raise ValueError("window: (nGuard, nTrain) or (nGuardDelay, nTrainDelay, nRowsDoppler)")
+    return w
+
+
+def gocfar_counts(n_doppler, n_delay, window):
+    """``(a, b)`` int64 ``[nD, nC]``: the cells of the leading and the lagging half of every cell's window (in-bounds cells,
+    never delay column 0 in the leading half)."""
+    g, t, hR = gocfar_window(window)
+    i, j = np.arange(int(n_doppler)), np.arange(int(n_delay))
+    rows = np.minimum(i + hR, n_doppler - 1) - np.maximum(i - hR, 0) + 1
+    lead = np.maximum(np.minimum(j - g, n_delay) - np.maximum(j - g - t, 1), 0)
+    lag = np.maximum(np.minimum(j + g + t + 1, n_delay) - np.minimum(j + g + 1, n_delay), 0)
+    return rows[:, None] * lead[None, :], rows[:, None] * lag[None, :]
+
+
+def gocfar_hits(map, delay, doppler, noise_power, alpha, kind, window, min_delay=-128, min_doppler=0.0):
+    """The greatest-of / smallest-of detectors' rule restated in fp64 NumPy for one map ``[nD, nC]`` with its axes
+    (include/blah2hip.h).  ``p = re^2 + im^2``; the halves of cell ``(i, j)`` are the columns ``j - nG - nT .. j - nG - 1``
+    (never column 0) and ``j + nG + 1 .. j + nG + nT`` inside the map, over the rows ``i - hR .. i + hR`` inside it; per
+    column the rows are added in ascending order from 0.0, then the columns in ascending order from 0.0.  Both halves
+    occupied: ``p_c > alpha mu_A`` and (greatest-of) / or (smallest-of) ``p_c > alpha mu_B``; one empty: the averaging
+    rule over the other with the factor ``alpha`` gives for ``(a, 0)``; both: no hit.  ``alpha``: a callable
+    ``alpha(a, b)`` or a dictionary over ``(a, b)``.  ``window``: ``(nGuard, nTrain)`` or ``(nGuardDelay, nTrainDelay,
+    nRowsDoppler)``.  Returns ``(row, col, snr)`` in row-major order, ``snr = 5 log10(p) - noise_power``."""
+    kind = gocfar_kind(kind)
+    g, t, hR = gocfar_window(window)
+    hC = g + t
+    m = np.asarray(map)
+    re, im = m.real.astype(np.float64), m.imag.astype(np.float64)
+    p = re * re + im * im
+    nD, nC = p.shape
+    a, b = gocfar_counts(nD, nC, (g, t, hR))
+    P = np.zeros((nD + 2 * hR, nC + 2 * hC))  # a cell that does not train adds an exact 0.0
+    P[hR:hR + nD, hC + 1:hC + nC] = p[:, 1:]
+    with np.errstate(all="ignore"):
+        Csum = np.zeros((nD, nC + 2 * hC))
+        for r in range(2 * hR + 1):
+            Csum = Csum + P[r:r + nD]
+        SA, SB = np.zeros((nD, nC)), np.zeros((nD, nC))
+        for c in range(t):
+            SA = SA + Csum[:, c:c + nC]
+        for c in range(t):
+            SB = SB + Csum[:, hC + g + 1 + c:hC + g + 1 + c + nC]
+        pairs = np.unique(np.stack([a.ravel(), b.ravel()], axis=1), axis=0)
+        al = np.full((nD, nC), np.nan)
+        for x, y in pairs.tolist():
+            if x or y:
+                v = alpha(x, y) if callable(alpha) else alpha[(x, y)]
+                al[(a == x) & (b == y)] = float(v)
+        one = (a == 0) != (b == 0)
+        both = (a > 0) & (b > 0)
+        hitA = p > al * (SA / a.astype(np.float64))
+        hitB = p > al * (SB / b.astype(np.float64))
+        single = p > al * (np.where(a > 0, SA, SB) / (a + b).astype(np.float64))
+        two = (hitA & hitB) if kind == _lib.CFAR_GO else (hitA | hitB)
+        tested = ~(np.abs(np.asarray(doppler, dtype=np.float64)) < float(min_doppler))[:, None] \
+            & (np.asarray(delay) >= int(min_delay))[None, :]
+        hit = tested & ((both & two) | (one & single))
+        row, col = np.nonzero(hit)
+        snr = 5.0 * np.log10(p[row, col]) - float(noise_power)
+    return row.astype(np.int32), col.astype(np.int32), snr
+
+
+def gocfar_table_for(pfa, kind, n_doppler, n_delay, window):
+    """The library's factors (:func:`gocfar_alpha_table`) for every pair a map of this shape gives under ``window``, as the
+    dictionary :func:`gocfar_hits` takes."""
+    a, b = gocfar_counts(n_doppler, n_delay, window)
+    pairs = np.unique(np.stack([a.ravel(), b.ravel()], axis=1), axis=0)
+    al = gocfar_alpha_table(pfa, kind, pairs[:, 0], pairs[:, 1])
+    return {(int(x), int(y)): float(v) for (x, y), v in zip(pairs.tolist(), al)}
+
+
 def clutter_map_weights(age, memory):
     """The weights ``c_i`` of the clutter map's average ``b = sum_i c_i u_i`` at age ``age >= 1`` (the CPIs absorbed) with
     memory ``T``, newest value first: ``age`` times ``1 / age`` while ``age <= T``; beyond, ``w (1 - w)^m`` for
@@ -1896,6 +2075,64 @@ class OsCfarDetector2D(_OsCfar):
 
     def _args(self):
         return (self.pfa, self.rank_permille, *self.p, self.minDelay, self.minDoppler)
+
+    def process(self, x: Map, amb=None) -> Detection:
+        return self._process_any(x, amb)
+
+
+class _GoCfar(_OsCfar):
+    """The greatest-of / smallest-of detectors: a kind, one look per cell, and :class:`_OsCfar`'s ``process``."""
+
+    def _init_kind(self, kind, looks):
+        if int(looks) != 1:
+            raise ValueError("looks: the greatest-of / smallest-of thresholds are made for one look per cell")
+        self.kind = gocfar_kind(kind)
+
+
+class GoCfarDetector1D(_GoCfar):
+    """Greatest-of (``kind="go"``) or smallest-of (``"so"``) CFAR along delay (blah2hip_gocfar1d_*): the geometry of
+    :class:`CfarDetector1D`, the cell against the mean of each half of its window on its own.  No reference class.
+    :func:`gocfar_hits` is the same rule in NumPy."""
+
+    _entry = "blah2hip_gocfar1d"
+
+    def __init__(self, pfa, nGuard, nTrain, minDelay, minDoppler, kind="go", looks=1):
+        self._init(pfa, minDelay, minDoppler, looks, (("nGuard", nGuard), ("nTrain", nTrain), ("minDelay", minDelay)))
+        self._init_kind(kind, looks)
+        self.nGuard, self.nTrain = int(nGuard), int(nTrain)
+
+    def _args(self):
+        return (self.pfa, self.kind, self.nGuard, self.nTrain, self.minDelay, self.minDoppler)
+
+    def prepare(self, amb):
+        """Build and pin the table on ``amb`` (blah2hip_gocfar1d_prepare): the call to make before capturing a graph."""
+        amb.set_cfar_looks(self.looks)
+        check(amb._L.blah2hip_gocfar1d_prepare(amb._h, self.pfa, self.kind, self.nGuard, self.nTrain))
+
+    def process(self, x: Map, amb=None) -> Detection:
+        """On the engine's device copy while ``x`` still is that map, else on an upload of ``x.data`` (``amb``: the handle
+        that gives the geometry when the map has no owner)."""
+        return self._process_any(x, amb)
+
+
+class GoCfarDetector2D(_GoCfar):
+    """Greatest-of / smallest-of CFAR with the halves of :class:`GoCfarDetector1D` averaged over ``nRowsDoppler`` rows on
+    either side (blah2hip_gocfar2d_*); with ``nRowsDoppler = 0`` it returns what the 1-D detector returns.  Windows beyond
+    ``nRowsDoppler <= 24``, ``nGuardDelay + nTrainDelay <= 40`` are refused (ERR_UNSUPPORTED)."""
+
+    _entry = "blah2hip_gocfar2d"
+
+    def __init__(self, pfa, nGuardDelay, nTrainDelay, nRowsDoppler, minDelay, minDoppler, kind="go", looks=1):
+        self._init(pfa, minDelay, minDoppler, looks)
+        self._init_kind(kind, looks)
+        self.p = [int(nGuardDelay), int(nTrainDelay), int(nRowsDoppler)]
+
+    def _args(self):
+        return (self.pfa, self.kind, *self.p, self.minDelay, self.minDoppler)
+
+    def prepare(self, amb):
+        amb.set_cfar_looks(self.looks)
+        check(amb._L.blah2hip_gocfar2d_prepare(amb._h, self.pfa, self.kind, *self.p))
 
     def process(self, x: Map, amb=None) -> Detection:
         return self._process_any(x, amb)

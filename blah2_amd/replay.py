@@ -614,7 +614,9 @@ class GpuChain:
 
     ``cfg["detection"]["cfar"] = "os"`` (default "ca") builds :class:`blah2_amd.OsCfarDetector1D` at
     ``cfg["detection"]["rank"]`` (default 0.75) in the place of ``CfarDetector1D``, for the integrator's looks as well; the
-    hit buffers, the finisher and the results are the same.
+    hit buffers, the finisher and the results are the same.  ``"goca"`` / ``"soca"`` build
+    :class:`blah2_amd.GoCfarDetector1D` (greatest-of / smallest-of) there; their thresholds are made for one look per cell,
+    so with ``integrate`` or several carriers the plan raises a ValueError that names ``detection.cfar``.
 
     ``cfg["detection"]["clutterMap"] = {"memory": T, "mode": "gate" | "detect"}`` puts a
     :class:`blah2_amd.ClutterMapDetector` of memory T CPIs (normalised, at the detector's pfa -- ``pfa / K`` behind a rate
@@ -791,7 +793,8 @@ class GpuChain:
         if p.cfar_kind:
             args = (p.pfa, det_c["nGuard"], det_c["nTrain"], det_c["minDelay"], det_c["minDoppler"])
             self.cfar = (b2.OsCfarDetector1D(*args, rank=p.rank, **looks) if p.cfar_kind == "os" else
-                         b2.CfarDetector1D(*args, **looks))  # both leave the same hit lists
+                         b2.GoCfarDetector1D(*args, kind=p.cfar_kind[:2], **looks) if p.cfar_kind in ("goca", "soca") else
+                         b2.CfarDetector1D(*args, **looks))  # all leave the same hit lists
             if p.cmap:
                 self.cmap = self._own(b2.ClutterMapDetector(amb, p.pfa, p.cmap[0], det_c["minDelay"], det_c["minDoppler"]))
                 self.cmap_mode = p.cmap[1]
@@ -1388,7 +1391,9 @@ def main(argv=None):
                          "maximum over K hypotheses multiplies the false-alarm rate by at most K, so the detector is made with "
                          "pfa / K (the union bound).  Overrides process.ambiguity.dopplerRate (QMAX or {max: QMAX, step: STEP})")
     ap.add_argument("--cfar", default=None, metavar="KIND[:RANK]",
-                    help="the detector: ca (cell averaging, the reference's) or os[:RANK] (ordered statistic: the threshold "
+                    help="the detector: ca (cell averaging, the reference's), goca / soca (greatest-of / smallest-of: the cell "
+                         "against the mean of each half of its window, for clutter edges / for echoes in each other's window) "
+                         "or os[:RANK] (ordered statistic: the threshold "
                          "from the RANK-th part of the sorted training cells, default 0.75); overrides "
                          "process.detection.cfar / .rank of the config")
     ap.add_argument("--clutter-map", default=None, metavar="T[:detect]",
@@ -1511,10 +1516,10 @@ def main(argv=None):
     if a.cfar is not None:
         kind, _, rank_ = a.cfar.partition(":")
         try:
-            if kind not in ("ca", "os") or (rank_ and (kind != "os" or not 0.001 <= float(rank_) <= 1.0)):
+            if kind not in ("ca", "os", "goca", "soca") or (rank_ and (kind != "os" or not 0.001 <= float(rank_) <= 1.0)):
                 raise ValueError
         except ValueError:
-            ap.error("--cfar takes ca, os or os:RANK with RANK in [0.001, 1]")
+            ap.error("--cfar takes ca, goca, soca, os or os:RANK with RANK in [0.001, 1]")
         cfg["detection"] = det_(cfar=kind, **({"rank": float(rank_)} if rank_ else {}))
     if a.clutter_map is not None:
         cfg["detection"] = det_(clutterMap=parsed("clutter_map", "T or T:detect (T:gate is the default), T a memory of 1 .. 64 CPIs",

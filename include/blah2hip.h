@@ -870,6 +870,78 @@ int blah2hip_oscfar2d_process(blah2hip_amb_t h, uint32_t cpi, double pfa, uint32
                               double min_doppler, double *delay, double *doppler, double *snr, uint32_t cap,
                               uint32_t *count);
 
+/* ---- Greatest-of and smallest-of CFAR (GO-CFAR, Hansen and Sawyers; SO-CFAR, Trunk; NOT in the reference) -------
+ * The averaging detectors take one mean over both sides of the cell under test.  At a clutter edge -- the end of the clutter
+ * filter's lag span, the flank of the direct-path residue -- half of the window lies in the weak region, the mean is too low
+ * and the cells just inside the strong region are reported as noise; greatest-of thresholds against the larger half.  Two
+ * echoes in each other's window raise each other's mean; smallest-of thresholds against the smaller half, one of which is
+ * clean (the ordered-statistic detectors do that at several times the cost).  With p = re^2 + im^2 in fp64 from the fp32
+ * parts, formed as the detectors above form it, and kind BLAH2HIP_CFAR_GO or BLAH2HIP_CFAR_SO:
+ *
+ * 1-D, geometry and quirks of blah2hip_cfar1d_*.  For cell (i, j) of a row with nC delay bins
+ *   leading set  A = { k : j - nG - nT <= k < j - nG,  0 < k < nC }      (delay column 0 never trains)
+ *   lagging set  B = { k : j + nG < k <= j + nG + nT,  0 <= k < nC }
+ *   a = |A|, b = |B|;  S_A, S_B: fp64 sums started at 0.0 and taken in ascending k;  mu_A = S_A / (double)a, mu_B = S_B / (double)b
+ *   a >= 1 and b >= 1, alpha = alpha(kind; a, b):   GO hits  <=>  p_c > alpha mu_A  and  p_c > alpha mu_B
+ *                                                   SO hits  <=>  p_c > alpha mu_A  or   p_c > alpha mu_B
+ *     each threshold one fp64 multiply and one compare; no max or min is formed.  The rule is the contract and fixes the
+ *     special values: a NaN half never supports a hit, a NaN cell under test never hits, an all-zero map has no hits.
+ *   exactly one half empty: the cell-averaging rule over the other,  p_c > alpha_ca[a + b] (S / (a + b)),  alpha_ca
+ *     blah2hip_cfar_alpha's one-look value;   both empty: no hit.
+ * The min_delay / min_doppler skips, the hit records, snr = 5 log10(p_c) - noisePower, the count > cap behaviour and the
+ * emission order of _process are those of blah2hip_cfar1d_*.
+ *
+ * 2-D: the halves are split along delay and each is averaged over the window's Doppler extent, n_rows_doppler = hR rows on
+ * either side.  Rows [i - hR, i + hR] in [0, nD); leading columns [j - nGd - nTd, j - nGd - 1] in [1, nC); lagging columns
+ * [j + nGd + 1, j + nGd + nTd] in [0, nC); the columns j - nGd .. j + nGd train in no row (the cell's own Doppler sidelobes
+ * stay out of both halves).  a = rows colsLeading, b = rows colsLagging.  The sums have a fixed order, so the decision is
+ * reproducible bit for bit: per column C[k] = sum of p[ii][k] over the rows in ascending ii, started at 0.0, then S = sum of
+ * C[k] in ascending k, started at 0.0 -- no sliding add-and-subtract and no summed-area table (different bits, and small
+ * windows lost beside tall cells).  With hR = 0 the detector reports exactly the 1-D detector's hits.  hR <= 24 and
+ * nGd + nTd <= 40; a wider window is BLAH2HIP_ERR_UNSUPPORTED.
+ *
+ * Threshold factors, one look.  Under noise of unit power the cell is Exp(1), U = Gamma(a) / a, V = Gamma(b) / b, and
+ *   T(alpha; a, b) = E[e^(-alpha U); U < V] = sum_{j=0}^{b-1} C(a-1+j, j) (b/a)^j s^-(a+j),   s = 1 + (alpha + b) / a
+ *   Pfa_SO(alpha; a, b) = T(alpha; a, b) + T(alpha; b, a)
+ *   Pfa_GO(alpha; a, b) = (1 + alpha/a)^-a + (1 + alpha/b)^-b - Pfa_SO(alpha; a, b)
+ *                       = T'(alpha; a, b) + T'(alpha; b, a),   T' the series of T from j = b on (the whole series sums to
+ *                         (1 + alpha/a)^-a): this form is the one evaluated, positive terms until what is left is below
+ *                         1e-17 of the sum -- with uneven halves and a small pfa the difference above loses eight digits
+ * T term by term in the log domain (the ratio of consecutive terms is ((a-1+j)/j) (b/a) / s); for a = b = n it is the textbook
+ * 2 sum_k C(n-1+k, k) (2 + alpha/n)^-(n+k).  alpha solves Pfa = pfa by bisection in fp64 until the interval no longer splits
+ * (its upper end), after bracketing by doubling, and back-substitutes to pfa within 1e-10 of it; alpha(a, b) = alpha(b, a).
+ * pfa 1e-3: alpha_GO(8, 8) = 7.487313, alpha_SO(8, 8) = 12.599715 (averaging over the 16: 8.638824); alpha_GO(3, 8) =
+ * 8.211435, alpha_SO(3, 8) = 27.069698; alpha_GO(1, 1) = (-3 + sqrt(8001)) / 2, alpha_SO(1, 1) = 1998.
+ * blah2hip_gocfar_alpha: host arithmetic only (no GPU is touched): alpha[i] for the pair (a[i], b[i]), i < n_pairs; a pair
+ * with one zero gets the averaging value of the other half, the pair (0, 0) NaN.  BLAH2HIP_ERR_INVALID: a NULL pointer, an
+ * unknown kind, pfa outside (0, 1).
+ *
+ * The entry points take their averaging detector's arguments with `kind` after pfa (the 2-D ones n_rows_doppler in the place
+ * of the two Doppler sizes; _prepare takes n_guard too, because the table holds the pairs the map's geometry reaches under
+ * the window).  The tables live in a cache of their own keyed by (pfa, kind, window) for the handle's map geometry, with the
+ * rules of the averaging detectors' cache (eight unpinned entries, least recently used first out, _prepare pins, a miss
+ * while the stream is being captured is refused), which these calls do not touch.  Timing counts under BLAH2HIP_K_CFAR.
+ * The factors are made for one look per cell: a call while BLAH2HIP_OPT_CFAR_LOOKS is above 1 is BLAH2HIP_ERR_UNSUPPORTED
+ * (the Gamma(L) form is a double sum whose cost does not fit a table build).  Every refusal writes nothing. */
+#define BLAH2HIP_CFAR_GO 1
+#define BLAH2HIP_CFAR_SO 2
+int blah2hip_gocfar_alpha(double pfa, uint32_t kind, uint32_t n_pairs, const uint32_t *a, const uint32_t *b, double *alpha);
+int blah2hip_gocfar1d_dev(blah2hip_amb_t h, const void *d_map, const double *d_metrics, uint32_t n_cpi, double pfa, uint32_t kind,
+                          int32_t n_guard, int32_t n_train, int32_t min_delay, double min_doppler, blah2hip_hit_t *d_hits,
+                          uint32_t cap, uint32_t *d_count, void *stream);
+int blah2hip_gocfar1d_prepare(blah2hip_amb_t h, double pfa, uint32_t kind, int32_t n_guard, int32_t n_train);
+int blah2hip_gocfar1d_process(blah2hip_amb_t h, uint32_t cpi, double pfa, uint32_t kind, int32_t n_guard, int32_t n_train,
+                              int32_t min_delay, double min_doppler, double *delay, double *doppler, double *snr, uint32_t cap,
+                              uint32_t *count);
+int blah2hip_gocfar2d_dev(blah2hip_amb_t h, const void *d_map, const double *d_metrics, uint32_t n_cpi, double pfa, uint32_t kind,
+                          int32_t n_guard_delay, int32_t n_train_delay, int32_t n_rows_doppler, int32_t min_delay,
+                          double min_doppler, blah2hip_hit_t *d_hits, uint32_t cap, uint32_t *d_count, void *stream);
+int blah2hip_gocfar2d_prepare(blah2hip_amb_t h, double pfa, uint32_t kind, int32_t n_guard_delay, int32_t n_train_delay,
+                              int32_t n_rows_doppler);
+int blah2hip_gocfar2d_process(blah2hip_amb_t h, uint32_t cpi, double pfa, uint32_t kind, int32_t n_guard_delay,
+                              int32_t n_train_delay, int32_t n_rows_doppler, int32_t min_delay, double min_doppler,
+                              double *delay, double *doppler, double *snr, uint32_t cap, uint32_t *count);
+
 /* ---- Clutter-map CFAR (Nitzberg; NOT in the reference) and the gate behind the spatial detectors -------
  * The detectors above compare a cell with its neighbours in the same map, so whatever stands out from its surroundings
  * is reported in every CPI: a clutter discrete the filter left, the direct path's residue, an interferer's Doppler line.
