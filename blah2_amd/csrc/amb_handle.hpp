@@ -8,6 +8,7 @@
 
 #include "blah2hip.h"
 #include "range_core.hpp"
+#include "table_cache.hpp"
 #include "timing.hpp"
 
 #include <algorithm>
@@ -108,14 +109,15 @@ struct blah2hip_amb_s {
 
   // ---- written by detect.hip; bearingGridLast by array.hip, taperGridLast by taper.hip, the migration and rate fields by walk.hip,
   // the carrier fields by carriers.hip
-  // a threshold table of detect.hip's cfar_table(); d: alpha[n + 1], then with a rank (permille) rank[n + 1] words; pinned:
-  // handed out by *_prepare, never evicted.  Two lists, each with its own budget; destroy (capi.hip) frees both.
-  struct CfarTable { double pfa; uint32_t looks, rank; size_t n; double *d; bool pinned; };
-  std::vector<CfarTable> alphaTables; // cell averaging (rank 0): one per (pfa, looks, size) seen
-  std::vector<CfarTable> osTables;    // ordered statistic: one per (pfa, looks, rank_permille, size) seen
-  // a greatest-of / smallest-of table of detect.hip's gocfar_table(): (2 hR + 1)(nT + 1)^2 factors for this handle's maps
-  struct GoTable { double pfa; uint32_t kind; int32_t nG, nT, hR; double *d; bool pinned; };
-  std::vector<GoTable> goTables;      // one per (pfa, kind, nGuard, nTrain, hR) seen; its own budget, freed by destroy
+  // The detectors' threshold tables on the device: three lists under the one policy of table_cache.hpp (eight unpinned
+  // tables each, what *_prepare handed out is pinned and never evicted), filled by detect.hip, freed by destroy (capi.hip).
+  // An averaging or ordered-statistic table is alpha[n + 1], then with a rank (permille) rank[n + 1] words; a greatest-of /
+  // smallest-of table is (2 hR + 1)(nT + 1)^2 factors for this handle's maps.
+  struct CfarKey { double pfa; uint32_t looks, rank; size_t n; };
+  struct GoKey { double pfa; uint32_t kind; int32_t nG, nT, hR; };
+  blah2::TableCache<CfarKey> alphaTables; // cell averaging (rank 0): one per (pfa, looks, size) seen
+  blah2::TableCache<CfarKey> osTables;    // ordered statistic: one per (pfa, looks, rank_permille, size) seen
+  blah2::TableCache<GoKey> goTables;      // one per (pfa, kind, nGuard, nTrain, hR) seen
   double *d_sat = nullptr;          // 2-D CFAR summed-area table [max_batch][nD+1][nDelay+1], allocated at its first use
   blah2hip_hit_t *d_hits = nullptr; // the *_process calls' hit list, grown to the map's cell count
   uint32_t hitCap = 0;
@@ -175,6 +177,20 @@ static inline int toc(blah2hip_amb_s *h, int k, hipStream_t st)
   HIPCHK(h->timer.toc(k, st));
   return BLAH2HIP_OK;
 }
+
+// table_cache.hpp's device: HIP on the current device
+struct HipTableDevice {
+  static const char *text(hipError_t e) { return e == hipSuccess ? nullptr : hipGetErrorString(e); }
+  const char *alloc(size_t bytes, double **d) { return text(hipMalloc(d, bytes)); }
+  const char *upload(double *d, const double *host, size_t bytes) { return text(hipMemcpy(d, host, bytes, hipMemcpyHostToDevice)); }
+  bool free(double *d) { return hipFree(d) == hipSuccess; }
+  const char *synchronize() { return text(hipDeviceSynchronize()); }
+  bool capturing(void *stream)
+  {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    return hipStreamIsCapturing((hipStream_t)stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
+  }
+};
 
 // whether the byte ranges [a, a + na) and [b, b + nb) share a byte: what the calls with caller-owned outputs refuse
 static inline bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)

@@ -1030,12 +1030,10 @@ int blah2hip_amb_destroy(blah2hip_amb_t h)
                   (void *)h->d_bf, (void *)h->d_bfn, (void *)h->d_H, (void *)h->d_dopW64, (void *)h->d_hotCount, (void *)h->d_firK0,
                   (void *)h->d_detWords, (void *)h->d_rangeWalk, (void *)h->d_migrate, (void *)h->d_rates, h->d_carriers})
     if (p) (void)hipFree(p);
-  for (auto &t : h->alphaTables)
-    if (t.d) (void)hipFree(t.d);
-  for (auto &t : h->osTables)
-    if (t.d) (void)hipFree(t.d);
-  for (auto &t : h->goTables)
-    if (t.d) (void)hipFree(t.d);
+  HipTableDevice dev;
+  h->alphaTables.free_all(dev);
+  h->osTables.free_all(dev);
+  h->goTables.free_all(dev);
   if (h->h_pin) (void)hipHostFree(h->h_pin);
   leak_clear(h);
   h->timer.destroy();

@@ -39,51 +39,85 @@ struct CfarArgs {
   uint32_t cap;
 };
 
-// STAGED = false: rows longer than the LDS holds as fp64 (more than 19 k delay bins; blah2hip_cfar1d_map on a host-built
-// map): the same window sums with |z|^2 formed straight from the L2-resident row.
-template <bool STAGED>
-__global__ void cfar1d_kernel(CfarArgs a)
+// |z|^2 in fp64: |z*z| (:47)
+__device__ __forceinline__ double cell_power(cf c) { return (double)c.x * (double)c.x + (double)c.y * (double)c.y; }
+
+// One record through the CPI's atomic counter; a record beyond `cap` is counted and not stored.  p = |z|^2, so the
+// reference's 10 log10|z| - noisePower (:48) is 5 log10 p - noise.
+__device__ __forceinline__ void append_hit(blah2hip_hit_t *hits, uint32_t *count, uint32_t cap, int cpi, int row, int col, double p,
+                                           double noise)
+{
+  const uint32_t slot = atomicAdd(&count[cpi], 1u);
+  if (slot < cap) {
+    blah2hip_hit_t h;
+    h.row = row;
+    h.col = col;
+    h.snr = 5.0 * log10(p) - noise;
+    hits[(size_t)cpi * cap + slot] = h;
+  }
+}
+
+// The 1-D detectors' skeleton (cfar1d_kernel, oscfar1d_kernel, gocfar1d_kernel), one workgroup per Doppler row: rows with
+// |doppler| < minDoppler and cells with delay < minDelay are not tested (:40, :53); the cell's two runs of training cells
+// are clipped to the row, [l0, l1) before the guard -- never column 0: leading cells need k > 0 (:61) -- and [t0, t1) behind
+// it (trailing k >= 0, :68), either one possibly empty (l1 <= l0, t1 == t0).  rule(l0, l1, t0, t1, sqv, j) decides: sqv(k)
+// is |z|^2 of cell k of the row, j the cell under test.
+// STAGED: |z|^2 of the row in LDS as fp64 (lanes read neighbouring doubles: no bank conflict); false: rows longer than the
+// LDS holds (more than 19 k delay bins; blah2hip_cfar1d_map on a host-built map), |z|^2 formed straight from the L2-resident
+// row.
+template <bool STAGED, class Rule>
+__device__ __forceinline__ void row_detect(const CfarArgs &a, Rule rule)
 {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   double *sq = reinterpret_cast<double *>(smem);
   const int row = blockIdx.x, cpi = blockIdx.y;
   if (fabs(a.doppler[row]) < a.minDoppler) return; // :40
   const cf *z = a.map + ((size_t)cpi * a.nD + row) * a.nDelay;
-  auto sqv = [&](int k) -> double {
-    if (STAGED) return sq[k];
-    const cf c = z[k];
-    return (double)c.x * (double)c.x + (double)c.y * (double)c.y;
-  };
+  auto sqv = [&](int k) -> double { return STAGED ? sq[k] : cell_power(z[k]); };
   if (STAGED) {
-    for (int j = threadIdx.x; j < a.nDelay; j += blockDim.x) {
-      const cf c = z[j];
-      sq[j] = (double)c.x * (double)c.x + (double)c.y * (double)c.y; // |z*z| (:47)
-    }
+    for (int j = threadIdx.x; j < a.nDelay; j += blockDim.x) sq[j] = cell_power(z[j]);
     __syncthreads();
   }
   const double noisePower = a.metrics[2 * cpi];
   for (int j = threadIdx.x; j < a.nDelay; j += blockDim.x) {
     if ((a.delayAxis ? a.delayAxis[j] : j + a.delayMin) < a.minDelay) continue; // :53  x->delay[j] < minDelay
-    int n = 0;
-    double tot = 0.0;
-    for (int k = j - a.nGuard - a.nTrain; k < j - a.nGuard; k++)
-      if (k > 0 && k < a.nDelay) { tot += sqv(k); n++; }
-    for (int k = j + a.nGuard + 1; k < j + a.nGuard + a.nTrain + 1; k++)
-      if (k >= 0 && k < a.nDelay) { tot += sqv(k); n++; }
-    if (n == 0) continue; // alpha = 0*inf = NaN in the reference: never exceeds
-    const double thr = a.alpha[n] * (tot / n);
-    const double sj = sqv(j);
-    if (sj > thr) {
-      const uint32_t slot = atomicAdd(&a.count[cpi], 1u);
-      if (slot < a.cap) {
-        blah2hip_hit_t h;
-        h.row = row;
-        h.col = j;
-        h.snr = 5.0 * log10(sj) - noisePower; // 10 log10|z| - noisePower (:48)
-        a.hits[(size_t)cpi * a.cap + slot] = h;
-      }
+    const int l0 = max(j - a.nGuard - a.nTrain, 1), l1 = min(j - a.nGuard, a.nDelay);                 // :61
+    const int t0 = min(j + a.nGuard + 1, a.nDelay), t1 = min(j + a.nGuard + a.nTrain + 1, a.nDelay); // :68
+    if (rule(l0, l1, t0, t1, sqv, j)) append_hit(a.hits, a.count, a.cap, cpi, row, j, sqv(j), noisePower);
+  }
+}
+
+// The LDS tile of oscfar2d_kernel and gocfar2d_kernel: |z|^2 as fp64 of the `rows` x HALO_COLS cells under test whose corner
+// is map cell (i0, j0) and of their halo, hR rows and hC columns on either side, at an odd row pitch.  A cell that does not
+// train -- outside the map, or in delay column 0 (:61) -- is written as `fill`.  Four waves: wave <-> every fourth row.
+constexpr int HALO_COLS = 64;
+__host__ __device__ inline int halo_pitch(int hC) { return (HALO_COLS + 2 * hC) | 1; }
+__device__ __forceinline__ void halo_fill(double *T, const cf *map, int nD, int nC, int i0, int j0, int rows, int hR, int hC, double fill,
+                                          int wave, int lane)
+{
+  const int SP = halo_pitch(hC), SC = HALO_COLS + 2 * hC, SR = rows + 2 * hR;
+  for (int r = wave; r < SR; r += 4) {
+    const int i = i0 - hR + r;
+    const bool rok = i >= 0 && i < nD;
+    for (int c = lane; c < SC; c += 64) {
+      const int j = j0 - hC + c;
+      T[r * SP + c] = rok && j >= 1 && j < nC ? cell_power(map[(size_t)i * nC + j]) : fill;
     }
   }
+}
+
+// Cell averaging: one sum over the leading, then the trailing cells, in ascending index from 0.0 (the reference's order)
+template <bool STAGED>
+__global__ void cfar1d_kernel(CfarArgs a)
+{
+  row_detect<STAGED>(a, [&](int l0, int l1, int t0, int t1, auto sqv, int j) {
+    const int n = max(l1 - l0, 0) + (t1 - t0);
+    if (n == 0) return false; // alpha = 0*inf = NaN in the reference: never exceeds
+    double tot = 0.0;
+    for (int k = l0; k < l1; k++) tot += sqv(k);
+    for (int k = t0; k < t1; k++) tot += sqv(k);
+    return sqv(j) > a.alpha[n] * (tot / n);
+  });
 }
 
 // --------------------------------------------------------------------------
@@ -123,8 +157,7 @@ __global__ __launch_bounds__(256) void sat_rows_kernel(Cfar2dArgs a)
     const int j = j0 + t;
     double val = 0.0;
     if (j < a.nDelay && j != 0) {
-      const cf c = z[j];
-      val = (double)c.x * (double)c.x + (double)c.y * (double)c.y;
+      val = cell_power(z[j]);
     }
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) {
@@ -188,10 +221,9 @@ __global__ __launch_bounds__(256) void cfar2d_kernel(Cfar2dArgs a)
   const double tot = box(R0, R1, C0, C1) - box(G0, G1, H0, H1);
   const int n = (R1 - R0) * cols(C0, C1) - (G1 - G0) * cols(H0, H1);
   if (n <= 0) return;
-  const cf c = a.map[((size_t)cpi * nD + i) * nC + j];
-  const double sq = (double)c.x * (double)c.x + (double)c.y * (double)c.y;
+  const double sq = cell_power(a.map[((size_t)cpi * nD + i) * nC + j]);
   if (sq > a.alpha[n] * (tot / n)) {
-    const uint32_t slot = atomicAdd(&a.count[cpi], 1u);
+    const uint32_t slot = atomicAdd(&a.count[cpi], 1u); // (append_hit with the level loaded behind the cap test)
     if (slot < a.cap) {
       blah2hip_hit_t h;
       h.row = i;
@@ -480,7 +512,7 @@ __global__ __launch_bounds__(64 * C2T_WAVES) void cfar2d_tile_kernel(Cfar2dTileA
         const double noise = a.metrics[2 * cpi];
         for (int m = 0; m < 8; m++) {
           if (!((hitMask >> m) & 1u)) continue;
-          const uint32_t slot = atomicAdd(&a.count[cpi], 1u);
+          const uint32_t slot = atomicAdd(&a.count[cpi], 1u); // (append_hit written out: the kernel's code stays as it was timed)
           if (slot < a.cap) {
             blah2hip_hit_t h;
             h.row = i0 + o + m;
@@ -691,9 +723,8 @@ __global__ __launch_bounds__(256) void cfar2d_stream_kernel(Cfar2dStreamArgs ta)
       for (int u = 0; u < U; u++) {
         if (!((hitRows >> u) & 1u)) continue;
         const int i = rb + u - HR;
-        const cf c = mapc[(size_t)i * nC + j];
-        const double cut = (double)c.x * (double)c.x + (double)c.y * (double)c.y;
-        const uint32_t slot = atomicAdd(&a.count[cpi], 1u);
+        const double cut = cell_power(mapc[(size_t)i * nC + j]);
+        const uint32_t slot = atomicAdd(&a.count[cpi], 1u); // (append_hit with the level loaded behind the cap test)
         if (slot < a.cap) {
           blah2hip_hit_t h;
           h.row = i;

@@ -62,6 +62,7 @@ __device__ __forceinline__ bool cmap_cell(cm_v2 z, bool norm, float s, uint32_t 
   return ex;
 }
 
+// append_hit (cfar_kernels.hpp) for an fp32 power, the CPI's level loaded behind the cap test
 __device__ __forceinline__ void cmap_hit(const CmapArgs &a, uint32_t c, int row, int col, float p)
 {
   const uint32_t slot = atomicAdd(&a.count[c], 1u);

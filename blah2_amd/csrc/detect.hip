@@ -22,76 +22,44 @@ struct blah2hip_cmap_s {
   uint32_t memory = 0, flags = 0;
   uint64_t age = 0;      // CPIs absorbed since the creation or the last reset
   float *d_bg = nullptr; // [cells]: b
-  struct Table { double pfa; double *d; bool pinned; };
-  std::vector<Table> tables; // alpha[0 .. 16 T] per pfa, least recently used first
+  TableCache<double> tables; // alpha[0 .. 16 T] per pfa
 };
 
 namespace {
 
-// The detectors' threshold tables on the device, one cache for both kinds.  Cell averaging (permille 0, h->alphaTables,
-// `rank` unused): blah2hip_cfar_alpha's alpha[0 .. maxN], keyed by (pfa, looks, size); a larger table serves a smaller
-// request.  Ordered statistic (h->osTables): blah2hip_oscfar_alpha's alpha[maxN + 1] doubles, then rank[maxN + 1] words, in
-// one allocation, keyed by (pfa, looks, rank, size); the size must match, because the rank words sit behind alpha[maxN].
-// The looks are the handle's BLAH2HIP_OPT_CFAR_LOOKS at the time of the call.  Each list keeps its least recently used
-// entry first and holds eight unpinned ones (a caller that adapts pfa per CPI does not grow device memory); a call never
-// touches the other list.  A hit only hands out the pointers; a miss allocates and uploads (blocking), which is refused
-// while `st` is being captured into a graph -- *_prepare is the call for that.  A table *_prepare has handed out lives as
-// long as the handle (`pin`): a graph captured afterwards has its address baked in, and no synchronisation at eviction
-// time protects a later replay.  Only unpinned tables are evicted.
-constexpr size_t CFAR_TABLES_MAX = 8;
-
+// The detectors' threshold tables on the device.  Four lists -- cell averaging, ordered statistic, greatest-of / smallest-of
+// on the ambiguity handle, the clutter map's on its own handle -- under the one policy of table_cache.hpp: a hit only hands
+// out the pointer; a miss builds, allocates and uploads (blocking), which is refused while `st` is being captured into a
+// graph -- *_prepare is the call for that, and what it hands out (`pin`) lives as long as the handle; eight unpinned tables
+// a list, and a call never touches another list.  What differs is below: the key, when an entry serves a request, the
+// builder and the two texts.
+//
+// Cell averaging (permille 0, h->alphaTables, `rank` unused): blah2hip_cfar_alpha's alpha[0 .. maxN], keyed by (pfa, looks,
+// size); a larger table serves a smaller request.  Ordered statistic (h->osTables): blah2hip_oscfar_alpha's alpha[maxN + 1]
+// doubles, then rank[maxN + 1] words, in one allocation, keyed by (pfa, looks, rank, size); the size must match, because
+// the rank words sit behind alpha[maxN].  The looks are the handle's BLAH2HIP_OPT_CFAR_LOOKS at the time of the call.
 int cfar_table(blah2hip_amb_s *h, double pfa, uint32_t permille, size_t maxN, const double **alpha, const uint32_t **rank,
                hipStream_t st = nullptr, bool pin = false)
 {
+  typedef blah2hip_amb_s::CfarKey Key;
   const bool os = permille != 0;
-  auto &T = os ? h->osTables : h->alphaTables;
-  const uint32_t looks = h->cfarLooks;
-  for (size_t i = 0; i < T.size(); i++)
-    if (T[i].pfa == pfa && T[i].looks == looks && T[i].rank == permille && (os ? T[i].n == maxN : T[i].n >= maxN)) {
-      blah2hip_amb_s::CfarTable t = T[i];
-      t.pinned = t.pinned || pin;
-      T.erase(T.begin() + (long)i);
-      T.push_back(t); // most recently used last
-      *alpha = t.d;
-      if (os) *rank = reinterpret_cast<const uint32_t *>(t.d + (maxN + 1));
-      return BLAH2HIP_OK;
-    }
-  if (st) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-      return fail(BLAH2HIP_ERR_INVALID,
-                  os ? "ordered-statistic table of this (pfa, rank, window) is not resident: call "
-                       "blah2hip_oscfar1d_prepare / blah2hip_oscfar2d_prepare before capturing the stream"
-                     : "threshold table of this (pfa, window) is not resident: call blah2hip_cfar1d_prepare / "
-                       "blah2hip_cfar2d_prepare before capturing the stream");
-  }
-  const size_t bytes = (maxN + 1) * (sizeof(double) + (os ? sizeof(uint32_t) : 0));
-  std::vector<double> host((bytes + sizeof(double) - 1) / sizeof(double));
-  int rc = os ? blah2hip_oscfar_alpha(pfa, looks, permille, (uint32_t)maxN, host.data(), reinterpret_cast<uint32_t *>(host.data() + (maxN + 1)))
-              : blah2hip_cfar_alpha(pfa, looks, (uint32_t)maxN, host.data());
-  if (rc) return rc;
-  size_t unpinned = 0;
-  for (const auto &e : T) unpinned += e.pinned ? 0 : 1;
-  if (unpinned >= CFAR_TABLES_MAX) {
-    HIPCHK(hipDeviceSynchronize()); // the oldest unpinned table may still be read by enqueued work
-    for (size_t i = 0; i < T.size(); i++)
-      if (!T[i].pinned) {
-        (void)hipFree(T[i].d);
-        T.erase(T.begin() + (long)i);
-        break;
-      }
-  }
-  blah2hip_amb_s::CfarTable t{pfa, looks, permille, maxN, nullptr, pin};
-  HIPCHK(hipMalloc(&t.d, host.size() * sizeof(double)));
-  hipError_t e = hipMemcpy(t.d, host.data(), bytes, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    (void)hipFree(t.d);
-    return fail(BLAH2HIP_ERR_HIP, std::string(os ? "ordered-statistic table upload: " : "alpha table upload: ") + hipGetErrorString(e));
-  }
-  T.push_back(t);
-  *alpha = t.d;
-  if (os) *rank = reinterpret_cast<const uint32_t *>(t.d + (maxN + 1));
-  return BLAH2HIP_OK;
+  const Key key{pfa, h->cfarLooks, permille, maxN};
+  HipTableDevice dev;
+  const int rc = (os ? h->osTables : h->alphaTables).get(
+      dev, key,
+      [&](const Key &e) { return e.pfa == pfa && e.looks == key.looks && e.rank == permille && (os ? e.n == maxN : e.n >= maxN); },
+      [&](std::vector<double> &host) {
+        host.resize(((maxN + 1) * (sizeof(double) + (os ? sizeof(uint32_t) : 0)) + sizeof(double) - 1) / sizeof(double));
+        return os ? blah2hip_oscfar_alpha(pfa, key.looks, permille, (uint32_t)maxN, host.data(), reinterpret_cast<uint32_t *>(host.data() + (maxN + 1)))
+                  : blah2hip_cfar_alpha(pfa, key.looks, (uint32_t)maxN, host.data());
+      },
+      os ? "ordered-statistic table of this (pfa, rank, window) is not resident: call "
+           "blah2hip_oscfar1d_prepare / blah2hip_oscfar2d_prepare before capturing the stream"
+         : "threshold table of this (pfa, window) is not resident: call blah2hip_cfar1d_prepare / "
+           "blah2hip_cfar2d_prepare before capturing the stream",
+      os ? "ordered-statistic table upload: " : "alpha table upload: ", st, pin, alpha);
+  if (rc == BLAH2HIP_OK && os) *rank = reinterpret_cast<const uint32_t *>(*alpha + (maxN + 1));
+  return rc;
 }
 
 // ---- the checks the entry points share, in the order each entry point makes them ----
@@ -357,52 +325,23 @@ int cfar1d_pin(bool os, blah2hip_amb_s *h, double pfa, uint32_t permille, int32_
   return cfar_table(h, pfa, permille, (size_t)(2 * n_train), &d, &r, nullptr, true);
 }
 
-// The clutter map's table of this pfa on the device: cfar_table's rules (a hit hands out the pointer, a miss builds and
-// uploads, blocking, and is refused while `st` is being captured; eight unpinned tables, what *_prepare made stays)
+// The clutter map's table of this pfa on the device, in the map's own list
 int cmap_table(blah2hip_cmap_s *cm, double pfa, const double **alpha, hipStream_t st = nullptr, bool pin = false)
 {
-  auto &T = cm->tables;
-  for (size_t i = 0; i < T.size(); i++)
-    if (T[i].pfa == pfa) {
-      blah2hip_cmap_s::Table t = T[i];
-      t.pinned = t.pinned || pin;
-      T.erase(T.begin() + (long)i);
-      T.push_back(t);
-      *alpha = t.d;
-      return BLAH2HIP_OK;
-    }
-  if (st) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-      return fail(BLAH2HIP_ERR_INVALID, "clutter-map table of this pfa is not resident: call blah2hip_cmap_prepare before capturing the stream");
-  }
-  const uint32_t last = CMAP_AGES * cm->memory;
-  std::vector<double> host(last + 1);
-  cmap_alpha_fill(pfa, cm->memory, last, host.data());
-  size_t unpinned = 0;
-  for (const auto &e : T) unpinned += e.pinned ? 0 : 1;
-  if (unpinned >= CFAR_TABLES_MAX) {
-    HIPCHK(hipDeviceSynchronize()); // the oldest unpinned table may still be read by enqueued work
-    for (size_t i = 0; i < T.size(); i++)
-      if (!T[i].pinned) {
-        (void)hipFree(T[i].d);
-        T.erase(T.begin() + (long)i);
-        break;
-      }
-  }
-  blah2hip_cmap_s::Table t{pfa, nullptr, pin};
-  HIPCHK(hipMalloc(&t.d, host.size() * sizeof(double)));
-  hipError_t e = hipMemcpy(t.d, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    (void)hipFree(t.d);
-    return fail(BLAH2HIP_ERR_HIP, std::string("clutter-map table upload: ") + hipGetErrorString(e));
-  }
-  T.push_back(t);
-  *alpha = t.d;
-  return BLAH2HIP_OK;
+  HipTableDevice dev;
+  return cm->tables.get(
+      dev, pfa, [&](double e) { return e == pfa; },
+      [&](std::vector<double> &host) {
+        const uint32_t last = CMAP_AGES * cm->memory;
+        host.resize(last + 1);
+        cmap_alpha_fill(pfa, cm->memory, last, host.data());
+        return BLAH2HIP_OK;
+      },
+      "clutter-map table of this pfa is not resident: call blah2hip_cmap_prepare before capturing the stream",
+      "clutter-map table upload: ", st, pin, alpha);
 }
 
-int cmap_check_pfa(double pfa)
+int check_pfa(double pfa)
 {
   if (!(pfa > 0.0 && pfa < 1.0)) return fail(BLAH2HIP_ERR_INVALID, "pfa outside (0, 1)");
   return BLAH2HIP_OK;
@@ -446,58 +385,29 @@ void gocfar_host_table(const blah2hip_amb_s *h, double pfa, uint32_t kind, int n
         tab[(size_t)(rows - 1) * W * W + c] = alpha[index.at(std::make_pair((uint32_t)(rows * (c / W)), (uint32_t)(rows * (c % W))))];
 }
 
-// ... on the device, in a cache of its own (h->goTables) keyed by (pfa, kind, nGuard, nTrain, hR) -- the map's geometry is the
-// handle's -- with cfar_table's rules: a hit hands out the pointer, a miss builds and uploads (blocking) and is refused while
-// `st` is being captured; eight unpinned tables, least recently used first out; what *_prepare made stays.
+// ... on the device, in h->goTables, keyed by (pfa, kind, nGuard, nTrain, hR) -- the map's geometry is the handle's
 int gocfar_table(blah2hip_amb_s *h, double pfa, uint32_t kind, int nG, int nT, int hR, const double **alpha,
                  hipStream_t st = nullptr, bool pin = false)
 {
-  auto &T = h->goTables;
-  for (size_t i = 0; i < T.size(); i++)
-    if (T[i].pfa == pfa && T[i].kind == kind && T[i].nG == nG && T[i].nT == nT && T[i].hR == hR) {
-      blah2hip_amb_s::GoTable t = T[i];
-      t.pinned = t.pinned || pin;
-      T.erase(T.begin() + (long)i);
-      T.push_back(t);
-      *alpha = t.d;
-      return BLAH2HIP_OK;
-    }
-  if (st) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-      return fail(BLAH2HIP_ERR_INVALID, "greatest-of / smallest-of table of this (pfa, kind, window) is not resident: call "
-                                        "blah2hip_gocfar1d_prepare / blah2hip_gocfar2d_prepare before capturing the stream");
-  }
-  std::vector<double> host;
-  gocfar_host_table(h, pfa, kind, nG, nT, hR, host);
-  size_t unpinned = 0;
-  for (const auto &e : T) unpinned += e.pinned ? 0 : 1;
-  if (unpinned >= CFAR_TABLES_MAX) {
-    HIPCHK(hipDeviceSynchronize()); // the oldest unpinned table may still be read by enqueued work
-    for (size_t i = 0; i < T.size(); i++)
-      if (!T[i].pinned) {
-        (void)hipFree(T[i].d);
-        T.erase(T.begin() + (long)i);
-        break;
-      }
-  }
-  blah2hip_amb_s::GoTable t{pfa, kind, nG, nT, hR, nullptr, pin};
-  HIPCHK(hipMalloc(&t.d, host.size() * sizeof(double)));
-  hipError_t e = hipMemcpy(t.d, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    (void)hipFree(t.d);
-    return fail(BLAH2HIP_ERR_HIP, std::string("greatest-of / smallest-of table upload: ") + hipGetErrorString(e));
-  }
-  T.push_back(t);
-  *alpha = t.d;
-  return BLAH2HIP_OK;
+  typedef blah2hip_amb_s::GoKey Key;
+  HipTableDevice dev;
+  return h->goTables.get(
+      dev, Key{pfa, kind, nG, nT, hR},
+      [&](const Key &e) { return e.pfa == pfa && e.kind == kind && e.nG == nG && e.nT == nT && e.hR == hR; },
+      [&](std::vector<double> &host) {
+        gocfar_host_table(h, pfa, kind, nG, nT, hR, host);
+        return BLAH2HIP_OK;
+      },
+      "greatest-of / smallest-of table of this (pfa, kind, window) is not resident: call "
+      "blah2hip_gocfar1d_prepare / blah2hip_gocfar2d_prepare before capturing the stream",
+      "greatest-of / smallest-of table upload: ", st, pin, alpha);
 }
 
 // what the greatest-of / smallest-of calls check after the window's sizes: the kind, pfa, the handle's looks
 int gocfar_check(const blah2hip_amb_s *h, double pfa, uint32_t kind)
 {
   if (kind != BLAH2HIP_CFAR_GO && kind != BLAH2HIP_CFAR_SO) return fail(BLAH2HIP_ERR_INVALID, "kind: BLAH2HIP_CFAR_GO or BLAH2HIP_CFAR_SO");
-  if (int rc = cmap_check_pfa(pfa)) return rc;
+  if (int rc = check_pfa(pfa)) return rc;
   if (h->cfarLooks > 1)
     return fail(BLAH2HIP_ERR_UNSUPPORTED, "greatest-of / smallest-of: the thresholds are made for one look per cell (BLAH2HIP_OPT_CFAR_LOOKS is above 1)");
   return BLAH2HIP_OK;
@@ -521,7 +431,7 @@ int blah2hip_cmap_alpha(double pfa, uint32_t memory, uint32_t max_age, double *a
 {
   if (!alpha) return fail(BLAH2HIP_ERR_INVALID, "NULL table");
   if (memory == 0 || memory > BLAH2HIP_MAX_CMAP_MEMORY) return fail(BLAH2HIP_ERR_INVALID, "memory outside [1, BLAH2HIP_MAX_CMAP_MEMORY]");
-  if (int rc = cmap_check_pfa(pfa)) return rc;
+  if (int rc = check_pfa(pfa)) return rc;
   cmap_alpha_fill(pfa, memory, max_age, alpha);
   return BLAH2HIP_OK;
 }
@@ -556,8 +466,8 @@ int blah2hip_cmap_destroy(blah2hip_cmap_t cm)
   (void)hipSetDevice(cm->amb->device);
   (void)hipDeviceSynchronize(); // enqueued calls may still use the plane and the tables
   if (hipFree(cm->d_bg) != hipSuccess) rc = fail(BLAH2HIP_ERR_HIP, "hipFree(clutter map)");
-  for (auto &t : cm->tables)
-    if (hipFree(t.d) != hipSuccess) rc = fail(BLAH2HIP_ERR_HIP, "hipFree(clutter-map table)");
+  HipTableDevice dev;
+  if (!cm->tables.free_all(dev)) rc = fail(BLAH2HIP_ERR_HIP, "hipFree(clutter-map table)");
   delete cm;
   return rc;
 }
@@ -579,7 +489,7 @@ int blah2hip_cmap_age(blah2hip_cmap_t cm, uint64_t *age)
 int blah2hip_cmap_prepare(blah2hip_cmap_t cm, double pfa)
 {
   if (!cm) return fail(BLAH2HIP_ERR_INVALID, "NULL handle");
-  if (int rc = cmap_check_pfa(pfa)) return rc;
+  if (int rc = check_pfa(pfa)) return rc;
   HIPCHK(hipSetDevice(cm->amb->device));
   const double *d = nullptr;
   return cmap_table(cm, pfa, &d, nullptr, true);
@@ -593,7 +503,7 @@ int blah2hip_cmap_process_dev(blah2hip_cmap_t cm, const void *d_map, const doubl
   blah2hip_amb_s *h = cm->amb;
   if (n_cpi == 0 || n_cpi > h->dims.max_batch) return fail(BLAH2HIP_ERR_INVALID, "n_cpi outside [1, max_batch]");
   int rc;
-  if ((rc = cmap_check_pfa(pfa))) return rc;
+  if ((rc = check_pfa(pfa))) return rc;
   if ((d_hits == nullptr) != (d_count == nullptr)) return fail(BLAH2HIP_ERR_INVALID, "d_hits and d_count: both or neither");
   if (d_hits && cap == 0) return fail(BLAH2HIP_ERR_INVALID, "cap is 0");
   const cf *map = d_map ? (const cf *)d_map : h->d_map;
@@ -859,8 +769,8 @@ int blah2hip_oscfar_alpha(double pfa, uint32_t looks, uint32_t rank_permille, ui
 {
   if (!alpha) return fail(BLAH2HIP_ERR_INVALID, "NULL table");
   if (looks == 0 || looks > BLAH2HIP_MAX_CFAR_LOOKS) return fail(BLAH2HIP_ERR_INVALID, "looks outside [1, BLAH2HIP_MAX_CFAR_LOOKS]");
-  if (rank_permille < 1 || rank_permille > 1000) return fail(BLAH2HIP_ERR_INVALID, "rank_permille outside [1, 1000]");
-  if (!(pfa > 0.0 && pfa < 1.0)) return fail(BLAH2HIP_ERR_INVALID, "pfa outside (0, 1)");
+  if (int rc = os_check_rank(rank_permille)) return rc;
+  if (int rc = check_pfa(pfa)) return rc;
   oscfar_alpha_fill(pfa, looks, rank_permille, max_n, alpha, rank);
   return BLAH2HIP_OK;
 }
@@ -950,7 +860,7 @@ int blah2hip_gocfar_alpha(double pfa, uint32_t kind, uint32_t n_pairs, const uin
 {
   if (!a || !b || !alpha) return fail(BLAH2HIP_ERR_INVALID, "NULL argument");
   if (kind != BLAH2HIP_CFAR_GO && kind != BLAH2HIP_CFAR_SO) return fail(BLAH2HIP_ERR_INVALID, "kind: BLAH2HIP_CFAR_GO or BLAH2HIP_CFAR_SO");
-  if (int rc = cmap_check_pfa(pfa)) return rc;
+  if (int rc = check_pfa(pfa)) return rc;
   goso_alpha_fill(pfa, kind, n_pairs, a, b, alpha);
   return BLAH2HIP_OK;
 }

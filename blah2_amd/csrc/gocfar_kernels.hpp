@@ -39,54 +39,19 @@ struct GoCfarArgs {
   uint32_t kind;
 };
 
-// One workgroup per Doppler row like cfar1d_kernel; leading cells need k > 0, trailing k >= 0 (CfarDetector1D.cpp:61, :68),
-// rows with |doppler| < minDoppler and cells with delay < minDelay are not tested (:40, :53).  STAGED: the row's |z|^2 in
-// LDS as fp64 (lanes read neighbouring doubles: no bank conflict); false: rows longer than the LDS holds, |z|^2 from the
-// L2-resident row.  cfar1d_kernel's loads and adds, in two sums, plus a second divide, multiply and compare.
+// row_detect's geometry (cfar_kernels.hpp): cfar1d_kernel's loads and adds, in two sums, plus a second divide, multiply and
+// compare
 template <bool STAGED>
 __global__ __launch_bounds__(256) void gocfar1d_kernel(GoCfarArgs ga)
 {
-  const CfarArgs &a = ga.c;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  double *sq = reinterpret_cast<double *>(smem);
-  const int row = blockIdx.x, cpi = blockIdx.y;
-  if (fabs(a.doppler[row]) < a.minDoppler) return;
-  const cf *z = a.map + ((size_t)cpi * a.nD + row) * a.nDelay;
-  auto sqv = [&](int k) -> double {
-    if (STAGED) return sq[k];
-    const cf c = z[k];
-    return (double)c.x * (double)c.x + (double)c.y * (double)c.y;
-  };
-  if (STAGED) {
-    for (int j = threadIdx.x; j < a.nDelay; j += blockDim.x) {
-      const cf c = z[j];
-      sq[j] = (double)c.x * (double)c.x + (double)c.y * (double)c.y;
-    }
-    __syncthreads();
-  }
-  const double noisePower = a.metrics[2 * cpi];
-  for (int j = threadIdx.x; j < a.nDelay; j += blockDim.x) {
-    if ((a.delayAxis ? a.delayAxis[j] : j + a.delayMin) < a.minDelay) continue;
-    // the two halves, clipped to the row: [l0, l1) before the guard (never column 0), [t0, t1) behind it
-    const int l0 = max(j - a.nGuard - a.nTrain, 1), l1 = min(j - a.nGuard, a.nDelay);
-    const int t0 = min(j + a.nGuard + 1, a.nDelay), t1 = min(j + a.nGuard + a.nTrain + 1, a.nDelay);
+  row_detect<STAGED>(ga.c, [&](int l0, int l1, int t0, int t1, auto sqv, int j) {
     const int na = max(l1 - l0, 0), nb = t1 - t0;
-    if (na + nb == 0) continue;
+    if (na + nb == 0) return false;
     double SA = 0.0, SB = 0.0;
     for (int k = l0; k < l1; k++) SA += sqv(k);
     for (int k = t0; k < t1; k++) SB += sqv(k);
-    const double al = a.alpha[na * (a.nTrain + 1) + nb], sj = sqv(j);
-    if (gocfar_decide(sj, al, SA, SB, na, nb, ga.kind)) {
-      const uint32_t slot = atomicAdd(&a.count[cpi], 1u);
-      if (slot < a.cap) {
-        blah2hip_hit_t h;
-        h.row = row;
-        h.col = j;
-        h.snr = 5.0 * log10(sj) - noisePower;
-        a.hits[(size_t)cpi * a.cap + slot] = h;
-      }
-    }
-  }
+    return gocfar_decide(sqv(j), ga.c.alpha[na * (ga.c.nTrain + 1) + nb], SA, SB, na, nb, ga.kind);
+  });
 }
 
 // --------------------------------------------------------------------------
@@ -105,9 +70,8 @@ __global__ __launch_bounds__(256) void gocfar1d_kernel(GoCfarArgs ga)
 // (column 0 is 0.0 in LDS).  Per tile (2 hR + 1) 16 (64 + 2 hC) + 2 nTd 16 64 LDS reads: 23 808 for the 17 x 9 window's extent
 // (hR 4, nGd 2, nTd 6), where oscfar2d_kernel reads each of a cell's 138 training cells: 141 312.
 // LDS: (16 + 2 hR + 16)(64 + 2 hC | 1) doubles: 25.3 KB for hR 4, hC 8; 90.6 KB at the halo limits (hR 24, hC 40).
-constexpr int G2_ROWS = 16, G2_COLS = 64, G2_M = 4;
-__host__ __device__ inline int g2_pitch(int hC) { return (G2_COLS + 2 * hC) | 1; }
-__host__ inline size_t g2_lds_bytes(int hC, int hR) { return (size_t)(2 * G2_ROWS + 2 * hR) * g2_pitch(hC) * sizeof(double); }
+constexpr int G2_ROWS = 16, G2_COLS = HALO_COLS, G2_M = 4;
+__host__ inline size_t g2_lds_bytes(int hC, int hR) { return (size_t)(2 * G2_ROWS + 2 * hR) * halo_pitch(hC) * sizeof(double); }
 
 struct GoCfar2dArgs {
   Cfar2dArgs d; // ngD, ntD: the halves; ntF: hR (ngF 0); alpha: the table above, (2 hR + 1)(nTd + 1)^2 doubles; sat unused
@@ -119,7 +83,7 @@ __global__ __launch_bounds__(256) void gocfar2d_kernel(GoCfar2dArgs ga)
   const Cfar2dArgs &a = ga.d;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int hR = a.ntF, g = a.ngD, t = a.ntD, hC = g + t;
-  const int SP = g2_pitch(hC), SC = G2_COLS + 2 * hC, SR = G2_ROWS + 2 * hR;
+  const int SP = halo_pitch(hC), SC = G2_COLS + 2 * hC, SR = G2_ROWS + 2 * hR;
   double *P = reinterpret_cast<double *>(smem), *Cs = P + SR * SP;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -127,19 +91,7 @@ __global__ __launch_bounds__(256) void gocfar2d_kernel(GoCfar2dArgs ga)
   const int j0 = blockIdx.x * G2_COLS, i0 = blockIdx.y * G2_ROWS, cpi = blockIdx.z;
   const cf *map = a.map + (size_t)cpi * nD * nC;
 
-  for (int r = wave; r < SR; r += 4) {
-    const int i = i0 - hR + r;
-    const bool rok = i >= 0 && i < nD;
-    for (int c = lane; c < SC; c += 64) {
-      const int j = j0 - hC + c;
-      double v = 0.0;
-      if (rok && j >= 1 && j < nC) {
-        const cf q = map[(size_t)i * nC + j];
-        v = (double)q.x * (double)q.x + (double)q.y * (double)q.y;
-      }
-      P[r * SP + c] = v;
-    }
-  }
+  halo_fill(P, map, nD, nC, i0, j0, G2_ROWS, hR, hC, 0.0, wave, lane);
   __syncthreads();
 
   // the column sums of this wave's four rows of cells: the cells' row o + m spans the tile rows o + m .. o + m + 2 hR
@@ -177,19 +129,9 @@ __global__ __launch_bounds__(256) void gocfar2d_kernel(GoCfar2dArgs ga)
     for (int c = 0; c < t; c++) SA += row[c];
 #pragma unroll 4
     for (int c = 0; c < t; c++) SB += row[hC + g + 1 + c];
-    const cf q = map[(size_t)i * nC + j];
-    const double p = (double)q.x * (double)q.x + (double)q.y * (double)q.y;
+    const double p = cell_power(map[(size_t)i * nC + j]);
     const double al = a.alpha[((rows - 1) * (t + 1) + cL) * (t + 1) + cR];
-    if (gocfar_decide(p, al, SA, SB, rows * cL, rows * cR, ga.kind)) {
-      const uint32_t slot = atomicAdd(&a.count[cpi], 1u);
-      if (slot < a.cap) {
-        blah2hip_hit_t h;
-        h.row = i;
-        h.col = j;
-        h.snr = 5.0 * log10(p) - noise;
-        a.hits[(size_t)cpi * a.cap + slot] = h;
-      }
-    }
+    if (gocfar_decide(p, al, SA, SB, rows * cL, rows * cR, ga.kind)) append_hit(a.hits, a.count, a.cap, cpi, i, j, p, noise);
   }
 }
 

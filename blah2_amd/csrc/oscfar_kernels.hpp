@@ -28,55 +28,20 @@ struct OsCfarArgs {
   const uint32_t *rank; // [2*nTrain+1]: k(n)
 };
 
-// One workgroup per Doppler row like cfar1d_kernel; leading cells need k > 0, trailing k >= 0 (CfarDetector1D.cpp:61,
-// :68), rows with |doppler| < minDoppler and cells with delay < minDelay are not tested (:40, :53).  STAGED: the row's
-// |z|^2 in LDS as fp64 (lanes read neighbouring doubles: no bank conflict); false: rows longer than the LDS holds,
-// |z|^2 from the L2-resident row.
+// row_detect's geometry (cfar_kernels.hpp), and a count of n multiply-compares over the two runs
 template <bool STAGED>
 __global__ __launch_bounds__(256) void oscfar1d_kernel(OsCfarArgs oa)
 {
-  const CfarArgs &a = oa.c;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  double *sq = reinterpret_cast<double *>(smem);
-  const int row = blockIdx.x, cpi = blockIdx.y;
-  if (fabs(a.doppler[row]) < a.minDoppler) return;
-  const cf *z = a.map + ((size_t)cpi * a.nD + row) * a.nDelay;
-  auto sqv = [&](int k) -> double {
-    if (STAGED) return sq[k];
-    const cf c = z[k];
-    return (double)c.x * (double)c.x + (double)c.y * (double)c.y;
-  };
-  if (STAGED) {
-    for (int j = threadIdx.x; j < a.nDelay; j += blockDim.x) {
-      const cf c = z[j];
-      sq[j] = (double)c.x * (double)c.x + (double)c.y * (double)c.y;
-    }
-    __syncthreads();
-  }
-  const double noisePower = a.metrics[2 * cpi];
-  for (int j = threadIdx.x; j < a.nDelay; j += blockDim.x) {
-    if ((a.delayAxis ? a.delayAxis[j] : j + a.delayMin) < a.minDelay) continue;
-    // the two runs of training cells, clipped to the row: [l0, l1) before the guard (never column 0), [t0, t1) behind it
-    const int l0 = max(j - a.nGuard - a.nTrain, 1), l1 = min(j - a.nGuard, a.nDelay);
-    const int t0 = max(j + a.nGuard + 1, 0), t1 = min(j + a.nGuard + a.nTrain + 1, a.nDelay);
-    const int n = max(l1 - l0, 0) + max(t1 - t0, 0);
-    if (n == 0) continue;
-    const double al = a.alpha[n], sj = sqv(j);
+  row_detect<STAGED>(oa.c, [&](int l0, int l1, int t0, int t1, auto sqv, int j) {
+    const int n = max(l1 - l0, 0) + (t1 - t0);
+    if (n == 0) return false;
+    const double al = oa.c.alpha[n], sj = sqv(j);
     const uint32_t need = oa.rank[n];
     uint32_t below = 0;
     for (int k = l0; k < l1; k++) below += (al * sqv(k) < sj) ? 1u : 0u;
     for (int k = t0; k < t1; k++) below += (al * sqv(k) < sj) ? 1u : 0u;
-    if (below >= need) {
-      const uint32_t slot = atomicAdd(&a.count[cpi], 1u);
-      if (slot < a.cap) {
-        blah2hip_hit_t h;
-        h.row = row;
-        h.col = j;
-        h.snr = 5.0 * log10(sj) - noisePower;
-        a.hits[(size_t)cpi * a.cap + slot] = h;
-      }
-    }
-  }
+    return below >= need;
+  });
 }
 
 // --------------------------------------------------------------------------
@@ -92,9 +57,8 @@ __global__ __launch_bounds__(256) void oscfar1d_kernel(OsCfarArgs oa)
 // 2048, against 1.6 x for this one -- the branches, not the LDS reads, were the cost)  The cell under test is read from
 // the map itself (column 0 is +Inf in LDS), the same arithmetic.
 // LDS: (16 + 2 hR)(64 + 2 hC | 1) doubles: 15.6 KB for the 17 x 9 window, 74 KB at the halo limits (hR 24, hC 40).
-constexpr int O2_ROWS = 16, O2_COLS = 64, O2_M = 4;
-__host__ __device__ inline int o2_pitch(int hC) { return (O2_COLS + 2 * hC) | 1; }
-__host__ inline size_t o2_lds_bytes(int hC, int hR) { return (size_t)(O2_ROWS + 2 * hR) * o2_pitch(hC) * sizeof(double); }
+constexpr int O2_ROWS = 16, O2_COLS = HALO_COLS, O2_M = 4;
+__host__ inline size_t o2_lds_bytes(int hC, int hR) { return (size_t)(O2_ROWS + 2 * hR) * halo_pitch(hC) * sizeof(double); }
 
 struct OsCfar2dArgs {
   Cfar2dArgs d;         // alpha: the ordered-statistic factors; sat unused
@@ -107,27 +71,13 @@ __global__ __launch_bounds__(256) void oscfar2d_kernel(OsCfar2dArgs oa)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   double *T = reinterpret_cast<double *>(smem);
   const int hR = a.ngF + a.ntF, hC = a.ngD + a.ntD;
-  const int SP = o2_pitch(hC), SC = O2_COLS + 2 * hC, SR = O2_ROWS + 2 * hR;
+  const int SP = halo_pitch(hC);
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int nD = a.nD, nC = a.nDelay;
   const int j0 = blockIdx.x * O2_COLS, i0 = blockIdx.y * O2_ROWS, cpi = blockIdx.z;
   const cf *map = a.map + (size_t)cpi * nD * nC;
-  const double inf = __builtin_huge_val();
-
-  for (int r = wave; r < SR; r += 4) {
-    const int i = i0 - hR + r;
-    const bool rok = i >= 0 && i < nD;
-    for (int c = lane; c < SC; c += 64) {
-      const int j = j0 - hC + c;
-      double v = inf;
-      if (rok && j >= 1 && j < nC) {
-        const cf q = map[(size_t)i * nC + j];
-        v = (double)q.x * (double)q.x + (double)q.y * (double)q.y;
-      }
-      T[r * SP + c] = v;
-    }
-  }
+  halo_fill(T, map, nD, nC, i0, j0, O2_ROWS, hR, hC, __builtin_huge_val(), wave, lane);
   __syncthreads();
 
   // this lane's four cells: rows i0 + 4 wave + m of column j0 + lane
@@ -150,8 +100,7 @@ __global__ __launch_bounds__(256) void oscfar2d_kernel(OsCfar2dArgs oa)
       const int n = (clampi(i + hR + 1, 0, nD) - clampi(i - hR, 0, nD)) * nColsAll -
                     (clampi(i + a.ngF + 1, 0, nD) - clampi(i - a.ngF, 0, nD)) * nColsGuard;
       if (n > 0) {
-        const cf q = map[(size_t)i * nC + j];
-        p[m] = (double)q.x * (double)q.x + (double)q.y * (double)q.y;
+        p[m] = cell_power(map[(size_t)i * nC + j]);
         al[m] = a.alpha[n];
         need[m] = oa.rank[n];
         any = true;
@@ -186,15 +135,7 @@ __global__ __launch_bounds__(256) void oscfar2d_kernel(OsCfar2dArgs oa)
   const double noise = a.metrics[2 * cpi];
 #pragma unroll
   for (int m = 0; m < O2_M; m++) {
-    if (below[m] < need[m]) continue;
-    const uint32_t slot = atomicAdd(&a.count[cpi], 1u);
-    if (slot < a.cap) {
-      blah2hip_hit_t h;
-      h.row = i0 + o + m;
-      h.col = j;
-      h.snr = 5.0 * log10(p[m]) - noise;
-      a.hits[(size_t)cpi * a.cap + slot] = h;
-    }
+    if (below[m] >= need[m]) append_hit(a.hits, a.count, a.cap, cpi, i0 + o + m, j, p[m], noise);
   }
 }
 

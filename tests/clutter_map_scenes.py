@@ -87,13 +87,14 @@ def b_bound(age, memory, umax):
     return (min(int(age), int(memory)) + 4) * EPS * np.asarray(umax)
 
 
-def margin_cells(detail, alpha, memory, age0=0):
+def margin_cells(detail, alpha, memory, age0=0, umax0=None):
     """bool [n_cpi, ...]: the cells whose decision the bound does not settle (they may go either way on the device).  ``detail``:
-    clutter_map's third value for a call that started at age ``age0``; ``alpha``: its table."""
+    clutter_map's third value for a call that started at age ``age0``; ``alpha``: its table; ``umax0``: the largest ``u`` each
+    cell had absorbed before the call (clutter_map's ``state["umax"]``; None: nothing, as at age 0)."""
     u, thr = detail["u"], detail["thr"]
     out = np.zeros(u.shape, dtype=bool)
     T = int(memory)
-    umax = np.zeros(u.shape[1:])
+    umax = np.zeros(u.shape[1:]) if umax0 is None else np.array(umax0, dtype=np.float64)
     for c in range(u.shape[0]):
         age = age0 + c
         fin = np.isfinite(u[c])

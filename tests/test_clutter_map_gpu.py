@@ -177,6 +177,46 @@ def test_cuts_into_calls_change_no_bit(b2, torch):
             det.close()
 
 
+def test_table_cache_keeps_eight(b2, torch):
+    """21 x 111, T = 3, one detector: thirteen pfa values and then the first again, one CPI per call, so the ninth to the
+    thirteenth table evict the first five and the last call builds the first one anew.  Every call's plane and list against
+    the restatement carried over the same sequence with the same tables, under the bounds of test_against_the_restatement.
+    The comparison is about something: N times the pfa values of the calls from age 1 on is 532 expected hits, at least half
+    are asked; and a stale table would show: with the table of the call before, N (pfa[0] - pfa[12]) = 233 decisions are
+    expected to change over the twelve falling steps and as many at the last call, at least 100 are asked."""
+    case = S.Case("cache", 21, 111, 14, 3, None, True, 41)
+    amb = handle(b2, case.nD, case.nC)
+    maps = S.case_maps(case)
+    mets = S.metrics(maps)
+    pfas = [10.0 ** -(1.0 + 0.25 * k) for k in range(13)]
+    det = detector(b2, amb, case.T, pfas[0])
+    state, in_margin, tested, hits, stale, before = {}, 0, 0, 0, 0, None
+    try:
+        for c, pfa in enumerate(pfas + pfas[:1]):
+            det.pfa = pfa
+            got = run(b2, torch, det, maps[c:c + 1], mets[c:c + 1])
+            assert det.age() == c + 1
+            alpha = b2.clutter_map_alpha_table(pfa, case.T, 16 * case.T)
+            umax0 = state.get("umax")
+            exceed, _, detail = b2.clutter_map(maps[c:c + 1], got["level"].astype(np.float64), alpha, case.T, state, detail=True)
+            margin = S.margin_cells(detail, alpha, case.T, age0=c, umax0=umax0)
+            assert not ((got["exceed"] != exceed) & ~margin).any(), (c, pfa)
+            want = sorted(zip(*[v.tolist() for v in np.nonzero(got["exceed"][0])]))
+            assert got["count"][0] == len(want) and hit_cells(got["hits"][0]) == want, (c, pfa)
+            if c >= 1:
+                in_margin += int(margin.sum())
+                tested += exceed.size
+                hits += int(exceed.sum())
+                idx = min(c, 16 * case.T)
+                stale += int(np.count_nonzero((detail["u"] > before[idx] * (detail["thr"] / alpha[idx])) != (exceed != 0)))
+            before = alpha
+    finally:
+        det.close()
+    print(f"cache: {hits} hits, {in_margin} of {tested} decisions inside the margin; {stale} would change under the table of the call before")
+    assert in_margin <= 1e-4 * tested
+    assert hits >= 266 and stale >= 100
+
+
 def test_map_pointer_8_bytes_off_and_reset(b2, torch):
     case = S.CASES[0]
     amb = handle(b2, case.nD, case.nC)
